@@ -6,8 +6,14 @@ re-rank) over one query batch, inputs and index resident in HBM, through the C A
 (gbnns_search_ex with device buffers).  The index is replicated per GPU; ranks search disjoint
 query blocks and all-gather the answer ids over RCCL each step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--ef EF]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--ef EF] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs: set-up, warm-up, the K timed steps, the result line.  Everything else
+it can measure or check (recall sweep, cold start, serialised steps with per-kernel times and the roofline, the ef sweep,
+the diagnostic sections, the CPU baseline against the compiled reference, the other configurations, the N > 1 self-checks
+and the C-ABI multi-replica section) runs under --full.  --dump-outputs DIR writes what the last timed step handed its
+caller to DIR/<name>.npy (float64): the inputs are seeded, so two builds can be compared output for output.
 
 --config picks one of BASELINE.json's shapes (default `sift` = configs[1], the one `metric` is
 quoted on; the others are the survey's configurations 3-5 as bench lines of their own):
@@ -156,7 +162,14 @@ def main():
     ap.add_argument("--no-other-configs", action="store_true",
                     help="default sift run at N = 1: do not append the gist / glove / glove-dot (/ deep) lines under other_configs")
     ap.add_argument("--budget-s", type=float, default=float(os.environ.get("GBNNS_BENCH_BUDGET_S", "400")),
-                    help="wall-clock budget of the whole default run; the other configurations are started only while it lasts")
+                    help="wall-clock budget of the whole --full run; the other configurations are started only while it lasts")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: recall sweep, cold start, serialised steps with per-kernel times and "
+                         "roofline, ef sweep, diagnostic sections, CPU baseline, the other configurations, N > 1 self-checks and the "
+                         "C-ABI multi-replica section (a plain run sets up, warms up, times the steps and prints the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller (ids, hops, dist_calc, edges) "
+                         "as DIR/<name>.npy in float64")
     argv = sys.argv[1:]
     if not argv and os.environ.get("GBNNS_BENCH_ARGV") and "WORLD_SIZE" in os.environ:
         argv = json.loads(os.environ["GBNNS_BENCH_ARGV"])  # a worker started by the branch below
@@ -267,7 +280,7 @@ def main():
     # calm; the first call also pays the runtime's lazy loading of the code objects and the lanes'
     # workspace allocations.  What a caller sees before any of that has settled:
     cold = None
-    if world == 1 and nq_rank <= 20_000:
+    if args.full and world == 1 and nq_rank <= 20_000:
         times = []
         for j in range(12):
             torch.cuda.synchronize()
@@ -286,10 +299,19 @@ def main():
     # ---- recall sweep (untimed) ------------------------------------------------------------
     ef = args.ef or cfg["ef"]
     sweep = {}
-    for e in sorted(set(([16, 32, 64, 128] if args.config == "sift" else []) + [ef] + cfg["efs"])):
-        r = ix.search(q, e, want=())
-        torch.cuda.synchronize()
-        sweep[e] = recall_of(r["ids"])
+    sweep_efs = sorted(set(([16, 32, 64, 128] if args.config == "sift" else []) + [ef] + cfg["efs"]))
+
+    def score(efs):
+        for e in efs:
+            if e not in sweep:
+                r = ix.search(q, e, want=())
+                torch.cuda.synchronize()
+                sweep[e] = recall_of(r["ids"])
+    # a plain run scores the timed beam alone; the whole sweep is scored under --full, or where the beam misses the gate (the
+    # bisection below then starts from the same points as under --full and picks the same beam)
+    score(sweep_efs if args.full else [ef])
+    if sweep[ef] < 0.95:
+        score(sweep_efs)
     gate_failed = False
     if sweep[ef] < 0.95:
         for e in [e for e in REF_EFS + [200, 256, 300, 400, 512, 600, 800, 1000] if e > ef]:
@@ -429,6 +451,15 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+    ms_per_step = elapsed * 1e3 / args.steps
+    qps = nq_total * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        b = (args.steps - 1) % nbuf   # the last timed step's buffers: nothing has written to them since
+        last = {k: outs[b][k] for k in ("ids",) + want}
+        if world > 1:
+            last["ids_all_ranks"] = gathered[b]
+        dump_outputs(args.dump_outputs, last)
+    if world > 1 and args.full:
         # per rank (diagnostic, after the timed region): its own ms per step, how long it then waited at the closing barrier, and the
         # exchange step alone -- one all-gather of the id vectors, timed by itself
         tg0 = time.perf_counter()
@@ -445,12 +476,10 @@ def main():
         per_rank = {"ms_per_step": [round(v[0], 4) for v in allr], "barrier_wait_ms": [round(v[1], 3) for v in allr],
                     "gather_alone_ms": [round(v[2], 4) for v in allr], "queries": [int(v[3]) for v in allr]}
 
-    ms_per_step = elapsed * 1e3 / args.steps
-    qps = nq_total * args.steps / elapsed
     # every rank's own piece of the last gathered id vectors equals what it searched itself (the buffers of the last
     # `nbuf` steps are all still in place): a wrong join / gather order in the pipelined loop would show here
     gather_ok = None
-    if world > 1:
+    if world > 1 and args.full:
         good = True
         for b in range(nbuf):
             if gathered[b] is not None and "ids" in outs[b]:
@@ -459,35 +488,7 @@ def main():
         dist.all_reduce(tg, op=dist.ReduceOp.MIN)
         gather_ok = bool(tg.item() == 1.0)
 
-    # ---- the same K steps serialised (GBNNS_FLAG_SERIAL semantics: profiling implies it): one batch at a time on one
-    # stream, kernels back to back, with the library's hipEvent pairs around every stage on the launch stream.  This is
-    # where roofline.kernel_ms comes from -- overlapped kernels cannot be timed individually.
-    ix.profile_read(reset=True)
-    ix.profile_enable(True)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for i in range(args.steps):
-        ix.search(batches[i % nb], ef, want=want, out=outs[i % nbuf], hash_capacity=args.hash_capacity, flags=tune_flags)
-    torch.cuda.synchronize()
-    elapsed_serial = time.perf_counter() - t1
-    prof = ix.profile_read(reset=True)
-    ix.profile_enable(False)
-    # walk statistics of every rotated batch (algorithmic bytes are averaged over them)
-    stats = {k: [] for k in want}
-    for j in range(nb):
-        r = ix.search(batches[j], ef, want=want, flags=tune_flags | g.FLAG_SERIAL)
-        for k in want:
-            stats[k].append(r[k].clone())
-    res = {k: torch.cat(v) for k, v in stats.items()}
-    res["ids"] = ix.search(q, ef, want=(), flags=tune_flags | g.FLAG_SERIAL)["ids"].clone()
-    torch.cuda.synchronize()
-
-    # ---- algorithmic bytes of the dominant kernel (the beam walk), SURVEY.md section 8d ------
     max_degree = int(np.diff(np.asarray(ds.graph_off).astype(np.int64)).max())
-    rl = roofline_of(ds, res, prof, ef, nq_rank, max_degree, cfg, rank, launches=nb)
-    hops = res["hops"].double()
-    dc = res["dist_calc"].double()
-
     result = {
         "metric": "queries/sec @ recall@1>=0.95, %s" % cfg["label"].split(" (")[0].replace(", 1M-query batch", ""),
         "value": round(qps, 1),
@@ -514,8 +515,6 @@ def main():
             "recall_at_1": round(recall, 4),
             "recall_scored_queries": int(n_scored),
             "recall_sweep": {str(k): round(v, 4) for k, v in sorted(sweep.items())},
-            "mean_hops": round(hops.mean().item(), 1),
-            "mean_dist_calc": round(dc.mean().item(), 1),
             "graph": "kNN(%d)->GD(M=%d,reverse), avg degree %.1f, max %d" % (
                 ds.recipe["knn_k"], ds.recipe["M"], len(ds.graph_nbr) / ds.n, max_degree),
             "parallelism": "query-sharded replicas x%d" % world,
@@ -523,36 +522,67 @@ def main():
         },
         "config_nq": nq_rank,
         "ranks_seen": dist.get_world_size() if world > 1 else 1,
-        "gather_self_check": gather_ok,
-        "per_rank": per_rank,
         "strong_batch": nq_total if strong else None,
-        "roofline": rl["roofline"],
-        "kernels_ms": rl["kernels_ms"],
         "batches_rotated": nb,
         "pipelined": bool(pipelined),
         "batches_in_flight": depth,
-        # the same K steps one batch at a time on one stream, kernels back to back (what round 1 / 2 reported as `value`)
-        "serial": {"ms_per_step": round(elapsed_serial * 1e3 / args.steps, 4),
-                   "queries_per_s": round(nq_rank * args.steps / elapsed_serial, 1),
-                   "note": "per rank, GBNNS_FLAG_SERIAL semantics, hipEvent profiling on: roofline.kernel_ms is measured here"},
         # what `value` leaves out, per SURVEY 8d's definition (one gbnns_search_batch incl. H2D / D2H): see
-        # survey_8d_value below (filled at N = 1 unless --no-extras)
+        # survey_8d_value below (filled at N = 1 under --full unless --no-extras)
         "value_definition": "queries of all ranks / wall time of K steps, inputs and outputs resident in HBM (device "
                             "buffers), %s; the PCIe-inclusive rate of the host-buffer call is survey_8d_value" % (
                                 "steps pipelined %d deep inside the library (GBNNS_FLAG_DEFER_JOIN: later batches are released "
                                 "before the stream waits for batch i), %d distinct batches rotating" % (depth, nb) if pipelined
                                 else "one batch at a time"),
     }
-    if cold:
-        result["cold"] = cold
     if gate_failed:
         result["recall_gate_failed"] = True  # `value` is NOT a figure at recall >= 0.95
+
+    if args.full:
+        # ---- the same K steps serialised (GBNNS_FLAG_SERIAL semantics: profiling implies it): one batch at a time on one
+        # stream, kernels back to back, with the library's hipEvent pairs around every stage on the launch stream.  This is
+        # where roofline.kernel_ms comes from -- overlapped kernels cannot be timed individually.
+        ix.profile_read(reset=True)
+        ix.profile_enable(True)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for i in range(args.steps):
+            ix.search(batches[i % nb], ef, want=want, out=outs[i % nbuf], hash_capacity=args.hash_capacity, flags=tune_flags)
+        torch.cuda.synchronize()
+        elapsed_serial = time.perf_counter() - t1
+        prof = ix.profile_read(reset=True)
+        ix.profile_enable(False)
+        # walk statistics of every rotated batch (algorithmic bytes are averaged over them)
+        stats = {k: [] for k in want}
+        for j in range(nb):
+            r = ix.search(batches[j], ef, want=want, flags=tune_flags | g.FLAG_SERIAL)
+            for k in want:
+                stats[k].append(r[k].clone())
+        res = {k: torch.cat(v) for k, v in stats.items()}
+        res["ids"] = ix.search(q, ef, want=(), flags=tune_flags | g.FLAG_SERIAL)["ids"].clone()
+        torch.cuda.synchronize()
+
+        # ---- algorithmic bytes of the dominant kernel (the beam walk), SURVEY.md section 8d ------
+        rl = roofline_of(ds, res, prof, ef, nq_rank, max_degree, cfg, rank, launches=nb)
+        result["config"]["mean_hops"] = round(res["hops"].double().mean().item(), 1)
+        result["config"]["mean_dist_calc"] = round(res["dist_calc"].double().mean().item(), 1)
+        result.update({
+            "gather_self_check": gather_ok,
+            "per_rank": per_rank,
+            "roofline": rl["roofline"],
+            "kernels_ms": rl["kernels_ms"],
+            # the same K steps one batch at a time on one stream, kernels back to back (what round 1 / 2 reported as `value`)
+            "serial": {"ms_per_step": round(elapsed_serial * 1e3 / args.steps, 4),
+                       "queries_per_s": round(nq_rank * args.steps / elapsed_serial, 1),
+                       "note": "per rank, GBNNS_FLAG_SERIAL semantics, hipEvent profiling on: roofline.kernel_ms is measured here"},
+        })
+        if cold:
+            result["cold"] = cold
 
     # ---- N > 1: the same batch through the C ABI's own multi-device path (gbnns_multi_create + gbnns_multi_search_device:
     # one host process, one host thread and stream per device, ONE RCCL all-gather of the ids per batch) -- what a C++
     # host links against.  A fresh child process of rank 0 drives all N devices while every rank is parked at a barrier
     # (their GPUs idle); never `value`; an RCCL or launch failure is a field of the line, not a failed bench.
-    if world > 1 and not args.no_capi_multi:
+    if args.full and world > 1 and not args.no_capi_multi:
         ref = ix.search(q, ef, want=(), flags=tune_flags | g.FLAG_SERIAL)["ids"].clone()
         torch.cuda.synchronize()
         if not strong or nq_total % world == 0:   # (equal blocks: one all-gather of the ranks' answers to batch 0)
@@ -573,7 +603,7 @@ def main():
             result["capi_multi"] = capi_multi_parent(args, argv, world, pieces, rehearsal)
         dist.barrier()
 
-    extras = world == 1 and not args.no_extras
+    extras = args.full and world == 1 and not args.no_extras
     small = nq_rank <= 20_000
 
     # ---- other efs of this configuration: kernel time and roofline fraction each -------------------
@@ -677,7 +707,7 @@ def main():
         result["host_buffers_pinned_qps"] = round(5 * nq_rank / (time.perf_counter() - t1), 1)
 
     # ---- CPU baseline (rank 0, N = 1 only): the compiled reference if present, else the port ----
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(ds, q, ef, res["ids"], metric_id, sample=args.cpu_sample)
 
     if isinstance(result.get("throughput_option"), dict) and "_ids" in result["throughput_option"]:
@@ -688,7 +718,7 @@ def main():
             result["throughput_option"]["reference_sample"] = nref
 
     # ---- the other BASELINE.json configurations, each as a short run of its own in a child process --------------
-    if world == 1 and args.config == "sift" and not args.no_extras and not args.no_other_configs and not args.n and not args.nq:
+    if extras and args.config == "sift" and not args.no_other_configs and not args.n and not args.nq:
         ix.close()
         ix = None
         del ds
@@ -712,6 +742,24 @@ def main():
         ix.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 60_000_000  # --dump-outputs stays under 64 MB in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name -> tensor) as path/<name>.npy in float64 (exact for every id and counter).  Where the whole
+    set would pass DUMP_BYTES, each array keeps a fixed, seeded sample of its rows, written beside it as <name>_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.cpu().numpy().astype(np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES:
+            keep = max(1, int(len(a) * DUMP_BYTES / (2 * total)))   # (half the budget: the row numbers ride along)
+            rows = np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def throughput_option(g, ix, q, ef, res_exact, batches, depth, nq):
@@ -1001,7 +1049,7 @@ def capi_multi_child(args, cfg):
 
 
 def other_configs(args, t_start):
-    """BASELINE.json configurations 3 - 5 as short runs of their own (`python bench.py --config <name> --no-extras
+    """BASELINE.json configurations 3 - 5 as short runs of their own (`python bench.py --config <name> --full --no-extras
     --cpu-sample 1000`), each in a fresh child process started after this one has released its index: GIST1M-shaped
     (ef 200, the reference's 1 000-query batch), GloVe-shaped with the L2 and the negative-dot metric (ef 64) and,
     while the wall-clock budget lasts, DEEP10M-shaped at full size (n = 10^7, ONE 1 M-query batch).  Per configuration:
@@ -1023,7 +1071,8 @@ def other_configs(args, t_start):
             out[name] = {"skipped": "%.0f s of the %.0f s budget left, this configuration is given %d s" % (left, args.budget_s, need_s)}
             continue
         cmd = [sys.executable, os.path.abspath(__file__), "--config", name.split("-M")[0] if "-M" in name else name, "--steps", str(steps),
-               "--warmup", "3" if steps > 3 else "1", "--no-extras", "--cpu-sample", "1000", "--cache-dir", args.cache_dir, "--full-line"]
+               "--warmup", "3" if steps > 3 else "1", "--full", "--no-extras", "--cpu-sample", "1000", "--cache-dir", args.cache_dir,
+               "--full-line"]
         if "-M" in name:
             cmd += ["--graph-M", name.split("-M")[1]]
         t1 = time.time()
@@ -1311,7 +1360,7 @@ def emit(result, args):
                 f.write(full + "\n")
         except OSError:
             pass
-    if args.full_line or (args.no_extras and len(full) <= 8000):   # (a --no-extras record is small: tools read it whole)
+    if args.full_line or ((args.no_extras or not args.full) and len(full) <= 8000):   # (a plain or --no-extras record is small: tools read it whole)
         print(full, flush=True)
         return
     line = json.dumps(compact(result))

@@ -643,7 +643,7 @@ def test_bench_two_ranks_rehearsal():
     # the padded gather)
     for extra in ([], ["--config", "deep", "--ef", "40"], ["--strong", "--strong-nq", "5001"]):
         p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                            "--n", "60000", "--nq", "3000", "--no-extras", "--no-cpu-baseline"] + extra,
+                            "--n", "60000", "--nq", "3000", "--full", "--no-extras", "--no-cpu-baseline"] + extra,
                            env=env, capture_output=True, text=True, timeout=900)
         assert p.returncode == 0, p.stderr[-3000:]
         lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -8,7 +8,7 @@ while [ $# -gt 0 ] && [ "$1" != "--" ]; do CGROUPS+=("$1"); shift; done
 OUT=gpurun_out/cp_$TAG
 mkdir -p $OUT
 export GBNNS_CACHE=/tmp/gbnns_cache
-ARGS="bench.py --steps 10 --warmup 2 --no-cpu-baseline $@"
+ARGS="bench.py --full --steps 10 --warmup 2 --no-cpu-baseline $@"
 python3 $ARGS > $OUT/bench_plain.json 2> $OUT/bench_plain.err
 i=0
 for g in "${CGROUPS[@]}"; do

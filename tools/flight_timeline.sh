@@ -6,7 +6,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/tl_$TAG
 mkdir -p $OUT
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 $R/bench.py --steps 30 --warmup 5 --no-other-configs --no-cpu-baseline --no-extras "$@" > $OUT/bench.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 $R/bench.py --full --steps 30 --warmup 5 --no-other-configs --no-cpu-baseline --no-extras "$@" > $OUT/bench.json 2> $OUT/bench.err
 cd $R
 python3 - <<PY
 import csv, glob, re

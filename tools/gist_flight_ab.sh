@@ -7,7 +7,7 @@ run() {  # label, env assignments..., -- bench args
     local label=$1; shift
     local envs=()
     while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-    env "${envs[@]}" python3 bench.py --config gist --steps $STEPS --warmup 10 --no-other-configs --no-cpu-baseline --no-extras "$@" 2>/dev/null |
+    env "${envs[@]}" python3 bench.py --full --config gist --steps $STEPS --warmup 10 --no-other-configs --no-cpu-baseline --no-extras "$@" 2>/dev/null |
         python3 -c "import sys, json; d = json.loads(sys.stdin.readline()); print('%-44s %.4f ms per batch  %.3f M queries/s  project %.4f ms  walk %.4f ms (serialised)' % ('$label', d['ms_per_step'], d['value'] / 1e6, d['kernels_ms']['project'], d['kernels_ms']['walk']))"
 }
 run "default, depth 3" X=1 --

@@ -4,7 +4,7 @@ TAG=${1:-l}; shift
 OUT=gpurun_out/lds_$TAG
 mkdir -p $OUT
 export GBNNS_CACHE=/tmp/gbnns_cache
-ARGS="bench.py --steps 10 --warmup 2 --no-cpu-baseline $@"
+ARGS="bench.py --full --steps 10 --warmup 2 --no-cpu-baseline $@"
 python3 $ARGS > $OUT/bench_plain.json 2> $OUT/bench_plain.err
 rocprofv3 --pmc SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL SQ_LDS_MEM_VIOLATIONS SQ_LDS_ATOMIC_RETURN SQ_INSTS_LDS GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/pmc_l1 -- python3 $ARGS > /dev/null 2> $OUT/pmc_l1.err
 rocprofv3 --pmc SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_INST_LEVEL_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --kernel-trace --output-format csv -d $OUT/pmc_l2 -- python3 $ARGS > /dev/null 2> $OUT/pmc_l2.err

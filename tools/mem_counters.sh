@@ -8,7 +8,7 @@ shift 3 2>/dev/null || shift $#
 OUT=gpurun_out/mem_${TAG}_${CFG}_ef${EF}
 mkdir -p $OUT
 export GBNNS_CACHE=/tmp/gbnns_cache
-ARGS="bench.py --config $CFG --ef $EF --steps 10 --warmup 2 --no-cpu-baseline --no-extras --serial $*"
+ARGS="bench.py --full --config $CFG --ef $EF --steps 10 --warmup 2 --no-cpu-baseline --no-extras --serial $*"
 cd /tmp >/dev/null; export TMPDIR=/tmp; cd - >/dev/null
 pass() {  # name counters...   (at most two counters per hardware block and pass: more is refused for TA, and a refused pass hangs)
   local name=$1; shift

@@ -4,7 +4,7 @@ cd /tmp >/dev/null; export TMPDIR=/tmp; cd - >/dev/null
 for Q in 0 1; do
   export GBNNS_QUOTIENT=$Q
   O=gpurun_out/qpmc_$1_$2_q$Q
-  rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_WAIT_INST_ANY SQ_WAVE_CYCLES --kernel-trace --output-format csv -d $O -- python3 bench.py --config $1 --ef $2 --steps 5 --warmup 2 --no-cpu-baseline --no-extras --serial > /dev/null 2> $O.err
+  rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_WAIT_INST_ANY SQ_WAVE_CYCLES --kernel-trace --output-format csv -d $O -- python3 bench.py --full --config $1 --ef $2 --steps 5 --warmup 2 --no-cpu-baseline --no-extras --serial > /dev/null 2> $O.err
   python3 - $O <<'PY'
 import csv,glob,sys,collections
 f=glob.glob(sys.argv[1]+"/**/*counter_collection.csv",recursive=True)[0]
