@@ -127,7 +127,6 @@ struct Lane {
     bool stats_pending = false;
     int stats_ef = 0;
     uint32_t stats_cap = 0;
-    bool stats_hot2 = false;     // that call ran a hand-laid-out kernel over two-pass adjacency rows (sizing: knob vs_fill2)
     // which of the two control-word blocks the next call uses, and whether each is known to be zero
     int ctrl_phase = 0;
     bool ctrl_clean[2] = {true, true};
@@ -145,7 +144,7 @@ struct Lane {
 // starts from, so a test or an A/B run that flips one no longer changes every other handle of the process.  The three knobs of
 // gbnns_exact_knn -- a function without a handle -- stay process-wide.
 struct Knobs {
-    int quotient, vs_disp, max_waves, spec_min_nq, spec_any_form, mlp_small, mlp_net, mlp_slab, late_rows, vs_fill2, spec_tail, coop, coop_pack;
+    int quotient, vs_disp, max_waves, spec_min_nq, spec_any_form, mlp_small, mlp_net, mlp_slab, late_rows, spec_tail, coop;
 };
 Knobs knob_defaults();                                    // the process-wide defaults as they stand now
 bool knob_set(Knobs& k, const char* name, int value);     // clamps like the environment does; false = no such handle knob

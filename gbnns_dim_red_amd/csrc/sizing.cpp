@@ -28,7 +28,7 @@ FirstPassSizing size_first_pass(gbnns_index* ix, WalkParams& w, const gbnns_sear
     // (most wavefronts per CU worth cutting the LDS for: the register files' limit of the first-pass kernel -- 32 for the
     // one-register hot instances, 28 / 24 / 20 for the others -- or the diagnostic knob)
     const int knob_waves = ix->knob.max_waves;
-    // (the two- / three-wavefront walk of a lone small batch: as many workgroups per CU as the batch puts there, the table takes the rest
+    // (the two-wavefront walk of a lone small batch: as many workgroups per CU as the batch puts there, the table takes the rest
     // of the LDS -- shorter probe sequences, gist shape ef 200 / 400: 0.486 / 0.933 against 0.490 / 0.945 ms)
     const size_t cus = (size_t)(ix->cus > 0 ? ix->cus : 256);
     const size_t coop_cap = std::min<size_t>(32, std::max<size_t>(1, ((size_t)nq + cus - 1) / cus));
@@ -47,9 +47,6 @@ FirstPassSizing size_first_pass(gbnns_index* ix, WalkParams& w, const gbnns_sear
         if (slots < wave_cap && ix->maxdc_for_ef.count(skey)) {
             const uint32_t m = ix->maxdc_for_ef[skey];
             uint32_t need_min = std::max((m + m / 32 + 64) / 15 * 16 + 16 + extra, floor_entries);
-            // (the hand-laid-out kernels over two-pass adjacency rows: the extra wavefront must leave the table at the fill the rule aims at + 4 points)
-            const int fill2 = ix->knob.vs_fill2;
-            if (hot && ix->ell_stride > 32u && fill2 > 0) need_min = std::max(need_min, (uint32_t)((uint64_t)m * 100u / (uint32_t)(fill2 + 4)) + extra);
             const size_t share1 = kMaxLds / (slots + 1) / gran * gran;
             if (share1 > lds_fixed && walk_hash_entries(share1 - lds_fixed, f) >= need_min + 4) slots += 1;
         }

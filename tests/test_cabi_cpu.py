@@ -100,6 +100,27 @@ def test_argument_validation(lib):
     assert b"struct_size" in lib.gbnns_last_error()
 
 
+def test_debug_knob_names(lib):
+    """gbnns_debug_knob needs no GPU: every handle knob is accepted ("coop" 2 too: clamped, the two-wavefront walk has one form),
+    the removed "coop_pack" and "vs_fill2" are refused like any unknown name (GBNNS_ERR_INVALID).  In a child process: a handle
+    knob set here would be the default of every handle this process creates afterwards."""
+    import subprocess
+    handle_knobs = {"quotient": 1, "vs_disp": 15, "max_waves": 0, "spec_min_nq": 32768, "spec_any_form": 0, "mlp_small": 4096,
+                    "mlp_net": 1, "mlp_slab": 1, "late_rows": -1, "spec_tail": 50, "coop": 2}
+    refused = ("coop_pack", "vs_fill2", "no_such_knob")
+    script = ("import ctypes, sys\n"
+              "lib = ctypes.CDLL(sys.argv[1])\n"
+              "lib.gbnns_debug_knob.argtypes = [ctypes.c_char_p, ctypes.c_int]\n"
+              "for a in sys.argv[2:]:\n"
+              "    n, v = a.split('=')\n"
+              "    print(n, lib.gbnns_debug_knob(n.encode(), int(v)))\n")
+    args = ["%s=%d" % kv for kv in handle_knobs.items()] + ["%s=1" % n for n in refused]
+    p = subprocess.run([sys.executable, "-c", script, binding._LIB_PATH] + args, capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr[-2000:]
+    codes = dict(ln.split() for ln in p.stdout.splitlines())
+    assert codes == {**{n: "0" for n in handle_knobs}, **{n: "1" for n in refused}}, codes
+
+
 def test_exact_knn_argument_validation(lib):
     base = np.zeros((8, 200), np.float32)
     ids = np.zeros((8, 3), np.uint32)

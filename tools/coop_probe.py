@@ -1,4 +1,4 @@
-"""GPU box: the profile record of a lone gist-shaped call per small-batch walk form (knob coop 0 / 1 / 2) -- which kernels ran, how long,
+"""GPU box: the profile record of a lone gist-shaped call per small-batch walk form (knob coop 0 / 1) -- which kernels ran, how long,
 how many queries were handed over."""
 import os, sys, json
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
@@ -12,7 +12,7 @@ ds = synth.make_dataset(device="cuda:0", cache_dir="/tmp/gbnns_cache", **kw)
 ix = ds.index()
 q = ds.queries
 ef = int(sys.argv[1]) if len(sys.argv) > 1 else cfg["ef"]
-for coop in (0, 1, 2, 2, 1):
+for coop in (0, 1, 1, 0):
     ix.knob("coop", coop)
     for _ in range(5):
         ix.search(q, ef, want=())

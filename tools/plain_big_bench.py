@@ -7,7 +7,6 @@ import torch
 import bench
 import gbnns_dim_red_amd as g
 from gbnns_dim_red_amd import synth
-lib = g.load_library()
 for name, efs in (("sift", (100, 130, 140, 200)), ("deep1m", (120, 160, 200))):
     cfg = bench.CONFIGS[name]
     ds = synth.make_dataset(device="cuda:0", cache_dir=os.environ.get("GBNNS_CACHE", "/tmp/gbnns_cache"), n=cfg["n"], nq=cfg["nq"],
@@ -15,7 +14,7 @@ for name, efs in (("sift", (100, 130, 140, 200)), ("deep1m", (120, 160, 200))):
     ix = ds.index()
     for ef in efs:
         for late in (0, 1):
-            lib.gbnns_debug_knob(b"late_rows", late)
+            ix.knob("late_rows", late)   # (this handle's own setting: gbnns_debug_knob only sets the default of later handles)
             for _ in range(3):
                 r = ix.search(ds.queries, ef, mode=g.MODE_PLAIN, k=1, want=("hops", "dist_calc"))
             torch.cuda.synchronize()
@@ -29,4 +28,3 @@ for name, efs in (("sift", (100, 130, 140, 200)), ("deep1m", (120, 160, 200))):
             print("%s plain d=%d ef=%d late_rows=%d: walk %.3f ms  %-44s dist_calc %.0f -> %.0f GB/s of row bytes (%.3f of 8 TB/s)"
                   % (name, ds.d, ef, late, wm, p["walk_kernel"][:44], dc, dc * ds.d * 4 * ds.nq / (wm * 1e-3) / 1e9, dc * ds.d * 4 * ds.nq / (wm * 1e-3) / 8e12), flush=True)
     ix.close()
-lib.gbnns_debug_knob(b"late_rows", -1)
