@@ -132,6 +132,11 @@ struct Lane {
     bool ctrl_clean[2] = {true, true};
     bool ctrl_ready = false;
     uint32_t last_general = 0;
+    // page-locked staging for a caller's PAGEABLE host buffers (host_copy_in / host_copy_out, handle.cpp)
+    void* stage = nullptr;             // two halves, used alternately
+    hipEvent_t stage_ev[2] = {nullptr, nullptr};  // recorded behind the last copy that reads / writes a half
+    bool stage_busy[2] = {false, false};
+    int stage_next = 0;
     DevBuf* bufs(int i) {
         DevBuf* b[] = {&q_in, &q_low, &h1, &h2, &cand, &cand_dist, &cnt, &hops, &dc, &edges, &out, &entries,
                        &ovf_list, &ovf2_list, &ctrl, &g_bitmap, &g_keys, &fp_bitmap, &order, &order_hist};
@@ -201,6 +206,13 @@ namespace gbnns_api {
 
 // handle.cpp
 int h2d_staged(void* dst, const void* src, size_t bytes);
+// Copies between a caller's HOST buffer and device memory for the per-call entry points (gbnns_search_ex, gbnns_project,
+// gbnns_rerank), enqueued on `s`.  Page-locked caller memory is handed to the runtime as it is (asynchronous, as before); pageable
+// memory passes through the lane's own page-locked staging buffer in pieces, for the reason given at h2d_staged -- host_copy_out
+// then returns with the data in place.  host_copy_out: `rows` rows of `width` bytes, `spitch` bytes apart on the device, packed at dst.
+struct Lane;
+int host_copy_in(Lane& L, void* dst_dev, const void* src, size_t bytes, hipStream_t s);
+int host_copy_out(Lane& L, void* dst, const void* src_dev, size_t spitch, size_t width, size_t rows, hipStream_t s);
 int upload(DevBuf& dst, const void* src, size_t rows, size_t row_floats, size_t pad_floats, int mem_kind);
 int build_ell(const uint64_t* off, const uint32_t* nbr, uint64_t n, std::vector<uint32_t>& ell, uint32_t& stride);
 int run_project(gbnns_index* ix, Lane& L, const float* x, uint32_t xstride, uint32_t nx, float* out, hipStream_t s, bool in_flight = false,

@@ -62,6 +62,73 @@ int h2d_staged(void* dst, const void* src, size_t bytes) {
     return rc;
 }
 
+// The per-call copies (declared in api_internal.h).  The caller's arrays of a long-lived process are exactly the arrays of the note
+// above: numpy hands the addresses of a freed batch to the next one.  Met in the host path of gbnns_project at the end of a full
+// test-suite run ("an illegal memory access", never in a short run), so pageable buffers no longer reach the runtime's copy calls.
+namespace {
+constexpr size_t kStageHalf = 2u << 20;
+// The half to use next, free of the copy that used it last (host memcpy of one piece then runs beside the DMA of the piece before).
+int lane_stage_half(Lane& L, char*& half, int& h) {
+    if (!L.stage) {
+        HIP_TRY(hipHostMalloc(&L.stage, 2 * kStageHalf, hipHostMallocDefault));
+        HIP_TRY(hipEventCreateWithFlags(&L.stage_ev[0], hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&L.stage_ev[1], hipEventDisableTiming));
+    }
+    h = L.stage_next;
+    L.stage_next ^= 1;
+    if (L.stage_busy[h]) HIP_TRY(hipEventSynchronize(L.stage_ev[h]));
+    L.stage_busy[h] = false;
+    half = static_cast<char*>(L.stage) + (size_t)h * kStageHalf;
+    return GBNNS_OK;
+}
+}  // namespace
+
+int host_copy_in(Lane& L, void* dst_dev, const void* src, size_t bytes, hipStream_t s) {
+    if (bytes == 0) return GBNNS_OK;
+    if (pinned_alias(static_cast<const char*>(src), bytes)) {
+        HIP_TRY(hipMemcpyAsync(dst_dev, src, bytes, hipMemcpyHostToDevice, s));
+        return GBNNS_OK;
+    }
+    for (size_t done = 0; done < bytes; done += kStageHalf) {
+        const size_t nb = std::min(kStageHalf, bytes - done);
+        char* half;
+        int h;
+        if (int rc = lane_stage_half(L, half, h)) return rc;
+        std::memcpy(half, static_cast<const char*>(src) + done, nb);
+        HIP_TRY(hipMemcpyAsync(static_cast<char*>(dst_dev) + done, half, nb, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(L.stage_ev[h], s));
+        L.stage_busy[h] = true;
+    }
+    return GBNNS_OK;
+}
+
+int host_copy_out(Lane& L, void* dst, const void* src_dev, size_t spitch, size_t width, size_t rows, hipStream_t s) {
+    if (width == 0 || rows == 0) return GBNNS_OK;
+    if (pinned_alias(static_cast<const char*>(dst), width * rows)) {
+        if (spitch == width || rows == 1) HIP_TRY(hipMemcpyAsync(dst, src_dev, width * rows, hipMemcpyDeviceToHost, s));
+        else HIP_TRY(hipMemcpy2DAsync(dst, width, src_dev, spitch, width, rows, hipMemcpyDeviceToHost, s));
+        return GBNNS_OK;
+    }
+    if (spitch == width || rows == 1) {  // one contiguous run
+        rows = width * rows;
+        spitch = width = 1;
+    }
+    if (width > kStageHalf) return fail(GBNNS_ERR_INVALID, "host_copy_out: a row of %zu bytes", width);
+    const size_t per = kStageHalf / width;  // rows per piece
+    for (size_t r = 0; r < rows; r += per) {
+        const size_t nr = std::min(per, rows - r);
+        char* half;
+        int h;
+        if (int rc = lane_stage_half(L, half, h)) return rc;
+        const char* from = static_cast<const char*>(src_dev) + r * spitch;
+        if (width == 1) HIP_TRY(hipMemcpyAsync(half, from, nr, hipMemcpyDeviceToHost, s));
+        else HIP_TRY(hipMemcpy2DAsync(half, width, from, spitch, width, nr, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        std::memcpy(static_cast<char*>(dst) + r * width, half, nr * width);
+    }
+    return GBNNS_OK;
+}
+
 int upload(DevBuf& dst, const void* src, size_t rows, size_t row_floats, size_t pad_floats,
            int mem_kind) {
     // copies a [rows x row_floats] f32 matrix into a zero-padded [rows x pad_floats] device matrix
@@ -396,6 +463,9 @@ int gbnns_index_destroy(gbnns_index* ix) {
         if (L.done_ev) (void)hipEventDestroy(L.done_ev);
         if (L.prev_ev) (void)hipEventDestroy(L.prev_ev);
         if (L.h_stats) (void)hipHostFree(L.h_stats);
+        if (L.stage) (void)hipHostFree(L.stage);
+        for (hipEvent_t e : L.stage_ev)
+            if (e) (void)hipEventDestroy(e);
         if (L.stream) (void)hipStreamDestroy(L.stream);
         for (int i = 0; DevBuf* b = L.bufs(i); ++i) b->release();
     }
@@ -631,7 +701,7 @@ int gbnns_project(gbnns_index* ix, const float* x, uint64_t n_x, float* out, int
         const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n_x - b);
         const float* xin = x + b * ix->d;
         if (mem_kind == GBNNS_MEM_HOST) {
-            HIP_TRY(hipMemcpyAsync(L.q_in.p, xin, (size_t)m * ix->d * 4, hipMemcpyHostToDevice, s));
+            if ((rc = host_copy_in(L, L.q_in.p, xin, (size_t)m * ix->d * 4, s))) return rc;
             xin = L.q_in.as<float>();
         }
         float* dst = L.q_low.as<float>();
@@ -639,10 +709,11 @@ int gbnns_project(gbnns_index* ix, const float* x, uint64_t n_x, float* out, int
         if (direct) dst = out + b * ix->d_low;
         rc = run_project(ix, L, xin, ix->d, m, dst, s);
         if (rc) return rc;
-        if (!direct) {
-            const hipMemcpyKind kind = mem_kind == GBNNS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        if (mem_kind == GBNNS_MEM_HOST) {
+            if ((rc = host_copy_out(L, out + b * ix->d_low, dst, (size_t)ix->dl_pad * 4, (size_t)ix->d_low * 4, m, s))) return rc;
+        } else if (!direct) {
             HIP_TRY(hipMemcpy2DAsync(out + b * ix->d_low, (size_t)ix->d_low * 4, dst, (size_t)ix->dl_pad * 4,
-                                     (size_t)ix->d_low * 4, m, kind, s));
+                                     (size_t)ix->d_low * 4, m, hipMemcpyDeviceToDevice, s));
         }
         if (mem_kind == GBNNS_MEM_HOST) HIP_TRY(hipStreamSynchronize(s));
     }
@@ -678,9 +749,9 @@ int gbnns_rerank(gbnns_index* ix, const float* queries, uint64_t n_q, const uint
                 if (cand[i * cand_stride + j] >= ix->n)
                     return fail(GBNNS_ERR_INVALID, "candidate id %u >= n", cand[i * cand_stride + j]);
         }
-        HIP_TRY(hipMemcpyAsync(L.q_in.p, queries, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(L.cand.p, cand, (size_t)nq * cand_stride * 4, hipMemcpyHostToDevice, s));
-        if (count) HIP_TRY(hipMemcpyAsync(cnt_dev, count, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+        if ((rc = host_copy_in(L, L.q_in.p, queries, (size_t)nq * ix->d * 4, s))) return rc;
+        if ((rc = host_copy_in(L, L.cand.p, cand, (size_t)nq * cand_stride * 4, s))) return rc;
+        if (count && (rc = host_copy_in(L, cnt_dev, count, (size_t)nq * 4, s))) return rc;
         r.q = L.q_in.as<float>(); r.cand = L.cand.as<uint32_t>(); r.out = L.out.as<uint32_t>();
     } else {
         r.q = queries; r.cand = cand; r.out = out_ids;
@@ -690,7 +761,7 @@ int gbnns_rerank(gbnns_index* ix, const float* queries, uint64_t n_q, const uint
     r.count = cnt_dev;
     HIP_TRY(launch_rerank(r, ix->metric, s));
     if (host) {
-        HIP_TRY(hipMemcpyAsync(out_ids, r.out, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+        if ((rc = host_copy_out(L, out_ids, r.out, (size_t)nq * 4, (size_t)nq * 4, 1, s))) return rc;
         HIP_TRY(hipStreamSynchronize(s));
         ix->in_flight = false;
     }

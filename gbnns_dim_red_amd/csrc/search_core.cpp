@@ -53,13 +53,13 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
     const float* q_dev = a->queries;
     if (host) {
         if ((rc = L.q_in.ensure((size_t)nq * ix->d * 4))) return rc;
-        HIP_TRY(hipMemcpyAsync(L.q_in.p, a->queries, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice, s));
+        if ((rc = host_copy_in(L, L.q_in.p, a->queries, (size_t)nq * ix->d * 4, s))) return rc;
         q_dev = L.q_in.as<float>();
     }
     const uint32_t* entries_dev = a->entry_ids;
     if (a->entry_ids && host) {
         if ((rc = L.entries.ensure((size_t)nq * n_ent * 4))) return rc;
-        HIP_TRY(hipMemcpyAsync(L.entries.p, a->entry_ids, (size_t)nq * n_ent * 4, hipMemcpyHostToDevice, s));
+        if ((rc = host_copy_in(L, L.entries.p, a->entry_ids, (size_t)nq * n_ent * 4, s))) return rc;
         entries_dev = L.entries.as<uint32_t>();
     }
     if (a->entry_ids && host) {
@@ -89,16 +89,19 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
                 return rc;
             w.q = ql; w.qstride = ix->dl_pad;
         } else if (host) {
-            HIP_TRY(hipMemcpyAsync(ql, a->queries_low, (size_t)nq * ix->d_low * 4, hipMemcpyHostToDevice, s));
+            if ((rc = host_copy_in(L, ql, a->queries_low, (size_t)nq * ix->d_low * 4, s))) return rc;
             w.q = ql; w.qstride = ix->d_low;
         } else {
             w.q = a->queries_low; w.qstride = ix->d_low;
         }
         w.db = ix->db_low; w.dstride = ix->dl_pad; w.dim = ix->d_low;
         if (a->out_q_low && a->mode == GBNNS_MODE_NET) {
-            const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-            HIP_TRY(hipMemcpy2DAsync(a->out_q_low, (size_t)ix->d_low * 4, ql, (size_t)ix->dl_pad * 4,
-                                     (size_t)ix->d_low * 4, nq, kind, s));
+            if (host) {
+                if ((rc = host_copy_out(L, a->out_q_low, ql, (size_t)ix->dl_pad * 4, (size_t)ix->d_low * 4, nq, s))) return rc;
+            } else {
+                HIP_TRY(hipMemcpy2DAsync(a->out_q_low, (size_t)ix->d_low * 4, ql, (size_t)ix->dl_pad * 4,
+                                         (size_t)ix->d_low * 4, nq, hipMemcpyDeviceToDevice, s));
+            }
         }
     }
     // Deep batches are walked in locality order (walk_common.h, walk_query_of): a counting sort on the sign bits of the
@@ -382,15 +385,14 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
 
     // ---- outputs ----------------------------------------------------------------------
     if (host) {
-        if (!ids_alias) HIP_TRY(hipMemcpyAsync(a->out_ids, out_dev, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-        if (a->out_hops && !hops_alias) HIP_TRY(hipMemcpyAsync(a->out_hops, w.hops, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-        if (a->out_dist_calc && !dc_alias)
-            HIP_TRY(hipMemcpyAsync(a->out_dist_calc, w.dist_calc, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-        if (a->out_edges && !edges_alias) HIP_TRY(hipMemcpyAsync(a->out_edges, w.edges, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-        if (a->out_cand)
-            HIP_TRY(hipMemcpyAsync(a->out_cand, w.cand, (size_t)nq * cstride * 4, hipMemcpyDeviceToHost, s));
-        if (a->out_cand_dist)
-            HIP_TRY(hipMemcpyAsync(a->out_cand_dist, w.cand_dist, (size_t)nq * cstride * 4, hipMemcpyDeviceToHost, s));
+        // (pageable buffers: through the lane's staging buffer, each copy complete on return -- host_copy_out)
+        const size_t b4 = (size_t)nq * 4, bc = (size_t)nq * cstride * 4;
+        if (!ids_alias && (rc = host_copy_out(L, a->out_ids, out_dev, b4, b4, 1, s))) return rc;
+        if (a->out_hops && !hops_alias && (rc = host_copy_out(L, a->out_hops, w.hops, b4, b4, 1, s))) return rc;
+        if (a->out_dist_calc && !dc_alias && (rc = host_copy_out(L, a->out_dist_calc, w.dist_calc, b4, b4, 1, s))) return rc;
+        if (a->out_edges && !edges_alias && (rc = host_copy_out(L, a->out_edges, w.edges, b4, b4, 1, s))) return rc;
+        if (a->out_cand && (rc = host_copy_out(L, a->out_cand, w.cand, bc, bc, 1, s))) return rc;
+        if (a->out_cand_dist && (rc = host_copy_out(L, a->out_cand_dist, w.cand_dist, bc, bc, 1, s))) return rc;
         g_slow.mark("copy_out");
         if (sync_host) {
             HIP_TRY(hipStreamSynchronize(s));

@@ -28,6 +28,12 @@
  * Ids in DEVICE buffers are not validated on the host.  An entry id >= n is never dereferenced: that query
  * gets answer 0xFFFFFFFF, an all-0xFFFFFFFF candidate row and zero counters.  Candidate ids >= n passed to
  * gbnns_rerank read row 0 instead.  HOST buffers are validated (GBNNS_ERR_INVALID).
+ *
+ * HOST buffers of gbnns_search_ex / gbnns_search_batch / gbnns_project / gbnns_rerank may be pageable or page-locked.
+ * Page-locked ones (hipHostMalloc, hipHostRegister, gbnns_host_pin) are copied from / to directly.  Pageable ones pass
+ * through 4 MB of page-locked staging per workspace, so the runtime never page-locks a caller's array on the fly: it
+ * keeps such mappings, and a caller whose allocator later reuses the addresses of a freed array would have a copy fault
+ * on the stale one ("an illegal memory access", seen only in long-lived processes).  Costs one pass over host memory.
  */
 #ifndef GBNNS_H_
 #define GBNNS_H_

@@ -3,6 +3,14 @@
 Everything here is built from numpy's PCG64 integer stream and exact integer->float32
 conversions (no libm, no BLAS), so the same seed gives the same bytes on every host; the golden
 fixtures store a sha256 of the regenerated inputs to prove it.
+
+Two families.  `clustered`, `lattice` and `net_layers` (the `Case` kinds, the golden fixtures) emit
+small dyadic rationals -- coordinates k/256 with |k| <= 88, weights k/2^s with |k| <= 128 -- on which
+every difference, square and partial sum of a distance is exact in float32: they pin ids, ties,
+hops and counters, but ANY summation order returns their distance bits.  `full_mantissa`,
+`net_layers_full`, `contest_l2` and `contest_dot` carry 20 and more significant bits per number, so
+that the order of the roundings shows: in the distance bits, and (the contests) in which candidate
+a re-rank returns.  tests/test_rounding_fixtures.py proves both statements on the CPU.
 """
 import hashlib
 
@@ -47,6 +55,76 @@ def net_layers(rng, d, dh, dlow):
     return layer(dh, d, s1), layer(dh, dh, s2), layer(dlow, dh, s2)
 
 
+def full_mantissa(rng, n, d, n_centers=16, spread=40):
+    """`clustered`'s geometry (same centres / noise recipe, same [-0.35, 0.35] range) with about 22
+    significant bits per coordinate: the grid value times 2^15 plus a jitter from [-2^14, 2^14),
+    over 2^23.  Squares and partial sums of such coordinates round at every step."""
+    centers = _ints(rng, (n_centers, d), -12, 13)
+    assign = _ints(rng, (n,), 0, n_centers)
+    noise = _ints(rng, (n, d), -spread, spread + 1)
+    v = (centers[assign] * 4 + noise) * (1 << 15) + _ints(rng, (n, d), -(1 << 14), 1 << 14)
+    assert np.abs(v).max(initial=0) < (1 << 24)     # integer -> float32 stays exact
+    return (v.astype(np.float32) / np.float32(1 << 23)).astype(np.float32)
+
+
+def net_layers_full(rng, d, dh, dlow):
+    """`net_layers` with about 20 significant bits per weight and bias (an integer of +-2^20 over a
+    power of two, same magnitudes): layer 1 is inexact already on exact inputs."""
+    def layer(dout, din, shift):
+        w = _ints(rng, (dout, din + 1), -(1 << 20), (1 << 20) + 1).astype(np.float32)
+        return (w / np.float32(1 << (shift + 13))).astype(np.float32)
+    s1 = 7 + max(0, int(np.log2(max(d, 2))) // 2)
+    s2 = 7 + max(0, int(np.log2(max(dh, 2))) // 2)
+    return layer(dh, d, s1), layer(dh, dh, s2), layer(dlow, dh, s2)
+
+
+def _permuted_rows(rng, v, per_group, width):
+    """per_group copies of v, the first `width` entries of each under a fresh permutation."""
+    rows = np.repeat(v[None, :], per_group, axis=0)
+    for r in range(per_group):
+        rows[r, :width] = v[:width][rng.permutation(width)]
+    return rows
+
+
+def contest_l2(rng, groups, per_group, d):
+    """The equal-distance contest for L2Metric::Dist.  Group g has one query, ((80 + m) << 17) / 2^23
+    with m in [0, 32]^d (coordinates in [1.25, 1.75]), and per_group rows query + pi(j) / 2^23 with
+    j in (-2^21, 2^21)^d and a fresh permutation pi per row over the 4 * floor(d / 4) coordinates
+    the reference reads (the rest: arbitrary jitter, which must not matter).  All numerators lie in
+    [2^23, 2^24): conversions and row - query are exact, so in real arithmetic every row of a group
+    is equidistant from its query, and in float32 the distances are a few values some ulp apart --
+    decided by the order of the roundings alone.  Returns base [groups * per_group x d] (group-major),
+    queries [groups x d], group [groups * per_group]."""
+    width = 4 * (d // 4)
+    base = np.empty((groups * per_group, d), np.int64)
+    queries = np.empty((groups, d), np.int64)
+    for g in range(groups):
+        m = _ints(rng, (d,), 0, 33)
+        j = _ints(rng, (d,), -(1 << 21) + 1, 1 << 21)
+        q = (80 + m) << 17
+        rows = _permuted_rows(rng, j, per_group, width)
+        rows[:, width:] = _ints(rng, (per_group, d - width), -(1 << 21) + 1, 1 << 21)
+        queries[g] = q
+        base[g * per_group:(g + 1) * per_group] = q[None, :] + rows
+    assert base.min() >= (1 << 23) and base.max() < (1 << 24)
+    f = lambda a: (a.astype(np.float32) / np.float32(1 << 23)).astype(np.float32)
+    return f(base), f(queries), np.repeat(np.arange(groups, dtype=np.int64), per_group)
+
+
+def contest_dot(rng, groups, per_group, d):
+    """The equal-distance contest for Angular::Dist.  Every query is c * (1, ..., 1) with
+    c = 11184811 / 2^23 (1.333..., a full mantissa); the rows of a group are permutations of one vector
+    of integers from (-2^23, 2^23) over 2^23 -- all d coordinates, the masked tail takes part.  The
+    real dot products of a group are equal; every float32 product rounds.  Returns as contest_l2."""
+    base = np.empty((groups * per_group, d), np.int64)
+    for g in range(groups):
+        v = _ints(rng, (d,), -(1 << 23) + 1, 1 << 23)
+        base[g * per_group:(g + 1) * per_group] = _permuted_rows(rng, v, per_group, d)
+    f = lambda a: (a.astype(np.float32) / np.float32(1 << 23)).astype(np.float32)
+    queries = f(np.full((groups, d), 11184811, np.int64))
+    return f(base), queries, np.repeat(np.arange(groups, dtype=np.int64), per_group)
+
+
 def knn_bruteforce(x, k, block=512):
     """Exact-enough kNN lists (float64 distances, ties by id); excludes self.  Generator-side
     helper only: its output is an *input* (and is committed where bit-portability matters)."""
@@ -89,7 +167,17 @@ def random_graph(rng, n, deg_lo, deg_hi):
     return lists_to_csr(lists)
 
 
-KAT_DIMS = list(range(0, 41)) + [45, 96, 128, 200, 257, 960]
+def contest_graph(rng, groups, per_group, deg_lo, deg_hi):
+    """A random_graph per contest group, offset to the group's rows: the groups are disconnected components, so a
+    walk entered inside a group returns candidates of that group only."""
+    lists = []
+    for g in range(groups):
+        off, nbr = random_graph(rng, per_group, deg_lo, deg_hi)
+        lists += [nbr[int(off[i]):int(off[i + 1])] + np.uint32(g * per_group) for i in range(per_group)]
+    return lists_to_csr(lists)
+
+
+KAT_DIMS =list(range(0, 41)) + [45, 96, 128, 200, 257, 960]
 
 
 def kat_pairs():

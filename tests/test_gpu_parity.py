@@ -426,13 +426,17 @@ def test_projection_of_batches_in_flight_small_footprint_kernel(g, orc):
     the big-tile kernel: q_low bit patterns and answers of deferred calls equal the oracle's for input widths with every
     tail rule (d % 8 = 0 / 4, a hidden width that is no multiple of the block's 16 neurons), batch sizes that are no
     multiple of the block's 64 queries, with the kernel forced onto small batches (knob "mlp_small") and at its default
-    threshold."""
+    threshold.  The knob is the smallest batch that takes the kernel and 32 times the knob the largest, so 64 serves the batches
+    of 300 .. 1 000 here (the value 1 this test used to set served batches of up to 32: none of these); the kernel has no profile
+    name of its own -- that it ran shows in the slab kernel, which these deferred calls take otherwise, not being reported.  (The
+    4 500-query batch at the default threshold is served by mlp_net_kernel; tests/test_gpu_rounding.py runs the small-footprint
+    kernel on inexact inputs.)"""
     import torch
     dev = torch.device("cuda:0")
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     lib = g.load_library()
     try:
-        for si, (d, dh, nq, small) in enumerate(((40, 64, 1000, 1), (44, 72, 777, 1), (132, 136, 300, 1), (64, 64, 4500, 4096))):
+        for si, (d, dh, nq, small) in enumerate(((40, 64, 1000, 64), (44, 72, 777, 64), (132, 136, 300, 64), (64, 64, 4500, 4096))):
             c, off, nbr, db_low, ent = _oracle_case(orc, 8700 + si, 8000, nq, d, 32, dh)
             want_q = orc.project(c.net, c.queries)
             sref = orc.search_batch(orc_mod.MODE_NET, c.queries, c.base, off, nbr, 48, db_low=db_low, net=c.net, entries=ent, threads=8)
@@ -442,6 +446,8 @@ def test_projection_of_batches_in_flight_small_footprint_kernel(g, orc):
             outs = [ix.search(q, 48, entry_ids=e, want=("q_low",), out={}, flags=g.FLAG_DEFER_JOIN, defer_depth=3) for _ in range(4)]
             ix.join()
             torch.cuda.synchronize()
+            if small == 64:
+                assert ix.profile_read(reset=False)["project_kernel"] == "mlp_layer_kernels", (d, dh, nq)
             for r in outs:
                 assert np.array_equal(gu.bits(r["q_low"].cpu().numpy()), gu.bits(want_q)), (d, dh, nq)
                 assert np.array_equal(r["ids"].cpu().numpy().view(np.uint32), sref["ids"]), (d, dh, nq)
@@ -1726,7 +1732,10 @@ def test_plain_walks_over_wide_rows_two_list_pair_form(g, orc):
     sift (d = 128: 512-byte rows) vectors at beams of more than 128 run on pair-form instances of the two-list kernel
     (walk_reg_big_kernel<0, 24 | 32, ...>: two lanes per neighbour, 12 / 16 sixteen-byte steps each; 512-byte rows from ef = 201 on), rows
     requested before or after the visited test (knob "late_rows"); shorter beams stay on the generic instances.  Candidate lists in pop order, distance bits, hops,
-    dist_calc equal the oracle's; one- and two-pass adjacency rows, k = 1 and k = ef."""
+    dist_calc equal the oracle's; one- and two-pass adjacency rows, k = 1 and k = ef.
+    The vectors are datagen.Case's (coordinates k / 256): every difference, square and partial sum of a distance is exact on them, so
+    the distance bits asserted here hold under ANY summation order -- this test pins the kernel choice, ids, ties and counters; the
+    order of the roundings is pinned on full-mantissa vectors in tests/test_gpu_rounding.py."""
     lib = g.load_library()
     try:
         for si, (d, deg) in enumerate(((96, 30), (128, 30), (128, 50), (96, 50))):
@@ -1783,7 +1792,10 @@ def test_plain_walks_over_long_rows_four_lanes_per_row(g, orc):
     of up to 128, any d at beams beyond the two-list kernels) compute their distances four lanes per row (l2_quad_rows, csrc/walk_lists.h:
     lane j of a quad owns L2Metric::Dist's running sum j).  Candidate lists in pop order, distance bits, hops, dist_calc equal the oracle's:
     step counts that are multiples of sixteen and not (a masked last batch), every kernel family (one- / two-register lists, two-list,
-    LDS list at ef > 1 024, the bitmap forms), more than sixteen new ids in a pass (two rounds)."""
+    LDS list at ef > 1 024, the bitmap forms), more than sixteen new ids in a pass (two rounds).
+    The vectors are datagen.Case's (coordinates k / 256): all arithmetic of a distance is exact on them, so the distance bits asserted
+    here do not depend on which lane owns which running sum or on the order of the final adds -- that is pinned on full-mantissa
+    vectors in tests/test_gpu_rounding.py; this test pins ids, ties, masking and counters."""
     for si, (d, deg, efs) in enumerate(((960, 30, (8, 100, 200)), (300, 30, (40, 300, 1100)), (128, 60, (64, 100)), (132, 30, (64, 200)),
                                         (516, 30, (8, 64)))):
         c, off, nbr, _, ent = _oracle_case(orc, 3100 + si, 3000, 70, d, 8, 8, deg=(2, deg))
@@ -2184,6 +2196,33 @@ def test_host_batches_in_flight(g, orc):
     ids_n[:] = 0xFFFFFFFF
     B._check(lib.gbnns_search_ex(ix._h, C.byref(a)))  # pageable again: the plain synchronous call
     assert np.array_equal(ids_n, want[1]["ids"])
+    ix.close()
+
+
+def test_pageable_host_buffers_in_several_staging_pieces(g, orc):
+    """Pageable HOST buffers (numpy arrays) pass through the workspace's page-locked staging buffer, 2 MB at a time (gbnns.h): inputs
+    and outputs of several pieces -- 40 000 queries of 24 floats in, candidate lists and distances of 10 MB out -- and rows that are
+    padded on the device (d_low = 14: a pitched copy out, more rows than one piece holds) arrive whole; gbnns_project, gbnns_rerank
+    and the search on the same arrays."""
+    c = datagen.Case("stage", 7400, 5000, 40000, 24, 14, 32)
+    rng = np.random.Generator(np.random.PCG64(7401))
+    off, nbr = datagen.random_graph(rng, c.n, 4, 24)
+    db_low = orc.project(c.net, c.base, threads=8)
+    ent = rng.integers(0, c.n, size=c.nq).astype(np.uint32)
+    ix = g.Index(c.base, off, nbr, db_low=db_low, net=c.net)
+    q_low = orc.project(c.net, c.queries, threads=8)
+    assert np.array_equal(gu.bits(ix.project(c.queries)), gu.bits(q_low))
+    ef = 64
+    w = orc.walk(q_low, db_low, off, nbr, ef, entries=ent, threads=8)
+    want = orc.rerank(c.queries, w["ids"], w["count"], c.base, threads=8)
+    r = ix.search(c.queries, ef, entry_ids=ent, want=("hops", "dist_calc", "cand", "cand_dist", "q_low"))
+    assert np.array_equal(gu.bits(r["q_low"]), gu.bits(q_low))
+    assert np.array_equal(r["cand"], w["ids"]) and np.array_equal(gu.bits(r["cand_dist"]), gu.bits(w["dists"]))
+    assert np.array_equal(r["hops"], w["hops"]) and np.array_equal(r["dist_calc"], w["dist_calc"])
+    assert np.array_equal(r["ids"], want)
+    assert np.array_equal(ix.rerank(c.queries, w["ids"], w["count"]), want)
+    r1 = ix.search(c.queries, ef, mode=g.MODE_LOWQ, queries_low=q_low, entry_ids=ent, want=())
+    assert np.array_equal(r1["ids"], want)
     ix.close()
 
 
