@@ -125,6 +125,71 @@ def contest_dot(rng, groups, per_group, d):
     return f(base), queries, np.repeat(np.arange(groups, dtype=np.int64), per_group)
 
 
+def _gd_contest_lists(rng, hubs, rivals):
+    """Node ids and candidate lists of the GD contests.  A cluster is rivals + 2 consecutive ids under a fresh permutation:
+    slot[0] the hub, slot[1] the candidate c, slot[2:] the rivals g_1 .. g_rivals.  Lists (each shuffled: the builder sorts
+    them itself): hub -> all its satellites; g_t -> hub, c and the other g; c -> the hub alone (its distances to the hub and to
+    every g_t are equal in real arithmetic: two of them tie in float32 at two nodes c of three, and a node with a tie is not
+    decided on the device).  Every cluster is a component of its own."""
+    size = rivals + 2
+    slots = np.stack([h * size + rng.permutation(size) for h in range(hubs)])
+    lists = [None] * (hubs * size)
+    for s in slots:
+        lists[s[0]] = s[1:][rng.permutation(size - 1)]
+        lists[s[1]] = s[:1]
+        for t in range(rivals):
+            other = np.concatenate([s[:2 + t], s[3 + t:]])
+            lists[s[2 + t]] = other[rng.permutation(size - 1)]
+    return slots, lists_to_csr(lists)
+
+
+def gd_contest_l2(rng, hubs, d, rivals=4):
+    """The equal-distance contest for hnswlikeGD's pruning test  Dist(c, i) + eps > Dist(c, g)  under L2Metric::Dist.  Per
+    hub i = Q / 2^23 with Q = (96 + m) << 17, m in [0, 12]^d: one candidate c = Q + v with v = 2^19 + r, r in [0, 2^19)^d, and
+    `rivals` nodes g_t = Q + v - pi_t(v), a fresh permutation pi_t each over the 4 * floor(d / 4) coordinates the reference
+    reads (the rest: arbitrary jitter).  All numerators lie in [2^23, 2^24): conversions and differences are exact, c - g_t =
+    pi_t(v), so Dist(c, i) = Dist(c, g_t) in real arithmetic and a few ulp apart in float32 -- which is larger is decided by the
+    order of the roundings alone.  Dist(i, g_t) is about 0.07 Dist(i, c): the g_t sort first (and fill the M / 2 always-linked
+    slots at M = 2 * rivals), c comes last and its survival is the contest; at a g_t, c meets the hub in the same way.
+    Returns base [hubs * (rivals + 2) x d], (offsets, neighbours) of the candidate lists, hub ids [hubs]."""
+    width = 4 * (d // 4)
+    slots, csr = _gd_contest_lists(rng, hubs, rivals)
+    base = np.empty((slots.size, d), np.int64)
+    for s in slots:
+        q = (96 + _ints(rng, (d,), 0, 13)) << 17
+        v = (1 << 19) + _ints(rng, (d,), 0, 1 << 19)
+        base[s[0]] = q
+        base[s[1]] = q + v
+        for t in range(rivals):
+            pv = v - _ints(rng, (d,), -(1 << 19) + 1, 1 << 19)      # (the tail; overwritten where Dist reads)
+            pv[:width] = v[:width][rng.permutation(width)]
+            base[s[2 + t]] = q + v - pv
+    assert base.min() >= (1 << 23) and base.max() < (1 << 24)
+    return (base.astype(np.float32) / np.float32(1 << 23)).astype(np.float32), csr, np.ascontiguousarray(slots[:, 0])
+
+
+def gd_contest_dot(rng, hubs, d, rivals=4):
+    """The same contest under Angular::Dist (d % 8 == 0).  Hub = [x | -y] with x in [2^22, 2^23)^(d/2), y in [1, 2^21)^(d/2)
+    over 2^23; g_t = [-sigma_t(y) | tau_t(x)] with fresh permutations; c = -(11184811 / 2^23) (1, ..., 1).  In real
+    arithmetic Dist(c, hub) = Dist(c, g_t) = 1.333 (sum x - sum y) > 0, every float32 product rounds.  Dist(hub, g_t) is
+    positive and smaller than Dist(hub, c); Dist(g_s, g_t) is negative, so at the hub only the nearest rival survives the
+    pruning (the others are linked by the M / 2 rule) and c faces that one opponent, and in a rival's own list the other
+    rivals fall to the `Dist > eps` filter.  Returns as gd_contest_l2."""
+    assert d % 8 == 0
+    half = d // 2
+    slots, csr = _gd_contest_lists(rng, hubs, rivals)
+    base = np.empty((slots.size, d), np.int64)
+    for s in slots:
+        x = _ints(rng, (half,), 1 << 22, 1 << 23)
+        y = _ints(rng, (half,), 1, 1 << 21)
+        base[s[0]] = np.concatenate([x, -y])
+        base[s[1]] = -11184811
+        for t in range(rivals):
+            base[s[2 + t]] = np.concatenate([-y[rng.permutation(half)], x[rng.permutation(half)]])
+    assert np.abs(base).max() < (1 << 24)
+    return (base.astype(np.float32) / np.float32(1 << 23)).astype(np.float32), csr, np.ascontiguousarray(slots[:, 0])
+
+
 def knn_bruteforce(x, k, block=512):
     """Exact-enough kNN lists (float64 distances, ties by id); excludes self.  Generator-side
     helper only: its output is an *input* (and is committed where bit-portability matters)."""

@@ -11,7 +11,10 @@ space, not L2Metric::Dist's four running sums and ((s0+s1)+s2)+s3, Angular::Dist
     arithmetic, so a re-rank -- which returns ids only -- is decided by the order of the roundings (a wrong order moves
     the winner of 15 % and more of 32-candidate lists) and, among the several candidates tied at the float32 minimum,
     by pop position;
-  * datagen.net_layers_full nets (about 20 significant bits per weight): layer 1 rounds at every step.
+  * datagen.net_layers_full nets (about 20 significant bits per weight): layer 1 rounds at every step;
+  * graph preparation, whose kernels restate the two distances on their own (knn.hip, gd_order.hip): the exact kNN on
+    full-mantissa vectors and on the contests, GD pruning on datagen.gd_contest_l2 / gd_contest_dot, where a hub keeps its
+    candidate or not by a comparison of two distances that are equal in real arithmetic, and on full-mantissa vectors.
 
 tests/test_rounding_fixtures.py proves those shares on the CPU.  Everything here is bit-exact against the CPU oracle;
 nothing takes a tolerance.  The first-pass kernel of every walk is asserted by name where test_gpu_parity.py
@@ -325,3 +328,156 @@ def test_projection_of_full_mantissa_inputs_small_footprint_kernel(g, orc):
     torch.cuda.synchronize()
     assert np.array_equal(gu.bits(pl.cpu().numpy()), gu.bits(orc.project(net, base[:700], threads=8)))
     ix.close()
+
+
+# ---- e. graph preparation: the exact kNN ----------------------------------------------------------------------------
+@pytest.fixture
+def knn_knobs(g):
+    """Sets gbnns_exact_knn's process-wide knobs; the defaults (filter by size, pool from k = 64) come back afterwards."""
+    lib = g.load_library()
+
+    def set_knobs(knn_filter=1, knn_pool_min_k=64):
+        assert lib.gbnns_debug_knob(b"knn_filter", knn_filter) == 0 and lib.gbnns_debug_knob(b"knn_pool_min_k", knn_pool_min_k) == 0
+    try:
+        yield set_knobs
+    finally:
+        lib.gbnns_debug_knob(b"knn_filter", 1)
+        lib.gbnns_debug_knob(b"knn_pool_min_k", 64)
+
+
+_KNN_CACHE = {}
+
+
+def knn_full_mantissa(orc, metric, d, n=2500, nq=257, k=63):
+    """full_mantissa rows and queries (257 queries: the last thread block is partial) and the oracle's k nearest, computed once."""
+    key = (metric, d, n, nq, k)
+    if key not in _KNN_CACHE:
+        rng = _rng(5900 + 2 * d + metric)
+        base, queries = datagen.full_mantissa(rng, n, d), datagen.full_mantissa(rng, nq, d)
+        _KNN_CACHE[key] = (base, queries) + orc.exact_knn(base, queries, k, metric, threads=8)
+    return _KNN_CACHE[key]
+
+
+def _knn_equal(g, base, queries, k, metric, oi, od, key, **kw):
+    """ids and distance bits of g.exact_knn against the first k columns of the oracle's lists."""
+    ids, dist = g.exact_knn(base, queries, k, metric=metric, want_dist=True, **kw)
+    bad = np.flatnonzero((ids != oi[:, :k]).any(axis=1) | (gu.bits(dist) != gu.bits(od[:, :k])).any(axis=1))
+    assert bad.size == 0, (key, k, bad.size, bad[:8].tolist())
+
+
+KNN_SCAN_SHAPES = [(0, 32), (0, 45), (0, 64), (0, 96), (0, 100), (0, 128), (0, 130), (0, 200), (0, 960), (1, 32), (1, 200), (1, 960)]
+
+
+@pytest.mark.parametrize("metric,d", KNN_SCAN_SHAPES, ids=["m%d_d%d" % s for s in KNN_SCAN_SHAPES])
+def test_exact_knn_heap_scan_on_full_mantissa_vectors(g, orc, knn_knobs, metric, d):
+    """gbnns_exact_knn's plain scan (the filter off) on full-mantissa vectors against the oracle: ids and distance bits at k = 1 / 20 /
+    63.  knn_scan_kernel<METRIC, 8 / 16 / 32>: d = 32; 45 (the tail Dist ignores) and 64; 96, 100 (d % 16 != 0) and 128.
+    knn_scan_wide_kernel: d = 130 (d % 4 != 0, rows that are not 16-byte aligned), 200 (a last chunk of two steps) and 960."""
+    base, queries, oi, od = knn_full_mantissa(orc, metric, d)
+    knn_knobs(knn_filter=0)
+    for k in (1, 20, 63):
+        _knn_equal(g, base, queries, k, metric, oi, od, (metric, d))
+
+
+@pytest.mark.parametrize("metric,d", [(0, 32), (0, 200), (1, 32), (1, 200)], ids=lambda v: str(v))
+def test_exact_knn_of_a_set_over_itself_on_full_mantissa_vectors(g, orc, knn_knobs, metric, d):
+    """The kNN lists of a set over itself (self_offset: row i + offset is query i and is left out), in two slices of queries."""
+    n, k = 1500, 20
+    base = datagen.full_mantissa(_rng(6000 + 2 * d + metric), n, d)
+    oi, od = orc.exact_knn(base, base, k, metric, self_offset=0, threads=8)
+    knn_knobs(knn_filter=0)
+    half = n // 2 + 7
+    _knn_equal(g, base, base[:half].copy(), k, metric, oi[:half], od[:half], (metric, d, "first slice"), self_offset=0)
+    _knn_equal(g, base, base[half:].copy(), k, metric, oi[half:], od[half:], (metric, d, "second slice"), self_offset=half)
+
+
+@pytest.mark.parametrize("d", (32, 64, 100, 128))
+def test_exact_knn_behind_the_filter_on_full_mantissa_vectors(g, orc, knn_knobs, d):
+    """The matrix-core filter forced on: the distances come from knn_rescore_kernel<8 / 16 / 32> (k = 20) and, lists on the pool path,
+    from knn_pool_update_kernel (k = 64 and 300 on 2 048 rows -- the path needs n > 4 k -- and k = 7 with knob "knn_pool_min_k" = 1).
+    Against the oracle, not against the other GPU path."""
+    base, queries, oi, od = knn_full_mantissa(orc, 0, d)
+    knn_knobs(knn_filter=2)
+    _knn_equal(g, base, queries, 20, 0, oi, od, (d, "rescore"))
+    pb, pq, pi, pd = knn_full_mantissa(orc, 0, d, n=2048, nq=130, k=300)
+    for k in (64, 300):
+        _knn_equal(g, pb, pq, k, 0, pi, pd, (d, "pool"))
+    knn_knobs(knn_filter=2, knn_pool_min_k=1)
+    _knn_equal(g, pb, pq, 7, 0, pi, pd, (d, "pool, short list"))
+
+
+KNN_CONTEST_SHAPES = [(0, 32), (0, 128), (0, 300), (1, 32), (1, 200)]
+
+
+@pytest.mark.parametrize("metric,d", KNN_CONTEST_SHAPES, ids=["m%d_d%d" % s for s in KNN_CONTEST_SHAPES])
+def test_exact_knn_on_the_contests(g, orc, knn_knobs, metric, d):
+    """The k nearest rows of the contest groups' queries (8 groups x 256 rows equidistant from their query in real arithmetic; every
+    query five times, so that it also sits in other lanes): which rows are returned is decided by the order of the roundings
+    (tests/test_rounding_fixtures.py: a wrong order changes every list) and, among the rows at the k-th float32 distance, by
+    ascending id.  k = 1 .. 257: at 257 a group's rows run out.  L2 at d <= 128 also with the filter forced -- 256 rows at one real
+    distance, with norms far larger than the distance, are the worst case for its c (|q|^2 + |x|^2) slack, and overflow its
+    256-entry candidate lists into the exact fallback at k = 16 -- and with every list on the pool path."""
+    rng = _rng(6100 + 2 * d + metric)
+    base, gq, _ = (datagen.contest_dot if metric else datagen.contest_l2)(rng, GROUPS, PER, d)
+    queries = np.ascontiguousarray(np.tile(gq, (5, 1)))
+    oi, od = orc.exact_knn(base, queries, 257, metric, threads=8)
+    # the contest is one: rows share the 16th float32 distance, so ids decide
+    dist = np.array([[(orc.negdot if metric else orc.l2)(r, q) for r in base] for q in gq], np.float32)
+    shared = (dist == od[:GROUPS, 15:16]).sum(axis=1)
+    assert (shared >= 2).sum() * 2 >= GROUPS, shared
+    modes = [("scan", 0, 64)] + ([("filter", 2, 1 << 20), ("pool", 2, 1)] if metric == 0 and d <= 128 else [])
+    for tag, knn_filter, pool_min_k in modes:
+        knn_knobs(knn_filter=knn_filter, knn_pool_min_k=pool_min_k)
+        for k in (1, 16, 100, 255, 256, 257):
+            _knn_equal(g, base, queries, k, metric, oi, od, (metric, d, tag))
+
+
+# ---- f. graph preparation: GD pruning on the device -----------------------------------------------------------------
+def _gd_equal(g, orc, koff, knbr, x, M, metric, key, host_share=100):
+    """gbnns_build_graph_gd_device against the oracle's hnswlikeGD, reverse edges on and off; at most n / host_share nodes finished
+    on the host."""
+    for rev in (True, False):
+        want_off, want_nbr = orc.hnswlike_gd(koff, knbr, x, M, metric=metric, reverse=rev, threads=8)
+        off, nbr, on_host = g.build_graph_gd_device(koff, knbr, x, M, metric=metric, reverse=rev, threads=8)
+        print("gd", key, M, rev, "on host", on_host, "of", len(x))
+        assert np.array_equal(off, want_off) and np.array_equal(nbr, want_nbr), (key, M, rev)
+        assert on_host <= len(x) // host_share, (key, M, rev, on_host)
+
+
+GD_CONTEST_SHAPES = [(0, 32), (0, 44), (0, 96), (0, 128), (1, 32), (1, 128)]
+
+
+@pytest.mark.parametrize("metric,d", GD_CONTEST_SHAPES, ids=["m%d_d%d" % s for s in GD_CONTEST_SHAPES])
+def test_gd_pruning_on_device_contests(g, orc, metric, d):
+    """gd_prune_kernel on datagen.gd_contest_l2 / gd_contest_dot (300 hubs, 4 rivals): whether a hub keeps its candidate c is
+    Dist(c, hub) + eps > Dist(c, g) between two distances that are equal in real arithmetic -- the order of the roundings decides
+    (tests/test_rounding_fixtures.py: a wrong order changes 10 % and more of the hubs' lists).  The graph equals the oracle's at
+    M = 8 (the rivals fill the M / 2 always-linked slots) and at M = 2 (the loop stops at M kept, after the contest); no more than
+    1 % of the nodes are finished on the host.  d = 44: d % 8 == 4."""
+    base, (koff, knbr), _ = (datagen.gd_contest_dot if metric else datagen.gd_contest_l2)(_rng(6200 + 2 * d + metric), 300, d, 4)
+    for M in (8, 2):
+        _gd_equal(g, orc, koff, knbr, base, M, metric, (metric, d))
+
+
+GD_FULL_SHAPES = [(32, 40, 12, 0), (128, 100, 30, 0), (14, 64, 16, 0), (16, 50, 10, 1)]
+
+
+@pytest.mark.parametrize("d,K,M,metric", GD_FULL_SHAPES, ids=["d%d_K%d_M%d_m%d" % s for s in GD_FULL_SHAPES])
+def test_gd_pruning_on_device_full_mantissa_vectors(g, orc, d, K, M, metric):
+    """gd_prune_kernel on 3 000 full-mantissa vectors with exact K-NN lists from gbnns_exact_knn, cut to ragged lengths and shuffled
+    (the builder sorts them itself): the oracle's graph, and at most 1 % of the nodes on the host.  Negative dot: signs as in
+    test_gd_pruning_on_device, so that some distances are positive."""
+    n = 3000
+    rng = _rng(6300 + d)
+    x = datagen.full_mantissa(rng, n, d)
+    if metric == 1:
+        x = -np.abs(x)
+        x[::2] *= -1.0
+    knn = g.exact_knn(x, x, K, self_offset=0)
+    lists = []
+    for i in range(n):
+        row = knn[i][:int(rng.integers(1, K + 1))].copy()
+        rng.shuffle(row)
+        lists.append(row)
+    koff, knbr = datagen.lists_to_csr(lists)
+    _gd_equal(g, orc, koff, knbr, x, M, metric, (d, K, M, metric))
