@@ -6,11 +6,12 @@
 //   lanes.cpp       gbnns_search_ex and the batches-in-flight machinery (lanes, fork / join events), gbnns_index_wait / _join
 //   search_core.cpp one batch on one lane: workspaces, copies, the kernel sequence
 //   sizing.cpp      the visited-set sizing rule of the first pass (capacity, form, wavefronts per CU)
+//   walk_plan.cpp   which walk kernel instance serves a pass over a shape, and its LDS layout (walk_plan.h; no HIP calls)
 //   pin.cpp         gbnns_host_pin / gbnns_host_unpin and the page registry
 #pragma once
 
 #include "../../include/gbnns.h"
-#include "kernels.h"
+#include "walk_plan.h"
 
 #include <hip/hip_runtime.h>
 
@@ -177,6 +178,7 @@ struct gbnns_index {
     float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *w3 = nullptr, *b3 = nullptr;
     uint32_t ws1 = 0, ws2 = 0, ws3 = 0;
     int cus = 0;                    // compute units of the device (sizes the one-launch projection's query strips)
+    size_t cu_count() const { return cus > 0 ? (size_t)cus : 256; }   // ... for the walk's residency rules (unknown: an MI355X's)
     gbnns_api::Knobs knob{};        // this handle's diagnostic knobs (gbnns_index_knob; start: the process defaults at creation)
     // workspaces: lane 0 serves plain calls on the caller's stream; the batches of deferred calls rotate over
     // lanes 0 .. n_lanes-1, each on its own internal stream (see gbnns_search_ex)
@@ -236,11 +238,12 @@ int flush_join(gbnns_index* ix);
 
 // sizing.cpp: the first pass's visited set for this batch -- sets w.vs_shr / hash_cap / hash_limit / spec_rows / spec_from
 struct FirstPassSizing {
-    bool hot, packed, auto_cap;   // hand-laid-out instance; 24-bit packed ids; capacity chosen by the library (hash_capacity == 0)
+    bool auto_cap;                // capacity chosen by the library (hash_capacity == 0)
     int form;                     // 0 = 4-byte slots, 1 = packed, 2 = quotient
     uint32_t cap;                 // entries
 };
-FirstPassSizing size_first_pass(gbnns_index* ix, WalkParams& w, const gbnns_search_args* a, int ef, int skey, uint32_t nq, bool sync_host);
+FirstPassSizing size_first_pass(gbnns_index* ix, WalkParams& w, const WalkPlan& plan, const gbnns_search_args* a, int ef, int skey, uint32_t nq,
+                                bool sync_host);
 
 // search_core.cpp
 int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_t s, bool sync_host);

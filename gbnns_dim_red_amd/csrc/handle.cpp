@@ -630,6 +630,27 @@ int gbnns_debug_knob(const char* name, int value) {
     return GBNNS_OK;
 }
 
+int gbnns_debug_walk_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef,
+                          uint32_t n_entries, int force_wide, int coop, int late_rows, int spec_rows, int pass, uint32_t rr_reserve,
+                          char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
+    if (!name || name_bytes == 0 || !lds_bytes) return fail(GBNNS_ERR_INVALID, "gbnns_debug_walk_plan: null output");
+    if ((metric != GBNNS_METRIC_L2 && metric != GBNNS_METRIC_NEG_DOT) || dim == 0 || dstride != round_up(dim, 4) || n == 0 || n > 0xFFFFFFFFull ||
+        ell_stride == 0 || ell_stride % 16 || aux_stride % 16 || ef < 1 || n_entries > 4096 || pass < 0 || pass > 2)
+        return fail(GBNNS_ERR_INVALID, "gbnns_debug_walk_plan: not the shape of an index or a search");
+    WalkParams w{};
+    w.dim = dim; w.dstride = dstride; w.n = (uint32_t)n; w.ell_stride = ell_stride; w.ef = ef; w.n_entries = n_entries ? n_entries : 1u;
+    w.aux_ell = aux_stride ? &w.aux_stride : nullptr; w.aux_stride = aux_stride;  // (the plan asks only WHETHER there is an auxiliary graph)
+    w.force_wide = force_wide != 0; w.late_rows = late_rows != 0; w.spec_rows = spec_rows != 0; w.rr_reserve = rr_reserve;
+    const WalkPass wp = pass == 1 ? WalkPass::Bitmap : (pass == 2 ? WalkPass::Retry : WalkPass::First);
+    w.coop = coop && wp == WalkPass::First && plan_walk(w, metric, wp).coop_serves;
+    const WalkPlan plan = plan_walk(w, metric, wp);
+    const char* planned = plan.general_only ? "walk_general_kernel" : walk_plan_name(plan);
+    if (!planned) return fail(GBNNS_ERR_INTERNAL, "gbnns_debug_walk_plan: no kernel instance for the plan");
+    std::snprintf(name, name_bytes, "%s", planned);
+    *lds_bytes = plan.lds_fixed;
+    return GBNNS_OK;
+}
+
 int gbnns_index_knob_get(gbnns_index* ix, const char* name, int* out) {
     if (!ix || !name || !out) return fail(GBNNS_ERR_INVALID, "gbnns_index_knob_get: null argument");
     const Knobs& k = ix->knob;

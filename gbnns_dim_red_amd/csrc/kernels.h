@@ -1,5 +1,6 @@
 // kernels.h -- launch interface between the C-ABI host layer (handle.cpp, lanes.cpp, search_core.cpp, sizing.cpp, graph_api.cpp, pin.cpp) and the gfx950 kernels
-// (the .hip units beside it: walk_hot, walk_l2 / walk_dot / walk_wide, walk_bitmap, walk_general, rerank, mlp, gd_order, knn).  Plain structs of device pointers and sizes; no HIP types besides hipStream_t.
+// (the .hip units beside it: the walk units behind launch_walk, walk_general, rerank, mlp, gd_order, knn).  Plain structs of device pointers and sizes; no HIP
+// types besides hipStream_t.  Which walk instance serves a shape, and its LDS layout, is walk_plan.h's.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -84,34 +85,22 @@ struct WalkParams {
     uint32_t spec_from;      // ... and in the tested-first instances, for the wavefronts from this work item on (the last, partial round
                              // of a launch walks a draining machine: the shorter hop wins there); 0xFFFFFFFF = none
     const uint32_t* order;   // optional [nq]: work item b of a first pass runs query order[b] (a permutation: locality order of a deep batch)
-    int32_t coop;            // 1: the first pass is the two-wavefront walk (walk_coop.hip: kCoopExtraLds more bytes of LDS per query)
+    int32_t coop;            // 1: the first pass is the two-wavefront walk (walk_coop.hip: kCoopExtraLds, walk_plan.h, more bytes of LDS per query)
     int32_t force_wide;      // diagnostic: treat the index as a large one (64-bit offsets, 4-byte visited-set slots)
     unsigned long long* stamps;  // diagnostic builds only (GBNNS_STAMPS): [32] segment cycle sums / histograms
     int32_t stamps_on;           // 1 in diagnostic builds: use the instrumented generic kernel
 };
 
-bool walk_uses_hot(const WalkParams& p, int metric);           // first pass runs walk_hot_kernel
-bool walk_uses_lds_list(const WalkParams& p);                   // result list in LDS (walk_fast_kernel) instead of registers
-size_t walk_fast_lds_bytes(const WalkParams& p, bool hot);
-bool walk_uses_packed(const WalkParams& p);                     // visited set of 24-bit ids, five per 16-byte bucket
 // `form` of a visited set: 0 = 4-byte slots, 1 = five 24-bit ids per 16-byte bucket, 2 = quotient form (seven 16-bit entries)
 size_t walk_hash_bytes(uint32_t entries, int form);             // LDS bytes of a visited set of `entries` ids
 uint32_t walk_hash_entries(size_t bytes, int form);             // ids that fit into `bytes` (whole buckets)
-bool walk_knows_quotient(const WalkParams& p, int metric);      // the first-pass kernel of this shape reads p.vs_shr
-int walk_hash_form(const WalkParams& p, bool hot);              // the form the first pass uses (p.vs_shr chooses 2 for the hot kernels)
-size_t walk_fast_lds_fixed_bytes(int ef, uint32_t dstride, bool hot, bool lds_list = false, int coop = 0);  // everything but the visited set
-                                                                                             // (lds_list: walk_uses_lds_list; coop: WalkParams::coop)
-constexpr size_t kCoopExtraLds = 1280;  // the two-wavefront walk's two 64-word result buffers + three 64-word slots of adjacency words requested ahead (its mailbox lives in the query area)
-bool walk_coop_serves(const WalkParams& p, int metric);   // shape the two-wavefront walk has an instance for (walk_coop.hip)
-hipError_t launch_walk_coop(const WalkParams& p, hipStream_t s);
-hipError_t launch_walk_fast(const WalkParams& p, int metric, hipStream_t s);
-hipError_t launch_walk_retry(const WalkParams& p, int metric, hipStream_t s);
-hipError_t launch_walk_general(const WalkParams& p, int metric, hipStream_t s);
-bool walk_bitmap_uses_reg(const WalkParams& p, int metric);
-size_t walk_bitmap_lds_bytes(const WalkParams& p, int metric);
+// Which instance runs a pass, and on what LDS layout: plan_walk (walk_plan.h).  launch_walk launches the plan's instance (bitmap first pass:
+// `slots` persistent wavefronts) and fails with hipErrorInvalidValue when no unit holds it.
+struct WalkPlan;
+hipError_t launch_walk(const WalkPlan& pl, const WalkParams& p, unsigned slots, hipStream_t s);
+const char* walk_plan_name(const WalkPlan& pl);   // printable name of the plan's instance, template arguments included (no device needed); nullptr: none
 const char* walk_first_pass_name(hipStream_t s);  // (mangled) name of the first-pass kernel this thread launched last
-size_t walk_rr_room(const WalkParams& p, int metric, bool hot, bool bitmap_pass);  // LDS the fused re-rank may stage its query in
-hipError_t launch_walk_bitmap(const WalkParams& p, int metric, unsigned slots, hipStream_t s);  // persistent first pass, HBM bitmaps
+hipError_t launch_walk_general(const WalkParams& p, int metric, hipStream_t s);
 
 // Re-rank (search_function.h:105-125).  One query per wavefront, one candidate per lane.
 struct RerankParams {

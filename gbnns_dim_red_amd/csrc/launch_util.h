@@ -1,16 +1,10 @@
-// launch_util.h -- host-side helpers shared by the kernel families' launchers.
+// launch_util.h -- host-side helpers shared by the kernel families' launchers: the LDS attribute, and the instance tables of the walk units (separate
+// units so that the instantiations build in parallel; which of them serves a shape is plan_walk's business -- walk_plan.cpp -- not theirs).
 #pragma once
 
-#include "kernels.h"
+#include "walk_plan.h"
 
 namespace gbnns {
-
-// Shape served by the walk_hot* kernels (first pass only): L2, 128-byte rows, adjacency rows of one 32-slot pass
-// (walk_hotw*: 33 .. 64 slots, two passes), 32-bit byte offsets.
-static bool walk_off32(const WalkParams& p) {  // "compact" index: every table the walk indexes is < 4 GiB, ids fit 24 bits
-    return !p.force_wide && (uint64_t)p.n * p.dstride * 4 < (1ull << 32) && (uint64_t)p.n * p.ell_stride * 4 < (1ull << 32) &&
-           (!p.aux_ell || (uint64_t)p.n * p.aux_stride * 4 < (1ull << 32)) && p.n <= 0xFFFFFFu;
-}
 
 template <typename K>
 static hipError_t set_lds(K kernel, size_t bytes) {
@@ -20,25 +14,52 @@ static hipError_t set_lds(K kernel, size_t bytes) {
     return hipSuccess;
 }
 
-// Host function of the last first-pass walk kernel this thread launched (profiling: gbnns_profile.walk_kernel); defined in walk_l2.hip.
-extern thread_local const void* g_walk_first_fn;
+// One row of a unit's instance table: the instance (walk_plan.h), its kernel, and the kernel's printable name -- taken from the same
+// expression as the pointer, written with every template argument the way the demangler prints it.
+struct WalkEntry {
+    WalkInstance inst;
+    const void* fn;
+    const char* name;
+};
+#define WALK_KERNEL(...) reinterpret_cast<const void*>(&__VA_ARGS__), #__VA_ARGS__
+// (macro arguments: the instance's fields in the order of the kernel's own template arguments)
+#define WALK_REG(M, S, OFF32, RETRY, R, ONE, AUX) \
+    {{WalkFamily::RegList, M, S, R, OFF32, RETRY, ONE, AUX}, WALK_KERNEL(walk_reg_kernel<M, S, OFF32, RETRY, R, ONE, AUX>)}
+#define WALK_BIG(M, S, OFF32, RETRY, AUX, ONE, LATE) \
+    {{WalkFamily::TwoList, M, S, 4, OFF32, RETRY, ONE, AUX, LATE}, WALK_KERNEL(walk_reg_big_kernel<M, S, OFF32, RETRY, AUX, ONE, LATE>)}
+#define WALK_LDS(M, S, RETRY, PACKED) \
+    {{WalkFamily::LdsList, M, S, 0, false, RETRY, false, false, false, false, PACKED}, WALK_KERNEL(walk_fast_kernel<M, S, RETRY, PACKED>)}
+#define WALK_WIDE(S, LATE) {{WalkFamily::RegWide, 0, S, 0, false, false, false, false, LATE}, WALK_KERNEL(walk_reg_wide_kernel<S, LATE>)}
+// per (metric, steps): the LDS-list kernels; R list registers, and the two-list kernels (+ first pass over one-pass adjacency rows): compact /
+// non-compact index x first pass / retry, the auxiliary-graph hop
+#define WALK_LDS_SET(M, S) WALK_LDS(M, S, false, false), WALK_LDS(M, S, false, true), WALK_LDS(M, S, true, false), WALK_LDS(M, S, true, true)
+#define WALK_REG_SET(M, S, R)                                                                                                       \
+    WALK_REG(M, S, true, false, R, false, false), WALK_REG(M, S, true, true, R, false, false), WALK_REG(M, S, false, false, R, false, false), \
+        WALK_REG(M, S, false, true, R, false, false), WALK_REG(M, S, true, false, R, false, true), WALK_REG(M, S, true, true, R, false, true)
+#define WALK_BIG_SET(M, S)                                                                                                                   \
+    WALK_BIG(M, S, true, false, false, false, false), WALK_BIG(M, S, true, true, false, false, false), WALK_BIG(M, S, false, false, false, false, false), \
+        WALK_BIG(M, S, false, true, false, false, false), WALK_BIG(M, S, true, false, true, false, false), WALK_BIG(M, S, true, true, true, false, false), \
+        WALK_BIG(M, S, true, false, false, true, false)
+// ef <= 64: one list register per lane (+ the loop-free expansion over one-pass adjacency rows); ef <= 128: two; beyond that the two-list
+// kernels; ef > 1 024 (and auxiliary-graph walks over a non-compact index): the list lives in LDS
+#define WALK_GENERIC_SET(M, S) WALK_LDS_SET(M, S), WALK_REG_SET(M, S, 1), WALK_REG(M, S, true, false, 1, true, false), WALK_REG_SET(M, S, 2), WALK_BIG_SET(M, S)
+// (the rows requested after the visited test: one- and two-pass adjacency rows)
+#define WALK_BIG_LATE(S) WALK_BIG(0, S, true, false, false, true, true), WALK_BIG(0, S, true, false, false, false, true)
 
-template <typename K>
-static hipError_t launch_walk_k(K kernel, const WalkParams& p, bool retry, size_t lds, hipStream_t s) {
-    hipError_t e = set_lds(kernel, lds);
-    if (e != hipSuccess) return e;
-    if (!retry) g_walk_first_fn = reinterpret_cast<const void*>(kernel);
-    const unsigned grid = retry ? (unsigned)kRetrySlots : p.nq;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, s, p);
-    return hipGetLastError();
+template <size_t N> static const WalkEntry* find_walk_entry(const WalkEntry (&rows)[N], const WalkInstance& k) {
+    for (const WalkEntry& r : rows)
+        if (r.inst == k) return &r;
+    return nullptr;
 }
 
-// The hand-laid-out instances (walk_hot.hip): the kernel of p's beam class (ef <= 64, <= 128, above), adjacency width and metric.
-hipError_t launch_walk_hot(const WalkParams& p, int metric, hipStream_t s);
-// the walk launchers of the dot-metric and the wide-row (192 / 256-byte, L2) translation units
-hipError_t launch_walk_dot(const WalkParams& p, bool retry, hipStream_t s);
-hipError_t launch_walk_wide(const WalkParams& p, int steps, bool retry, hipStream_t s);
-hipError_t launch_walk_wide2(const WalkParams& p, int steps, bool retry, hipStream_t s);
-hipError_t launch_walk_wide2_list(const WalkParams& p, hipStream_t s);  // 384-byte rows, ef <= 128: pair-form register-list instances (walk_wide3.hip)
+// The units' tables: the entry of an instance, nullptr when the unit does not hold it.  walk_entry (walk_l2.hip) asks them all.
+const WalkEntry* walk_l2_entry(const WalkInstance& k);
+const WalkEntry* walk_dot_entry(const WalkInstance& k);
+const WalkEntry* walk_wide_entry(const WalkInstance& k);
+const WalkEntry* walk_wide2_entry(const WalkInstance& k);
+const WalkEntry* walk_wide3_entry(const WalkInstance& k);
+const WalkEntry* walk_hot_entry(const WalkInstance& k);
+const WalkEntry* walk_coop_entry(const WalkInstance& k);
+const WalkEntry* walk_bitmap_entry(const WalkInstance& k);
 
 }  // namespace gbnns

@@ -61,8 +61,6 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
         if ((rc = L.entries.ensure((size_t)nq * n_ent * 4))) return rc;
         if ((rc = host_copy_in(L, L.entries.p, a->entry_ids, (size_t)nq * n_ent * 4, s))) return rc;
         entries_dev = L.entries.as<uint32_t>();
-    }
-    if (a->entry_ids && host) {
         for (size_t i = 0; i < (size_t)nq * n_ent; ++i)
             if (a->entry_ids[i] >= ix->n) return fail(GBNNS_ERR_INVALID, "entry id %u >= n", a->entry_ids[i]);
     }
@@ -204,30 +202,34 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
     // (at most four queries per CU); measured on the gist shape at ef 200: first-pass kernel 0.487 against 0.526 ms.  NOT with batches in
     // flight: those fill the machine by themselves and are bound by bytes, and the second wavefront's issue slots and speculative rows
     // cost them (1.8 against 2.5 M queries/s).  Knob "coop": 0 never, 1 whenever the shape allows (tests), -1 this rule.
+    // The first pass's instance and LDS layout (walk_plan.h); the instance depends on late / speculative rows, decided below: taken again then.
+    const size_t cus = ix->cu_count();
+    WalkPlan plan = plan_walk(w, ix->metric, WalkPass::First);
     {
         const int knob = ix->knob.coop;
-        const uint32_t cus = (uint32_t)(ix->cus > 0 ? ix->cus : 256);
         const bool in_flight = s == L.stream && L.stream != nullptr;
-        w.coop = 0;
-        if (knob != 0 && n_ent == 1 && !(a->flags & (GBNNS_FLAG_BITMAP_PASS | GBNNS_FLAG_WIDE_INDEX)) && walk_coop_serves(w, ix->metric) &&
-            (knob > 0 || (nq <= 4u * cus && !in_flight)))
+        if (knob != 0 && n_ent == 1 && !(a->flags & (GBNNS_FLAG_BITMAP_PASS | GBNNS_FLAG_WIDE_INDEX)) && plan.coop_serves &&
+            (knob > 0 || (nq <= 4u * cus && !in_flight))) {
             w.coop = 1;
-    }
-    // the first pass's visited set: capacity, form (packed / quotient), the wavefronts per CU it leaves (sizing.cpp)
-    FirstPassSizing fps = size_first_pass(ix, w, a, ef, skey, nq, sync_host);
-    if (w.coop && ix->knob.coop < 0) {
-        // (auto: only when every workgroup of the batch is resident at once -- LDS share per query, eight workgroups of two wavefronts per CU)
-        const size_t per_wg = (walk_fast_lds_bytes(w, false) + kLdsGran - 1) / kLdsGran * kLdsGran;
-        const size_t per_cu = std::min<size_t>(8, per_wg ? kMaxLds / per_wg : 0);
-        if ((size_t)nq > per_cu * (size_t)(ix->cus > 0 ? ix->cus : 256)) {
-            w.coop = 0;
-            fps = size_first_pass(ix, w, a, ef, skey, nq, sync_host);
+            plan = plan_walk(w, ix->metric, WalkPass::First);
         }
     }
-    const bool hot = fps.hot, packed = fps.packed, auto_cap = fps.auto_cap;
-    const int form = fps.form;
-    const uint32_t cap = fps.cap;
-    w.all_general = (walk_fast_lds_bytes(w, hot) > kMaxLds || n_ent > 1) ? 1 : 0;  // several entry points: general kernel only
+    auto first_lds = [&] { return plan.lds_fixed + walk_hash_bytes(w.hash_cap, plan.hash_form(w.vs_shr)); };
+    auto granules = [](size_t bytes) { return (bytes + kLdsGran - 1) / kLdsGran * kLdsGran; };
+    // the first pass's visited set: capacity, form (packed / quotient), the wavefronts per CU it leaves (sizing.cpp)
+    FirstPassSizing fps = size_first_pass(ix, w, plan, a, ef, skey, nq, sync_host);
+    if (w.coop && ix->knob.coop < 0) {
+        // (auto: only when every workgroup of the batch is resident at once -- LDS share per query, eight workgroups of two wavefronts per CU)
+        const size_t per_wg = granules(first_lds());
+        const size_t per_cu = std::min<size_t>(8, per_wg ? kMaxLds / per_wg : 0);
+        if ((size_t)nq > per_cu * cus) {
+            w.coop = 0;
+            plan = plan_walk(w, ix->metric, WalkPass::First);
+            fps = size_first_pass(ix, w, plan, a, ef, skey, nq, sync_host);
+        }
+    }
+    const auto [auto_cap, form, cap] = fps;
+    w.all_general = (first_lds() > kMaxLds || plan.general_only) ? 1 : 0;
     // Fused re-rank: with a register-list first pass (ef <= 512; and its retry / general successors) every
     // wavefront re-ranks its own query when its walk ends; no re-rank launch.  Needs the pair form
     // (d % 8 == 0) and room for the original-space query in the walk kernels' LDS.
@@ -235,6 +237,7 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
     // keeps its visited sets as bitmaps in HBM and runs as many persistent wavefronts as the LDS holds result
     // lists (LDS-list kernel); taken when that at least doubles the resident wavefronts.
     size_t bitmap_per_cu = 0;
+    WalkPlan bitmap_plan{};
     // (L2: d % 8 == 4 too -- glove's 300 -- the pair form's last 16-byte step is the even lane's alone)
     const bool pair_form = ix->d % 8 == 0 || (ix->d % 4 == 0 && ix->metric == GBNNS_METRIC_L2);
     const bool want_fuse = !plain && pair_form && !(a->flags & GBNNS_FLAG_NO_FUSED_RERANK);
@@ -257,11 +260,10 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
         const int min_ef = min_ef_env ? min_ef_env : (rows576 ? 450 : (form == 2 ? 480 : 385));
         const bool forced = (a->flags & GBNNS_FLAG_BITMAP_PASS) != 0;  // diagnostic: whatever ef and batch size
         if (!w.all_general && !w.coop && (ef >= min_ef || forced) && !(a->flags & GBNNS_FLAG_WIDE_INDEX) && (a->hash_capacity == 0 || forced)) {
-            const size_t gran = kLdsGran;
-            const size_t cus = ix->cus > 0 ? (size_t)ix->cus : 256;  // (the device's, as in sizing.cpp: the slot counts below follow it)
-            const size_t per_wave = (walk_bitmap_lds_bytes(w, ix->metric) + gran - 1) / gran * gran;
+            bitmap_plan = plan_walk(w, ix->metric, WalkPass::Bitmap);
+            const size_t per_wave = granules(bitmap_plan.lds_fixed);   // (the slot counts below follow the device's CU count, as in sizing.cpp)
             const size_t per_cu = std::min<size_t>(rows576 ? 8 : 32, kMaxLds / per_wave);  // (576-byte rows: 223 registers, two wavefronts per SIMD)
-            const size_t table_waves = std::min<size_t>(32, kMaxLds / ((walk_fast_lds_bytes(w, hot) + gran - 1) / gran * gran));
+            const size_t table_waves = std::min<size_t>(32, kMaxLds / granules(first_lds()));
             // ... and only when the batch is deeper than 1.5 rounds of the wavefronts the table would allow (a
             // 1 000-query batch is resident at once either way, and the register list is faster per hop)
             // ... or, short of that, when the table needs a second round and the bitmap pass holds the whole batch at once
@@ -276,7 +278,7 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
         // least five wavefronts per CU by LDS (ef 300 / 400 / 600: 4.15 / 5.36 / 10.4 against 5.08 / 6.74 / 10.7 ms; ef 800 / 1 000, four and
         // fewer per CU: 18.2 / 23.8 against 17.4 / 22.3) on a batch that fills the machine
         const int knob = ix->knob.late_rows;
-        const size_t per_wave = (walk_fast_lds_bytes(w, hot) + kLdsGran - 1) / kLdsGran * kLdsGran;
+        const size_t per_wave = granules(first_lds());
         const size_t lds_waves = per_wave ? kMaxLds / per_wave : 0;
         // ... and 192-byte rows at ef <= 64 (walk_reg_wide_kernel<12>, the reference's deep 96 -> 48: 2.24 GB moved for 1.62 GB of
         // algorithmic bytes at ef = 40, 6.5 TB/s; 0.351 -> 0.342 ms alone, 29.4 -> 30.9 M queries/s in flight; its longer beams: no gain)
@@ -289,10 +291,12 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
         const bool bitmap_late = bitmap_per_cu != 0 && w.dim == 144u && l2;
         w.late_rows = knob < 0 ? ((auto_late || bitmap_late) ? 1 : 0) : knob;
     }
-    // (the ef > 128 hot instance keeps its result list in LDS and stages the re-rank query in the visited-set area)
-    const size_t rr_room = walk_rr_room(w, ix->metric, hot, bitmap_per_cu != 0);
-    const bool fuse = !walk_uses_lds_list(w) && (!bitmap_per_cu || walk_bitmap_uses_reg(w, ix->metric)) && want_fuse && !w.all_general &&
-                      (size_t)ix->d_pad * 4 <= rr_room;
+    plan = plan_walk(w, ix->metric, WalkPass::First);
+    if (bitmap_per_cu) bitmap_plan = plan_walk(w, ix->metric, WalkPass::Bitmap);
+    const WalkPlan& first = bitmap_per_cu ? bitmap_plan : plan;
+    // (the two-list instances keep their result list in LDS and stage the re-rank query in the visited-set area)
+    const size_t rr_room = first.rr_room(walk_hash_bytes(w.hash_cap, first.hash_form(w.vs_shr)));
+    const bool fuse = !first.lds_list && want_fuse && !w.all_general && (size_t)ix->d_pad * 4 <= rr_room;
     if (fuse) {
         w.rr_q = q_dev; w.rr_qstride = ix->d; w.rr_db = ix->db; w.rr_dstride = ix->d_pad; w.rr_dim = ix->d;
         w.rr_n = (uint32_t)ix->n; w.rr_out = out_dev; w.rr_metric = ix->metric;
@@ -308,26 +312,25 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
     }
     bool bitmap_pass = false;
     if (bitmap_per_cu) {
-        const size_t cus = ix->cus > 0 ? (size_t)ix->cus : 256;
         if ((rc = L.fp_bitmap.ensure(bitmap_per_cu * cus * (size_t)bitmap_words * 4))) return rc;
         w.fp_bitmap = L.fp_bitmap.as<uint32_t>();
         w.fp_cursor = ctrl + 6;
-        HIP_TRY(launch_walk_bitmap(w, ix->metric, (unsigned)(bitmap_per_cu * cus), s));
+        HIP_TRY(launch_walk(bitmap_plan, w, (unsigned)(bitmap_per_cu * cus), s));
         bitmap_pass = true;
     }
     if (!w.all_general) {
-        if (!bitmap_pass) HIP_TRY(launch_walk_fast(w, ix->metric, s));
+        if (!bitmap_pass) HIP_TRY(launch_walk(plan, w, 0, s));
         // retry pass: hand-overs of the first pass, one wavefront per CU with all the LDS
         WalkParams w2 = w;
         w2.vs_shr = 0;  // (the retry kernels keep the packed form)
         w2.coop = 0;    // (... and one wavefront per query)
-        const size_t gran = kLdsGran;
-        w2.hash_cap = walk_hash_entries(kMaxLds / gran * gran - walk_fast_lds_fixed_bytes(ef, w.dstride, false, walk_uses_lds_list(w)), packed);
+        const WalkPlan retry = plan_walk(w2, ix->metric, WalkPass::Retry);
+        w2.hash_cap = walk_hash_entries(kMaxLds / kLdsGran * kLdsGran - retry.lds_fixed, retry.hash_form(0));
         w2.hash_limit = w2.hash_cap - w2.hash_cap / 16;
         if (skip_retry) {
             // nothing to launch
         } else if (w2.hash_cap > cap) {
-            HIP_TRY(launch_walk_retry(w2, ix->metric, s));
+            HIP_TRY(launch_walk(retry, w2, 0, s));
         } else {
             HIP_TRY(hipMemcpyAsync(ctrl + 3, ctrl, 4, hipMemcpyDeviceToDevice, s));  // nothing to gain: A -> B
             HIP_TRY(hipMemcpyAsync(w.ovf2_list, w.ovf_list, (size_t)nq * 4, hipMemcpyDeviceToDevice, s));
@@ -347,6 +350,9 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
             if (pos != std::string::npos) name = name.substr(pos);
             pos = name.rfind("(gbnns::WalkParams)");
             if (pos != std::string::npos) name = name.substr(0, pos);
+            const char* planned = walk_plan_name(first);
+            if (!planned || name != planned)
+                return fail(GBNNS_ERR_INTERNAL, "first pass: planned %s, launched %s", planned ? planned : "(none)", name.c_str());
         }
         std::snprintf(ix->acc.walk_kernel, sizeof(ix->acc.walk_kernel), "%s", name.c_str());
     }

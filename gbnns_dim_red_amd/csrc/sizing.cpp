@@ -9,17 +9,17 @@ using namespace gbnns;
 
 namespace gbnns_api {
 
-FirstPassSizing size_first_pass(gbnns_index* ix, WalkParams& w, const gbnns_search_args* a, int ef, int skey, uint32_t nq, bool sync_host) {
-    const bool hot = walk_uses_hot(w, ix->metric);
-    const bool packed = walk_uses_packed(w);
-    const size_t lds_fixed = walk_fast_lds_fixed_bytes(ef, w.dstride, hot, walk_uses_lds_list(w), w.coop);
+FirstPassSizing size_first_pass(gbnns_index* ix, WalkParams& w, const WalkPlan& plan, const gbnns_search_args* a, int ef, int skey, uint32_t nq,
+                                bool sync_host) {
+    const bool packed = plan.packed;
+    const size_t lds_fixed = plan.lds_fixed;
     // The hot first pass may keep its visited set in the quotient form (walk_hot.hip, GBNNS_VS_ASM: seven 16-bit entries
     // per bucket instead of five 24-bit ids): ids are told apart inside a home bucket by W - floor(log2 buckets) <= 13
     // bits (n <= 2^W), so the table needs at least 2^(W-13) buckets.
     uint32_t idbits = 1;
     while (idbits < 32 && (1ull << idbits) < ix->n) ++idbits;
     const bool quotient_on = ix->knob.quotient != 0;  // tuning / A-B runs, tests: gbnns_debug_knob
-    const bool vs_ok = walk_knows_quotient(w, ix->metric);
+    const bool vs_ok = plan.knows_quotient;
     constexpr uint32_t kStashBuckets = 4;  // (walk_common.h: the table's last four "buckets" are the stash)
     const uint32_t quotient_min = 7u * ((idbits > 13 ? 1u << (idbits - 13) : 1u) + kStashBuckets + 8u);  // entries (>= 8 real buckets: probe steps of up to 8)
     uint32_t cap;
@@ -30,7 +30,7 @@ FirstPassSizing size_first_pass(gbnns_index* ix, WalkParams& w, const gbnns_sear
     const int knob_waves = ix->knob.max_waves;
     // (the two-wavefront walk of a lone small batch: as many workgroups per CU as the batch puts there, the table takes the rest
     // of the LDS -- shorter probe sequences, gist shape ef 200 / 400: 0.486 / 0.933 against 0.490 / 0.945 ms)
-    const size_t cus = (size_t)(ix->cus > 0 ? ix->cus : 256);
+    const size_t cus = ix->cu_count();
     const size_t coop_cap = std::min<size_t>(32, std::max<size_t>(1, ((size_t)nq + cus - 1) / cus));
     const size_t wave_cap = knob_waves > 0 ? (size_t)knob_waves : (w.coop ? coop_cap : 32);
     // visited-set capacity for `need` entries in the given form, and the wavefronts per CU it leaves (0: no fit)
@@ -112,7 +112,7 @@ FirstPassSizing size_first_pass(gbnns_index* ix, WalkParams& w, const gbnns_sear
         // already-visited ids cost nothing there) -- walk_hot_kernel 0.320 -> 0.307 ms, 0.68 -> 0.71 of the peak.  Only for a
         // batch that runs alone: with batches in flight the neighbours fill that tail and the extra rows cost 2 - 4 %.
         // wavefront slots of the device (ef <= 64 hot instances: 8 per SIMD, 32 per CU; the CU count is the device's, not a literal)
-        const uint32_t slots = (uint32_t)(ix->cus > 0 ? ix->cus : 256) * 32u;
+        const uint32_t slots = (uint32_t)ix->cu_count() * 32u;
         const int knob = ix->knob.spec_tail;
         w.spec_from = 0xFFFFFFFFu;
         if (sync_host && knob > 0 && nq > slots && nq % slots != 0 && nq % slots <= slots * (uint32_t)knob / 100u) w.spec_from = nq - nq % slots;
@@ -126,7 +126,7 @@ FirstPassSizing size_first_pass(gbnns_index* ix, WalkParams& w, const gbnns_sear
         const uint32_t slots = cap - 7u * kStashBuckets;
         w.hash_limit = slots - slots / 16;
     }
-    return FirstPassSizing{hot, packed, auto_cap, form, cap};
+    return FirstPassSizing{auto_cap, form, cap};
 }
 
 }  // namespace gbnns_api

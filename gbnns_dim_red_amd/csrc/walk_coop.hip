@@ -666,36 +666,11 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     coop_barrier();   // G
 }
 
-template <int STEPS>
-hipError_t launch_coop_t(const WalkParams& p, size_t lds, hipStream_t s) {
-    auto go = [&](auto kernel) -> hipError_t {
-        hipError_t e = set_lds(kernel, lds);
-        if (e != hipSuccess) return e;
-        g_walk_first_fn = reinterpret_cast<const void*>(kernel);
-        hipLaunchKernelGGL(kernel, dim3(p.nq), dim3(128), lds, s, p);
-        return hipGetLastError();
-    };
-    return p.late_rows ? go(walk_coop_kernel<STEPS, true>) : go(walk_coop_kernel<STEPS, false>);
-}
-
 }  // namespace
 
-bool walk_coop_serves(const WalkParams& p, int metric) {
-    const bool rows = p.dim == p.dstride && (p.dim == 32u || p.dim == 48u || p.dim == 64u);
-    // (a visited set in the packed form: no id may look like a half-written slot -- see visited_test_mask_packed)
-    return metric == 0 && rows && p.ef > kHot2MaxEf && p.ef <= kRegListMaxEf && walk_off32(p) && p.n < 0xFF0000u && !p.aux_ell && p.ell_stride <= 32u &&
-           p.n_entries <= 1u;
-}
-
-hipError_t launch_walk_coop(const WalkParams& p, hipStream_t s) {
-    if (p.nq == 0) return hipSuccess;
-    if (!walk_coop_serves(p, 0)) return hipErrorInvalidValue;
-    const size_t lds = walk_fast_lds_bytes(p, false);
-    switch (p.dim) {
-        case 32: return launch_coop_t<8>(p, lds, s);
-        case 48: return launch_coop_t<12>(p, lds, s);
-        default: return launch_coop_t<16>(p, lds, s);
-    }
-}
+// walked rows of 128 / 192 / 256 bytes; LATE: the rows requested after the scout's visited test
+#define WALK_COOP(S, LATE) {{WalkFamily::Coop, 0, S, 0, false, false, false, false, LATE}, WALK_KERNEL(walk_coop_kernel<S, LATE>)}
+static const WalkEntry kEntries[] = {WALK_COOP(8, false), WALK_COOP(8, true), WALK_COOP(12, false), WALK_COOP(12, true), WALK_COOP(16, false), WALK_COOP(16, true)};
+const WalkEntry* walk_coop_entry(const WalkInstance& k) { return find_walk_entry(kEntries, k); }
 
 }  // namespace gbnns

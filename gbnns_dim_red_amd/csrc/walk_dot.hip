@@ -1,11 +1,13 @@
-// walk_dot.hip -- the generic walks with the negative-dot metric (Angular::Dist).
-#include "walk_launch.h"
+// walk_dot.hip -- the generic walks with the negative-dot metric (Angular::Dist): 128-byte rows in the pair form, and run-time length.
+#include "launch_util.h"
+#include "walk_generic.h"
 
 namespace gbnns {
 
-hipError_t launch_walk_dot(const WalkParams& p, bool retry, hipStream_t s) {
-    if (p.dstride == p.dim && p.dim == 32) return launch_fast_t<1, 8>(p, retry, s);  // 128-byte rows: pair form
-    return launch_fast_t<1, 0>(p, retry, s);
-}
+static const WalkEntry kEntries[] = {
+    WALK_GENERIC_SET(1, 8),
+    WALK_GENERIC_SET(1, 0),
+};
+const WalkEntry* walk_dot_entry(const WalkInstance& k) { return find_walk_entry(kEntries, k); }
 
 }  // namespace gbnns

@@ -209,7 +209,7 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
     const uint32_t cap = p.hash_cap;  // any size: slot = mulhi(id * C, cap)
     const uint32_t hash_lds = (uint32_t)(size_t)((__attribute__((address_space(3))) unsigned char*)reinterpret_cast<unsigned char*>(hash));
 
-    // OFF32 instantiations serve "compact" indexes (tables < 4 GiB and n < 2^24, walk_off32): 32-bit byte
+    // OFF32 instantiations serve "compact" indexes (tables < 4 GiB and n < 2^24: WalkInstance::off32, walk_plan.cpp): 32-bit byte
     // offsets and the packed visited set (24-bit ids, five per 16-byte bucket)
     constexpr bool packed = OFF32;
     // (first pass of a compact index: the host may ask for the quotient form of the table -- p.vs_shr, GBNNS_VS_ASM)

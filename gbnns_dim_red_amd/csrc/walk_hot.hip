@@ -1001,20 +1001,17 @@ __global__ __launch_bounds__(64) void walk_hot_dot_big_kernel(WalkParams p) {
 
 }  // namespace
 
-hipError_t launch_walk_hot(const WalkParams& p, int metric, hipStream_t s) {
-    const size_t lds = walk_fast_lds_bytes(p, true);
-    const bool wide = p.ell_stride > 32u;  // adjacency rows of 33 .. 64 slots: the two-pass instances
-    if (p.ef <= 64) {
-        if (metric == 1) return wide ? launch_walk_k(walk_hot_dot_kernel<1, true>, p, false, lds, s) : launch_walk_k(walk_hot_dot_kernel<1, false>, p, false, lds, s);
-        if (!wide && p.spec_rows && !GBNNS_HOT1_SPEC) return launch_walk_k(walk_hot_spec_kernel, p, false, lds, s);
-        return wide ? launch_walk_k(walk_hotw_kernel, p, false, lds, s) : launch_walk_k(walk_hot_kernel, p, false, lds, s);
-    }
-    if (p.ef <= kHot2MaxEf) {
-        if (metric == 1) return wide ? launch_walk_k(walk_hot_dot_kernel<2, true>, p, false, lds, s) : launch_walk_k(walk_hot_dot_kernel<2, false>, p, false, lds, s);
-        return wide ? launch_walk_k(walk_hotw2_kernel, p, false, lds, s) : launch_walk_k(walk_hot2_kernel, p, false, lds, s);
-    }
-    if (metric == 1) return wide ? launch_walk_k(walk_hot_dot_big_kernel<true>, p, false, lds, s) : launch_walk_k(walk_hot_dot_big_kernel<false>, p, false, lds, s);
-    return wide ? launch_walk_k(walk_hotw_big_kernel, p, false, lds, s) : launch_walk_k(walk_hot_big_kernel, p, false, lds, s);
-}
+// The instances by beam class (ef <= 64, <= 128, above: 1 / 2 list registers, the two-list form), adjacency width (one pass, or walk_hotw*: two)
+// and metric; walk_hot_spec_kernel where the plan asks for the rows before the visited test.
+#define WALK_HOT(M, R, ONE, SPEC, ...) {{WalkFamily::Hot, M, 0, R, false, false, ONE, false, false, SPEC}, WALK_KERNEL(__VA_ARGS__)}
+static const WalkEntry kEntries[] = {
+    WALK_HOT(0, 1, true, false, walk_hot_kernel), WALK_HOT(0, 1, true, true, walk_hot_spec_kernel), WALK_HOT(0, 1, false, false, walk_hotw_kernel),
+    WALK_HOT(0, 2, true, false, walk_hot2_kernel), WALK_HOT(0, 2, false, false, walk_hotw2_kernel),
+    WALK_HOT(0, 4, true, false, walk_hot_big_kernel), WALK_HOT(0, 4, false, false, walk_hotw_big_kernel),
+    WALK_HOT(1, 1, true, false, walk_hot_dot_kernel<1, false>), WALK_HOT(1, 1, false, false, walk_hot_dot_kernel<1, true>),
+    WALK_HOT(1, 2, true, false, walk_hot_dot_kernel<2, false>), WALK_HOT(1, 2, false, false, walk_hot_dot_kernel<2, true>),
+    WALK_HOT(1, 4, true, false, walk_hot_dot_big_kernel<false>), WALK_HOT(1, 4, false, false, walk_hot_dot_big_kernel<true>),
+};
+const WalkEntry* walk_hot_entry(const WalkInstance& k) { return find_walk_entry(kEntries, k); }
 
 }  // namespace gbnns

@@ -5,6 +5,7 @@
 #pragma once
 
 #include "walk_common.h"
+#include "walk_plan.h"
 
 namespace gbnns {
 
@@ -31,15 +32,7 @@ __device__ __forceinline__ uint64_t clear_bit64(uint64_t m, int bit) {  // wave-
     return m;
 }
 
-// Layout of the one-register hot instances (ef <= 64), A/B switches: GBNNS_HOT1_QLDS = the query is re-read from LDS every
-// hop (64 vector registers: 8 wavefronts per SIMD) instead of living in 16 registers (72: 7 per SIMD); GBNNS_HOT1_SPEC = the
-// rows are requested before the visited test (speculatively, for every valid slot) instead of after it (new ids only).
-#ifndef GBNNS_HOT1_QLDS
-#define GBNNS_HOT1_QLDS 1
-#endif
-#ifndef GBNNS_HOT1_SPEC
-#define GBNNS_HOT1_SPEC 0
-#endif
+// (GBNNS_HOT1_QLDS / GBNNS_HOT1_SPEC, the layout switches of the one-register hot instances: walk_plan.h, with the other layout constants)
 // GBNNS_HOT1_PF2_IN_MERGE = 1: the second prefetch's closest survivor comes out of the merge's rank loop (one scalar minimum per
 // survivor) instead of a DPP butterfly in front of the merge -- 20 instructions per hop less, and the prefetch ~60
 // instructions later: measured 1 - 2 % SLOWER on the SIFT / GloVe shapes at ef = 36 / 64 (profiles/r04_ab.txt), so off.
@@ -49,8 +42,6 @@ __device__ __forceinline__ uint64_t clear_bit64(uint64_t m, int bit) {  // wave-
 #ifndef GBNNS_HOT1_PF2_IN_MERGE
 #define GBNNS_HOT1_PF2_IN_MERGE 0
 #endif
-constexpr int kRegTieCap = 16;       // tie list of the register kernel (LDS, 128 B)
-constexpr int kRegListMaxEf = 1024;  // largest ef served by the register-list / two-list kernels (beyond: result list as one sorted LDS array)
 
 __device__ __forceinline__ uint32_t dpp_wave_shr1(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x138, 0xf, 0xf, false);
@@ -438,7 +429,6 @@ __device__ __forceinline__ bool reg_offer(uint32_t dl, uint32_t nlo, RegList<R>&
 #define GBNNS_MERGE_SHI "s47"
 #define GBNNS_MERGE_SPAIR "s[46:47]"
 #endif
-constexpr int kRegStageSlots = 66;   // merge scatter buffer: ranks 0..ef (ef <= 64), padded to 16 B
 
 // WANT_MIN: the loop also keeps the smallest survivor distance key (one scalar instruction per survivor) and hands it to
 // `after_ranks(dmin)` right behind the loop -- the hot instance requests its second prefetch there (round 4; before, a
@@ -651,11 +641,7 @@ __device__ __forceinline__ uint32_t reg_id_at_rank(const RegList<R>& L, int rank
 // the union holds the same keys as the single list did, selection and eviction see the same total order; the
 // sequential fallback on a boundary tie and the tie list work as before.  Nothing depends on R any more: one kernel.
 
-constexpr int kBigMaxEf = kRegListMaxEf;  // (the structure itself reaches 64 chunks = 4 096 entries: one mask lane per chunk)
-#ifndef GBNNS_HOT2_MAX
-#define GBNNS_HOT2_MAX 128  // (64: experiments with the two-list kernels from ef = 65 on)
-#endif
-constexpr int kHot2MaxEf = GBNNS_HOT2_MAX;  // up to here the two-register lists (walk_hot_one<2>, walk_reg_one<2>) are the faster ones
+// (kBigMaxEf, kHot2MaxEf -- up to there the two-register lists are the faster ones: walk_plan.h)
 
 __device__ __forceinline__ uint64_t dpp_wave_shl1_u64(uint64_t v) {  // lane j <- lane j + 1
     const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, 0x130, 0xf, 0xf, false);
@@ -663,18 +649,7 @@ __device__ __forceinline__ uint64_t dpp_wave_shl1_u64(uint64_t v) {  // lane j <
     return ((uint64_t)hi << 32) | lo;
 }
 
-// LDS of the instance besides the visited set: [tie list][front-merge buffer: 66 keys][base list: ef_pad keys]
-// [flush flags: ef_pad + 64 bytes], ef_pad = ef rounded up to 64.  The flush flags live inside the front-merge buffer
-// when they fit (ef <= 448: the two are never in use at the same time) -- at ef = 140 .. 180 those 256 bytes are what
-// separates 14 / 13 / 12 resident wavefronts per CU from 15 / 14 / 13.
-__host__ __device__ __forceinline__ constexpr bool big_list_flags_in_stage(int ef) {
-    return (size_t)((ef + 63) / 64 * 64) + 64 <= (size_t)kRegStageSlots * 8;
-}
-__host__ __device__ __forceinline__ constexpr size_t big_list_fixed_bytes(int ef) {
-    return (size_t)kRegTieCap * 8 + (size_t)kRegStageSlots * 8 + (size_t)((ef + 63) / 64 * 64) * 8 +
-           (big_list_flags_in_stage(ef) ? 0 : (size_t)((ef + 63) / 64 * 64) + 64);
-}
-
+// (LDS of the instance besides the visited set: big_list_fixed_bytes, walk_plan.h)
 struct BigList {
     uint64_t* tie;          // [kRegTieCap]
     uint64_t* stage;        // [kRegStageSlots] scatter buffer of the front-list merge

@@ -1,0 +1,119 @@
+// walk_plan.cpp -- plan_walk: the one mapping from (shape, beam, pass) to a walk kernel instance and its LDS layout (walk_plan.h).  Plain host code.
+// The tuning rules (when the two-wavefront walk, the bitmap pass, late or speculative rows are WANTED) stay in search_core.cpp and sizing.cpp.
+#include "walk_plan.h"
+#include <cstdlib>
+
+namespace gbnns {
+
+const WalkEnv& walk_env() {
+    static const WalkEnv env{!getenv("GBNNS_WIDE2") || atoi(getenv("GBNNS_WIDE2")) != 0, getenv("GBNNS_STAMPS_GENERIC") != nullptr};  // read once
+    return env;
+}
+
+// "compact" index: every table the walk indexes is < 4 GiB (32-bit byte offsets) and ids fit 24 bits
+static bool compact_index(const WalkParams& p) {
+    return !p.force_wide && (uint64_t)p.n * p.dstride * 4 < (1ull << 32) && (uint64_t)p.n * p.ell_stride * 4 < (1ull << 32) &&
+           (!p.aux_ell || (uint64_t)p.n * p.aux_stride * 4 < (1ull << 32)) && p.n <= 0xFFFFFFu;
+}
+
+// LDS of one wavefront without the visited set.  Register kernels: tie list + merge buffer + query (the hot kernel stages it inside the merge buffer).
+static size_t lds_fixed_bytes(int ef, uint32_t dstride, bool hot, bool lds_list, bool coop) {
+    if (coop) return big_list_fixed_bytes(ef) + (size_t)dstride * 4 + kCoopExtraLds;  // (walk_coop.hip: the two-list layout + result buffers)
+    if (hot)  // tie list + merge buffer of 1 / 2 list registers; ef > 128: + the base list and the flush's flag bytes (walk_hot_big)
+        return ef <= 64 ? (size_t)kRegTieCap * 8 + (size_t)kRegStageSlots * 8 + (GBNNS_HOT1_QLDS ? 128 : 0)   // (+ the query, re-read every hop)
+                        : (ef <= kHot2MaxEf ? (size_t)kRegTieCap * 8 + (size_t)(64 * 2 + 2) * 8 : big_list_fixed_bytes(ef));
+    if (!lds_list) {  // tie list + merge buffer (ranks 0..ef of the 1 / 2-register list) + query
+        if (ef > kHot2MaxEf) return big_list_fixed_bytes(ef) + (size_t)dstride * 4;  // walk_reg_big_one
+        return (size_t)kRegTieCap * 8 + (size_t)(64 * (ef <= 64 ? 1 : 2) + 2) * 8 + (size_t)dstride * 4;
+    }
+    return (((size_t)ef + 63) & ~(size_t)63) * 8 + (size_t)kTieCap * 8 + (size_t)dstride * 4;  // the list, padded to 64 entries + tie list + query
+}
+
+WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv& env) {
+    const bool off32 = compact_index(p), aux = p.aux_ell != nullptr, retry = pass == WalkPass::Retry;
+    const int ef = p.ef, regs = ef <= 64 ? 1 : (ef <= kHot2MaxEf ? 2 : 4);
+    const uint32_t rows = p.dim == p.dstride ? p.dim : 0u;  // floats of an unpadded row (0: padded -- run-time-length instances only)
+    const bool one = p.ell_stride <= 32u, late = p.late_rows != 0;
+    WalkPlan pl{};
+    WalkInstance& k = pl.inst;
+    pl.pass = pass;
+    pl.general_only = p.n_entries > 1;
+    // The LDS-list kernel serves ef beyond the register lists, and auxiliary-graph walks over tables >= 4 GiB (the register-list /
+    // two-list kernels have their auxiliary-graph hop in the 32-bit-offset instances only).
+    pl.lds_list = ef > kRegListMaxEf || (aux && !off32);
+    // Every LDS kernel packs its visited set when ids fit 24 bits (the register-list kernels: in their compact, 32-bit-offset instances).
+    pl.packed = pl.lds_list ? (p.n <= 0xFFFFFFu && !p.force_wide) : off32;
+    // (a visited set in the packed form: no id may look like a half-written slot -- see visited_test_mask_packed)
+    pl.coop_serves = metric == 0 && (rows == 32u || rows == 48u || rows == 64u) && regs == 4 && ef <= kRegListMaxEf && off32 && p.n < 0xFF0000u && !aux &&
+                     one && p.n_entries <= 1u;
+    if (pass == WalkPass::Bitmap) {
+        // The bitmap first pass runs the register-list (ef <= 128, L2) / two-list (128 < ef <= 1 024, both metrics) walk for 128-byte rows
+        // of a compact index, the two-list walk for 256- and 576-byte rows with L2 (the reference's glove 300 -> 144), else the LDS-list walk.
+        const bool reg = (metric == 0 || regs == 4) && ef <= kRegListMaxEf && (rows == 32u || ((rows == 64u || rows == 144u) && metric == 0 && regs == 4)) && off32 && !aux;
+        const bool big = reg && regs == 4;
+        if (big) k = {WalkFamily::BitmapBig, metric, (int)rows / 4, 0, false, false, one, false, rows == 144u && late, false, false};
+        else if (reg) k = {WalkFamily::BitmapReg, 0, 0, regs};
+        else k = {WalkFamily::BitmapLds, metric, metric == 0 && rows == 32u ? 8 : 0};
+        pl.lds_list = !reg;
+        // no visited table (two-list kernel: + the re-rank query, which cannot overlay the base list it reads its candidates from)
+        pl.lds_fixed = lds_fixed_bytes(ef, p.dstride, false, !reg, false) + (big ? p.rr_reserve : 0u);
+        pl.rr_base = big ? (size_t)p.rr_reserve : pl.lds_fixed;
+        return pl;
+    }
+    const bool coop = !retry && p.coop;
+    // Shape served by the walk_hot* kernels (first pass only): 128-byte rows, adjacency rows of one 32-slot pass (walk_hotw*: 33 .. 64
+    // slots, two passes), compact index (their visited set stores 24-bit ids)
+    const bool hot = !retry && !coop && (metric == 0 || metric == 1) && rows == 32u && ef <= kBigMaxEf && p.ell_stride <= 64u && off32 &&
+             (!p.stamps_on || (regs == 4 && !env.stamps_generic)) && !aux;
+    pl.lds_fixed = lds_fixed_bytes(ef, p.dstride, hot, pl.lds_list, coop);
+    // the quotient form: the walk_hot* family and the register-list / two-list kernels of a compact index (the retry kernels keep the packed form)
+    pl.knows_quotient = !retry && (hot || (off32 && !pl.lds_list && !aux));
+    // the re-rank query is staged once the walk is over: two-list instances keep their result list in LDS and use the visited-set area
+    pl.rr_in_table = true;
+    pl.rr_base = (regs == 4 && !pl.lds_list) ? 0 : pl.lds_fixed;
+    if (coop || hot) {  // (the two-wavefront walk on a shape it has no instance for: WalkFamily::None)
+        if (hot) k = {WalkFamily::Hot, metric, 0, regs, false, false, one, false, false, regs == 1 && metric == 0 && one && p.spec_rows && !GBNNS_HOT1_SPEC};
+        else if (pl.coop_serves) k = {WalkFamily::Coop, 0, (int)rows / 4, 0, false, false, false, false, late};
+        return pl;
+    }
+    // steps the generic instances are unrolled for: 128-byte rows (both metrics); with L2 192-, 256- and 576-byte rows and, by beam, the
+    // 384- / 512-byte rows of PLAIN walks over deep / sift vectors -- 512-byte rows up to ef = 200 are faster on the run-time-length
+    // two-list instance, four lanes per row (ef 130 / 200: 1.72 / 2.77 against 1.93 / 2.87 ms; ef 300 / 400: 5.25 / 8.25 against 4.20 / 5.51)
+    int steps = 0;
+    if (metric == 1) steps = rows == 32u ? 8 : 0;
+    else if (rows == 32u || rows == 48u || rows == 64u || rows == 144u) steps = (int)rows / 4;
+    else if (rows == 96u && env.wide2 && regs == 4 && !pl.lds_list) steps = 24;
+    else if (rows == 128u && env.wide2 && ef > kPlain512PairMinEf && !pl.lds_list) steps = 32;
+    if (pl.lds_list) {
+        k = {WalkFamily::LdsList, metric, steps, 0, false, retry, false, false, false, false, pl.packed};
+        return pl;
+    }
+    if (regs == 4) {  // the two-list kernels, one instance for every ef up to 1 024
+        const bool l2_unrolled = metric == 0 && steps >= 12;
+        k = {WalkFamily::TwoList, metric, steps, 4, off32, retry, false, aux};  // (aux: off32 -- over a non-compact index it is an LDS-list plan)
+        if (!aux && off32 && !retry) {
+            // the common shape (compact index, adjacency rows of one pass; pair form: 32 slots per pass) gets the hop without the pass loop;
+            // 384- / 512- / 576-byte rows have instances with the rows requested after the visited test, in the pass loop too
+            k.one = p.ell_stride <= ((steps == 8 || l2_unrolled) ? 32u : 64u);
+            k.late = l2_unrolled && steps >= 24 && late;
+        }
+        return pl;
+    }
+    // one / two list registers.  384-byte rows: the pair form for the first pass of a compact index over one-pass adjacency rows
+    // (two-pass ones: the one-register list only -- GD(M = 30) graph, rows of up to 45 slots, ef 40: 0.678 against 0.763 ms a lane per
+    // row; the two-register list 1.254 / 1.834 at ef 80 / 120 against 1.255 / 1.814: stays on the run-time-length instance)
+    if (rows == 96u && metric == 0 && env.wide2 && !retry && off32 && !aux && (one || (p.ell_stride <= 64u && regs == 1)) && !p.stamps_on) {
+        k = {WalkFamily::RegList, 0, 24, regs, true, false, one};
+        return pl;
+    }
+    if (steps >= 24) steps = 0;  // (576-byte rows at ef <= 128: the run-time-length instances)
+    k = {WalkFamily::RegList, metric, steps, regs, off32, retry, false, aux};
+    if (!aux && regs == 1 && off32 && !retry && p.ell_stride <= ((steps == 8 || (metric == 0 && steps >= 12)) ? 32u : 64u)) {
+        // ef <= 64, adjacency rows of one pass: a loop-free expansion; 192- / 256-byte rows with L2: the instance with the query in LDS
+        if (metric == 0 && steps >= 12 && !p.stamps_on) k = {WalkFamily::RegWide, 0, steps, 0, false, false, false, false, late};
+        else k.one = true;
+    }
+    return pl;
+}
+
+}  // namespace gbnns

@@ -1,0 +1,99 @@
+// walk_plan.h -- which walk kernel instance serves a pass over a shape, and the LDS layout that instance uses: decided in ONE place, plan_walk
+// (walk_plan.cpp: plain host code).  The host layer (search_core.cpp, sizing.cpp) sizes the visited set, the re-rank room and the retry pass from
+// the plan; launch_walk (walk_l2.hip) launches the very instance the plan names: the LDS a kernel runs on is always the LDS of its own layout.
+#pragma once
+
+#include "kernels.h"
+
+namespace gbnns {
+
+// Layout constants the plan shares with the kernels.  Layout of the one-register hot instances (ef <= 64), A/B switches: GBNNS_HOT1_QLDS = the query is re-read from LDS every
+// hop (64 vector registers: 8 wavefronts per SIMD) instead of living in 16 registers (72: 7 per SIMD); GBNNS_HOT1_SPEC = the
+// rows are requested before the visited test (speculatively, for every valid slot) instead of after it (new ids only).
+#ifndef GBNNS_HOT1_QLDS
+#define GBNNS_HOT1_QLDS 1
+#endif
+#ifndef GBNNS_HOT1_SPEC
+#define GBNNS_HOT1_SPEC 0
+#endif
+constexpr int kRegTieCap = 16;       // tie list of the register kernel (LDS, 128 B)
+constexpr int kRegListMaxEf = 1024;  // largest ef served by the register-list / two-list kernels (beyond: result list as one sorted LDS array)
+constexpr int kRegStageSlots = 66;   // merge scatter buffer: ranks 0..ef (ef <= 64), padded to 16 B
+constexpr int kBigMaxEf = kRegListMaxEf;  // (the two-list structure itself reaches 64 chunks = 4 096 entries: one mask lane per chunk)
+#ifndef GBNNS_HOT2_MAX
+#define GBNNS_HOT2_MAX 128  // (64: experiments with the two-list kernels from ef = 65 on)
+#endif
+constexpr int kHot2MaxEf = GBNNS_HOT2_MAX;  // up to here the two-register lists (walk_hot_one<2>, walk_reg_one<2>) are the faster ones
+constexpr int kPlain512PairMinEf = 200;  // 512-byte rows (PLAIN walks over sift vectors): beams beyond this take the pair-form two-list instance
+constexpr size_t kCoopExtraLds = 1280;  // the two-wavefront walk's two 64-word result buffers + three 64-word slots of adjacency words requested ahead (its mailbox lives in the query area)
+
+// LDS of a two-list instance besides the visited set: [tie list][front-merge buffer: 66 keys][base list: ef_pad keys]
+// [flush flags: ef_pad + 64 bytes], ef_pad = ef rounded up to 64.  The flush flags live inside the front-merge buffer
+// when they fit (ef <= 448: the two are never in use at the same time) -- at ef = 140 .. 180 those 256 bytes are what
+// separates 14 / 13 / 12 resident wavefronts per CU from 15 / 14 / 13.
+__host__ __device__ __forceinline__ constexpr bool big_list_flags_in_stage(int ef) {
+    return (size_t)((ef + 63) / 64 * 64) + 64 <= (size_t)kRegStageSlots * 8;
+}
+__host__ __device__ __forceinline__ constexpr size_t big_list_fixed_bytes(int ef) {
+    return (size_t)kRegTieCap * 8 + (size_t)kRegStageSlots * 8 + (size_t)((ef + 63) / 64 * 64) * 8 +
+           (big_list_flags_in_stage(ef) ? 0 : (size_t)((ef + 63) / 64 * 64) + 64);
+}
+
+enum class WalkPass { First, Bitmap, Retry };  // first pass with the visited set in LDS / as bitmaps in HBM; retry pass over the hand-overs
+enum class WalkFamily : uint8_t {
+    None,       // no instance serves what was asked for (the two-wavefront walk on a shape it has no instance for): launching it is an error
+    Coop,       // walk_coop_kernel<STEPS, LATE>                                     (walk_coop.hip)
+    Hot,        // walk_hot* / walk_hotw* / walk_hot_dot*: hand-laid-out, 128-byte rows (walk_hot.hip)
+    RegWide,    // walk_reg_wide_kernel<STEPS, LATE>: 192- / 256-byte rows, ef <= 64  (walk_wide.hip)
+    RegList,    // walk_reg_kernel<METRIC, STEPS, OFF32, RETRY, R, ONE_CHUNK, AUX>   (walk_l2 / walk_dot / walk_wide / walk_wide3)
+    TwoList,    // walk_reg_big_kernel<METRIC, STEPS, OFF32, RETRY, AUX, ONE_PASS, LATE> (walk_l2 / walk_dot / walk_wide / walk_wide2)
+    LdsList,    // walk_fast_kernel<METRIC, STEPS, RETRY, PACKED>                    (walk_l2 / walk_dot / walk_wide)
+    BitmapReg,  // walk_bitmap_reg_kernel<METRIC, R>                                 (walk_bitmap.hip)
+    BitmapBig,  // walk_bitmap_big_kernel<METRIC, STEPS, ONE_PASS, LATE>
+    BitmapLds,  // walk_bitmap_kernel<METRIC, STEPS>
+};
+
+// One kernel instance, named completely: its family and every template argument.  An argument the family does not have stays 0 / false.
+struct WalkInstance {
+    WalkFamily family;
+    int metric;   // 0 = L2, 1 = negative dot
+    int steps;    // 16-byte steps of a row the distance is unrolled for (0: run-time length)
+    int regs;     // list registers per lane: 1 (ef <= 64), 2 (ef <= 128); 4 = the two-list structure
+    bool off32;   // compact index: 32-bit byte offsets, 24-bit ids
+    bool retry;
+    bool one;     // adjacency rows of one 32-slot pass (ONE_PASS / ONE_CHUNK; the hot family: its one-pass instances, else walk_hotw*)
+    bool aux;     // auxiliary-graph hop
+    bool late, spec;  // rows requested after the visited test (WalkParams::late_rows) / walk_hot_spec_kernel: before it (spec_rows)
+    bool packed;  // LDS-list family: visited set of 24-bit ids
+};
+inline bool operator==(const WalkInstance& a, const WalkInstance& b) {
+    return a.family == b.family && a.metric == b.metric && a.steps == b.steps && a.regs == b.regs && a.off32 == b.off32 && a.retry == b.retry && a.one == b.one &&
+           a.aux == b.aux && a.late == b.late && a.spec == b.spec && a.packed == b.packed;
+}
+
+struct WalkPlan {
+    WalkPass pass;
+    WalkInstance inst;
+    // layout facts of that instance (none of them depends on the visited set's size or form)
+    size_t lds_fixed;      // LDS bytes of a wavefront (two-wavefront walk: of a query) without the visited set
+    bool packed;           // visited set without the quotient form: five 24-bit ids per 16-byte bucket (else 4-byte slots)
+    bool knows_quotient;   // the instance reads WalkParams::vs_shr
+    bool lds_list;         // result list in LDS as one sorted array: no fused re-rank
+    bool coop_serves;      // the two-wavefront walk has an instance for this shape (whether or not this plan is it)
+    bool general_only;     // several entry points per query: the general kernel takes the whole batch
+    size_t rr_base;        // room of the fused re-rank's query = rr_base (+ the visited set's bytes when rr_in_table)
+    bool rr_in_table;      // (rr_room below)
+    // form of the visited set (walk_hash_bytes, kernels.h); vs_shr is set only where the instance knows the quotient form
+    int hash_form(uint32_t vs_shr) const { return vs_shr ? 2 : (packed ? 1 : 0); }
+    size_t rr_room(size_t hash_bytes) const { return rr_base + (rr_in_table ? hash_bytes : 0); }
+};
+
+// Environment switches, read once: GBNNS_WIDE2=0 sends the 384- / 512-byte rows to the run-time-length instances at every beam (A/B runs);
+// GBNNS_STAMPS_GENERIC keeps diagnostic (GBNNS_STAMPS) builds off the hot two-list instances.
+struct WalkEnv { bool wide2, stamps_generic; };
+const WalkEnv& walk_env();
+// Reads the shape (dim, dstride, n, ell_stride, aux_ell / aux_stride), ef, n_entries, force_wide, coop, late_rows, spec_rows, stamps_on and
+// rr_reserve -- nothing the sizing rule writes (hash_cap, hash_limit, vs_shr), so the layout is known before the visited set is sized.
+WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv& env = walk_env());
+
+}  // namespace gbnns

@@ -53,7 +53,8 @@ typedef enum {
     GBNNS_ERR_NO_DEVICE = 2,   /* no HIP device, or device ordinal out of range */
     GBNNS_ERR_HIP = 3,         /* a HIP runtime call failed (message in gbnns_last_error) */
     GBNNS_ERR_OOM = 4,         /* host or device allocation failed */
-    GBNNS_ERR_UNSUPPORTED = 5  /* valid request outside what this build implements */
+    GBNNS_ERR_UNSUPPORTED = 5, /* valid request outside what this build implements */
+    GBNNS_ERR_INTERNAL = 6     /* the library contradicted itself (a bug): with profiling on, a first pass that launched another kernel than planned */
 } gbnns_status;
 
 /* support_func.h:87-163: the Metric* slot.  L2 = L2Metric::Dist (:107-128, drops d%4 tail
@@ -303,6 +304,16 @@ int gbnns_debug_knob(const char* name, int value);
 int gbnns_index_knob(gbnns_index* index, const char* name, int value);   /* GBNNS_ERR_INVALID: not a handle knob */
 int gbnns_index_knob_get(gbnns_index* index, const char* name, int* out_value);   /* the handle's current value */
 int gbnns_profile_read(gbnns_index* index, gbnns_profile* out, int reset);
+/* Diagnostic, no device needed: which first-pass walk kernel the library plans for a shape, and that instance's LDS bytes per wavefront
+ * without the visited set.  The inputs are what a search derives from its index and arguments: metric, walked dimension and row stride
+ * (floats, a multiple of 4), rows, adjacency stride (slots, a multiple of 16), auxiliary-graph stride (0: no GBNNS_FLAG_AUX_GRAPH), beam,
+ * entry points per query, GBNNS_FLAG_WIDE_INDEX, the resolved "coop" / "late_rows" / speculative-rows decisions (0 / 1; the two-wavefront
+ * walk only where the shape has it, as in a search), the pass (0 first pass, 1 bitmap first pass -- GBNNS_FLAG_BITMAP_PASS --, 2 retry
+ * pass) and the bytes the bitmap pass reserves for the re-rank query.  `name` receives the kernel's name, template arguments included
+ * ("walk_general_kernel" for several entry points per query); GBNNS_ERR_INVALID for inputs no index or search can produce. */
+int gbnns_debug_walk_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef,
+                          uint32_t n_entries, int force_wide, int coop, int late_rows, int spec_rows, int pass, uint32_t rr_reserve,
+                          char* name, uint32_t name_bytes, uint64_t* lds_bytes);
 
 /* hnswlikeGD (support_func.h:521-575, need_const_degree = false) + addReverseEdgesForGD
  * (:402-445): prunes a kNN graph (CSR, host) over `ds` [n x d] (host) into the search graph, as

@@ -210,3 +210,79 @@ def test_rccl_load_failure_is_an_error_not_a_crash(lib):
             os.environ.pop("GBNNS_RCCL_LIB")
         else:
             os.environ["GBNNS_RCCL_LIB"] = old
+
+
+def _walk_plan(lib, metric, dim, dstride, n, ell_stride, aux_stride, ef, n_entries, force_wide, coop, late_rows, spec_rows, pas, rr_reserve):
+    name = ctypes.create_string_buffer(128)
+    lds = ctypes.c_uint64()
+    rc = lib.gbnns_debug_walk_plan(metric, dim, dstride, n, ell_stride, aux_stride, ef, n_entries, force_wide, coop, late_rows, spec_rows, pas,
+                                   rr_reserve, name, 128, ctypes.byref(lds))
+    return rc, name.value.decode(), lds.value
+
+
+def test_walk_plan_over_every_shape(lib):
+    """The full cross product of the plan's inputs, indexes of 2^24 rows and more and tables of 4 GiB and more included (no small GPU
+    case reaches those): every shape gets a plan; its LDS without the visited set leaves room for the smallest visited set (128 4-byte
+    slots) inside the 160 KB of a CU -- beams of up to 4 096, one entry point: what search_core does not send to the general kernel
+    outright --; the retry plan of a shape is a retry instance and keeps the first pass's visited-set packing (compact 24-bit ids or
+    4-byte slots: the retry pass is sized for the form the first pass's hand-overs were counted in); inputs no index can have are refused."""
+    import itertools
+
+    def packed(name):   # which visited-set packing the instance's name says: walk_fast_kernel<M, S, RETRY, PACKED>, <M, S, OFF32, ...>
+        args = name[name.index("<") + 1:-1].split(", ") if "<" in name else []
+        if name.startswith("walk_fast_kernel<"):
+            return args[3] == "true"
+        if name.startswith(("walk_reg_kernel<", "walk_reg_big_kernel<")):
+            return args[2] == "true"
+        assert name.startswith(("walk_hot", "walk_coop_kernel<", "walk_reg_wide_kernel<")), name  # compact indexes only
+        return True
+
+    def is_retry(name):
+        args = name[name.index("<") + 1:-1].split(", ")
+        return args[2 if name.startswith("walk_fast_kernel<") else 3] == "true"
+
+    count = 0
+    for metric, dim, n, ell, aux, ef in itertools.product((0, 1), (8, 16, 30, 32, 48, 64, 96, 128, 132, 144, 300, 960),
+                                                          (3000, 0xFEFFFF, 0xFFFFFF, 1 << 24, 1 << 26, 0xFFFFFFFF), (16, 32, 64, 80), (0, 16),
+                                                          (1, 8, 64, 65, 128, 129, 200, 201, 512, 1024, 1100, 4096)):
+        dstride = (dim + 3) // 4 * 4
+        for n_ent, wide, coop, late, spec in itertools.product((1, 3), (0, 1), (0, 1), (0, 1), (0, 1)):
+            shape = (metric, dim, dstride, n, ell, aux, ef, n_ent, wide, coop, late, spec)
+            rc0, first, lds0 = _walk_plan(lib, *shape, 0, 0)
+            rc1, bitmap, lds1 = _walk_plan(lib, *shape, 1, 4 * 960)
+            rc2, retry, lds2 = _walk_plan(lib, *shape, 2, 0)
+            count += 3
+            assert (rc0, rc1, rc2) == (0, 0, 0) and first and bitmap and retry, shape
+            if n_ent > 1:
+                assert first == "walk_general_kernel", shape
+                continue
+            assert max(lds0, lds1, lds2) + 128 * 4 <= 160 * 1024, (shape, lds0, lds1, lds2)
+            assert first.startswith("walk_") and bitmap.startswith("walk_bitmap_") and is_retry(retry), (shape, first, bitmap, retry)
+            assert packed(first) == packed(retry), (shape, first, retry)
+    assert count > 1_000_000
+    # refused: unknown metric, no dimension, a row stride that is not the padded dimension, no rows, more rows than ids, adjacency
+    # strides that are no multiple of 16, no beam, an unknown pass
+    ok = (0, 32, 32, 3000, 32, 0, 64, 1, 0, 0, 0, 0, 0, 0)
+    assert _walk_plan(lib, *ok)[0] == 0
+    for i, v in ((0, 2), (1, 0), (2, 36), (3, 0), (3, 1 << 32), (4, 0), (4, 40), (5, 8), (6, 0), (12, 3)):
+        bad = list(ok)
+        bad[i] = v
+        assert _walk_plan(lib, *bad)[0] == 1, bad
+
+
+def test_walk_plan_equals_the_launchers_it_replaced(lib):
+    """tests/golden/walk_launches_before_plan.tsv.gz: what the launchers launched when the choice of instance still lived in them -- that
+    commit's object files, driven without a device over the cross product of both metrics, walked rows of 8 .. 960 floats, indexes of
+    3 000, 2^24 - 1 (tables of 4 GiB and more from 300 floats a row on) and 2^24 rows, adjacency rows of one pass, two passes and more
+    than 64 slots, with and without the auxiliary graph, beams of 1 .. 1 100, forced-wide indexes, the two-wavefront walk, late and
+    speculative rows, for the first, the bitmap and the retry pass (the file's header says how).  For every row the plan names the
+    kernel that was launched, with the same LDS besides the visited set; no row is left out, and all 210 walk instances of the first,
+    bitmap and retry passes occur."""
+    import gzip
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "walk_launches_before_plan.tsv.gz"), "rt") as f:
+        rows = [ln.rstrip("\n").split("\t") for ln in f if not ln.startswith("#")]
+    assert len(rows) == 104544 and all(len(r) == 16 for r in rows)
+    assert len({r[15] for r in rows}) == 210 and {r[12] for r in rows} == {"0", "1", "2"}
+    for r in rows:
+        rc, name, lds = _walk_plan(lib, *(int(v) for v in r[:14]))
+        assert (rc, name, lds) == (0, r[15], int(r[14])), (r, rc, name, lds)
