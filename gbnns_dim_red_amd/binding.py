@@ -71,12 +71,14 @@ class Profile(C.Structure):
         ("walk_ms", C.c_double), ("walk_general_ms", C.c_double), ("rerank_ms", C.c_double),
         ("total_ms", C.c_double), ("queries", C.c_uint64), ("general_queries", C.c_uint64),
         ("walk_kernel", C.c_char * 96), ("project_kernel", C.c_char * 32),
+        ("retry_kernel", C.c_char * 96), ("retry_queries", C.c_uint64), ("retry_general_queries", C.c_uint64),
     ]
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
         d["walk_kernel"] = d["walk_kernel"].decode("ascii", "replace")
         d["project_kernel"] = d["project_kernel"].decode("ascii", "replace")
+        d["retry_kernel"] = d["retry_kernel"].decode("ascii", "replace")
         return d
 
 

@@ -188,6 +188,9 @@ struct gbnns_index {
     bool profiling = false;
     std::vector<ProfCall> pending;
     gbnns_profile acc{};
+    uint32_t* prof_ctrl = nullptr;     // [4] page-locked copy of the last profiled call's control words (hand-over counts), made behind its general kernel
+    bool prof_ctrl_pending = false;    // ... a copy is under way or done and not yet read; prof_ctrl_direct: that call's first pass appended to list B itself
+    bool prof_ctrl_direct = false;
     // visited-set sizing feedback, shared by the lanes (host-side bookkeeping; the statistics of a call arrive
     // asynchronously in the lane's pinned block)
     std::map<int, uint32_t> cap_for_ef;

@@ -458,6 +458,7 @@ int gbnns_index_destroy(gbnns_index* ix) {
     (void)hipDeviceSynchronize();  // lanes may still be running a call whose join was deferred
     if (ix->order_ev) (void)hipEventDestroy(ix->order_ev);
     if (ix->fork_ev) (void)hipEventDestroy(ix->fork_ev);
+    if (ix->prof_ctrl) (void)hipHostFree(ix->prof_ctrl);
     for (Lane& L : ix->lanes) {
         if (L.stats_ev) (void)hipEventDestroy(L.stats_ev);
         if (L.done_ev) (void)hipEventDestroy(L.done_ev);
@@ -684,9 +685,15 @@ int gbnns_profile_read(gbnns_index* ix, gbnns_profile* out, int reset) {
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(&total, ix->lanes[0].ctrl.as<uint32_t>() + 5, 4, hipMemcpyDeviceToHost));
     ix->acc.general_queries = total;
+    if (ix->prof_ctrl_pending) {  // hand-over counts of the last profiled call (copied behind its general kernel; the device is idle now)
+        ix->prof_ctrl_pending = false;
+        // (a first pass that appended to list B itself -- no retry launch -- handed all of it on)
+        ix->acc.retry_queries = ix->prof_ctrl[ix->prof_ctrl_direct ? 3 : 0];
+        ix->acc.retry_general_queries = ix->prof_ctrl[3];
+    }
     ix->acc.struct_size = sizeof(gbnns_profile);
     // out->struct_size on entry = the caller's sizeof(gbnns_profile): a caller built against an older header (the struct grew from 160 to
-    // 192 bytes in round 5) gets the prefix it knows and nothing written past it; 0 (callers that never set it) = the 160-byte round-4 layout
+    // 192 bytes in round 5, to 304 with the retry pass's name and counts) gets the prefix it knows and nothing written past it; 0 (callers that never set it) = the 160-byte round-4 layout
     {
         const size_t theirs = out->struct_size ? out->struct_size : 160u;
         const size_t take = std::min(theirs, sizeof(gbnns_profile));

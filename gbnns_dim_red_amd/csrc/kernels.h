@@ -100,6 +100,7 @@ struct WalkPlan;
 hipError_t launch_walk(const WalkPlan& pl, const WalkParams& p, unsigned slots, hipStream_t s);
 const char* walk_plan_name(const WalkPlan& pl);   // printable name of the plan's instance, template arguments included (no device needed); nullptr: none
 const char* walk_first_pass_name(hipStream_t s);  // (mangled) name of the first-pass kernel this thread launched last
+const char* walk_retry_pass_name(hipStream_t s);  // ... and of the retry-pass kernel
 hipError_t launch_walk_general(const WalkParams& p, int metric, hipStream_t s);
 
 // Re-rank (search_function.h:105-125).  One query per wavefront, one candidate per lane.

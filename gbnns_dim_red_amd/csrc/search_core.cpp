@@ -311,6 +311,7 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
         w.ovf_list = w.ovf2_list;
     }
     bool bitmap_pass = false;
+    const char* retry_planned = nullptr;  // the retry instance this call launched (profiling)
     if (bitmap_per_cu) {
         if ((rc = L.fp_bitmap.ensure(bitmap_per_cu * cus * (size_t)bitmap_words * 4))) return rc;
         w.fp_bitmap = L.fp_bitmap.as<uint32_t>();
@@ -331,6 +332,7 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
             // nothing to launch
         } else if (w2.hash_cap > cap) {
             HIP_TRY(launch_walk(retry, w2, 0, s));
+            if (prof) retry_planned = walk_plan_name(retry);
         } else {
             HIP_TRY(hipMemcpyAsync(ctrl + 3, ctrl, 4, hipMemcpyDeviceToDevice, s));  // nothing to gain: A -> B
             HIP_TRY(hipMemcpyAsync(w.ovf2_list, w.ovf_list, (size_t)nq * 4, hipMemcpyDeviceToDevice, s));
@@ -339,22 +341,35 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
     if (prof) {
         HIP_TRY(hipEventRecord(pc.ev[2], s));
         // name of the first-pass kernel of this call, template arguments included ("walk_general_kernel" when there was none)
-        const char* mangled = w.all_general ? nullptr : walk_first_pass_name(s);
-        std::string name = "walk_general_kernel";
-        if (mangled) {
+        auto printable = [](const char* mangled) {  // drop "void gbnns::(anonymous namespace)::" and the parameter list
             int st = 0;
             char* dm = abi::__cxa_demangle(mangled, nullptr, nullptr, &st);
-            name = (st == 0 && dm) ? dm : mangled;
+            std::string name = (st == 0 && dm) ? dm : mangled;
             std::free(dm);
-            size_t pos = name.find("walk_");  // drop "void gbnns::(anonymous namespace)::" and the parameter list
+            size_t pos = name.find("walk_");
             if (pos != std::string::npos) name = name.substr(pos);
             pos = name.rfind("(gbnns::WalkParams)");
             if (pos != std::string::npos) name = name.substr(0, pos);
+            return name;
+        };
+        const char* mangled = w.all_general ? nullptr : walk_first_pass_name(s);
+        std::string name = "walk_general_kernel";
+        if (mangled) {
+            name = printable(mangled);
             const char* planned = walk_plan_name(first);
             if (!planned || name != planned)
                 return fail(GBNNS_ERR_INTERNAL, "first pass: planned %s, launched %s", planned ? planned : "(none)", name.c_str());
         }
         std::snprintf(ix->acc.walk_kernel, sizeof(ix->acc.walk_kernel), "%s", name.c_str());
+        // ... and of its retry-pass kernel (empty: none launched)
+        std::string retry_name;
+        if (retry_planned) {
+            const char* rm = walk_retry_pass_name(s);
+            retry_name = rm ? printable(rm) : "(none)";
+            if (retry_name != retry_planned)
+                return fail(GBNNS_ERR_INTERNAL, "retry pass: planned %s, launched %s", retry_planned, retry_name.c_str());
+        }
+        std::snprintf(ix->acc.retry_kernel, sizeof(ix->acc.retry_kernel), "%s", retry_name.c_str());
     }
     g_slow.mark("walk");
     HIP_TRY(launch_walk_general(w, ix->metric, s));
@@ -387,6 +402,12 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
     if (prof) {
         HIP_TRY(hipEventRecord(pc.ev[4], s));
         ix->pending.push_back(pc);
+        // hand-over counts of this call for gbnns_profile_read, behind the timed stages: this call's control block stays as it is until a
+        // later call's general kernel clears it
+        if (!ix->prof_ctrl) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ix->prof_ctrl), 16, hipHostMallocDefault));
+        HIP_TRY(hipMemcpyAsync(ix->prof_ctrl, ctrl, 16, hipMemcpyDeviceToHost, s));
+        ix->prof_ctrl_pending = true;
+        ix->prof_ctrl_direct = skip_retry;
     }
 
     // ---- outputs ----------------------------------------------------------------------

@@ -34,6 +34,11 @@ static thread_local const void* g_walk_first_fn = nullptr;
 const char* walk_first_pass_name(hipStream_t s) {
     return g_walk_first_fn ? hipKernelNameRefByPtr(g_walk_first_fn, s) : nullptr;
 }
+// ... and of the last retry-pass kernel (gbnns_profile.retry_kernel)
+static thread_local const void* g_walk_retry_fn = nullptr;
+const char* walk_retry_pass_name(hipStream_t s) {
+    return g_walk_retry_fn ? hipKernelNameRefByPtr(g_walk_retry_fn, s) : nullptr;
+}
 
 // First pass: a workgroup per query (the two-wavefront walk: of two wavefronts); retry: a wavefront per CU; bitmap pass: `slots` wavefronts, no LDS visited set
 hipError_t launch_walk(const WalkPlan& pl, const WalkParams& p, unsigned slots, hipStream_t s) {
@@ -44,7 +49,7 @@ hipError_t launch_walk(const WalkPlan& pl, const WalkParams& p, unsigned slots, 
     const size_t lds = pl.lds_fixed + (bitmap ? 0 : walk_hash_bytes(p.hash_cap, pl.hash_form(p.vs_shr)));
     const hipError_t err = set_lds(e->fn, lds);
     if (err != hipSuccess) return err;
-    if (!retry) g_walk_first_fn = e->fn;
+    (retry ? g_walk_retry_fn : g_walk_first_fn) = e->fn;
     void* args[] = {const_cast<WalkParams*>(&p)};
     (void)hipLaunchKernel(e->fn, dim3(bitmap ? slots : retry ? (unsigned)kRetrySlots : p.nq), dim3(pl.inst.family == WalkFamily::Coop ? 128 : 64), args, lds, s);
     return hipGetLastError();

@@ -251,7 +251,7 @@ int gbnns_rerank(gbnns_index* index, const float* queries, uint64_t n_q, const u
  * reset.  Reading synchronises the recorded events. */
 typedef struct {
     uint32_t struct_size;         /* in: the caller's sizeof(gbnns_profile) (0 = the 160-byte layout of rounds 1-4, which ends before
-                                     project_kernel); out: the bytes gbnns_profile_read filled in -- never more than the caller said */
+                                     project_kernel; 192 = the layout that ends before retry_kernel); out: the bytes gbnns_profile_read filled in -- never more than the caller said */
     uint32_t calls;               /* search calls accumulated */
     double project_ms;            /* MLP layers + normalise */
     double walk_ms;               /* LDS-resident beam-walk kernel */
@@ -262,6 +262,13 @@ typedef struct {
     uint64_t general_queries;     /* of which were (re)run by the general kernel */
     char walk_kernel[96];         /* first-pass walk kernel of the last profiled call, template arguments included */
     char project_kernel[32];      /* kernel family of the handle's last projection: "mlp_net_kernel" (one launch) or "mlp_layer_kernels" */
+    /* The retry pass of the last profiled call (304-byte layout; a caller that says 192 gets the fields above only).  The first pass
+     * hands the queries its visited set cannot finish to the retry pass (list A), which walks them again with a CU's whole LDS and
+     * hands what it cannot finish either on to the general kernel (list B). */
+    char retry_kernel[96];        /* retry-pass kernel that call launched, template arguments included; empty when it launched none (batches of
+                                     a beam that have been calm, a retry pass with nothing to gain, the general kernel taking the whole batch) */
+    uint64_t retry_queries;       /* queries the first pass of that call handed over */
+    uint64_t retry_general_queries; /* of those, how many went on to the general kernel (all of them when no retry kernel was launched) */
 } gbnns_profile;
 
 int gbnns_profile_enable(gbnns_index* index, int on);

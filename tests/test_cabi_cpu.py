@@ -36,7 +36,7 @@ def test_struct_sizes_match_header(lib):
     # 8-byte aligned C layouts as declared in include/gbnns.h
     assert ctypes.sizeof(binding._IndexDesc) == 96
     assert ctypes.sizeof(binding._SearchArgs) == 136  # + n_entries, defer_depth
-    assert ctypes.sizeof(binding.Profile) == 192  # + walk_kernel[96], project_kernel[32]
+    assert ctypes.sizeof(binding.Profile) == 304  # + walk_kernel[96], project_kernel[32]; + retry_kernel[96], retry_queries, retry_general_queries
 
 
 def test_shard_bounds_arithmetic(lib):
@@ -286,3 +286,63 @@ def test_walk_plan_equals_the_launchers_it_replaced(lib):
     for r in rows:
         rc, name, lds = _walk_plan(lib, *(int(v) for v in r[:14]))
         assert (rc, name, lds) == (0, r[15], int(r[14])), (r, rc, name, lds)
+
+
+def _golden_walk_names():
+    import gzip
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "walk_launches_before_plan.tsv.gz"), "rt") as f:
+        return {ln.rstrip("\n").split("\t")[15] for ln in f if not ln.startswith("#")}
+
+
+def test_walk_instance_table_covers_every_instance(lib):
+    """tests/walk_instances.py, the case table of the device census (tests/test_gpu_walk_instances.py): for every case the plan, asked
+    with the decisions a search of that case resolves, names the case's `first` (first or bitmap pass) and -- hash_capacity != 0 --
+    `retry` instance; the union of those names IS the set of the 210 instances of the golden file, none missing and none unknown, so
+    every instance is the target of at least one case; the table stays a census (at most 260 cases) inside its own domain: the
+    documented dimensions and beams, a retry case at the top of its beam class with a 128-entry visited set, speculative rows only
+    with both knobs, and no two cases alike."""
+    import walk_instances as wi
+    golden = _golden_walk_names()
+    assert len(golden) == 210
+    assert len(wi.CASES) <= 260 and len(set(c[:11] for c in wi.CASES)) == len(wi.CASES)
+    recorded = set()
+    for c in wi.CASES:
+        assert c.metric in (0, 1) and c.dim in wi.DIMS and c.deg in wi.ELL_STRIDE and c.ef in wi.BEAMS, c
+        assert {c.aux, c.wide, c.bitmap, c.coop, c.late_rows, c.spec} <= {0, 1} and c.hash_capacity in (0, 128), c
+        assert not (c.bitmap and (c.wide or c.coop)) and not (c.coop and c.wide), c   # (a search would not take the case as written)
+        assert c.knobs["spec_tail"] == 0 and (c.knobs["spec_min_nq"], c.knobs["spec_any_form"]) in ((0, 0), (1, 1)), c
+        rc, first, _ = _walk_plan(lib, *c.plan_args(c.first_pass))
+        assert (rc, first) == (0, c.first), (c, rc, first)
+        recorded.add(first)
+        if c.hash_capacity:
+            assert c.ef in (64, 128, 200, 1024, 1100), c
+            assert c.ef != 1024 or ", 32, " in c.first, c   # (1 024 only where the instance serves no beam up to 200)
+            rc, retry, _ = _walk_plan(lib, *c.plan_args(2))
+            assert (rc, retry) == (0, c.retry), (c, rc, retry)
+            recorded.add(retry)
+        else:
+            assert c.retry is None, c
+    assert recorded == golden, (sorted(golden - recorded), sorted(recorded - golden))
+    assert {c.first for c in wi.CASES} | {c.retry for c in wi.CASES if c.retry} == golden
+    # short lists on every first-pass family that serves ef <= 64, as ordinary cases; one padded dimension, one beam per family
+    for ef in (1, 8):
+        fams = {c.first.split("<")[0] for c in wi.CASES if c.ef == ef and not c.hash_capacity}
+        assert fams >= {"walk_hot_kernel", "walk_hot_spec_kernel", "walk_hotw_kernel", "walk_hot_dot_kernel", "walk_reg_wide_kernel", "walk_reg_kernel",
+                        "walk_fast_kernel", "walk_bitmap_reg_kernel", "walk_bitmap_kernel"}, (ef, fams)
+    padded = [c for c in wi.CASES if c.dim % 4]
+    assert {c.dim for c in padded} == {30} and len({(c.metric, c.first) for c in padded}) == len(padded) == 8
+
+
+def test_walk_instance_retry_cases_outgrow_their_visited_set(orc):
+    """The precondition of the census's retry assertions, on the CPU: on the data of every retry case the oracle's walk computes more
+    distances than the case's visited set holds (hash_capacity) for at least three quarters of the queries -- so the first pass hands at
+    least that share over whatever the kernel, and "the retry pass finished half the batch" is a condition the retry instance has to
+    meet, not an observation."""
+    import walk_instances as wi
+    retry_cases = [c for c in wi.CASES if c.hash_capacity]
+    assert len({c.retry for c in retry_cases}) == 77
+    for c in retry_cases:
+        assert c.ef >= 64, c
+        w, _ = wi.oracle_walk(orc, c)
+        over = int((w["dist_calc"] > c.hash_capacity).sum())
+        assert 4 * over >= 3 * wi.NQ, (c, over, int(w["dist_calc"].min()))

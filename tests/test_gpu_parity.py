@@ -1623,7 +1623,8 @@ def test_two_list_kernels_by_name(g, orc):
     row length and metric; the library reports the first-pass kernel it launched (gbnns_profile.walk_kernel), so the
     test checks WHICH kernel produced the bit-exact answer: hot instance (L2, 128-byte rows), generic pair form for the
     dot metric, pair form for 192- / 256-byte rows (ef <= 64: walk_reg_wide_kernel), the HBM-bitmap variants, and the
-    two-register kernels below the crossover."""
+    two-register kernels below the crossover.  The names here are prefixes; tests/test_gpu_walk_instances.py asserts the exact name,
+    template tail included, of every instance of the first, the bitmap and the retry pass (case table: tests/walk_instances.py)."""
     shapes = [  # d, d_low, d_hidden, metric, max degree, [(ef, flags, expected kernel-name prefix)]
         (64, 32, 64, 0, 30, [(8, 0, "walk_hot_kernel"), (64, 0, "walk_hot_kernel"),
                              # (big batches request a hop's rows before its visited test: knob "spec_min_nq")
