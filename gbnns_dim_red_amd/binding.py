@@ -27,7 +27,7 @@ FLAG_MFMA_PROJECTION = 256
 # every symbol include/gbnns.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "gbnns_index_create", "gbnns_index_destroy", "gbnns_index_set_aux_graph", "gbnns_search_ex", "gbnns_search_batch", "gbnns_index_join", "gbnns_index_wait", "gbnns_host_pin", "gbnns_host_unpin",
-    "gbnns_project", "gbnns_rerank", "gbnns_debug_knob", "gbnns_debug_walk_plan", "gbnns_index_knob", "gbnns_index_knob_get", "gbnns_profile_enable", "gbnns_profile_read", "gbnns_build_graph_gd", "gbnns_build_graph_gd_device",
+    "gbnns_project", "gbnns_rerank", "gbnns_rerank_topk", "gbnns_search_topk", "gbnns_debug_knob", "gbnns_debug_walk_plan", "gbnns_index_knob", "gbnns_index_knob_get", "gbnns_profile_enable", "gbnns_profile_read", "gbnns_build_graph_gd", "gbnns_build_graph_gd_device",
     "gbnns_free", "gbnns_exact_knn", "gbnns_device_count", "gbnns_version", "gbnns_last_error",
     "gbnns_index_n", "gbnns_index_d", "gbnns_index_d_low", "gbnns_index_device",
     "gbnns_multi_create", "gbnns_multi_destroy", "gbnns_multi_size", "gbnns_multi_replica", "gbnns_multi_device_of",
@@ -114,6 +114,9 @@ def load_library():
                                   C.c_void_p]
     lib.gbnns_rerank.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
                                  C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.gbnns_rerank_topk.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.gbnns_search_topk.argtypes = [C.c_void_p, C.POINTER(_SearchArgs), C.c_int, C.c_void_p, C.c_void_p]
     if hasattr(lib, "gbnns_debug_knob"):  # (absent from the rounds 1-3 libraries that tools/ab4.sh may put in place of this one)
         lib.gbnns_debug_knob.argtypes = [C.c_char_p, C.c_int]
     if hasattr(lib, "gbnns_debug_walk_plan"):
@@ -443,13 +446,15 @@ class Index:
     # -- search ------------------------------------------------------------------------------
     def search(self, queries, ef, mode=MODE_NET, k=1, queries_low=None, entry_ids=None,
                want=("hops", "dist_calc"), hash_capacity=0, stream=None, out=None, flags=0,
-               aux=False, llf=False, hops_bound=50, defer_depth=0):
+               aux=False, llf=False, hops_bound=50, defer_depth=0, top_k=0):
         """Runs one batch.  numpy queries -> synchronous call, numpy results.  torch CUDA queries
         -> enqueued on `stream` (torch stream or None = current), torch results, no sync.  Pinned torch CPU queries ->
         HOST buffers in page-locked memory, pinned torch results: synchronous, or with FLAG_DEFER_JOIN a host batch in
         flight (copy in, kernels and ids out on a lane's stream; wait() / join() + stream.synchronize() to read them).
         `want` may also name "cand", "cand_dist", "q_low", "edges".  Returns a dict with "ids" + wanted.
-        aux / llf / hops_bound: the reference's use_second_graph walk over set_aux_graph()'s graph."""
+        aux / llf / hops_bound: the reference's use_second_graph walk over set_aux_graph()'s graph.
+        top_k > 0 (NET / LOWQ): gbnns_search_topk -- also "top_ids" / "top_dist" [nq x top_k], the top_k best of each query's ef
+        candidates in ascending (original-space distance, pop index); top_ids[:, 0] == ids."""
         if aux:
             flags |= FLAG_AUX_GRAPH | (FLAG_LLF if llf else 0)
         dev = _is_dev(queries) and queries.is_cuda
@@ -518,7 +523,12 @@ class Index:
             a.out_q_low = _ptr(alloc("q_low", (nq, self.d_low), f32))
         if "edges" in want:
             a.out_edges = _ptr(alloc("edges", (nq,), i32))
-        _check(self._lib.gbnns_search_ex(self._h, C.byref(a)))
+        if top_k > 0:
+            top_ids = alloc("top_ids", (nq, top_k), i32 if (dev or pinned) else np.uint32)
+            top_dist = alloc("top_dist", (nq, top_k), f32)
+            _check(self._lib.gbnns_search_topk(self._h, C.byref(a), top_k, _ptr(top_ids), _ptr(top_dist)))
+        else:
+            _check(self._lib.gbnns_search_ex(self._h, C.byref(a)))
         # Inputs (and the result buffers handed out) stay referenced while a lane stream may still read / write them: torch's
         # caching allocators do not know the library's internal streams.  A plain call: until the next call; deferred
         # calls: the last four (= the most lanes a handle has), until wait() / join() / a plain call joins them.
@@ -584,6 +594,18 @@ class Index:
         _check(self._lib.gbnns_rerank(self._h, q.ctypes.data, q.shape[0], cand.ctypes.data,
                                       cand.shape[1], _ptr(count), out.ctypes.data, MEM_HOST, None))
         return out
+
+    def rerank_topk(self, queries, cand, k, count=None, want_dist=True):
+        """gbnns_rerank_topk (host buffers): the k best of each row of cand [nq x stride] (pop order) -> (ids, dist) [nq x k],
+        ascending (distance, pop index); 0xFFFFFFFF / +inf from column count on.  ids[:, 0] == rerank(queries, cand, count)."""
+        q = _host(queries, np.float32)
+        cand = _host(cand, np.uint32)
+        count = None if count is None else _host(count, np.int32)
+        ids = np.empty((q.shape[0], k), np.uint32)
+        dist = np.empty((q.shape[0], k), np.float32) if want_dist else None
+        _check(self._lib.gbnns_rerank_topk(self._h, q.ctypes.data, q.shape[0], cand.ctypes.data, cand.shape[1], _ptr(count), k,
+                                           ids.ctypes.data, _ptr(dist), MEM_HOST, None))
+        return ids, dist
 
     # -- profiling -----------------------------------------------------------------------------
     def profile_enable(self, on=True):

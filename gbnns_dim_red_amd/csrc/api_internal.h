@@ -122,6 +122,7 @@ struct Lane {
     uint64_t ticket = 0, prev_ticket = 0;  // serial numbers of those two batches (0 = none), for gbnns_index_wait
     DevBuf q_in, q_low, h1, h2, cand, cand_dist, cnt, hops, dc, edges, out, entries, ovf_list, ovf2_list, ctrl;
     DevBuf g_bitmap, g_keys, fp_bitmap, order, order_hist;
+    DevBuf top_ids, top_dist;          // the k-answer rows of a HOST call (gbnns_rerank_topk / gbnns_search_topk)
     // visited-set sizing feedback: stats of an earlier call arrive asynchronously in pinned memory
     uint32_t* h_stats = nullptr;       // [4] copy of ctrl after the walk kernels
     hipEvent_t stats_ev = nullptr;
@@ -140,7 +141,7 @@ struct Lane {
     int stage_next = 0;
     DevBuf* bufs(int i) {
         DevBuf* b[] = {&q_in, &q_low, &h1, &h2, &cand, &cand_dist, &cnt, &hops, &dc, &edges, &out, &entries,
-                       &ovf_list, &ovf2_list, &ctrl, &g_bitmap, &g_keys, &fp_bitmap, &order, &order_hist};
+                       &ovf_list, &ovf2_list, &ctrl, &g_bitmap, &g_keys, &fp_bitmap, &order, &order_hist, &top_ids, &top_dist};
         return i < (int)(sizeof b / sizeof b[0]) ? b[i] : nullptr;
     }
 };
@@ -248,8 +249,19 @@ struct FirstPassSizing {
 FirstPassSizing size_first_pass(gbnns_index* ix, WalkParams& w, const WalkPlan& plan, const gbnns_search_args* a, int ef, int skey, uint32_t nq,
                                 bool sync_host);
 
+// The k best of each query's candidates beside a search's answers (gbnns_search_topk): ids [n_q x k], dist likewise or nullptr;
+// buffers of args->mem_kind.
+struct TopkOut {
+    int k;
+    uint32_t* ids;
+    float* dist;
+};
+
+// lanes.cpp: the body of gbnns_search_ex / gbnns_search_topk (topk == nullptr: the former)
+int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk);
+
 // search_core.cpp
-int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_t s, bool sync_host);
+int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_t s, bool sync_host, const TopkOut* topk = nullptr);
 
 
 // How one call is laid out over the handle's lanes (workspace + internal stream each).

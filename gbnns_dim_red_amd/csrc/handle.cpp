@@ -796,4 +796,65 @@ int gbnns_rerank(gbnns_index* ix, const float* queries, uint64_t n_q, const uint
     return GBNNS_OK;
 }
 
+int gbnns_rerank_topk(gbnns_index* ix, const float* queries, uint64_t n_q, const uint32_t* cand, uint32_t cand_stride,
+                      const int32_t* count, int k, uint32_t* out_ids, float* out_dist, int mem_kind, void* stream) {
+    // (what needs neither the handle nor a device first, then what needs no device)
+    if (!queries || !cand || !out_ids) return fail(GBNNS_ERR_INVALID, "null argument");
+    if (cand_stride == 0 || n_q >= (1ull << 31)) return fail(GBNNS_ERR_INVALID, "bad sizes");
+    if (k < 1 || (uint32_t)k > cand_stride) return fail(GBNNS_ERR_INVALID, "k = %d outside 1 .. cand_stride = %u", k, cand_stride);
+    if (mem_kind != GBNNS_MEM_HOST && mem_kind != GBNNS_MEM_DEVICE) return fail(GBNNS_ERR_INVALID, "unknown mem_kind %d", mem_kind);
+    if (!ix) return fail(GBNNS_ERR_INVALID, "null index");
+    if (n_q == 0) return GBNNS_OK;
+    const size_t lds = rerank_topk_lds(ix->d_pad, cand_stride);
+    if (lds > kMaxLds)
+        return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_rerank_topk: query + %u candidates' keys and distances need %zu bytes of LDS (limit %zu)",
+                    cand_stride, lds, kMaxLds);
+    const uint32_t nq = (uint32_t)n_q;
+    const bool host = mem_kind == GBNNS_MEM_HOST;
+    if (host) {
+        for (uint64_t i = 0; i < n_q; ++i) {
+            const uint32_t c = count ? (uint32_t)std::max(count[i], 0) : cand_stride;
+            if (c > cand_stride) return fail(GBNNS_ERR_INVALID, "count[%llu] > stride", (unsigned long long)i);
+            for (uint32_t j = 0; j < c; ++j)
+                if (cand[i * cand_stride + j] >= ix->n)
+                    return fail(GBNNS_ERR_INVALID, "candidate id %u >= n", cand[i * cand_stride + j]);
+        }
+    }
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc;
+    if ((rc = enter_stream(ix, s))) return rc;
+    Lane& L = ix->lanes[0];
+    RerankTopkParams r{};
+    r.db = ix->db; r.dstride = ix->d_pad; r.dim = ix->d; r.qstride = ix->d; r.cand_stride = cand_stride;
+    r.nq = nq; r.n = (uint32_t)ix->n; r.k = (uint32_t)k;
+    if ((rc = L.cnt.ensure((size_t)nq * 4))) return rc;
+    int32_t* cnt_dev = L.cnt.as<int32_t>();
+    const size_t bk = (size_t)nq * k * 4;
+    if (host) {
+        if ((rc = L.q_in.ensure((size_t)nq * ix->d * 4))) return rc;
+        if ((rc = L.cand.ensure((size_t)nq * cand_stride * 4))) return rc;
+        if ((rc = L.top_ids.ensure(bk))) return rc;
+        if (out_dist && (rc = L.top_dist.ensure(bk))) return rc;
+        if ((rc = host_copy_in(L, L.q_in.p, queries, (size_t)nq * ix->d * 4, s))) return rc;
+        if ((rc = host_copy_in(L, L.cand.p, cand, (size_t)nq * cand_stride * 4, s))) return rc;
+        if (count && (rc = host_copy_in(L, cnt_dev, count, (size_t)nq * 4, s))) return rc;
+        r.q = L.q_in.as<float>(); r.cand = L.cand.as<uint32_t>(); r.out = L.top_ids.as<uint32_t>();
+        r.out_dist = out_dist ? L.top_dist.as<float>() : nullptr;
+    } else {
+        r.q = queries; r.cand = cand; r.out = out_ids; r.out_dist = out_dist;
+        if (count) cnt_dev = const_cast<int32_t*>(count);
+    }
+    if (!count) HIP_TRY(launch_fill_u32(reinterpret_cast<uint32_t*>(cnt_dev), cand_stride, nq, s));
+    r.count = cnt_dev;
+    HIP_TRY(launch_rerank_topk(r, ix->metric, s));
+    if (host) {
+        if ((rc = host_copy_out(L, out_ids, r.out, bk, bk, 1, s))) return rc;
+        if (out_dist && (rc = host_copy_out(L, out_dist, r.out_dist, bk, bk, 1, s))) return rc;
+        HIP_TRY(hipStreamSynchronize(s));
+        ix->in_flight = false;
+    }
+    return GBNNS_OK;
+}
+
 }  // extern "C"

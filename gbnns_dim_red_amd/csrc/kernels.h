@@ -118,6 +118,16 @@ struct RerankParams {
     uint32_t* out;           // [nq]
 };
 hipError_t launch_rerank(const RerankParams& p, int metric, hipStream_t s);
+// The k best of every list instead of the best one: `out` is [nq x k] (ascending (distance, pop index); 0xFFFFFFFF from column count on),
+// `out_dist` (optional) the distances' bits beside it (+inf from column count on).  1 <= k <= cand_stride; one wavefront per query.
+struct RerankTopkParams : RerankParams {
+    uint32_t k;
+    float* out_dist;         // [nq x k] or nullptr
+};
+// (LDS of a workgroup: the staged query, cand_stride 8-byte keys -- an even number of slots: they are swept two at a time -- and 4-byte distances)
+constexpr uint32_t rerank_topk_key_slots(uint32_t cand_stride) { return (cand_stride + 1u) & ~1u; }
+size_t rerank_topk_lds(uint32_t dstride, uint32_t cand_stride);
+hipError_t launch_rerank_topk(const RerankTopkParams& p, int metric, hipStream_t s);
 // diagnostic (tests): one batch merge of a sorted list [size] with up to 64 survivor keys (~0 = none)
 hipError_t launch_debug_merge(int regs, const uint64_t* entries, int size, const uint64_t* surv, int ef, uint64_t* out,
                               int* out_size, hipStream_t s);

@@ -1,4 +1,4 @@
-// lanes.cpp -- gbnns_search_ex and the batches-in-flight machinery: lanes (workspace + internal stream + done events), the fork /
+// lanes.cpp -- gbnns_search_ex / gbnns_search_topk and the batches-in-flight machinery: lanes (workspace + internal stream + done events), the fork /
 // join events between the caller's stream and the lanes, gbnns_index_wait / _join, gbnns_search_batch.  Cut out of api.cpp in round 5.
 
 #include "api_internal.h"
@@ -69,11 +69,8 @@ int flush_joins(gbnns_index* ix, size_t keep) {
 
 int flush_join(gbnns_index* ix) { return flush_joins(ix, 0); }
 
-}  // namespace gbnns_api
-
-extern "C" {
-
-int gbnns_search_ex(gbnns_index* ix, const gbnns_search_args* a) {
+// One search call: validation, the layout over the lanes, the batch (search_core).  `topk`: gbnns_search_topk's extra outputs.
+int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk) {
     if (!ix || !a) return fail(GBNNS_ERR_INVALID, "null argument");
     if (a->struct_size != sizeof(gbnns_search_args))
         return fail(GBNNS_ERR_INVALID, "gbnns_search_args.struct_size mismatch (%u != %zu)",
@@ -97,6 +94,16 @@ int gbnns_search_ex(gbnns_index* ix, const gbnns_search_args* a) {
     const uint32_t n_ent = a->n_entries ? a->n_entries : 1u;
     if (n_ent > 1 && !a->entry_ids) return fail(GBNNS_ERR_INVALID, "n_entries > 1 needs entry_ids");
     if (n_ent > 4096) return fail(GBNNS_ERR_INVALID, "n_entries too large");
+    if (topk) {
+        if (a->mode == GBNNS_MODE_PLAIN)
+            return fail(GBNNS_ERR_INVALID, "gbnns_search_topk: NET / LOWQ only (a PLAIN walk's out_cand / out_cand_dist are the answer in the walked space)");
+        if (!topk->ids) return fail(GBNNS_ERR_INVALID, "gbnns_search_topk: out_top_ids missing");
+        if (topk->k < 1 || topk->k > a->ef) return fail(GBNNS_ERR_INVALID, "gbnns_search_topk: k = %d outside 1 .. ef = %d", topk->k, a->ef);
+        const size_t lds = rerank_topk_lds(ix->d_pad, (uint32_t)a->ef);
+        if (lds > kMaxLds)
+            return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_search_topk: query + %d candidates' keys and distances need %zu bytes of LDS (limit %zu)",
+                        a->ef, lds, kMaxLds);
+    }
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t s = static_cast<hipStream_t>(a->stream);
     int rc;
@@ -111,14 +118,15 @@ int gbnns_search_ex(gbnns_index* ix, const gbnns_search_args* a) {
             {a->queries, nq * ix->d * 4}, {a->queries_low, nq * ix->d_low * 4},
             {a->entry_ids, nq * std::max<size_t>(a->n_entries, 1) * 4}, {a->out_ids, nq * 4}, {a->out_hops, nq * 4},
             {a->out_dist_calc, nq * 4}, {a->out_edges, nq * 4}, {a->out_cand, nq * kk * 4}, {a->out_cand_dist, nq * kk * 4},
-            {a->out_q_low, nq * ix->d_low * 4}};
+            {a->out_q_low, nq * ix->d_low * 4},
+            {topk ? topk->ids : nullptr, nq * (topk ? (size_t)topk->k : 0) * 4}, {topk ? topk->dist : nullptr, nq * (topk ? (size_t)topk->k : 0) * 4}};
         for (const auto& b : bufs)
             if (b.p && !pinned_alias(static_cast<const char*>(b.p), b.bytes)) n_lanes = 1;
         if (n_lanes == 1) ix->next_lane = lane;  // (the rotation did not advance)
     }
     if (n_lanes <= 1) {
         if ((rc = enter_stream(ix, s))) return rc;
-        return search_core(ix, ix->lanes[0], a, s, true);
+        return search_core(ix, ix->lanes[0], a, s, true, topk);
     }
 
     // ---- deferred join: the batch runs on lane `lane`'s internal stream ---------------------------------------
@@ -141,7 +149,7 @@ int gbnns_search_ex(gbnns_index* ix, const gbnns_search_args* a) {
     ix->in_flight = true;
     HIP_TRY(hipStreamWaitEvent(L.stream, ix->fork_ev, 0));
     g_slow.mark("fork");
-    if ((rc = search_core(ix, L, a, L.stream, false))) {
+    if ((rc = search_core(ix, L, a, L.stream, false, topk))) {
         (void)hipDeviceSynchronize();  // leave nothing in flight behind an error
         ix->in_flight = false;
         return rc;
@@ -156,6 +164,17 @@ int gbnns_search_ex(gbnns_index* ix, const gbnns_search_args* a) {
     g_slow.mark("recorded");
     g_slow.finish();
     return GBNNS_OK;
+}
+
+}  // namespace gbnns_api
+
+extern "C" {
+
+int gbnns_search_ex(gbnns_index* ix, const gbnns_search_args* a) { return search_call(ix, a, nullptr); }
+
+int gbnns_search_topk(gbnns_index* ix, const gbnns_search_args* a, int k, uint32_t* out_top_ids, float* out_top_dist) {
+    const TopkOut t{k, out_top_ids, out_top_dist};
+    return search_call(ix, a, &t);
 }
 
 int gbnns_index_wait(gbnns_index* ix, uint32_t keep) {

@@ -1,5 +1,6 @@
 // rerank.hip -- the stand-alone re-rank kernels (getRealNearest, search_function.h:105-125): gbnns_rerank, d % 8 != 0 and
-// GBNNS_FLAG_NO_FUSED_RERANK; the walk kernels re-rank their own query through the same core (walk_common.h).
+// GBNNS_FLAG_NO_FUSED_RERANK; the walk kernels re-rank their own query through the same core (walk_common.h).  And their k-answer
+// forms (gbnns_rerank_topk, gbnns_search_topk): the same distances, every one of them kept, the k smallest reported in order.
 #include "launch_util.h"
 #include "walk_common.h"
 
@@ -59,6 +60,125 @@ __global__ __launch_bounds__(64) void rerank_pair_kernel(RerankParams p) {
     if (lane == 0) p.out[qi] = (win >= 0) ? cand[win] : kInvalidId;
 }
 
+// ------------------------------------------------------------------------------------------
+// the k best of a candidate list (gbnns_rerank_topk / gbnns_search_topk; no reference function: the natural extension of
+// getRealNearest -- ascending (distance, pop index), so that column 0 is getRealNearest's answer)
+// ------------------------------------------------------------------------------------------
+// LDS behind the staged query: keys[r] = fkey(dist_r) << 32 | r (8 bytes, padded with all-ones to an even number of entries) and
+// dist[r], the distance's own bits.  The keys are unique (r is part of them), so a candidate's output column is its RANK, the number of
+// keys smaller than its own: lane l owns keys l, l + 64, ...; it sweeps the whole array -- every lane reads the same 16 bytes (two keys)
+// in the same step, which the LDS broadcasts -- and counts.  A function of the keys alone, whatever the order they were written in.
+// Every output column gets exactly one store: ranks < min(k, count) from their owners, the columns behind them the padding.
+struct TopkLds {
+    uint64_t* keys;
+    float* dist;
+};
+__device__ __forceinline__ TopkLds topk_lds(unsigned char* smem, const RerankTopkParams& p) {
+    unsigned char* at = smem + (size_t)p.dstride * 4;  // (dstride % 4 == 0: 16-byte aligned)
+    TopkLds t;
+    t.keys = reinterpret_cast<uint64_t*>(at);
+    t.dist = reinterpret_cast<float*>(at + (size_t)rerank_topk_key_slots(p.cand_stride) * 8);
+    return t;
+}
+
+// ranks of the keys lane + 64 (t0 + j), j < OWN, and their stores
+template <int OWN>
+__device__ __forceinline__ void topk_rank_and_store(const RerankTopkParams& p, const TopkLds& t, const uint32_t* cand, uint32_t qi, int cnt,
+                                                    int kk, int t0, int lane) {
+    uint64_t my[OWN];
+    int rank[OWN];
+#pragma unroll
+    for (int j = 0; j < OWN; ++j) {
+        const int r = lane + 64 * (t0 + j);
+        my[j] = r < cnt ? t.keys[r] : ~0ull;  // (all-ones: not below any key, and never stored)
+        rank[j] = 0;
+    }
+    const uint4* two = reinterpret_cast<const uint4*>(t.keys);
+    for (int i = 0; 2 * i < cnt; ++i) {  // (keys[cnt] is all-ones when cnt is odd)
+        const uint4 v = two[i];
+        const uint64_t k0 = ((uint64_t)v.y << 32) | v.x, k1 = ((uint64_t)v.w << 32) | v.z;
+#pragma unroll
+        for (int j = 0; j < OWN; ++j) rank[j] += (k0 < my[j] ? 1 : 0) + (k1 < my[j] ? 1 : 0);
+    }
+#pragma unroll
+    for (int j = 0; j < OWN; ++j) {
+        const int r = lane + 64 * (t0 + j);
+        if (r < cnt && rank[j] < kk) {
+            p.out[(size_t)qi * p.k + rank[j]] = cand[r];  // the id as given (an id >= n was read as row 0, like gbnns_rerank)
+            if (p.out_dist) p.out_dist[(size_t)qi * p.k + rank[j]] = t.dist[r];
+        }
+    }
+}
+
+__device__ __forceinline__ void topk_select(const RerankTopkParams& p, const TopkLds& t, const uint32_t* cand, uint32_t qi, int cnt, int lane) {
+    if (lane == 0 && (cnt & 1)) t.keys[cnt] = ~0ull;
+    wave_sync();  // every key and distance is in LDS
+    const int kk = cnt < (int)p.k ? cnt : (int)p.k;
+    if (cnt <= 64) {
+        topk_rank_and_store<1>(p, t, cand, qi, cnt, kk, 0, lane);
+    } else {
+        for (int t0 = 0; 64 * t0 < cnt; t0 += 4) topk_rank_and_store<4>(p, t, cand, qi, cnt, kk, t0, lane);
+    }
+    for (int c = kk + lane; c < (int)p.k; c += 64) {
+        p.out[(size_t)qi * p.k + c] = kInvalidId;
+        if (p.out_dist) p.out_dist[(size_t)qi * p.k + c] = __builtin_inff();
+    }
+}
+
+// a count outside [0, cand_stride] (DEVICE buffers are not validated) must not reach past the row or the LDS arrays sized by the stride
+__device__ __forceinline__ int topk_count(const RerankTopkParams& p, uint32_t qi) {
+    const int c = p.count[qi];
+    return c < 0 ? 0 : (c > (int)p.cand_stride ? (int)p.cand_stride : c);
+}
+
+// a lane per row (d % 8 != 0 for the dot metric, d % 4 != 0 for L2): rerank_kernel's distances
+template <int METRIC>
+__global__ __launch_bounds__(64) void rerank_topk_kernel(RerankTopkParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = lane_id();
+    const uint32_t qi = blockIdx.x;
+    float* qf = reinterpret_cast<float*>(smem);
+    const float4* qs = reinterpret_cast<const float4*>(qf);
+    const TopkLds t = topk_lds(smem, p);
+    for (uint32_t i = lane; i < p.dstride; i += 64)
+        qf[i] = (i < p.dim) ? p.q[(size_t)qi * p.qstride + i] : 0.f;
+    wave_sync();
+    const int cnt = topk_count(p, qi);
+    const uint32_t* cand = p.cand + (size_t)qi * p.cand_stride;
+    for (int base = 0; base < cnt; base += 64) {
+        const int r = base + lane;
+        if (r < cnt) {
+            uint32_t id = cand[r];
+            id = id < p.n ? id : 0u;  // (never dereference an id outside the table)
+            const float dv = metric_dist<METRIC>(
+                reinterpret_cast<const float4*>(p.db + (size_t)id * p.dstride), qs, p.dim);
+            t.keys[r] = ((uint64_t)fkey(dv) << 32) | (uint32_t)r;
+            t.dist[r] = dv;
+        }
+    }
+    topk_select(p, t, cand, qi, cnt, lane);
+}
+
+// the pair form (rerank_pairs_core, all its shapes): the core's sink keeps what rerank_pair_kernel folds into a minimum
+template <int METRIC>
+__global__ __launch_bounds__(64) void rerank_topk_pair_kernel(RerankTopkParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = lane_id();
+    const uint32_t qi = blockIdx.x;
+    const int cnt = topk_count(p, qi);
+    const uint32_t* cand = p.cand + (size_t)qi * p.cand_stride;
+    const TopkLds t = topk_lds(smem, p);
+    RerankSrc a{p.q, p.qstride, p.db, p.dstride, p.dim, p.n};
+    auto id_at = [&](int r) { return cand[r]; };
+    auto keep = [&](int r, float dv) {
+        t.keys[r] = ((uint64_t)fkey(dv) << 32) | (uint32_t)r;
+        t.dist[r] = dv;
+    };
+    if (METRIC == 0 && p.dim >= 384u) rerank_pairs_core<METRIC, 24>(a, qi, cnt, reinterpret_cast<float*>(smem), lane, id_at, 0, 1, nullptr, keep);
+    else rerank_pairs_core<METRIC>(a, qi, cnt, reinterpret_cast<float*>(smem), lane, id_at, 0, 1, nullptr, keep);
+    topk_select(p, t, cand, qi, cnt, lane);
+}
+
 }  // namespace
 
 hipError_t launch_rerank(const RerankParams& p, int metric, hipStream_t s) {
@@ -87,6 +207,27 @@ hipError_t launch_rerank(const RerankParams& p, int metric, hipStream_t s) {
         hipLaunchKernelGGL((rerank_kernel<0>), dim3(p.nq), dim3(64), lds, s, p);
     }
     return hipGetLastError();
+}
+
+size_t rerank_topk_lds(uint32_t dstride, uint32_t cand_stride) {
+    return (size_t)dstride * 4 + (size_t)rerank_topk_key_slots(cand_stride) * 8 + (size_t)cand_stride * 4;
+}
+
+template <typename K>
+static hipError_t launch_topk(K kernel, const RerankTopkParams& p, size_t lds, hipStream_t s) {
+    const hipError_t e = set_lds(kernel, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(p.nq), dim3(64), lds, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_rerank_topk(const RerankTopkParams& p, int metric, hipStream_t s) {
+    if (p.nq == 0) return hipSuccess;
+    if (p.k == 0 || p.k > p.cand_stride) return hipErrorInvalidValue;
+    const size_t lds = rerank_topk_lds(p.dstride, p.cand_stride);
+    const bool pairs = p.dim > 0 && (p.dim % 8 == 0 || (metric == 0 && p.dim % 4 == 0));  // as launch_rerank
+    if (metric == 1) return pairs ? launch_topk(rerank_topk_pair_kernel<1>, p, lds, s) : launch_topk(rerank_topk_kernel<1>, p, lds, s);
+    return pairs ? launch_topk(rerank_topk_pair_kernel<0>, p, lds, s) : launch_topk(rerank_topk_kernel<0>, p, lds, s);
 }
 
 }  // namespace gbnns

@@ -9,8 +9,9 @@ using namespace gbnns_api;
 namespace gbnns_api {
 
 // One (sub-)batch on one lane's workspace, enqueued on stream s; arguments validated by gbnns_search_ex.  With HOST
-// buffers the copies in and out are enqueued on s too and, when sync_host, waited for.
-int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_t s, bool sync_host) {
+// buffers the copies in and out are enqueued on s too and, when sync_host, waited for.  `topk` (optional, NET / LOWQ): the k best of
+// each query's candidates go to its arrays as well (rerank_topk kernels, behind stage 3).
+int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_t s, bool sync_host, const TopkOut* topk) {
     int rc;
     const uint32_t n_ent = a->n_entries ? a->n_entries : 1u;
     const bool host = a->mem_kind == GBNNS_MEM_HOST;
@@ -37,6 +38,10 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
         if ((rc = L.out.ensure((size_t)nq * 4))) return rc;
     if (host && a->out_edges)
         if ((rc = L.edges.ensure((size_t)nq * 4))) return rc;
+    if (host && topk) {
+        if ((rc = L.top_ids.ensure((size_t)nq * topk->k * 4))) return rc;
+        if (topk->dist && (rc = L.top_dist.ensure((size_t)nq * topk->k * 4))) return rc;
+    }
     // general-kernel slots: visited bits + tie bits (n / 4 bytes per slot) and the result list -- 16 n bytes + 512 ef
     // per handle in all (see gbnns.h, "Device memory")
     const uint32_t bitmap_words = ((uint32_t)((ix->n + 31) / 32) + 3u) & ~3u;  // per slot; a multiple of 4 words: slots stay 16-B aligned (the bitmap pass clears with 16-B stores)
@@ -399,6 +404,17 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
         r.cand = w.cand; r.cand_stride = cstride; r.count = w.count; r.nq = nq; r.n = (uint32_t)ix->n; r.out = out_dev;
         HIP_TRY(launch_rerank(r, ix->metric, s));
     }
+    // ... and the k best of the same candidates (gbnns_search_topk): every first pass, the retry pass and the general kernel leave the
+    // candidate row and its count behind, whether they re-ranked their query themselves or not
+    RerankTopkParams tk{};
+    if (topk) {
+        tk.q = q_dev; tk.qstride = ix->d; tk.db = ix->db; tk.dstride = ix->d_pad; tk.dim = ix->d;
+        tk.cand = w.cand; tk.cand_stride = cstride; tk.count = w.count; tk.nq = nq; tk.n = (uint32_t)ix->n;
+        tk.k = (uint32_t)topk->k;
+        tk.out = host ? L.top_ids.as<uint32_t>() : topk->ids;
+        tk.out_dist = topk->dist ? (host ? L.top_dist.as<float>() : topk->dist) : nullptr;
+        HIP_TRY(launch_rerank_topk(tk, ix->metric, s));
+    }
     if (prof) {
         HIP_TRY(hipEventRecord(pc.ev[4], s));
         ix->pending.push_back(pc);
@@ -420,6 +436,11 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
         if (a->out_edges && !edges_alias && (rc = host_copy_out(L, a->out_edges, w.edges, b4, b4, 1, s))) return rc;
         if (a->out_cand && (rc = host_copy_out(L, a->out_cand, w.cand, bc, bc, 1, s))) return rc;
         if (a->out_cand_dist && (rc = host_copy_out(L, a->out_cand_dist, w.cand_dist, bc, bc, 1, s))) return rc;
+        if (topk) {
+            const size_t bk = (size_t)nq * topk->k * 4;
+            if ((rc = host_copy_out(L, topk->ids, tk.out, bk, bk, 1, s))) return rc;
+            if (topk->dist && (rc = host_copy_out(L, topk->dist, tk.out_dist, bk, bk, 1, s))) return rc;
+        }
         g_slow.mark("copy_out");
         if (sync_host) {
             HIP_TRY(hipStreamSynchronize(s));

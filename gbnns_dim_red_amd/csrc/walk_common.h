@@ -514,9 +514,14 @@ __device__ __forceinline__ float dpp_from_odd(float x) {  // even lane <- its od
 // `pass0` / `pass_step` (walk_coop.hip: two wavefronts share a query's candidates): this wavefront takes the 32-candidate passes
 // pass0, pass0 + pass_step, ...; `best_key` (optional) receives min (fkey(dist) << 32 | pop index) over them, all-ones when it
 // saw none -- the minimum over the wavefronts' keys is the minimum over all candidates.
-template <int METRIC, int DEEP = 8, typename IdAt>
+// `sink(r, dv)` (optional) receives every candidate's finished distance, in the lane that owns the sum -- the odd lane of the pair for
+// L2, the even lane for the negative dot product -- before it is folded into the minimum (rerank_topk_pair_kernel keeps them all).
+struct RerankNoSink {
+    __device__ __forceinline__ void operator()(int, float) const {}
+};
+template <int METRIC, int DEEP = 8, typename IdAt, typename Sink = RerankNoSink>
 __device__ __forceinline__ int rerank_pairs_core(const RerankSrc& a, uint32_t qi, int cnt, float* qf, int lane, IdAt id_at,
-                                                 int pass0 = 0, int pass_step = 1, uint64_t* best_key = nullptr) {
+                                                 int pass0 = 0, int pass_step = 1, uint64_t* best_key = nullptr, Sink sink = Sink{}) {
     const uint32_t half = (uint32_t)lane & 1u, slot = (uint32_t)lane >> 1;
     const float4* qs = reinterpret_cast<const float4*>(qf);
     for (uint32_t i = lane; i < a.dstride; i += 64)
@@ -553,6 +558,7 @@ __device__ __forceinline__ int rerank_pairs_core(const RerankSrc& a, uint32_t qi
             const float m2 = dpp_from_odd(c2) + c2, m3 = dpp_from_odd(c3) + c3;
             const float dv = -((m0 + m1) + (m2 + m3));
             if (valid && !half) {
+                sink(r, dv);
                 const uint64_t kv = ((uint64_t)fkey(dv) << 32) | (uint32_t)r;
                 bestk = kv < bestk ? kv : bestk;
             }
@@ -628,6 +634,7 @@ __device__ __forceinline__ int rerank_pairs_core(const RerankSrc& a, uint32_t qi
         // the odd lane's v holds all steps: in the even lane `u` is the valid one, in the odd lane `v`
         const float dv = ((v0 + v1) + v2) + v3;
         if (valid && half) {
+            sink(r, dv);
             const uint64_t kv = ((uint64_t)fkey(dv) << 32) | (uint32_t)r;
             bestk = kv < bestk ? kv : bestk;
         }

@@ -247,6 +247,32 @@ int gbnns_rerank(gbnns_index* index, const float* queries, uint64_t n_q, const u
                  uint32_t cand_stride, const int32_t* count, uint32_t* out_ids, int mem_kind,
                  void* stream);
 
+/* Candidates in, k best out -- the k-answer form of gbnns_rerank.  The reference has no such function (getRealNearest
+ * returns one id); this is its natural extension, chosen so that k = 1 reproduces it.  With dist_r = Dist(db[cand_r], q_i)
+ * in the space of `db`, in the reference's arithmetic (the very bits gbnns_rerank minimises over) and r = 0 .. count[i] - 1
+ * the pop index, row i of out_ids [n_q x k] holds the min(k, count[i]) smallest candidates in ascending order of
+ * (dist_r, r): distances compare as everywhere in the library (-0 equals +0), the lower pop index wins ties.  Column 0
+ * is therefore always exactly the id gbnns_rerank -- or a search's fused re-rank -- returns for that list.  out_dist
+ * (optional, [n_q x k]) receives each distance's own bit pattern as computed.  Columns from count[i] on hold 0xFFFFFFFF
+ * and +inf; a candidate that occurs twice is reported twice.  1 <= k <= cand_stride (GBNNS_ERR_INVALID).  HOST buffers are
+ * validated (an id >= n or a count above the stride: GBNNS_ERR_INVALID) and the call is synchronous; DEVICE buffers are
+ * enqueued on `stream`, an id >= n is read as row 0 and reported as given, as in gbnns_rerank.  One wavefront per query
+ * keeps the list's keys and distances in LDS beside the query: a shape whose 4 * d + 12 * cand_stride bytes exceed the
+ * 160 KiB of a workgroup is refused (GBNNS_ERR_UNSUPPORTED). */
+int gbnns_rerank_topk(gbnns_index* index, const float* queries, uint64_t n_q, const uint32_t* cand,
+                      uint32_t cand_stride, const int32_t* count, int k, uint32_t* out_ids, float* out_dist,
+                      int mem_kind, void* stream);
+
+/* gbnns_search_ex plus the k best of each query's ef candidates in the original space (the contract of
+ * gbnns_rerank_topk over the walk's candidate list in pop order): out_top_ids [n_q x k], out_top_dist (optional)
+ * likewise, buffers of args->mem_kind.  Everything gbnns_search_ex writes is written as before, the very same search
+ * runs, and out_top_ids[i * k] == args->out_ids[i]; a query with an entry id >= n gets a row of 0xFFFFFFFF / +inf.
+ * NET / LOWQ only: a PLAIN walk's out_cand / out_cand_dist already are the answer in the walked space
+ * (GBNNS_ERR_INVALID).  1 <= k <= ef.  GBNNS_FLAG_DEFER_JOIN holds as for gbnns_search_ex (HOST buffers: the two arrays
+ * must be page-locked too); the selection runs behind the re-rank and is part of gbnns_profile.rerank_ms. */
+int gbnns_search_topk(gbnns_index* index, const gbnns_search_args* args, int k, uint32_t* out_top_ids,
+                      float* out_top_dist);
+
 /* Per-kernel device timing (hipEvent pairs on the launch stream), accumulated since the last
  * reset.  Reading synchronises the recorded events. */
 typedef struct {
