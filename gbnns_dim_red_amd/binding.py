@@ -23,6 +23,7 @@ FLAG_BITMAP_PASS = 32
 FLAG_SERIAL = 64
 FLAG_DEFER_JOIN = 128
 FLAG_MFMA_PROJECTION = 256
+FLAG_HALF_ROWS = 512
 
 # every symbol include/gbnns.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -34,6 +35,7 @@ SYMBOLS = [
     "gbnns_multi_stream", "gbnns_multi_set_aux_graph", "gbnns_shard_bounds", "gbnns_multi_search_ex",
     "gbnns_multi_search_device", "gbnns_multi_synchronize", "gbnns_multi_last_error",
     "gbnns_multi_rccl_single_rank", "gbnns_multi_rccl_version",
+    "gbnns_round_to_half", "gbnns_index_enable_half_rows", "gbnns_index_low_rows",
 ]
 
 
@@ -154,6 +156,9 @@ def load_library():
     lib.gbnns_multi_rccl_version.argtypes = [C.c_void_p]
     lib.gbnns_shard_bounds.argtypes = [C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.gbnns_shard_bounds.restype = None
+    lib.gbnns_round_to_half.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.gbnns_index_enable_half_rows.argtypes = [C.c_void_p]
+    lib.gbnns_index_low_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.gbnns_index_d_low.argtypes = [C.c_void_p]
     lib.gbnns_index_d_low.restype = C.c_uint32
     _lib = lib
@@ -175,6 +180,17 @@ def device_count():
 
 def _is_dev(x):
     return hasattr(x, "data_ptr")
+
+
+def round_to_half(a):
+    """gbnns_round_to_half (host code): (bits uint16, widened float32), both of a's shape -- a rounded to IEEE binary16, nearest even.
+    GbnnsError when a value is not finite or rounds out of the binary16 range.  widened is the table R that
+    FLAG_HALF_ROWS searches walk when a is db_low."""
+    a = _host(a, np.float32)
+    bits = np.empty(a.shape, np.uint16)
+    wide = np.empty(a.shape, np.float32)
+    _check(load_library().gbnns_round_to_half(a.ctypes.data, a.size, bits.ctypes.data, wide.ctypes.data))
+    return bits, wide
 
 
 def _ptr(x):
@@ -431,6 +447,22 @@ class Index:
         if off.shape[0] != self.n + 1:
             raise ValueError("auxiliary graph offsets must have n+1 entries")
         _check(self._lib.gbnns_index_set_aux_graph(self._h, _ptr(off), _ptr(nbr)))
+
+    def enable_half_rows(self):
+        """gbnns_index_enable_half_rows: builds the binary16 table (and its float32 copy) that FLAG_HALF_ROWS searches walk."""
+        _check(self._lib.gbnns_index_enable_half_rows(self._h))
+
+    def low_rows(self, device=False):
+        """gbnns_index_low_rows: R = float32(float16(db_low)) [n x d_low] as a numpy array, or (device=True) a torch tensor on the
+        index's device (enqueued on the current stream)."""
+        if device:
+            import torch
+            out = torch.empty((self.n, self.d_low), dtype=torch.float32, device=torch.device("cuda", self.device))
+            _check(self._lib.gbnns_index_low_rows(self._h, out.data_ptr(), MEM_DEVICE, torch.cuda.current_stream(out.device).cuda_stream))
+            return out
+        out = np.empty((self.n, self.d_low), np.float32)
+        _check(self._lib.gbnns_index_low_rows(self._h, out.ctypes.data, MEM_HOST, None))
+        return out
 
     def close(self):
         if self._h:

@@ -172,6 +172,10 @@ struct gbnns_index {
     const float* db_low = nullptr;  // [n x dl_pad]
     DevBuf db_own, db_low_own, ell, net, aux_ell;
     DevBuf net_mfma;                // the net repacked for the one-launch matrix-core projection (filled on the option's first use)
+    // GBNNS_FLAG_HALF_ROWS (gbnns_index_enable_half_rows): R = float32(float16(db_low)) as binary16 rows [n x round_up(d_low, 8)], zero padded,
+    // and as float32 rows in db_low's own layout [n x dl_pad]; db_low itself stays, for the searches without the flag
+    DevBuf low_half, low_r;
+    bool half_ready = false;
     bool net_mfma_ready = false;
     uint32_t ell_stride = 0, aux_stride = 0;
     bool has_aux = false;

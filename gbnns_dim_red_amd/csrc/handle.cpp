@@ -9,6 +9,8 @@
 
 #include "api_internal.h"
 
+#include <cmath>
+
 using namespace gbnns;
 using namespace gbnns_api;
 
@@ -470,7 +472,7 @@ int gbnns_index_destroy(gbnns_index* ix) {
         if (L.stream) (void)hipStreamDestroy(L.stream);
         for (int i = 0; DevBuf* b = L.bufs(i); ++i) b->release();
     }
-    DevBuf* bufs[] = {&ix->db_own, &ix->db_low_own, &ix->ell, &ix->aux_ell, &ix->net, &ix->net_mfma};
+    DevBuf* bufs[] = {&ix->db_own, &ix->db_low_own, &ix->ell, &ix->aux_ell, &ix->net, &ix->net_mfma, &ix->low_half, &ix->low_r};
     for (DevBuf* b : bufs) b->release();
     delete ix;
     return GBNNS_OK;
@@ -649,6 +651,111 @@ int gbnns_debug_walk_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n
     if (!planned) return fail(GBNNS_ERR_INTERNAL, "gbnns_debug_walk_plan: no kernel instance for the plan");
     std::snprintf(name, name_bytes, "%s", planned);
     *lds_bytes = plan.lds_fixed;
+    return GBNNS_OK;
+}
+
+// ---- GBNNS_FLAG_HALF_ROWS: the rounded table ---------------------------------------------------------------------------------------------
+
+namespace {
+// float32 -> binary16, round to nearest, ties to even; subnormals and the sign of zero kept.  false: not finite, or rounds out of range.
+bool float_to_half_bits(float f, uint16_t& h) {
+    uint32_t x;
+    std::memcpy(&x, &f, 4);
+    const uint32_t sign = (x >> 16) & 0x8000u, ax = x & 0x7FFFFFFFu;
+    if (ax >= 0x477FF000u) return false;  // |f| >= 65 520 = the midpoint between 65 504 and 2^16 (ties to even: up), infinities, NaNs
+    const uint32_t e = ax >> 23;
+    uint32_t q, rem, halfway;
+    if (e < 113u) {  // |f| < 2^-14: a binary16 subnormal (units of 2^-24) or zero
+        const uint32_t m = e ? ((ax & 0x7FFFFFu) | 0x800000u) : 0u, shift = 126u - e;  // |f| = m * 2^(e - 150) = m * 2^-shift units
+        if (shift > 25u || m == 0u) { h = (uint16_t)sign; return true; }           // (m < 2^24: below half a unit)
+        q = m >> shift; rem = m & ((1u << shift) - 1u); halfway = 1u << (shift - 1u);
+    } else {
+        q = ((e - 112u) << 10) | ((ax & 0x7FFFFFu) >> 13); rem = ax & 0x1FFFu; halfway = 0x1000u;
+    }
+    if (rem > halfway || (rem == halfway && (q & 1u))) q += 1u;  // (a carry out of the mantissa is the next exponent's first value)
+    h = (uint16_t)(sign | q);
+    return true;
+}
+float half_bits_to_float(uint16_t h) {
+    const uint32_t e = (h >> 10) & 31u, m = h & 0x3FFu;
+    const float v = e ? std::ldexp((float)(1024u + m), (int)e - 25) : std::ldexp((float)m, -24);
+    return (h & 0x8000u) ? -v : v;
+}
+}  // namespace
+
+int gbnns_round_to_half(const float* in, uint64_t count, uint16_t* out_bits, float* out_widened) {
+    if (!in && count) return fail(GBNNS_ERR_INVALID, "gbnns_round_to_half: null input");
+    for (uint64_t i = 0; i < count; ++i) {
+        uint16_t h;
+        if (!float_to_half_bits(in[i], h))
+            return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_round_to_half: value %llu (%g) is not finite or rounds out of the binary16 range",
+                        (unsigned long long)i, (double)in[i]);
+        if (out_bits) out_bits[i] = h;
+        if (out_widened) out_widened[i] = half_bits_to_float(h);
+    }
+    return GBNNS_OK;
+}
+
+int gbnns_index_enable_half_rows(gbnns_index* ix) {
+    if (!ix) return fail(GBNNS_ERR_INVALID, "null argument");
+    if (!ix->db_low) return fail(GBNNS_ERR_INVALID, "gbnns_index_enable_half_rows: the index has no db_low");
+    if (ix->half_ready) return GBNNS_OK;
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(hipDeviceSynchronize());  // (a borrowed db_low may have been written on any stream)
+    const uint32_t hstride = round_up(ix->d_low, 8);
+    // exactly sized (DevBuf::ensure adds slack for buffers that grow): 0.5 + 1 times the low-dimensional table
+    DevBuf h, r, flag;
+    auto alloc = [](DevBuf& b, size_t bytes) -> int {
+        const hipError_t e = hipMalloc(&b.p, bytes);
+        if (e != hipSuccess) {
+            b.p = nullptr;
+            return fail(GBNNS_ERR_OOM, "hipMalloc(%zu): %s", bytes, hipGetErrorString(e));
+        }
+        b.bytes = bytes;
+        return GBNNS_OK;
+    };
+    int rc = alloc(h, (size_t)ix->n * hstride * 2);
+    if (!rc) rc = alloc(r, (size_t)ix->n * ix->dl_pad * 4);
+    if (!rc) rc = alloc(flag, 4);
+    uint32_t bad = 0xFFFFFFFFu;
+    if (!rc) {
+        hipError_t e = hipMemcpy(flag.p, &bad, 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e == hipSuccess)
+            e = launch_half_rows_convert(ix->db_low, ix->dl_pad, ix->d_low, ix->n, h.as<uint16_t>(), hstride, r.as<float>(), ix->dl_pad, flag.as<uint32_t>(), nullptr);
+        if (e == hipSuccess) e = hipMemcpy(&bad, flag.p, 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) rc = fail(GBNNS_ERR_HIP, "gbnns_index_enable_half_rows: %s", hipGetErrorString(e));
+    }
+    if (!rc && bad != 0xFFFFFFFFu)
+        rc = fail(GBNNS_ERR_UNSUPPORTED, "gbnns_index_enable_half_rows: row %u of db_low holds a value that is not finite or rounds out of the binary16 range", bad);
+    flag.release();
+    if (rc) {  // the handle stays as it was
+        h.release();
+        r.release();
+        return rc;
+    }
+    ix->low_half = h;
+    ix->low_r = r;
+    ix->half_ready = true;
+    return GBNNS_OK;
+}
+
+int gbnns_index_low_rows(gbnns_index* ix, float* out, int mem_kind, void* stream) {
+    if (!ix || !out) return fail(GBNNS_ERR_INVALID, "null argument");
+    if (mem_kind != GBNNS_MEM_HOST && mem_kind != GBNNS_MEM_DEVICE) return fail(GBNNS_ERR_INVALID, "unknown mem_kind %d", mem_kind);
+    if (!ix->half_ready) return fail(GBNNS_ERR_INVALID, "gbnns_index_low_rows: gbnns_index_enable_half_rows has not been called");
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t spitch = (size_t)ix->dl_pad * 4, width = (size_t)ix->d_low * 4;
+    if (mem_kind == GBNNS_MEM_DEVICE) {
+        HIP_TRY(hipMemcpy2DAsync(out, width, ix->low_r.p, spitch, width, ix->n, hipMemcpyDeviceToDevice, s));
+        return GBNNS_OK;
+    }
+    if (int rc = enter_stream(ix, s)) return rc;  // (lane 0's staging buffer is ordered by stream order, like the rest of the workspace)
+    if (int rc = host_copy_out(ix->lanes[0], out, ix->low_r.p, spitch, width, ix->n, s)) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    ix->in_flight = false;
     return GBNNS_OK;
 }
 

@@ -88,7 +88,10 @@ struct WalkParams {
     int32_t coop;            // 1: the first pass is the two-wavefront walk (walk_coop.hip: kCoopExtraLds, walk_plan.h, more bytes of LDS per query)
     int32_t force_wide;      // diagnostic: treat the index as a large one (64-bit offsets, 4-byte visited-set slots)
     unsigned long long* stamps;  // diagnostic builds only (GBNNS_STAMPS): [32] segment cycle sums / histograms
-    int32_t stamps_on;           // 1 in diagnostic builds: use the instrumented generic kernel
+    int32_t stamps_on;           // 1 in diagnostic builds: use the instrumented generic kernel    // GBNNS_FLAG_HALF_ROWS (last, so that no other field moves): the walked table is R = float32(float16(db_low)) -- `db` above is then the
+    // float32 copy of R, which every kernel but the half instances reads
+    const void* db_h;        // [n x dstride] binary16 rows of R (dstride a multiple of 8, no padding), or nullptr
+    int32_t half_rows;       // 1: the first pass takes a half instance where the plan has one (walk_plan.cpp)
 };
 
 // `form` of a visited set: 0 = 4-byte slots, 1 = five 24-bit ids per 16-byte bucket, 2 = quotient form (seven 16-bit entries)
@@ -102,6 +105,11 @@ const char* walk_plan_name(const WalkPlan& pl);   // printable name of the plan'
 const char* walk_first_pass_name(hipStream_t s);  // (mangled) name of the first-pass kernel this thread launched last
 const char* walk_retry_pass_name(hipStream_t s);  // ... and of the retry-pass kernel
 hipError_t launch_walk_general(const WalkParams& p, int metric, hipStream_t s);
+// GBNNS_FLAG_HALF_ROWS (walk_half.hip): src [n x sstride] (dim coordinates a row) -> out_h [n x hstride] binary16 bits, round to nearest even,
+// columns from dim on zero; out_f [n x fstride] the same values widened back (fstride <= hstride).  *bad_row (preset to 0xFFFFFFFF) receives the
+// lowest row that holds a coordinate which is not finite or rounds out of the binary16 range.
+hipError_t launch_half_rows_convert(const float* src, uint32_t sstride, uint32_t dim, uint64_t n, uint16_t* out_h, uint32_t hstride, float* out_f,
+                                    uint32_t fstride, uint32_t* bad_row, hipStream_t s);
 
 // Re-rank (search_function.h:105-125).  One query per wavefront, one candidate per lane.
 struct RerankParams {

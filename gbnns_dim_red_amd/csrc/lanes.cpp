@@ -89,6 +89,11 @@ int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk
         return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_LLF needs GBNNS_FLAG_AUX_GRAPH");
     if ((a->flags & GBNNS_FLAG_AUX_GRAPH) && !ix->has_aux)
         return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_AUX_GRAPH without gbnns_index_set_aux_graph");
+    if (a->flags & GBNNS_FLAG_HALF_ROWS) {
+        if (a->mode == GBNNS_MODE_PLAIN)
+            return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_HALF_ROWS: NET / LOWQ only (a PLAIN walk's space is the answer space)");
+        if (!ix->half_ready) return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_HALF_ROWS without gbnns_index_enable_half_rows");
+    }
     if (a->hash_capacity != 0 && a->hash_capacity < 128)
         return fail(GBNNS_ERR_INVALID, "hash_capacity must be 0 (auto) or >= 128");
     const uint32_t n_ent = a->n_entries ? a->n_entries : 1u;

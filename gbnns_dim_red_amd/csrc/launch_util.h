@@ -61,5 +61,6 @@ const WalkEntry* walk_wide3_entry(const WalkInstance& k);
 const WalkEntry* walk_hot_entry(const WalkInstance& k);
 const WalkEntry* walk_coop_entry(const WalkInstance& k);
 const WalkEntry* walk_bitmap_entry(const WalkInstance& k);
+const WalkEntry* walk_half_entry(const WalkInstance& k);
 
 }  // namespace gbnns

@@ -98,6 +98,11 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
             w.q = a->queries_low; w.qstride = ix->d_low;
         }
         w.db = ix->db_low; w.dstride = ix->dl_pad; w.dim = ix->d_low;
+        if (a->flags & GBNNS_FLAG_HALF_ROWS) {
+            // the walked table is R = float32(float16(db_low)): every kernel reads its float32 copy, in db_low's layout, but the half
+            // instances of the first pass (walk_plan.cpp), whose hops gather the 2-byte rows
+            w.db = ix->low_r.as<float>(); w.db_h = ix->low_half.p; w.half_rows = 1;
+        }
         if (a->out_q_low && a->mode == GBNNS_MODE_NET) {
             if (host) {
                 if ((rc = host_copy_out(L, a->out_q_low, ql, (size_t)ix->dl_pad * 4, (size_t)ix->d_low * 4, nq, s))) return rc;
@@ -191,7 +196,8 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
     }
     w.force_wide = (a->flags & GBNNS_FLAG_WIDE_INDEX) ? 1 : 0;
     const bool aux = (a->flags & GBNNS_FLAG_AUX_GRAPH) != 0;
-    const int skey = (ef * 8 + a->mode * 2 + (aux ? 1 : 0)) * 2 + w.force_wide;  // sizing statistics are kept per (ef, mode, aux, wide)
+    // sizing statistics are kept per (ef, mode, aux, wide, half rows: another table, other walks)
+    const int skey = ((ef * 8 + a->mode * 2 + (aux ? 1 : 0)) * 2 + w.force_wide) | (w.half_rows ? 1 << 30 : 0);
     const int calm = ix->calm_streak.count(skey) ? ix->calm_streak[skey] : 0;
     if (aux) {
         w.aux_ell = ix->aux_ell.as<uint32_t>(); w.aux_stride = ix->aux_stride;

@@ -177,7 +177,10 @@ __global__ __launch_bounds__(64) void walk_bitmap_kernel(WalkParams p) {
 // hops < hops_bound), then -- unless llf and that step inserted something -- its main row.
 // BITMAP: visited set = one bit per node in HBM (`bitmap`, this wavefront's slot), see walk_bitmap_kernel.
 // LATE: rows requested after the visited test -- 1 always, 0 never, -1 by WalkParams::late_rows (both orders in the kernel)
-template <int METRIC, int STEPS, bool OFF32, int R, bool ONE_CHUNK = false, bool AUX = false, bool BITMAP = false, bool QLDS_W = false, int LATE = -1>
+// HALF: the hop's rows come from the 2-byte table WalkParams::db_h (walk_half.hip; pair-form instances of a compact index) -- p.db is then
+// the float32 copy of the same table R, which the entry row is read from; nothing else differs
+template <int METRIC, int STEPS, bool OFF32, int R, bool ONE_CHUNK = false, bool AUX = false, bool BITMAP = false, bool QLDS_W = false, int LATE = -1,
+          bool HALF = false>
 __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, unsigned char* smem,
                                              uint32_t* ovf_count, uint32_t* ovf_list, uint32_t* bitmap = nullptr) {
     static_assert(!(AUX && ONE_CHUNK), "auxiliary rows have their own length");
@@ -197,6 +200,7 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
     constexpr uint32_t kRowBytes = (uint32_t)STEPS * 16u;
     constexpr uint32_t kChunk = kPair ? 32u : 64u;           // adjacency slots per pass
     constexpr uint64_t kSlotLanes = kPair ? 0x5555555555555555ull : ~0ull;  // lanes that own a slot
+    static_assert(!HALF || (kPair && OFF32 && !QLDS_W), "HALF: pair-form instances of a compact index");
     const int lane = lane_id();
     const uint32_t slot = kPair ? (uint32_t)lane >> 1 : (uint32_t)lane;    // adjacency slot of this lane
     const uint32_t half = kPair ? (uint32_t)lane & 1u : 0u;
@@ -413,6 +417,7 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
             // neighbours are fetched in vain) -- or, wide rows in the pair form with WalkParams::late_rows, after it for the new ids only:
             // the 192-byte-row launch at ef = 40 moved 2.24 GB for 1.62 GB of algorithmic bytes, 6.5 TB/s -- bandwidth-bound on those
             RowRegs<kQSteps> rr;
+            HalfRowRegs<HALF ? kQSteps : 0> rh;  // (HALF: the row as loaded, packed until the distance consumes it)
             uint32_t roff = 0;  // row byte offset, kept live past the loads (see below)
             constexpr bool kLateLoad = kPair && ONE_CHUNK && STEPS >= 12 && STEPS <= 16 && LATE != 0;
             const bool late = kLateLoad && (LATE > 0 || p.late_rows != 0);
@@ -423,7 +428,12 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
                 constexpr bool kAllLanes = (kPair && (ONE_CHUNK || STEPS == 24)) || (!kPair && kQSteps >= 12);
                 const uint32_t nbl = kAllLanes ? (want ? nb : 0u) : nb;
                 const bool ld = kAllLanes || want;
-                if constexpr (OFF32) {
+                if constexpr (HALF) {  // rows of kRowBytes / 2 bytes: the same float4 pieces, two bytes a coordinate
+                    roff = nbl * (kRowBytes / 2u) + half * (kAlt ? 8u : kRowBytes / 4u);
+                    const void* rp = reinterpret_cast<const char*>(p.db_h) + roff;
+                    if constexpr (kAlt) { if (ld) load_row_half_alt(rh, rp); }
+                    else { if (ld) load_row_half<kQSteps>(rh, rp); }
+                } else if constexpr (OFF32) {
                     roff = kPair ? nbl * kRowBytes + half * (kAlt ? 16u : kRowBytes / 2u) : nbl * (p.dstride * 4u);
                     const float* rp = reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.db) + roff);
                     if constexpr (kAlt) { if (ld) load_row_alt(rr, rp); }
@@ -462,6 +472,7 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
                 if (late) request_rows(__builtin_amdgcn_inverse_ballot_w64(mclaimed | mfresh));  // (both lanes of a new id's pair)
             }
             uint32_t dk = 0xFFFFFFFFu;
+            if constexpr (HALF) widen_row(rr, rh);
             if constexpr (kEarlyLoad) {
                 if constexpr (kAlt) {
                     const uint32_t kd = fkey(dot_pair_from_regs(rr, qreg.v));  // all lanes; odd lanes hold distances
@@ -581,7 +592,8 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
 // ef <= 64 whatever ef is (the R-register lists spent 28 % of a hop selecting and 30 % inserting at ef = 300).
 // LDS: [BigList: big_list_fixed_bytes(ef)][query: dstride floats][visited set | (BITMAP) re-rank scratch].
 // ONE_PASS: adjacency rows of one pass (the host checks ell_stride), no auxiliary graph -- the hop is straight-line code.
-template <int METRIC, int STEPS, bool OFF32, bool AUX = false, bool BITMAP = false, bool ONE_PASS = false, bool LATE = false>
+// HALF: as in walk_reg_one.
+template <int METRIC, int STEPS, bool OFF32, bool AUX = false, bool BITMAP = false, bool ONE_PASS = false, bool LATE = false, bool HALF = false>
 __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t qi, unsigned char* smem,
                                                  uint32_t* ovf_count, uint32_t* ovf_list, uint32_t* bitmap = nullptr) {
     constexpr bool kEarlyLoad = (STEPS > 0);
@@ -600,6 +612,7 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
     constexpr uint32_t kRowBytes = (uint32_t)STEPS * 16u;
     constexpr uint32_t kChunk = kPair ? 32u : 64u;
     constexpr uint64_t kSlotLanes = kPair ? 0x5555555555555555ull : ~0ull;
+    static_assert(!HALF || (kPair && OFF32), "HALF: pair-form instances of a compact index");
     const int lane = lane_id();
 #ifdef GBNNS_STAMPS  // diagnostic build: cycles per segment of the hop (tools/stamps.py)
     unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -637,8 +650,12 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
     for (uint32_t i = lane; i < p.dstride; i += 64)
         qf[i] = (i < p.dim) ? p.q[(size_t)qi * p.qstride + i] : 0.f;
     wave_sync();
-    RowRegs<kQSteps> qreg;
-    if constexpr (kEarlyLoad) {
+    // (half rows of 24 steps and more: the lane's query pieces are re-read from the wavefront's LDS copy every hop, as in walk_reg_wide_kernel --
+    // 72 registers of query beside 72 of squared differences are two wavefronts per SIMD; the float32 instances, bound by their rows' bytes,
+    // live with that, the half instance has half the bytes in flight per wavefront and wants the third)
+    constexpr bool kQLds = HALF && STEPS >= 24;
+    RowRegs<kQLds ? 0 : kQSteps> qreg;
+    if constexpr (kEarlyLoad && !kQLds) {
 #pragma unroll
         for (int t = 0; t < kQSteps; ++t) qreg.v[t] = kAlt ? qs[2 * t + half] : qs[kQSteps * half + t];
     }
@@ -659,6 +676,7 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
             uint32_t kd;
             if constexpr (kAlt) kd = fkey(dot_pair_from_regs(er, qreg.v));
             else if constexpr (STEPS == 8) kd = fkey_sumsq(l2_pair_from_regs(er, qreg.v));
+            else if constexpr (kQLds) kd = fkey_sumsq(l2_pair_from_regs_wide<kQSteps>(er, qs + kQSteps * half));
             else kd = fkey_sumsq(l2_pair_from_regs_wide<kQSteps>(er, qreg.v));
             k0 = readlane_u32(kd, 1);  // odd lanes hold the distance
         } else {
@@ -732,6 +750,7 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
             if (c == 0 && !is_aux) { STAMP_ADD(2, t2, t3) }
             edges += __popcll(mv & kSlotLanes);
             RowRegs<kQSteps> rr;
+            HalfRowRegs<HALF ? kQSteps : 0> rh;  // (HALF: the row as loaded, packed until the distance consumes it)
             uint32_t roff = 0;
             // the row loads of this pass; `want` = lanes whose row is needed (the others read row 0, all of them the same lines)
             auto request_rows = [&](bool want) {
@@ -742,7 +761,12 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
                 constexpr bool kAllLanes = kPair || kQSteps >= 12;
                 const uint32_t nbl = kAllLanes ? (want ? nb : 0u) : nb;
                 const bool ld = kAllLanes || want;
-                if constexpr (OFF32) {
+                if constexpr (HALF) {  // rows of kRowBytes / 2 bytes: the same float4 pieces, two bytes a coordinate
+                    roff = nbl * (kRowBytes / 2u) + half * (kAlt ? 8u : kRowBytes / 4u);
+                    const void* rp = reinterpret_cast<const char*>(p.db_h) + roff;
+                    if constexpr (kAlt) { if (ld) load_row_half_alt(rh, rp); }
+                    else { if (ld) load_row_half<kQSteps>(rh, rp); }
+                } else if constexpr (OFF32) {
                     roff = kPair ? nbl * kRowBytes + half * (kAlt ? 16u : kRowBytes / 2u) : nbl * (p.dstride * 4u);
                     const float* rp = reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.db) + roff);
                     if constexpr (kAlt) { if (ld) load_row_alt(rr, rp); }
@@ -780,12 +804,18 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
                 if (late) request_rows(__builtin_amdgcn_inverse_ballot_w64(mclaimed | mfresh));  // (both lanes of a new id's pair)
             }
             uint32_t dk = 0xFFFFFFFFu;
+            if constexpr (HALF) widen_row(rr, rh);
             if constexpr (kEarlyLoad) {
                 if constexpr (kAlt) {
                     const uint32_t kd = fkey(dot_pair_from_regs(rr, qreg.v));
                     dk = fresh ? kd : 0xFFFFFFFFu;
                 } else if constexpr (kPair && STEPS == 8) {
                     const uint32_t kd = fkey_sumsq(l2_pair_from_regs(rr, qreg.v));
+                    dk = fresh ? kd : 0xFFFFFFFFu;
+                } else if constexpr (kPair && kQLds) {
+                    const float4* ql = qs + kQSteps * half;
+                    asm volatile("" : "+v"(ql));  // (not hoisted out of the hop loop)
+                    const uint32_t kd = fkey_sumsq(l2_pair_from_regs_wide<kQSteps>(rr, ql));
                     dk = fresh ? kd : 0xFFFFFFFFu;
                 } else if constexpr (kPair) {
                     const uint32_t kd = fkey_sumsq(l2_pair_from_regs_wide<kQSteps>(rr, qreg.v));

@@ -235,6 +235,44 @@ __device__ __forceinline__ void load_row_alt(RowRegs<4>& r, const float* row) {
     for (int t = 0; t < 4; ++t) r.v[t] = r4[2 * t];
 }
 
+// Rows stored as IEEE binary16 (GBNNS_FLAG_HALF_ROWS, walk_half.hip): the walked table is R = float32(float16(db_low)), and a lane
+// loads its share of a row of the 2-byte table packed -- piece t = the four halves that widen to the float4 piece t the float32 forms
+// above load.  The row stays packed until the distance consumes it (widen_row: v_cvt_f32_f16, exact; binary16 subnormals are kept by
+// the kernels' default denormal mode), so every lane ends up with the very float4 pieces load_row / load_row_alt would have read from
+// the float32 copy of R, and the distance code is the float32 one.
+template <int STEPS>
+struct HalfRowRegs {
+    uint2 v[STEPS > 0 ? STEPS : 1];
+};
+// STEPS / 2 loads of 16 bytes: 8 * STEPS contiguous bytes of the 2-byte row
+template <int STEPS>
+__device__ __forceinline__ void load_row_half(HalfRowRegs<STEPS>& r, const void* row) {
+    static_assert(STEPS % 2 == 0, "a lane's share of a half row is whole 16-byte pieces");
+    const uint4* r4 = reinterpret_cast<const uint4*>(row);
+#pragma unroll
+    for (int t = 0; t < STEPS / 2; ++t) {
+        const uint4 x = r4[t];
+        r.v[2 * t] = make_uint2(x.x, x.y);
+        r.v[2 * t + 1] = make_uint2(x.z, x.w);
+    }
+}
+// four 8-byte loads at a stride of 16 bytes (the even or the odd float4 pieces of a 32-float row: load_row_alt)
+__device__ __forceinline__ void load_row_half_alt(HalfRowRegs<4>& r, const void* row) {
+    const uint2* r2 = reinterpret_cast<const uint2*>(row);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) r.v[t] = r2[2 * t];
+}
+__device__ __forceinline__ float half_bits_to_float(uint32_t bits16) {
+    return (float)__builtin_bit_cast(_Float16, (unsigned short)bits16);
+}
+template <int STEPS>
+__device__ __forceinline__ void widen_row(RowRegs<STEPS>& out, const HalfRowRegs<STEPS>& h) {
+#pragma unroll
+    for (int t = 0; t < STEPS; ++t)
+        out.v[t] = make_float4(half_bits_to_float(h.v[t].x & 0xFFFFu), half_bits_to_float(h.v[t].x >> 16),
+                               half_bits_to_float(h.v[t].y & 0xFFFFu), half_bits_to_float(h.v[t].y >> 16));
+}
+
 // Row address.  OFF32: every byte offset into the table fits 32 bits, so the load can use the
 // "scalar base + 32-bit lane offset" form (one address VGPR instead of two, no 64-bit multiply).
 template <bool OFF32>

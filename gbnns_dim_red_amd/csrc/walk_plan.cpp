@@ -29,6 +29,15 @@ static size_t lds_fixed_bytes(int ef, uint32_t dstride, bool hot, bool lds_list,
     return (((size_t)ef + 63) & ~(size_t)63) * 8 + (size_t)kTieCap * 8 + (size_t)dstride * 4;  // the list, padded to 64 entries + tie list + query
 }
 
+// The half instances (walk_half.hip): first pass, one wavefront and one entry point per query, no auxiliary graph, compact index, unpadded rows
+// (the caller has checked those: `steps` is only set for unpadded rows) of 32 / 48 / 64 floats with L2 and 32 floats with the negative dot in
+// the one- / two-register-list and two-list kernels, of 144 floats with L2 in the two-list kernel.  Everything else walks the float32 copy of R.
+static bool half_serves(int metric, int steps, int regs, uint32_t n_entries) {
+    if (n_entries > 1u) return false;
+    if (steps == 8) return true;
+    return metric == 0 && (steps == 12 || steps == 16 || (steps == 36 && regs == 4));
+}
+
 WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv& env) {
     const bool off32 = compact_index(p), aux = p.aux_ell != nullptr, retry = pass == WalkPass::Retry;
     const int ef = p.ef, regs = ef <= 64 ? 1 : (ef <= kHot2MaxEf ? 2 : 4);
@@ -63,7 +72,9 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
     const bool coop = !retry && p.coop;
     // Shape served by the walk_hot* kernels (first pass only): 128-byte rows, adjacency rows of one 32-slot pass (walk_hotw*: 33 .. 64
     // slots, two passes), compact index (their visited set stores 24-bit ids)
-    const bool hot = !retry && !coop && (metric == 0 || metric == 1) && rows == 32u && ef <= kBigMaxEf && p.ell_stride <= 64u && off32 &&
+    // (half rows, GBNNS_FLAG_HALF_ROWS: never -- the family reads float32 rows; the generic instances below have half forms)
+    const bool half = p.half_rows != 0 && pass == WalkPass::First;
+    const bool hot = !retry && !coop && !half && (metric == 0 || metric == 1) && rows == 32u && ef <= kBigMaxEf && p.ell_stride <= 64u && off32 &&
              (!p.stamps_on || (regs == 4 && !env.stamps_generic)) && !aux;
     pl.lds_fixed = lds_fixed_bytes(ef, p.dstride, hot, pl.lds_list, coop);
     // the quotient form: the walk_hot* family and the register-list / two-list kernels of a compact index (the retry kernels keep the packed form)
@@ -96,6 +107,7 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
             // 384- / 512- / 576-byte rows have instances with the rows requested after the visited test, in the pass loop too
             k.one = p.ell_stride <= ((steps == 8 || l2_unrolled) ? 32u : 64u);
             k.late = l2_unrolled && steps >= 24 && late;
+            k.half = half && half_serves(metric, steps, 4, p.n_entries);
         }
         return pl;
     }
@@ -110,9 +122,11 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
     k = {WalkFamily::RegList, metric, steps, regs, off32, retry, false, aux};
     if (!aux && regs == 1 && off32 && !retry && p.ell_stride <= ((steps == 8 || (metric == 0 && steps >= 12)) ? 32u : 64u)) {
         // ef <= 64, adjacency rows of one pass: a loop-free expansion; 192- / 256-byte rows with L2: the instance with the query in LDS
-        if (metric == 0 && steps >= 12 && !p.stamps_on) k = {WalkFamily::RegWide, 0, steps, 0, false, false, false, false, late};
+        // (half rows: the loop-free expansion of the list family itself -- the query-in-LDS instances have no half form)
+        if (metric == 0 && steps >= 12 && !p.stamps_on && !half) k = {WalkFamily::RegWide, 0, steps, 0, false, false, false, false, late};
         else k.one = true;
     }
+    k.half = half && !aux && off32 && half_serves(metric, steps, regs, p.n_entries);
     return pl;
 }
 

@@ -46,7 +46,9 @@ enum class WalkFamily : uint8_t {
     Hot,        // walk_hot* / walk_hotw* / walk_hot_dot*: hand-laid-out, 128-byte rows (walk_hot.hip)
     RegWide,    // walk_reg_wide_kernel<STEPS, LATE>: 192- / 256-byte rows, ef <= 64  (walk_wide.hip)
     RegList,    // walk_reg_kernel<METRIC, STEPS, OFF32, RETRY, R, ONE_CHUNK, AUX>   (walk_l2 / walk_dot / walk_wide / walk_wide3)
+                // half: walk_reg_half_kernel<METRIC, STEPS, R, ONE_CHUNK>          (walk_half.hip)
     TwoList,    // walk_reg_big_kernel<METRIC, STEPS, OFF32, RETRY, AUX, ONE_PASS, LATE> (walk_l2 / walk_dot / walk_wide / walk_wide2)
+                // half: walk_reg_big_half_kernel<METRIC, STEPS, ONE_PASS, LATE>    (walk_half.hip)
     LdsList,    // walk_fast_kernel<METRIC, STEPS, RETRY, PACKED>                    (walk_l2 / walk_dot / walk_wide)
     BitmapReg,  // walk_bitmap_reg_kernel<METRIC, R>                                 (walk_bitmap.hip)
     BitmapBig,  // walk_bitmap_big_kernel<METRIC, STEPS, ONE_PASS, LATE>
@@ -65,10 +67,11 @@ struct WalkInstance {
     bool aux;     // auxiliary-graph hop
     bool late, spec;  // rows requested after the visited test (WalkParams::late_rows) / walk_hot_spec_kernel: before it (spec_rows)
     bool packed;  // LDS-list family: visited set of 24-bit ids
+    bool half;    // the hop's rows come from the 2-byte table (WalkParams::db_h): walk_reg_half_kernel / walk_reg_big_half_kernel (walk_half.hip)
 };
 inline bool operator==(const WalkInstance& a, const WalkInstance& b) {
     return a.family == b.family && a.metric == b.metric && a.steps == b.steps && a.regs == b.regs && a.off32 == b.off32 && a.retry == b.retry && a.one == b.one &&
-           a.aux == b.aux && a.late == b.late && a.spec == b.spec && a.packed == b.packed;
+           a.aux == b.aux && a.late == b.late && a.spec == b.spec && a.packed == b.packed && a.half == b.half;
 }
 
 struct WalkPlan {
@@ -92,8 +95,8 @@ struct WalkPlan {
 // GBNNS_STAMPS_GENERIC keeps diagnostic (GBNNS_STAMPS) builds off the hot two-list instances.
 struct WalkEnv { bool wide2, stamps_generic; };
 const WalkEnv& walk_env();
-// Reads the shape (dim, dstride, n, ell_stride, aux_ell / aux_stride), ef, n_entries, force_wide, coop, late_rows, spec_rows, stamps_on and
-// rr_reserve -- nothing the sizing rule writes (hash_cap, hash_limit, vs_shr), so the layout is known before the visited set is sized.
+// Reads the shape (dim, dstride, n, ell_stride, aux_ell / aux_stride), ef, n_entries, force_wide, coop, late_rows, spec_rows, stamps_on, half_rows
+// and rr_reserve -- nothing the sizing rule writes (hash_cap, hash_limit, vs_shr), so the layout is known before the visited set is sized.
 WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv& env = walk_env());
 
 }  // namespace gbnns

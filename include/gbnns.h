@@ -194,6 +194,38 @@ typedef struct {
 #define GBNNS_FLAG_SERIAL 64u
 #define GBNNS_FLAG_DEFER_JOIN 128u
 
+/* Half rows (opt-in; never a default, never what bench.py reports): the walk gathers its low-dimensional rows from a table of IEEE
+ * binary16 values, half the bytes a hop reads.  The feature has an exact definition: a search with GBNNS_FLAG_HALF_ROWS is the
+ * reference's search run on the table R = float32(float16(db_low)) -- every coordinate rounded once to nearest-even binary16
+ * (gbnns_round_to_half below IS that rounding) and widened back, which is exact.  All arithmetic stays float32 in the reference's
+ * order, the query is never rounded (NET: the exact projection, as always), and the re-rank in the space of `db` is untouched.  Every
+ * output keeps its meaning with db_low read as R: ids, pop order, hops, dist_calc, and out_cand_dist = the distances to rows of R,
+ * bit for bit.  NET / LOWQ only (PLAIN walks the answer space: GBNNS_ERR_INVALID); the handle must have been prepared with
+ * gbnns_index_enable_half_rows (else GBNNS_ERR_INVALID).  Applies to gbnns_search_ex, gbnns_search_topk and the gbnns_multi_*
+ * searches (which pass the flag through: the caller enables each gbnns_multi_replica) and combines with every other flag,
+ * hash_capacity, several entry points, the auxiliary graph, batches in flight and HOST or DEVICE buffers.  The first pass gathers
+ * 2-byte rows (walk_reg_half_kernel / walk_reg_big_half_kernel in gbnns_profile.walk_kernel) for a compact index (tables < 4 GiB,
+ * n < 2^24) with one entry point per query and no auxiliary graph, over rows of 32 / 48 / 64 floats with L2 and 32 floats with the
+ * negative dot at every beam up to 1 024, and of 144 floats with L2 at beams above 128; every other case -- and the retry pass, the
+ * general kernel, the bitmap pass, the two-wavefront walk -- runs the float32 kernels on a float32 copy of R: same results.  No call
+ * without the flag changes in any way. */
+#define GBNNS_FLAG_HALF_ROWS 512u
+/* Host code, no device needed: out_bits[i] = in[i] rounded to binary16 (nearest, ties to even; subnormals and the sign of zero
+ * kept), out_widened[i] = that value as a float.  Either output may be NULL.  A value that is not finite or whose rounding leaves the
+ * binary16 range (|x| >= 65 520) gives GBNNS_ERR_UNSUPPORTED with the index of the first such value in gbnns_last_error(); outputs
+ * before it have been written. */
+int gbnns_round_to_half(const float* in, uint64_t count, uint16_t* out_bits, float* out_widened);
+/* Builds, on the handle's device and from its db_low (copied from the host or borrowed from the device), the two tables flagged
+ * searches walk: R as binary16 rows of round_up(d_low, 8) values, zero padded, and R as float32 rows in db_low's layout.  Device
+ * memory: 1.5 x the low-dimensional table ON TOP of it -- db_low itself stays and searches without the flag keep using it (the
+ * option halves the bytes a hop reads, not the memory).  Synchronises the device; idempotent.  GBNNS_ERR_INVALID without db_low,
+ * GBNNS_ERR_UNSUPPORTED when a value is not finite or rounds out of the binary16 range (the handle stays as it was),
+ * GBNNS_ERR_OOM. */
+int gbnns_index_enable_half_rows(gbnns_index* index);
+/* out [n x d_low] = R, the table flagged searches walk (HOST: synchronous; DEVICE: enqueued on `stream`).  GBNNS_ERR_INVALID before
+ * gbnns_index_enable_half_rows. */
+int gbnns_index_low_rows(gbnns_index* index, float* out, int mem_kind, void* stream);
+
 /* Replaces the timed query loop of performNetTest (search_function.h:346-387) / performTest
  * (:151-188): one call = the whole batch.  With HOST buffers the call copies in, runs and
  * copies out synchronously (what the drop-in harness times).  With DEVICE buffers everything is
