@@ -28,7 +28,7 @@ FLAG_HALF_ROWS = 512
 # every symbol include/gbnns.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "gbnns_index_create", "gbnns_index_destroy", "gbnns_index_set_aux_graph", "gbnns_search_ex", "gbnns_search_batch", "gbnns_index_join", "gbnns_index_wait", "gbnns_host_pin", "gbnns_host_unpin",
-    "gbnns_project", "gbnns_rerank", "gbnns_rerank_topk", "gbnns_search_topk", "gbnns_debug_knob", "gbnns_debug_walk_plan", "gbnns_index_knob", "gbnns_index_knob_get", "gbnns_profile_enable", "gbnns_profile_read", "gbnns_build_graph_gd", "gbnns_build_graph_gd_device",
+    "gbnns_project", "gbnns_rerank", "gbnns_rerank_topk", "gbnns_search_topk", "gbnns_debug_knob", "gbnns_debug_walk_plan", "gbnns_debug_net_lds", "gbnns_index_knob", "gbnns_index_knob_get", "gbnns_profile_enable", "gbnns_profile_read", "gbnns_build_graph_gd", "gbnns_build_graph_gd_device",
     "gbnns_free", "gbnns_exact_knn", "gbnns_device_count", "gbnns_version", "gbnns_last_error",
     "gbnns_index_n", "gbnns_index_d", "gbnns_index_d_low", "gbnns_index_device",
     "gbnns_multi_create", "gbnns_multi_destroy", "gbnns_multi_size", "gbnns_multi_replica", "gbnns_multi_device_of",
@@ -124,6 +124,8 @@ def load_library():
     if hasattr(lib, "gbnns_debug_walk_plan"):
         lib.gbnns_debug_walk_plan.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int,
                                               C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(C.c_uint64)]
+    if hasattr(lib, "gbnns_debug_net_lds"):
+        lib.gbnns_debug_net_lds.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
     if hasattr(lib, "gbnns_index_knob"):
         lib.gbnns_index_knob.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         lib.gbnns_index_knob_get.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]

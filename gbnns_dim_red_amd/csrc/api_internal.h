@@ -177,6 +177,7 @@ struct gbnns_index {
     DevBuf low_half, low_r;
     bool half_ready = false;
     bool net_mfma_ready = false;
+    int net_form = -1;              // form of the last one-launch exact projection (kernels.h: kNetWholeCu / kNetHalfCu; -1: none yet)
     uint32_t ell_stride = 0, aux_stride = 0;
     bool has_aux = false;
     bool has_net = false;

@@ -229,7 +229,10 @@ int build_ell(const uint64_t* off, const uint32_t* nbr, uint64_t n, std::vector<
 //                   GBNNS_SPEC_MIN_NQ; 0 = never)
 //   "spec_any_form" 1: ... whatever the form of the visited set (tests; default: only tables NOT in the quotient form)
 //   "mlp_small"     smallest batch IN FLIGHT whose hidden projection layers run on the small-footprint kernel (0 = never)
-//   "mlp_net"       0 = never the one-launch projection (mlp_net.hip), 1 = for the shapes and batch sizes it serves (GBNNS_MLP_NET)
+//   "mlp_net"       0 = never the one-launch projection (mlp_net.hip), 1 = for the shapes and batch sizes it serves, in the form
+//                   run_project's rule picks, 2 = always its whole-CU form, 3 = its half-CU form wherever that fits (GBNNS_MLP_NET)
+//   "mlp_net_form"  (read only, gbnns_index_knob_get) the form the handle's last one-launch projection ran in: 0 = whole-CU blocks,
+//                   1 = half-CU blocks, -1 = none yet
 //   "mlp_slab"      0 = never the slab kernel for single layers (mlp_net.hip, mlp_slab_kernel), 1 = where a layer is one round of it
 //   "late_rows"     generic two-list kernels over 192- / 256- / 576-byte rows -- -1 = by shape and residency (search_core.cpp), 0 = rows
 //                   requested before the visited test, 1 = after it (GBNNS_LATE_ROWS)
@@ -253,7 +256,7 @@ bool knob_set(Knobs& k, const char* name, int value) {
     else if (!std::strcmp(name, "spec_any_form")) k.spec_any_form = value != 0;
     else if (!std::strcmp(name, "spec_min_nq")) k.spec_min_nq = std::max(0, value);
     else if (!std::strcmp(name, "mlp_small")) k.mlp_small = std::max(0, value);
-    else if (!std::strcmp(name, "mlp_net")) k.mlp_net = value != 0;
+    else if (!std::strcmp(name, "mlp_net")) k.mlp_net = std::max(0, std::min(3, value));
     else if (!std::strcmp(name, "mlp_slab")) k.mlp_slab = std::max(0, std::min(2, value));
     else if (!std::strcmp(name, "late_rows")) k.late_rows = std::max(-1, std::min(1, value));
     else if (!std::strcmp(name, "spec_tail")) k.spec_tail = std::max(0, std::min(100, value));
@@ -497,7 +500,14 @@ int run_project(gbnns_index* ix, Lane& L, const float* x, uint32_t xstride, uint
         n.din[0] = ix->d; n.din[1] = n.din[2] = ix->d_hidden;
         n.dout[0] = n.dout[1] = ix->d_hidden; n.dout[2] = ix->d_low;
         if (mlp_net_serves(n)) {
+            // batches in flight: blocks of half a CU (4 wavefronts, <= 80 KB) -- one is placed as soon as a CU is half drained of the
+            // other lanes' walk wavefronts, where a whole-CU block waits for all of them (profiles/half_cu_projection.txt: sift-like
+            // 33.2 against 32.2 M queries/s); alone the whole-CU form is the faster one (50 against 62 us), so lone calls keep it
+            const int mode = ix->knob.mlp_net;
+            const bool want_half = mode == 3 || (mode == 1 && in_flight);
+            n.form = want_half && mlp_net_half_serves(n) ? kNetHalfCu : kNetWholeCu;
             HIP_TRY(launch_mlp_net(n, s));
+            ix->net_form = n.form;
             std::snprintf(ix->acc.project_kernel, sizeof(ix->acc.project_kernel), "mlp_net_kernel");
             return GBNNS_OK;
         }
@@ -633,6 +643,18 @@ int gbnns_debug_knob(const char* name, int value) {
     return GBNNS_OK;
 }
 
+int gbnns_debug_net_lds(uint32_t d, uint32_t d_hidden, uint32_t d_low, int form, int a, uint64_t* lds_bytes, int* admitted) {
+    if (!lds_bytes || !admitted) return fail(GBNNS_ERR_INVALID, "gbnns_debug_net_lds: null output");
+    if (!d || !d_hidden || !d_low || a < 2 || a > 5 || (form != kNetWholeCu && form != kNetHalfCu))
+        return fail(GBNNS_ERR_INVALID, "gbnns_debug_net_lds: no such net, form or strip");
+    NetLaunch n{};
+    n.din[0] = d; n.din[1] = n.din[2] = d_hidden;
+    n.dout[0] = n.dout[1] = d_hidden; n.dout[2] = d_low;
+    *lds_bytes = mlp_net_lds_bytes(n, form, a);
+    *admitted = mlp_net_lds_bytes(n, form, 4) <= (form == kNetHalfCu ? 80u : 160u) * 1024u;
+    return GBNNS_OK;
+}
+
 int gbnns_debug_walk_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef,
                           uint32_t n_entries, int force_wide, int coop, int late_rows, int spec_rows, int pass, uint32_t rr_reserve,
                           char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
@@ -765,7 +787,7 @@ int gbnns_index_knob_get(gbnns_index* ix, const char* name, int* out) {
     const struct { const char* n; int v; } all[] = {
         {"quotient", k.quotient}, {"vs_disp", k.vs_disp}, {"max_waves", k.max_waves}, {"spec_min_nq", k.spec_min_nq},
         {"spec_any_form", k.spec_any_form}, {"mlp_small", k.mlp_small}, {"mlp_net", k.mlp_net}, {"mlp_slab", k.mlp_slab},
-        {"late_rows", k.late_rows}, {"spec_tail", k.spec_tail}, {"coop", k.coop}};
+        {"late_rows", k.late_rows}, {"spec_tail", k.spec_tail}, {"coop", k.coop}, {"mlp_net_form", ix->net_form}};
     for (const auto& e : all)
         if (!std::strcmp(name, e.n)) { *out = e.v; return GBNNS_OK; }
     return fail(GBNNS_ERR_INVALID, "gbnns_index_knob_get: unknown handle knob '%s'", name);

@@ -158,7 +158,8 @@ struct LayerParams {
 hipError_t launch_mlp_layer(const LayerParams& p, hipStream_t s);
 // the throughput option (GBNNS_FLAG_MFMA_PROJECTION): the same layer as a v_mfma_f32_32x32x2_f32 GEMM -- NOT bit-exact
 hipError_t launch_mlp_layer_mfma(const LayerParams& p, hipStream_t s);
-// The whole three-layer net in one launch (mlp_net.hip): activations stay in LDS, one block per 16 .. 40 queries.  Same
+// The whole three-layer net in one launch (mlp_net.hip): activations stay in LDS, one block per 16 .. 40 queries (8 .. 20 in the
+// half-CU form, which a batch in flight takes: its blocks start on half-drained CUs).  Same
 // arithmetic as three launch_mlp_layer calls (relu, relu, normalize), bit for bit.
 struct NetLaunch {
     const float* x;          // [nq x xstride]
@@ -172,8 +173,13 @@ struct NetLaunch {
     int32_t cus;             // compute units of the device (0: 256)
     int32_t force_a;         // diagnostic: queries per lane group (2 .. 5; 0 = chosen by the launcher)
     unsigned long long* stamps;  // diagnostic builds (-DGBNNS_NET_STAMPS): [blocks x 8] 100 MHz timestamps of the phase ends
+    int32_t form;            // kNetWholeCu: blocks of 8 wavefronts, one per CU; kNetHalfCu: of 4 wavefronts and half the LDS, two per CU
+    uint32_t lds_floor;      // diagnostic: request at least this much LDS per block (> 80 KB: half-CU blocks one per CU)
 };
+constexpr int32_t kNetWholeCu = 0, kNetHalfCu = 1;
 bool mlp_net_serves(const NetLaunch& n);   // shape, alignment and batch size fit the one-launch kernel
+bool mlp_net_half_serves(const NetLaunch& n);   // ... and the half-CU form's block (16 queries and more) fits 80 KB of LDS
+size_t mlp_net_lds_bytes(const NetLaunch& n, int form, int A);   // LDS of a block of `form` with A queries per lane (2 .. 5)
 hipError_t launch_mlp_net(const NetLaunch& n, hipStream_t s);
 // The throughput option as ONE launch (mlp_mfma_net.hip): v_mfma_f32_16x16x4_f32, one workgroup per CU over its share of the batch, weights
 // repacked once per handle into the instruction's B-operand order, activations in LDS.  NOT bit-exact.

@@ -6,7 +6,7 @@
 // (support_func.h:131-163); products and sums rounded separately (v_pk_mul_f32 / v_pk_add_f32, never a fused multiply-add);
 // normalizeVector (:636-642) on the last layer's outputs.
 //
-// Layout of the work.  Block = 16 wavefronts (4 per SIMD), Q = 8 A queries.  A wavefront owns 2 B neurons of a layer pass
+// Layout of the work (whole-CU form).  Block = 8 wavefronts (2 per SIMD), Q = 8 A queries.  A wavefront owns 2 B neurons of a layer pass
 // and ALL Q queries: its weights are its own (no workgroup barrier inside a layer), the activations are shared.  The eight
 // running sums of an output are split over FOUR lanes: lane j keeps the pair (c_j, c_{j+4}) in one 64-bit register pair, so
 // one v_pk_mul_f32 + one v_pk_add_f32 advance an output by one k-step of 8.  Lane = 16 j + 8 go + gq: gq = 0..7 picks the
@@ -20,6 +20,18 @@
 // offset 4 j returns (x[16kb+j], x[16kb+4+j], x[16kb+8+j], x[16kb+12+j]) = the operands of sums (j, j + 4) for k-steps 2 kb
 // and 2 kb + 1.  A lane's A queries are 64 bytes apart: every read of the k loop is one base register + an immediate.  The
 // gq groups are 32 bytes (mod 256) apart: the 16 lanes one LDS cycle serves hit 16 different 16-byte bank groups.
+//
+// Half-CU form (GO = 4; for batches in flight: one such block fits as soon as a CU is HALF drained of walk wavefronts, two
+// fill a drained CU as one whole-CU block does).  Block = 4 wavefronts (1 per SIMD), Q = 4 A queries.  Lane = 16 j + 4 go +
+// gq: gq = 0..3 picks the lane's A queries (gq, gq + 4, ...), go = 0..3 its B neurons -- a wavefront owns 4 B neurons of a
+// pass, so the four wavefronts cover the same 128 neurons as the eight.  The per-lane tile (A x B), the operand ratio, the
+// four-lane split of the running sums and the row reduce-scatter are the whole-CU form's; so is every rounding.  LDS: two
+// images of 4 gq groups, four staging pairs of 4 B rows -- 78 080 bytes for 128 -> 256 -> 256 -> 32 at A = 5.  The 16 lanes
+// of one LDS cycle of ds_read_b128 are {0-3, 12-15, 20-27} (and the like): gq groups of two rows j -- 4 x addresses 32 bytes
+// apart plus 4 more 16 bytes beside them, conflict-free with the same group stride -- and, of the weights, go = 0 and 3 of
+// one row j and go = 1 and 2 of the next.  The staged weight rows of B >= 4 (144 bytes each) are interleaved, row b GO + go:
+// the four go are 144 bytes apart (slots 0, 9, 2, 11 of the 16 of a bank row), distinct for those lanes and for any 16
+// lanes of one row j alike; at B = 2 (272-byte rows) the plain order go B + b is (go 544 bytes apart: slots 0, 2, 4, 6).
 #include <algorithm>
 
 #include "launch_util.h"
@@ -36,55 +48,68 @@ __host__ __device__ constexpr uint32_t net_pad16(uint32_t k) { return (k + 15u) 
 __host__ __device__ constexpr uint32_t net_gstride(uint32_t k, uint32_t A) { return net_pad16(k) * A + 8u; }
 // position of input k inside its 16-float block
 __device__ __forceinline__ uint32_t net_swz16(uint32_t k) { return ((k & 3u) << 2) | (((k >> 3) & 1u) << 1) | ((k >> 2) & 1u); }
-// float offset of input k of query row q (= gq + 8 a) in an image of group stride sg
-template <int A>
+// float offset of input k of query row q (= gq + GQ a) in an image of GQ groups, group stride sg
+template <int A, int GQ = 8>
 __device__ __forceinline__ uint32_t net_xpos(uint32_t q, uint32_t k, uint32_t sg) {
-    return (q & 7u) * sg + ((k >> 4) * A + (q >> 3)) * 16u + net_swz16(k);
+    return (q % GQ) * sg + ((k >> 4) * A + q / GQ) * 16u + net_swz16(k);
 }
 
-template <int B>
+// GO = neuron groups among the 16 lanes of a row j (2: whole-CU form and the slab kernel, 4: half-CU form); GQ = 16 / GO query groups
+template <int B, int GO = 2>
 struct NetGeom {
-    static constexpr int CK = B >= 4 ? 32 : 64;       // k-values per staged chunk (2 B rows x CK floats: 1 KB, 2 KB at B = 8)
+    static constexpr int CK = B >= 4 ? 32 : 64;       // k-values per staged chunk (GO B rows x CK floats: 1 KB, 2 KB at B = 8, GO = 2)
     static constexpr int LDW = CK + 4;        // staged row stride
     static constexpr int P = CK / 4;          // 16-byte pieces per row
-    static constexpr int BUF = 2 * B * LDW;   // floats per staging buffer
+    static constexpr int BUF = GO * B * LDW;  // floats per staging buffer
     static constexpr int NU = CK / 16;        // double k-steps per chunk
-    static constexpr int NF = 2 * B * P / 64; // 16-byte pieces per lane and chunk
+    // What a wavefront requests from L2 and stages at a time: a whole chunk -- or, in the half-CU form's B >= 4 layers, whose chunk of
+    // 4 B rows would be 16 registers per lane in flight (272 vector registers at A = 5, B = 8 where the form is held to 240; 232 this way), ONE double k-step of it,
+    // requested a step (1 300 cycles of packed arithmetic and more) ahead instead of a chunk
+    static constexpr int FK = (GO == 4 && B >= 4) ? 16 : CK;   // k-values per fetch unit
+    static constexpr int PF = FK / 4;         // 16-byte pieces per row and unit
+    static constexpr int NF = GO * B * PF / 64; // 16-byte pieces per lane and unit
+    static constexpr bool BY_STEP = FK != CK;
+    // staged position of row b of neuron group go: go B + b, or interleaved b GO + go (GO = 4, 144-byte rows: the header)
+    static constexpr bool INTERLEAVED = GO == 4 && B >= 4;
+    static constexpr int BSTEP = INTERLEAVED ? GO : 1;   // rows between a group's consecutive neurons
+    static constexpr int GSTEP = INTERLEAVED ? 1 : B;    // rows between the groups
 };
-template <int B>
+template <int B, int GO = 2>
 struct NetChunk {
-    float4 v[NetGeom<B>::NF];
+    float4 v[NetGeom<B, GO>::NF];
 };
-template <>
-struct NetChunk<0> {};
+template <int GO>
+struct NetChunk<0, GO> {};
 __host__ __device__ constexpr uint32_t net_padk(uint32_t k, uint32_t ck) { return (k + ck - 1u) / ck * ck; }
 
-// the 16-byte pieces of a weight chunk this lane fetches: rows obase .. obase + 2B - 1 (clamped to the last row: the results
-// of rows beyond dout are dropped), inputs k0 .. k0 + CK - 1, zero from the row's padded end (k16 <= wstride) on
-template <int B>
-__device__ __forceinline__ NetChunk<B> net_fetch(const float* __restrict__ W, uint32_t wstride, uint32_t k16, uint32_t dout,
-                                                 uint32_t obase, uint32_t k0, int lane) {
-    using G = NetGeom<B>;
-    NetChunk<B> g;
+// the 16-byte pieces of a weight chunk (fetch unit) this lane fetches: rows obase .. obase + GO B - 1 (clamped to the last row: the
+// results of rows beyond dout are dropped), inputs k0 .. k0 + FK - 1, zero from the row's padded end (k16 <= wstride) on
+template <int B, int GO = 2>
+__device__ __forceinline__ NetChunk<B, GO> net_fetch(const float* __restrict__ W, uint32_t wstride, uint32_t k16, uint32_t dout,
+                                                     uint32_t obase, uint32_t k0, int lane) {
+    using G = NetGeom<B, GO>;
+    NetChunk<B, GO> g;
 #pragma unroll
     for (int f = 0; f < G::NF; ++f) {
         const uint32_t e = (uint32_t)lane + 64u * f;
-        uint32_t o = obase + e / G::P;
+        uint32_t o = obase + e / G::PF;
         o = o < dout ? o : dout - 1u;
-        const uint32_t k = k0 + 4u * (e % G::P);
+        const uint32_t k = k0 + 4u * (e % G::PF);
         g.v[f] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (k < k16) g.v[f] = *reinterpret_cast<const float4*>(W + (size_t)o * wstride + k);
     }
     return g;
 }
 
-template <int B>
-__device__ __forceinline__ void net_stage(float* wb, const NetChunk<B>& g, int lane) {
-    using G = NetGeom<B>;
+template <int B, int GO = 2>
+__device__ __forceinline__ void net_stage(float* wb, const NetChunk<B, GO>& g, int lane) {
+    using G = NetGeom<B, GO>;
 #pragma unroll
     for (int f = 0; f < G::NF; ++f) {
         const uint32_t e = (uint32_t)lane + 64u * f;
-        const uint32_t r = e / G::P, p = e % G::P;
+        const uint32_t p = e % G::PF;
+        uint32_t r = e / G::PF;
+        if constexpr (G::INTERLEAVED) r = (r % B) * GO + r / B;
         float* d = wb + r * G::LDW + (p >> 2) * 16u + ((p >> 1) & 1u) * 2u + (p & 1u);
         d[0] = g.v[f].x; d[4] = g.v[f].y; d[8] = g.v[f].z; d[12] = g.v[f].w;
     }
@@ -145,12 +170,12 @@ __device__ __forceinline__ void net_row2(f2& c0, f2& c1, const float4& x, const 
         : "v"(f2{x.x, x.y}), "v"(f2{x.z, x.w}), "v"(f2{w0.x, w0.y}), "v"(f2{w0.z, w0.w}), "v"(f2{w1.x, w1.y}), "v"(f2{w1.z, w1.w}));
 }
 
-// One layer for the block's Q = 8 A rows.  xs: input image (group stride sx, inputs padded with zeros to a multiple of the
+// One layer for the block's Q = GQ A rows (GQ = 16 / GO query groups: 8, or 4 in the half-CU form).  xs: input image (group stride sx, inputs padded with zeros to a multiple of the
 // layer's chunk); outs: the next layer's image (group stride so) when OIMG, else plain rows y[q][so].
 // The k loop is a software pipeline over double k-steps u (16 inputs): the NEXT step's weights are requested at the top of a
 // step, query a's 16 bytes of the next step right after query a's products of this step (into the same registers); the weight
-// chunks (CK inputs of the wavefront's 2 B rows) run two ahead: chunk i + 2 is on its way from L2 while chunk i + 1 sits
-// staged in the wavefront's other LDS buffer.  Chunks and steps are numbered THROUGH the layer's passes.
+// chunks (CK inputs of the wavefront's GO B rows) run two ahead: chunk i + 2 is on its way from L2 while chunk i + 1 sits
+// staged in the wavefront's other LDS buffer (half-CU form, B >= 4: one double k-step of the rows at a time, NetGeom::BY_STEP).  Chunks and steps are numbered THROUGH the layer's passes.
 // Which 2 B-neuron slices of a layer a wavefront takes, in order: round robin.  (The vector pipe is arbitrated by age -- with two
 // slices each the four older wavefronts of a block are through a 256-neuron layer in 16 us, the younger in 25 -- but handing
 // the older ones three slices and the younger one made the older ones the slow ones: 25.2 / 17.4 us, 52.5 us per projection
@@ -164,32 +189,35 @@ __device__ __forceinline__ uint32_t net_slices(uint32_t wave, uint32_t total) { 
     return n;
 }
 
-template <int NW, int B>
+template <int NW, int B, int GO>
 struct NetW;
-template <int NW>
-struct NetW<NW, 0> {};
-template <int NW, int B>
+template <int NW, int GO>
+struct NetW<NW, 0, GO> {};
+template <int NW, int B, int GO>
 struct NetW {            // one layer's weights as a wavefront's stream of chunks
     const float* __restrict__ W;
     uint32_t wstride, k16, dout, nch;
     __device__ __forceinline__ NetW(const float* w, uint32_t ws, uint32_t din, uint32_t dout_)
-        : W(w), wstride(ws), k16(net_pad16(din)), dout(dout_), nch(net_padk(din, NetGeom<B>::CK) / NetGeom<B>::CK) {}
-    __device__ __forceinline__ NetChunk<B> fetch(uint32_t i, int lane, int wave) const {  // chunk i of the stream
-        const uint32_t ps = i / nch, c = i - ps * nch;
-        return net_fetch<B>(W, wstride, k16, dout, net_slice<NW>((uint32_t)wave, ps) * 2u * B, c * NetGeom<B>::CK, lane);
+        : W(w), wstride(ws), k16(net_pad16(din)), dout(dout_), nch(net_padk(din, NetGeom<B, GO>::CK) / NetGeom<B, GO>::CK) {}
+    __device__ __forceinline__ NetChunk<B, GO> fetch(uint32_t i, int lane, int wave) const {  // fetch unit i of the stream
+        using G = NetGeom<B, GO>;
+        const uint32_t nun = nch * (G::CK / G::FK), ps = i / nun, c = i - ps * nun;
+        return net_fetch<B, GO>(W, wstride, k16, dout, net_slice<NW>((uint32_t)wave, ps) * (uint32_t)(GO * B), c * G::FK, lane);
     }
 };
 
-template <int NW, int A, int B, int NB, bool RELU, bool OIMG>
-__device__ __forceinline__ void net_layer(const float* xs, uint32_t sx, const NetW<NW, B>& w, const float* __restrict__ bias, float* wb,
-                                          float* outs, uint32_t so, const NetChunk<B>& g0, const NetChunk<B>& g1,
-                                          const NetW<NW, NB>& nw, NetChunk<NB>& n0, NetChunk<NB>& n1, int lane, int wave,
+template <int NW, int A, int B, int NB, bool RELU, bool OIMG, int GO>
+__device__ __forceinline__ void net_layer(const float* xs, uint32_t sx, const NetW<NW, B, GO>& w, const float* __restrict__ bias, float* wb,
+                                          float* outs, uint32_t so, const NetChunk<B, GO>& g0, const NetChunk<B, GO>& g1,
+                                          const NetW<NW, NB, GO>& nw, NetChunk<NB, GO>& n0, NetChunk<NB, GO>& n1, int lane, int wave,
                                           unsigned long long* st = nullptr) {
-    using G = NetGeom<B>;
+    using G = NetGeom<B, GO>;
     static_assert(B == 2 || B == 4 || B == 8, "neurons per lane group");
-    const uint32_t j = (uint32_t)lane >> 4, go = ((uint32_t)lane >> 3) & 1u, gq = (uint32_t)lane & 7u;
+    static_assert(GO == 2 || GO == 4, "neuron groups per row of 16 lanes");
+    constexpr uint32_t GQ = 16 / GO;  // query groups per row
+    const uint32_t j = (uint32_t)lane >> 4, go = ((uint32_t)lane / GQ) % GO, gq = (uint32_t)lane % GQ;
     const uint32_t dout = w.dout, nch = w.nch;
-    const uint32_t npass = net_slices<NW>((uint32_t)wave, (dout + 2 * B - 1) / (2 * B));  // this wavefront's slices of 2 B neurons
+    const uint32_t npass = net_slices<NW>((uint32_t)wave, (dout + GO * B - 1) / (GO * B));  // this wavefront's slices of GO B neurons
     const uint32_t total = nch * npass;
     if (npass == 0) {  // (a layer of fewer slices than wavefronts) nothing here but the next layer's first chunks
         if constexpr (NB > 0) {
@@ -199,13 +227,13 @@ __device__ __forceinline__ void net_layer(const float* xs, uint32_t sx, const Ne
         return;
     }
     const float* xl = xs + gq * sx + 4 * j;
-    const float* wl = wb + go * B * G::LDW + 4 * j;
-    net_stage<B>(wb, g0, lane);
-    NetChunk<B> g = g1;
+    const float* wl = wb + go * G::GSTEP * G::LDW + 4 * j;
+    net_stage<B, GO>(wb, g0, lane);
+    NetChunk<B, GO> g = g1;
     constexpr int NBV = B >= 4 ? B / 4 : 1;  // distinct neurons among a lane's outputs: b = (4 gi + j) mod B
     float bsv[NBV];
     auto load_bias = [&](uint32_t ps) {
-        const uint32_t ob = net_slice<NW>((uint32_t)wave, ps) * 2u * B + go * B;
+        const uint32_t ob = net_slice<NW>((uint32_t)wave, ps) * (uint32_t)(GO * B) + go * B;
 #pragma unroll
         for (int tb = 0; tb < NBV; ++tb) {
             const uint32_t o = ob + (B >= 4 ? j + 4u * tb : j % B);
@@ -221,7 +249,7 @@ __device__ __forceinline__ void net_layer(const float* xs, uint32_t sx, const Ne
     // operands of step 0
     float4 xv[A], wv[2][B];
 #pragma unroll
-    for (int b = 0; b < B; ++b) wv[0][b] = *reinterpret_cast<const float4*>(wl + b * G::LDW);
+    for (int b = 0; b < B; ++b) wv[0][b] = *reinterpret_cast<const float4*>(wl + b * G::BSTEP * G::LDW);
 #pragma unroll
     for (int a = 0; a < A; ++a) xv[a] = *reinterpret_cast<const float4*>(xl + a * 16);
     static_assert(G::NU % 2 == 0, "the weight registers alternate by step: a chunk must end on the set it began with");
@@ -234,8 +262,10 @@ __device__ __forceinline__ void net_layer(const float* xs, uint32_t sx, const Ne
         for (uint32_t c = 0; c < nch; ++c, ++i) {
             // (a wavefront's LDS operations execute in order: its own staged rows are visible to its later reads, and the rows
             //  of chunk i - 1 were last read before these stores; past the layer's last chunk the store and the fetch repeat it)
-            net_stage<B>(wb + ((i + 1) & 1u) * G::BUF, g, lane);
-            g = w.fetch(i + 2 < total ? i + 2 : total - 1, lane, wave);
+            if constexpr (!G::BY_STEP) {
+                net_stage<B, GO>(wb + ((i + 1) & 1u) * G::BUF, g, lane);
+                g = w.fetch(i + 2 < total ? i + 2 : total - 1, lane, wave);
+            }
             const float* wcur = wl + (i & 1u) * G::BUF;
             const float* wnxt = wl + ((i + 1) & 1u) * G::BUF;
             const float* xc = xl + c * (G::NU * A * 16);
@@ -243,11 +273,18 @@ __device__ __forceinline__ void net_layer(const float* xs, uint32_t sx, const Ne
 #pragma unroll
             for (int u = 0; u < G::NU; ++u) {
                 const int cb = u & 1, nb = cb ^ 1;
+                if constexpr (G::BY_STEP) {
+                    // the next step's 16 inputs of the wavefront's rows go into place (they were requested a step ago: the rows of
+                    // this step are in registers since the last one), those of the step after next set out
+                    net_stage<B, GO>(u + 1 < G::NU ? wb + (i & 1u) * G::BUF + 16 * (u + 1) : wb + ((i + 1) & 1u) * G::BUF, g, lane);
+                    const uint32_t v2 = i * G::NU + u + 2, nv = total * G::NU;
+                    g = w.fetch(v2 < nv ? v2 : nv - 1, lane, wave);
+                }
                 // the next step's weights: this chunk's next 16 inputs, or the next chunk's first
 #pragma unroll
                 for (int b = 0; b < B; ++b)
-                    wv[nb][b] = u + 1 < G::NU ? *reinterpret_cast<const float4*>(wcur + b * G::LDW + 16 * (u + 1))
-                                              : *reinterpret_cast<const float4*>(wnxt + b * G::LDW);
+                    wv[nb][b] = u + 1 < G::NU ? *reinterpret_cast<const float4*>(wcur + b * G::BSTEP * G::LDW + 16 * (u + 1))
+                                              : *reinterpret_cast<const float4*>(wnxt + b * G::BSTEP * G::LDW);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int a = 0; a < A; ++a) {
@@ -276,7 +313,7 @@ __device__ __forceinline__ void net_layer(const float* xs, uint32_t sx, const Ne
             }
         }
         // fold (support_func.h:159-161): m = c_{j+4} + c_j in the lane, then the rows' reduce-scatter; row j owns output 4 gi + j
-        const uint32_t obase = net_slice<NW>((uint32_t)wave, ps) * 2u * B;
+        const uint32_t obase = net_slice<NW>((uint32_t)wave, ps) * (uint32_t)(GO * B);
         constexpr int N = A * B, NG = (N + 3) / 4;
         float res[NG];
 #pragma unroll
@@ -307,7 +344,7 @@ __device__ __forceinline__ void net_layer(const float* xs, uint32_t sx, const Ne
             if (RELU && v < 0.f) v = 0.f;                // :629-631
             if (live) {
                 if (OIMG) outs[gq * so + ((o >> 4) * A + a) * 16u + net_swz16(o)] = v;
-                else outs[(size_t)(gq + 8u * a) * so + o] = v;
+                else outs[(size_t)(gq + GQ * a) * so + o] = v;
             }
         }
         if (ps + 1 < npass) load_bias(ps + 1);
@@ -339,27 +376,30 @@ struct NetParams {
 #define NET_STAMP(i) do { } while (0)
 #endif
 
-template <int NW, int A, int BH, int B3>
+// GO = 2: the whole-CU form (NW = 8); GO = 4: the half-CU form (NW = 4) -- the header
+template <int NW, int A, int BH, int B3, int GO = 2>
 __global__ __launch_bounds__(NW * 64) void mlp_net_kernel(NetParams p) {
     extern __shared__ __attribute__((aligned(16))) float nsm[];
-    constexpr int Q = 8 * A, NT = NW * 64;
+    constexpr int GQ = 16 / GO, Q = GQ * A, NT = NW * 64;
+    using GH = NetGeom<BH, GO>;
+    using G3 = NetGeom<B3, GO>;
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     float* bufa = nsm;                     // x, then h2
     float* bufb = bufa + p.bufa;           // h1, then y
-    float* wb = bufb + p.bufb + (size_t)wave * (2 * NetGeom<BH>::BUF);  // (the hidden layers' staging pair is the largest)
+    float* wb = bufb + p.bufb + (size_t)wave * (2 * GH::BUF);  // (the hidden layers' staging pair is the largest)
     const uint32_t qbase = blockIdx.x * Q;
-    const uint32_t s0 = net_gstride(net_padk(p.din[0], NetGeom<BH>::CK), A), s1 = net_gstride(net_padk(p.dout[0], NetGeom<BH>::CK), A),
-                   s2 = net_gstride(net_padk(p.dout[1], NetGeom<B3>::CK), A);
+    const uint32_t s0 = net_gstride(net_padk(p.din[0], GH::CK), A), s1 = net_gstride(net_padk(p.dout[0], GH::CK), A),
+                   s2 = net_gstride(net_padk(p.dout[1], G3::CK), A);
     NET_STAMP(0);
 
-    const NetW<NW, BH> w1(p.w[0], p.wstride[0], p.din[0], p.dout[0]), w2(p.w[1], p.wstride[1], p.din[1], p.dout[1]);
-    const NetW<NW, B3> w3(p.w[2], p.wstride[2], p.din[2], p.dout[2]);
-    const NetW<NW, 0> w_none;
-    NetChunk<BH> ga = w1.fetch(0, lane, wave), gb = w1.fetch(1, lane, wave);  // (a net's first layer has two chunks: din > 32)
+    const NetW<NW, BH, GO> w1(p.w[0], p.wstride[0], p.din[0], p.dout[0]), w2(p.w[1], p.wstride[1], p.din[1], p.dout[1]);
+    const NetW<NW, B3, GO> w3(p.w[2], p.wstride[2], p.din[2], p.dout[2]);
+    const NetW<NW, 0, GO> w_none;
+    NetChunk<BH, GO> ga = w1.fetch(0, lane, wave), gb = w1.fetch(1, lane, wave);  // (a net's first layer has two chunks: din > 32)
     // the block's queries: 16 floats per thread and turn, permuted on the way into LDS (zeros beyond din)
     {
-        const uint32_t nb = net_padk(p.din[0], NetGeom<BH>::CK) / 16u;
+        const uint32_t nb = net_padk(p.din[0], GH::CK) / 16u;
         for (uint32_t e = t; e < (uint32_t)Q * nb; e += NT) {
             const uint32_t row = e / nb, blk = e % nb, qg = qbase + row;
             float4 v[4];
@@ -369,7 +409,7 @@ __global__ __launch_bounds__(NW * 64) void mlp_net_kernel(NetParams p) {
                 v[i] = (qg < p.nq && k < p.din[0]) ? *reinterpret_cast<const float4*>(p.x + (size_t)qg * p.xstride + k)
                                                    : make_float4(0.f, 0.f, 0.f, 0.f);
             }
-            float4* d = reinterpret_cast<float4*>(bufa + net_xpos<A>(row, 16u * blk, s0));
+            float4* d = reinterpret_cast<float4*>(bufa + net_xpos<A, GQ>(row, 16u * blk, s0));
             d[0] = make_float4(v[0].x, v[1].x, v[2].x, v[3].x);
             d[1] = make_float4(v[0].y, v[1].y, v[2].y, v[3].y);
             d[2] = make_float4(v[0].z, v[1].z, v[2].z, v[3].z);
@@ -378,32 +418,32 @@ __global__ __launch_bounds__(NW * 64) void mlp_net_kernel(NetParams p) {
     }
     // h1 / h2 columns beyond dout (up to the reading layer's chunk multiple) are read by the next layer: zero them once
     {
-        const uint32_t h = p.dout[0], hp = net_padk(h, NetGeom<BH>::CK) - h;
-        for (uint32_t e = t; e < (uint32_t)Q * hp; e += NT) bufb[net_xpos<A>(e / hp, h + e % hp, s1)] = 0.f;
+        const uint32_t h = p.dout[0], hp = net_padk(h, GH::CK) - h;
+        for (uint32_t e = t; e < (uint32_t)Q * hp; e += NT) bufb[net_xpos<A, GQ>(e / hp, h + e % hp, s1)] = 0.f;
     }
     __syncthreads();
     NET_STAMP(1);
-    NetChunk<BH> gc, gd;
-    net_layer<NW, A, BH, BH, true, true>(bufa, s0, w1, p.bias[0], wb, bufb, s1, ga, gb, w2, gc, gd, lane, wave);
+    NetChunk<BH, GO> gc, gd;
+    net_layer<NW, A, BH, BH, true, true, GO>(bufa, s0, w1, p.bias[0], wb, bufb, s1, ga, gb, w2, gc, gd, lane, wave);
     NET_STAMP(2);
     __syncthreads();
     NET_STAMP(3);
     {
-        const uint32_t h = p.dout[1], hp = net_padk(h, NetGeom<B3>::CK) - h;
-        for (uint32_t e = t; e < (uint32_t)Q * hp; e += NT) bufa[net_xpos<A>(e / hp, h + e % hp, s2)] = 0.f;
+        const uint32_t h = p.dout[1], hp = net_padk(h, G3::CK) - h;
+        for (uint32_t e = t; e < (uint32_t)Q * hp; e += NT) bufa[net_xpos<A, GQ>(e / hp, h + e % hp, s2)] = 0.f;
     }
-    NetChunk<B3> ge, gf;
+    NetChunk<B3, GO> ge, gf;
 #ifdef GBNNS_NET_STAMPS
-    net_layer<NW, A, BH, B3, true, true>(bufb, s1, w2, p.bias[1], wb, bufa, s2, gc, gd, w3, ge, gf, lane, wave,
+    net_layer<NW, A, BH, B3, true, true, GO>(bufb, s1, w2, p.bias[1], wb, bufa, s2, gc, gd, w3, ge, gf, lane, wave,
                                          p.stamps ? p.stamps + 8 * 1024 + 2 * (blockIdx.x * NW + wave) : nullptr);
 #else
-    net_layer<NW, A, BH, B3, true, true>(bufb, s1, w2, p.bias[1], wb, bufa, s2, gc, gd, w3, ge, gf, lane, wave);
+    net_layer<NW, A, BH, B3, true, true, GO>(bufb, s1, w2, p.bias[1], wb, bufa, s2, gc, gd, w3, ge, gf, lane, wave);
 #endif
     __syncthreads();
     NET_STAMP(4);
     const uint32_t ldy = p.dout[2] + 1u;
-    NetChunk<0> gz;
-    net_layer<NW, A, B3, 0, false, false>(bufa, s2, w3, p.bias[2], wb, bufb, ldy, ge, gf, w_none, gz, gz, lane, wave);
+    NetChunk<0, GO> gz;
+    net_layer<NW, A, B3, 0, false, false, GO>(bufa, s2, w3, p.bias[2], wb, bufb, ldy, ge, gf, w_none, gz, gz, lane, wave);
     __syncthreads();
     NET_STAMP(5);
     // normalizeVector (support_func.h:636-642): 8 threads per query; threads 0..3 of a query run the four running sums of
@@ -625,14 +665,23 @@ __global__ __launch_bounds__(NW * 64) void mlp_slab_kernel(SlabParams sp) {
 
 }  // namespace
 
-// LDS bytes of the one-launch projection for Q = 8 A queries per block, NW wavefronts, BH neurons per lane group in the hidden layers
-static size_t net_lds_bytes(const NetLaunch& n, int A, int nw, int bh, uint32_t* bufa, uint32_t* bufb) {
-    const uint32_t Q = 8u * A;
+// LDS bytes of the one-launch projection for Q = gq A queries per block (gq = 8: whole-CU form, 4: half-CU form, 16 / gq neuron
+// groups per wavefront), NW wavefronts, BH neurons per lane group in the hidden layers
+static size_t net_lds_bytes(const NetLaunch& n, int A, int nw, int bh, uint32_t gq, uint32_t* bufa, uint32_t* bufb) {
+    const uint32_t Q = gq * A, go = 16u / gq;
     // (images padded to 64 inputs: the largest chunk of any layer form)
-    *bufa = 8u * std::max(net_gstride(net_padk(n.din[0], 64), A), net_gstride(net_padk(n.dout[1], 64), A));
-    *bufb = (std::max(8u * net_gstride(net_padk(n.dout[0], 64), A), Q * (n.dout[2] + 1u)) + 3u) & ~3u;
-    const size_t stage = (size_t)2 * 2 * bh * (32 + 4);  // (>= the last layer's 2 x 2 B3 x 68 for B3 <= bh / 2 ... checked below)
+    *bufa = gq * std::max(net_gstride(net_padk(n.din[0], 64), A), net_gstride(net_padk(n.dout[1], 64), A));
+    *bufb = (std::max(gq * net_gstride(net_padk(n.dout[0], 64), A), Q * (n.dout[2] + 1u)) + 3u) & ~3u;
+    const size_t stage = (size_t)2 * go * bh * (32 + 4);  // (>= the last layer's 2 x go B3 x 68 for B3 <= bh / 2 ... checked below)
     return ((size_t)*bufa + *bufb + (size_t)nw * stage) * sizeof(float);
+}
+
+// the half-CU form: 4 wavefronts x 8 neurons x 4 groups, LDS of at most half a CU's (two blocks per CU)
+constexpr size_t kNetHalfLds = 80u * 1024u;
+
+size_t mlp_net_lds_bytes(const NetLaunch& n, int form, int A) {
+    uint32_t ba, bb;
+    return form == kNetHalfCu ? net_lds_bytes(n, A, 4, 8, 4, &ba, &bb) : net_lds_bytes(n, A, 8, 8, 8, &ba, &bb);
 }
 
 bool mlp_net_serves(const NetLaunch& n) {
@@ -650,25 +699,28 @@ bool mlp_net_serves(const NetLaunch& n) {
     if (n.dout[2] > 128u) return false;
     // (strips of at least 32 queries must fit: hidden layers of 512 and more leave room for 24 -- 256 -> 512 -> 512 -> 64 then
     // takes 223 us against 215)
-    uint32_t ba, bb;
-    return net_lds_bytes(n, 4, 8, 8, &ba, &bb) <= 160u * 1024u;
+    return mlp_net_lds_bytes(n, kNetWholeCu, 4) <= 160u * 1024u;
 }
 
-template <int NW, int A, int BH, int B3>
+// ... and strips of 16 queries (A = 4, as above) fit half a CU's LDS: the nets the half-CU form takes
+bool mlp_net_half_serves(const NetLaunch& n) { return mlp_net_serves(n) && mlp_net_lds_bytes(n, kNetHalfCu, 4) <= kNetHalfLds; }
+
+template <int NW, int A, int BH, int B3, int GO>
 static hipError_t net_launch(const NetParams& p, size_t lds, hipStream_t s) {
-    hipError_t e = set_lds(mlp_net_kernel<NW, A, BH, B3>, lds);
+    hipError_t e = set_lds(mlp_net_kernel<NW, A, BH, B3, GO>, lds);
     if (e != hipSuccess) return e;
-    const unsigned grid = (p.nq + 8u * A - 1u) / (8u * A);
-    hipLaunchKernelGGL((mlp_net_kernel<NW, A, BH, B3>), dim3(grid), dim3(NW * 64), lds, s, p);
+    constexpr unsigned Q = 16u / GO * A;
+    const unsigned grid = (p.nq + Q - 1u) / Q;
+    hipLaunchKernelGGL((mlp_net_kernel<NW, A, BH, B3, GO>), dim3(grid), dim3(NW * 64), lds, s, p);
     return hipGetLastError();
 }
 
-template <int NW, int BH>
+template <int NW, int BH, int GO>
 static hipError_t net_launch_a(const NetParams& p, int A, int b3, size_t lds, hipStream_t s) {
 #define GBNNS_NET_CASE(AA)                                                        \
     case AA:                                                                      \
-        if (b3 == 2) return net_launch<NW, AA, BH, 2>(p, lds, s);                 \
-        return net_launch<NW, AA, BH, 4>(p, lds, s);
+        if (b3 == 2) return net_launch<NW, AA, BH, 2, GO>(p, lds, s);             \
+        return net_launch<NW, AA, BH, 4, GO>(p, lds, s);
     switch (A) {
         GBNNS_NET_CASE(2)
         GBNNS_NET_CASE(3)
@@ -682,30 +734,39 @@ static hipError_t net_launch_a(const NetParams& p, int A, int b3, size_t lds, hi
 hipError_t launch_mlp_net(const NetLaunch& n, hipStream_t s) {
     if (n.nq == 0) return hipSuccess;
     if (!mlp_net_serves(n)) return hipErrorInvalidValue;
-    constexpr int nw = 8, bh = 8;  // (blocks of 16 wavefronts x 8 neurons and of 4 x 16 were measured too: DESIGN.md 5.3)
-    // queries per lane group: the A that needs the fewest rounds of the machine x A (a block per CU: one round of 8 A queries)
-    int cus = n.cus > 0 ? n.cus : 256;
+    const bool half = n.form == kNetHalfCu;
+    if (half && !mlp_net_half_serves(n)) return hipErrorInvalidValue;
+    // whole-CU form: 8 wavefronts x 8 neurons x 2 groups (blocks of 16 wavefronts x 8 neurons and of 4 x 16 were measured too: DESIGN.md 5.3)
+    constexpr int bh = 8;
+    const int nw = half ? 4 : 8;
+    const uint32_t gq = half ? 4u : 8u;
+    const size_t lds_max = half ? kNetHalfLds : 160u * 1024u;
+    // queries per lane group: the A that needs the fewest rounds of the machine x A (one whole-CU block or two half-CU blocks per
+    // CU: a round of 8 A queries per CU either way)
+    const uint64_t slots = (uint64_t)(n.cus > 0 ? n.cus : 256) * (half ? 2u : 1u);
     int bestA = 0;
     uint64_t best = ~0ull;
     NetParams p{};
     for (int A = 5; A >= 2; --A) {
         uint32_t ba, bb;
-        if (net_lds_bytes(n, A, nw, bh, &ba, &bb) > 160u * 1024u) continue;
+        if (net_lds_bytes(n, A, nw, bh, gq, &ba, &bb) > lds_max) continue;
         if (n.force_a && n.force_a != A) continue;
-        const uint64_t blocks = (n.nq + 8u * A - 1u) / (8u * A);
-        const uint64_t cost = ((blocks + cus - 1) / cus) * A;
+        const uint64_t blocks = (n.nq + gq * A - 1u) / (gq * A);
+        const uint64_t cost = ((blocks + slots - 1) / slots) * A;
         if (cost < best) { best = cost; bestA = A; }
     }
     if (!bestA) return hipErrorInvalidValue;
-    const size_t lds = net_lds_bytes(n, bestA, nw, bh, &p.bufa, &p.bufb);
+    size_t lds = net_lds_bytes(n, bestA, nw, bh, gq, &p.bufa, &p.bufb);
+    // (diagnostic: a larger request -- more than half a CU's keeps the half-CU blocks one per CU)
+    if (n.lds_floor > lds && n.lds_floor <= 160u * 1024u) lds = n.lds_floor;
     p.x = n.x; p.xstride = n.xstride; p.nq = n.nq; p.out = n.out; p.ostride = n.ostride; p.stamps = n.stamps;
     for (int l = 0; l < 3; ++l) {
         p.w[l] = n.w[l]; p.wstride[l] = n.wstride[l]; p.bias[l] = n.bias[l]; p.din[l] = n.din[l]; p.dout[l] = n.dout[l];
     }
-    // neurons per lane group in the last layer: a pass covers NW x 2 B3 neurons
-    const uint32_t per = (n.dout[2] + 2u * nw - 1u) / (2u * nw);
+    // neurons per lane group in the last layer: a pass covers 16 B3 neurons (NW x 2 B3, NW x 4 B3 in the half-CU form)
+    const uint32_t per = (n.dout[2] + 15u) / 16u;
     const int b3 = per <= 2 ? 2 : 4;
-    return net_launch_a<8, 8>(p, bestA, b3, lds, s);
+    return half ? net_launch_a<4, 8, 4>(p, bestA, b3, lds, s) : net_launch_a<8, 8, 2>(p, bestA, b3, lds, s);
 }
 
 bool mlp_slab_serves(const LayerParams& p) {

@@ -353,7 +353,11 @@ int gbnns_profile_enable(gbnns_index* index, int on);
  * kernel (mlp_layer_sw_kernel; default 4 096, up to 32 times that, 0 = never; GBNNS_MLP_SMALL).
  * "mlp_net": 1 (default) = batches of 2 048 queries and more whose net has d % 8 == 0 and d_hidden % 8 == 0 are projected
  * by the one-launch kernel (mlp_net_kernel: the three layers of a strip of queries in one workgroup, activations in LDS),
- * 0 = always the per-layer kernels; identical outputs either way (GBNNS_MLP_NET).
+ * 0 = always the per-layer kernels; identical outputs either way (GBNNS_MLP_NET).  The kernel has two forms: workgroups of a
+ * whole CU (8 wavefronts) and of half a CU (4 wavefronts, at most 80 KB of LDS: nets up to 256 hidden units or so), which a
+ * batch in flight (GBNNS_FLAG_DEFER_JOIN) takes where it fits -- its workgroups start on CUs the other batches' walks have half
+ * left.  2 = always the whole-CU form, 3 = the half-CU form wherever it fits.  "mlp_net_form" (gbnns_index_knob_get only): the
+ * form of the handle's last one-launch projection, 0 whole-CU, 1 half-CU, -1 none yet.
  * "mlp_slab": 1 (default) = a projection layer that is one round of the machine for mlp_slab_kernel (small batches; the GIST
  * shape's 1 000 queries through 960 -> 1 024 -> 1 024 -> 64) takes it, 0 = never; identical outputs either way (GBNNS_MLP_SLAB).
  * "late_rows": the wide-row instances that have both forms (walk_reg_wide_kernel: 192- / 256-byte rows at ef <= 64; the two-list kernel
@@ -379,6 +383,10 @@ int gbnns_profile_read(gbnns_index* index, gbnns_profile* out, int reset);
 int gbnns_debug_walk_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef,
                           uint32_t n_entries, int force_wide, int coop, int late_rows, int spec_rows, int pass, uint32_t rr_reserve,
                           char* name, uint32_t name_bytes, uint64_t* lds_bytes);
+/* Diagnostic, no device needed: LDS bytes of a workgroup of the one-launch projection for a net d -> d_hidden -> d_hidden -> d_low, in
+ * the whole-CU form (form 0) or the half-CU form (form 1), with a queries per lane (2 .. 5), and whether that form takes the net at all
+ * (*admitted: a workgroup with a = 4 fits 160 KB / 80 KB). */
+int gbnns_debug_net_lds(uint32_t d, uint32_t d_hidden, uint32_t d_low, int form, int a, uint64_t* lds_bytes, int* admitted);
 
 /* hnswlikeGD (support_func.h:521-575, need_const_degree = false) + addReverseEdgesForGD
  * (:402-445): prunes a kNN graph (CSR, host) over `ds` [n x d] (host) into the search graph, as

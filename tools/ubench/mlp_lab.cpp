@@ -1,9 +1,10 @@
-// mlp_lab (diagnostic): the one-launch projection (csrc/mlp_net.hip) against the three per-layer launches (csrc/mlp.hip) on
-// one random net -- outputs compared bit for bit, both timed with HIP events -- and a few issue-rate loops for the packed
+// mlp_lab (diagnostic): the one-launch projection (csrc/mlp_net.hip; its whole-CU form, and its half-CU form at two blocks and at one
+// block per CU) against the three per-layer launches (csrc/mlp.hip) on one random net -- outputs compared bit for bit,
+// both timed with HIP events -- and a few issue-rate loops for the packed
 // f32 instructions the projection is made of.
 // Build (from the repo root, after `make -C gbnns_dim_red_amd/csrc`):
-//   hipcc --offload-arch=gfx950 -O2 -std=c++17 -x hip -Igbnns_dim_red_amd/csrc tools/ubench/mlp_lab.cpp gbnns_dim_red_amd/csrc/build/mlp.o \
-//         gbnns_dim_red_amd/csrc/build/mlp_net.o -o tools/ubench/mlp_lab
+//   hipcc --offload-arch=gfx950 -O2 -std=c++17 -x hip -Igbnns_dim_red_amd/csrc tools/ubench/mlp_lab.cpp -x none \
+//         gbnns_dim_red_amd/csrc/build/mlp.o gbnns_dim_red_amd/csrc/build/mlp_net.o -o tools/ubench/mlp_lab
 // Run on the GPU box: tools/ubench/mlp_lab [nq d d_hidden d_low [force_a]]
 #include <hip/hip_runtime.h>
 
@@ -292,8 +293,8 @@ int main(int argc, char** argv) {
     }
     timeit("three launches (mlp.hip)", [&] { per_layer(0); });
     timeit("three launches, small-footprint hidden", [&] { per_layer(1); });
-    if (gbnns::mlp_net_serves(n)) {
-        timeit("one launch (mlp_net.hip)", [&] { CK(gbnns::launch_mlp_net(n, s)); });
+    // outputs of the last run against the three launches', bit for bit
+    auto compare = [&](const char* what) {
         per_layer(0);
         CK(hipStreamSynchronize(s));
         std::vector<uint32_t> a((size_t)nq * ostride), b((size_t)nq * ostride);
@@ -302,13 +303,29 @@ int main(int argc, char** argv) {
         size_t bad = 0, first = (size_t)-1;
         for (size_t i = 0; i < a.size(); ++i)
             if (a[i] != b[i]) { if (!bad) first = i; ++bad; }
-        printf("  outputs that differ in a bit: %zu of %zu", bad, a.size());
+        printf("  %s: outputs that differ in a bit: %zu of %zu", what, bad, a.size());
         if (bad) {
             float fa, fb;
             memcpy(&fa, &a[first], 4); memcpy(&fb, &b[first], 4);
             printf(" (first at query %zu column %zu: %.9g against %.9g)", first / ostride, first % ostride, fa, fb);
         }
         printf("\n");
+        CK(hipMemset(o_net, 0xEE, (size_t)nq * ostride * 4));
+    };
+    if (gbnns::mlp_net_serves(n)) {
+        timeit("one launch (mlp_net.hip), whole-CU blocks", [&] { CK(gbnns::launch_mlp_net(n, s)); });
+        compare("whole-CU blocks");
+    }
+    if (gbnns::mlp_net_half_serves(n)) {  // the half-CU form alone: two blocks per CU (its LDS allows it), and one (a request of 84 KB)
+        printf("  half-CU form: %zu bytes of LDS per block at 5 queries per lane\n", gbnns::mlp_net_lds_bytes(n, gbnns::kNetHalfCu, 5));
+        n.form = gbnns::kNetHalfCu;
+        timeit("one launch, half-CU blocks, two per CU", [&] { CK(gbnns::launch_mlp_net(n, s)); });
+        compare("half-CU blocks, two per CU");
+        n.lds_floor = 84u * 1024u;
+        timeit("one launch, half-CU blocks, one per CU", [&] { CK(gbnns::launch_mlp_net(n, s)); });
+        compare("half-CU blocks, one per CU");
+        n.lds_floor = 0;
+        n.form = gbnns::kNetWholeCu;
     }
     if (getenv("MLP_LAB_STAMPS") && gbnns::mlp_net_serves(n)) {   // needs a library built with EXTRA_DEFS=-DGBNNS_NET_STAMPS
         const int nb = 1024;
