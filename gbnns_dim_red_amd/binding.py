@@ -36,6 +36,7 @@ SYMBOLS = [
     "gbnns_multi_search_device", "gbnns_multi_synchronize", "gbnns_multi_last_error",
     "gbnns_multi_rccl_single_rank", "gbnns_multi_rccl_version",
     "gbnns_round_to_half", "gbnns_index_enable_half_rows", "gbnns_index_low_rows",
+    "gbnns_index_set_tags", "gbnns_search_tagged", "gbnns_debug_tag_plan",
 ]
 
 
@@ -161,6 +162,10 @@ def load_library():
     lib.gbnns_round_to_half.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.gbnns_index_enable_half_rows.argtypes = [C.c_void_p]
     lib.gbnns_index_low_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.gbnns_index_set_tags.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
+    lib.gbnns_search_tagged.argtypes = [C.c_void_p, C.POINTER(_SearchArgs), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.gbnns_debug_tag_plan.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int,
+                                         C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(C.c_uint64)]
     lib.gbnns_index_d_low.argtypes = [C.c_void_p]
     lib.gbnns_index_d_low.restype = C.c_uint32
     _lib = lib
@@ -193,6 +198,32 @@ def round_to_half(a):
     wide = np.empty(a.shape, np.float32)
     _check(load_library().gbnns_round_to_half(a.ctypes.data, a.size, bits.ctypes.data, wide.ctypes.data))
     return bits, wide
+
+
+def cut_graph(off, nbr, allowed):
+    """G' of a tagged search, by NumPy: the CSR graph (off [n + 1], nbr) with every adjacency row keeping only the neighbours j with
+    allowed[j] (a boolean mask over the n rows), in their original order -> (offsets uint64, nbrs uint32).  A tagged search of a query
+    whose allowed rows are `allowed` is the reference's search on this graph: allowed = (tags & q_tag) != 0."""
+    off = np.asarray(off, np.uint64)
+    nbr = np.asarray(nbr, np.uint32)
+    allowed = np.asarray(allowed, bool)
+    n = len(off) - 1
+    if allowed.shape != (n,):
+        raise ValueError("allowed must have one entry per row")
+    keep = allowed[nbr]
+    owner = np.repeat(np.arange(n), np.diff(off.astype(np.int64)))
+    new_off = np.zeros(n + 1, np.uint64)
+    new_off[1:] = np.cumsum(np.bincount(owner[keep], minlength=n))
+    return new_off, np.ascontiguousarray(nbr[keep])
+
+
+def tag_plan(metric, dim, n, ell_stride, ef, aux_stride=0, n_entries=1, wide=False, rr_reserve=0):
+    """gbnns_debug_tag_plan (no device needed): name of the first-pass kernel a tagged search of that shape gets."""
+    name = C.create_string_buffer(128)
+    lds = C.c_uint64(0)
+    _check(load_library().gbnns_debug_tag_plan(metric, dim, (dim + 3) // 4 * 4, n, ell_stride, aux_stride, ef, n_entries, int(wide), rr_reserve,
+                                               name, 128, C.byref(lds)))
+    return name.value.decode()
 
 
 def _ptr(x):
@@ -466,6 +497,26 @@ class Index:
         _check(self._lib.gbnns_index_low_rows(self._h, out.ctypes.data, MEM_HOST, None))
         return out
 
+    def set_tags(self, tags, first=0):
+        """gbnns_index_set_tags: rows [first, first + len(tags)) get these 32-bit tag words (numpy: synchronous; torch CUDA int32 tensor:
+        enqueued on the current stream).  The table starts out all ones."""
+        if _is_dev(tags):
+            import torch
+            tags = _prep(tags, np.uint32, "int32")
+            if not tags.is_cuda:
+                raise TypeError("tags: a numpy array or a CUDA/ROCm int32 tensor")
+            _check(self._lib.gbnns_index_set_tags(self._h, tags.data_ptr(), first, tags.numel(), MEM_DEVICE,
+                                                  torch.cuda.current_stream(tags.device).cuda_stream))
+            self._tags_keep = tags
+            return
+        tags = _host(tags, np.uint32)
+        src = tags if tags.size else np.zeros(1, np.uint32)   # (an empty range still names a buffer: NULL with count 0 drops the table)
+        _check(self._lib.gbnns_index_set_tags(self._h, src.ctypes.data, first, tags.size, MEM_HOST, None))
+
+    def clear_tags(self):
+        """Drops the tag table (gbnns_index_set_tags(NULL, 0, 0)): tagged searches are refused until set_tags is called again."""
+        _check(self._lib.gbnns_index_set_tags(self._h, None, 0, 0, MEM_HOST, None))
+
     def close(self):
         if self._h:
             self._lib.gbnns_index_destroy(self._h)
@@ -480,7 +531,7 @@ class Index:
     # -- search ------------------------------------------------------------------------------
     def search(self, queries, ef, mode=MODE_NET, k=1, queries_low=None, entry_ids=None,
                want=("hops", "dist_calc"), hash_capacity=0, stream=None, out=None, flags=0,
-               aux=False, llf=False, hops_bound=50, defer_depth=0, top_k=0):
+               aux=False, llf=False, hops_bound=50, defer_depth=0, top_k=0, query_tags=None):
         """Runs one batch.  numpy queries -> synchronous call, numpy results.  torch CUDA queries
         -> enqueued on `stream` (torch stream or None = current), torch results, no sync.  Pinned torch CPU queries ->
         HOST buffers in page-locked memory, pinned torch results: synchronous, or with FLAG_DEFER_JOIN a host batch in
@@ -488,7 +539,10 @@ class Index:
         `want` may also name "cand", "cand_dist", "q_low", "edges".  Returns a dict with "ids" + wanted.
         aux / llf / hops_bound: the reference's use_second_graph walk over set_aux_graph()'s graph.
         top_k > 0 (NET / LOWQ): gbnns_search_topk -- also "top_ids" / "top_dist" [nq x top_k], the top_k best of each query's ef
-        candidates in ascending (original-space distance, pop index); top_ids[:, 0] == ids."""
+        candidates in ascending (original-space distance, pop index); top_ids[:, 0] == ids.
+        query_tags [nq] (uint32 numpy / int32 torch, like entry_ids): gbnns_search_tagged -- query i walks only the rows j with
+        (tags[j] & query_tags[i]) != 0 (set_tags), i.e. the graph cut_graph gives; combines with top_k."""
+        top_k = top_k or 0
         if aux:
             flags |= FLAG_AUX_GRAPH | (FLAG_LLF if llf else 0)
         dev = _is_dev(queries) and queries.is_cuda
@@ -505,6 +559,7 @@ class Index:
             tdev = queries.device
             entry_ids = None if entry_ids is None else entry_ids.to(torch.int32).contiguous() \
                 if entry_ids.dtype != torch.int32 else entry_ids.contiguous()
+            query_tags = _prep(query_tags, np.uint32, "int32")
 
             def alloc(name, shape, dtype):
                 if name not in res:
@@ -518,6 +573,8 @@ class Index:
             import torch
             if entry_ids is not None and not (_is_dev(entry_ids) and entry_ids.dtype == torch.int32 and entry_ids.is_pinned()):
                 raise TypeError("entry_ids must be a pinned int32 tensor beside pinned queries")
+            if query_tags is not None and not (_is_dev(query_tags) and query_tags.dtype == torch.int32 and query_tags.is_pinned()):
+                raise TypeError("query_tags must be a pinned int32 tensor beside pinned queries")
 
             def alloc(name, shape, dtype):
                 if name not in res:
@@ -529,6 +586,7 @@ class Index:
             sptr = stream.cuda_stream
         else:
             entry_ids = None if entry_ids is None else _host(entry_ids, np.uint32)
+            query_tags = None if query_tags is None else _host(query_tags, np.uint32)
 
             def alloc(name, shape, dtype):
                 if name not in res:
@@ -557,16 +615,23 @@ class Index:
             a.out_q_low = _ptr(alloc("q_low", (nq, self.d_low), f32))
         if "edges" in want:
             a.out_edges = _ptr(alloc("edges", (nq,), i32))
+        if query_tags is not None and int(query_tags.shape[0]) != nq:
+            raise ValueError("query_tags must have one word per query")
         if top_k > 0:
             top_ids = alloc("top_ids", (nq, top_k), i32 if (dev or pinned) else np.uint32)
             top_dist = alloc("top_dist", (nq, top_k), f32)
-            _check(self._lib.gbnns_search_topk(self._h, C.byref(a), top_k, _ptr(top_ids), _ptr(top_dist)))
+            if query_tags is not None:
+                _check(self._lib.gbnns_search_tagged(self._h, C.byref(a), _ptr(query_tags), top_k, _ptr(top_ids), _ptr(top_dist)))
+            else:
+                _check(self._lib.gbnns_search_topk(self._h, C.byref(a), top_k, _ptr(top_ids), _ptr(top_dist)))
+        elif query_tags is not None:
+            _check(self._lib.gbnns_search_tagged(self._h, C.byref(a), _ptr(query_tags), 0, None, None))
         else:
             _check(self._lib.gbnns_search_ex(self._h, C.byref(a)))
         # Inputs (and the result buffers handed out) stay referenced while a lane stream may still read / write them: torch's
         # caching allocators do not know the library's internal streams.  A plain call: until the next call; deferred
         # calls: the last four (= the most lanes a handle has), until wait() / join() / a plain call joins them.
-        held = (queries, queries_low, entry_ids, res)
+        held = (queries, queries_low, entry_ids, query_tags, res)
         if flags & FLAG_DEFER_JOIN:
             self._in_flight.append(held)
         else:

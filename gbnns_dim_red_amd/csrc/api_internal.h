@@ -123,6 +123,7 @@ struct Lane {
     DevBuf q_in, q_low, h1, h2, cand, cand_dist, cnt, hops, dc, edges, out, entries, ovf_list, ovf2_list, ctrl;
     DevBuf g_bitmap, g_keys, fp_bitmap, order, order_hist;
     DevBuf top_ids, top_dist;          // the k-answer rows of a HOST call (gbnns_rerank_topk / gbnns_search_topk)
+    DevBuf qtags;                      // the query tag words of a HOST call (gbnns_search_tagged)
     // visited-set sizing feedback: stats of an earlier call arrive asynchronously in pinned memory
     uint32_t* h_stats = nullptr;       // [4] copy of ctrl after the walk kernels
     hipEvent_t stats_ev = nullptr;
@@ -141,7 +142,7 @@ struct Lane {
     int stage_next = 0;
     DevBuf* bufs(int i) {
         DevBuf* b[] = {&q_in, &q_low, &h1, &h2, &cand, &cand_dist, &cnt, &hops, &dc, &edges, &out, &entries,
-                       &ovf_list, &ovf2_list, &ctrl, &g_bitmap, &g_keys, &fp_bitmap, &order, &order_hist, &top_ids, &top_dist};
+                       &ovf_list, &ovf2_list, &ctrl, &g_bitmap, &g_keys, &fp_bitmap, &order, &order_hist, &top_ids, &top_dist, &qtags};
         return i < (int)(sizeof b / sizeof b[0]) ? b[i] : nullptr;
     }
 };
@@ -151,7 +152,7 @@ struct Lane {
 // starts from, so a test or an A/B run that flips one no longer changes every other handle of the process.  The three knobs of
 // gbnns_exact_knn -- a function without a handle -- stay process-wide.
 struct Knobs {
-    int quotient, vs_disp, max_waves, spec_min_nq, spec_any_form, mlp_small, mlp_net, mlp_slab, late_rows, spec_tail, coop;
+    int quotient, vs_disp, max_waves, spec_min_nq, spec_any_form, mlp_small, mlp_net, mlp_slab, late_rows, spec_tail, coop, hot;
 };
 Knobs knob_defaults();                                    // the process-wide defaults as they stand now
 bool knob_set(Knobs& k, const char* name, int value);     // clamps like the environment does; false = no such handle knob
@@ -176,6 +177,7 @@ struct gbnns_index {
     // and as float32 rows in db_low's own layout [n x dl_pad]; db_low itself stays, for the searches without the flag
     DevBuf low_half, low_r;
     bool half_ready = false;
+    DevBuf tags;                    // gbnns_index_set_tags: [n] tag words, all ones until written (empty: no table)
     bool net_mfma_ready = false;
     int net_form = -1;              // form of the last one-launch exact projection (kernels.h: kNetWholeCu / kNetHalfCu; -1: none yet)
     uint32_t ell_stride = 0, aux_stride = 0;
@@ -262,11 +264,17 @@ struct TopkOut {
     float* dist;
 };
 
-// lanes.cpp: the body of gbnns_search_ex / gbnns_search_topk (topk == nullptr: the former)
-int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk);
+// gbnns_search_tagged's extra input: the queries' tag words [n_q], a buffer of args->mem_kind
+struct TagIn {
+    const uint32_t* qtags;
+};
+
+// lanes.cpp: the body of gbnns_search_ex / gbnns_search_topk / gbnns_search_tagged (topk == nullptr: no k-answer rows; tag == nullptr: untagged)
+int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk, const TagIn* tag = nullptr);
 
 // search_core.cpp
-int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_t s, bool sync_host, const TopkOut* topk = nullptr);
+int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_t s, bool sync_host, const TopkOut* topk = nullptr,
+                const TagIn* tag = nullptr);
 
 
 // How one call is laid out over the handle's lanes (workspace + internal stream each).

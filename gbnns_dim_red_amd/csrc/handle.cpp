@@ -241,6 +241,8 @@ int build_ell(const uint64_t* off, const uint32_t* nbr, uint64_t n, std::vector<
 //   "coop"          the two-wavefront walk for small batches (walk_coop.hip): -1 = where it serves and the batch leaves the room
 //                   (default), 0 = never, 1 = wherever the shape allows (tests, A/B runs; GBNNS_COOP)
 // Process-wide only (gbnns_exact_knn has no handle):
+//   "hot"            0 = the generic register-list / two-list instances also where the plan has a walk_hot* / walk_reg_wide instance
+//                    (GBNNS_HOT; A/B runs: the instance family a tagged call's kernels are built from, untagged)
 //   "knn_chunk"      most rows per filtered chunk (a multiple of 64)
 //   "knn_pool_min_k" shortest list gbnns_exact_knn keeps as an unordered pool (one wavefront per query and chunk) instead of a heap
 //                    (measured on 10^6 x 32: k = 48 0.327 against 0.333 s, k = 100 0.425 against 0.536 s, k = 1 000 2.4 against 7.6 s)
@@ -261,6 +263,7 @@ bool knob_set(Knobs& k, const char* name, int value) {
     else if (!std::strcmp(name, "late_rows")) k.late_rows = std::max(-1, std::min(1, value));
     else if (!std::strcmp(name, "spec_tail")) k.spec_tail = std::max(0, std::min(100, value));
     else if (!std::strcmp(name, "coop")) k.coop = std::max(-1, std::min(1, value));
+    else if (!std::strcmp(name, "hot")) k.hot = value != 0;
     else return false;
     return true;
 }
@@ -279,6 +282,7 @@ static Knobs& knob_default_ref() {  // (function-local: initialised on first use
         knob_set(k, "late_rows", knob_env("GBNNS_LATE_ROWS", -1));
         knob_set(k, "spec_tail", knob_env("GBNNS_SPEC_TAIL", 50));
         knob_set(k, "coop", knob_env("GBNNS_COOP", -1));
+        knob_set(k, "hot", knob_env("GBNNS_HOT", 1));
         return k;
     }();
     return d;
@@ -475,7 +479,7 @@ int gbnns_index_destroy(gbnns_index* ix) {
         if (L.stream) (void)hipStreamDestroy(L.stream);
         for (int i = 0; DevBuf* b = L.bufs(i); ++i) b->release();
     }
-    DevBuf* bufs[] = {&ix->db_own, &ix->db_low_own, &ix->ell, &ix->aux_ell, &ix->net, &ix->net_mfma, &ix->low_half, &ix->low_r};
+    DevBuf* bufs[] = {&ix->db_own, &ix->db_low_own, &ix->ell, &ix->aux_ell, &ix->net, &ix->net_mfma, &ix->low_half, &ix->low_r, &ix->tags};
     for (DevBuf* b : bufs) b->release();
     delete ix;
     return GBNNS_OK;
@@ -676,6 +680,63 @@ int gbnns_debug_walk_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n
     return GBNNS_OK;
 }
 
+int gbnns_debug_tag_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries,
+                         int force_wide, uint32_t rr_reserve, char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
+    if (!name || name_bytes == 0 || !lds_bytes) return fail(GBNNS_ERR_INVALID, "gbnns_debug_tag_plan: null output");
+    if ((metric != GBNNS_METRIC_L2 && metric != GBNNS_METRIC_NEG_DOT) || dim == 0 || dstride != round_up(dim, 4) || n == 0 || n > 0xFFFFFFFFull ||
+        ell_stride == 0 || ell_stride % 16 || aux_stride % 16 || ef < 1 || n_entries > 4096)
+        return fail(GBNNS_ERR_INVALID, "gbnns_debug_tag_plan: not the shape of an index or a search");
+    WalkParams w{};
+    w.dim = dim; w.dstride = dstride; w.n = (uint32_t)n; w.ell_stride = ell_stride; w.ef = ef; w.n_entries = n_entries ? n_entries : 1u;
+    w.aux_ell = aux_stride ? &w.aux_stride : nullptr; w.aux_stride = aux_stride;  // (the plan asks only WHETHER there is an auxiliary graph)
+    w.force_wide = force_wide != 0; w.rr_reserve = rr_reserve; w.tagged = 1;
+    const WalkPlan plan = plan_walk(w, metric, WalkPass::First);
+    const char* planned = plan.general_only ? "walk_general_kernel" : walk_plan_name(plan);
+    if (!planned) return fail(GBNNS_ERR_INTERNAL, "gbnns_debug_tag_plan: no kernel instance for the plan");
+    std::snprintf(name, name_bytes, "%s", planned);
+    *lds_bytes = plan.lds_fixed;
+    return GBNNS_OK;
+}
+
+// ---- gbnns_search_tagged: the rows' tag words -------------------------------------------------------------------------------------------
+
+int gbnns_index_set_tags(gbnns_index* ix, const uint32_t* tags, uint64_t first, uint64_t count, int mem_kind, void* stream) {
+    if (!ix) return fail(GBNNS_ERR_INVALID, "null argument");
+    if (mem_kind != GBNNS_MEM_HOST && mem_kind != GBNNS_MEM_DEVICE) return fail(GBNNS_ERR_INVALID, "unknown mem_kind %d", mem_kind);
+    if (!tags && count) return fail(GBNNS_ERR_INVALID, "gbnns_index_set_tags: null tags");
+    if (first > ix->n || count > ix->n - first)
+        return fail(GBNNS_ERR_INVALID, "gbnns_index_set_tags: rows [%llu, %llu) outside n = %llu", (unsigned long long)first,
+                    (unsigned long long)(first + count), (unsigned long long)ix->n);
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!tags) {  // drop the table: nothing in flight may still read it
+        HIP_TRY(hipDeviceSynchronize());
+        ix->tags.release();
+        return GBNNS_OK;
+    }
+    // (the table is ordered like the rest of the handle's state: by stream order, a call on another stream first waits for the work in flight)
+    if (int rc = enter_stream(ix, s)) return rc;
+    if (!ix->tags.p) {
+        const size_t bytes = (size_t)ix->n * 4;  // exactly sized
+        const hipError_t e = hipMalloc(&ix->tags.p, bytes);
+        if (e != hipSuccess) {
+            ix->tags.p = nullptr;
+            return fail(GBNNS_ERR_OOM, "hipMalloc(%zu): %s", bytes, hipGetErrorString(e));
+        }
+        ix->tags.bytes = bytes;
+        HIP_TRY(launch_fill_u32(ix->tags.as<uint32_t>(), 0xFFFFFFFFu, (size_t)ix->n, s));
+    }
+    uint32_t* dst = ix->tags.as<uint32_t>() + first;
+    if (mem_kind == GBNNS_MEM_DEVICE) {
+        if (count) HIP_TRY(hipMemcpyAsync(dst, tags, (size_t)count * 4, hipMemcpyDeviceToDevice, s));
+        return GBNNS_OK;
+    }
+    if (int rc = host_copy_in(ix->lanes[0], dst, tags, (size_t)count * 4, s)) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    ix->in_flight = false;
+    return GBNNS_OK;
+}
+
 // ---- GBNNS_FLAG_HALF_ROWS: the rounded table ---------------------------------------------------------------------------------------------
 
 namespace {
@@ -787,7 +848,7 @@ int gbnns_index_knob_get(gbnns_index* ix, const char* name, int* out) {
     const struct { const char* n; int v; } all[] = {
         {"quotient", k.quotient}, {"vs_disp", k.vs_disp}, {"max_waves", k.max_waves}, {"spec_min_nq", k.spec_min_nq},
         {"spec_any_form", k.spec_any_form}, {"mlp_small", k.mlp_small}, {"mlp_net", k.mlp_net}, {"mlp_slab", k.mlp_slab},
-        {"late_rows", k.late_rows}, {"spec_tail", k.spec_tail}, {"coop", k.coop}, {"mlp_net_form", ix->net_form}};
+        {"late_rows", k.late_rows}, {"spec_tail", k.spec_tail}, {"coop", k.coop}, {"hot", k.hot}, {"mlp_net_form", ix->net_form}};
     for (const auto& e : all)
         if (!std::strcmp(name, e.n)) { *out = e.v; return GBNNS_OK; }
     return fail(GBNNS_ERR_INVALID, "gbnns_index_knob_get: unknown handle knob '%s'", name);

@@ -92,6 +92,12 @@ struct WalkParams {
     // float32 copy of R, which every kernel but the half instances reads
     const void* db_h;        // [n x dstride] binary16 rows of R (dstride a multiple of 8, no padding), or nullptr
     int32_t half_rows;       // 1: the first pass takes a half instance where the plan has one (walk_plan.cpp)
+    // gbnns_search_tagged (last again): row j is allowed for query i when (tags[j] & qtags[i]) != 0; the walk is the reference's on the graph
+    // whose adjacency rows keep the allowed neighbours only -- a disallowed neighbour is an empty slot
+    const uint32_t* tags;    // [n] tag word of every row, or nullptr
+    const uint32_t* qtags;   // [nq] tag word of every query
+    int32_t tagged;          // 1: the first pass takes a tag instance (walk_tag.hip) or the general kernel the whole batch (walk_plan.cpp)
+    int32_t generic_only;    // diagnostic (knob "hot" = 0): the generic instances also where the plan has a walk_hot* / walk_reg_wide instance
 };
 
 // `form` of a visited set: 0 = 4-byte slots, 1 = five 24-bit ids per 16-byte bucket, 2 = quotient form (seven 16-bit entries)
@@ -104,7 +110,7 @@ hipError_t launch_walk(const WalkPlan& pl, const WalkParams& p, unsigned slots, 
 const char* walk_plan_name(const WalkPlan& pl);   // printable name of the plan's instance, template arguments included (no device needed); nullptr: none
 const char* walk_first_pass_name(hipStream_t s);  // (mangled) name of the first-pass kernel this thread launched last
 const char* walk_retry_pass_name(hipStream_t s);  // ... and of the retry-pass kernel
-hipError_t launch_walk_general(const WalkParams& p, int metric, hipStream_t s);
+hipError_t launch_walk_general(const WalkParams& p, int metric, hipStream_t s);  // (p.tagged: its instance with the tag test)
 // GBNNS_FLAG_HALF_ROWS (walk_half.hip): src [n x sstride] (dim coordinates a row) -> out_h [n x hstride] binary16 bits, round to nearest even,
 // columns from dim on zero; out_f [n x fstride] the same values widened back (fstride <= hstride).  *bad_row (preset to 0xFFFFFFFF) receives the
 // lowest row that holds a coordinate which is not finite or rounds out of the binary16 range.

@@ -70,7 +70,7 @@ int flush_joins(gbnns_index* ix, size_t keep) {
 int flush_join(gbnns_index* ix) { return flush_joins(ix, 0); }
 
 // One search call: validation, the layout over the lanes, the batch (search_core).  `topk`: gbnns_search_topk's extra outputs.
-int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk) {
+int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk, const TagIn* tag) {
     if (!ix || !a) return fail(GBNNS_ERR_INVALID, "null argument");
     if (a->struct_size != sizeof(gbnns_search_args))
         return fail(GBNNS_ERR_INVALID, "gbnns_search_args.struct_size mismatch (%u != %zu)",
@@ -89,6 +89,12 @@ int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk
         return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_LLF needs GBNNS_FLAG_AUX_GRAPH");
     if ((a->flags & GBNNS_FLAG_AUX_GRAPH) && !ix->has_aux)
         return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_AUX_GRAPH without gbnns_index_set_aux_graph");
+    if (tag) {
+        if (a->flags & (GBNNS_FLAG_HALF_ROWS | GBNNS_FLAG_MFMA_PROJECTION))
+            return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_search_tagged: GBNNS_FLAG_HALF_ROWS / GBNNS_FLAG_MFMA_PROJECTION are not served");
+        if (!ix->tags.p) return fail(GBNNS_ERR_INVALID, "gbnns_search_tagged without gbnns_index_set_tags");
+        if (!tag->qtags) return fail(GBNNS_ERR_INVALID, "gbnns_search_tagged: query_tags missing");
+    }
     if (a->flags & GBNNS_FLAG_HALF_ROWS) {
         if (a->mode == GBNNS_MODE_PLAIN)
             return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_HALF_ROWS: NET / LOWQ only (a PLAIN walk's space is the answer space)");
@@ -124,14 +130,15 @@ int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk
             {a->entry_ids, nq * std::max<size_t>(a->n_entries, 1) * 4}, {a->out_ids, nq * 4}, {a->out_hops, nq * 4},
             {a->out_dist_calc, nq * 4}, {a->out_edges, nq * 4}, {a->out_cand, nq * kk * 4}, {a->out_cand_dist, nq * kk * 4},
             {a->out_q_low, nq * ix->d_low * 4},
-            {topk ? topk->ids : nullptr, nq * (topk ? (size_t)topk->k : 0) * 4}, {topk ? topk->dist : nullptr, nq * (topk ? (size_t)topk->k : 0) * 4}};
+            {topk ? topk->ids : nullptr, nq * (topk ? (size_t)topk->k : 0) * 4}, {topk ? topk->dist : nullptr, nq * (topk ? (size_t)topk->k : 0) * 4},
+            {tag ? tag->qtags : nullptr, nq * 4}};
         for (const auto& b : bufs)
             if (b.p && !pinned_alias(static_cast<const char*>(b.p), b.bytes)) n_lanes = 1;
         if (n_lanes == 1) ix->next_lane = lane;  // (the rotation did not advance)
     }
     if (n_lanes <= 1) {
         if ((rc = enter_stream(ix, s))) return rc;
-        return search_core(ix, ix->lanes[0], a, s, true, topk);
+        return search_core(ix, ix->lanes[0], a, s, true, topk, tag);
     }
 
     // ---- deferred join: the batch runs on lane `lane`'s internal stream ---------------------------------------
@@ -154,7 +161,7 @@ int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk
     ix->in_flight = true;
     HIP_TRY(hipStreamWaitEvent(L.stream, ix->fork_ev, 0));
     g_slow.mark("fork");
-    if ((rc = search_core(ix, L, a, L.stream, false, topk))) {
+    if ((rc = search_core(ix, L, a, L.stream, false, topk, tag))) {
         (void)hipDeviceSynchronize();  // leave nothing in flight behind an error
         ix->in_flight = false;
         return rc;
@@ -180,6 +187,13 @@ int gbnns_search_ex(gbnns_index* ix, const gbnns_search_args* a) { return search
 int gbnns_search_topk(gbnns_index* ix, const gbnns_search_args* a, int k, uint32_t* out_top_ids, float* out_top_dist) {
     const TopkOut t{k, out_top_ids, out_top_dist};
     return search_call(ix, a, &t);
+}
+
+int gbnns_search_tagged(gbnns_index* ix, const gbnns_search_args* a, const uint32_t* query_tags, int k, uint32_t* out_top_ids, float* out_top_dist) {
+    const TagIn g{query_tags};
+    if (k == 0 && !out_top_ids && !out_top_dist) return search_call(ix, a, nullptr, &g);
+    const TopkOut t{k, out_top_ids, out_top_dist};  // (k outside 1 .. ef, PLAIN mode, no out_top_ids: refused as for gbnns_search_topk)
+    return search_call(ix, a, &t, &g);
 }
 
 int gbnns_index_wait(gbnns_index* ix, uint32_t keep) {

@@ -11,7 +11,7 @@ namespace gbnns_api {
 // One (sub-)batch on one lane's workspace, enqueued on stream s; arguments validated by gbnns_search_ex.  With HOST
 // buffers the copies in and out are enqueued on s too and, when sync_host, waited for.  `topk` (optional, NET / LOWQ): the k best of
 // each query's candidates go to its arrays as well (rerank_topk kernels, behind stage 3).
-int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_t s, bool sync_host, const TopkOut* topk) {
+int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_t s, bool sync_host, const TopkOut* topk, const TagIn* tag) {
     int rc;
     const uint32_t n_ent = a->n_entries ? a->n_entries : 1u;
     const bool host = a->mem_kind == GBNNS_MEM_HOST;
@@ -66,8 +66,15 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
         if ((rc = L.entries.ensure((size_t)nq * n_ent * 4))) return rc;
         if ((rc = host_copy_in(L, L.entries.p, a->entry_ids, (size_t)nq * n_ent * 4, s))) return rc;
         entries_dev = L.entries.as<uint32_t>();
-        for (size_t i = 0; i < (size_t)nq * n_ent; ++i)
+        // (a tagged call: an entry the query cannot start from is data, HOST and DEVICE buffers alike -- the kernels write its empty row)
+        for (size_t i = 0; i < (size_t)nq * n_ent && !tag; ++i)
             if (a->entry_ids[i] >= ix->n) return fail(GBNNS_ERR_INVALID, "entry id %u >= n", a->entry_ids[i]);
+    }
+    const uint32_t* qtags_dev = tag ? tag->qtags : nullptr;
+    if (tag && host) {
+        if ((rc = L.qtags.ensure((size_t)nq * 4))) return rc;
+        if ((rc = host_copy_in(L, L.qtags.p, tag->qtags, (size_t)nq * 4, s))) return rc;
+        qtags_dev = L.qtags.as<uint32_t>();
     }
 
     g_slow.mark("copy_in");
@@ -195,9 +202,13 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
         streak = quiet ? std::min(streak + 1, 1 << 20) : 0;
     }
     w.force_wide = (a->flags & GBNNS_FLAG_WIDE_INDEX) ? 1 : 0;
+    w.generic_only = ix->knob.hot ? 0 : 1;
     const bool aux = (a->flags & GBNNS_FLAG_AUX_GRAPH) != 0;
-    // sizing statistics are kept per (ef, mode, aux, wide, half rows: another table, other walks)
-    const int skey = ((ef * 8 + a->mode * 2 + (aux ? 1 : 0)) * 2 + w.force_wide) | (w.half_rows ? 1 << 30 : 0);
+    if (tag) {  // gbnns_search_tagged: the walk of the graph cut to the rows each query may see (walk_tag.hip)
+        w.tags = ix->tags.as<uint32_t>(); w.qtags = qtags_dev; w.tagged = 1;
+    }
+    // sizing statistics are kept per (ef, mode, aux, wide, half rows: another table, other walks; tagged: other graphs, shorter walks; knob "hot" = 0: other kernels)
+    const int skey = ((ef * 8 + a->mode * 2 + (aux ? 1 : 0)) * 2 + w.force_wide) | (w.half_rows ? 1 << 30 : 0) | (w.tagged ? 1 << 29 : 0) | (w.generic_only ? 1 << 28 : 0);
     const int calm = ix->calm_streak.count(skey) ? ix->calm_streak[skey] : 0;
     if (aux) {
         w.aux_ell = ix->aux_ell.as<uint32_t>(); w.aux_stride = ix->aux_stride;
@@ -270,7 +281,7 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
         // below -- the pass must at least double the resident wavefronts: 8 by registers against <= 4 by the table -- does from ef 450 on)
         const int min_ef = min_ef_env ? min_ef_env : (rows576 ? 450 : (form == 2 ? 480 : 385));
         const bool forced = (a->flags & GBNNS_FLAG_BITMAP_PASS) != 0;  // diagnostic: whatever ef and batch size
-        if (!w.all_general && !w.coop && (ef >= min_ef || forced) && !(a->flags & GBNNS_FLAG_WIDE_INDEX) && (a->hash_capacity == 0 || forced)) {
+        if (!w.all_general && !w.coop && !w.tagged && (ef >= min_ef || forced) && !(a->flags & GBNNS_FLAG_WIDE_INDEX) && (a->hash_capacity == 0 || forced)) {
             bitmap_plan = plan_walk(w, ix->metric, WalkPass::Bitmap);
             const size_t per_wave = granules(bitmap_plan.lds_fixed);   // (the slot counts below follow the device's CU count, as in sizing.cpp)
             const size_t per_cu = std::min<size_t>(rows576 ? 8 : 32, kMaxLds / per_wave);  // (576-byte rows: 223 registers, two wavefronts per SIMD)
@@ -341,7 +352,7 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
         w2.hash_limit = w2.hash_cap - w2.hash_cap / 16;
         if (skip_retry) {
             // nothing to launch
-        } else if (w2.hash_cap > cap) {
+        } else if (w2.hash_cap > cap && !w.tagged) {  // (a tagged first pass has no retry pass: its hand-overs go straight to the general kernel)
             HIP_TRY(launch_walk(retry, w2, 0, s));
             if (prof) retry_planned = walk_plan_name(retry);
         } else {
@@ -364,7 +375,7 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
             return name;
         };
         const char* mangled = w.all_general ? nullptr : walk_first_pass_name(s);
-        std::string name = "walk_general_kernel";
+        std::string name = "walk_general_kernel";  // (a tagged call: its tagged instance, walk_general_tag_kernel -- one name for both, gbnns.h)
         if (mangled) {
             name = printable(mangled);
             const char* planned = walk_plan_name(first);

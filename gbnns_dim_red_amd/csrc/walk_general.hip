@@ -15,9 +15,12 @@ namespace {
 // node in a per-slot global bitmap (cleared per query); result list and tie list in global
 // memory (tie capacity n: every node can be in it at most once).
 
-template <int METRIC>
-__global__ __launch_bounds__(64) void walk_general_kernel(WalkParams p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+// TAG (gbnns_search_tagged): p.tags / p.qtags are set -- a neighbour j with (tags[j] & qtags[qi]) == 0 is an empty slot of its adjacency row
+// (main and auxiliary alike; the row still ends at its first chunk without a live slot), and an entry row the query may not see is a bad
+// entry.  A kernel of its own (walk_general_tag_kernel): walk_general_kernel keeps its instructions (the shared body moved the operand order
+// of 18 commutative instructions and the registers they name, nothing else).
+template <int METRIC, bool TAG>
+__device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* smem) {
     const int lane = lane_id();
     const uint32_t slot = blockIdx.x;
     float* qf = reinterpret_cast<float*>(smem);
@@ -44,9 +47,14 @@ __global__ __launch_bounds__(64) void walk_general_kernel(WalkParams p) {
             qf[i] = (i < p.dim) ? p.q[(size_t)qi * p.qstride + i] : 0.f;
         wave_sync();
 
+        uint32_t qtag = 0u;
+        if constexpr (TAG) qtag = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.qtags[qi]);
         {
             bool bad = false;  // an entry id outside the index: empty result, no row is touched
             for (uint32_t e = 0; e < n_ent; ++e) bad |= (p.entries ? p.entries[(size_t)qi * n_ent + e] : 0u) >= p.n;
+            if constexpr (TAG) {  // ... or an entry row the query may not see
+                for (uint32_t e = 0; e < n_ent && !bad; ++e) bad |= (p.tags[p.entries ? p.entries[(size_t)qi * n_ent + e] : 0u] & qtag) == 0u;
+            }
             if (bad) {
                 write_bad_entry(p, qi, lane);
                 wave_sync();
@@ -87,9 +95,14 @@ __global__ __launch_bounds__(64) void walk_general_kernel(WalkParams p) {
         auto make_step = [&](const uint32_t* row, uint32_t stride, bool& found) {  // search_function.h:15-40
             for (uint32_t c = 0; c < stride; c += 64) {
                 const uint32_t nb = (c + lane < stride) ? row[c + lane] : kInvalidId;
-                const bool valid = nb != kInvalidId;
-                const uint64_t mv = __ballot(valid);
+                bool valid = nb != kInvalidId;
+                uint64_t mv = __ballot(valid);
                 if (!mv) break;
+                if constexpr (TAG) {  // a disallowed neighbour is an empty slot from here on (a chunk of them is not the end of the row)
+                    valid = valid && (p.tags[nb] & qtag) != 0u;
+                    mv = __ballot(valid);
+                    if (!mv) continue;
+                }
                 st.edges += __popcll(mv);
                 bool fresh = false;
                 if (valid) {
@@ -133,6 +146,18 @@ __global__ __launch_bounds__(64) void walk_general_kernel(WalkParams p) {
     }
 }
 
+template <int METRIC>
+__global__ __launch_bounds__(64) void walk_general_kernel(WalkParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    walk_general_body<METRIC, false>(p, smem);
+}
+
+template <int METRIC>
+__global__ __launch_bounds__(64) void walk_general_tag_kernel(WalkParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    walk_general_body<METRIC, true>(p, smem);
+}
+
 // Diagnostic kernel (tests only): runs one batch merge on a list / survivor set supplied by the host.
 template <int R>
 __global__ __launch_bounds__(64) void debug_merge_kernel(const uint64_t* entries, int size, const uint64_t* surv, int ef,
@@ -174,7 +199,18 @@ __global__ __launch_bounds__(64) void debug_merge_kernel(const uint64_t* entries
 hipError_t launch_walk_general(const WalkParams& p, int metric, hipStream_t s) {
     if (p.nq == 0) return hipSuccess;
     const size_t lds = std::max((size_t)p.dstride * 4, p.rr_db ? (size_t)p.rr_dstride * 4 : (size_t)0);
-    if (metric == 1) {
+    if (p.tagged) {
+        if (!p.tags || !p.qtags) return hipErrorInvalidValue;
+        if (metric == 1) {
+            hipError_t e = set_lds(walk_general_tag_kernel<1>, lds);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL((walk_general_tag_kernel<1>), dim3(kGeneralSlots), dim3(64), lds, s, p);
+        } else {
+            hipError_t e = set_lds(walk_general_tag_kernel<0>, lds);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL((walk_general_tag_kernel<0>), dim3(kGeneralSlots), dim3(64), lds, s, p);
+        }
+    } else if (metric == 1) {
         hipError_t e = set_lds(walk_general_kernel<1>, lds);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((walk_general_kernel<1>), dim3(kGeneralSlots), dim3(64), lds, s, p);

@@ -13,6 +13,19 @@ namespace {
 constexpr uint32_t kQuadRowsMinDim = 128;  // (measured: d = 96 is faster a lane per row -- 1.56 against 1.86 ms at ef 120 --, d = 128 four lanes per row: 1.39 against 1.75)
 
 
+// tag word of row `id` of a compact index (n < 2^24: a 32-bit byte offset)
+__device__ __forceinline__ uint32_t tag_word(const uint32_t* tags, uint32_t id) {
+    return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(tags) + (id << 2));
+}
+
+// The row registers count as read here: a path that leaves the hop early keeps the row loads issued ahead of it where they are (the compiler
+// otherwise sinks them below the branch that only the other path needs them on).
+template <int STEPS>
+__device__ __forceinline__ void keep_rows(const RowRegs<STEPS>& r) {
+#pragma unroll
+    for (int t = 0; t < STEPS; ++t) asm volatile("" ::"v"(r.v[t].x), "v"(r.v[t].y), "v"(r.v[t].z), "v"(r.v[t].w));
+}
+
 // ---- fast kernel: result list, tie list, visited hash set and the query all live in LDS -------
 //
 // LDS layout (dynamic): [keys: ef_pad x u64][tie: kTieCap x u64][q: dstride x f32][hash: cap x u32]
@@ -179,8 +192,21 @@ __global__ __launch_bounds__(64) void walk_bitmap_kernel(WalkParams p) {
 // LATE: rows requested after the visited test -- 1 always, 0 never, -1 by WalkParams::late_rows (both orders in the kernel)
 // HALF: the hop's rows come from the 2-byte table WalkParams::db_h (walk_half.hip; pair-form instances of a compact index) -- p.db is then
 // the float32 copy of the same table R, which the entry row is read from; nothing else differs
+// TAG: gbnns_search_tagged (walk_tag.hip; pair-form instances of a compact index) -- the walk of the graph whose adjacency rows keep only the
+// neighbours j with (p.tags[j] & p.qtags[qi]) != 0.  A hop loads the tag word of every live slot and treats a disallowed slot as an empty one
+// from there on: never claimed in the visited set, no distance, not counted in edges.  The end of a row is still decided by the slots that
+// are non-empty BEFORE the tag test -- a chunk of disallowed neighbours is not the end of the row.  The source asks for the tags first and
+// for the rows of every live slot right behind them (loads return in order: a tag test that waits with the rows still counted as in flight
+// waits for the tags alone), so that a hop keeps two dependent round trips (adjacency row; tags and rows together) where waiting for the tags
+// first makes them three -- the walk is bound by that chain, not by bytes.  What the compiler makes of it differs by
+// instance (read off the code object; tests/test_tags_cpu.py pins the first class): the one-chunk / one-pass instances of 8- / 12- / 16-step
+// rows issue tags, rows, s_waitcnt vmcnt(rows) -- the order meant; the pass-loop register-list instances issue the rows beside the tags but
+// wait for both (their row loads are conditional, the wait is vmcnt(0)); the pass-loop two-list instances and the 36-step ones issue the
+// rows BEHIND the tag test (three round trips, rows of allowed slots only).  keep_rows is what holds the first two classes' loads ahead of
+// the early `continue`.  The instances that request their rows after the visited test (LATE) ask for the new allowed ids only, as before.
+// The query's tag word is wave-uniform and lives in a scalar register.
 template <int METRIC, int STEPS, bool OFF32, int R, bool ONE_CHUNK = false, bool AUX = false, bool BITMAP = false, bool QLDS_W = false, int LATE = -1,
-          bool HALF = false>
+          bool HALF = false, bool TAG = false>
 __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, unsigned char* smem,
                                              uint32_t* ovf_count, uint32_t* ovf_list, uint32_t* bitmap = nullptr) {
     static_assert(!(AUX && ONE_CHUNK), "auxiliary rows have their own length");
@@ -201,6 +227,7 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
     constexpr uint32_t kChunk = kPair ? 32u : 64u;           // adjacency slots per pass
     constexpr uint64_t kSlotLanes = kPair ? 0x5555555555555555ull : ~0ull;  // lanes that own a slot
     static_assert(!HALF || (kPair && OFF32 && !QLDS_W), "HALF: pair-form instances of a compact index");
+    static_assert(!TAG || (kPair && OFF32 && !BITMAP && !HALF), "TAG: pair-form instances of a compact index");
     const int lane = lane_id();
     const uint32_t slot = kPair ? (uint32_t)lane >> 1 : (uint32_t)lane;    // adjacency slot of this lane
     const uint32_t half = kPair ? (uint32_t)lane & 1u : 0u;
@@ -245,6 +272,12 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
     uint32_t worst;                                // hi of lane size-1 (wave-uniform)
     const uint32_t entry = p.entries ? p.entries[qi] : 0u;
     if (entry >= p.n) { write_bad_entry(p, qi, lane); return; }
+    uint32_t qtag = 0u, tg = 0u;  // TAG: the query's tag word; a slot's (declared here: a local inside the hop loop moved the AUX instances' code)
+    if constexpr (TAG) {
+        qtag = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.qtags[qi]);
+        // an entry row the query may not see: the row an entry id >= n gets (the entry itself enters the list untested, as in the reference)
+        if ((tag_word(p.tags, entry) & qtag) == 0u) { write_bad_entry(p, qi, lane); return; }
+    }
     {
         const float d0 = walk_dist<METRIC, STEPS>(qs, row_ptr<OFF32>(p.db, entry, p.dstride), p.dim);
         worst = fkey(d0);
@@ -409,10 +442,11 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
                 mv = __ballot(nb != kInvalidId);
             }
             if (!mv) break;
+            if constexpr (TAG) tg = nb != kInvalidId ? tag_word(p.tags, nb) : 0u;  // the slot's tag word, requested ahead of the rows
             if constexpr (!BITMAP)
                 if ((uint32_t)dist_calc + 64u > p.hash_limit) { status = 2; break; }
             const bool valid = nb != kInvalidId;
-            edges += __popcll(mv & kSlotLanes);
+            if constexpr (!TAG) edges += __popcll(mv & kSlotLanes);
             // row loads go out before the visited test: its LDS round trips overlap the memory latency (rows of already-visited
             // neighbours are fetched in vain) -- or, wide rows in the pair form with WalkParams::late_rows, after it for the new ids only:
             // the 192-byte-row launch at ef = 40 moved 2.24 GB for 1.62 GB of algorithmic bytes, 6.5 TB/s -- bandwidth-bound on those
@@ -446,6 +480,14 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
             };
             if constexpr (kEarlyLoad) {
                 if (!late) request_rows(valid);
+            }
+            if constexpr (TAG) {  // from here on a disallowed slot is an empty one (both lanes of a pair read the same tag word)
+                mv = __ballot(valid && (tg & qtag) != 0u);
+                if (!mv) {  // (not the end of the row: that is the raw mask's business, above)
+                    if (kEarlyLoad && !late) keep_rows(rr);
+                    continue;
+                }
+                edges += __popcll(mv & kSlotLanes);
             }
             // pair form: the even lane of a pair tests / claims the id, the odd lane ends up with the distance
             uint64_t mclaimed;
@@ -592,8 +634,9 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
 // ef <= 64 whatever ef is (the R-register lists spent 28 % of a hop selecting and 30 % inserting at ef = 300).
 // LDS: [BigList: big_list_fixed_bytes(ef)][query: dstride floats][visited set | (BITMAP) re-rank scratch].
 // ONE_PASS: adjacency rows of one pass (the host checks ell_stride), no auxiliary graph -- the hop is straight-line code.
-// HALF: as in walk_reg_one.
-template <int METRIC, int STEPS, bool OFF32, bool AUX = false, bool BITMAP = false, bool ONE_PASS = false, bool LATE = false, bool HALF = false>
+// HALF, TAG: as in walk_reg_one.
+template <int METRIC, int STEPS, bool OFF32, bool AUX = false, bool BITMAP = false, bool ONE_PASS = false, bool LATE = false, bool HALF = false,
+          bool TAG = false>
 __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t qi, unsigned char* smem,
                                                  uint32_t* ovf_count, uint32_t* ovf_list, uint32_t* bitmap = nullptr) {
     constexpr bool kEarlyLoad = (STEPS > 0);
@@ -613,6 +656,7 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
     constexpr uint32_t kChunk = kPair ? 32u : 64u;
     constexpr uint64_t kSlotLanes = kPair ? 0x5555555555555555ull : ~0ull;
     static_assert(!HALF || (kPair && OFF32), "HALF: pair-form instances of a compact index");
+    static_assert(!TAG || (kPair && OFF32 && !BITMAP && !HALF), "TAG: pair-form instances of a compact index");
     const int lane = lane_id();
 #ifdef GBNNS_STAMPS  // diagnostic build: cycles per segment of the hop (tools/stamps.py)
     unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -653,7 +697,8 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
     // (half rows of 24 steps and more: the lane's query pieces are re-read from the wavefront's LDS copy every hop, as in walk_reg_wide_kernel --
     // 72 registers of query beside 72 of squared differences are two wavefronts per SIMD; the float32 instances, bound by their rows' bytes,
     // live with that, the half instance has half the bytes in flight per wavefront and wants the third)
-    constexpr bool kQLds = HALF && STEPS >= 24;
+    // (TAG: the same -- 223 registers would be two wavefronts per SIMD by registers alone, and the tag word wants one more)
+    constexpr bool kQLds = (HALF || TAG) && STEPS >= 24;
     RowRegs<kQLds ? 0 : kQSteps> qreg;
     if constexpr (kEarlyLoad && !kQLds) {
 #pragma unroll
@@ -664,6 +709,11 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
     // (readfirstlane: every lane computes the same entry id / distance; the compiler must know they are wave-uniform)
     const uint32_t entry = (uint32_t)__builtin_amdgcn_readfirstlane((int)(p.entries ? p.entries[qi] : 0u));
     if (entry >= p.n) { write_bad_entry(p, qi, lane); return; }
+    uint32_t qtag = 0u;  // TAG: the query's tag word
+    if constexpr (TAG) {
+        qtag = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.qtags[qi]);
+        if ((tag_word(p.tags, entry) & qtag) == 0u) { write_bad_entry(p, qi, lane); return; }  // (as in walk_reg_one)
+    }
     {
         uint32_t k0;
         if constexpr (kPair) {
@@ -743,12 +793,14 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
                 mv = __ballot(nb != kInvalidId);
             }
             if (!mv) break;
+            uint32_t tg = 0u;  // TAG: the slot's tag word, requested ahead of the rows
+            if constexpr (TAG) tg = nb != kInvalidId ? tag_word(p.tags, nb) : 0u;
             if constexpr (!BITMAP)
                 if ((uint32_t)dist_calc + 64u > p.hash_limit) { status = 2; break; }
             const bool valid = nb != kInvalidId;
             STAMP(t3)
             if (c == 0 && !is_aux) { STAMP_ADD(2, t2, t3) }
-            edges += __popcll(mv & kSlotLanes);
+            if constexpr (!TAG) edges += __popcll(mv & kSlotLanes);
             RowRegs<kQSteps> rr;
             HalfRowRegs<HALF ? kQSteps : 0> rh;  // (HALF: the row as loaded, packed until the distance consumes it)
             uint32_t roff = 0;
@@ -779,6 +831,15 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
             };
             if constexpr (kEarlyLoad) {
                 if (!late) request_rows(valid);
+            }
+            if constexpr (TAG) {  // from here on a disallowed slot is an empty one (walk_reg_one)
+                mv = __ballot(valid && (tg & qtag) != 0u);
+                if (!mv) {
+                    // (rows of 24 steps and more: not kept -- 72 row registers live across this branch are the 223 registers kQLds avoids)
+                    if constexpr (kEarlyLoad && !late && STEPS < 24) keep_rows(rr);
+                    continue;
+                }
+                edges += __popcll(mv & kSlotLanes);
             }
             uint64_t mclaimed;
             if constexpr (BITMAP) {

@@ -38,6 +38,13 @@ static bool half_serves(int metric, int steps, int regs, uint32_t n_entries) {
     return metric == 0 && (steps == 12 || steps == 16 || (steps == 36 && regs == 4));
 }
 
+// The tag instances (walk_tag.hip): the same shapes -- first pass of a compact index, one entry point per query, no auxiliary graph (plan_walk
+// checks those).  A tagged call outside them runs whole on the general kernel (WalkPlan::general_only).
+static bool tag_serves(int metric, int steps, int regs) {
+    if (steps == 8) return true;
+    return metric == 0 && (steps == 12 || steps == 16 || (steps == 36 && regs == 4));
+}
+
 WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv& env) {
     const bool off32 = compact_index(p), aux = p.aux_ell != nullptr, retry = pass == WalkPass::Retry;
     const int ef = p.ef, regs = ef <= 64 ? 1 : (ef <= kHot2MaxEf ? 2 : 4);
@@ -46,7 +53,9 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
     WalkPlan pl{};
     WalkInstance& k = pl.inst;
     pl.pass = pass;
-    pl.general_only = p.n_entries > 1;
+    // (gbnns_search_tagged: first pass only -- a tagged call has neither a retry nor a bitmap pass, search_core.cpp)
+    const bool tag = p.tagged != 0 && pass == WalkPass::First;
+    pl.general_only = p.n_entries > 1 || (tag && (aux || !off32));
     // The LDS-list kernel serves ef beyond the register lists, and auxiliary-graph walks over tables >= 4 GiB (the register-list /
     // two-list kernels have their auxiliary-graph hop in the 32-bit-offset instances only).
     pl.lds_list = ef > kRegListMaxEf || (aux && !off32);
@@ -54,7 +63,7 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
     pl.packed = pl.lds_list ? (p.n <= 0xFFFFFFu && !p.force_wide) : off32;
     // (a visited set in the packed form: no id may look like a half-written slot -- see visited_test_mask_packed)
     pl.coop_serves = metric == 0 && (rows == 32u || rows == 48u || rows == 64u) && regs == 4 && ef <= kRegListMaxEf && off32 && p.n < 0xFF0000u && !aux &&
-                     one && p.n_entries <= 1u;
+                     one && p.n_entries <= 1u && !tag;
     if (pass == WalkPass::Bitmap) {
         // The bitmap first pass runs the register-list (ef <= 128, L2) / two-list (128 < ef <= 1 024, both metrics) walk for 128-byte rows
         // of a compact index, the two-list walk for 256- and 576-byte rows with L2 (the reference's glove 300 -> 144), else the LDS-list walk.
@@ -69,12 +78,13 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
         pl.rr_base = big ? (size_t)p.rr_reserve : pl.lds_fixed;
         return pl;
     }
-    const bool coop = !retry && p.coop;
+    const bool coop = !retry && p.coop && !tag;
     // Shape served by the walk_hot* kernels (first pass only): 128-byte rows, adjacency rows of one 32-slot pass (walk_hotw*: 33 .. 64
     // slots, two passes), compact index (their visited set stores 24-bit ids)
     // (half rows, GBNNS_FLAG_HALF_ROWS: never -- the family reads float32 rows; the generic instances below have half forms)
     const bool half = p.half_rows != 0 && pass == WalkPass::First;
-    const bool hot = !retry && !coop && !half && (metric == 0 || metric == 1) && rows == 32u && ef <= kBigMaxEf && p.ell_stride <= 64u && off32 &&
+    // (a tagged call: never either -- the generic instances below have tag forms)
+    const bool hot = !retry && !coop && !half && !tag && !p.generic_only && (metric == 0 || metric == 1) && rows == 32u && ef <= kBigMaxEf && p.ell_stride <= 64u && off32 &&
              (!p.stamps_on || (regs == 4 && !env.stamps_generic)) && !aux;
     pl.lds_fixed = lds_fixed_bytes(ef, p.dstride, hot, pl.lds_list, coop);
     // the quotient form: the walk_hot* family and the register-list / two-list kernels of a compact index (the retry kernels keep the packed form)
@@ -97,6 +107,7 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
     else if (rows == 128u && env.wide2 && ef > kPlain512PairMinEf && !pl.lds_list) steps = 32;
     if (pl.lds_list) {
         k = {WalkFamily::LdsList, metric, steps, 0, false, retry, false, false, false, false, pl.packed};
+        pl.general_only = pl.general_only || tag;  // (no tag form)
         return pl;
     }
     if (regs == 4) {  // the two-list kernels, one instance for every ef up to 1 024
@@ -108,7 +119,9 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
             k.one = p.ell_stride <= ((steps == 8 || l2_unrolled) ? 32u : 64u);
             k.late = l2_unrolled && steps >= 24 && late;
             k.half = half && half_serves(metric, steps, 4, p.n_entries);
+            k.tag = tag && tag_serves(metric, steps, 4);
         }
+        pl.general_only = pl.general_only || (tag && !k.tag);
         return pl;
     }
     // one / two list registers.  384-byte rows: the pair form for the first pass of a compact index over one-pass adjacency rows
@@ -116,6 +129,7 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
     // row; the two-register list 1.254 / 1.834 at ef 80 / 120 against 1.255 / 1.814: stays on the run-time-length instance)
     if (rows == 96u && metric == 0 && env.wide2 && !retry && off32 && !aux && (one || (p.ell_stride <= 64u && regs == 1)) && !p.stamps_on) {
         k = {WalkFamily::RegList, 0, 24, regs, true, false, one};
+        pl.general_only = pl.general_only || tag;  // (no tag form)
         return pl;
     }
     if (steps >= 24) steps = 0;  // (576-byte rows at ef <= 128: the run-time-length instances)
@@ -123,10 +137,12 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
     if (!aux && regs == 1 && off32 && !retry && p.ell_stride <= ((steps == 8 || (metric == 0 && steps >= 12)) ? 32u : 64u)) {
         // ef <= 64, adjacency rows of one pass: a loop-free expansion; 192- / 256-byte rows with L2: the instance with the query in LDS
         // (half rows: the loop-free expansion of the list family itself -- the query-in-LDS instances have no half form)
-        if (metric == 0 && steps >= 12 && !p.stamps_on && !half) k = {WalkFamily::RegWide, 0, steps, 0, false, false, false, false, late};
+        if (metric == 0 && steps >= 12 && !p.stamps_on && !half && !tag && !p.generic_only) k = {WalkFamily::RegWide, 0, steps, 0, false, false, false, false, late};
         else k.one = true;
     }
     k.half = half && !aux && off32 && half_serves(metric, steps, regs, p.n_entries);
+    k.tag = tag && !aux && off32 && p.n_entries <= 1u && tag_serves(metric, steps, regs);
+    pl.general_only = pl.general_only || (tag && !k.tag);
     return pl;
 }
 

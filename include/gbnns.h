@@ -305,6 +305,44 @@ int gbnns_rerank_topk(gbnns_index* index, const float* queries, uint64_t n_q, co
 int gbnns_search_topk(gbnns_index* index, const gbnns_search_args* args, int k, uint32_t* out_top_ids,
                       float* out_top_dist);
 
+/* Tag-filtered search (opt-in: an entry point of its own; no other call changes in any way).  Every row j of the index has a 32-bit tag
+ * word T[j], every query i a word Q[i], and row j is ALLOWED for query i when (T[j] & Q[i]) != 0: deleted rows, tenants, categories, "not
+ * the item itself".  The definition: a tagged search of query i is the reference's search of query i on the graph G'(i) -- the index's graph
+ * with every adjacency row keeping only the neighbours allowed for query i, in their original order; the auxiliary graph, where used, is
+ * cut the same way.  Nothing else changes: the arithmetic, the visit order among the kept neighbours, the tie behaviour, the fused or
+ * separate re-rank (whose candidates are all allowed by construction), and the meaning of every output -- ids, hops, dist_calc, edges (the
+ * degrees in G'), out_cand / out_cand_dist in pop order, out_q_low, the top-k rows.  Consequences:
+ *   - a disallowed row is never claimed in the visited set, never has its distance computed and is never counted;
+ *   - the expected value of every output is the CPU oracle's on the CSR cut with NumPy (gbnns_dim_red_amd.cut_graph), one oracle call per
+ *     distinct value of Q -- bit for bit, the tests take no tolerance;
+ *   - the entry point is the reference's: it enters the heap untested.  A query whose entry row is not allowed for it (with several entry
+ *     points: any of them) gets the row an entry id >= n gets: answer 0xFFFFFFFF, an all-0xFFFFFFFF candidate row, +inf distances, zero
+ *     counters, 0xFFFFFFFF / +inf top-k rows.  That includes every query with Q[i] == 0.  In a tagged call this is data, not an argument
+ *     error, for HOST and DEVICE buffers alike (an entry id >= n in a HOST buffer too);
+ *   - with T all 0xFFFFFFFF and Q all 0xFFFFFFFF every output equals the untagged search's bit for bit, counters included;
+ *   - restricting the walk to G' can strand a query in a small component when few rows are allowed.  That is the definition, not a
+ *     defect: raise ef, or supply entry points that are allowed (and close).  DESIGN.md 5.1 ("Tagged search") has the measured recall by allowed fraction.
+ *
+ * gbnns_index_set_tags: the handle owns an n x 4-byte device table, created on first use and initialised to 0xFFFFFFFF.  The call
+ * overwrites rows [first, first + count) from a HOST (synchronous) or DEVICE buffer, ordered on `stream` like a search on that stream.
+ * tags == NULL with count == 0 drops the table (synchronises the device).  A range outside n: GBNNS_ERR_INVALID.
+ *
+ * gbnns_search_tagged: query_tags [n_q], a buffer of args->mem_kind.  With k == 0 and both outputs NULL it is gbnns_search_ex under the
+ * contract above, with 1 <= k <= ef gbnns_search_topk under it (k > ef, or PLAIN mode with k != 0: GBNNS_ERR_INVALID).  NET, LOWQ and
+ * PLAIN modes.  Needs gbnns_index_set_tags and query_tags (else GBNNS_ERR_INVALID).  Combines with hash_capacity, several entry points,
+ * GBNNS_FLAG_AUX_GRAPH / GBNNS_FLAG_LLF, GBNNS_FLAG_WIDE_INDEX, GBNNS_FLAG_SERIAL, GBNNS_FLAG_NO_FUSED_RERANK and GBNNS_FLAG_DEFER_JOIN
+ * (query_tags then obeys the lifetime and page-lock rules of the other inputs); GBNNS_FLAG_BITMAP_PASS is ignored.  With
+ * GBNNS_FLAG_HALF_ROWS or GBNNS_FLAG_MFMA_PROJECTION: GBNNS_ERR_UNSUPPORTED for now.  The gbnns_multi_* searches have no tagged form yet.
+ * The first pass is a tag instance (walk_reg_tag_kernel / walk_reg_big_tag_kernel in gbnns_profile.walk_kernel: the tag test per neighbour,
+ * inside the hop) for a compact index (tables < 4 GiB, n < 2^24) with one entry point per query and no auxiliary graph, over rows of
+ * 32 / 48 / 64 floats with L2 and 32 floats with the negative dot at every beam up to 1 024 and of 144 floats with L2 at beams above 128;
+ * what it hands over goes straight to the general kernel (there is no tagged retry pass), and every other case runs whole on the general
+ * kernel: same results.  gbnns_profile.walk_kernel and gbnns_debug_tag_plan then say "walk_general_kernel": the name stands for the general
+ * kernel in both its forms -- what a tagged call launches is its instance with the tag test, walk_general_tag_kernel.  Device memory: 4 n bytes. */
+int gbnns_index_set_tags(gbnns_index* index, const uint32_t* tags, uint64_t first, uint64_t count, int mem_kind, void* stream);
+int gbnns_search_tagged(gbnns_index* index, const gbnns_search_args* args, const uint32_t* query_tags, int k, uint32_t* out_top_ids,
+                        float* out_top_dist);
+
 /* Per-kernel device timing (hipEvent pairs on the launch stream), accumulated since the last
  * reset.  Reading synchronises the recorded events. */
 typedef struct {
@@ -363,6 +401,8 @@ int gbnns_profile_enable(gbnns_index* index, int on);
  * "late_rows": the wide-row instances that have both forms (walk_reg_wide_kernel: 192- / 256-byte rows at ef <= 64; the two-list kernel
  * over 576-byte rows) request a hop's rows before its visited test (0) or after it, for the new ids only (1); -1 (default) = by
  * shape and residency (576-byte rows with at least five wavefronts per CU, 192-byte rows at ef <= 64: after; GBNNS_LATE_ROWS).
+ * "hot": 0 = the first pass takes the generic register-list / two-list instances also where the plan has a hand-laid-out walk_hot* or
+ * walk_reg_wide instance (default 1; GBNNS_HOT) -- the family the tag instances of gbnns_search_tagged are built from, untagged, for A/B runs.
  * "knn_chunk": most base rows per filtered chunk of gbnns_exact_knn (default 32 768; the pool path takes four times that;
  * GBNNS_KNN_CHUNK).
  * "knn_pool_min_k": shortest list gbnns_exact_knn's filter path keeps as an unordered pool with a radix select (one
@@ -383,6 +423,10 @@ int gbnns_profile_read(gbnns_index* index, gbnns_profile* out, int reset);
 int gbnns_debug_walk_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef,
                           uint32_t n_entries, int force_wide, int coop, int late_rows, int spec_rows, int pass, uint32_t rr_reserve,
                           char* name, uint32_t name_bytes, uint64_t* lds_bytes);
+/* Diagnostic, no device needed: the first-pass kernel a gbnns_search_tagged call of that shape gets ("walk_general_kernel": the whole
+ * batch runs on the general kernel), rows requested before the visited test where an instance has both orders.  Inputs as for gbnns_debug_walk_plan. */
+int gbnns_debug_tag_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef,
+                         uint32_t n_entries, int force_wide, uint32_t rr_reserve, char* name, uint32_t name_bytes, uint64_t* lds_bytes);
 /* Diagnostic, no device needed: LDS bytes of a workgroup of the one-launch projection for a net d -> d_hidden -> d_hidden -> d_low, in
  * the whole-CU form (form 0) or the half-CU form (form 1), with a queries per lane (2 .. 5), and whether that form takes the net at all
  * (*admitted: a workgroup with a = 4 fits 160 KB / 80 KB). */
