@@ -185,7 +185,8 @@ struct gbnns_index {
     bool has_net = false;
     float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *w3 = nullptr, *b3 = nullptr;
     uint32_t ws1 = 0, ws2 = 0, ws3 = 0;
-    int cus = 0;                    // compute units of the device (sizes the one-launch projection's query strips)
+    const float* net_img[2][3] = {};   // [form][layer]: the weights in the one-launch projection's staged order (kernels.h pack_net_image; in `net`)
+    int cus = 0;                   // compute units of the device (sizes the one-launch projection's query strips)
     size_t cu_count() const { return cus > 0 ? (size_t)cus : 256; }   // ... for the walk's residency rules (unknown: an MI355X's)
     gbnns_api::Knobs knob{};        // this handle's diagnostic knobs (gbnns_index_knob; start: the process defaults at creation)
     // workspaces: lane 0 serves plain calls on the caller's stream; the batches of deferred calls rotate over

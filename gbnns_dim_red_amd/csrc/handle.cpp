@@ -173,6 +173,32 @@ void repack_layer(const float* layer, uint32_t din, uint32_t dout, uint32_t wstr
     }
 }
 
+}  // namespace gbnns_api
+
+// W [dout x wstride] (repack_layer's rows) -> the staged-order image of kernels.h, [slice][chunk][go b rows x ldw floats]: the
+// one-launch projection's wavefronts copy a chunk of it into their staging buffers as it stands.  Once per index and form.
+void gbnns::pack_net_image(const float* w, uint32_t wstride, uint32_t din, uint32_t dout, uint32_t b, uint32_t go, float* out) {
+    const NetImageGeom g = net_image_geom(din, dout, b, go);
+    const uint32_t k16 = round_up(din, 16);
+    std::memset(out, 0, net_image_floats(din, dout, b, go) * sizeof(float));
+    for (uint32_t s = 0; s < g.slices; ++s)
+        for (uint32_t c = 0; c < g.nch; ++c) {
+            float* chunk = out + ((size_t)s * g.nch + c) * g.buf;
+            for (uint32_t r = 0; r < g.rows; ++r) {
+                const uint32_t nr = g.interleaved ? (r % go) * b + r / go : r;   // the slice's neuron staged in row r
+                const uint32_t o = std::min(s * g.rows + nr, dout - 1u);         // (rows beyond dout repeat the last: their results are dropped)
+                for (uint32_t kk = 0; kk < g.ck; ++kk) {
+                    const uint32_t k = c * g.ck + kk;
+                    if (k >= k16) break;                                         // zeros from the row's padded end on
+                    const uint32_t q = (kk >> 2) & 3u, t = kk & 3u;
+                    chunk[(size_t)r * g.ldw + (kk & ~15u) + 4u * t + 2u * (q >> 1) + (q & 1u)] = w[(size_t)o * wstride + k];
+                }
+            }
+        }
+}
+
+namespace gbnns_api {
+
 // CSR (host) -> padded adjacency.  Order inside each list is preserved.  A neighbour id that
 // repeats inside one list is dropped after its first occurrence: the reference would find it
 // already visited (search_function.h:25), so this changes nothing observable.
@@ -406,6 +432,19 @@ int gbnns_index_create(const gbnns_index_desc* desc, gbnns_index** out) {
             repack_layer(p2, dh, dh, ix->ws2, packed);
             const size_t o3 = packed.size();
             repack_layer(p3, dh, dl, ix->ws3, packed);
+            // the one-launch projection's staged-order images, one per form: built here, once, so that no search packs or waits
+            size_t img_off[2][3];
+            {
+                const size_t wo[3] = {0, o2, o3};
+                const uint32_t din[3] = {d, dh, dh}, dout[3] = {dh, dh, dl}, ws[3] = {ix->ws1, ix->ws2, ix->ws3};
+                for (int form = 0; form < 2; ++form)
+                    for (int l = 0; l < 3; ++l) {
+                        const uint32_t b = l < 2 ? 8u : net_image_b3(dl), go = net_image_go(form);
+                        img_off[form][l] = packed.size();
+                        packed.resize(packed.size() + net_image_floats(din[l], dout[l], b, go));
+                        pack_net_image(packed.data() + wo[l], ws[l], din[l], dout[l], b, go, packed.data() + img_off[form][l]);
+                    }
+            }
             rc = ix->net.ensure(packed.size() * 4);
             if (!rc) {
                 hipError_t e = hipMemcpy(ix->net.p, packed.data(), packed.size() * 4, hipMemcpyHostToDevice);
@@ -418,6 +457,8 @@ int gbnns_index_create(const gbnns_index_desc* desc, gbnns_index** out) {
             ix->b2 = ix->w2 + (size_t)dh * ix->ws2;
             ix->w3 = base + o3;
             ix->b3 = ix->w3 + (size_t)dl * ix->ws3;
+            for (int form = 0; form < 2; ++form)
+                for (int l = 0; l < 3; ++l) ix->net_img[form][l] = base + img_off[form][l];
             ix->has_net = true;
         }
     }
@@ -510,6 +551,7 @@ int run_project(gbnns_index* ix, Lane& L, const float* x, uint32_t xstride, uint
             const int mode = ix->knob.mlp_net;
             const bool want_half = mode == 3 || (mode == 1 && in_flight);
             n.form = want_half && mlp_net_half_serves(n) ? kNetHalfCu : kNetWholeCu;
+            for (int l = 0; l < 3; ++l) n.img[l] = ix->net_img[n.form][l];
             HIP_TRY(launch_mlp_net(n, s));
             ix->net_form = n.form;
             std::snprintf(ix->acc.project_kernel, sizeof(ix->acc.project_kernel), "mlp_net_kernel");
@@ -656,6 +698,24 @@ int gbnns_debug_net_lds(uint32_t d, uint32_t d_hidden, uint32_t d_low, int form,
     n.dout[0] = n.dout[1] = d_hidden; n.dout[2] = d_low;
     *lds_bytes = mlp_net_lds_bytes(n, form, a);
     *admitted = mlp_net_lds_bytes(n, form, 4) <= (form == kNetHalfCu ? 80u : 160u) * 1024u;
+    return GBNNS_OK;
+}
+
+// Diagnostic (not in gbnns.h; host only, no device): the staged-order image of one layer (kernels.h pack_net_image) for host weights
+// w [dout x wstride], b neurons per lane group (8 hidden; last layer: *b3_of_d_low says which), go neuron groups (2 whole-CU, 4 half-CU).
+// out == NULL: only the sizes.  geom: {ck, ldw, rows, buf, nch, slices, interleaved, floats of the image}.
+int gbnns_debug_net_image(const float* w, uint32_t wstride, uint32_t din, uint32_t dout, uint32_t b, uint32_t go, float* out,
+                          uint64_t out_floats, uint64_t* geom8, uint32_t* b3_of_dout) {
+    if (!geom8 || !din || !dout || !(b == 2 || b == 4 || b == 8) || !(go == 2 || go == 4) || wstride < round_up(din, 16))
+        return fail(GBNNS_ERR_INVALID, "gbnns_debug_net_image: no such layer or form");
+    const NetImageGeom g = net_image_geom(din, dout, b, go);
+    const uint64_t floats = net_image_floats(din, dout, b, go);
+    const uint64_t v[8] = {g.ck, g.ldw, g.rows, g.buf, g.nch, g.slices, g.interleaved ? 1u : 0u, floats};
+    std::memcpy(geom8, v, sizeof v);
+    if (b3_of_dout) *b3_of_dout = net_image_b3(dout);
+    if (!out) return GBNNS_OK;
+    if (!w || out_floats < floats) return fail(GBNNS_ERR_INVALID, "gbnns_debug_net_image: output of %llu floats needed", (unsigned long long)floats);
+    pack_net_image(w, wstride, din, dout, b, go, out);
     return GBNNS_OK;
 }
 

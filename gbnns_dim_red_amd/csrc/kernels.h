@@ -181,8 +181,33 @@ struct NetLaunch {
     unsigned long long* stamps;  // diagnostic builds (-DGBNNS_NET_STAMPS): [blocks x 8] 100 MHz timestamps of the phase ends
     int32_t form;            // kNetWholeCu: blocks of 8 wavefronts, one per CU; kNetHalfCu: of 4 wavefronts and half the LDS, two per CU
     uint32_t lds_floor;      // diagnostic: request at least this much LDS per block (> 80 KB: half-CU blocks one per CU)
+    const float* img[3];     // the layers' weights as the staged-order image of `form` (pack_net_image below), 16-byte aligned
 };
 constexpr int32_t kNetWholeCu = 0, kNetHalfCu = 1;
+// The staged-order weight image of a layer of the one-launch kernel: what a wavefront's staging buffer holds for each of its chunks,
+// byte for byte, so that a chunk goes from memory to LDS by DMA (mlp_net.hip).  A layer is cut into slices of go x b neurons (go
+// neuron groups per row of 16 lanes: 2 in the whole-CU form, 4 in the half-CU form; b neurons per lane group: 8 in the hidden
+// layers, net_image_b3 in the last) and chunks of ck inputs; the image is [slice][chunk][rows x ldw floats]: staged row r holds
+// neuron obase + (interleaved ? (r % go) * b + r / go : r) of the slice, clamped to the layer's last neuron, the chunk's ck inputs
+// permuted in blocks of 16 (input 16 m + 4 q + t at float 16 m + 4 t + 2 (q / 2) + q % 2), zero from the row's padded end
+// ((din + 15) & ~15) on, and ldw - ck padding floats (zero).
+struct NetImageGeom {
+    uint32_t ck, ldw, rows, buf;   // inputs per chunk, floats per staged row, rows (go x b) and floats (rows x ldw) per chunk
+    uint32_t nch, slices;          // chunks per slice, slices of the layer
+    bool interleaved;
+};
+constexpr NetImageGeom net_image_geom(uint32_t din, uint32_t dout, uint32_t b, uint32_t go) {
+    const uint32_t ck = b >= 4 ? 32u : 64u;
+    return NetImageGeom{ck, ck + 4u, go * b, go * b * (ck + 4u), (din + ck - 1u) / ck, (dout + go * b - 1u) / (go * b), go == 4 && b >= 4};
+}
+constexpr uint32_t net_image_b3(uint32_t d_low) { return (d_low + 15u) / 16u <= 2u ? 2u : 4u; }  // the last layer's neurons per lane group
+constexpr uint32_t net_image_go(int32_t form) { return form == kNetHalfCu ? 4u : 2u; }
+constexpr size_t net_image_floats(uint32_t din, uint32_t dout, uint32_t b, uint32_t go) {
+    const NetImageGeom g = net_image_geom(din, dout, b, go);
+    return (size_t)g.slices * g.nch * g.buf;
+}
+// host only, no device needed (handle.cpp): w [dout x wstride] rows -> out [net_image_floats]
+void pack_net_image(const float* w, uint32_t wstride, uint32_t din, uint32_t dout, uint32_t b, uint32_t go, float* out);
 bool mlp_net_serves(const NetLaunch& n);   // shape, alignment and batch size fit the one-launch kernel
 bool mlp_net_half_serves(const NetLaunch& n);   // ... and the half-CU form's block (16 queries and more) fits 80 KB of LDS
 size_t mlp_net_lds_bytes(const NetLaunch& n, int form, int A);   // LDS of a block of `form` with A queries per lane (2 .. 5)

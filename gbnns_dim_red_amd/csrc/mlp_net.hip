@@ -1,5 +1,5 @@
 // mlp_net.hip -- the projection (GetLowQueryFromNet, support_func.h:645-658) as ONE launch: a workgroup takes a strip of
-// queries through the three layers, activations never leave LDS, weights stream from L2 through wavefront-private LDS.
+// queries through the three layers, activations never leave LDS, weights stream from L2 into wavefront-private LDS by DMA.
 //
 // Arithmetic (bit for bit the per-layer kernels' of mlp.hip): per neuron  out = 0 - Angular::Dist(row, in) + bias
 // (support_func.h:624-633), Angular::Dist = eight running sums over k mod 8, fold m_j = c_{j+4} + c_j, (m0 + m1) + (m2 + m3)
@@ -32,6 +32,19 @@
 // one row j and go = 1 and 2 of the next.  The staged weight rows of B >= 4 (144 bytes each) are interleaved, row b GO + go:
 // the four go are 144 bytes apart (slots 0, 9, 2, 11 of the 16 of a bank row), distinct for those lanes and for any 16
 // lanes of one row j alike; at B = 2 (272-byte rows) the plain order go B + b is (go 544 bytes apart: slots 0, 2, 4, 6).
+//
+// Weights.  They are constant for the life of an index, so the order a staging buffer wants them in -- the rows of a wavefront's
+// slice, interleaved where the form says so, each row's inputs permuted in blocks of 16 like the activations, 4 padding floats a
+// row, zeros beyond the layer's padded inputs, the last neuron repeated beyond dout -- is made ONCE, on the host, when the index is
+// created (handle.cpp pack_net_image; kernels.h NetImageGeom: [slice][chunk][GO B rows x LDW floats], one image per form).  A chunk
+// then goes from memory to LDS as it stands: global_load_lds_dwordx4, 1 KiB per wave-instruction (lane l's 16 bytes at 16 l), NP
+// = 5 of them for the 4 608 bytes of a half-CU hidden chunk, 3 for the whole-CU form's 2 304 -- the last piece starts 1 KiB before
+// the buffer's end and writes some bytes of the piece before it a second time, so buffers keep their size and nothing is written
+// beyond one.  No weight passes through a vector register, no ds_write stages one, and with no chunk held in registers both forms
+// stage whole chunks (until this the half-CU form staged one double k-step at a time to stay under 240 registers).  Order: the
+// DMA counts on the issuing wavefront's vector-memory counter; staging is wavefront-private, so the wavefront's own s_waitcnt
+// vmcnt(0) before its first read of a buffer is all the ordering a read needs (net_dma_wait), and a DMA into a buffer is issued
+// only behind arithmetic that has consumed the last weights read from it (net_layer).
 #include <algorithm>
 
 #include "launch_util.h"
@@ -62,28 +75,30 @@ struct NetGeom {
     static constexpr int P = CK / 4;          // 16-byte pieces per row
     static constexpr int BUF = GO * B * LDW;  // floats per staging buffer
     static constexpr int NU = CK / 16;        // double k-steps per chunk
-    // What a wavefront requests from L2 and stages at a time: a whole chunk -- or, in the half-CU form's B >= 4 layers, whose chunk of
-    // 4 B rows would be 16 registers per lane in flight (272 vector registers at A = 5, B = 8 where the form is held to 240; 232 this way), ONE double k-step of it,
-    // requested a step (1 300 cycles of packed arithmetic and more) ahead instead of a chunk
-    static constexpr int FK = (GO == 4 && B >= 4) ? 16 : CK;   // k-values per fetch unit
-    static constexpr int PF = FK / 4;         // 16-byte pieces per row and unit
-    static constexpr int NF = GO * B * PF / 64; // 16-byte pieces per lane and unit
-    static constexpr bool BY_STEP = FK != CK;
+    static constexpr int NF = GO * B * P / 64;  // 16-byte pieces per lane and chunk (register staging: the slab kernel)
+    // LDS-DMA of a chunk (mlp_net_kernel): one wave-instruction writes 1 KiB, lane l its 16 bytes at 16 l; a buffer is NP such
+    // pieces, the last one moved back so that it ends where the buffer ends (it writes some bytes of the one before it again)
+    static constexpr int BYTES = BUF * 4;
+    static constexpr int NP = (BYTES + 1023) / 1024;
+    static_assert(BYTES >= 1024 && BYTES % 16 == 0, "a staging buffer holds a whole DMA piece, in 16-byte units");
+    __host__ __device__ static constexpr int piece(int p) { return p * 1024 < BYTES - 1024 ? p * 1024 : BYTES - 1024; }
     // staged position of row b of neuron group go: go B + b, or interleaved b GO + go (GO = 4, 144-byte rows: the header)
     static constexpr bool INTERLEAVED = GO == 4 && B >= 4;
     static constexpr int BSTEP = INTERLEAVED ? GO : 1;   // rows between a group's consecutive neurons
     static constexpr int GSTEP = INTERLEAVED ? 1 : B;    // rows between the groups
 };
+static_assert(net_image_geom(1, 1, 8, 4).buf == NetGeom<8, 4>::BUF && net_image_geom(1, 1, 8, 2).buf == NetGeom<8, 2>::BUF &&
+                  net_image_geom(1, 1, 4, 4).buf == NetGeom<4, 4>::BUF && net_image_geom(1, 1, 2, 2).buf == NetGeom<2, 2>::BUF &&
+                  net_image_geom(1, 1, 4, 4).interleaved == NetGeom<4, 4>::INTERLEAVED && net_image_geom(1, 1, 2, 4).ck == NetGeom<2, 4>::CK,
+              "the host's staged-order image (kernels.h) and the kernel's staging buffers are one layout");
 template <int B, int GO = 2>
 struct NetChunk {
     float4 v[NetGeom<B, GO>::NF];
 };
-template <int GO>
-struct NetChunk<0, GO> {};
 __host__ __device__ constexpr uint32_t net_padk(uint32_t k, uint32_t ck) { return (k + ck - 1u) / ck * ck; }
 
-// the 16-byte pieces of a weight chunk (fetch unit) this lane fetches: rows obase .. obase + GO B - 1 (clamped to the last row: the
-// results of rows beyond dout are dropped), inputs k0 .. k0 + FK - 1, zero from the row's padded end (k16 <= wstride) on
+// Register staging (the slab kernel): the 16-byte pieces of a weight chunk this lane fetches: rows obase .. obase + GO B - 1 (clamped
+// to the last row: the results of rows beyond dout are dropped), inputs k0 .. k0 + CK - 1, zero from the row's padded end (k16 <= wstride) on
 template <int B, int GO = 2>
 __device__ __forceinline__ NetChunk<B, GO> net_fetch(const float* __restrict__ W, uint32_t wstride, uint32_t k16, uint32_t dout,
                                                      uint32_t obase, uint32_t k0, int lane) {
@@ -92,9 +107,9 @@ __device__ __forceinline__ NetChunk<B, GO> net_fetch(const float* __restrict__ W
 #pragma unroll
     for (int f = 0; f < G::NF; ++f) {
         const uint32_t e = (uint32_t)lane + 64u * f;
-        uint32_t o = obase + e / G::PF;
+        uint32_t o = obase + e / G::P;
         o = o < dout ? o : dout - 1u;
-        const uint32_t k = k0 + 4u * (e % G::PF);
+        const uint32_t k = k0 + 4u * (e % G::P);
         g.v[f] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (k < k16) g.v[f] = *reinterpret_cast<const float4*>(W + (size_t)o * wstride + k);
     }
@@ -107,8 +122,8 @@ __device__ __forceinline__ void net_stage(float* wb, const NetChunk<B, GO>& g, i
 #pragma unroll
     for (int f = 0; f < G::NF; ++f) {
         const uint32_t e = (uint32_t)lane + 64u * f;
-        const uint32_t p = e % G::PF;
-        uint32_t r = e / G::PF;
+        const uint32_t p = e % G::P;
+        uint32_t r = e / G::P;
         if constexpr (G::INTERLEAVED) r = (r % B) * GO + r / B;
         float* d = wb + r * G::LDW + (p >> 2) * 16u + ((p >> 1) & 1u) * 2u + (p & 1u);
         d[0] = g.v[f].x; d[4] = g.v[f].y; d[8] = g.v[f].z; d[12] = g.v[f].w;
@@ -170,12 +185,6 @@ __device__ __forceinline__ void net_row2(f2& c0, f2& c1, const float4& x, const 
         : "v"(f2{x.x, x.y}), "v"(f2{x.z, x.w}), "v"(f2{w0.x, w0.y}), "v"(f2{w0.z, w0.w}), "v"(f2{w1.x, w1.y}), "v"(f2{w1.z, w1.w}));
 }
 
-// One layer for the block's Q = GQ A rows (GQ = 16 / GO query groups: 8, or 4 in the half-CU form).  xs: input image (group stride sx, inputs padded with zeros to a multiple of the
-// layer's chunk); outs: the next layer's image (group stride so) when OIMG, else plain rows y[q][so].
-// The k loop is a software pipeline over double k-steps u (16 inputs): the NEXT step's weights are requested at the top of a
-// step, query a's 16 bytes of the next step right after query a's products of this step (into the same registers); the weight
-// chunks (CK inputs of the wavefront's GO B rows) run two ahead: chunk i + 2 is on its way from L2 while chunk i + 1 sits
-// staged in the wavefront's other LDS buffer (half-CU form, B >= 4: one double k-step of the rows at a time, NetGeom::BY_STEP).  Chunks and steps are numbered THROUGH the layer's passes.
 // Which 2 B-neuron slices of a layer a wavefront takes, in order: round robin.  (The vector pipe is arbitrated by age -- with two
 // slices each the four older wavefronts of a block are through a 256-neuron layer in 16 us, the younger in 25 -- but handing
 // the older ones three slices and the younger one made the older ones the slow ones: 25.2 / 17.4 us, 52.5 us per projection
@@ -189,27 +198,65 @@ __device__ __forceinline__ uint32_t net_slices(uint32_t wave, uint32_t total) { 
     return n;
 }
 
+// One 16-byte-per-lane LDS-DMA piece: 1 KiB from src + voff (per lane: 16 lane) to the LDS byte address dst (wave-uniform).  M0 holds
+// the destination and belongs to the compiler: saved, set and restored inside the one statement.  (s_nop 2: with the two moves, the
+// five wait states a freshly written scalar base wants before a vector memory instruction reads it; it covers the M0 write too.)
+// The piece counts on the wavefront's vector-memory counter; the compiler does not know of it: net_dma_wait before the buffer is read.
+__device__ __forceinline__ void net_dma_piece(const float* src, uint32_t voff, uint32_t dst) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 2\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(voff), "s"(dst), "s"(src)
+                 : "memory");
+}
+// every DMA piece this wavefront has issued has landed (N = 0 is the count: at most one chunk of a layer's stream is in flight at a
+// wait, and whatever else the counter holds is older); the wavefront's own LDS reads behind this see the bytes
+__device__ __forceinline__ void net_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
 template <int NW, int B, int GO>
 struct NetW;
 template <int NW, int GO>
-struct NetW<NW, 0, GO> {};
+struct NetW<NW, 0, GO> {
+    __device__ __forceinline__ void start(uint32_t, int, int) const {}
+};
 template <int NW, int B, int GO>
-struct NetW {            // one layer's weights as a wavefront's stream of chunks
-    const float* __restrict__ W;
-    uint32_t wstride, k16, dout, nch;
-    __device__ __forceinline__ NetW(const float* w, uint32_t ws, uint32_t din, uint32_t dout_)
-        : W(w), wstride(ws), k16(net_pad16(din)), dout(dout_), nch(net_padk(din, NetGeom<B, GO>::CK) / NetGeom<B, GO>::CK) {}
-    __device__ __forceinline__ NetChunk<B, GO> fetch(uint32_t i, int lane, int wave) const {  // fetch unit i of the stream
-        using G = NetGeom<B, GO>;
-        const uint32_t nun = nch * (G::CK / G::FK), ps = i / nun, c = i - ps * nun;
-        return net_fetch<B, GO>(W, wstride, k16, dout, net_slice<NW>((uint32_t)wave, ps) * (uint32_t)(GO * B), c * G::FK, lane);
+struct NetW {            // one layer's weights as a wavefront's stream of chunks of the staged-order image [slice][chunk][BUF]
+    using G = NetGeom<B, GO>;
+    const float* __restrict__ img;
+    uint32_t dout, nch;
+    __device__ __forceinline__ NetW(const float* im, uint32_t din, uint32_t dout_)
+        : img(im), dout(dout_), nch(net_padk(din, G::CK) / G::CK) {}
+    __device__ __forceinline__ uint32_t npass(int wave) const { return net_slices<NW>((uint32_t)wave, (dout + GO * B - 1) / (GO * B)); }
+    // chunk c of the wavefront's pass ps -> the staging buffer at LDS byte address dst
+    __device__ __forceinline__ void dma(uint32_t ps, uint32_t c, uint32_t dst, int lane, int wave) const {
+        const float* src = img + ((size_t)net_slice<NW>((uint32_t)wave, ps) * nch + c) * (size_t)G::BUF;
+#pragma unroll
+        for (int p = 0; p < G::NP; ++p) net_dma_piece(src + G::piece(p) / 4, 16u * (uint32_t)lane, dst + (uint32_t)G::piece(p));
+    }
+    // the stream's first two chunks set out, into the staging pair at wbl (a wavefront without a slice of the layer asks for nothing)
+    __device__ __forceinline__ void start(uint32_t wbl, int lane, int wave) const {
+        const uint32_t np = npass(wave);
+        if (np == 0) return;
+        dma(0, 0, wbl, lane, wave);
+        if (nch > 1) dma(0, 1, wbl + G::BYTES, lane, wave);
+        else if (np > 1) dma(1, 0, wbl + G::BYTES, lane, wave);
     }
 };
 
+// One layer for the block's Q = GQ A rows (GQ = 16 / GO query groups: 8, or 4 in the half-CU form).  xs: input image (group stride sx, inputs padded with zeros to a multiple of the
+// layer's chunk); outs: the next layer's image (group stride so) when OIMG, else plain rows y[q][so].
+// The k loop is a software pipeline over double k-steps u (16 inputs): the NEXT step's weights are read from LDS at the top of a
+// step, query a's 16 bytes of the next step right after query a's products of this step (into the same registers).  The weight
+// chunks (CK inputs of the wavefront's GO B rows, in staged order in memory) come by LDS-DMA into the wavefront's own pair of
+// staging buffers (wb; wbl its LDS byte address), one chunk ahead: chunk i + 2 sets out in the LAST step of chunk i, right behind
+// the products of that step's first query -- they have consumed the last weights read from chunk i's buffer, which chunk i + 2
+// takes --, and is waited for before the last step of chunk i + 1 reads its first weights: a chunk's arithmetic (two double
+// k-steps at B >= 4: 1 280 issue cycles and more) covers the trip.  The layer's first two chunks were sent by whoever ran before
+// (NetW::start: the kernel's prologue, the layer before under its last fold).  Chunks are numbered THROUGH the layer's passes.
+// Which 2 B-neuron slices of a layer a wavefront takes, in order: round robin (net_slice above).
 template <int NW, int A, int B, int NB, bool RELU, bool OIMG, int GO>
-__device__ __forceinline__ void net_layer(const float* xs, uint32_t sx, const NetW<NW, B, GO>& w, const float* __restrict__ bias, float* wb,
-                                          float* outs, uint32_t so, const NetChunk<B, GO>& g0, const NetChunk<B, GO>& g1,
-                                          const NetW<NW, NB, GO>& nw, NetChunk<NB, GO>& n0, NetChunk<NB, GO>& n1, int lane, int wave,
+__device__ __forceinline__ void net_layer(const float* xs, uint32_t sx, const NetW<NW, B, GO>& w, const float* __restrict__ bias, const float* wb,
+                                          uint32_t wbl, float* outs, uint32_t so, const NetW<NW, NB, GO>& nw, int lane, int wave,
                                           unsigned long long* st = nullptr) {
     using G = NetGeom<B, GO>;
     static_assert(B == 2 || B == 4 || B == 8, "neurons per lane group");
@@ -217,19 +264,14 @@ __device__ __forceinline__ void net_layer(const float* xs, uint32_t sx, const Ne
     constexpr uint32_t GQ = 16 / GO;  // query groups per row
     const uint32_t j = (uint32_t)lane >> 4, go = ((uint32_t)lane / GQ) % GO, gq = (uint32_t)lane % GQ;
     const uint32_t dout = w.dout, nch = w.nch;
-    const uint32_t npass = net_slices<NW>((uint32_t)wave, (dout + GO * B - 1) / (GO * B));  // this wavefront's slices of GO B neurons
+    const uint32_t npass = w.npass(wave);  // this wavefront's slices of GO B neurons
     const uint32_t total = nch * npass;
     if (npass == 0) {  // (a layer of fewer slices than wavefronts) nothing here but the next layer's first chunks
-        if constexpr (NB > 0) {
-            n0 = nw.fetch(0, lane, wave);
-            n1 = nw.fetch(1, lane, wave);
-        }
+        nw.start(wbl, lane, wave);
         return;
     }
     const float* xl = xs + gq * sx + 4 * j;
     const float* wl = wb + go * G::GSTEP * G::LDW + 4 * j;
-    net_stage<B, GO>(wb, g0, lane);
-    NetChunk<B, GO> g = g1;
     constexpr int NBV = B >= 4 ? B / 4 : 1;  // distinct neurons among a lane's outputs: b = (4 gi + j) mod B
     float bsv[NBV];
     auto load_bias = [&](uint32_t ps) {
@@ -246,26 +288,23 @@ __device__ __forceinline__ void net_layer(const float* xs, uint32_t sx, const Ne
     for (int a = 0; a < A; ++a)
 #pragma unroll
         for (int b = 0; b < B; ++b) acc[a][b] = f2{0.f, 0.f};
-    // operands of step 0
+    // operands of step 0 (the stream's first two chunks are in place behind this wait)
+    net_dma_wait();
     float4 xv[A], wv[2][B];
 #pragma unroll
     for (int b = 0; b < B; ++b) wv[0][b] = *reinterpret_cast<const float4*>(wl + b * G::BSTEP * G::LDW);
 #pragma unroll
     for (int a = 0; a < A; ++a) xv[a] = *reinterpret_cast<const float4*>(xl + a * 16);
     static_assert(G::NU % 2 == 0, "the weight registers alternate by step: a chunk must end on the set it began with");
-    uint32_t i = 0;  // chunk of the layer's stream
+    uint32_t i = 0;          // chunk of the layer's stream
+    uint32_t ps2 = 0, c2 = 2;  // pass and chunk in it of chunk i + 2
+    while (c2 >= nch) { c2 -= nch; ++ps2; }
     for (uint32_t ps = 0; ps < npass; ++ps) {
 #ifdef GBNNS_NET_STAMPS
         unsigned long long ts0 = __builtin_amdgcn_s_memrealtime();
 #endif
 #pragma clang loop unroll(disable)
         for (uint32_t c = 0; c < nch; ++c, ++i) {
-            // (a wavefront's LDS operations execute in order: its own staged rows are visible to its later reads, and the rows
-            //  of chunk i - 1 were last read before these stores; past the layer's last chunk the store and the fetch repeat it)
-            if constexpr (!G::BY_STEP) {
-                net_stage<B, GO>(wb + ((i + 1) & 1u) * G::BUF, g, lane);
-                g = w.fetch(i + 2 < total ? i + 2 : total - 1, lane, wave);
-            }
             const float* wcur = wl + (i & 1u) * G::BUF;
             const float* wnxt = wl + ((i + 1) & 1u) * G::BUF;
             const float* xc = xl + c * (G::NU * A * 16);
@@ -273,14 +312,9 @@ __device__ __forceinline__ void net_layer(const float* xs, uint32_t sx, const Ne
 #pragma unroll
             for (int u = 0; u < G::NU; ++u) {
                 const int cb = u & 1, nb = cb ^ 1;
-                if constexpr (G::BY_STEP) {
-                    // the next step's 16 inputs of the wavefront's rows go into place (they were requested a step ago: the rows of
-                    // this step are in registers since the last one), those of the step after next set out
-                    net_stage<B, GO>(u + 1 < G::NU ? wb + (i & 1u) * G::BUF + 16 * (u + 1) : wb + ((i + 1) & 1u) * G::BUF, g, lane);
-                    const uint32_t v2 = i * G::NU + u + 2, nv = total * G::NU;
-                    g = w.fetch(v2 < nv ? v2 : nv - 1, lane, wave);
-                }
-                // the next step's weights: this chunk's next 16 inputs, or the next chunk's first
+                // the next step's weights: this chunk's next 16 inputs, or the next chunk's first -- chunk i + 1 set out a chunk ago
+                // (past the layer's last chunk: whatever the other buffer holds, never used)
+                if (u + 1 == G::NU) net_dma_wait();
 #pragma unroll
                 for (int b = 0; b < B; ++b)
                     wv[nb][b] = u + 1 < G::NU ? *reinterpret_cast<const float4*>(wcur + b * G::BSTEP * G::LDW + 16 * (u + 1))
@@ -298,6 +332,12 @@ __device__ __forceinline__ void net_layer(const float* xs, uint32_t sx, const Ne
                     xv[a] = u + 1 < G::NU ? *reinterpret_cast<const float4*>(xc + ((u + 1) * A + a) * 16)
                                           : *reinterpret_cast<const float4*>(xn + a * 16);
                     __builtin_amdgcn_sched_barrier(0);
+                    if (u + 1 == G::NU && a == 0) {
+                        // chunk i's buffer is free: its last weights (this step's) were in registers before the products above ran
+                        if (i + 2 < total) w.dma(ps2, c2, wbl + (i & 1u) * (uint32_t)G::BYTES, lane, wave);
+                        if (++c2 == nch) { c2 = 0; ++ps2; }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
                 }
             }
         }
@@ -305,13 +345,9 @@ __device__ __forceinline__ void net_layer(const float* xs, uint32_t sx, const Ne
         unsigned long long ts1 = __builtin_amdgcn_s_memrealtime();
         if (st && lane == 0) st[0] += ts1 - ts0;
 #endif
-        // end of a pass.  The next layer's first two chunks set out now, under the fold and the barrier.
-        if constexpr (NB > 0) {
-            if (ps + 1 == npass) {
-                n0 = nw.fetch(0, lane, wave);
-                n1 = nw.fetch(1, lane, wave);
-            }
-        }
+        // end of a pass.  The next layer's first two chunks set out now, under the fold and the barrier: nothing of this layer's is
+        // in flight (its last chunk was waited for a chunk ago) and every weight this layer needs has been read.
+        if (ps + 1 == npass) nw.start(wbl, lane, wave);
         // fold (support_func.h:159-161): m = c_{j+4} + c_j in the lane, then the rows' reduce-scatter; row j owns output 4 gi + j
         const uint32_t obase = net_slice<NW>((uint32_t)wave, ps) * (uint32_t)(GO * B);
         constexpr int N = A * B, NG = (N + 3) / 4;
@@ -357,8 +393,7 @@ __device__ __forceinline__ void net_layer(const float* xs, uint32_t sx, const Ne
 struct NetParams {
     const float* x;          // [nq x xstride]
     uint32_t xstride, nq;
-    const float* w[3];       // [dout x wstride] each, rows zero padded to a multiple of 16 floats
-    uint32_t wstride[3];
+    const float* img[3];     // the layers' weights in staged order (kernels.h pack_net_image, this form's)
     const float* bias[3];
     uint32_t din[3], dout[3];
     float* out;              // [nq x ostride]; columns [dout[2], ostride) are written as zero
@@ -388,15 +423,19 @@ __global__ __launch_bounds__(NW * 64) void mlp_net_kernel(NetParams p) {
     float* bufa = nsm;                     // x, then h2
     float* bufb = bufa + p.bufa;           // h1, then y
     float* wb = bufb + p.bufb + (size_t)wave * (2 * GH::BUF);  // (the hidden layers' staging pair is the largest)
+    static_assert(2 * G3::BUF <= 2 * GH::BUF, "the last layer's staging pair fits the hidden layers'");
+    // its LDS byte address, for the DMA (wave-uniform: a scalar)
+    const uint32_t wbl = __builtin_amdgcn_readfirstlane(
+        (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float*)wb);
     const uint32_t qbase = blockIdx.x * Q;
     const uint32_t s0 = net_gstride(net_padk(p.din[0], GH::CK), A), s1 = net_gstride(net_padk(p.dout[0], GH::CK), A),
                    s2 = net_gstride(net_padk(p.dout[1], G3::CK), A);
     NET_STAMP(0);
 
-    const NetW<NW, BH, GO> w1(p.w[0], p.wstride[0], p.din[0], p.dout[0]), w2(p.w[1], p.wstride[1], p.din[1], p.dout[1]);
-    const NetW<NW, B3, GO> w3(p.w[2], p.wstride[2], p.din[2], p.dout[2]);
+    const NetW<NW, BH, GO> w1(p.img[0], p.din[0], p.dout[0]), w2(p.img[1], p.din[1], p.dout[1]);
+    const NetW<NW, B3, GO> w3(p.img[2], p.din[2], p.dout[2]);
     const NetW<NW, 0, GO> w_none;
-    NetChunk<BH, GO> ga = w1.fetch(0, lane, wave), gb = w1.fetch(1, lane, wave);  // (a net's first layer has two chunks: din > 32)
+    w1.start(wbl, lane, wave);  // layer 1's first two chunks set out under the strip's load
     // the block's queries: 16 floats per thread and turn, permuted on the way into LDS (zeros beyond din)
     {
         const uint32_t nb = net_padk(p.din[0], GH::CK) / 16u;
@@ -423,8 +462,7 @@ __global__ __launch_bounds__(NW * 64) void mlp_net_kernel(NetParams p) {
     }
     __syncthreads();
     NET_STAMP(1);
-    NetChunk<BH, GO> gc, gd;
-    net_layer<NW, A, BH, BH, true, true, GO>(bufa, s0, w1, p.bias[0], wb, bufb, s1, ga, gb, w2, gc, gd, lane, wave);
+    net_layer<NW, A, BH, BH, true, true, GO>(bufa, s0, w1, p.bias[0], wb, wbl, bufb, s1, w2, lane, wave);
     NET_STAMP(2);
     __syncthreads();
     NET_STAMP(3);
@@ -432,18 +470,16 @@ __global__ __launch_bounds__(NW * 64) void mlp_net_kernel(NetParams p) {
         const uint32_t h = p.dout[1], hp = net_padk(h, G3::CK) - h;
         for (uint32_t e = t; e < (uint32_t)Q * hp; e += NT) bufa[net_xpos<A, GQ>(e / hp, h + e % hp, s2)] = 0.f;
     }
-    NetChunk<B3, GO> ge, gf;
 #ifdef GBNNS_NET_STAMPS
-    net_layer<NW, A, BH, B3, true, true, GO>(bufb, s1, w2, p.bias[1], wb, bufa, s2, gc, gd, w3, ge, gf, lane, wave,
+    net_layer<NW, A, BH, B3, true, true, GO>(bufb, s1, w2, p.bias[1], wb, wbl, bufa, s2, w3, lane, wave,
                                          p.stamps ? p.stamps + 8 * 1024 + 2 * (blockIdx.x * NW + wave) : nullptr);
 #else
-    net_layer<NW, A, BH, B3, true, true, GO>(bufb, s1, w2, p.bias[1], wb, bufa, s2, gc, gd, w3, ge, gf, lane, wave);
+    net_layer<NW, A, BH, B3, true, true, GO>(bufb, s1, w2, p.bias[1], wb, wbl, bufa, s2, w3, lane, wave);
 #endif
     __syncthreads();
     NET_STAMP(4);
     const uint32_t ldy = p.dout[2] + 1u;
-    NetChunk<0, GO> gz;
-    net_layer<NW, A, B3, 0, false, false, GO>(bufa, s2, w3, p.bias[2], wb, bufb, ldy, ge, gf, w_none, gz, gz, lane, wave);
+    net_layer<NW, A, B3, 0, false, false, GO>(bufa, s2, w3, p.bias[2], wb, wbl, bufb, ldy, w_none, lane, wave);
     __syncthreads();
     NET_STAMP(5);
     // normalizeVector (support_func.h:636-642): 8 threads per query; threads 0..3 of a query run the four running sums of
@@ -736,6 +772,8 @@ hipError_t launch_mlp_net(const NetLaunch& n, hipStream_t s) {
     if (!mlp_net_serves(n)) return hipErrorInvalidValue;
     const bool half = n.form == kNetHalfCu;
     if (half && !mlp_net_half_serves(n)) return hipErrorInvalidValue;
+    for (int l = 0; l < 3; ++l)   // the weights come from the staged-order image of the form alone
+        if (!n.img[l] || (reinterpret_cast<uintptr_t>(n.img[l]) & 15u)) return hipErrorInvalidValue;
     // whole-CU form: 8 wavefronts x 8 neurons x 2 groups (blocks of 16 wavefronts x 8 neurons and of 4 x 16 were measured too: DESIGN.md 5.3)
     constexpr int bh = 8;
     const int nw = half ? 4 : 8;
@@ -761,7 +799,7 @@ hipError_t launch_mlp_net(const NetLaunch& n, hipStream_t s) {
     if (n.lds_floor > lds && n.lds_floor <= 160u * 1024u) lds = n.lds_floor;
     p.x = n.x; p.xstride = n.xstride; p.nq = n.nq; p.out = n.out; p.ostride = n.ostride; p.stamps = n.stamps;
     for (int l = 0; l < 3; ++l) {
-        p.w[l] = n.w[l]; p.wstride[l] = n.wstride[l]; p.bias[l] = n.bias[l]; p.din[l] = n.din[l]; p.dout[l] = n.dout[l];
+        p.img[l] = n.img[l]; p.bias[l] = n.bias[l]; p.din[l] = n.din[l]; p.dout[l] = n.dout[l];
     }
     // neurons per lane group in the last layer: a pass covers 16 B3 neurons (NW x 2 B3, NW x 4 B3 in the half-CU form)
     const uint32_t per = (n.dout[2] + 15u) / 16u;

@@ -23,7 +23,9 @@
  * flight with GBNNS_FLAG_DEFER_JOIN, at most four): per-batch buffers (n_q x (d_low + 2 d_hidden + ef + 6) x 4 bytes at
  * most) plus the exact fall-back walk's 64 slots of two n-bit sets and an ef-entry list: 16 n + 512 ef bytes
  * (16 MB at n = 10^6, 160 MB at 10^7).  The large-ef first pass (ef >= 385, deep batches) adds one n-bit set
- * per resident wavefront, capped at 8 GiB.
+ * per resident wavefront, capped at 8 GiB.  An index with a net also keeps, beside the net itself, the weights in the
+ * order the one-launch projection stages them, once per form of that kernel: about 2 x 1.13 x the net (SIFT net
+ * 128 -> 256 -> 256 -> 32: 0.43 MB + 0.95 MB), built when the index is created.
  *
  * Ids in DEVICE buffers are not validated on the host.  An entry id >= n is never dereferenced: that query
  * gets answer 0xFFFFFFFF, an all-0xFFFFFFFF candidate row and zero counters.  Candidate ids >= n passed to

@@ -248,6 +248,23 @@ int main(int argc, char** argv) {
     CK(hipGetDeviceProperties(&prop, 0));
     n.cus = prop.multiProcessorCount;
     for (int l = 0; l < 3; ++l) { n.w[l] = dw[l]; n.wstride[l] = ws[l]; n.bias[l] = db[l]; n.din[l] = din[l]; n.dout[l] = dout[l]; }
+    // the weights in the one-launch kernel's staged order (kernels.h pack_net_image), one image per form: what an index builds once
+    float* dimg[2][3];
+    size_t img_bytes[2] = {0, 0};
+    for (int form = 0; form < 2; ++form)
+        for (int l = 0; l < 3; ++l) {
+            const uint32_t b = l < 2 ? 8u : gbnns::net_image_b3(dl), go = gbnns::net_image_go(form);
+            std::vector<float> img(gbnns::net_image_floats(din[l], dout[l], b, go));
+            gbnns::pack_net_image(w[l].data(), ws[l], din[l], dout[l], b, go, img.data());
+            CK(hipMalloc(&dimg[form][l], img.size() * 4));
+            CK(hipMemcpy(dimg[form][l], img.data(), img.size() * 4, hipMemcpyHostToDevice));
+            img_bytes[form] += img.size() * 4;
+        }
+    auto set_form = [&](int form) {
+        n.form = form;
+        for (int l = 0; l < 3; ++l) n.img[l] = dimg[form][l];
+    };
+    set_form(gbnns::kNetWholeCu);
     printf("net %u x %u -> %u -> %u -> %u on %s (%d CUs); one-launch kernel serves it: %d\n", nq, d, dh, dh, dl, prop.name, n.cus,
            (int)gbnns::mlp_net_serves(n));
 
@@ -313,22 +330,28 @@ int main(int argc, char** argv) {
         CK(hipMemset(o_net, 0xEE, (size_t)nq * ostride * 4));
     };
     if (gbnns::mlp_net_serves(n)) {
+        printf("  whole-CU form: %zu bytes of LDS per block at 5 queries per lane, staged-order image %zu bytes (the net: %zu)\n",
+               gbnns::mlp_net_lds_bytes(n, gbnns::kNetWholeCu, 5), img_bytes[0], (w[0].size() + w[1].size() + w[2].size()) * 4);
         timeit("one launch (mlp_net.hip), whole-CU blocks", [&] { CK(gbnns::launch_mlp_net(n, s)); });
         compare("whole-CU blocks");
     }
     if (gbnns::mlp_net_half_serves(n)) {  // the half-CU form alone: two blocks per CU (its LDS allows it), and one (a request of 84 KB)
-        printf("  half-CU form: %zu bytes of LDS per block at 5 queries per lane\n", gbnns::mlp_net_lds_bytes(n, gbnns::kNetHalfCu, 5));
-        n.form = gbnns::kNetHalfCu;
+        printf("  half-CU form: %zu bytes of LDS per block at 5 queries per lane, staged-order image %zu bytes\n",
+               gbnns::mlp_net_lds_bytes(n, gbnns::kNetHalfCu, 5), img_bytes[1]);
+        set_form(gbnns::kNetHalfCu);
         timeit("one launch, half-CU blocks, two per CU", [&] { CK(gbnns::launch_mlp_net(n, s)); });
         compare("half-CU blocks, two per CU");
         n.lds_floor = 84u * 1024u;
         timeit("one launch, half-CU blocks, one per CU", [&] { CK(gbnns::launch_mlp_net(n, s)); });
         compare("half-CU blocks, one per CU");
         n.lds_floor = 0;
-        n.form = gbnns::kNetWholeCu;
+        set_form(gbnns::kNetWholeCu);
     }
     if (getenv("MLP_LAB_STAMPS") && gbnns::mlp_net_serves(n)) {   // needs a library built with EXTRA_DEFS=-DGBNNS_NET_STAMPS
         const int nb = 1024;
+        const bool half = !strcmp(getenv("MLP_LAB_STAMPS"), "half") && gbnns::mlp_net_half_serves(n);   // MLP_LAB_STAMPS=half: the half-CU form
+        set_form(half ? gbnns::kNetHalfCu : gbnns::kNetWholeCu);
+        printf("  stamps, %s form:\n", half ? "half-CU" : "whole-CU");
         unsigned long long* d_st;
         CK(hipMalloc(&d_st, nb * 40 * 8));
         CK(hipMemset(d_st, 0, nb * 40 * 8));
@@ -348,7 +371,7 @@ int main(int argc, char** argv) {
         printf("  phases of wave 0, mean over %d blocks (10 ns ticks):", cnt);
         for (int i = 1; i <= 6; ++i) printf(" %s %.2f us;", names[i], sum[i] / cnt / 100.0);
         printf(" first start -> last end %.2f us\n", (double)(t6max - t0min) / 100.0);
-        const int nwv = 8;
+        const int nwv = half ? 4 : 8;
         printf("  layer 2 by wavefront (k loops / folds + outputs, us, sums over the layer's passes):");
         for (int wv = 0; wv < nwv; ++wv) {
             double ml = 0, ep = 0;
@@ -357,6 +380,7 @@ int main(int argc, char** argv) {
         }
         printf("\n");
         n.stamps = nullptr;
+        set_form(gbnns::kNetWholeCu);
     }
     if (!getenv("MLP_LAB_NO_RATES")) {
         float* d_out;
