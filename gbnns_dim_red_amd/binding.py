@@ -24,6 +24,7 @@ FLAG_SERIAL = 64
 FLAG_DEFER_JOIN = 128
 FLAG_MFMA_PROJECTION = 256
 FLAG_HALF_ROWS = 512
+FLAG_TAG_BRIDGE = 1024   # gbnns_search_tagged only: disallowed neighbours are looked through (bridge_graph)
 
 # every symbol include/gbnns.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -36,7 +37,7 @@ SYMBOLS = [
     "gbnns_multi_search_device", "gbnns_multi_synchronize", "gbnns_multi_last_error",
     "gbnns_multi_rccl_single_rank", "gbnns_multi_rccl_version",
     "gbnns_round_to_half", "gbnns_index_enable_half_rows", "gbnns_index_low_rows",
-    "gbnns_index_set_tags", "gbnns_search_tagged", "gbnns_debug_tag_plan",
+    "gbnns_index_set_tags", "gbnns_search_tagged", "gbnns_debug_tag_plan", "gbnns_debug_bridge_plan",
 ]
 
 
@@ -166,6 +167,7 @@ def load_library():
     lib.gbnns_search_tagged.argtypes = [C.c_void_p, C.POINTER(_SearchArgs), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.gbnns_debug_tag_plan.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int,
                                          C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(C.c_uint64)]
+    lib.gbnns_debug_bridge_plan.argtypes = lib.gbnns_debug_tag_plan.argtypes
     lib.gbnns_index_d_low.argtypes = [C.c_void_p]
     lib.gbnns_index_d_low.restype = C.c_uint32
     _lib = lib
@@ -217,6 +219,36 @@ def cut_graph(off, nbr, allowed):
     return new_off, np.ascontiguousarray(nbr[keep])
 
 
+def bridge_graph(off, nbr, allowed):
+    """G'' of a bridged tagged search (FLAG_TAG_BRIDGE), by NumPy: row u of the CSR graph (off [n + 1], nbr) rebuilt from its slots in order --
+    an allowed neighbour v (allowed[v], a boolean mask over the n rows) stands for itself, a disallowed v is replaced by the allowed entries
+    of v's own row in their order (one level: a disallowed entry of v's row is dropped).  A plain concatenation: a row may hold u itself and
+    the same id more than once.  -> (offsets uint64, nbrs uint32).  A bridged tagged search of a query whose allowed rows are `allowed` is the
+    reference's search on this graph: allowed = (tags & q_tag) != 0."""
+    off = np.asarray(off, np.uint64)
+    nbr = np.asarray(nbr, np.uint32)
+    allowed = np.asarray(allowed, bool)
+    n = len(off) - 1
+    if allowed.shape != (n,):
+        raise ValueError("allowed must have one entry per row")
+    o = off.astype(np.int64)
+    cut_off, cut_nbr = cut_graph(off, nbr, allowed)
+    cut_o = cut_off.astype(np.int64)
+    cut_deg = np.diff(cut_o)
+    # what every slot contributes: itself, or the cut row of the neighbour it names
+    width = np.where(allowed[nbr], 1, cut_deg[nbr]) if len(nbr) else np.zeros(0, np.int64)
+    start = np.zeros(len(nbr) + 1, np.int64)
+    start[1:] = np.cumsum(width)
+    total = int(start[-1])
+    src = np.repeat(np.arange(len(nbr)), width)            # the slot every output entry comes from
+    k = np.arange(total) - start[src]                      # its index inside that slot's contribution
+    v = nbr[src]
+    from_cut = cut_nbr[np.minimum(cut_o[v] + k, max(len(cut_nbr) - 1, 0))] if len(cut_nbr) else np.zeros(total, np.uint32)
+    out = np.where(allowed[v], v, from_cut).astype(np.uint32)
+    new_off = start[o].astype(np.uint64)
+    return new_off, np.ascontiguousarray(out)
+
+
 def tag_plan(metric, dim, n, ell_stride, ef, aux_stride=0, n_entries=1, wide=False, rr_reserve=0):
     """gbnns_debug_tag_plan (no device needed): name of the first-pass kernel a tagged search of that shape gets."""
     name = C.create_string_buffer(128)
@@ -224,6 +256,16 @@ def tag_plan(metric, dim, n, ell_stride, ef, aux_stride=0, n_entries=1, wide=Fal
     _check(load_library().gbnns_debug_tag_plan(metric, dim, (dim + 3) // 4 * 4, n, ell_stride, aux_stride, ef, n_entries, int(wide), rr_reserve,
                                                name, 128, C.byref(lds)))
     return name.value.decode()
+
+
+def bridge_plan(metric, dim, n, ell_stride, ef, aux_stride=0, n_entries=1, wide=False, rr_reserve=0, with_lds=False):
+    """gbnns_debug_bridge_plan (no device needed): name of the first-pass kernel a tagged search with FLAG_TAG_BRIDGE of that shape gets;
+    with_lds: (name, LDS bytes of that instance per wavefront without the visited set)."""
+    name = C.create_string_buffer(128)
+    lds = C.c_uint64(0)
+    _check(load_library().gbnns_debug_bridge_plan(metric, dim, (dim + 3) // 4 * 4, n, ell_stride, aux_stride, ef, n_entries, int(wide), rr_reserve,
+                                                  name, 128, C.byref(lds)))
+    return (name.value.decode(), int(lds.value)) if with_lds else name.value.decode()
 
 
 def _ptr(x):
@@ -541,7 +583,8 @@ class Index:
         top_k > 0 (NET / LOWQ): gbnns_search_topk -- also "top_ids" / "top_dist" [nq x top_k], the top_k best of each query's ef
         candidates in ascending (original-space distance, pop index); top_ids[:, 0] == ids.
         query_tags [nq] (uint32 numpy / int32 torch, like entry_ids): gbnns_search_tagged -- query i walks only the rows j with
-        (tags[j] & query_tags[i]) != 0 (set_tags), i.e. the graph cut_graph gives; combines with top_k."""
+        (tags[j] & query_tags[i]) != 0 (set_tags), i.e. the graph cut_graph gives; combines with top_k.  With flags=FLAG_TAG_BRIDGE a disallowed neighbour is looked
+        through instead of dropped: the graph bridge_graph gives."""
         top_k = top_k or 0
         if aux:
             flags |= FLAG_AUX_GRAPH | (FLAG_LLF if llf else 0)

@@ -268,6 +268,7 @@ struct TopkOut {
 // gbnns_search_tagged's extra input: the queries' tag words [n_q], a buffer of args->mem_kind
 struct TagIn {
     const uint32_t* qtags;
+    bool bridge;  // GBNNS_FLAG_TAG_BRIDGE: disallowed neighbours are looked through
 };
 
 // lanes.cpp: the body of gbnns_search_ex / gbnns_search_topk / gbnns_search_tagged (topk == nullptr: no k-answer rows; tag == nullptr: untagged)

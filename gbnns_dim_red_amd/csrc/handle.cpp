@@ -740,22 +740,32 @@ int gbnns_debug_walk_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n
     return GBNNS_OK;
 }
 
-int gbnns_debug_tag_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries,
+static int debug_tag_plan(const char* fn, int bridged, int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries,
                          int force_wide, uint32_t rr_reserve, char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
-    if (!name || name_bytes == 0 || !lds_bytes) return fail(GBNNS_ERR_INVALID, "gbnns_debug_tag_plan: null output");
+    if (!name || name_bytes == 0 || !lds_bytes) return fail(GBNNS_ERR_INVALID, "%s: null output", fn);
     if ((metric != GBNNS_METRIC_L2 && metric != GBNNS_METRIC_NEG_DOT) || dim == 0 || dstride != round_up(dim, 4) || n == 0 || n > 0xFFFFFFFFull ||
         ell_stride == 0 || ell_stride % 16 || aux_stride % 16 || ef < 1 || n_entries > 4096)
-        return fail(GBNNS_ERR_INVALID, "gbnns_debug_tag_plan: not the shape of an index or a search");
+        return fail(GBNNS_ERR_INVALID, "%s: not the shape of an index or a search", fn);
     WalkParams w{};
     w.dim = dim; w.dstride = dstride; w.n = (uint32_t)n; w.ell_stride = ell_stride; w.ef = ef; w.n_entries = n_entries ? n_entries : 1u;
     w.aux_ell = aux_stride ? &w.aux_stride : nullptr; w.aux_stride = aux_stride;  // (the plan asks only WHETHER there is an auxiliary graph)
-    w.force_wide = force_wide != 0; w.rr_reserve = rr_reserve; w.tagged = 1;
+    w.force_wide = force_wide != 0; w.rr_reserve = rr_reserve; w.tagged = 1; w.bridged = bridged;
     const WalkPlan plan = plan_walk(w, metric, WalkPass::First);
     const char* planned = plan.general_only ? "walk_general_kernel" : walk_plan_name(plan);
-    if (!planned) return fail(GBNNS_ERR_INTERNAL, "gbnns_debug_tag_plan: no kernel instance for the plan");
+    if (!planned) return fail(GBNNS_ERR_INTERNAL, "%s: no kernel instance for the plan", fn);
     std::snprintf(name, name_bytes, "%s", planned);
     *lds_bytes = plan.lds_fixed;
     return GBNNS_OK;
+}
+
+int gbnns_debug_tag_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries,
+                         int force_wide, uint32_t rr_reserve, char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
+    return debug_tag_plan("gbnns_debug_tag_plan", 0, metric, dim, dstride, n, ell_stride, aux_stride, ef, n_entries, force_wide, rr_reserve, name, name_bytes, lds_bytes);
+}
+
+int gbnns_debug_bridge_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries,
+                            int force_wide, uint32_t rr_reserve, char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
+    return debug_tag_plan("gbnns_debug_bridge_plan", 1, metric, dim, dstride, n, ell_stride, aux_stride, ef, n_entries, force_wide, rr_reserve, name, name_bytes, lds_bytes);
 }
 
 // ---- gbnns_search_tagged: the rows' tag words -------------------------------------------------------------------------------------------

@@ -98,6 +98,9 @@ struct WalkParams {
     const uint32_t* qtags;   // [nq] tag word of every query
     int32_t tagged;          // 1: the first pass takes a tag instance (walk_tag.hip) or the general kernel the whole batch (walk_plan.cpp)
     int32_t generic_only;    // diagnostic (knob "hot" = 0): the generic instances also where the plan has a walk_hot* / walk_reg_wide instance
+    // GBNNS_FLAG_TAG_BRIDGE (last again; with `tagged`): a disallowed neighbour is looked through -- its place in the adjacency row is taken by
+    // the allowed entries of its own row, one level deep (walk_bridge.hip)
+    int32_t bridged;         // 1: the first pass takes a bridge instance (walk_bridge.hip) or the general kernel the whole batch (walk_plan.cpp)
 };
 
 // `form` of a visited set: 0 = 4-byte slots, 1 = five 24-bit ids per 16-byte bucket, 2 = quotient form (seven 16-bit entries)
@@ -110,7 +113,7 @@ hipError_t launch_walk(const WalkPlan& pl, const WalkParams& p, unsigned slots, 
 const char* walk_plan_name(const WalkPlan& pl);   // printable name of the plan's instance, template arguments included (no device needed); nullptr: none
 const char* walk_first_pass_name(hipStream_t s);  // (mangled) name of the first-pass kernel this thread launched last
 const char* walk_retry_pass_name(hipStream_t s);  // ... and of the retry-pass kernel
-hipError_t launch_walk_general(const WalkParams& p, int metric, hipStream_t s);  // (p.tagged: its instance with the tag test)
+hipError_t launch_walk_general(const WalkParams& p, int metric, hipStream_t s);  // (p.tagged: its instance with the tag test; p.bridged too: the one that looks through disallowed neighbours)
 // GBNNS_FLAG_HALF_ROWS (walk_half.hip): src [n x sstride] (dim coordinates a row) -> out_h [n x hstride] binary16 bits, round to nearest even,
 // columns from dim on zero; out_f [n x fstride] the same values widened back (fstride <= hstride).  *bad_row (preset to 0xFFFFFFFF) receives the
 // lowest row that holds a coordinate which is not finite or rounds out of the binary16 range.

@@ -89,6 +89,8 @@ int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk
         return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_LLF needs GBNNS_FLAG_AUX_GRAPH");
     if ((a->flags & GBNNS_FLAG_AUX_GRAPH) && !ix->has_aux)
         return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_AUX_GRAPH without gbnns_index_set_aux_graph");
+    if (!tag && (a->flags & GBNNS_FLAG_TAG_BRIDGE))
+        return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_TAG_BRIDGE has a meaning in gbnns_search_tagged only");
     if (tag) {
         if (a->flags & (GBNNS_FLAG_HALF_ROWS | GBNNS_FLAG_MFMA_PROJECTION))
             return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_search_tagged: GBNNS_FLAG_HALF_ROWS / GBNNS_FLAG_MFMA_PROJECTION are not served");
@@ -190,7 +192,7 @@ int gbnns_search_topk(gbnns_index* ix, const gbnns_search_args* a, int k, uint32
 }
 
 int gbnns_search_tagged(gbnns_index* ix, const gbnns_search_args* a, const uint32_t* query_tags, int k, uint32_t* out_top_ids, float* out_top_dist) {
-    const TagIn g{query_tags};
+    const TagIn g{query_tags, a && (a->flags & GBNNS_FLAG_TAG_BRIDGE) != 0};
     if (k == 0 && !out_top_ids && !out_top_dist) return search_call(ix, a, nullptr, &g);
     const TopkOut t{k, out_top_ids, out_top_dist};  // (k outside 1 .. ef, PLAIN mode, no out_top_ids: refused as for gbnns_search_topk)
     return search_call(ix, a, &t, &g);

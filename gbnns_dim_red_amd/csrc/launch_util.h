@@ -64,5 +64,7 @@ const WalkEntry* walk_bitmap_entry(const WalkInstance& k);
 const WalkEntry* walk_half_entry(const WalkInstance& k);
 // (a table of its own, asked last by walk_entry, walk_l2.hip: only an instance with `tag` set matches a row of it)
 const WalkEntry* walk_tag_entry(const WalkInstance& k);
+// (the same for `bridge`: walk_bridge.hip)
+const WalkEntry* walk_bridge_entry(const WalkInstance& k);
 
 }  // namespace gbnns

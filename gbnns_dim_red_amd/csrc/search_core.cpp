@@ -206,9 +206,10 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
     const bool aux = (a->flags & GBNNS_FLAG_AUX_GRAPH) != 0;
     if (tag) {  // gbnns_search_tagged: the walk of the graph cut to the rows each query may see (walk_tag.hip)
         w.tags = ix->tags.as<uint32_t>(); w.qtags = qtags_dev; w.tagged = 1;
+        w.bridged = tag->bridge ? 1 : 0;  // (walk_bridge.hip)
     }
-    // sizing statistics are kept per (ef, mode, aux, wide, half rows: another table, other walks; tagged: other graphs, shorter walks; knob "hot" = 0: other kernels)
-    const int skey = ((ef * 8 + a->mode * 2 + (aux ? 1 : 0)) * 2 + w.force_wide) | (w.half_rows ? 1 << 30 : 0) | (w.tagged ? 1 << 29 : 0) | (w.generic_only ? 1 << 28 : 0);
+    // sizing statistics are kept per (ef, mode, aux, wide, half rows: another table, other walks; tagged: other graphs, shorter walks; bridged: two to three times the rows claimed; knob "hot" = 0: other kernels)
+    const int skey = ((ef * 8 + a->mode * 2 + (aux ? 1 : 0)) * 2 + w.force_wide) | (w.half_rows ? 1 << 30 : 0) | (w.tagged ? 1 << 29 : 0) | (w.bridged ? 1 << 27 : 0) | (w.generic_only ? 1 << 28 : 0);
     const int calm = ix->calm_streak.count(skey) ? ix->calm_streak[skey] : 0;
     if (aux) {
         w.aux_ell = ix->aux_ell.as<uint32_t>(); w.aux_stride = ix->aux_stride;
@@ -400,8 +401,10 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
     if (prof) HIP_TRY(hipEventRecord(pc.ev[3], s));
     // statistics of this call (hand-over counts, largest walk), read back asynchronously: every call until
     // things are calm, every 16th afterwards (each read is a small copy on the stream)
+    // (a bridged call: every call -- the length of its walks follows the allowed fraction of the batch, and what a table sized for another
+    // fraction hands over runs on the general kernel: 10 000 queries at sift ef 64 took it 2 s)
     ix->stats_tick += 1;
-    if (auto_cap && !w.all_general && !L.stats_pending && (calm < 4 || (ix->stats_tick & 15u) == 0)) {
+    if (auto_cap && !w.all_general && !L.stats_pending && (calm < 4 || (ix->stats_tick & 15u) == 0 || w.bridged)) {
         if (!L.h_stats) {
             HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&L.h_stats), 16, hipHostMallocDefault));
             HIP_TRY(hipEventCreateWithFlags(&L.stats_ev, hipEventDisableTiming));

@@ -19,8 +19,12 @@ namespace {
 // (main and auxiliary alike; the row still ends at its first chunk without a live slot), and an entry row the query may not see is a bad
 // entry.  A kernel of its own (walk_general_tag_kernel): walk_general_kernel keeps its instructions (the shared body moved the operand order
 // of 18 commutative instructions and the registers they name, nothing else).
-template <int METRIC, bool TAG>
-__device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* smem) {
+// TAG == 2 (GBNNS_FLAG_TAG_BRIDGE, walk_general_bridge_kernel): a disallowed neighbour is looked through -- the allowed entries of its own row
+// (main graph through the main graph, auxiliary through the auxiliary) take its place, one level deep.  The ids of that row G'' are compacted
+// in order into `bst` (64 words of LDS) and run through the expansion a chunk at a time; of equal ids inside a chunk only the first stays
+// (two lanes that claim one id at once would both be told it is new, or the later one alone).
+template <int METRIC, int TAG>
+__device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* smem, uint32_t* bst = nullptr) {
     const int lane = lane_id();
     const uint32_t slot = blockIdx.x;
     float* qf = reinterpret_cast<float*>(smem);
@@ -48,11 +52,11 @@ __device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* s
         wave_sync();
 
         uint32_t qtag = 0u;
-        if constexpr (TAG) qtag = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.qtags[qi]);
+        if constexpr (TAG != 0) qtag = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.qtags[qi]);
         {
             bool bad = false;  // an entry id outside the index: empty result, no row is touched
             for (uint32_t e = 0; e < n_ent; ++e) bad |= (p.entries ? p.entries[(size_t)qi * n_ent + e] : 0u) >= p.n;
-            if constexpr (TAG) {  // ... or an entry row the query may not see
+            if constexpr (TAG != 0) {  // ... or an entry row the query may not see
                 for (uint32_t e = 0; e < n_ent && !bad; ++e) bad |= (p.tags[p.entries ? p.entries[(size_t)qi * n_ent + e] : 0u] & qtag) == 0u;
             }
             if (bad) {
@@ -98,7 +102,7 @@ __device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* s
                 bool valid = nb != kInvalidId;
                 uint64_t mv = __ballot(valid);
                 if (!mv) break;
-                if constexpr (TAG) {  // a disallowed neighbour is an empty slot from here on (a chunk of them is not the end of the row)
+                if constexpr (TAG == 1) {  // a disallowed neighbour is an empty slot from here on (a chunk of them is not the end of the row)
                     valid = valid && (p.tags[nb] & qtag) != 0u;
                     mv = __ballot(valid);
                     if (!mv) continue;
@@ -127,12 +131,98 @@ __device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* s
                 }
             }
         };
+        // TAG == 2: one chunk of a row of G'' -- every id allowed, in order; what make_step does with a chunk, behind the first-occurrence filter
+        auto offer_chunk = [&](uint32_t nb, bool valid, bool& found) {
+            uint64_t mv = __ballot(valid);
+            st.edges += __popcll(mv);  // (the degree in G'' counts repeated ids)
+            uint64_t dup = 0ull;
+            for (uint64_t rem = mv; rem;) {
+                const int j = __ffsll((unsigned long long)rem) - 1;
+                const uint64_t eq = __ballot(valid && nb == (uint32_t)__shfl((int)nb, j));
+                dup |= eq & ~(1ull << j);
+                rem &= ~eq;
+            }
+            valid = valid && !((dup >> lane) & 1ull);
+            bool fresh = false;
+            if (valid) {
+                const uint32_t bit = 1u << (nb & 31u);
+                fresh = !(atomicOr(&bitmap[nb >> 5], bit) & bit);
+            }
+            uint32_t dk = 0xFFFFFFFFu;
+            if (fresh)
+                dk = fkey(metric_dist<METRIC>(qs, reinterpret_cast<const float4*>(p.db + (size_t)nb * p.dstride), p.dim));
+            const uint64_t mf = __ballot(fresh);
+            st.dist_calc += __popcll(mf);
+            const uint32_t worst0 = key_hi(keys[st.size - 1]);
+            uint64_t m = __ballot(fresh && (st.size < ef || dk < worst0));
+            if (m) found = true;
+            while (m) {
+                const int l = __ffsll((unsigned long long)m) - 1;
+                m &= m - 1;
+                const uint32_t dl = (uint32_t)__shfl((int)dk, l);
+                const uint32_t il = (uint32_t)__shfl((int)nb, l);
+                offer(keys, tie, st, ef, dl, il, lane);
+            }
+        };
+        auto bridged_step = [&](const uint32_t* ell, uint32_t stride, bool& found) {
+            int cnt = 0;  // ids staged in bst
+            auto flush = [&]() {
+                wave_sync();
+                const uint32_t id = lane < cnt ? bst[lane] : kInvalidId;
+                offer_chunk(id, lane < cnt, found);
+                wave_sync();
+                cnt = 0;
+            };
+            auto emit = [&](uint32_t id, bool pred) {  // appends the ids of the lanes with `pred`, in lane order
+                const uint64_t m = __ballot(pred);
+                if (!m) return;
+                const int idx = cnt + __popcll(m & ((1ull << lane) - 1ull));
+                const int tot = cnt + __popcll(m);
+                if (pred && idx < 64) bst[idx] = id;
+                if (tot >= 64) {
+                    cnt = 64;
+                    flush();
+                    if (pred && idx >= 64) bst[idx - 64] = id;
+                    cnt = tot - 64;
+                } else cnt = tot;
+            };
+            const uint32_t* row = ell + (size_t)node * stride;
+            for (uint32_t c = 0; c < stride; c += 64) {
+                const uint32_t nb = (c + lane < stride) ? row[c + lane] : kInvalidId;
+                const bool live = nb != kInvalidId;
+                const uint64_t mlive = __ballot(live);
+                if (!mlive) break;  // (the end of a row: decided before the tag test, for u's row and for a looked-through one)
+                const bool allowed = live && (p.tags[nb] & qtag) != 0u;
+                uint64_t md = mlive & ~__ballot(allowed);
+                int pos = 0;  // slots below it are emitted
+                while (md) {
+                    const int d = __ffsll((unsigned long long)md) - 1;
+                    md &= md - 1;
+                    emit(nb, allowed && lane >= pos && lane < d);
+                    const uint32_t* vrow = ell + (size_t)(uint32_t)__shfl((int)nb, d) * stride;
+                    for (uint32_t c2 = 0; c2 < stride; c2 += 64) {
+                        const uint32_t nb2 = (c2 + lane < stride) ? vrow[c2 + lane] : kInvalidId;
+                        const bool live2 = nb2 != kInvalidId;
+                        if (!__ballot(live2)) break;
+                        emit(nb2, live2 && (p.tags[nb2] & qtag) != 0u);
+                    }
+                    pos = d + 1;
+                }
+                emit(nb, allowed && lane >= pos);
+            }
+            if (cnt) flush();
+        };
         while (select_candidate(keys, tie, st, node, lane)) {
             bool found = false;
+            if constexpr (TAG == 2) {
+                if (p.aux_ell && (uint32_t)st.hops < p.hops_bound) bridged_step(p.aux_ell, p.aux_stride, found);
+                if (!(found && p.llf)) bridged_step(p.ell, p.ell_stride, found);
+            } else {
             if (p.aux_ell && (uint32_t)st.hops < p.hops_bound)  // :73-80
                 make_step(p.aux_ell + (size_t)node * p.aux_stride, p.aux_stride, found);
             if (!(found && p.llf))                                // :82-89
                 make_step(p.ell + (size_t)node * p.ell_stride, p.ell_stride, found);
+            }
             st.hops += 1;
         }
         }  // entry points
@@ -149,13 +239,20 @@ __device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* s
 template <int METRIC>
 __global__ __launch_bounds__(64) void walk_general_kernel(WalkParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    walk_general_body<METRIC, false>(p, smem);
+    walk_general_body<METRIC, 0>(p, smem);
 }
 
 template <int METRIC>
 __global__ __launch_bounds__(64) void walk_general_tag_kernel(WalkParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    walk_general_body<METRIC, true>(p, smem);
+    walk_general_body<METRIC, 1>(p, smem);
+}
+
+template <int METRIC>
+__global__ __launch_bounds__(64) void walk_general_bridge_kernel(WalkParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ uint32_t bst[64];
+    walk_general_body<METRIC, 2>(p, smem, bst);
 }
 
 // Diagnostic kernel (tests only): runs one batch merge on a list / survivor set supplied by the host.
@@ -199,7 +296,18 @@ __global__ __launch_bounds__(64) void debug_merge_kernel(const uint64_t* entries
 hipError_t launch_walk_general(const WalkParams& p, int metric, hipStream_t s) {
     if (p.nq == 0) return hipSuccess;
     const size_t lds = std::max((size_t)p.dstride * 4, p.rr_db ? (size_t)p.rr_dstride * 4 : (size_t)0);
-    if (p.tagged) {
+    if (p.tagged && p.bridged) {
+        if (!p.tags || !p.qtags) return hipErrorInvalidValue;
+        if (metric == 1) {
+            hipError_t e = set_lds(walk_general_bridge_kernel<1>, lds);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL((walk_general_bridge_kernel<1>), dim3(kGeneralSlots), dim3(64), lds, s, p);
+        } else {
+            hipError_t e = set_lds(walk_general_bridge_kernel<0>, lds);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL((walk_general_bridge_kernel<0>), dim3(kGeneralSlots), dim3(64), lds, s, p);
+        }
+    } else if (p.tagged) {
         if (!p.tags || !p.qtags) return hipErrorInvalidValue;
         if (metric == 1) {
             hipError_t e = set_lds(walk_general_tag_kernel<1>, lds);

@@ -45,6 +45,12 @@ static bool tag_serves(int metric, int steps, int regs) {
     return metric == 0 && (steps == 12 || steps == 16 || (steps == 36 && regs == 4));
 }
 
+// The bridge instances (walk_bridge.hip): the tag instances' domain cut to the register lists (ef <= 128) over rows of 32 / 48 / 64 floats.  The
+// two-list shapes (beams above 128, 144-float rows) of a bridged call run whole on the general kernel.
+static bool bridge_serves(int metric, int steps, int regs) {
+    return regs <= 2 && (steps == 8 || (metric == 0 && (steps == 12 || steps == 16)));
+}
+
 WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv& env) {
     const bool off32 = compact_index(p), aux = p.aux_ell != nullptr, retry = pass == WalkPass::Retry;
     const int ef = p.ef, regs = ef <= 64 ? 1 : (ef <= kHot2MaxEf ? 2 : 4);
@@ -55,6 +61,7 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
     pl.pass = pass;
     // (gbnns_search_tagged: first pass only -- a tagged call has neither a retry nor a bitmap pass, search_core.cpp)
     const bool tag = p.tagged != 0 && pass == WalkPass::First;
+    const bool bridge = tag && p.bridged != 0;  // GBNNS_FLAG_TAG_BRIDGE: a table and instances of their own
     pl.general_only = p.n_entries > 1 || (tag && (aux || !off32));
     // The LDS-list kernel serves ef beyond the register lists, and auxiliary-graph walks over tables >= 4 GiB (the register-list /
     // two-list kernels have their auxiliary-graph hop in the 32-bit-offset instances only).
@@ -119,7 +126,7 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
             k.one = p.ell_stride <= ((steps == 8 || l2_unrolled) ? 32u : 64u);
             k.late = l2_unrolled && steps >= 24 && late;
             k.half = half && half_serves(metric, steps, 4, p.n_entries);
-            k.tag = tag && tag_serves(metric, steps, 4);
+            k.tag = tag && !bridge && tag_serves(metric, steps, 4);  // (no bridged two-list instance)
         }
         pl.general_only = pl.general_only || (tag && !k.tag);
         return pl;
@@ -134,14 +141,19 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
     }
     if (steps >= 24) steps = 0;  // (576-byte rows at ef <= 128: the run-time-length instances)
     k = {WalkFamily::RegList, metric, steps, regs, off32, retry, false, aux};
-    if (!aux && regs == 1 && off32 && !retry && p.ell_stride <= ((steps == 8 || (metric == 0 && steps >= 12)) ? 32u : 64u)) {
+    if (!aux && regs == 1 && off32 && !retry && !bridge && p.ell_stride <= ((steps == 8 || (metric == 0 && steps >= 12)) ? 32u : 64u)) {
         // ef <= 64, adjacency rows of one pass: a loop-free expansion; 192- / 256-byte rows with L2: the instance with the query in LDS
         // (half rows: the loop-free expansion of the list family itself -- the query-in-LDS instances have no half form)
         if (metric == 0 && steps >= 12 && !p.stamps_on && !half && !tag && !p.generic_only) k = {WalkFamily::RegWide, 0, steps, 0, false, false, false, false, late};
         else k.one = true;
     }
     k.half = half && !aux && off32 && half_serves(metric, steps, regs, p.n_entries);
-    k.tag = tag && !aux && off32 && p.n_entries <= 1u && tag_serves(metric, steps, regs);
+    k.tag = tag && !aux && off32 && p.n_entries <= 1u && tag_serves(metric, steps, regs) && (!bridge || bridge_serves(metric, steps, regs));
+    k.bridge = bridge && k.tag;
+    if (k.bridge) {  // the staged ids of a bridged row sit between the query and the visited set
+        pl.lds_fixed += (size_t)kBridgeStageIds * 4;
+        pl.rr_base = pl.lds_fixed;
+    }
     pl.general_only = pl.general_only || (tag && !k.tag);
     return pl;
 }

@@ -25,6 +25,7 @@ constexpr int kBigMaxEf = kRegListMaxEf;  // (the two-list structure itself reac
 #endif
 constexpr int kHot2MaxEf = GBNNS_HOT2_MAX;  // up to here the two-register lists (walk_hot_one<2>, walk_reg_one<2>) are the faster ones
 constexpr int kPlain512PairMinEf = 200;  // 512-byte rows (PLAIN walks over sift vectors): beams beyond this take the pair-form two-list instance
+constexpr int kBridgeStageIds = 64;  // walk_bridge.hip: ids of a bridged adjacency row staged in LDS between two runs of the hop step (two 32-slot chunks)
 constexpr size_t kCoopExtraLds = 1280;  // the two-wavefront walk's two 64-word result buffers + three 64-word slots of adjacency words requested ahead (its mailbox lives in the query area)
 
 // LDS of a two-list instance besides the visited set: [tie list][front-merge buffer: 66 keys][base list: ef_pad keys]
@@ -50,6 +51,7 @@ enum class WalkFamily : uint8_t {
     TwoList,    // walk_reg_big_kernel<METRIC, STEPS, OFF32, RETRY, AUX, ONE_PASS, LATE> (walk_l2 / walk_dot / walk_wide / walk_wide2)
                 // half: walk_reg_big_half_kernel<METRIC, STEPS, ONE_PASS, LATE>    (walk_half.hip)
                 // tag (either family): walk_reg_tag_kernel<METRIC, STEPS, R, ONE_CHUNK> / walk_reg_big_tag_kernel<METRIC, STEPS, ONE_PASS, LATE> (walk_tag.hip)
+                // bridge (register lists): walk_bridge_kernel<METRIC, STEPS, R>                (walk_bridge.hip)
     LdsList,    // walk_fast_kernel<METRIC, STEPS, RETRY, PACKED>                    (walk_l2 / walk_dot / walk_wide)
     BitmapReg,  // walk_bitmap_reg_kernel<METRIC, R>                                 (walk_bitmap.hip)
     BitmapBig,  // walk_bitmap_big_kernel<METRIC, STEPS, ONE_PASS, LATE>
@@ -70,10 +72,11 @@ struct WalkInstance {
     bool packed;  // LDS-list family: visited set of 24-bit ids
     bool half;    // the hop's rows come from the 2-byte table (WalkParams::db_h): walk_reg_half_kernel / walk_reg_big_half_kernel (walk_half.hip)
     bool tag;     // the hop tests every neighbour's tag word against the query's (WalkParams::tags / qtags): walk_reg_tag_kernel / walk_reg_big_tag_kernel (walk_tag.hip)
+    bool bridge;  // (with tag) a disallowed neighbour is looked through, its allowed neighbours staged in LDS in its place: walk_bridge_kernel (walk_bridge.hip)
 };
 inline bool operator==(const WalkInstance& a, const WalkInstance& b) {
     return a.family == b.family && a.metric == b.metric && a.steps == b.steps && a.regs == b.regs && a.off32 == b.off32 && a.retry == b.retry && a.one == b.one &&
-           a.aux == b.aux && a.late == b.late && a.spec == b.spec && a.packed == b.packed && a.half == b.half && a.tag == b.tag;
+           a.aux == b.aux && a.late == b.late && a.spec == b.spec && a.packed == b.packed && a.half == b.half && a.tag == b.tag && a.bridge == b.bridge;
 }
 
 struct WalkPlan {
@@ -85,7 +88,7 @@ struct WalkPlan {
     bool knows_quotient;   // the instance reads WalkParams::vs_shr
     bool lds_list;         // result list in LDS as one sorted array: no fused re-rank
     bool coop_serves;      // the two-wavefront walk has an instance for this shape (whether or not this plan is it)
-    bool general_only;     // several entry points per query, or a tagged call outside the tag instances' domain: the general kernel takes the whole batch
+    bool general_only;     // several entry points per query, or a tagged / bridged call outside its instances' domain: the general kernel takes the whole batch
     size_t rr_base;        // room of the fused re-rank's query = rr_base (+ the visited set's bytes when rr_in_table)
     bool rr_in_table;      // (rr_room below)
     // form of the visited set (walk_hash_bytes, kernels.h); vs_shr is set only where the instance knows the quotient form
@@ -97,7 +100,7 @@ struct WalkPlan {
 // GBNNS_STAMPS_GENERIC keeps diagnostic (GBNNS_STAMPS) builds off the hot two-list instances.
 struct WalkEnv { bool wide2, stamps_generic; };
 const WalkEnv& walk_env();
-// Reads the shape (dim, dstride, n, ell_stride, aux_ell / aux_stride), ef, n_entries, force_wide, coop, late_rows, spec_rows, stamps_on, half_rows, tagged, generic_only
+// Reads the shape (dim, dstride, n, ell_stride, aux_ell / aux_stride), ef, n_entries, force_wide, coop, late_rows, spec_rows, stamps_on, half_rows, tagged, bridged, generic_only
 // and rr_reserve -- nothing the sizing rule writes (hash_cap, hash_limit, vs_shr), so the layout is known before the visited set is sized.
 WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv& env = walk_env());
 

@@ -345,6 +345,33 @@ int gbnns_index_set_tags(gbnns_index* index, const uint32_t* tags, uint64_t firs
 int gbnns_search_tagged(gbnns_index* index, const gbnns_search_args* args, const uint32_t* query_tags, int k, uint32_t* out_top_ids,
                         float* out_top_dist);
 
+/* Bridged tagged search (a flag of gbnns_search_tagged, with and without k): the walk looks THROUGH a disallowed neighbour instead of
+ * dropping it -- one-level two-hop expansion, the ACORN-1 rule -- so that a filter which allows few rows no longer strands the walk (DESIGN.md
+ * 5.1, "Bridged tagged search", has the measured recall and cost).  Tags, query words and the allowed test are gbnns_search_tagged's.  The
+ * definition: a bridged tagged search of query i is the reference's search of query i on the graph G''(i), whose row of node u is built from
+ * the slots of u's row in the index's graph, in order:
+ *   - an allowed neighbour v contributes v;
+ *   - a disallowed neighbour v contributes, in v's place, the allowed entries of v's own row, in their order;
+ *   - one level only: a disallowed entry of v's row is dropped, not looked through;
+ *   - the row is a plain concatenation: it may hold u itself and the same id more than once -- the reference's visited test disposes of both
+ *     (of equal ids the first occurrence is the one claimed, measured and offered);
+ *   - the auxiliary graph, where used, is bridged through itself.
+ * Nothing else changes: ids, pop order, distance bits, hops, dist_calc, out_q_low and the top-k rows are the CPU oracle's on G''
+ * (gbnns_dim_red_amd.bridge_graph builds it with NumPy), bit for bit.  Looking through v is not a hop; a disallowed row is never claimed in
+ * the visited set, never has a distance computed and is never counted in dist_calc; out_edges is the degree in G'' of the expanded nodes,
+ * repeated ids included.  The entry row enters untested and must be allowed: a bad or disallowed entry gives the bad-entry row of a tagged
+ * call, so every expanded node is allowed.  With every row allowed G'' is the index's graph and every output equals the untagged search's,
+ * counters and edges included.
+ * The flag combines with everything a tagged call combines with (hash_capacity, several entry points, GBNNS_FLAG_AUX_GRAPH / GBNNS_FLAG_LLF,
+ * GBNNS_FLAG_WIDE_INDEX, GBNNS_FLAG_SERIAL, GBNNS_FLAG_NO_FUSED_RERANK, GBNNS_FLAG_DEFER_JOIN, HOST and DEVICE buffers, NET / LOWQ / PLAIN);
+ * GBNNS_FLAG_HALF_ROWS and GBNNS_FLAG_MFMA_PROJECTION stay GBNNS_ERR_UNSUPPORTED.  In gbnns_search_ex, gbnns_search_topk and the
+ * gbnns_multi_* searches the flag is GBNNS_ERR_INVALID.
+ * The first pass is a bridge instance (walk_bridge_kernel in gbnns_profile.walk_kernel) for a compact index with one entry point per query and
+ * no auxiliary graph, over rows of 32 / 48 / 64 floats with L2 and 32 floats with the negative dot at beams up to 128; what it hands over,
+ * and every other case (beams above 128 and 144-float rows included), runs on the general kernel's bridged instance ("walk_general_kernel"
+ * in the profile and in gbnns_debug_bridge_plan): same results. */
+#define GBNNS_FLAG_TAG_BRIDGE 1024u
+
 /* Per-kernel device timing (hipEvent pairs on the launch stream), accumulated since the last
  * reset.  Reading synchronises the recorded events. */
 typedef struct {
@@ -429,6 +456,9 @@ int gbnns_debug_walk_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n
  * batch runs on the general kernel), rows requested before the visited test where an instance has both orders.  Inputs as for gbnns_debug_walk_plan. */
 int gbnns_debug_tag_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef,
                          uint32_t n_entries, int force_wide, uint32_t rr_reserve, char* name, uint32_t name_bytes, uint64_t* lds_bytes);
+/* The same for a gbnns_search_tagged call with GBNNS_FLAG_TAG_BRIDGE; *lds_bytes: that instance's LDS bytes per wavefront without the visited set. */
+int gbnns_debug_bridge_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef,
+                            uint32_t n_entries, int force_wide, uint32_t rr_reserve, char* name, uint32_t name_bytes, uint64_t* lds_bytes);
 /* Diagnostic, no device needed: LDS bytes of a workgroup of the one-launch projection for a net d -> d_hidden -> d_hidden -> d_low, in
  * the whole-CU form (form 0) or the half-CU form (form 1), with a queries per lane (2 .. 5), and whether that form takes the net at all
  * (*admitted: a workgroup with a = 4 fits 160 KB / 80 KB). */

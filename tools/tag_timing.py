@@ -10,6 +10,8 @@ queries all carry Q = 1 / 2 / 4 / 8 may see all, 1/2, 1/8 and 1/64 of the rows. 
 it may not see is the empty row by definition -- include/gbnns.h).  Per (workload, beam, fraction):
 
   tagged     walk_ms of gbnns_search_tagged (the tag instance of the generic kernel family)
+  bridged    walk_ms of gbnns_search_tagged with GBNNS_FLAG_TAG_BRIDGE (walk_bridge_kernel: disallowed neighbours are looked through), with the
+             queries per call its first pass handed to the general kernel, its hops and dist_calc per query and its recall@1
   generic    walk_ms of the untagged search from the same entries on the same family, untagged (knob "hot" = 0): at fraction 1 the two walk the
              same graph and the ratio is the cost of the tag gather per hop
   default    walk_ms of the untagged search as every caller gets it (walk_hot_kernel on sift, walk_reg_wide_kernel on deep)
@@ -45,9 +47,9 @@ FRACTIONS = (("1", 1), ("1/2", 2), ("1/8", 4), ("1/64", 8))   # (name, Q)
 
 def measure(ix, q, ef, ent, qt):
     """{variant: (walk_ms per call of each round, kernel name)} for the tagged call, the untagged generic family and the default, interleaved."""
-    variants = (("tagged", dict(query_tags=qt), 1), ("generic", {}, 0), ("default", {}, 1))
+    variants = (("tagged", dict(query_tags=qt), 1), ("bridged", dict(query_tags=qt, flags=g.FLAG_TAG_BRIDGE), 1), ("generic", {}, 0), ("default", {}, 1))
     rounds = {name: [] for name, _, _ in variants}
-    kernel = {}
+    kernel, handed = {}, {}
     for rnd in range(-1, REPEATS):   # (round -1: the warm-up)
         for name, kw, hot in variants:
             ix.knob("hot", hot)
@@ -61,8 +63,9 @@ def measure(ix, q, ef, ent, qt):
             if rnd >= 0:
                 rounds[name].append((p["walk_ms"] + p["walk_general_ms"]) / p["calls"])
                 kernel[name] = p["walk_kernel"].split(" (")[0]
+                handed[name] = p["general_queries"] / p["calls"]
     ix.knob("hot", 1)
-    return rounds, kernel
+    return rounds, kernel, handed
 
 
 def main():
@@ -75,7 +78,7 @@ def main():
     os.makedirs(args.cache_dir, exist_ok=True)
     only = {s for s in args.only.split(",") if s}
     lines = ["walk_ms per call (first pass + general kernel): median of %d rounds of %d calls [lowest .. highest]; tagged = gbnns_search_tagged, "
-             "generic = untagged on the same kernel family (knob hot = 0), default = untagged" % (REPEATS, CALLS)]
+             "bridged = the same with GBNNS_FLAG_TAG_BRIDGE, generic = untagged on the same kernel family (knob hot = 0), default = untagged" % (REPEATS, CALLS)]
     records = []
     for name, kw, efs in WORKLOADS:
         if only and name not in only:
@@ -103,12 +106,16 @@ def main():
             torch.cuda.synchronize()
             del sub
             for ef in efs:
-                rounds, kernel = measure(ix, q, ef, ent, qt)
+                rounds, kernel, handed = measure(ix, q, ef, ent, qt)
                 res = ix.search(q, ef, entry_ids=ent, query_tags=qt, want=("hops", "dist_calc"))
+                br = ix.search(q, ef, entry_ids=ent, query_tags=qt, flags=g.FLAG_TAG_BRIDGE, want=("hops", "dist_calc"))
                 plain = ix.search(q, ef, entry_ids=ent, want=("hops", "dist_calc"))
                 torch.cuda.synchronize()
                 ids = res["ids"].to(torch.int64)
                 recall = (ids == truth).float().mean().item()
+                b_recall = (br["ids"].to(torch.int64) == truth).float().mean().item()
+                b_hops = br["hops"].to(torch.float64).mean().item()
+                b_dc = br["dist_calc"].to(torch.float64).mean().item()
                 found = (res["ids"] != -1).float().mean().item()
                 hops = res["hops"].to(torch.float64).mean().item()
                 dc = res["dist_calc"].to(torch.float64).mean().item()
@@ -117,14 +124,20 @@ def main():
                        "hops": round(hops, 2), "dist_calc": round(dc, 1), "recall_at_1_allowed": round(recall, 4), "answered": round(found, 4),
                        "untagged_hops": round(plain["hops"].to(torch.float64).mean().item(), 2),
                        "untagged_dist_calc": round(plain["dist_calc"].to(torch.float64).mean().item(), 1),
-                       "tagged_over_generic": round(med["tagged"] / med["generic"], 3), "tagged_over_default": round(med["tagged"] / med["default"], 3)}
+                       "tagged_over_generic": round(med["tagged"] / med["generic"], 3), "tagged_over_default": round(med["tagged"] / med["default"], 3),
+                       "bridged_hops": round(b_hops, 2), "bridged_dist_calc": round(b_dc, 1), "bridged_recall_at_1_allowed": round(b_recall, 4),
+                       "bridged_handed_over": round(handed["bridged"], 1), "bridged_over_tagged": round(med["bridged"] / med["tagged"], 3),
+                       "bridged_over_default": round(med["bridged"] / med["default"], 3)}
                 lines.append("%s  n %d  %d queries  %d -> %d  ef %d  allowed %s (%d rows)" % (name, n, nq, kw["d"], kw["d_low"], ef, fname, len(rows)))
-                for v in ("tagged", "generic", "default"):
+                for v in ("tagged", "bridged", "generic", "default"):
                     rec[v] = {"walk_ms": round(med[v], 5), "lowest": round(min(rounds[v]), 5), "highest": round(max(rounds[v]), 5), "kernel": kernel[v]}
                     lines.append("  %-8s %.4f [%.4f .. %.4f] ms  %s" % (v, med[v], min(rounds[v]), max(rounds[v]), kernel[v]))
                 lines.append("  tagged / generic %.3f  tagged / default %.3f   per query: hops %.1f (untagged %.1f)  dist_calc %.0f (untagged %.0f)   "
                              "recall@1 over the allowed rows %.4f" % (rec["tagged_over_generic"], rec["tagged_over_default"], hops, rec["untagged_hops"], dc,
                                                                       rec["untagged_dist_calc"], recall))
+                lines.append("  bridged / tagged %.3f  bridged / default %.3f   per query: hops %.1f  dist_calc %.0f   handed over per call %.1f   "
+                             "recall@1 over the allowed rows %.4f (tagged %.4f)" % (rec["bridged_over_tagged"], rec["bridged_over_default"], b_hops, b_dc,
+                                                                                   handed["bridged"], b_recall, recall))
                 records.append(rec)
         ix.close()
         del ds, ix, q
