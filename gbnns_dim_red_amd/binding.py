@@ -25,6 +25,7 @@ FLAG_DEFER_JOIN = 128
 FLAG_MFMA_PROJECTION = 256
 FLAG_HALF_ROWS = 512
 FLAG_TAG_BRIDGE = 1024   # gbnns_search_tagged only: disallowed neighbours are looked through (bridge_graph)
+FLAG_BYTE_WALK = 2048    # MODE_PLAIN on a byte handle (Index(db=<uint8>)): walk the uint8 rows; the float handle's answers over db.astype(float32), bit for bit
 
 # every symbol include/gbnns.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -38,7 +39,7 @@ SYMBOLS = [
     "gbnns_multi_rccl_single_rank", "gbnns_multi_rccl_version",
     "gbnns_round_to_half", "gbnns_index_enable_half_rows", "gbnns_index_low_rows",
     "gbnns_index_set_tags", "gbnns_search_tagged", "gbnns_debug_tag_plan", "gbnns_debug_bridge_plan",
-    "gbnns_index_create_bytes", "gbnns_index_is_bytes", "gbnns_debug_byte_plan",
+    "gbnns_index_create_bytes", "gbnns_index_is_bytes", "gbnns_debug_byte_plan", "gbnns_debug_byte_walk_plan",
 ]
 
 
@@ -171,6 +172,8 @@ def load_library():
     lib.gbnns_debug_bridge_plan.argtypes = lib.gbnns_debug_tag_plan.argtypes
     lib.gbnns_index_create_bytes.argtypes = [C.POINTER(_IndexDesc), C.c_void_p, C.POINTER(C.c_void_p)]
     lib.gbnns_index_is_bytes.argtypes = [C.c_void_p]
+    lib.gbnns_debug_byte_walk_plan.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int,
+                                              C.c_char_p, C.c_uint32, C.POINTER(C.c_uint64)]
     lib.gbnns_debug_byte_plan.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int,
                                           C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(C.c_int)]
     lib.gbnns_index_d_low.argtypes = [C.c_void_p]
@@ -271,6 +274,16 @@ def bridge_plan(metric, dim, n, ell_stride, ef, aux_stride=0, n_entries=1, wide=
     _check(load_library().gbnns_debug_bridge_plan(metric, dim, (dim + 3) // 4 * 4, n, ell_stride, aux_stride, ef, n_entries, int(wide), rr_reserve,
                                                   name, 128, C.byref(lds)))
     return (name.value.decode(), int(lds.value)) if with_lds else name.value.decode()
+
+
+def byte_walk_plan(metric, dim, n, ell_stride, ef, aux_stride=0, n_entries=1, wide=False, tagged=False):
+    """gbnns_debug_byte_walk_plan (no device needed): name of the first-pass kernel a MODE_PLAIN search with FLAG_BYTE_WALK of that shape gets
+    on a byte handle (dim: the original dimension); "walk_general_kernel": the general kernel's byte-walk instance takes the whole batch."""
+    name = C.create_string_buffer(128)
+    lds = C.c_uint64(0)
+    _check(load_library().gbnns_debug_byte_walk_plan(metric, dim, n, ell_stride, aux_stride, ef, n_entries, int(wide), int(tagged), name, 128,
+                                                     C.byref(lds)))
+    return name.value.decode()
 
 
 def byte_plan(metric, dim, n, ell_stride, ef, aux_stride=0, n_entries=1, wide=False, coop=False, late_rows=False, spec_rows=False, pass_no=0,

@@ -828,6 +828,24 @@ int gbnns_debug_byte_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n
     return GBNNS_OK;
 }
 
+int gbnns_debug_byte_walk_plan(int metric, uint32_t dim, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries, int force_wide,
+                               int tagged, char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
+    if (!name || name_bytes == 0 || !lds_bytes) return fail(GBNNS_ERR_INVALID, "gbnns_debug_byte_walk_plan: null output");
+    if ((metric != GBNNS_METRIC_L2 && metric != GBNNS_METRIC_NEG_DOT) || dim == 0 || n == 0 || n > 0xFFFFFFFFull || ell_stride == 0 || ell_stride % 16 ||
+        aux_stride % 16 || ef < 1 || n_entries > 4096)
+        return fail(GBNNS_ERR_INVALID, "gbnns_debug_byte_walk_plan: not the shape of an index or a search");
+    WalkParams w{};
+    w.dim = dim; w.dstride = round_up(dim, 16); w.n = (uint32_t)n; w.ell_stride = ell_stride; w.ef = ef; w.n_entries = n_entries ? n_entries : 1u;
+    w.aux_ell = aux_stride ? &w.aux_stride : nullptr; w.aux_stride = aux_stride;  // (the plan asks only WHETHER there is an auxiliary graph)
+    w.force_wide = force_wide != 0; w.tagged = tagged != 0; w.walk_bytes = 1;   // (what search_core.cpp sets for a flagged PLAIN call)
+    const WalkPlan plan = plan_walk(w, metric, WalkPass::First);
+    const char* planned = plan.general_only ? "walk_general_kernel" : walk_plan_name(plan);
+    if (!planned) return fail(GBNNS_ERR_INTERNAL, "gbnns_debug_byte_walk_plan: no kernel instance for the plan");
+    std::snprintf(name, name_bytes, "%s", planned);
+    *lds_bytes = plan.general_only ? (uint64_t)w.dstride * 4u : plan.lds_fixed;  // (the general kernel: the staged query alone)
+    return GBNNS_OK;
+}
+
 static int debug_tag_plan(const char* fn, int bridged, int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries,
                          int force_wide, uint32_t rr_reserve, char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
     if (!name || name_bytes == 0 || !lds_bytes) return fail(GBNNS_ERR_INVALID, "%s: null output", fn);

@@ -106,6 +106,11 @@ struct WalkParams {
     // padded) and the floats of the staged query, rr_dim % 16 == 0, rr_metric L2.  No other kernel looks at it.
     const uint8_t* rr_db_b;  // [n x rr_dstride] original-space byte rows, 16-byte aligned, or nullptr
     uint32_t bytes_dim;      // a byte handle's call that wants its re-rank fused: d of the uint8 rows (walk_plan.cpp: a byte instance where there is one); 0: not asked for
+    // GBNNS_FLAG_BYTE_WALK (last again): a PLAIN walk over a byte handle's table -- the walked rows are uint8, `db` above is nullptr, `dstride`
+    // is the BYTES of a row (round_up(dim, 16), zero padded) and the floats of the staged query.  The distances are the float walk's on
+    // float32(db_b), operation for operation; no float copy of the table exists.
+    const uint8_t* db_b;     // [n x dstride] walked byte rows, 16-byte aligned, or nullptr
+    int32_t walk_bytes;      // 1: the first pass takes a byte-walk instance (walk_bytes.hip) or the general kernel's the whole batch (walk_plan.cpp)
 };
 
 // `form` of a visited set: 0 = 4-byte slots, 1 = five 24-bit ids per 16-byte bucket, 2 = quotient form (seven 16-bit entries)
@@ -118,7 +123,7 @@ hipError_t launch_walk(const WalkPlan& pl, const WalkParams& p, unsigned slots, 
 const char* walk_plan_name(const WalkPlan& pl);   // printable name of the plan's instance, template arguments included (no device needed); nullptr: none
 const char* walk_first_pass_name(hipStream_t s);  // (mangled) name of the first-pass kernel this thread launched last
 const char* walk_retry_pass_name(hipStream_t s);  // ... and of the retry-pass kernel
-hipError_t launch_walk_general(const WalkParams& p, int metric, hipStream_t s);  // (p.tagged: its instance with the tag test; p.bridged too: the one that looks through disallowed neighbours)
+hipError_t launch_walk_general(const WalkParams& p, int metric, hipStream_t s);  // (p.tagged: its instance with the tag test; p.bridged too: the one that looks through disallowed neighbours; p.walk_bytes: their byte-walk twins)
 // GBNNS_FLAG_HALF_ROWS (walk_half.hip): src [n x sstride] (dim coordinates a row) -> out_h [n x hstride] binary16 bits, round to nearest even,
 // columns from dim on zero; out_f [n x fstride] the same values widened back (fstride <= hstride).  *bad_row (preset to 0xFFFFFFFF) receives the
 // lowest row that holds a coordinate which is not finite or rounds out of the binary16 range.

@@ -84,8 +84,12 @@ int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk
     if (!a->queries || !a->out_ids) return fail(GBNNS_ERR_INVALID, "queries / out_ids missing");
     if (a->mode == GBNNS_MODE_NET && !ix->has_net) return fail(GBNNS_ERR_INVALID, "NET mode needs a net");
     if (a->mode != GBNNS_MODE_PLAIN && !ix->db_low) return fail(GBNNS_ERR_INVALID, "mode needs db_low");
-    if (a->mode == GBNNS_MODE_PLAIN && ix->db_b)
-        return fail(GBNNS_ERR_UNSUPPORTED, "GBNNS_MODE_PLAIN walks the original space: not served on a byte handle (gbnns_index_create_bytes)");
+    if (a->mode == GBNNS_MODE_PLAIN && ix->db_b && !(a->flags & GBNNS_FLAG_BYTE_WALK))
+        return fail(GBNNS_ERR_UNSUPPORTED, "GBNNS_MODE_PLAIN on a byte handle (gbnns_index_create_bytes) walks the uint8 rows: served with GBNNS_FLAG_BYTE_WALK only");
+    if (a->flags & GBNNS_FLAG_BYTE_WALK) {
+        if (!ix->db_b) return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_BYTE_WALK needs a byte handle (gbnns_index_create_bytes)");
+        if (a->mode != GBNNS_MODE_PLAIN) return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_BYTE_WALK: PLAIN only (NET / LOWQ walk db_low, which is float32)");
+    }
     if (a->mode == GBNNS_MODE_LOWQ && !a->queries_low) return fail(GBNNS_ERR_INVALID, "queries_low missing");
     if ((a->flags & GBNNS_FLAG_LLF) && !(a->flags & GBNNS_FLAG_AUX_GRAPH))
         return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_LLF needs GBNNS_FLAG_AUX_GRAPH");

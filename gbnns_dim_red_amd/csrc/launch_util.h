@@ -66,5 +66,7 @@ const WalkEntry* walk_half_entry(const WalkInstance& k);
 const WalkEntry* walk_tag_entry(const WalkInstance& k);
 // (the same for `bridge`: walk_bridge.hip)
 const WalkEntry* walk_bridge_entry(const WalkInstance& k);
+// (the same for `bwalk`: walk_bytes.hip)
+const WalkEntry* walk_bytes_entry(const WalkInstance& k);
 
 }  // namespace gbnns

@@ -90,6 +90,9 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
     WalkParams w{};
     if (plain) {
         w.q = q_dev; w.qstride = ix->d; w.db = ix->db; w.dstride = ix->d_pad; w.dim = ix->d;
+        if (ix->db_b) {  // GBNNS_FLAG_BYTE_WALK (checked by search_call): the walked rows are the handle's uint8 rows, d_pad bytes each; no float table exists
+            w.db = nullptr; w.db_b = ix->db_b; w.walk_bytes = 1;
+        }
     } else {
         if ((rc = L.q_low.ensure((size_t)nq * ix->dl_pad * 4))) return rc;
         float* ql = L.q_low.as<float>();
@@ -212,8 +215,9 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
     // every other first pass runs as on a float handle with GBNNS_FLAG_NO_FUSED_RERANK, the stand-alone byte kernel behind it
     const bool bytes = ix->db_b != nullptr;
     if (bytes && !plain && !(a->flags & GBNNS_FLAG_NO_FUSED_RERANK) && rerank_bytes_pair_form(ix->d, ix->metric)) w.bytes_dim = ix->d;
+    // (a byte walk, GBNNS_FLAG_BYTE_WALK: a bit of its own too -- other kernels, no retry pass, and never the float handle's or the byte re-rank's state)
     // sizing statistics are kept per (ef, mode, aux, wide, byte instances: no retry pass behind them, half rows: another table, other walks; tagged: other graphs, shorter walks; bridged: two to three times the rows claimed; knob "hot" = 0: other kernels)
-    const int skey = ((ef * 8 + a->mode * 2 + (aux ? 1 : 0)) * 2 + w.force_wide) | (w.half_rows ? 1 << 30 : 0) | (w.tagged ? 1 << 29 : 0) | (w.bridged ? 1 << 27 : 0) | (w.generic_only ? 1 << 28 : 0) | (w.bytes_dim ? 1 << 26 : 0);
+    const int skey = ((ef * 8 + a->mode * 2 + (aux ? 1 : 0)) * 2 + w.force_wide) | (w.half_rows ? 1 << 30 : 0) | (w.tagged ? 1 << 29 : 0) | (w.bridged ? 1 << 27 : 0) | (w.generic_only ? 1 << 28 : 0) | (w.bytes_dim ? 1 << 26 : 0) | (w.walk_bytes ? 1 << 25 : 0);
     const int calm = ix->calm_streak.count(skey) ? ix->calm_streak[skey] : 0;
     if (aux) {
         w.aux_ell = ix->aux_ell.as<uint32_t>(); w.aux_stride = ix->aux_stride;
@@ -286,7 +290,7 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
         // below -- the pass must at least double the resident wavefronts: 8 by registers against <= 4 by the table -- does from ef 450 on)
         const int min_ef = min_ef_env ? min_ef_env : (rows576 ? 450 : (form == 2 ? 480 : 385));
         const bool forced = (a->flags & GBNNS_FLAG_BITMAP_PASS) != 0;  // diagnostic: whatever ef and batch size
-        if (!w.all_general && !w.coop && !w.tagged && (ef >= min_ef || forced) && !(a->flags & GBNNS_FLAG_WIDE_INDEX) && (a->hash_capacity == 0 || forced)) {
+        if (!w.all_general && !w.coop && !w.tagged && !w.walk_bytes && (ef >= min_ef || forced) && !(a->flags & GBNNS_FLAG_WIDE_INDEX) && (a->hash_capacity == 0 || forced)) {
             bitmap_plan = plan_walk(w, ix->metric, WalkPass::Bitmap);
             const size_t per_wave = granules(bitmap_plan.lds_fixed);   // (the slot counts below follow the device's CU count, as in sizing.cpp)
             const size_t per_cu = std::min<size_t>(rows576 ? 8 : 32, kMaxLds / per_wave);  // (576-byte rows: 223 registers, two wavefronts per SIMD)
@@ -358,7 +362,7 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
         w2.hash_limit = w2.hash_cap - w2.hash_cap / 16;
         if (skip_retry) {
             // nothing to launch
-        } else if (w2.hash_cap > cap && !w.tagged && !w.rr_db_b) {  // (a tagged first pass has no retry pass: its hand-overs go straight to the general kernel; a byte instance's to the general kernel's byte instance)
+        } else if (w2.hash_cap > cap && !w.tagged && !w.rr_db_b && !w.walk_bytes) {  // (a tagged first pass has no retry pass: its hand-overs go straight to the general kernel; a byte instance's and a byte walk's to the general kernel's byte instances)
             HIP_TRY(launch_walk(retry, w2, 0, s));
             if (prof) retry_planned = walk_plan_name(retry);
         } else {

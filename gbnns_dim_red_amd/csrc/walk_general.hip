@@ -25,7 +25,11 @@ namespace {
 // (two lanes that claim one id at once would both be told it is new, or the later one alone).
 // BYTES (walk_general_bytes_kernel: the hand-overs of a byte handle's fused first pass, gbnns_index_create_bytes): the same walk, the fused
 // re-rank over uint8 rows (WalkParams::rr_db_b).
-template <int METRIC, int TAG, bool BYTES = false>
+// BWALK (GBNNS_FLAG_BYTE_WALK: walk_general_bwalk_kernel / _tag_ / _bridge_): the WALKED rows are uint8 (WalkParams::db_b, p.dstride bytes a
+// row = the floats of the staged query) -- the three distances read the row through ByteRow4, a lane per row: l2_ordered / negdot_ordered on
+// float32(row), any dimension, both metrics.  Exact, not tuned.  It takes every flagged call outside the domain of walk_bytes.hip's instances
+// and every query those hand over.
+template <int METRIC, int TAG, bool BYTES = false, bool BWALK = false>
 __device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* smem, uint32_t* bst = nullptr) {
     const int lane = lane_id();
     const uint32_t slot = blockIdx.x;
@@ -83,7 +87,9 @@ __device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* s
         wave_sync();
         const uint32_t entry = p.entries ? p.entries[(size_t)qi * n_ent + e] : 0u;
         {
-            const float d0 =
+            float d0;
+            if constexpr (BWALK) d0 = metric_dist<METRIC>(qs, ByteRow4{reinterpret_cast<const uint32_t*>(p.db_b + (size_t)entry * p.dstride)}, p.dim);
+            else d0 =
                 metric_dist<METRIC>(qs, reinterpret_cast<const float4*>(p.db + (size_t)entry * p.dstride),
                                     p.dim);
             if (e == 0) {
@@ -117,6 +123,9 @@ __device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* s
                     fresh = !(atomicOr(&bitmap[nb >> 5], bit) & bit);
                 }
                 uint32_t dk = 0xFFFFFFFFu;
+                if constexpr (BWALK) {
+                    if (fresh) dk = fkey(metric_dist<METRIC>(qs, ByteRow4{reinterpret_cast<const uint32_t*>(p.db_b + (size_t)nb * p.dstride)}, p.dim));
+                } else
                 if (fresh)
                     dk = fkey(metric_dist<METRIC>(
                         qs, reinterpret_cast<const float4*>(p.db + (size_t)nb * p.dstride), p.dim));
@@ -152,6 +161,9 @@ __device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* s
                 fresh = !(atomicOr(&bitmap[nb >> 5], bit) & bit);
             }
             uint32_t dk = 0xFFFFFFFFu;
+            if constexpr (BWALK) {
+                if (fresh) dk = fkey(metric_dist<METRIC>(qs, ByteRow4{reinterpret_cast<const uint32_t*>(p.db_b + (size_t)nb * p.dstride)}, p.dim));
+            } else
             if (fresh)
                 dk = fkey(metric_dist<METRIC>(qs, reinterpret_cast<const float4*>(p.db + (size_t)nb * p.dstride), p.dim));
             const uint64_t mf = __ballot(fresh);
@@ -268,6 +280,22 @@ __global__ __launch_bounds__(64) void walk_general_bridge_kernel(WalkParams p) {
     walk_general_body<METRIC, 2>(p, smem, bst);
 }
 
+// GBNNS_FLAG_BYTE_WALK: plain, cut (gbnns_search_tagged) and bridged (GBNNS_FLAG_TAG_BRIDGE) over uint8 walked rows
+template <int METRIC, int TAG>
+__global__ __launch_bounds__(64) void walk_general_bwalk_kernel(WalkParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ uint32_t bst[TAG == 2 ? 64 : 1];
+    walk_general_body<METRIC, TAG, false, true>(p, smem, TAG == 2 ? bst : nullptr);
+}
+
+template <typename K>
+hipError_t launch_general(K kernel, const WalkParams& p, size_t lds, hipStream_t s) {
+    const hipError_t e = set_lds(kernel, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(kGeneralSlots), dim3(64), lds, s, p);
+    return hipGetLastError();
+}
+
 // Diagnostic kernel (tests only): runs one batch merge on a list / survivor set supplied by the host.
 template <int R>
 __global__ __launch_bounds__(64) void debug_merge_kernel(const uint64_t* entries, int size, const uint64_t* surv, int ef,
@@ -309,6 +337,18 @@ __global__ __launch_bounds__(64) void debug_merge_kernel(const uint64_t* entries
 hipError_t launch_walk_general(const WalkParams& p, int metric, hipStream_t s) {
     if (p.nq == 0) return hipSuccess;
     const size_t lds = std::max((size_t)p.dstride * 4, (p.rr_db || p.rr_db_b) ? (size_t)p.rr_dstride * 4 : (size_t)0);
+    if (p.walk_bytes) {  // GBNNS_FLAG_BYTE_WALK: a PLAIN walk over uint8 rows, no re-rank
+        if (!p.db_b || p.rr_db || p.rr_db_b || (p.tagged && (!p.tags || !p.qtags))) return hipErrorInvalidValue;
+        const int tag = p.tagged ? (p.bridged ? 2 : 1) : 0;
+        if (metric == 1) {
+            if (tag == 2) return launch_general(walk_general_bwalk_kernel<1, 2>, p, lds, s);
+            if (tag == 1) return launch_general(walk_general_bwalk_kernel<1, 1>, p, lds, s);
+            return launch_general(walk_general_bwalk_kernel<1, 0>, p, lds, s);
+        }
+        if (tag == 2) return launch_general(walk_general_bwalk_kernel<0, 2>, p, lds, s);
+        if (tag == 1) return launch_general(walk_general_bwalk_kernel<0, 1>, p, lds, s);
+        return launch_general(walk_general_bwalk_kernel<0, 0>, p, lds, s);
+    }
     if (p.rr_db_b) {  // a byte handle's fused call: untagged, L2 (walk_plan.cpp)
         if (p.rr_db || p.tagged || metric != 0) return hipErrorInvalidValue;
         hipError_t e = set_lds(walk_general_bytes_kernel, lds);

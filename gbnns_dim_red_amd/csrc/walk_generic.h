@@ -26,6 +26,21 @@ __device__ __forceinline__ void keep_rows(const RowRegs<STEPS>& r) {
     for (int t = 0; t < STEPS; ++t) asm volatile("" ::"v"(r.v[t].x), "v"(r.v[t].y), "v"(r.v[t].z), "v"(r.v[t].w));
 }
 
+// BYTES (GBNNS_FLAG_BYTE_WALK, walk_bytes.hip): a lane's share of a 128-byte uint8 row -- the even lane of a pair holds the 16-byte chunks
+// 0, 2, 4, 6, the odd lane 1, 3, 5, 7, packed as loaded (load_row_alt's pieces: 16 registers) -- against the query's float4 pieces in LDS
+// (`qh` = the staged query + 4 * half float4).  byte_chunk_add (walk_common.h) widens and consumes a chunk at a time; the sums hop to the
+// partner once per chunk, the finished sum of squares is the odd lane's: l2_ordered on float32(row), operation for operation.
+__device__ __forceinline__ float l2_pair_from_bytes(const RowRegs<4>& r, const float4* qh) {
+    float u[4], v[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float4* qc = qh + 8 * j;
+        const float4 q[4] = {qc[0], qc[1], qc[2], qc[3]};
+        byte_chunk_add(make_uint4(__float_as_uint(r.v[j].x), __float_as_uint(r.v[j].y), __float_as_uint(r.v[j].z), __float_as_uint(r.v[j].w)), q, u, v);
+    }
+    return ((v[0] + v[1]) + v[2]) + v[3];
+}
+
 // ---- fast kernel: result list, tie list, visited hash set and the query all live in LDS -------
 //
 // LDS layout (dynamic): [keys: ef_pad x u64][tie: kTieCap x u64][q: dstride x f32][hash: cap x u32]
@@ -205,8 +220,11 @@ __global__ __launch_bounds__(64) void walk_bitmap_kernel(WalkParams p) {
 // rows BEHIND the tag test (three round trips, rows of allowed slots only).  keep_rows is what holds the first two classes' loads ahead of
 // the early `continue`.  The instances that request their rows after the visited test (LATE) ask for the new allowed ids only, as before.
 // The query's tag word is wave-uniform and lives in a scalar register.
+// BYTES: GBNNS_FLAG_BYTE_WALK (walk_bytes.hip; L2, STEPS = 8 = the 16-byte chunks of a 128-byte uint8 row of d = 128, compact index) -- the hop's
+// rows and the entry row come from the byte table WalkParams::db_b (p.db is nullptr, p.dstride the bytes of a row), a lane keeps its four
+// chunks packed until l2_pair_from_bytes consumes them, and the query (128 floats) is re-read from LDS every hop; nothing else differs
 template <int METRIC, int STEPS, bool OFF32, int R, bool ONE_CHUNK = false, bool AUX = false, bool BITMAP = false, bool QLDS_W = false, int LATE = -1,
-          bool HALF = false, bool TAG = false>
+          bool HALF = false, bool TAG = false, bool BYTES = false>
 __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, unsigned char* smem,
                                              uint32_t* ovf_count, uint32_t* ovf_list, uint32_t* bitmap = nullptr) {
     static_assert(!(AUX && ONE_CHUNK), "auxiliary rows have their own length");
@@ -228,6 +246,7 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
     constexpr uint64_t kSlotLanes = kPair ? 0x5555555555555555ull : ~0ull;  // lanes that own a slot
     static_assert(!HALF || (kPair && OFF32 && !QLDS_W), "HALF: pair-form instances of a compact index");
     static_assert(!TAG || (kPair && OFF32 && !BITMAP && !HALF), "TAG: pair-form instances of a compact index");
+    static_assert(!BYTES || (METRIC == 0 && STEPS == 8 && OFF32 && !AUX && !BITMAP && !QLDS_W && !HALF && !TAG), "BYTES: L2 over 128-byte uint8 rows of a compact index");
     const int lane = lane_id();
     const uint32_t slot = kPair ? (uint32_t)lane >> 1 : (uint32_t)lane;    // adjacency slot of this lane
     const uint32_t half = kPair ? (uint32_t)lane & 1u : 0u;
@@ -258,7 +277,7 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
     // issue-bound from ~14 wavefronts/CU, so the registers cost nothing and each hop saves 8 LDS reads
     // QLDS_W (walk_reg_wide_kernel: 192- / 256-byte rows, ef <= 64, one pass): the lane's query pieces are re-read from the
     // wavefront's LDS copy every hop, in the shadow of the row loads -- 24 / 32 registers less across the hop
-    constexpr bool kWideQLds = QLDS_W;
+    constexpr bool kWideQLds = QLDS_W || BYTES;
     static_assert(!QLDS_W || (kPair && (STEPS == 12 || STEPS == 16) && R == 1 && !BITMAP), "QLDS_W: pair-form L2 instances over wide rows");
     RowRegs<kWideQLds ? 0 : kQSteps> qreg;
     if constexpr (kEarlyLoad && !kWideQLds) {
@@ -279,7 +298,9 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
         if ((tag_word(p.tags, entry) & qtag) == 0u) { write_bad_entry(p, qi, lane); return; }
     }
     {
-        const float d0 = walk_dist<METRIC, STEPS>(qs, row_ptr<OFF32>(p.db, entry, p.dstride), p.dim);
+        float d0;
+        if constexpr (BYTES) d0 = metric_dist<0>(qs, ByteRow4{reinterpret_cast<const uint32_t*>(p.db_b + entry * kRowBytes)}, p.dim);  // (a lane per row: the same sums)
+        else d0 = walk_dist<METRIC, STEPS>(qs, row_ptr<OFF32>(p.db, entry, p.dstride), p.dim);
         worst = fkey(d0);
         if (lane == 0) {
             L.hi[0] = worst;
@@ -462,7 +483,10 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
                 constexpr bool kAllLanes = (kPair && (ONE_CHUNK || STEPS == 24)) || (!kPair && kQSteps >= 12);
                 const uint32_t nbl = kAllLanes ? (want ? nb : 0u) : nb;
                 const bool ld = kAllLanes || want;
-                if constexpr (HALF) {  // rows of kRowBytes / 2 bytes: the same float4 pieces, two bytes a coordinate
+                if constexpr (BYTES) {  // rows of kRowBytes bytes: the lane's chunks half, half + 2, half + 4, half + 6
+                    roff = nbl * kRowBytes + half * 16u;
+                    if (ld) load_row_alt(rr, reinterpret_cast<const float*>(p.db_b + roff));
+                } else if constexpr (HALF) {  // rows of kRowBytes / 2 bytes: the same float4 pieces, two bytes a coordinate
                     roff = nbl * (kRowBytes / 2u) + half * (kAlt ? 8u : kRowBytes / 4u);
                     const void* rp = reinterpret_cast<const char*>(p.db_h) + roff;
                     if constexpr (kAlt) { if (ld) load_row_half_alt(rh, rp); }
@@ -516,7 +540,12 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
             uint32_t dk = 0xFFFFFFFFu;
             if constexpr (HALF) widen_row(rr, rh);
             if constexpr (kEarlyLoad) {
-                if constexpr (kAlt) {
+                if constexpr (BYTES) {
+                    const float4* ql = qs + 4u * half;
+                    asm volatile("" : "+v"(ql));  // (not hoisted out of the hop loop)
+                    const uint32_t kd = fkey_sumsq(l2_pair_from_bytes(rr, ql));  // all lanes; odd lanes hold distances
+                    dk = fresh ? kd : 0xFFFFFFFFu;
+                } else if constexpr (kAlt) {
                     const uint32_t kd = fkey(dot_pair_from_regs(rr, qreg.v));  // all lanes; odd lanes hold distances
                     dk = fresh ? kd : 0xFFFFFFFFu;
                 } else if constexpr (kPair && STEPS == 8) {
@@ -634,9 +663,9 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
 // ef <= 64 whatever ef is (the R-register lists spent 28 % of a hop selecting and 30 % inserting at ef = 300).
 // LDS: [BigList: big_list_fixed_bytes(ef)][query: dstride floats][visited set | (BITMAP) re-rank scratch].
 // ONE_PASS: adjacency rows of one pass (the host checks ell_stride), no auxiliary graph -- the hop is straight-line code.
-// HALF, TAG: as in walk_reg_one.
+// HALF, TAG, BYTES: as in walk_reg_one.
 template <int METRIC, int STEPS, bool OFF32, bool AUX = false, bool BITMAP = false, bool ONE_PASS = false, bool LATE = false, bool HALF = false,
-          bool TAG = false>
+          bool TAG = false, bool BYTES = false>
 __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t qi, unsigned char* smem,
                                                  uint32_t* ovf_count, uint32_t* ovf_list, uint32_t* bitmap = nullptr) {
     constexpr bool kEarlyLoad = (STEPS > 0);
@@ -657,6 +686,7 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
     constexpr uint64_t kSlotLanes = kPair ? 0x5555555555555555ull : ~0ull;
     static_assert(!HALF || (kPair && OFF32), "HALF: pair-form instances of a compact index");
     static_assert(!TAG || (kPair && OFF32 && !BITMAP && !HALF), "TAG: pair-form instances of a compact index");
+    static_assert(!BYTES || (METRIC == 0 && STEPS == 8 && OFF32 && !AUX && !BITMAP && !LATE && !HALF && !TAG), "BYTES: L2 over 128-byte uint8 rows of a compact index");
     const int lane = lane_id();
 #ifdef GBNNS_STAMPS  // diagnostic build: cycles per segment of the hop (tools/stamps.py)
     unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -698,7 +728,7 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
     // 72 registers of query beside 72 of squared differences are two wavefronts per SIMD; the float32 instances, bound by their rows' bytes,
     // live with that, the half instance has half the bytes in flight per wavefront and wants the third)
     // (TAG: the same -- 223 registers would be two wavefronts per SIMD by registers alone, and the tag word wants one more)
-    constexpr bool kQLds = (HALF || TAG) && STEPS >= 24;
+    constexpr bool kQLds = ((HALF || TAG) && STEPS >= 24) || BYTES;  // (BYTES: the query is 128 floats)
     RowRegs<kQLds ? 0 : kQSteps> qreg;
     if constexpr (kEarlyLoad && !kQLds) {
 #pragma unroll
@@ -720,11 +750,15 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
             // the entry's distance in the pair form, on the query registers (lanes 0 / 1 would do; every pair computes it):
             // the one-lane form reads the whole row and the whole query into registers and was the kernel's register peak
             RowRegs<kQSteps> er;
+            if constexpr (BYTES) load_row_alt(er, reinterpret_cast<const float*>(p.db_b + entry * kRowBytes + half * 16u));
+            else {
             const float* rp = row_ptr<OFF32>(p.db, entry, p.dstride) + half * (kAlt ? 4u : kRowBytes / 8u);
             if constexpr (kAlt) load_row_alt(er, rp);
             else load_row<kQSteps>(er, rp);
+            }
             uint32_t kd;
-            if constexpr (kAlt) kd = fkey(dot_pair_from_regs(er, qreg.v));
+            if constexpr (BYTES) kd = fkey_sumsq(l2_pair_from_bytes(er, qs + 4u * half));
+            else if constexpr (kAlt) kd = fkey(dot_pair_from_regs(er, qreg.v));
             else if constexpr (STEPS == 8) kd = fkey_sumsq(l2_pair_from_regs(er, qreg.v));
             else if constexpr (kQLds) kd = fkey_sumsq(l2_pair_from_regs_wide<kQSteps>(er, qs + kQSteps * half));
             else kd = fkey_sumsq(l2_pair_from_regs_wide<kQSteps>(er, qreg.v));
@@ -813,7 +847,10 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
                 constexpr bool kAllLanes = kPair || kQSteps >= 12;
                 const uint32_t nbl = kAllLanes ? (want ? nb : 0u) : nb;
                 const bool ld = kAllLanes || want;
-                if constexpr (HALF) {  // rows of kRowBytes / 2 bytes: the same float4 pieces, two bytes a coordinate
+                if constexpr (BYTES) {  // rows of kRowBytes bytes: the lane's chunks half, half + 2, half + 4, half + 6
+                    roff = nbl * kRowBytes + half * 16u;
+                    if (ld) load_row_alt(rr, reinterpret_cast<const float*>(p.db_b + roff));
+                } else if constexpr (HALF) {  // rows of kRowBytes / 2 bytes: the same float4 pieces, two bytes a coordinate
                     roff = nbl * (kRowBytes / 2u) + half * (kAlt ? 8u : kRowBytes / 4u);
                     const void* rp = reinterpret_cast<const char*>(p.db_h) + roff;
                     if constexpr (kAlt) { if (ld) load_row_half_alt(rh, rp); }
@@ -867,7 +904,12 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
             uint32_t dk = 0xFFFFFFFFu;
             if constexpr (HALF) widen_row(rr, rh);
             if constexpr (kEarlyLoad) {
-                if constexpr (kAlt) {
+                if constexpr (BYTES) {
+                    const float4* ql = qs + 4u * half;
+                    asm volatile("" : "+v"(ql));  // (not hoisted out of the hop loop)
+                    const uint32_t kd = fkey_sumsq(l2_pair_from_bytes(rr, ql));
+                    dk = fresh ? kd : 0xFFFFFFFFu;
+                } else if constexpr (kAlt) {
                     const uint32_t kd = fkey(dot_pair_from_regs(rr, qreg.v));
                     dk = fresh ? kd : 0xFFFFFFFFu;
                 } else if constexpr (kPair && STEPS == 8) {

@@ -71,6 +71,28 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
     // (a visited set in the packed form: no id may look like a half-written slot -- see visited_test_mask_packed)
     pl.coop_serves = metric == 0 && (rows == 32u || rows == 48u || rows == 64u) && regs == 4 && ef <= kRegListMaxEf && off32 && p.n < 0xFF0000u && !aux &&
                      one && p.n_entries <= 1u && !tag;
+    if (p.walk_bytes) {
+        // GBNNS_FLAG_BYTE_WALK: the walked rows are a byte handle's uint8 rows (WalkParams::db_b; dstride = the BYTES of a row).  The byte-walk
+        // instances (walk_bytes.hip): first pass, L2 over 128-byte rows of d = 128 (eight 16-byte chunks a lane pair shares), compact index
+        // (the byte table, the adjacency table < 4 GiB, 24-bit ids), one entry point per query, no auxiliary graph, untagged, ef <= 1 024 --
+        // the register lists with ONE_CHUNK, the two-list kernel with ONE_PASS where the adjacency rows are one 32-slot pass.  Everything else
+        // runs whole on the general kernel's byte-walk instance, which is also where a fast instance's hand-overs go: there is no byte form of
+        // the retry pass, the bitmap pass, the two-wavefront walk, the walk_hot* family, late / speculative rows or the LDS-list kernel.
+        const bool compact = !p.force_wide && (uint64_t)p.n * p.dstride < (1ull << 32) && (uint64_t)p.n * p.ell_stride * 4 < (1ull << 32) && p.n <= 0xFFFFFFu;
+        const bool fast = pass == WalkPass::First && metric == 0 && p.dim == 128u && p.dstride == 128u && compact && p.n_entries <= 1u && !aux && !p.tagged &&
+                          ef <= kRegListMaxEf;
+        pl.coop_serves = false;
+        pl.lds_list = false;
+        pl.general_only = !fast;
+        if (fast) {
+            k = {regs == 4 ? WalkFamily::TwoList : WalkFamily::RegList, 0, 8, regs, true, false, one};
+            k.bwalk = true;
+            pl.packed = true;
+            pl.lds_fixed = lds_fixed_bytes(ef, p.dstride, false, false, false);  // (the query: dstride = 128 floats, re-read from LDS every hop)
+            pl.knows_quotient = true;  // (as the float pair-form instances of a compact index)
+        }
+        return pl;  // (no rr_* room: PLAIN has no re-rank)
+    }
     if (pass == WalkPass::Bitmap) {
         // The bitmap first pass runs the register-list (ef <= 128, L2) / two-list (128 < ef <= 1 024, both metrics) walk for 128-byte rows
         // of a compact index, the two-list walk for 256- and 576-byte rows with L2 (the reference's glove 300 -> 144), else the LDS-list walk.

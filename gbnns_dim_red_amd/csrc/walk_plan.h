@@ -52,6 +52,7 @@ enum class WalkFamily : uint8_t {
                 // half: walk_reg_big_half_kernel<METRIC, STEPS, ONE_PASS, LATE>    (walk_half.hip)
                 // tag (either family): walk_reg_tag_kernel<METRIC, STEPS, R, ONE_CHUNK> / walk_reg_big_tag_kernel<METRIC, STEPS, ONE_PASS, LATE> (walk_tag.hip)
                 // bridge (register lists): walk_bridge_kernel<METRIC, STEPS, R>                (walk_bridge.hip)
+                // byte walk (either family): walk_reg_bytes_kernel<R, ONE_CHUNK> / walk_reg_big_bytes_kernel<ONE_PASS> (walk_bytes.hip)
     LdsList,    // walk_fast_kernel<METRIC, STEPS, RETRY, PACKED>                    (walk_l2 / walk_dot / walk_wide)
     BitmapReg,  // walk_bitmap_reg_kernel<METRIC, R>                                 (walk_bitmap.hip)
     BitmapBig,  // walk_bitmap_big_kernel<METRIC, STEPS, ONE_PASS, LATE>
@@ -74,10 +75,11 @@ struct WalkInstance {
     bool tag;     // the hop tests every neighbour's tag word against the query's (WalkParams::tags / qtags): walk_reg_tag_kernel / walk_reg_big_tag_kernel (walk_tag.hip)
     bool bridge;  // (with tag) a disallowed neighbour is looked through, its allowed neighbours staged in LDS in its place: walk_bridge_kernel (walk_bridge.hip)
     bool bytes;   // the fused re-rank reads uint8 rows (WalkParams::rr_db_b, a byte handle): walk_hot_bytes_kernel / walk_hot2_bytes_kernel (walk_hot.hip)
+    bool bwalk;   // the WALKED rows are uint8 (WalkParams::db_b, GBNNS_FLAG_BYTE_WALK): walk_reg_bytes_kernel / walk_reg_big_bytes_kernel (walk_bytes.hip)
 };
 inline bool operator==(const WalkInstance& a, const WalkInstance& b) {
     return a.family == b.family && a.metric == b.metric && a.steps == b.steps && a.regs == b.regs && a.off32 == b.off32 && a.retry == b.retry && a.one == b.one &&
-           a.aux == b.aux && a.late == b.late && a.spec == b.spec && a.packed == b.packed && a.half == b.half && a.tag == b.tag && a.bridge == b.bridge && a.bytes == b.bytes;
+           a.aux == b.aux && a.late == b.late && a.spec == b.spec && a.packed == b.packed && a.half == b.half && a.tag == b.tag && a.bridge == b.bridge && a.bytes == b.bytes && a.bwalk == b.bwalk;
 }
 
 struct WalkPlan {
@@ -89,7 +91,7 @@ struct WalkPlan {
     bool knows_quotient;   // the instance reads WalkParams::vs_shr
     bool lds_list;         // result list in LDS as one sorted array: no fused re-rank
     bool coop_serves;      // the two-wavefront walk has an instance for this shape (whether or not this plan is it)
-    bool general_only;     // several entry points per query, or a tagged / bridged call outside its instances' domain: the general kernel takes the whole batch
+    bool general_only;     // several entry points per query, or a tagged / bridged / byte-walk call outside its instances' domain: the general kernel takes the whole batch
     size_t rr_base;        // room of the fused re-rank's query = rr_base (+ the visited set's bytes when rr_in_table)
     bool rr_in_table;      // (rr_room below)
     // form of the visited set (walk_hash_bytes, kernels.h); vs_shr is set only where the instance knows the quotient form
@@ -101,7 +103,7 @@ struct WalkPlan {
 // GBNNS_STAMPS_GENERIC keeps diagnostic (GBNNS_STAMPS) builds off the hot two-list instances.
 struct WalkEnv { bool wide2, stamps_generic; };
 const WalkEnv& walk_env();
-// Reads the shape (dim, dstride, n, ell_stride, aux_ell / aux_stride), ef, n_entries, force_wide, coop, late_rows, spec_rows, stamps_on, half_rows, tagged, bridged, generic_only, bytes_dim
+// Reads the shape (dim, dstride, n, ell_stride, aux_ell / aux_stride), ef, n_entries, force_wide, coop, late_rows, spec_rows, stamps_on, half_rows, tagged, bridged, generic_only, bytes_dim, walk_bytes
 // and rr_reserve -- nothing the sizing rule writes (hash_cap, hash_limit, vs_shr), so the layout is known before the visited set is sized.
 WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv& env = walk_env());
 

@@ -111,8 +111,9 @@ int gbnns_index_create(const gbnns_index_desc* desc, gbnns_index** out);
  * value is a binary32 value: nothing is rounded, and the distances are evaluated in the same operation order.)
  * Served: gbnns_search_ex / gbnns_search_batch in NET and LOWQ mode, gbnns_search_topk, gbnns_search_tagged (with and without
  * GBNNS_FLAG_TAG_BRIDGE), gbnns_rerank, gbnns_rerank_topk, gbnns_project, with every flag that applies to them, several entry points,
- * HOST or DEVICE buffers.  GBNNS_MODE_PLAIN walks the original space: GBNNS_ERR_UNSUPPORTED on a byte handle for now.  gbnns_multi_create
- * has no byte form.
+ * HOST or DEVICE buffers; and, with GBNNS_FLAG_BYTE_WALK (below), gbnns_search_ex and gbnns_search_tagged in GBNNS_MODE_PLAIN, which walks
+ * the uint8 rows themselves.  GBNNS_MODE_PLAIN without that flag stays GBNNS_ERR_UNSUPPORTED on a byte handle.  gbnns_multi_create has no
+ * byte form.
  * Kernels: with L2, d % 16 == 0, 128-byte walked rows, a compact index, adjacency rows of at most 32 slots and ef <= 128 the first pass
  * (walk_hot_bytes_kernel, walk_hot2_bytes_kernel) re-ranks its own query over the byte rows and hands what it cannot finish to
  * walk_general_bytes_kernel, without a retry pass; every other call runs the very first-pass kernel a float handle would run, without the
@@ -389,6 +390,27 @@ int gbnns_search_tagged(gbnns_index* index, const gbnns_search_args* args, const
  * and every other case (beams above 128 and 144-float rows included), runs on the general kernel's bridged instance ("walk_general_kernel"
  * in the profile and in gbnns_debug_bridge_plan): same results. */
 #define GBNNS_FLAG_TAG_BRIDGE 1024u
+/* The byte-row PLAIN walk: gbnns_search_ex and gbnns_search_tagged (with and without GBNNS_FLAG_TAG_BRIDGE, k == 0) with
+ * mode == GBNNS_MODE_PLAIN on a byte handle (gbnns_index_create_bytes) walk the graph in the space of the handle's uint8 table -- the hnsw
+ * half of the reference's final_test over .bvecs data.
+ * Contract: Every output equals, bit for bit, what the same call without the flag returns on the handle created with
+ * db = float32(db_bytes).  The outputs are ids, out_cand in pop order, out_cand_dist bit patterns, hops, dist_calc and edges.  This holds
+ * for every k, both metrics, any d (the L2 d % 4 tail ignored, the dot's masked tail against the zero padding), and several entry points;
+ * with GBNNS_FLAG_AUX_GRAPH / GBNNS_FLAG_LLF, GBNNS_FLAG_WIDE_INDEX, hash_capacity, GBNNS_FLAG_SERIAL, GBNNS_FLAG_DEFER_JOIN, and HOST or
+ * DEVICE buffers.  GBNNS_FLAG_BITMAP_PASS is ignored.  A bad entry id gives the documented all-0xFFFFFFFF row.  (Each byte is widened with
+ * one exact conversion and the sums run in the reference's order -- four running sums, separately rounded subtract, multiply and add.)
+ * No float copy of the table is made, on the device or the host, at any point: the memory promise of the byte handle holds for PLAIN calls.
+ * Refused with GBNNS_ERR_INVALID: the flag on a float handle; the flag with NET / LOWQ (the walked space is db_low, which is float32); the
+ * flag in the gbnns_multi_* searches.  gbnns_search_topk in PLAIN mode and GBNNS_FLAG_HALF_ROWS in PLAIN mode stay GBNNS_ERR_INVALID.
+ * The walk is opt-in for now: GBNNS_MODE_PLAIN without the flag on a byte handle stays GBNNS_ERR_UNSUPPORTED.  Lifting the flag requirement
+ * -- PLAIN on a byte handle simply meaning this walk -- is a later, separate change.
+ * Kernels: L2 with d == 128, a compact index (n < 2^24, tables < 4 GiB), one entry point per query, no auxiliary graph, untagged and
+ * ef <= 1 024 run a byte-walk first pass (walk_reg_bytes_kernel<R, ONE_CHUNK>, walk_reg_big_bytes_kernel<ONE_PASS> in
+ * gbnns_profile.walk_kernel): two lanes per neighbour over packed 16-byte chunks, the query in LDS.  It has no retry pass; what it hands
+ * over, and every other flagged call -- other dimensions, the negative dot, several entry points, the auxiliary graph, GBNNS_FLAG_WIDE_INDEX,
+ * beams above 1 024, every tagged or bridged call -- runs on the general kernel's byte-walk instance ("walk_general_kernel" in the profile
+ * and in gbnns_debug_byte_walk_plan), which is exact, not tuned: a lane per row. */
+#define GBNNS_FLAG_BYTE_WALK 2048u
 
 /* Per-kernel device timing (hipEvent pairs on the launch stream), accumulated since the last
  * reset.  Reading synchronises the recorded events. */
@@ -484,6 +506,12 @@ int gbnns_debug_bridge_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t
 int gbnns_debug_byte_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef,
                           uint32_t n_entries, int force_wide, int coop, int late_rows, int spec_rows, int pass, uint32_t rr_reserve,
                           char* name, uint32_t name_bytes, int* fused);
+/* Diagnostic, no device needed: the first-pass kernel a GBNNS_MODE_PLAIN call with GBNNS_FLAG_BYTE_WALK of that shape gets on a byte handle
+ * ("walk_general_kernel": the general kernel's byte-walk instance takes the whole batch) and its LDS bytes per wavefront without the
+ * visited set.  `dim` is the original dimension -- the walked row is round_up(dim, 16) bytes --, `tagged` != 0 a gbnns_search_tagged call;
+ * the other inputs as for gbnns_debug_walk_plan. */
+int gbnns_debug_byte_walk_plan(int metric, uint32_t dim, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries, int force_wide,
+                               int tagged, char* name, uint32_t name_bytes, uint64_t* lds_bytes);
 /* Diagnostic, no device needed: LDS bytes of a workgroup of the one-launch projection for a net d -> d_hidden -> d_hidden -> d_low, in
  * the whole-CU form (form 0) or the half-CU form (form 1), with a queries per lane (2 .. 5), and whether that form takes the net at all
  * (*admitted: a workgroup with a = 4 fits 160 KB / 80 KB). */
