@@ -40,6 +40,7 @@ SYMBOLS = [
     "gbnns_round_to_half", "gbnns_index_enable_half_rows", "gbnns_index_low_rows",
     "gbnns_index_set_tags", "gbnns_search_tagged", "gbnns_debug_tag_plan", "gbnns_debug_bridge_plan",
     "gbnns_index_create_bytes", "gbnns_index_is_bytes", "gbnns_debug_byte_plan", "gbnns_debug_byte_walk_plan",
+    "gbnns_exact_knn_bytes", "gbnns_debug_knn_bytes_plan",
 ]
 
 
@@ -145,6 +146,9 @@ def load_library():
                                                 C.POINTER(C.c_uint64)]
     lib.gbnns_exact_knn.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
                                     C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.gbnns_exact_knn_bytes.argtypes = lib.gbnns_exact_knn.argtypes
+    lib.gbnns_debug_knn_bytes_plan.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
     lib.gbnns_multi_last_error.restype = C.c_char_p
     lib.gbnns_multi_create.argtypes = [C.POINTER(_IndexDesc), C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
     lib.gbnns_multi_destroy.argtypes = [C.c_void_p]
@@ -298,6 +302,14 @@ def byte_plan(metric, dim, n, ell_stride, ef, aux_stride=0, n_entries=1, wide=Fa
     return name.value.decode(), bool(fused.value)
 
 
+def knn_bytes_plan(n, n_q, d, k):
+    """gbnns_debug_knn_bytes_plan (no device needed): what exact_knn does with uint8 inputs of that shape under the current knn_chunk /
+    knn_pool_min_k knobs -- dict(dp, cap, first_rows, max_chunk, pool)."""
+    dp, cap, first, chunk, pool = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0), C.c_int(0)
+    _check(load_library().gbnns_debug_knn_bytes_plan(n, n_q, d, k, C.byref(dp), C.byref(cap), C.byref(first), C.byref(chunk), C.byref(pool)))
+    return {"dp": int(dp.value), "cap": int(cap.value), "first_rows": int(first.value), "max_chunk": int(chunk.value), "pool": bool(pool.value)}
+
+
 def _is_u8(x):
     if _is_dev(x):
         import torch
@@ -375,13 +387,20 @@ def build_graph_gd_device(knn_offsets, knn_nbrs, ds, M, metric=METRIC_L2, revers
 def exact_knn(base, queries, k, metric=METRIC_L2, self_offset=-1, want_dist=False, device=0, stream=None):
     """gbnns_exact_knn: ids [n_q x k] (and distances) of the k nearest base rows of every query, in the
     reference's distance arithmetic, ascending (distance, id).  numpy in -> numpy out; torch CUDA in -> torch
-    out.  self_offset >= 0: query i is base row i + self_offset (excluded from its own list)."""
+    out.  self_offset >= 0: query i is base row i + self_offset (excluded from its own list).
+    Both arguments uint8 (numpy or torch): gbnns_exact_knn_bytes -- the same answer as over the widened arrays, bit for
+    bit, on the int8 matrix cores and without a float copy (d <= 256, k <= 4096)."""
     lib = load_library()
     dev = _is_dev(base)
     if _is_dev(queries) != dev:
         raise TypeError("base and queries must live in the same memory kind")
-    base = _prep(base, np.float32, "float32")
-    queries = _prep(queries, np.float32, "float32")
+    u8 = _is_u8(base)
+    if _is_u8(queries) != u8:
+        raise TypeError("base and queries must both be uint8 (gbnns_exact_knn_bytes: byte rows against byte queries) or both be float "
+                        "(gbnns_exact_knn); for float queries against a byte table widen the table with .astype(float32)")
+    fn = lib.gbnns_exact_knn_bytes if u8 else lib.gbnns_exact_knn
+    base = _prep(base, np.uint8, "uint8") if u8 else _prep(base, np.float32, "float32")
+    queries = _prep(queries, np.uint8, "uint8") if u8 else _prep(queries, np.float32, "float32")
     n, d = int(base.shape[0]), int(base.shape[1])
     nq = int(queries.shape[0])
     if int(queries.shape[1]) != d:
@@ -398,8 +417,8 @@ def exact_knn(base, queries, k, metric=METRIC_L2, self_offset=-1, want_dist=Fals
         ids = np.empty((nq, k), np.uint32)
         dist = np.empty((nq, k), np.float32) if want_dist else None
         sptr = None
-    _check(lib.gbnns_exact_knn(device, _ptr(base), n, _ptr(queries), nq, d, k, metric, self_offset, _ptr(ids),
-                               _ptr(dist), MEM_DEVICE if dev else MEM_HOST, sptr))
+    _check(fn(device, _ptr(base), n, _ptr(queries), nq, d, k, metric, self_offset, _ptr(ids),
+              _ptr(dist), MEM_DEVICE if dev else MEM_HOST, sptr))
     return (ids, dist) if want_dist else ids
 
 

@@ -1,5 +1,6 @@
 // graph_api.cpp -- graph preparation entry points of the C ABI (include/gbnns.h): gbnns_exact_knn (getTruth, support_func.h:270-290,
-// generalised to k results: heaps, the matrix-core filter, long lists as pools) and gbnns_build_graph_gd_device (hnswlikeGD,
+// generalised to k results: heaps, the matrix-core filter, long lists as pools), gbnns_exact_knn_bytes (the same lists over uint8 rows,
+// their distances from the int8 matrix cores: knn_bytes.hip) with gbnns_debug_knn_bytes_plan, and gbnns_build_graph_gd_device (hnswlikeGD,
 // support_func.h:521-575, pruning on the device).  Cut out of api.cpp in round 5; api_internal.h lists the other units.
 
 #include "api_internal.h"
@@ -195,6 +196,169 @@ int gbnns_exact_knn(int device, const float* base, uint64_t n, const float* quer
     if (host) {
         HIP_TRY(hipMemcpyAsync(out_ids, p.out_ids, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
         if (out_dist) HIP_TRY(hipMemcpyAsync(out_dist, p.out_dist, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
+    }
+    // the temporaries are released below: wait for the work that uses them
+    HIP_TRY(hipStreamSynchronize(s));
+    return GBNNS_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// What gbnns_exact_knn_bytes does with a shape under the current knobs (gbnns_debug_knn_bytes_plan reports it).
+struct KnnBytesPlan {
+    uint32_t dp;          // row bytes of the packed operands: d rounded up to the K step
+    uint32_t cap;         // key slots of a query per chunk
+    uint64_t first_rows;  // rows of the first chunk (thresholds at "everything passes") and of a piece of a chunk swept again: <= cap, so no list can overflow
+    uint64_t max_chunk;   // most rows of a later chunk
+    bool pool;            // lists kept as pools with a radix select, not as heaps
+    uint32_t slab;        // queries served at a time: their key lists take at most 4 GiB
+};
+KnnBytesPlan knn_bytes_plan(uint64_t n, uint64_t nq, uint32_t d, int k) {
+    KnnBytesPlan pl{};
+    pl.dp = (d + kKnnBytesKStep - 1) / kKnnBytesKStep * kKnnBytesKStep;
+    pl.cap = (uint32_t)(4 * k + 64);
+    pl.first_rows = std::min<uint64_t>(n, pl.cap & ~63u);  // (chunks start on multiples of 64 rows: the sweep reads the row terms in aligned groups of four)
+    pl.max_chunk = 4ull * (uint64_t)g_knob_knn_chunk.load(std::memory_order_relaxed);  // (the knob is a multiple of 64, at least 64)
+    pl.pool = k >= g_knob_knn_pool_min_k.load(std::memory_order_relaxed);
+    pl.slab = (uint32_t)std::min<uint64_t>(nq, std::max<uint64_t>(1024, ((4ull << 30) / ((uint64_t)pl.cap * 8)) & ~(uint64_t)127));
+    return pl;
+}
+}  // namespace
+
+extern "C" {
+
+int gbnns_debug_knn_bytes_plan(uint64_t n, uint64_t n_q, uint32_t d, int k, uint32_t* dp, uint32_t* cap, uint64_t* first_rows,
+                               uint64_t* max_chunk, int* pool) {
+    if (!dp || !cap || !first_rows || !max_chunk || !pool) return fail(GBNNS_ERR_INVALID, "gbnns_debug_knn_bytes_plan: null output");
+    if (n == 0 || n >= (1ull << 32) - 1 || n_q >= (1ull << 31) || d == 0 || d > 256 || k < 1 || k > 4096)
+        return fail(GBNNS_ERR_INVALID, "gbnns_debug_knn_bytes_plan: not a shape gbnns_exact_knn_bytes takes");
+    const KnnBytesPlan pl = knn_bytes_plan(n, n_q, d, k);
+    *dp = pl.dp; *cap = pl.cap; *first_rows = pl.first_rows; *max_chunk = pl.max_chunk; *pool = pl.pool ? 1 : 0;
+    return GBNNS_OK;
+}
+
+int gbnns_exact_knn_bytes(int device, const uint8_t* base, uint64_t n, const uint8_t* queries, uint64_t n_q,
+                          uint32_t d, int k, int metric, int64_t self_offset, uint32_t* out_ids, float* out_dist,
+                          int mem_kind, void* stream) {
+    if (!base || !queries || !out_ids) return fail(GBNNS_ERR_INVALID, "null argument");
+    if (n == 0 || n >= (1ull << 32) - 1) return fail(GBNNS_ERR_INVALID, "n must be in [1, 2^32 - 1)");
+    if (n_q >= (1ull << 31)) return fail(GBNNS_ERR_INVALID, "n_q too large");
+    if (k < 1 || k > (1 << 20)) return fail(GBNNS_ERR_INVALID, "k must be in [1, 2^20]");
+    if (d == 0) return fail(GBNNS_ERR_INVALID, "d must be >= 1");
+    if (metric != GBNNS_METRIC_L2 && metric != GBNNS_METRIC_NEG_DOT) return fail(GBNNS_ERR_INVALID, "unknown metric %d", metric);
+    if (mem_kind != GBNNS_MEM_HOST && mem_kind != GBNNS_MEM_DEVICE) return fail(GBNNS_ERR_INVALID, "unknown mem_kind %d", mem_kind);
+    if (d > 256)
+        return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_exact_knn_bytes: d <= 256 (every sum of the distance must stay an integer below 2^24 to be exact "
+                    "in float32 and on the int8 matrix cores; got %u): widen the rows and call gbnns_exact_knn", d);
+    if (k > 4096) return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_exact_knn_bytes: k <= 4096 (got %d): widen the rows and call gbnns_exact_knn", k);
+    if (metric == GBNNS_METRIC_NEG_DOT && d % 8 != 0)
+        return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_exact_knn_bytes: the negative-dot form needs d %% 8 == 0 (got %u)", d);
+    if (self_offset < -1) return fail(GBNNS_ERR_INVALID, "self_offset must be >= -1");
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+        return fail(GBNNS_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
+    if (device < 0 || device >= count) return fail(GBNNS_ERR_NO_DEVICE, "device %d out of range (%d devices)", device, count);
+    if (n_q == 0) return GBNNS_OK;
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool host = mem_kind == GBNNS_MEM_HOST;
+    const uint32_t nq = (uint32_t)n_q;
+    const KnnBytesPlan pl = knn_bytes_plan(n, n_q, d, k);
+    const uint32_t dp = pl.dp, cap = pl.cap, slab = pl.slab;
+    DevBuf b_dev, q_dev, ids_dev, dist_dev, bpack, bterm, qpack, qterm, thr, cand, cnt, flag, keys, root;
+    struct Release {  // DevBuf has no destructor (index members are released by gbnns_index_destroy)
+        DevBuf* b[14];
+        ~Release() { for (DevBuf* x : b) x->release(); }
+    } release{{&b_dev, &q_dev, &ids_dev, &dist_dev, &bpack, &bterm, &qpack, &qterm, &thr, &cand, &cnt, &flag, &keys, &root}};
+    int rc;
+    const uint8_t* base_d = base;
+    const uint8_t* q_d = queries;
+    uint32_t* ids_d = out_ids;
+    float* dist_d = out_dist;
+    if (host) {  // uploaded as bytes: a quarter of the float call's traffic, and no float copy anywhere
+        if ((rc = b_dev.ensure((size_t)n * d))) return rc;
+        if ((rc = q_dev.ensure((size_t)nq * d))) return rc;
+        if ((rc = ids_dev.ensure((size_t)nq * k * 4))) return rc;
+        if (out_dist && (rc = dist_dev.ensure((size_t)nq * k * 4))) return rc;
+        HIP_TRY(hipMemcpyAsync(b_dev.p, base, (size_t)n * d, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(q_dev.p, queries, (size_t)nq * d, hipMemcpyHostToDevice, s));
+        base_d = b_dev.as<uint8_t>(); q_d = q_dev.as<uint8_t>(); ids_d = ids_dev.as<uint32_t>();
+        dist_d = out_dist ? dist_dev.as<float>() : nullptr;
+    }
+    const size_t heap_stride = ((size_t)slab + 63) & ~(size_t)63;
+    if ((rc = bpack.ensure((size_t)n * dp))) return rc;
+    if ((rc = bterm.ensure(((size_t)n + 64) * 4))) return rc;  // (the sweep reads whole blocks of 32 rows' terms)
+    if ((rc = qpack.ensure((size_t)slab * dp))) return rc;
+    if ((rc = qterm.ensure((size_t)slab * 4))) return rc;
+    if ((rc = thr.ensure((size_t)slab * 4))) return rc;
+    if ((rc = cand.ensure((size_t)slab * cap * 8))) return rc;
+    if ((rc = cnt.ensure((size_t)slab * 4))) return rc;
+    if ((rc = flag.ensure(4))) return rc;
+    if ((rc = keys.ensure(pl.pool ? (size_t)slab * (size_t)k * 8 : heap_stride * (size_t)k * 8))) return rc;
+    if (pl.pool && (rc = root.ensure((size_t)slab * 8))) return rc;
+    HIP_TRY(hipMemsetAsync(bterm.as<int32_t>() + n, 0, 64 * 4, s));
+    HIP_TRY(launch_knn_bytes_pack(base_d, d, dp, metric, 0, n, bpack.as<int8_t>(), bterm.as<int32_t>(), s));
+    for (uint32_t q0 = 0; q0 < nq; q0 += slab) {
+        const uint32_t qn = std::min(slab, nq - q0);
+        KnnBytesOfferParams op{};
+        op.cand = cand.as<uint64_t>(); op.count = cnt.as<uint32_t>(); op.cap = cap; op.nq = qn; op.k = k;
+        op.self_offset = self_offset >= 0 ? self_offset + (int64_t)q0 : -1;
+        op.qterm = qterm.as<int32_t>(); op.thr = thr.as<int32_t>();
+        if (pl.pool) { op.pool = keys.as<uint64_t>(); op.root = root.as<uint64_t>(); }
+        else { op.heap = keys.as<uint64_t>(); op.heap_stride = heap_stride; }
+        HIP_TRY(launch_knn_bytes_pack(q_d + (size_t)q0 * d, d, dp, metric, 1, qn, qpack.as<int8_t>(), qterm.as<int32_t>(), s));
+        HIP_TRY(hipMemsetAsync(keys.p, 0xFF, pl.pool ? (size_t)qn * (size_t)k * 8 : heap_stride * (size_t)k * 8, s));
+        if (pl.pool) HIP_TRY(hipMemsetAsync(root.p, 0xFF, (size_t)qn * 8, s));
+        HIP_TRY(launch_fill_u32(thr.as<uint32_t>(), 0x80000000u, qn, s));  // INT32_MIN: every row passes
+        uint32_t h_flag = 0;
+        auto sweep_rows = [&](uint64_t r0, uint32_t rows) -> int {
+            HIP_TRY(hipMemsetAsync(cnt.p, 0, (size_t)qn * 4, s));
+            HIP_TRY(hipMemsetAsync(flag.p, 0, 4, s));
+            KnnBytesSweepParams f{};
+            f.qpack = qpack.as<int8_t>(); f.bpack = bpack.as<int8_t>() + (size_t)r0 * dp; f.bterm = bterm.as<int32_t>() + r0;
+            f.qterm = qterm.as<int32_t>(); f.thr = thr.as<int32_t>(); f.nq = qn; f.dp = dp; f.rows = rows; f.row0 = (uint32_t)r0; f.cap = cap;
+            f.shift = metric == GBNNS_METRIC_L2 ? 1 : 0;
+            f.cand = cand.as<uint64_t>(); f.count = cnt.as<uint32_t>(); f.overflow = flag.as<uint32_t>();
+            HIP_TRY(launch_knn_bytes_sweep(f, s));
+            return GBNNS_OK;
+        };
+        // the first chunk cannot overflow a list; a later one is at most as long as everything before it -- a query is then
+        // expected to keep about k rows of it, whatever the chunk -- and at most max_chunk rows
+        for (uint64_t r0 = 0, chunk = 0; r0 < n; r0 += chunk) {
+            chunk = r0 == 0 ? pl.first_rows : std::min<uint64_t>(pl.max_chunk, r0);
+            const uint32_t rows = (uint32_t)std::min<uint64_t>(chunk, n - r0);
+            if ((rc = sweep_rows(r0, rows))) return rc;
+            if (r0 != 0) {
+                HIP_TRY(hipMemcpyAsync(&h_flag, flag.p, 4, hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+            }
+            if (r0 == 0 || !h_flag) {
+                HIP_TRY(launch_knn_bytes_offer(op, s));
+                continue;
+            }
+            // some query kept more rows of this chunk than its list holds (rows in an adversarial order, a mass of ties at the
+            // threshold): nothing of the chunk has been offered yet; the chunk again in pieces that cannot overflow
+            for (uint64_t r1 = r0; r1 < r0 + rows; r1 += pl.first_rows) {
+                if ((rc = sweep_rows(r1, (uint32_t)std::min<uint64_t>(pl.first_rows, r0 + rows - r1)))) return rc;
+                HIP_TRY(launch_knn_bytes_offer(op, s));
+            }
+        }
+        if (pl.pool) {
+            KnnPoolParams pp{};
+            pp.k.nq = qn; pp.k.k = k; pp.k.out_ids = ids_d + (size_t)q0 * k; pp.k.out_dist = dist_d ? dist_d + (size_t)q0 * k : nullptr;
+            pp.pool = keys.as<uint64_t>();
+            HIP_TRY(launch_knn_pool_finalize(pp, s));
+        } else {
+            KnnParams kp{};
+            kp.nq = qn; kp.k = k; kp.heap = keys.as<uint64_t>(); kp.heap_stride = heap_stride;
+            kp.out_ids = ids_d + (size_t)q0 * k; kp.out_dist = dist_d ? dist_d + (size_t)q0 * k : nullptr;
+            HIP_TRY(launch_knn_finalize(kp, s));
+        }
+    }
+    if (host) {
+        HIP_TRY(hipMemcpyAsync(out_ids, ids_d, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
+        if (out_dist) HIP_TRY(hipMemcpyAsync(out_dist, dist_d, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
     }
     // the temporaries are released below: wait for the work that uses them
     HIP_TRY(hipStreamSynchronize(s));

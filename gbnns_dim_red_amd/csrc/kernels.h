@@ -315,6 +315,50 @@ hipError_t launch_knn_pool_update(const KnnPoolParams& p, hipStream_t s);
 hipError_t launch_knn_pool_finalize(const KnnPoolParams& p, hipStream_t s);   // ascending order + outputs
 constexpr float kKnnFilterSlack = 1.0f / 4096.0f;  // c: |approximate - reference distance| <= c (|q|^2 + |x|^2) with room to spare (knn.hip)
 
+// Exact kNN over uint8 rows on the int8 matrix cores (knn_bytes.hip; d <= 256: every distance is an integer below 2^24, so
+// the int32 result of v_mfma_i32_32x32x32_i8 IS the reference's float distance).  Rows are packed as signed bytes x - 128,
+// dp = d rounded up to the K step of 32 with signed zeros, row-major: the operand fragment of lane (row, half) at K step s
+// is the 16 bytes at 32 s + 16 half.  Per row one int32 term that folds its norm (L2) or its sum (negative dot):
+//   base row x:  bterm = -|x'|^2          (L2)    128 sum(x')                   (NEG_DOT)
+//   query q:     qterm =  |q'|^2          (L2)   -128 sum(q') - 16384 d         (NEG_DOT)
+// and with s = (x'.q' << shift) + bterm (shift 1 for L2, 0 for NEG_DOT) the exact distance is  qterm - s.
+constexpr uint32_t kKnnBytesKStep = 32;    // K of one v_mfma_i32_32x32x32_i8
+constexpr uint32_t kKnnBytesRowBlock = 32; // base rows of one product
+hipError_t launch_knn_bytes_pack(const uint8_t* x, uint32_t dim, uint32_t dp, int metric, int query_side, uint64_t rows, int8_t* packed,
+                                 int32_t* term, hipStream_t s);
+struct KnnBytesSweepParams {
+    const int8_t* qpack;     // [nq x dp]
+    const int8_t* bpack;     // [rows x dp] packed base rows of this chunk (the chunk starts on a multiple of 4 rows)
+    const int32_t* bterm;    // [rows rounded up to 32] the chunk's row terms (readable, any value, beyond the set)
+    const int32_t* qterm;    // [nq]
+    const int32_t* thr;      // [nq] qterm - T_q: a row is kept when s >= thr, i.e. distance <= T_q (INT32_MIN: everything passes)
+    uint32_t nq, dp;
+    uint32_t rows;           // rows of the chunk
+    uint32_t row0;           // id of the chunk's first row
+    uint32_t cap;            // key slots per query
+    int32_t shift;           // 1 = L2, 0 = NEG_DOT
+    uint64_t* cand;          // [nq x cap] keys (knn_fkey(float(distance)) << 32 | id) of the rows kept
+    uint32_t* count;         // [nq] how many were kept (may exceed cap: then *overflow is set and the chunk is swept again in pieces)
+    uint32_t* overflow;      // [1]
+};
+hipError_t launch_knn_bytes_sweep(const KnnBytesSweepParams& p, hipStream_t s);
+// the kept keys offered to a query's heap (pool == nullptr; [k x heap_stride]) or pool ([nq x k] + root [nq]); then the new thresholds
+struct KnnBytesOfferParams {
+    uint64_t* heap;
+    size_t heap_stride;
+    uint64_t* pool;
+    uint64_t* root;
+    const uint64_t* cand;
+    const uint32_t* count;
+    uint32_t cap;
+    uint32_t nq;
+    int32_t k;
+    int64_t self_offset;     // >= 0: query i is base row i + self_offset and is not its own neighbour; -1: off
+    const int32_t* qterm;
+    int32_t* thr;
+};
+hipError_t launch_knn_bytes_offer(const KnnBytesOfferParams& p, hipStream_t s);
+
 // GD pruning of a kNN graph, one node per wavefront (support_func.h:521-563).  deg[i] = 0xFFFFFFFF marks a node
 // left to the host (equal distances in its list, list longer than 1024, id out of range).
 struct GdParams {

@@ -472,10 +472,10 @@ int gbnns_profile_enable(gbnns_index* index, int on);
  * shape and residency (576-byte rows with at least five wavefronts per CU, 192-byte rows at ef <= 64: after; GBNNS_LATE_ROWS).
  * "hot": 0 = the first pass takes the generic register-list / two-list instances also where the plan has a hand-laid-out walk_hot* or
  * walk_reg_wide instance (default 1; GBNNS_HOT) -- the family the tag instances of gbnns_search_tagged are built from, untagged, for A/B runs.
- * "knn_chunk": most base rows per filtered chunk of gbnns_exact_knn (default 32 768; the pool path takes four times that;
- * GBNNS_KNN_CHUNK).
- * "knn_pool_min_k": shortest list gbnns_exact_knn's filter path keeps as an unordered pool with a radix select (one
- * wavefront per query) instead of a binary heap (default 64; GBNNS_KNN_POOL_MIN_K).
+ * "knn_chunk": most base rows per filtered chunk of gbnns_exact_knn (default 32 768; the pool path, and every chunk of
+ * gbnns_exact_knn_bytes, takes four times that; GBNNS_KNN_CHUNK).
+ * "knn_pool_min_k": shortest list gbnns_exact_knn's filter path and gbnns_exact_knn_bytes keep as an unordered pool with a
+ * radix select (one wavefront per query) instead of a binary heap (default 64; GBNNS_KNN_POOL_MIN_K).
  * "knn_filter": gbnns_exact_knn's matrix-core filter -- 0 never, 1 by size (default), 2 whenever the shape allows
  * (GBNNS_KNN_FILTER). */
 int gbnns_debug_knob(const char* name, int value);
@@ -556,6 +556,29 @@ int gbnns_build_graph_gd_device(int device, const uint64_t* knn_offsets, const u
 int gbnns_exact_knn(int device, const float* base, uint64_t n, const float* queries, uint64_t n_q,
                     uint32_t d, int k, int metric, int64_t self_offset, uint32_t* out_ids, float* out_dist,
                     int mem_kind, void* stream);
+
+/* gbnns_exact_knn over uint8 rows (SIFT / BIGANN .bvecs tables: the ground truth and the kNN lists a byte index needs), without a float
+ * copy of anything: the result -- ids, and the bit patterns of out_dist -- is that of
+ * gbnns_exact_knn(float(base), float(queries), ...), argument for argument (rows dense, d bytes each; L2 over the first 4 floor(d / 4)
+ * dimensions; GBNNS_METRIC_NEG_DOT needs d % 8 == 0).  For bytes and d <= 256 every intermediate of the reference's distance is an integer
+ * below 2^24 (sums <= 256 * 255^2 = 16 646 400), so its float arithmetic is exact in any order and the int32 result of the int8 matrix
+ * cores (v_mfma_i32_32x32x32_i8 on x - 128) is that distance itself: one matrix product per pair, no error bound, nothing to rescore.
+ * One scheme for every shape: the rows in chunks, a query's rows at or below its current k-th distance appended as keys, the keys offered
+ * to a heap (k < "knn_pool_min_k") or an unordered pool with a radix select; a chunk that overflows a query's key list is swept again in
+ * pieces that cannot.  GBNNS_ERR_UNSUPPORTED: d > 256 (the 2^24 bound), k > 4096 -- widen the rows and call gbnns_exact_knn.  No CPU path.
+ * Device workspace for the duration of the call, dp = d rounded up to 32, cap = 4 k + 64, slab = min(n_q, max(1024, 2^32 / (8 cap))):
+ * n dp + 4 (n + 64) bytes of packed rows and row terms, and slab (dp + 8 cap + 8 k + 20) bytes of packed queries, key lists and
+ * heaps / pools; HOST buffers add n d + n_q d bytes of uploaded rows and 4 (or 8) n_q k bytes of results. */
+int gbnns_exact_knn_bytes(int device, const uint8_t* base, uint64_t n, const uint8_t* queries, uint64_t n_q,
+                          uint32_t d, int k, int metric, int64_t self_offset, uint32_t* out_ids, float* out_dist,
+                          int mem_kind, void* stream);
+/* Diagnostic, no device needed: what gbnns_exact_knn_bytes does with a shape under the current "knn_chunk" / "knn_pool_min_k" knobs --
+ * the padded row bytes (*dp, a multiple of the K step 32), a query's key slots per chunk (*cap), the rows of the first chunk, swept with
+ * thresholds at "everything passes" (*first_rows <= *cap; also the piece length when a chunk is swept again), the most rows of a later
+ * chunk (*max_chunk = 4 "knn_chunk"; a chunk is never longer than everything before it) and whether lists are pools (*pool).
+ * GBNNS_ERR_INVALID for a shape the call refuses. */
+int gbnns_debug_knn_bytes_plan(uint64_t n, uint64_t n_q, uint32_t d, int k,
+                               uint32_t* dp, uint32_t* cap, uint64_t* first_rows, uint64_t* max_chunk, int* pool);
 
 /* ---- several devices of one node: query-sharded replicas ----------------------------------------------------
  * The reference's only parallelism on this path is `#pragma omp parallel for` over the queries of a batch
