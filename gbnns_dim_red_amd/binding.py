@@ -41,6 +41,7 @@ SYMBOLS = [
     "gbnns_index_set_tags", "gbnns_search_tagged", "gbnns_debug_tag_plan", "gbnns_debug_bridge_plan",
     "gbnns_index_create_bytes", "gbnns_index_is_bytes", "gbnns_debug_byte_plan", "gbnns_debug_byte_walk_plan",
     "gbnns_exact_knn_bytes", "gbnns_debug_knn_bytes_plan",
+    "gbnns_search_byte_queries", "gbnns_debug_byte_query_plan",
 ]
 
 
@@ -178,6 +179,8 @@ def load_library():
     lib.gbnns_index_is_bytes.argtypes = [C.c_void_p]
     lib.gbnns_debug_byte_walk_plan.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int,
                                               C.c_char_p, C.c_uint32, C.POINTER(C.c_uint64)]
+    lib.gbnns_debug_byte_query_plan.argtypes = lib.gbnns_debug_byte_walk_plan.argtypes
+    lib.gbnns_search_byte_queries.argtypes = [C.c_void_p, C.POINTER(_SearchArgs), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.gbnns_debug_byte_plan.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int,
                                           C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(C.c_int)]
     lib.gbnns_index_d_low.argtypes = [C.c_void_p]
@@ -287,6 +290,17 @@ def byte_walk_plan(metric, dim, n, ell_stride, ef, aux_stride=0, n_entries=1, wi
     lds = C.c_uint64(0)
     _check(load_library().gbnns_debug_byte_walk_plan(metric, dim, n, ell_stride, aux_stride, ef, n_entries, int(wide), int(tagged), name, 128,
                                                      C.byref(lds)))
+    return name.value.decode()
+
+
+def byte_query_plan(metric, dim, n, ell_stride, ef, aux_stride=0, n_entries=1, wide=False, tagged=False):
+    """gbnns_debug_byte_query_plan (no device needed): byte_walk_plan for a call whose queries are uint8 too (Index.search(queries=<uint8>)) with
+    the knob "byte_query_int" = 7 -- an integer instance ("beam_u8_kernel<...>" / "beam_u8_big_kernel<...>") inside the byte-walk first pass's
+    domain, "walk_general_kernel" outside it."""
+    name = C.create_string_buffer(128)
+    lds = C.c_uint64(0)
+    _check(load_library().gbnns_debug_byte_query_plan(metric, dim, n, ell_stride, aux_stride, ef, n_entries, int(wide), int(tagged), name, 128,
+                                                      C.byref(lds)))
     return name.value.decode()
 
 
@@ -651,13 +665,19 @@ class Index:
         candidates in ascending (original-space distance, pop index); top_ids[:, 0] == ids.
         query_tags [nq] (uint32 numpy / int32 torch, like entry_ids): gbnns_search_tagged -- query i walks only the rows j with
         (tags[j] & query_tags[i]) != 0 (set_tags), i.e. the graph cut_graph gives; combines with top_k.  With flags=FLAG_TAG_BRIDGE a disallowed neighbour is looked
-        through instead of dropped: the graph bridge_graph gives."""
+        through instead of dropped: the graph bridge_graph gives.
+        uint8 queries (numpy uint8 / torch.uint8) on a byte handle (Index(db=<uint8>)): gbnns_search_byte_queries -- every result is, bit for
+        bit, that of the same call with queries.astype(float32); same keywords.  On a float handle they raise TypeError (exact_knn's mixed-pair
+        rule)."""
         top_k = top_k or 0
+        u8 = _is_u8(queries)
+        if u8 and not self.is_bytes:
+            raise TypeError("uint8 queries need a byte handle (Index(db=<uint8>)); widen them for a float handle")
         if aux:
             flags |= FLAG_AUX_GRAPH | (FLAG_LLF if llf else 0)
         dev = _is_dev(queries) and queries.is_cuda
         pinned = _is_dev(queries) and not queries.is_cuda
-        queries = _prep(queries, np.float32, "float32")
+        queries = _prep(queries, np.uint8, "uint8") if u8 else _prep(queries, np.float32, "float32")
         queries_low = _prep(queries_low, np.float32, "float32")
         nq = int(queries.shape[0])
         if queries.shape[1] != self.d:
@@ -710,7 +730,7 @@ class Index:
         ids = alloc("ids", (nq,), i32 if (dev or pinned) else np.uint32)
         a = _SearchArgs(struct_size=C.sizeof(_SearchArgs), mode=mode, ef=ef, k=kk,
                         mem_kind=MEM_DEVICE if dev else MEM_HOST, hash_capacity=hash_capacity,
-                        n_q=nq, queries=_ptr(queries), queries_low=_ptr(queries_low),
+                        n_q=nq, queries=None if u8 else _ptr(queries), queries_low=_ptr(queries_low),
                         entry_ids=_ptr(entry_ids), out_ids=_ptr(ids), stream=sptr, flags=flags,
                         hops_bound=hops_bound if aux else 0, n_entries=n_entries, defer_depth=defer_depth)
         if "hops" in want:
@@ -730,6 +750,10 @@ class Index:
         if top_k > 0:
             top_ids = alloc("top_ids", (nq, top_k), i32 if (dev or pinned) else np.uint32)
             top_dist = alloc("top_dist", (nq, top_k), f32)
+        if u8:
+            tk = (top_k, _ptr(top_ids), _ptr(top_dist)) if top_k > 0 else (0, None, None)
+            _check(self._lib.gbnns_search_byte_queries(self._h, C.byref(a), _ptr(queries), _ptr(query_tags), *tk))
+        elif top_k > 0:
             if query_tags is not None:
                 _check(self._lib.gbnns_search_tagged(self._h, C.byref(a), _ptr(query_tags), top_k, _ptr(top_ids), _ptr(top_dist)))
             else:

@@ -124,6 +124,7 @@ struct Lane {
     DevBuf g_bitmap, g_keys, fp_bitmap, order, order_hist;
     DevBuf top_ids, top_dist;          // the k-answer rows of a HOST call (gbnns_rerank_topk / gbnns_search_topk)
     DevBuf qtags;                      // the query tag words of a HOST call (gbnns_search_tagged)
+    DevBuf q_in_b;                     // the byte queries of a HOST call (gbnns_search_byte_queries; their widening goes to q_in)
     // visited-set sizing feedback: stats of an earlier call arrive asynchronously in pinned memory
     uint32_t* h_stats = nullptr;       // [4] copy of ctrl after the walk kernels
     hipEvent_t stats_ev = nullptr;
@@ -142,7 +143,7 @@ struct Lane {
     int stage_next = 0;
     DevBuf* bufs(int i) {
         DevBuf* b[] = {&q_in, &q_low, &h1, &h2, &cand, &cand_dist, &cnt, &hops, &dc, &edges, &out, &entries,
-                       &ovf_list, &ovf2_list, &ctrl, &g_bitmap, &g_keys, &fp_bitmap, &order, &order_hist, &top_ids, &top_dist, &qtags};
+                       &ovf_list, &ovf2_list, &ctrl, &g_bitmap, &g_keys, &fp_bitmap, &order, &order_hist, &top_ids, &top_dist, &qtags, &q_in_b};
         return i < (int)(sizeof b / sizeof b[0]) ? b[i] : nullptr;
     }
 };
@@ -152,7 +153,7 @@ struct Lane {
 // starts from, so a test or an A/B run that flips one no longer changes every other handle of the process.  The three knobs of
 // gbnns_exact_knn -- a function without a handle -- stay process-wide.
 struct Knobs {
-    int quotient, vs_disp, max_waves, spec_min_nq, spec_any_form, mlp_small, mlp_net, mlp_slab, late_rows, spec_tail, coop, hot;
+    int quotient, vs_disp, max_waves, spec_min_nq, spec_any_form, mlp_small, mlp_net, mlp_slab, late_rows, spec_tail, coop, hot, byte_query_int;
 };
 Knobs knob_defaults();                                    // the process-wide defaults as they stand now
 bool knob_set(Knobs& k, const char* name, int value);     // clamps like the environment does; false = no such handle knob
@@ -278,12 +279,13 @@ struct TagIn {
     bool bridge;  // GBNNS_FLAG_TAG_BRIDGE: disallowed neighbours are looked through
 };
 
-// lanes.cpp: the body of gbnns_search_ex / gbnns_search_topk / gbnns_search_tagged (topk == nullptr: no k-answer rows; tag == nullptr: untagged)
-int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk, const TagIn* tag = nullptr);
+// lanes.cpp: the body of gbnns_search_ex / gbnns_search_topk / gbnns_search_tagged / gbnns_search_byte_queries (topk == nullptr: no k-answer rows;
+// tag == nullptr: untagged; q_u8 != nullptr: the queries as bytes, a->queries is nullptr)
+int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk, const TagIn* tag = nullptr, const uint8_t* q_u8 = nullptr);
 
 // search_core.cpp
 int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_t s, bool sync_host, const TopkOut* topk = nullptr,
-                const TagIn* tag = nullptr);
+                const TagIn* tag = nullptr, const uint8_t* q_u8 = nullptr);
 
 
 // How one call is laid out over the handle's lanes (workspace + internal stream each).

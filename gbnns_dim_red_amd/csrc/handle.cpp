@@ -264,6 +264,9 @@ int build_ell(const uint64_t* off, const uint32_t* nbr, uint64_t n, std::vector<
 //                   requested before the visited test, 1 = after it (GBNNS_LATE_ROWS)
 //   "spec_tail"     largest partial last round of a lone launch, in percent of the device's wavefront slots, whose wavefronts request
 //                   their rows before the visited test (0 = off)
+//   "byte_query_int" gbnns_search_byte_queries: the beam classes whose byte-walk first pass is the integer instance (walk_bytes_q.hip) -- a mask,
+//                   bit 0 = one list register (ef <= 64), bit 1 = two (ef <= 128), bit 2 = the two-list kernel (ef <= 1 024); 0 = never: the call
+//                   is served by walk_bytes.hip on the widened queries (A/B runs; GBNNS_BYTE_QUERY_INT).  Default: kByteQueryIntDefault
 //   "coop"          the two-wavefront walk for small batches (walk_coop.hip): -1 = where it serves and the batch leaves the room
 //                   (default), 0 = never, 1 = wherever the shape allows (tests, A/B runs; GBNNS_COOP)
 // Process-wide only (gbnns_exact_knn has no handle):
@@ -273,6 +276,9 @@ int build_ell(const uint64_t* off, const uint32_t* nbr, uint64_t n, std::vector<
 //   "knn_pool_min_k" shortest list gbnns_exact_knn keeps as an unordered pool (one wavefront per query and chunk) instead of a heap
 //                    (measured on 10^6 x 32: k = 48 0.327 against 0.333 s, k = 100 0.425 against 0.536 s, k = 1 000 2.4 against 7.6 s)
 //   "knn_filter"     0 = gbnns_exact_knn without the matrix-core filter (GBNNS_KNN_FILTER; tests compare the two paths)
+// The classes where the integer first pass measured faster than the float byte walk plus the widening kernel by more than the baseline's
+// run-to-run spread (profiles/byte_query_timing.txt)
+constexpr int kByteQueryIntDefault = 7;
 int knob_env(const char* name, int dflt) {
     const char* v = getenv(name);
     return v ? atoi(v) : dflt;
@@ -290,6 +296,7 @@ bool knob_set(Knobs& k, const char* name, int value) {
     else if (!std::strcmp(name, "spec_tail")) k.spec_tail = std::max(0, std::min(100, value));
     else if (!std::strcmp(name, "coop")) k.coop = std::max(-1, std::min(1, value));
     else if (!std::strcmp(name, "hot")) k.hot = value != 0;
+    else if (!std::strcmp(name, "byte_query_int")) k.byte_query_int = std::max(0, std::min(7, value));
     else return false;
     return true;
 }
@@ -309,6 +316,7 @@ static Knobs& knob_default_ref() {  // (function-local: initialised on first use
         knob_set(k, "spec_tail", knob_env("GBNNS_SPEC_TAIL", 50));
         knob_set(k, "coop", knob_env("GBNNS_COOP", -1));
         knob_set(k, "hot", knob_env("GBNNS_HOT", 1));
+        knob_set(k, "byte_query_int", knob_env("GBNNS_BYTE_QUERY_INT", kByteQueryIntDefault));
         return k;
     }();
     return d;
@@ -484,10 +492,9 @@ static int index_create(const gbnns_index_desc* desc, const uint8_t* db_bytes, b
                     }
             }
             rc = ix->net.ensure(packed.size() * 4);
-            if (!rc) {
-                hipError_t e = hipMemcpy(ix->net.p, packed.data(), packed.size() * 4, hipMemcpyHostToDevice);
-                if (e != hipSuccess) rc = fail(GBNNS_ERR_HIP, "net upload: %s", hipGetErrorString(e));
-            }
+            // (through the staging buffer like every other upload of a pageable array here -- `packed` is one, and a plain hipMemcpy from it
+            // is the copy h2d_staged exists to avoid: "net upload: an illegal memory access" turned up once in a full test-suite run)
+            if (!rc) rc = h2d_staged(ix->net.p, packed.data(), packed.size() * 4);
             float* base = ix->net.as<float>();
             ix->w1 = base;
             ix->b1 = ix->w1 + (size_t)dh * ix->ws1;
@@ -846,6 +853,25 @@ int gbnns_debug_byte_walk_plan(int metric, uint32_t dim, uint64_t n, uint32_t el
     return GBNNS_OK;
 }
 
+int gbnns_debug_byte_query_plan(int metric, uint32_t dim, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries, int force_wide,
+                                int tagged, char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
+    if (!name || name_bytes == 0 || !lds_bytes) return fail(GBNNS_ERR_INVALID, "gbnns_debug_byte_query_plan: null output");
+    if ((metric != GBNNS_METRIC_L2 && metric != GBNNS_METRIC_NEG_DOT) || dim == 0 || n == 0 || n > 0xFFFFFFFFull || ell_stride == 0 || ell_stride % 16 ||
+        aux_stride % 16 || ef < 1 || n_entries > 4096)
+        return fail(GBNNS_ERR_INVALID, "gbnns_debug_byte_query_plan: not the shape of an index or a search");
+    WalkParams w{};
+    w.dim = dim; w.dstride = round_up(dim, 16); w.n = (uint32_t)n; w.ell_stride = ell_stride; w.ef = ef; w.n_entries = n_entries ? n_entries : 1u;
+    w.aux_ell = aux_stride ? &w.aux_stride : nullptr; w.aux_stride = aux_stride;  // (the plan asks only WHETHER there is an auxiliary graph)
+    w.force_wide = force_wide != 0; w.tagged = tagged != 0; w.walk_bytes = 1;
+    w.q_b = reinterpret_cast<const uint8_t*>(&w); w.bq_classes = 7u;  // (... and whether the call brought byte queries; every beam class: knob "byte_query_int" = 7)
+    const WalkPlan plan = plan_walk(w, metric, WalkPass::First);
+    const char* planned = plan.general_only ? "walk_general_kernel" : walk_plan_name(plan);
+    if (!planned) return fail(GBNNS_ERR_INTERNAL, "gbnns_debug_byte_query_plan: no kernel instance for the plan");
+    std::snprintf(name, name_bytes, "%s", planned);
+    *lds_bytes = plan.general_only ? (uint64_t)w.dstride * 4u : plan.lds_fixed;  // (the general kernel: the staged query alone)
+    return GBNNS_OK;
+}
+
 static int debug_tag_plan(const char* fn, int bridged, int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries,
                          int force_wide, uint32_t rr_reserve, char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
     if (!name || name_bytes == 0 || !lds_bytes) return fail(GBNNS_ERR_INVALID, "%s: null output", fn);
@@ -1024,7 +1050,7 @@ int gbnns_index_knob_get(gbnns_index* ix, const char* name, int* out) {
     const struct { const char* n; int v; } all[] = {
         {"quotient", k.quotient}, {"vs_disp", k.vs_disp}, {"max_waves", k.max_waves}, {"spec_min_nq", k.spec_min_nq},
         {"spec_any_form", k.spec_any_form}, {"mlp_small", k.mlp_small}, {"mlp_net", k.mlp_net}, {"mlp_slab", k.mlp_slab},
-        {"late_rows", k.late_rows}, {"spec_tail", k.spec_tail}, {"coop", k.coop}, {"hot", k.hot}, {"mlp_net_form", ix->net_form}};
+        {"late_rows", k.late_rows}, {"spec_tail", k.spec_tail}, {"coop", k.coop}, {"hot", k.hot}, {"byte_query_int", k.byte_query_int}, {"mlp_net_form", ix->net_form}};
     for (const auto& e : all)
         if (!std::strcmp(name, e.n)) { *out = e.v; return GBNNS_OK; }
     return fail(GBNNS_ERR_INVALID, "gbnns_index_knob_get: unknown handle knob '%s'", name);

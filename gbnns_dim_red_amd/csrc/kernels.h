@@ -111,7 +111,14 @@ struct WalkParams {
     // float32(db_b), operation for operation; no float copy of the table exists.
     const uint8_t* db_b;     // [n x dstride] walked byte rows, 16-byte aligned, or nullptr
     int32_t walk_bytes;      // 1: the first pass takes a byte-walk instance (walk_bytes.hip) or the general kernel's the whole batch (walk_plan.cpp)
+    // gbnns_search_byte_queries (last again): the call brought its queries as uint8 -- `q` above is their float32 widening (widen.hip), which
+    // every kernel reads but the integer byte-walk instances (walk_bytes_q.hip): those read the bytes themselves and compute the distance in
+    // uint32, which for d <= 256 is the float walk's value exactly.
+    uint32_t bq_classes;     // beam classes whose byte-walk first pass takes the integer instance: bit 0 one list register, bit 1 two, bit 2 the two-list kernel (in the struct's former tail padding)
+    const uint8_t* q_b;      // [nq x dim] the queries as bytes, rows 16-byte aligned, or nullptr
 };
+// uint8 -> float32, `count` values (every byte value is a binary32 value: nothing is rounded)
+hipError_t launch_widen_u8(const uint8_t* src, float* dst, size_t count, hipStream_t s);
 
 // `form` of a visited set: 0 = 4-byte slots, 1 = five 24-bit ids per 16-byte bucket, 2 = quotient form (seven 16-bit entries)
 size_t walk_hash_bytes(uint32_t entries, int form);             // LDS bytes of a visited set of `entries` ids

@@ -70,7 +70,7 @@ int flush_joins(gbnns_index* ix, size_t keep) {
 int flush_join(gbnns_index* ix) { return flush_joins(ix, 0); }
 
 // One search call: validation, the layout over the lanes, the batch (search_core).  `topk`: gbnns_search_topk's extra outputs.
-int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk, const TagIn* tag) {
+int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk, const TagIn* tag, const uint8_t* q_u8) {
     if (!ix || !a) return fail(GBNNS_ERR_INVALID, "null argument");
     if (a->struct_size != sizeof(gbnns_search_args))
         return fail(GBNNS_ERR_INVALID, "gbnns_search_args.struct_size mismatch (%u != %zu)",
@@ -81,7 +81,7 @@ int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk
         return fail(GBNNS_ERR_INVALID, "unknown mem_kind %d", a->mem_kind);
     if (a->n_q == 0) return GBNNS_OK;
     if (a->n_q >= (1ull << 31)) return fail(GBNNS_ERR_INVALID, "n_q too large");
-    if (!a->queries || !a->out_ids) return fail(GBNNS_ERR_INVALID, "queries / out_ids missing");
+    if ((!a->queries && !q_u8) || !a->out_ids) return fail(GBNNS_ERR_INVALID, "queries / out_ids missing");
     if (a->mode == GBNNS_MODE_NET && !ix->has_net) return fail(GBNNS_ERR_INVALID, "NET mode needs a net");
     if (a->mode != GBNNS_MODE_PLAIN && !ix->db_low) return fail(GBNNS_ERR_INVALID, "mode needs db_low");
     if (a->mode == GBNNS_MODE_PLAIN && ix->db_b && !(a->flags & GBNNS_FLAG_BYTE_WALK))
@@ -139,14 +139,14 @@ int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk
             {a->out_dist_calc, nq * 4}, {a->out_edges, nq * 4}, {a->out_cand, nq * kk * 4}, {a->out_cand_dist, nq * kk * 4},
             {a->out_q_low, nq * ix->d_low * 4},
             {topk ? topk->ids : nullptr, nq * (topk ? (size_t)topk->k : 0) * 4}, {topk ? topk->dist : nullptr, nq * (topk ? (size_t)topk->k : 0) * 4},
-            {tag ? tag->qtags : nullptr, nq * 4}};
+            {tag ? tag->qtags : nullptr, nq * 4}, {q_u8, nq * ix->d}};
         for (const auto& b : bufs)
             if (b.p && !pinned_alias(static_cast<const char*>(b.p), b.bytes)) n_lanes = 1;
         if (n_lanes == 1) ix->next_lane = lane;  // (the rotation did not advance)
     }
     if (n_lanes <= 1) {
         if ((rc = enter_stream(ix, s))) return rc;
-        return search_core(ix, ix->lanes[0], a, s, true, topk, tag);
+        return search_core(ix, ix->lanes[0], a, s, true, topk, tag, q_u8);
     }
 
     // ---- deferred join: the batch runs on lane `lane`'s internal stream ---------------------------------------
@@ -169,7 +169,7 @@ int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk
     ix->in_flight = true;
     HIP_TRY(hipStreamWaitEvent(L.stream, ix->fork_ev, 0));
     g_slow.mark("fork");
-    if ((rc = search_core(ix, L, a, L.stream, false, topk, tag))) {
+    if ((rc = search_core(ix, L, a, L.stream, false, topk, tag, q_u8))) {
         (void)hipDeviceSynchronize();  // leave nothing in flight behind an error
         ix->in_flight = false;
         return rc;
@@ -202,6 +202,22 @@ int gbnns_search_tagged(gbnns_index* ix, const gbnns_search_args* a, const uint3
     if (k == 0 && !out_top_ids && !out_top_dist) return search_call(ix, a, nullptr, &g);
     const TopkOut t{k, out_top_ids, out_top_dist};  // (k outside 1 .. ef, PLAIN mode, no out_top_ids: refused as for gbnns_search_topk)
     return search_call(ix, a, &t, &g);
+}
+
+int gbnns_search_byte_queries(gbnns_index* ix, const gbnns_search_args* a, const uint8_t* queries_u8, const uint32_t* query_tags, int k, uint32_t* out_top_ids,
+                              float* out_top_dist) {
+    if (!a) return fail(GBNNS_ERR_INVALID, "null argument");
+    const bool sized = a->struct_size == sizeof(gbnns_search_args);  // (a mismatch: search_call's refusal)
+    if (sized && a->queries) return fail(GBNNS_ERR_INVALID, "gbnns_search_byte_queries: args->queries must be NULL (the queries are queries_u8)");
+    if (!ix) return fail(GBNNS_ERR_INVALID, "null argument");
+    if (!ix->db_b) return fail(GBNNS_ERR_INVALID, "gbnns_search_byte_queries needs a byte handle (gbnns_index_create_bytes)");
+    if (sized && !queries_u8 && a->n_q) return fail(GBNNS_ERR_INVALID, "gbnns_search_byte_queries: queries_u8 missing");
+    // the corresponding float call: gbnns_search_tagged with query_tags, else gbnns_search_topk with k-answer rows, else gbnns_search_ex
+    const TagIn g{query_tags, (a->flags & GBNNS_FLAG_TAG_BRIDGE) != 0};
+    const TagIn* gp = query_tags ? &g : nullptr;
+    if (k == 0 && !out_top_ids && !out_top_dist) return search_call(ix, a, nullptr, gp, queries_u8);
+    const TopkOut t{k, out_top_ids, out_top_dist};
+    return search_call(ix, a, &t, gp, queries_u8);
 }
 
 int gbnns_index_wait(gbnns_index* ix, uint32_t keep) {

@@ -68,5 +68,7 @@ const WalkEntry* walk_tag_entry(const WalkInstance& k);
 const WalkEntry* walk_bridge_entry(const WalkInstance& k);
 // (the same for `bwalk`: walk_bytes.hip)
 const WalkEntry* walk_bytes_entry(const WalkInstance& k);
+// (the same for `bq`: walk_bytes_q.hip)
+const WalkEntry* walk_bytes_q_entry(const WalkInstance& k);
 
 }  // namespace gbnns

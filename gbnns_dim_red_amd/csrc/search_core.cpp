@@ -11,7 +11,10 @@ namespace gbnns_api {
 // One (sub-)batch on one lane's workspace, enqueued on stream s; arguments validated by gbnns_search_ex.  With HOST
 // buffers the copies in and out are enqueued on s too and, when sync_host, waited for.  `topk` (optional, NET / LOWQ): the k best of
 // each query's candidates go to its arrays as well (rerank_topk kernels, behind stage 3).
-int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_t s, bool sync_host, const TopkOut* topk, const TagIn* tag) {
+// `q_u8` (gbnns_search_byte_queries; a->queries is then nullptr): the queries as [n_q x d] bytes, a buffer of a->mem_kind.  They are widened
+// into the lane's q_in (widen.hip) and that copy takes a->queries' place everywhere below; the bytes themselves reach the walk as
+// WalkParams::q_b, for the integer byte-walk instances.
+int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_t s, bool sync_host, const TopkOut* topk, const TagIn* tag, const uint8_t* q_u8) {
     int rc;
     const uint32_t n_ent = a->n_entries ? a->n_entries : 1u;
     const bool host = a->mem_kind == GBNNS_MEM_HOST;
@@ -56,7 +59,23 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
     g_slow.mark("workspace");
     // ---- inputs -------------------------------------------------------------------------
     const float* q_dev = a->queries;
-    if (host) {
+    const uint8_t* qb_dev = q_u8;
+    if (q_u8) {
+        // (HOST buffers, and a DEVICE buffer that does not start on a 16-byte boundary: through the lane's byte staging buffer -- the integer
+        // instances read a query as 16-byte pieces)
+        const size_t count = (size_t)nq * ix->d;
+        if (host || (reinterpret_cast<uintptr_t>(q_u8) & 15u)) {
+            if ((rc = L.q_in_b.ensure(count))) return rc;
+            if (host) {
+                if ((rc = host_copy_in(L, L.q_in_b.p, q_u8, count, s))) return rc;
+            } else {
+                HIP_TRY(hipMemcpyAsync(L.q_in_b.p, q_u8, count, hipMemcpyDeviceToDevice, s));
+            }
+            qb_dev = L.q_in_b.as<uint8_t>();
+        }
+        if ((rc = L.q_in.ensure(count * 4))) return rc;
+        q_dev = L.q_in.as<float>();  // (filled by the widening kernel, behind the profile's first event: its time counts as stage 1's)
+    } else if (host) {
         if ((rc = L.q_in.ensure((size_t)nq * ix->d * 4))) return rc;
         if ((rc = host_copy_in(L, L.q_in.p, a->queries, (size_t)nq * ix->d * 4, s))) return rc;
         q_dev = L.q_in.as<float>();
@@ -88,10 +107,13 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
 
     // ---- stage 1: queries in the walked space ------------------------------------------
     WalkParams w{};
+    if (q_u8) HIP_TRY(launch_widen_u8(qb_dev, L.q_in.as<float>(), (size_t)nq * ix->d, s));
     if (plain) {
         w.q = q_dev; w.qstride = ix->d; w.db = ix->db; w.dstride = ix->d_pad; w.dim = ix->d;
         if (ix->db_b) {  // GBNNS_FLAG_BYTE_WALK (checked by search_call): the walked rows are the handle's uint8 rows, d_pad bytes each; no float table exists
             w.db = nullptr; w.db_b = ix->db_b; w.walk_bytes = 1;
+            // byte queries: the plan may name the integer twin of a byte-walk instance (walk_plan.cpp; knob "byte_query_int": for which beam classes)
+            w.q_b = qb_dev; w.bq_classes = (uint32_t)ix->knob.byte_query_int;
         }
     } else {
         if ((rc = L.q_low.ensure((size_t)nq * ix->dl_pad * 4))) return rc;
@@ -379,6 +401,7 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
             std::string name = (st == 0 && dm) ? dm : mangled;
             std::free(dm);
             size_t pos = name.find("walk_");
+            if (pos == std::string::npos) pos = name.find("beam_");  // (the integer byte-walk instances, walk_bytes_q.hip)
             if (pos != std::string::npos) name = name.substr(pos);
             pos = name.rfind("(gbnns::WalkParams)");
             if (pos != std::string::npos) name = name.substr(0, pos);

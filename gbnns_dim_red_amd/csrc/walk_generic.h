@@ -41,6 +41,46 @@ __device__ __forceinline__ float l2_pair_from_bytes(const RowRegs<4>& r, const f
     return ((v[0] + v[1]) + v[2]) + v[3];
 }
 
+// BQ (gbnns_search_byte_queries, walk_bytes_q.hip): the query is bytes as well.  For d <= 256 every intermediate of the reference's distance
+// over float32(bytes) is an integer below 2^24 (256 * 255^2 = 16 646 400): its float32 sums are exact in any order and equal the integer
+// sum(q - x)^2 = sum q^2 + sum x^2 - 2 sum q x, which is computed here in uint32 (wrap-around arithmetic: the end value is what counts), four
+// products an instruction (v_dot4_u32_u8), and converted once -- the float walk's distance bits.  A lane keeps its own four 16-byte chunks of
+// the query packed in 16 registers (the chunks its row loads bring: half, half + 2, half + 4, half + 6) and sum q^2 of the whole query.
+struct ByteQuery {
+    uint4 c[4];
+    uint32_t qq;
+};
+__device__ __forceinline__ uint32_t dpp_swap_pair_u32(uint32_t x) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xf, 0xf, false);
+}
+__device__ __forceinline__ void byte_query_load(ByteQuery& bq, const uint8_t* q, uint32_t half) {
+    const uint4* q4 = reinterpret_cast<const uint4*>(q) + half;
+    uint32_t s = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint4 c = q4[2 * j];
+        bq.c[j] = c;
+        s = __builtin_amdgcn_udot4(c.x, c.x, s, false); s = __builtin_amdgcn_udot4(c.y, c.y, s, false);
+        s = __builtin_amdgcn_udot4(c.z, c.z, s, false); s = __builtin_amdgcn_udot4(c.w, c.w, s, false);
+    }
+    bq.qq = s + dpp_swap_pair_u32(s);
+}
+// the row term sum x^2 is computed in flight beside sum q x (two chains each); the pair's partial sums meet once.  Both lanes of a pair end
+// up with the distance.
+__device__ __forceinline__ float l2_pair_u8(const RowRegs<4>& r, const ByteQuery& bq) {
+    uint32_t xx0 = 0u, xx1 = 0u, qx0 = 0u, qx1 = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t x0 = __float_as_uint(r.v[j].x), x1 = __float_as_uint(r.v[j].y), x2 = __float_as_uint(r.v[j].z), x3 = __float_as_uint(r.v[j].w);
+        xx0 = __builtin_amdgcn_udot4(x0, x0, xx0, false); qx0 = __builtin_amdgcn_udot4(bq.c[j].x, x0, qx0, false);
+        xx1 = __builtin_amdgcn_udot4(x1, x1, xx1, false); qx1 = __builtin_amdgcn_udot4(bq.c[j].y, x1, qx1, false);
+        xx0 = __builtin_amdgcn_udot4(x2, x2, xx0, false); qx0 = __builtin_amdgcn_udot4(bq.c[j].z, x2, qx0, false);
+        xx1 = __builtin_amdgcn_udot4(x3, x3, xx1, false); qx1 = __builtin_amdgcn_udot4(bq.c[j].w, x3, qx1, false);
+    }
+    const uint32_t s = (xx0 + xx1) - 2u * (qx0 + qx1);
+    return (float)(s + dpp_swap_pair_u32(s) + bq.qq);
+}
+
 // ---- fast kernel: result list, tie list, visited hash set and the query all live in LDS -------
 //
 // LDS layout (dynamic): [keys: ef_pad x u64][tie: kTieCap x u64][q: dstride x f32][hash: cap x u32]
@@ -223,8 +263,10 @@ __global__ __launch_bounds__(64) void walk_bitmap_kernel(WalkParams p) {
 // BYTES: GBNNS_FLAG_BYTE_WALK (walk_bytes.hip; L2, STEPS = 8 = the 16-byte chunks of a 128-byte uint8 row of d = 128, compact index) -- the hop's
 // rows and the entry row come from the byte table WalkParams::db_b (p.db is nullptr, p.dstride the bytes of a row), a lane keeps its four
 // chunks packed until l2_pair_from_bytes consumes them, and the query (128 floats) is re-read from LDS every hop; nothing else differs
+// BQ (with BYTES): gbnns_search_byte_queries (walk_bytes_q.hip) -- the query is read as bytes from WalkParams::q_b into 16 registers (ByteQuery: no
+// query area in LDS, the visited set starts where it would) and the distance is l2_pair_u8's integer one, the entry row's included
 template <int METRIC, int STEPS, bool OFF32, int R, bool ONE_CHUNK = false, bool AUX = false, bool BITMAP = false, bool QLDS_W = false, int LATE = -1,
-          bool HALF = false, bool TAG = false, bool BYTES = false>
+          bool HALF = false, bool TAG = false, bool BYTES = false, bool BQ = false>
 __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, unsigned char* smem,
                                              uint32_t* ovf_count, uint32_t* ovf_list, uint32_t* bitmap = nullptr) {
     static_assert(!(AUX && ONE_CHUNK), "auxiliary rows have their own length");
@@ -247,6 +289,7 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
     static_assert(!HALF || (kPair && OFF32 && !QLDS_W), "HALF: pair-form instances of a compact index");
     static_assert(!TAG || (kPair && OFF32 && !BITMAP && !HALF), "TAG: pair-form instances of a compact index");
     static_assert(!BYTES || (METRIC == 0 && STEPS == 8 && OFF32 && !AUX && !BITMAP && !QLDS_W && !HALF && !TAG), "BYTES: L2 over 128-byte uint8 rows of a compact index");
+    static_assert(!BQ || BYTES, "BQ: byte queries over byte rows");
     const int lane = lane_id();
     const uint32_t slot = kPair ? (uint32_t)lane >> 1 : (uint32_t)lane;    // adjacency slot of this lane
     const uint32_t half = kPair ? (uint32_t)lane & 1u : 0u;
@@ -254,7 +297,7 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
     uint64_t* tie = reinterpret_cast<uint64_t*>(smem);
     uint64_t* stage = tie + kRegTieCap;  // scatter buffer of the batch merge
     float* qf = reinterpret_cast<float*>(stage + reg_stage_slots(R));
-    uint32_t* hash = reinterpret_cast<uint32_t*>(qf + p.dstride);
+    uint32_t* hash = reinterpret_cast<uint32_t*>(qf + (BQ ? 0u : p.dstride));  // (BQ: no query area)
     const float4* qs = reinterpret_cast<const float4*>(qf);
     const uint32_t cap = p.hash_cap;  // any size: slot = mulhi(id * C, cap)
     const uint32_t hash_lds = (uint32_t)(size_t)((__attribute__((address_space(3))) unsigned char*)reinterpret_cast<unsigned char*>(hash));
@@ -269,8 +312,13 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
     else if (vs_shr) quotient_table_init(hash, nbuckets, lane);
     else if constexpr (packed) packed_table_init(hash, nbuckets, 0u, lane);
     else for (uint32_t i = lane; i < cap; i += 64) hash[i] = kInvalidId;
-    for (uint32_t i = lane; i < p.dstride; i += 64)
-        qf[i] = (i < p.dim) ? p.q[(size_t)qi * p.qstride + i] : 0.f;
+    ByteQuery bq;  // BQ: the lane's chunks of the query, packed, and the query's sum of squares
+    if constexpr (BQ) {
+        byte_query_load(bq, p.q_b + (size_t)qi * kRowBytes, half);
+    } else {
+        for (uint32_t i = lane; i < p.dstride; i += 64)
+            qf[i] = (i < p.dim) ? p.q[(size_t)qi * p.qstride + i] : 0.f;
+    }
     wave_sync();
 
     // the query stays in registers (every lane holds all of it): the occupancy scan shows the walk is
@@ -299,7 +347,11 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
     }
     {
         float d0;
-        if constexpr (BYTES) d0 = metric_dist<0>(qs, ByteRow4{reinterpret_cast<const uint32_t*>(p.db_b + entry * kRowBytes)}, p.dim);  // (a lane per row: the same sums)
+        if constexpr (BQ) {  // (the pair form: every pair computes it)
+            RowRegs<4> er;
+            load_row_alt(er, reinterpret_cast<const float*>(p.db_b + entry * kRowBytes + half * 16u));
+            d0 = __uint_as_float(readlane_u32(__float_as_uint(l2_pair_u8(er, bq)), 1));
+        } else if constexpr (BYTES) d0 = metric_dist<0>(qs, ByteRow4{reinterpret_cast<const uint32_t*>(p.db_b + entry * kRowBytes)}, p.dim);  // (a lane per row: the same sums)
         else d0 = walk_dist<METRIC, STEPS>(qs, row_ptr<OFF32>(p.db, entry, p.dstride), p.dim);
         worst = fkey(d0);
         if (lane == 0) {
@@ -540,7 +592,10 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
             uint32_t dk = 0xFFFFFFFFu;
             if constexpr (HALF) widen_row(rr, rh);
             if constexpr (kEarlyLoad) {
-                if constexpr (BYTES) {
+                if constexpr (BQ) {
+                    const uint32_t kd = fkey_sumsq(l2_pair_u8(rr, bq));  // all lanes hold distances
+                    dk = fresh ? kd : 0xFFFFFFFFu;
+                } else if constexpr (BYTES) {
                     const float4* ql = qs + 4u * half;
                     asm volatile("" : "+v"(ql));  // (not hoisted out of the hop loop)
                     const uint32_t kd = fkey_sumsq(l2_pair_from_bytes(rr, ql));  // all lanes; odd lanes hold distances
@@ -665,7 +720,7 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
 // ONE_PASS: adjacency rows of one pass (the host checks ell_stride), no auxiliary graph -- the hop is straight-line code.
 // HALF, TAG, BYTES: as in walk_reg_one.
 template <int METRIC, int STEPS, bool OFF32, bool AUX = false, bool BITMAP = false, bool ONE_PASS = false, bool LATE = false, bool HALF = false,
-          bool TAG = false, bool BYTES = false>
+          bool TAG = false, bool BYTES = false, bool BQ = false>
 __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t qi, unsigned char* smem,
                                                  uint32_t* ovf_count, uint32_t* ovf_list, uint32_t* bitmap = nullptr) {
     constexpr bool kEarlyLoad = (STEPS > 0);
@@ -687,6 +742,7 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
     static_assert(!HALF || (kPair && OFF32), "HALF: pair-form instances of a compact index");
     static_assert(!TAG || (kPair && OFF32 && !BITMAP && !HALF), "TAG: pair-form instances of a compact index");
     static_assert(!BYTES || (METRIC == 0 && STEPS == 8 && OFF32 && !AUX && !BITMAP && !LATE && !HALF && !TAG), "BYTES: L2 over 128-byte uint8 rows of a compact index");
+    static_assert(!BQ || BYTES, "BQ: byte queries over byte rows");
     const int lane = lane_id();
 #ifdef GBNNS_STAMPS  // diagnostic build: cycles per segment of the hop (tools/stamps.py)
     unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -700,7 +756,7 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
     BigList B;
     B.init(smem, ef);
     float* qf = reinterpret_cast<float*>(smem + big_list_fixed_bytes(ef));
-    unsigned char* after_q = reinterpret_cast<unsigned char*>(qf + p.dstride);  // visited set, or re-rank scratch
+    unsigned char* after_q = reinterpret_cast<unsigned char*>(qf + (BQ ? 0u : p.dstride));  // visited set, or re-rank scratch (BQ: no query area)
     uint32_t* hash = reinterpret_cast<uint32_t*>(after_q);
     const float4* qs = reinterpret_cast<const float4*>(qf);
     const uint32_t cap = p.hash_cap;
@@ -721,8 +777,13 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
     else if (vs_shr) quotient_table_init(hash, nbuckets, lane);
     else if constexpr (packed) packed_table_init(hash, nbuckets, 0u, lane);
     else for (uint32_t i = lane; i < cap; i += 64) hash[i] = kInvalidId;
-    for (uint32_t i = lane; i < p.dstride; i += 64)
-        qf[i] = (i < p.dim) ? p.q[(size_t)qi * p.qstride + i] : 0.f;
+    ByteQuery bq;  // BQ: the lane's chunks of the query, packed, and the query's sum of squares
+    if constexpr (BQ) {
+        byte_query_load(bq, p.q_b + (size_t)qi * kRowBytes, half);
+    } else {
+        for (uint32_t i = lane; i < p.dstride; i += 64)
+            qf[i] = (i < p.dim) ? p.q[(size_t)qi * p.qstride + i] : 0.f;
+    }
     wave_sync();
     // (half rows of 24 steps and more: the lane's query pieces are re-read from the wavefront's LDS copy every hop, as in walk_reg_wide_kernel --
     // 72 registers of query beside 72 of squared differences are two wavefronts per SIMD; the float32 instances, bound by their rows' bytes,
@@ -757,7 +818,8 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
             else load_row<kQSteps>(er, rp);
             }
             uint32_t kd;
-            if constexpr (BYTES) kd = fkey_sumsq(l2_pair_from_bytes(er, qs + 4u * half));
+            if constexpr (BQ) kd = fkey_sumsq(l2_pair_u8(er, bq));
+            else if constexpr (BYTES) kd = fkey_sumsq(l2_pair_from_bytes(er, qs + 4u * half));
             else if constexpr (kAlt) kd = fkey(dot_pair_from_regs(er, qreg.v));
             else if constexpr (STEPS == 8) kd = fkey_sumsq(l2_pair_from_regs(er, qreg.v));
             else if constexpr (kQLds) kd = fkey_sumsq(l2_pair_from_regs_wide<kQSteps>(er, qs + kQSteps * half));
@@ -904,7 +966,10 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
             uint32_t dk = 0xFFFFFFFFu;
             if constexpr (HALF) widen_row(rr, rh);
             if constexpr (kEarlyLoad) {
-                if constexpr (BYTES) {
+                if constexpr (BQ) {
+                    const uint32_t kd = fkey_sumsq(l2_pair_u8(rr, bq));
+                    dk = fresh ? kd : 0xFFFFFFFFu;
+                } else if constexpr (BYTES) {
                     const float4* ql = qs + 4u * half;
                     asm volatile("" : "+v"(ql));  // (not hoisted out of the hop loop)
                     const uint32_t kd = fkey_sumsq(l2_pair_from_bytes(rr, ql));

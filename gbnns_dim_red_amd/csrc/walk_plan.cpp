@@ -90,6 +90,12 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
             pl.packed = true;
             pl.lds_fixed = lds_fixed_bytes(ef, p.dstride, false, false, false);  // (the query: dstride = 128 floats, re-read from LDS every hop)
             pl.knows_quotient = true;  // (as the float pair-form instances of a compact index)
+            // gbnns_search_byte_queries: the call brought its queries as bytes -- the integer twin of the same instance (walk_bytes_q.hip), for the
+            // beam classes the handle's knob "byte_query_int" names.  Its query lives in registers: no query area in LDS.
+            if (p.q_b && (p.bq_classes & (regs == 4 ? 4u : (uint32_t)regs))) {
+                k.bq = true;
+                pl.lds_fixed = lds_fixed_bytes(ef, 0u, false, false, false);
+            }
         }
         return pl;  // (no rr_* room: PLAIN has no re-rank)
     }

@@ -53,6 +53,7 @@ enum class WalkFamily : uint8_t {
                 // tag (either family): walk_reg_tag_kernel<METRIC, STEPS, R, ONE_CHUNK> / walk_reg_big_tag_kernel<METRIC, STEPS, ONE_PASS, LATE> (walk_tag.hip)
                 // bridge (register lists): walk_bridge_kernel<METRIC, STEPS, R>                (walk_bridge.hip)
                 // byte walk (either family): walk_reg_bytes_kernel<R, ONE_CHUNK> / walk_reg_big_bytes_kernel<ONE_PASS> (walk_bytes.hip)
+                // ... with byte queries: beam_u8_kernel<R, ONE_CHUNK> / beam_u8_big_kernel<ONE_PASS> (walk_bytes_q.hip)
     LdsList,    // walk_fast_kernel<METRIC, STEPS, RETRY, PACKED>                    (walk_l2 / walk_dot / walk_wide)
     BitmapReg,  // walk_bitmap_reg_kernel<METRIC, R>                                 (walk_bitmap.hip)
     BitmapBig,  // walk_bitmap_big_kernel<METRIC, STEPS, ONE_PASS, LATE>
@@ -76,10 +77,11 @@ struct WalkInstance {
     bool bridge;  // (with tag) a disallowed neighbour is looked through, its allowed neighbours staged in LDS in its place: walk_bridge_kernel (walk_bridge.hip)
     bool bytes;   // the fused re-rank reads uint8 rows (WalkParams::rr_db_b, a byte handle): walk_hot_bytes_kernel / walk_hot2_bytes_kernel (walk_hot.hip)
     bool bwalk;   // the WALKED rows are uint8 (WalkParams::db_b, GBNNS_FLAG_BYTE_WALK): walk_reg_bytes_kernel / walk_reg_big_bytes_kernel (walk_bytes.hip)
+    bool bq;      // (with bwalk) the queries are uint8 too (WalkParams::q_b, gbnns_search_byte_queries), the distance is integer: beam_u8_kernel / beam_u8_big_kernel (walk_bytes_q.hip)
 };
 inline bool operator==(const WalkInstance& a, const WalkInstance& b) {
     return a.family == b.family && a.metric == b.metric && a.steps == b.steps && a.regs == b.regs && a.off32 == b.off32 && a.retry == b.retry && a.one == b.one &&
-           a.aux == b.aux && a.late == b.late && a.spec == b.spec && a.packed == b.packed && a.half == b.half && a.tag == b.tag && a.bridge == b.bridge && a.bytes == b.bytes && a.bwalk == b.bwalk;
+           a.aux == b.aux && a.late == b.late && a.spec == b.spec && a.packed == b.packed && a.half == b.half && a.tag == b.tag && a.bridge == b.bridge && a.bytes == b.bytes && a.bwalk == b.bwalk && a.bq == b.bq;
 }
 
 struct WalkPlan {
@@ -103,8 +105,8 @@ struct WalkPlan {
 // GBNNS_STAMPS_GENERIC keeps diagnostic (GBNNS_STAMPS) builds off the hot two-list instances.
 struct WalkEnv { bool wide2, stamps_generic; };
 const WalkEnv& walk_env();
-// Reads the shape (dim, dstride, n, ell_stride, aux_ell / aux_stride), ef, n_entries, force_wide, coop, late_rows, spec_rows, stamps_on, half_rows, tagged, bridged, generic_only, bytes_dim, walk_bytes
-// and rr_reserve -- nothing the sizing rule writes (hash_cap, hash_limit, vs_shr), so the layout is known before the visited set is sized.
+// Reads the shape (dim, dstride, n, ell_stride, aux_ell / aux_stride), ef, n_entries, force_wide, coop, late_rows, spec_rows, stamps_on, half_rows, tagged, bridged, generic_only, bytes_dim, walk_bytes,
+// q_b (whether the call brought byte queries), bq_classes and rr_reserve -- nothing the sizing rule writes (hash_cap, hash_limit, vs_shr), so the layout is known before the visited set is sized.
 WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv& env = walk_env());
 
 }  // namespace gbnns

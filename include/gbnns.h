@@ -412,6 +412,27 @@ int gbnns_search_tagged(gbnns_index* index, const gbnns_search_args* args, const
  * and in gbnns_debug_byte_walk_plan), which is exact, not tuned: a lane per row. */
 #define GBNNS_FLAG_BYTE_WALK 2048u
 
+/* Byte queries on a byte handle (gbnns_index_create_bytes): the search whose queries are uint8 as well -- BIGANN's query files are .bvecs too.
+ * `queries_u8` is [n_q x d] dense bytes, a buffer of args->mem_kind; args->queries must be NULL.  query_tags == NULL: untagged; k / out_top_*
+ * as in gbnns_search_tagged (k == 0 and both NULL: no k-answer rows).
+ * Contract: every output equals, bit for bit, what the corresponding existing call -- gbnns_search_ex, gbnns_search_topk or
+ * gbnns_search_tagged -- returns on the same handle with queries = float32(queries_u8): ids, out_cand in pop order, out_cand_dist bit
+ * patterns, hops, dist_calc, edges, out_q_low and the k-answer rows.  This holds in NET, LOWQ (queries_low stays float32) and PLAIN mode
+ * (GBNNS_FLAG_BYTE_WALK required, as for float queries), with HOST and DEVICE buffers, GBNNS_FLAG_DEFER_JOIN (the byte buffer obeys the
+ * lifetime and page-lock rules of the other inputs), GBNNS_FLAG_SERIAL, hash_capacity, several entry points, the auxiliary graph, tags and
+ * the bridge.  The library widens the bytes on the device into a buffer of its own (uint8 -> float32 rounds nothing) and every kernel runs
+ * unchanged on that copy -- it IS the definition -- but one family: inside the byte-walk first pass's domain (PLAIN, L2, d == 128, compact
+ * index, one entry point, no auxiliary graph, untagged, ef <= 1 024) the first pass is the integer twin of the byte-walk instance
+ * (beam_u8_kernel<R, ONE_CHUNK> / beam_u8_big_kernel<ONE_PASS> in gbnns_profile.walk_kernel), which reads the byte queries themselves and
+ * computes sum q^2 + sum x^2 - 2 sum q x in uint32, four products an instruction.  For d <= 256 every intermediate of the reference's distance
+ * is an integer below 2^24 (256 * 255^2), so its float32 sums are exact in any order and float(uint32) has the reference's bits.  The handle
+ * knob "byte_query_int" (a mask over the beam classes ef <= 64 / <= 128 / <= 1 024; 0 = never) switches that first pass off: the byte-walk
+ * instances then serve the call on the widened copy.  gbnns_profile.project_ms of a PLAIN call is the widening kernel's time.
+ * Refused: a float handle and a non-NULL args->queries with GBNNS_ERR_INVALID; whatever the corresponding float call refuses, with that
+ * call's own code.  The gbnns_multi_* searches, gbnns_rerank, gbnns_rerank_topk and gbnns_project have no byte-query form. */
+int gbnns_search_byte_queries(gbnns_index* index, const gbnns_search_args* args, const uint8_t* queries_u8, const uint32_t* query_tags, int k,
+                              uint32_t* out_top_ids, float* out_top_dist);
+
 /* Per-kernel device timing (hipEvent pairs on the launch stream), accumulated since the last
  * reset.  Reading synchronises the recorded events. */
 typedef struct {
@@ -512,6 +533,10 @@ int gbnns_debug_byte_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n
  * the other inputs as for gbnns_debug_walk_plan. */
 int gbnns_debug_byte_walk_plan(int metric, uint32_t dim, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries, int force_wide,
                                int tagged, char* name, uint32_t name_bytes, uint64_t* lds_bytes);
+/* The same for a gbnns_search_byte_queries call of that shape with the knob "byte_query_int" = 7 (every beam class): the integer instance
+ * inside the byte-walk first pass's domain (its query lives in registers: 512 bytes of LDS less), "walk_general_kernel" outside it. */
+int gbnns_debug_byte_query_plan(int metric, uint32_t dim, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries, int force_wide,
+                                int tagged, char* name, uint32_t name_bytes, uint64_t* lds_bytes);
 /* Diagnostic, no device needed: LDS bytes of a workgroup of the one-launch projection for a net d -> d_hidden -> d_hidden -> d_low, in
  * the whole-CU form (form 0) or the half-CU form (form 1), with a queries per lane (2 .. 5), and whether that form takes the net at all
  * (*admitted: a workgroup with a = 4 fits 160 KB / 80 KB). */
