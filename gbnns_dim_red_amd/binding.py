@@ -42,6 +42,7 @@ SYMBOLS = [
     "gbnns_index_create_bytes", "gbnns_index_is_bytes", "gbnns_debug_byte_plan", "gbnns_debug_byte_walk_plan",
     "gbnns_exact_knn_bytes", "gbnns_debug_knn_bytes_plan",
     "gbnns_search_byte_queries", "gbnns_debug_byte_query_plan",
+    "gbnns_exact_knn_tagged", "gbnns_exact_knn_bytes_tagged", "gbnns_index_exact_knn",
 ]
 
 
@@ -148,6 +149,11 @@ def load_library():
     lib.gbnns_exact_knn.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
                                     C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.gbnns_exact_knn_bytes.argtypes = lib.gbnns_exact_knn.argtypes
+    lib.gbnns_exact_knn_tagged.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_int64,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.gbnns_exact_knn_bytes_tagged.argtypes = lib.gbnns_exact_knn_tagged.argtypes
+    lib.gbnns_index_exact_knn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_int, C.c_void_p]
     lib.gbnns_debug_knn_bytes_plan.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
     lib.gbnns_multi_last_error.restype = C.c_char_p
@@ -398,12 +404,30 @@ def build_graph_gd_device(knn_offsets, knn_nbrs, ds, M, metric=METRIC_L2, revers
     return off, nbr, int(hn.value)
 
 
-def exact_knn(base, queries, k, metric=METRIC_L2, self_offset=-1, want_dist=False, device=0, stream=None):
+def _prep_tags(tags, dev, count, what):
+    """A tag array beside host (numpy uint32) or device (CUDA/ROCm int32 tensor) inputs, one word per row / query."""
+    if dev:
+        if not (_is_dev(tags) and tags.is_cuda):
+            raise TypeError(f"{what}: a CUDA/ROCm int32 tensor beside device inputs")
+        tags = _prep(tags, np.uint32, "int32")
+    else:
+        if _is_dev(tags):
+            raise TypeError(f"{what}: a numpy uint32 array beside host inputs")
+        tags = _host(tags, np.uint32)
+    if tags.ndim != 1 or int(tags.shape[0]) != count:
+        raise ValueError(f"{what} must have {count} words")
+    return tags
+
+
+def exact_knn(base, queries, k, metric=METRIC_L2, self_offset=-1, want_dist=False, device=0, stream=None, row_tags=None, query_tags=None):
     """gbnns_exact_knn: ids [n_q x k] (and distances) of the k nearest base rows of every query, in the
     reference's distance arithmetic, ascending (distance, id).  numpy in -> numpy out; torch CUDA in -> torch
     out.  self_offset >= 0: query i is base row i + self_offset (excluded from its own list).
     Both arguments uint8 (numpy or torch): gbnns_exact_knn_bytes -- the same answer as over the widened arrays, bit for
-    bit, on the int8 matrix cores and without a float copy (d <= 256, k <= 4096)."""
+    bit, on the int8 matrix cores and without a float copy (d <= 256, k <= 4096).
+    row_tags [n] and query_tags [n_q] (both or neither; numpy uint32, or int32 tensors beside device inputs): gbnns_exact_knn_tagged /
+    gbnns_exact_knn_bytes_tagged -- the same lists over the rows j with (row_tags[j] & query_tags[i]) != 0 only, under their original ids;
+    0xFFFFFFFF / +inf where fewer than k rows are allowed."""
     lib = load_library()
     dev = _is_dev(base)
     if _is_dev(queries) != dev:
@@ -412,13 +436,21 @@ def exact_knn(base, queries, k, metric=METRIC_L2, self_offset=-1, want_dist=Fals
     if _is_u8(queries) != u8:
         raise TypeError("base and queries must both be uint8 (gbnns_exact_knn_bytes: byte rows against byte queries) or both be float "
                         "(gbnns_exact_knn); for float queries against a byte table widen the table with .astype(float32)")
-    fn = lib.gbnns_exact_knn_bytes if u8 else lib.gbnns_exact_knn
+    tagged = row_tags is not None
+    if (query_tags is not None) != tagged:
+        raise TypeError("row_tags and query_tags: both or neither")
+    if tagged:
+        fn = lib.gbnns_exact_knn_bytes_tagged if u8 else lib.gbnns_exact_knn_tagged
+    else:
+        fn = lib.gbnns_exact_knn_bytes if u8 else lib.gbnns_exact_knn
     base = _prep(base, np.uint8, "uint8") if u8 else _prep(base, np.float32, "float32")
     queries = _prep(queries, np.uint8, "uint8") if u8 else _prep(queries, np.float32, "float32")
     n, d = int(base.shape[0]), int(base.shape[1])
     nq = int(queries.shape[0])
     if int(queries.shape[1]) != d:
         raise ValueError("dimension mismatch")
+    if tagged:
+        row_tags, query_tags = _prep_tags(row_tags, dev, n, "row_tags"), _prep_tags(query_tags, dev, nq, "query_tags")
     if dev:
         import torch
         ids = torch.empty((nq, k), dtype=torch.int32, device=base.device)
@@ -431,7 +463,8 @@ def exact_knn(base, queries, k, metric=METRIC_L2, self_offset=-1, want_dist=Fals
         ids = np.empty((nq, k), np.uint32)
         dist = np.empty((nq, k), np.float32) if want_dist else None
         sptr = None
-    _check(fn(device, _ptr(base), n, _ptr(queries), nq, d, k, metric, self_offset, _ptr(ids),
+    tag_args = (_ptr(row_tags), _ptr(query_tags)) if tagged else ()
+    _check(fn(device, _ptr(base), n, _ptr(queries), nq, d, k, metric, self_offset, *tag_args, _ptr(ids),
               _ptr(dist), MEM_DEVICE if dev else MEM_HOST, sptr))
     return (ids, dist) if want_dist else ids
 
@@ -839,6 +872,37 @@ class Index:
         _check(self._lib.gbnns_rerank_topk(self._h, q.ctypes.data, q.shape[0], cand.ctypes.data, cand.shape[1], _ptr(count), k,
                                            ids.ctypes.data, _ptr(dist), MEM_HOST, None))
         return ids, dist
+
+    def exact_knn(self, queries, k, query_tags=None, self_offset=-1, want_dist=False):
+        """gbnns_index_exact_knn: exact_knn(db, queries, k, metric=<the handle's>, ...) over the handle's resident table, read in place --
+        nothing of the table is uploaded.  query_tags [nq]: the tagged answer over set_tags()'s table (exact_knn's row_tags / query_tags
+        form, the ground truth of search(query_tags=...)); None: the untagged answer.  A float handle takes float queries (uint8 ones raise
+        TypeError), a byte handle uint8 queries (float ones: GbnnsError, code 5 -- there is no mixed-pair scan).  numpy queries -> numpy
+        results; torch CUDA queries -> torch results, on the current stream.  Returns ids, or (ids, dist) with want_dist."""
+        u8 = _is_u8(queries)
+        if u8 and not self.is_bytes:
+            raise TypeError("uint8 queries need a byte handle (Index(db=<uint8>)); widen them for a float handle")
+        dev = _is_dev(queries)
+        if dev and not queries.is_cuda:
+            raise TypeError("queries: a numpy array or a CUDA/ROCm tensor")
+        queries = _prep(queries, np.uint8, "uint8") if u8 else _prep(queries, np.float32, "float32")
+        nq = int(queries.shape[0])
+        if queries.ndim != 2 or int(queries.shape[1]) != self.d:
+            raise ValueError("query dimension mismatch")
+        if query_tags is not None:
+            query_tags = _prep_tags(query_tags, dev, nq, "query_tags")
+        if dev:
+            import torch
+            ids = torch.empty((nq, k), dtype=torch.int32, device=queries.device)
+            dist = torch.empty((nq, k), dtype=torch.float32, device=queries.device) if want_dist else None
+            sptr = torch.cuda.current_stream(queries.device).cuda_stream
+        else:
+            ids = np.empty((nq, k), np.uint32)
+            dist = np.empty((nq, k), np.float32) if want_dist else None
+            sptr = None
+        _check(self._lib.gbnns_index_exact_knn(self._h, None if u8 else _ptr(queries), _ptr(queries) if u8 else None, nq, _ptr(query_tags), k,
+                                               self_offset, _ptr(ids), _ptr(dist), MEM_DEVICE if dev else MEM_HOST, sptr))
+        return (ids, dist) if want_dist else ids
 
     # -- profiling -----------------------------------------------------------------------------
     def profile_enable(self, on=True):

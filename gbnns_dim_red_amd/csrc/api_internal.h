@@ -2,7 +2,7 @@
 // handle.cpp / graph_api.cpp / lanes.cpp / search_core.cpp / sizing.cpp / pin.cpp; no behaviour change).
 //   handle.cpp      the index handle: creation (uploads, layouts), destruction, projection / re-rank entry points, profiling,
 //                   the diagnostic knobs, error text
-//   graph_api.cpp   graph preparation: gbnns_exact_knn (heaps / matrix-core filter / pools), gbnns_exact_knn_bytes (uint8 rows), gbnns_build_graph_gd_device
+//   graph_api.cpp   graph preparation: gbnns_exact_knn (heaps / matrix-core filter / pools), gbnns_exact_knn_bytes (uint8 rows), their tagged forms and gbnns_index_exact_knn, gbnns_build_graph_gd_device
 //   lanes.cpp       gbnns_search_ex and the batches-in-flight machinery (lanes, fork / join events), gbnns_index_wait / _join
 //   search_core.cpp one batch on one lane: workspaces, copies, the kernel sequence
 //   sizing.cpp      the visited-set sizing rule of the first pass (capacity, form, wavefronts per CU)

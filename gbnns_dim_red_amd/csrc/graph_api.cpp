@@ -1,6 +1,8 @@
 // graph_api.cpp -- graph preparation entry points of the C ABI (include/gbnns.h): gbnns_exact_knn (getTruth, support_func.h:270-290,
 // generalised to k results: heaps, the matrix-core filter, long lists as pools), gbnns_exact_knn_bytes (the same lists over uint8 rows,
-// their distances from the int8 matrix cores: knn_bytes.hip) with gbnns_debug_knn_bytes_plan, and gbnns_build_graph_gd_device (hnswlikeGD,
+// their distances from the int8 matrix cores: knn_bytes.hip) with gbnns_debug_knn_bytes_plan, their tagged forms gbnns_exact_knn_tagged /
+// gbnns_exact_knn_bytes_tagged and gbnns_index_exact_knn over a handle's resident table (one body each for float and byte rows, whichever
+// entry point brought the call), and gbnns_build_graph_gd_device (hnswlikeGD,
 // support_func.h:521-575, pruning on the device).  Cut out of api.cpp in round 5; api_internal.h lists the other units.
 
 #include "api_internal.h"
@@ -8,12 +10,60 @@
 using namespace gbnns;
 using namespace gbnns_api;
 
-extern "C" {
+namespace {
+// One exact-kNN request, whichever entry point brought it: gbnns_exact_knn / _bytes (untagged, caller's arrays), their _tagged twins, and
+// gbnns_index_exact_knn (the table and the row tags are the handle's, resident on the device at the handle's row stride).  T = float / uint8_t.
+template <class T>
+struct KnnCall {
+    int device;
+    const T* base;             // [n x bstride]; a buffer of mem_kind, or (resident) device memory whatever mem_kind says
+    uint32_t bstride;          // elements between rows
+    bool resident;
+    uint64_t n;
+    const T* queries;          // [n_q x d], mem_kind
+    uint64_t n_q;
+    uint32_t d;
+    int k, metric;
+    int64_t self_offset;
+    bool tagged;
+    const uint32_t* row_tags;  // [n]; where base is
+    const uint32_t* query_tags;  // [n_q], mem_kind
+    uint32_t* out_ids;
+    float* out_dist;
+    int mem_kind;
+    void* stream;
+};
 
-int gbnns_exact_knn(int device, const float* base, uint64_t n, const float* queries, uint64_t n_q,
-                    uint32_t d, int k, int metric, int64_t self_offset, uint32_t* out_ids, float* out_dist,
-                    int mem_kind, void* stream) {
-    if (!base || !queries || !out_ids) return fail(GBNNS_ERR_INVALID, "null argument");
+// The tag words of a tagged call on the device: the rows' in a copy of its own, 16-byte aligned and 64 words longer than the set (zero
+// there) -- the sweep kernels read them in aligned groups of four to the end of a block of 32 rows, as they read bnorm / bterm -- and the
+// queries' (uploaded for HOST buffers).
+template <class T>
+int knn_stage_tags(const KnnCall<T>& c, DevBuf& tag_dev, DevBuf& qtag_dev, const uint32_t*& qtags, hipStream_t s) {
+    int rc;
+    if ((rc = tag_dev.ensure(((size_t)c.n + 64) * 4))) return rc;
+    HIP_TRY(hipMemsetAsync(tag_dev.as<uint32_t>() + c.n, 0, 64 * 4, s));
+    const bool host = c.mem_kind == GBNNS_MEM_HOST;
+    HIP_TRY(hipMemcpyAsync(tag_dev.p, c.row_tags, (size_t)c.n * 4, host && !c.resident ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+    qtags = c.query_tags;
+    if (host) {
+        if ((rc = qtag_dev.ensure((size_t)c.n_q * 4))) return rc;
+        HIP_TRY(hipMemcpyAsync(qtag_dev.p, c.query_tags, (size_t)c.n_q * 4, hipMemcpyHostToDevice, s));
+        qtags = qtag_dev.as<uint32_t>();
+    }
+    return GBNNS_OK;
+}
+
+int knn_float_call(const KnnCall<float>& c) {
+    const int device = c.device, k = c.k, metric = c.metric, mem_kind = c.mem_kind;
+    const float* const base = c.base;
+    const float* const queries = c.queries;
+    const uint64_t n = c.n, n_q = c.n_q;
+    const uint32_t d = c.d;
+    const int64_t self_offset = c.self_offset;
+    uint32_t* const out_ids = c.out_ids;
+    float* const out_dist = c.out_dist;
+    void* const stream = c.stream;
+    if (!base || !queries || !out_ids || (c.tagged && (!c.row_tags || !c.query_tags))) return fail(GBNNS_ERR_INVALID, "null argument");
     if (n == 0 || n >= (1ull << 32) - 1) return fail(GBNNS_ERR_INVALID, "n must be in [1, 2^32 - 1)");
     if (n_q >= (1ull << 31)) return fail(GBNNS_ERR_INVALID, "n_q too large");
     if (k < 1 || k > (1 << 20)) return fail(GBNNS_ERR_INVALID, "k must be in [1, 2^20]");
@@ -33,25 +83,34 @@ int gbnns_exact_knn(int device, const float* base, uint64_t n, const float* quer
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool host = mem_kind == GBNNS_MEM_HOST;
     const uint32_t nq = (uint32_t)n_q;
-    DevBuf b_dev, q_dev, ids_dev, dist_dev, heap;
+    DevBuf b_dev, q_dev, ids_dev, dist_dev, heap, tag_dev, qtag_dev;
     struct Release {  // DevBuf has no destructor (index members are released by gbnns_index_destroy)
-        DevBuf* b[5];
+        DevBuf* b[7];
         ~Release() { for (DevBuf* x : b) x->release(); }
-    } release{{&b_dev, &q_dev, &ids_dev, &dist_dev, &heap}};
+    } release{{&b_dev, &q_dev, &ids_dev, &dist_dev, &heap, &tag_dev, &qtag_dev}};
     int rc;
     KnnParams p{};
     p.base = base; p.q = queries; p.out_ids = out_ids; p.out_dist = out_dist;
     if (host) {
-        if ((rc = b_dev.ensure((size_t)n * d * 4))) return rc;
+        if (!c.resident) {
+            if ((rc = b_dev.ensure((size_t)n * d * 4))) return rc;
+            HIP_TRY(hipMemcpyAsync(b_dev.p, base, (size_t)n * d * 4, hipMemcpyHostToDevice, s));
+            p.base = b_dev.as<float>();
+        }
         if ((rc = q_dev.ensure((size_t)nq * d * 4))) return rc;
         if ((rc = ids_dev.ensure((size_t)nq * k * 4))) return rc;
         if (out_dist && (rc = dist_dev.ensure((size_t)nq * k * 4))) return rc;
-        HIP_TRY(hipMemcpyAsync(b_dev.p, base, (size_t)n * d * 4, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(q_dev.p, queries, (size_t)nq * d * 4, hipMemcpyHostToDevice, s));
-        p.base = b_dev.as<float>(); p.q = q_dev.as<float>(); p.out_ids = ids_dev.as<uint32_t>();
+        p.q = q_dev.as<float>(); p.out_ids = ids_dev.as<uint32_t>();
         p.out_dist = out_dist ? dist_dev.as<float>() : nullptr;
     }
-    p.bstride = d; p.qstride = d; p.n = n; p.nq = nq; p.dim = d; p.k = k; p.self_offset = self_offset;
+    const uint32_t* qtags = nullptr;  // tagged: the device copies of the tag words; a launch with null tags is the untagged instance
+    if (c.tagged) {
+        if ((rc = knn_stage_tags(c, tag_dev, qtag_dev, qtags, s))) return rc;
+        p.row_tags = tag_dev.as<uint32_t>(); p.query_tags = qtags;
+    }
+    const uint32_t* const tags = tag_dev.as<uint32_t>();
+    p.bstride = c.bstride; p.qstride = d; p.n = n; p.nq = nq; p.dim = d; p.k = k; p.self_offset = self_offset;
     p.heap_stride = ((size_t)nq + 63) & ~(size_t)63;
     // Matrix-core filter in front of the exact distances (knn.hip): the L2 metric on rows of whole 16-byte steps, sets
     // large enough to amortise its passes.  Same output, byte for byte (tests/test_gpu_parity.py); "knn_filter" 0 = off.
@@ -90,7 +149,7 @@ int gbnns_exact_knn(int device, const float* base, uint64_t n, const float* quer
         if ((rc = pool.ensure((size_t)slab * (size_t)k * 8))) return rc;
         if ((rc = root.ensure((size_t)slab * 8))) return rc;
         HIP_TRY(launch_fill_u32(bnorm.as<uint32_t>() + n, 0x7F800000u, 64, s));
-        HIP_TRY(launch_knn_pack(p.base, d, d, n, bpack.as<uint16_t>(), bnorm.as<float>(), s));
+        HIP_TRY(launch_knn_pack(p.base, p.bstride, d, n, bpack.as<uint16_t>(), bnorm.as<float>(), s));
         for (uint32_t q0 = 0; q0 < nq; q0 += slab) {
             const uint32_t qn = std::min(slab, nq - q0);
             KnnPoolParams pp{};
@@ -98,6 +157,7 @@ int gbnns_exact_knn(int device, const float* base, uint64_t n, const float* quer
             pp.k.q = p.q + (size_t)q0 * d; pp.k.nq = qn; pp.k.out_ids = p.out_ids + (size_t)q0 * k;
             pp.k.out_dist = p.out_dist ? p.out_dist + (size_t)q0 * k : nullptr;
             pp.k.self_offset = self_offset >= 0 ? self_offset + (int64_t)q0 : -1;
+            if (qtags) pp.k.query_tags = qtags + q0;
             pp.pool = pool.as<uint64_t>(); pp.root = root.as<uint64_t>(); pp.cand = cand.as<uint32_t>(); pp.count = count.as<uint32_t>();
             pp.cap = cap; pp.qnorm = qnorm.as<float>(); pp.rhs = rhs.as<float>();
             HIP_TRY(launch_knn_pack(pp.k.q, d, d, qn, qpack.as<uint16_t>(), qnorm.as<float>(), s));
@@ -112,6 +172,7 @@ int gbnns_exact_knn(int device, const float* base, uint64_t n, const float* quer
                 f.qpack = qpack.as<uint16_t>(); f.bpack = bpack.as<uint16_t>() + (size_t)r0 * dp * 2; f.bnorm = bnorm.as<float>() + r0;
                 f.rhs = rhs.as<float>(); f.nq = qn; f.dp = dp; f.rows = rows; f.row0 = (uint32_t)r0; f.cap = cap;
                 f.cand = cand.as<uint32_t>(); f.count = count.as<uint32_t>(); f.overflow = flag.as<uint32_t>();
+                if (qtags) { f.btag = tags + r0; f.qtag = qtags + q0; }
                 HIP_TRY(launch_knn_filter(f, s));
                 return GBNNS_OK;
             };
@@ -156,7 +217,7 @@ int gbnns_exact_knn(int device, const float* base, uint64_t n, const float* quer
         if ((rc = count.ensure((size_t)nq * 4))) return rc;
         if ((rc = flag.ensure(4))) return rc;
         HIP_TRY(launch_fill_u32(bnorm.as<uint32_t>() + n, 0x7F800000u, 64, s));
-        HIP_TRY(launch_knn_pack(p.base, d, d, n, bpack.as<uint16_t>(), bnorm.as<float>(), s));
+        HIP_TRY(launch_knn_pack(p.base, p.bstride, d, n, bpack.as<uint16_t>(), bnorm.as<float>(), s));
         HIP_TRY(launch_knn_pack(p.q, d, d, nq, qpack.as<uint16_t>(), qnorm.as<float>(), s));
         KnnParams ps = p;          // the first rows: the exact scan, heaps kept
         ps.n = first; ps.row0 = 0; ps.keep_heap = 1;
@@ -172,6 +233,7 @@ int gbnns_exact_knn(int device, const float* base, uint64_t n, const float* quer
             f.qpack = qpack.as<uint16_t>(); f.bpack = bpack.as<uint16_t>() + (size_t)r0 * dp * 2; f.bnorm = bnorm.as<float>() + r0;
             f.rhs = rhs.as<float>(); f.nq = nq; f.dp = dp; f.rows = rows; f.row0 = (uint32_t)r0; f.cap = cap;
             f.cand = cand.as<uint32_t>(); f.count = count.as<uint32_t>(); f.overflow = flag.as<uint32_t>();
+            if (qtags) { f.btag = tags + r0; f.qtag = qtags; }
             HIP_TRY(launch_knn_filter(f, s));
             HIP_TRY(hipMemcpyAsync(&h_flag, flag.p, 4, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
@@ -179,7 +241,7 @@ int gbnns_exact_knn(int device, const float* base, uint64_t n, const float* quer
                 // some query kept more rows of this chunk than its list holds (adversarial order of the rows, or thresholds
                 // not yet tight): the chunk is scanned exactly for everyone instead -- same heaps, nothing offered twice
                 KnnParams pc = p;
-                pc.base = p.base + (size_t)r0 * d; pc.n = rows; pc.row0 = r0; pc.keep_heap = 1;
+                pc.base = p.base + (size_t)r0 * p.bstride; pc.n = rows; pc.row0 = r0; pc.keep_heap = 1;
                 HIP_TRY(launch_knn_scan(pc, metric, s));
                 HIP_TRY(launch_knn_thresholds(p.heap, p.heap_stride, k, qnorm.as<float>(), nq, rhs.as<float>(), s));
             } else {
@@ -202,9 +264,6 @@ int gbnns_exact_knn(int device, const float* base, uint64_t n, const float* quer
     return GBNNS_OK;
 }
 
-}  // extern "C"
-
-namespace {
 // What gbnns_exact_knn_bytes does with a shape under the current knobs (gbnns_debug_knn_bytes_plan reports it).
 struct KnnBytesPlan {
     uint32_t dp;          // row bytes of the packed operands: d rounded up to the K step
@@ -224,24 +283,18 @@ KnnBytesPlan knn_bytes_plan(uint64_t n, uint64_t nq, uint32_t d, int k) {
     pl.slab = (uint32_t)std::min<uint64_t>(nq, std::max<uint64_t>(1024, ((4ull << 30) / ((uint64_t)pl.cap * 8)) & ~(uint64_t)127));
     return pl;
 }
-}  // namespace
 
-extern "C" {
-
-int gbnns_debug_knn_bytes_plan(uint64_t n, uint64_t n_q, uint32_t d, int k, uint32_t* dp, uint32_t* cap, uint64_t* first_rows,
-                               uint64_t* max_chunk, int* pool) {
-    if (!dp || !cap || !first_rows || !max_chunk || !pool) return fail(GBNNS_ERR_INVALID, "gbnns_debug_knn_bytes_plan: null output");
-    if (n == 0 || n >= (1ull << 32) - 1 || n_q >= (1ull << 31) || d == 0 || d > 256 || k < 1 || k > 4096)
-        return fail(GBNNS_ERR_INVALID, "gbnns_debug_knn_bytes_plan: not a shape gbnns_exact_knn_bytes takes");
-    const KnnBytesPlan pl = knn_bytes_plan(n, n_q, d, k);
-    *dp = pl.dp; *cap = pl.cap; *first_rows = pl.first_rows; *max_chunk = pl.max_chunk; *pool = pl.pool ? 1 : 0;
-    return GBNNS_OK;
-}
-
-int gbnns_exact_knn_bytes(int device, const uint8_t* base, uint64_t n, const uint8_t* queries, uint64_t n_q,
-                          uint32_t d, int k, int metric, int64_t self_offset, uint32_t* out_ids, float* out_dist,
-                          int mem_kind, void* stream) {
-    if (!base || !queries || !out_ids) return fail(GBNNS_ERR_INVALID, "null argument");
+int knn_bytes_call(const KnnCall<uint8_t>& c) {
+    const int device = c.device, k = c.k, metric = c.metric, mem_kind = c.mem_kind;
+    const uint8_t* const base = c.base;
+    const uint8_t* const queries = c.queries;
+    const uint64_t n = c.n, n_q = c.n_q;
+    const uint32_t d = c.d;
+    const int64_t self_offset = c.self_offset;
+    uint32_t* const out_ids = c.out_ids;
+    float* const out_dist = c.out_dist;
+    void* const stream = c.stream;
+    if (!base || !queries || !out_ids || (c.tagged && (!c.row_tags || !c.query_tags))) return fail(GBNNS_ERR_INVALID, "null argument");
     if (n == 0 || n >= (1ull << 32) - 1) return fail(GBNNS_ERR_INVALID, "n must be in [1, 2^32 - 1)");
     if (n_q >= (1ull << 31)) return fail(GBNNS_ERR_INVALID, "n_q too large");
     if (k < 1 || k > (1 << 20)) return fail(GBNNS_ERR_INVALID, "k must be in [1, 2^20]");
@@ -266,26 +319,32 @@ int gbnns_exact_knn_bytes(int device, const uint8_t* base, uint64_t n, const uin
     const uint32_t nq = (uint32_t)n_q;
     const KnnBytesPlan pl = knn_bytes_plan(n, n_q, d, k);
     const uint32_t dp = pl.dp, cap = pl.cap, slab = pl.slab;
-    DevBuf b_dev, q_dev, ids_dev, dist_dev, bpack, bterm, qpack, qterm, thr, cand, cnt, flag, keys, root;
+    DevBuf b_dev, q_dev, ids_dev, dist_dev, bpack, bterm, qpack, qterm, thr, cand, cnt, flag, keys, root, tag_dev, qtag_dev;
     struct Release {  // DevBuf has no destructor (index members are released by gbnns_index_destroy)
-        DevBuf* b[14];
+        DevBuf* b[16];
         ~Release() { for (DevBuf* x : b) x->release(); }
-    } release{{&b_dev, &q_dev, &ids_dev, &dist_dev, &bpack, &bterm, &qpack, &qterm, &thr, &cand, &cnt, &flag, &keys, &root}};
+    } release{{&b_dev, &q_dev, &ids_dev, &dist_dev, &bpack, &bterm, &qpack, &qterm, &thr, &cand, &cnt, &flag, &keys, &root, &tag_dev, &qtag_dev}};
     int rc;
     const uint8_t* base_d = base;
     const uint8_t* q_d = queries;
     uint32_t* ids_d = out_ids;
     float* dist_d = out_dist;
     if (host) {  // uploaded as bytes: a quarter of the float call's traffic, and no float copy anywhere
-        if ((rc = b_dev.ensure((size_t)n * d))) return rc;
+        if (!c.resident) {
+            if ((rc = b_dev.ensure((size_t)n * d))) return rc;
+            HIP_TRY(hipMemcpyAsync(b_dev.p, base, (size_t)n * d, hipMemcpyHostToDevice, s));
+            base_d = b_dev.as<uint8_t>();
+        }
         if ((rc = q_dev.ensure((size_t)nq * d))) return rc;
         if ((rc = ids_dev.ensure((size_t)nq * k * 4))) return rc;
         if (out_dist && (rc = dist_dev.ensure((size_t)nq * k * 4))) return rc;
-        HIP_TRY(hipMemcpyAsync(b_dev.p, base, (size_t)n * d, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(q_dev.p, queries, (size_t)nq * d, hipMemcpyHostToDevice, s));
-        base_d = b_dev.as<uint8_t>(); q_d = q_dev.as<uint8_t>(); ids_d = ids_dev.as<uint32_t>();
+        q_d = q_dev.as<uint8_t>(); ids_d = ids_dev.as<uint32_t>();
         dist_d = out_dist ? dist_dev.as<float>() : nullptr;
     }
+    const uint32_t* qtags = nullptr;  // tagged: the device copies of the tag words; a sweep with null tags is the untagged instance
+    if (c.tagged && (rc = knn_stage_tags(c, tag_dev, qtag_dev, qtags, s))) return rc;
+    const uint32_t* const tags = tag_dev.as<uint32_t>();
     const size_t heap_stride = ((size_t)slab + 63) & ~(size_t)63;
     if ((rc = bpack.ensure((size_t)n * dp))) return rc;
     if ((rc = bterm.ensure(((size_t)n + 64) * 4))) return rc;  // (the sweep reads whole blocks of 32 rows' terms)
@@ -298,7 +357,7 @@ int gbnns_exact_knn_bytes(int device, const uint8_t* base, uint64_t n, const uin
     if ((rc = keys.ensure(pl.pool ? (size_t)slab * (size_t)k * 8 : heap_stride * (size_t)k * 8))) return rc;
     if (pl.pool && (rc = root.ensure((size_t)slab * 8))) return rc;
     HIP_TRY(hipMemsetAsync(bterm.as<int32_t>() + n, 0, 64 * 4, s));
-    HIP_TRY(launch_knn_bytes_pack(base_d, d, dp, metric, 0, n, bpack.as<int8_t>(), bterm.as<int32_t>(), s));
+    HIP_TRY(launch_knn_bytes_pack(base_d, c.bstride, d, dp, metric, 0, n, bpack.as<int8_t>(), bterm.as<int32_t>(), s));
     for (uint32_t q0 = 0; q0 < nq; q0 += slab) {
         const uint32_t qn = std::min(slab, nq - q0);
         KnnBytesOfferParams op{};
@@ -307,7 +366,7 @@ int gbnns_exact_knn_bytes(int device, const uint8_t* base, uint64_t n, const uin
         op.qterm = qterm.as<int32_t>(); op.thr = thr.as<int32_t>();
         if (pl.pool) { op.pool = keys.as<uint64_t>(); op.root = root.as<uint64_t>(); }
         else { op.heap = keys.as<uint64_t>(); op.heap_stride = heap_stride; }
-        HIP_TRY(launch_knn_bytes_pack(q_d + (size_t)q0 * d, d, dp, metric, 1, qn, qpack.as<int8_t>(), qterm.as<int32_t>(), s));
+        HIP_TRY(launch_knn_bytes_pack(q_d + (size_t)q0 * d, d, d, dp, metric, 1, qn, qpack.as<int8_t>(), qterm.as<int32_t>(), s));
         HIP_TRY(hipMemsetAsync(keys.p, 0xFF, pl.pool ? (size_t)qn * (size_t)k * 8 : heap_stride * (size_t)k * 8, s));
         if (pl.pool) HIP_TRY(hipMemsetAsync(root.p, 0xFF, (size_t)qn * 8, s));
         HIP_TRY(launch_fill_u32(thr.as<uint32_t>(), 0x80000000u, qn, s));  // INT32_MIN: every row passes
@@ -320,6 +379,7 @@ int gbnns_exact_knn_bytes(int device, const uint8_t* base, uint64_t n, const uin
             f.qterm = qterm.as<int32_t>(); f.thr = thr.as<int32_t>(); f.nq = qn; f.dp = dp; f.rows = rows; f.row0 = (uint32_t)r0; f.cap = cap;
             f.shift = metric == GBNNS_METRIC_L2 ? 1 : 0;
             f.cand = cand.as<uint64_t>(); f.count = cnt.as<uint32_t>(); f.overflow = flag.as<uint32_t>();
+            if (qtags) { f.btag = tags + r0; f.qtag = qtags + q0; }
             HIP_TRY(launch_knn_bytes_sweep(f, s));
             return GBNNS_OK;
         };
@@ -362,6 +422,89 @@ int gbnns_exact_knn_bytes(int device, const uint8_t* base, uint64_t n, const uin
     }
     // the temporaries are released below: wait for the work that uses them
     HIP_TRY(hipStreamSynchronize(s));
+    return GBNNS_OK;
+}
+
+template <class T>
+KnnCall<T> knn_free_call(int device, const T* base, uint64_t n, const T* queries, uint64_t n_q, uint32_t d, int k, int metric, int64_t self_offset,
+                         bool tagged, const uint32_t* row_tags, const uint32_t* query_tags, uint32_t* out_ids, float* out_dist, int mem_kind, void* stream) {
+    KnnCall<T> c{};
+    c.device = device; c.base = base; c.bstride = d; c.resident = false; c.n = n; c.queries = queries; c.n_q = n_q; c.d = d; c.k = k;
+    c.metric = metric; c.self_offset = self_offset; c.tagged = tagged; c.row_tags = row_tags; c.query_tags = query_tags;
+    c.out_ids = out_ids; c.out_dist = out_dist; c.mem_kind = mem_kind; c.stream = stream;
+    return c;
+}
+}  // namespace
+
+extern "C" {
+
+int gbnns_exact_knn(int device, const float* base, uint64_t n, const float* queries, uint64_t n_q,
+                    uint32_t d, int k, int metric, int64_t self_offset, uint32_t* out_ids, float* out_dist,
+                    int mem_kind, void* stream) {
+    return knn_float_call(knn_free_call(device, base, n, queries, n_q, d, k, metric, self_offset, false, nullptr, nullptr, out_ids, out_dist, mem_kind, stream));
+}
+
+int gbnns_exact_knn_tagged(int device, const float* base, uint64_t n, const float* queries, uint64_t n_q, uint32_t d, int k, int metric,
+                           int64_t self_offset, const uint32_t* row_tags, const uint32_t* query_tags, uint32_t* out_ids, float* out_dist,
+                           int mem_kind, void* stream) {
+    return knn_float_call(knn_free_call(device, base, n, queries, n_q, d, k, metric, self_offset, true, row_tags, query_tags, out_ids, out_dist, mem_kind, stream));
+}
+
+int gbnns_exact_knn_bytes(int device, const uint8_t* base, uint64_t n, const uint8_t* queries, uint64_t n_q,
+                          uint32_t d, int k, int metric, int64_t self_offset, uint32_t* out_ids, float* out_dist,
+                          int mem_kind, void* stream) {
+    return knn_bytes_call(knn_free_call(device, base, n, queries, n_q, d, k, metric, self_offset, false, nullptr, nullptr, out_ids, out_dist, mem_kind, stream));
+}
+
+int gbnns_exact_knn_bytes_tagged(int device, const uint8_t* base, uint64_t n, const uint8_t* queries, uint64_t n_q, uint32_t d, int k, int metric,
+                                 int64_t self_offset, const uint32_t* row_tags, const uint32_t* query_tags, uint32_t* out_ids, float* out_dist,
+                                 int mem_kind, void* stream) {
+    return knn_bytes_call(knn_free_call(device, base, n, queries, n_q, d, k, metric, self_offset, true, row_tags, query_tags, out_ids, out_dist, mem_kind, stream));
+}
+
+// The same computation over the handle's own table, read in place at its device row stride (d_pad floats / bytes); the row tags are the
+// handle's.  The packed workspace is the call's own: none of the lanes' workspaces is touched.
+int gbnns_index_exact_knn(gbnns_index* ix, const float* queries, const uint8_t* queries_u8, uint64_t n_q, const uint32_t* query_tags, int k,
+                          int64_t self_offset, uint32_t* out_ids, float* out_dist, int mem_kind, void* stream) {
+    if ((queries != nullptr) == (queries_u8 != nullptr))
+        return fail(GBNNS_ERR_INVALID, "gbnns_index_exact_knn: exactly one of queries / queries_u8");
+    if (!ix) return fail(GBNNS_ERR_INVALID, "null argument");
+    if (queries_u8 && !ix->db_b) return fail(GBNNS_ERR_INVALID, "gbnns_index_exact_knn: queries_u8 needs a byte handle (gbnns_index_create_bytes)");
+    if (queries && ix->db_b)
+        return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_index_exact_knn: float queries on a byte handle: there is no mixed-pair scan (uint8 rows against "
+                    "float queries); pass queries_u8, or widen the table and call gbnns_exact_knn");
+    if (query_tags && !ix->tags.p) return fail(GBNNS_ERR_INVALID, "gbnns_index_exact_knn with query_tags but without gbnns_index_set_tags");
+    const bool tagged = query_tags != nullptr;
+    int rc;
+    if (queries) {
+        if (!ix->db) return fail(GBNNS_ERR_INVALID, "gbnns_index_exact_knn: the handle has no original-space table");
+        KnnCall<float> c = knn_free_call(ix->device, ix->db, ix->n, queries, n_q, ix->d, k, ix->metric, self_offset, tagged, ix->tags.as<uint32_t>(),
+                                         query_tags, out_ids, out_dist, mem_kind, stream);
+        c.bstride = ix->d_pad; c.resident = true;
+        // (enter_stream: the deferred calls still owed are joined, as by any call without GBNNS_FLAG_DEFER_JOIN, and `stream` waits for the
+        // handle's work in flight on another stream -- a gbnns_index_set_tags among it)
+        HIP_TRY(hipSetDevice(ix->device));
+        if ((rc = enter_stream(ix, static_cast<hipStream_t>(stream)))) return rc;
+        rc = knn_float_call(c);
+    } else {
+        KnnCall<uint8_t> c = knn_free_call(ix->device, ix->db_b, ix->n, queries_u8, n_q, ix->d, k, ix->metric, self_offset, tagged,
+                                           ix->tags.as<uint32_t>(), query_tags, out_ids, out_dist, mem_kind, stream);
+        c.bstride = ix->d_pad; c.resident = true;
+        HIP_TRY(hipSetDevice(ix->device));
+        if ((rc = enter_stream(ix, static_cast<hipStream_t>(stream)))) return rc;
+        rc = knn_bytes_call(c);
+    }
+    if (rc == GBNNS_OK && n_q) ix->in_flight = false;  // (the call returned behind a synchronisation of its stream)
+    return rc;
+}
+
+int gbnns_debug_knn_bytes_plan(uint64_t n, uint64_t n_q, uint32_t d, int k, uint32_t* dp, uint32_t* cap, uint64_t* first_rows,
+                               uint64_t* max_chunk, int* pool) {
+    if (!dp || !cap || !first_rows || !max_chunk || !pool) return fail(GBNNS_ERR_INVALID, "gbnns_debug_knn_bytes_plan: null output");
+    if (n == 0 || n >= (1ull << 32) - 1 || n_q >= (1ull << 31) || d == 0 || d > 256 || k < 1 || k > 4096)
+        return fail(GBNNS_ERR_INVALID, "gbnns_debug_knn_bytes_plan: not a shape gbnns_exact_knn_bytes takes");
+    const KnnBytesPlan pl = knn_bytes_plan(n, n_q, d, k);
+    *dp = pl.dp; *cap = pl.cap; *first_rows = pl.first_rows; *max_chunk = pl.max_chunk; *pool = pl.pool ? 1 : 0;
     return GBNNS_OK;
 }
 

@@ -273,6 +273,10 @@ struct KnnParams {
     float* out_dist;         // optional [nq x k]
     uint64_t row0;           // id of `base` row 0 (scans of a slice of the base set; 0 = the whole set)
     int32_t keep_heap;       // 1: leave the heaps as they are (no sort, no outputs): more rows follow
+    // gbnns_exact_knn_tagged (last, so that no other field moves): row j is offered to query i only when (row_tags[j] & query_tags[i]) != 0 --
+    // the tagged instances of the scan kernels; the rescore / pool kernels see allowed candidates only and do not look
+    const uint32_t* row_tags;   // [row0 + n] tag words by row ID (not by row of `base`), or nullptr: the untagged instances
+    const uint32_t* query_tags; // [nq]
 };
 hipError_t launch_knn_scan(const KnnParams& p, int metric, hipStream_t s);
 
@@ -292,6 +296,9 @@ struct KnnFilterParams {
     uint32_t* cand;          // [nq x cap] ids that passed
     uint32_t* count;         // [nq] how many passed (may exceed cap: then *overflow is set and the chunk is scanned exactly)
     uint32_t* overflow;      // [1]
+    // gbnns_exact_knn_tagged (last): a pair whose row is not allowed for its query is not a hit -- neither counted nor stored
+    const uint32_t* btag;    // [rows] tag words of the chunk's rows, 16-byte aligned and readable (any value) up to the end of the chunk's last block of 32, or nullptr: the untagged instances
+    const uint32_t* qtag;    // [nq]
 };
 hipError_t launch_knn_filter(const KnnFilterParams& p, hipStream_t s);
 // thresholds from the heaps: rhs[q] = 0.5 ((1 - c) |q|^2 - d_k(q)), -inf while the heap is not full
@@ -331,7 +338,8 @@ constexpr float kKnnFilterSlack = 1.0f / 4096.0f;  // c: |approximate - referenc
 // and with s = (x'.q' << shift) + bterm (shift 1 for L2, 0 for NEG_DOT) the exact distance is  qterm - s.
 constexpr uint32_t kKnnBytesKStep = 32;    // K of one v_mfma_i32_32x32x32_i8
 constexpr uint32_t kKnnBytesRowBlock = 32; // base rows of one product
-hipError_t launch_knn_bytes_pack(const uint8_t* x, uint32_t dim, uint32_t dp, int metric, int query_side, uint64_t rows, int8_t* packed,
+// (`stride` = bytes between rows of x, >= dim: d for a caller's array, d_pad for a byte handle's resident table)
+hipError_t launch_knn_bytes_pack(const uint8_t* x, uint32_t stride, uint32_t dim, uint32_t dp, int metric, int query_side, uint64_t rows, int8_t* packed,
                                  int32_t* term, hipStream_t s);
 struct KnnBytesSweepParams {
     const int8_t* qpack;     // [nq x dp]
@@ -347,6 +355,9 @@ struct KnnBytesSweepParams {
     uint64_t* cand;          // [nq x cap] keys (knn_fkey(float(distance)) << 32 | id) of the rows kept
     uint32_t* count;         // [nq] how many were kept (may exceed cap: then *overflow is set and the chunk is swept again in pieces)
     uint32_t* overflow;      // [1]
+    // gbnns_exact_knn_bytes_tagged (last): as KnnFilterParams::btag / qtag
+    const uint32_t* btag;    // [rows] tag words of the chunk's rows (16-byte aligned, readable to the end of the last block of 32), or nullptr
+    const uint32_t* qtag;    // [nq]
 };
 hipError_t launch_knn_bytes_sweep(const KnnBytesSweepParams& p, hipStream_t s);
 // the kept keys offered to a query's heap (pool == nullptr; [k x heap_stride]) or pool ([nq x k] + root [nq]); then the new thresholds

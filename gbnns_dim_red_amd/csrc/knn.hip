@@ -32,10 +32,13 @@ constexpr int kKnnThreads = 128;
 constexpr int kKnnTile = 64;  // base rows per LDS tile
 
 // S = 16-byte steps of a query held in registers (d <= 4 * S), QPT = queries per thread.
-template <int METRIC, int S, int QPT>
+// TAG (gbnns_exact_knn_tagged): a row whose tag word shares no bit with the query's is not offered; the tile's tag words are staged in LDS
+// with the tile, once for all its queries.  Same arithmetic; the untagged instances are the code they were.
+template <int METRIC, int S, int QPT, bool TAG>
 __global__ __launch_bounds__(kKnnThreads) void knn_scan_kernel(KnnParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float4* tile = reinterpret_cast<float4*>(smem);  // [kKnnTile][S]
+    uint32_t* tile_tag = reinterpret_cast<uint32_t*>(tile + kKnnTile * S);  // [kKnnTile], TAG instances only
     const int t = threadIdx.x;
     // L2Metric::Dist uses the first 4 * floor(d / 4) dims only; the dot form is offered for d % 8 == 0
     const uint32_t steps = p.dim >> 2;
@@ -46,11 +49,13 @@ __global__ __launch_bounds__(kKnnThreads) void knn_scan_kernel(KnnParams p) {
     uint32_t qi[QPT];
     bool live[QPT];
     uint64_t root[QPT];
+    uint32_t qtag[QPT];
 #pragma unroll
     for (int a = 0; a < QPT; ++a) {
         qi[a] = (blockIdx.x * QPT + a) * kKnnThreads + t;
         live[a] = qi[a] < p.nq;
         root[a] = live[a] ? p.heap[qi[a]] : ~0ull;  // (all-ones in a fresh heap; an earlier slice's root otherwise)
+        if constexpr (TAG) qtag[a] = live[a] ? p.query_tags[qi[a]] : 0u;
         const float* qp = p.q + (size_t)(live[a] ? qi[a] : 0u) * p.qstride;
 #pragma unroll
         for (int c = 0; c < S; ++c) {
@@ -75,6 +80,9 @@ __global__ __launch_bounds__(kKnnThreads) void knn_scan_kernel(KnnParams p) {
                 else v = make_float4(bp[4 * c], bp[4 * c + 1], bp[4 * c + 2], bp[4 * c + 3]);
             }
             tile[e] = v;
+        }
+        if constexpr (TAG) {
+            if (t < kKnnTile) tile_tag[t] = base0 + t < p.n ? p.row_tags[p.row0 + base0 + t] : 0u;
         }
         __syncthreads();
         const int rows = (p.n - base0 < (uint64_t)kKnnTile) ? (int)(p.n - base0) : kKnnTile;
@@ -124,10 +132,13 @@ __global__ __launch_bounds__(kKnnThreads) void knn_scan_kernel(KnnParams p) {
                 }
             }
             const uint64_t row = p.row0 + base0 + r;
+            uint32_t rtag = 0;
+            if constexpr (TAG) rtag = tile_tag[r];
 #pragma unroll
             for (int a = 0; a < QPT; ++a) {
                 const uint64_t key = ((uint64_t)knn_fkey(dist[a]) << 32) | (uint32_t)row;
-                const bool self = p.self_offset >= 0 && row == (uint64_t)qi[a] + (uint64_t)p.self_offset;
+                bool self = p.self_offset >= 0 && row == (uint64_t)qi[a] + (uint64_t)p.self_offset;
+                if constexpr (TAG) self = self || (rtag & qtag[a]) == 0u;  // (a disallowed row is dropped where the query's own row is)
                 if (live[a] && !self && key < root[a])
                     root[a] = heap_replace_root(p.heap + qi[a], p.heap_stride, p.k, key);
             }
@@ -163,19 +174,23 @@ __global__ __launch_bounds__(kKnnThreads) void knn_scan_kernel(KnnParams p) {
 // the tile [R][steps rounded up to 8, zero filled] sits in LDS and is read by broadcast.  Per distance the
 // operations and their order are exactly those of the narrow kernel (a zero-filled step adds +0 to sums that
 // are never -0).  Offers to the heap happen in ascending row order, as before.
-template <int METRIC, int R>
+// TAG: as in knn_scan_kernel (the tile's R tag words behind the tile in LDS).
+template <int METRIC, int R, bool TAG>
 __global__ __launch_bounds__(kKnnThreads) void knn_scan_wide_kernel(KnnParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float4* tile = reinterpret_cast<float4*>(smem);  // [R][steps8]
     const int t = threadIdx.x;
     const uint32_t steps = p.dim >> 2;
     const uint32_t steps8 = (steps + 7u) & ~7u;
+    uint32_t* tile_tag = reinterpret_cast<uint32_t*>(tile + (size_t)R * steps8);  // [R], TAG instances only
     const bool vec_ok = (p.bstride & 3u) == 0;
     const bool qvec_ok = (p.qstride & 3u) == 0;
     const uint32_t qi = blockIdx.x * kKnnThreads + t;
     const bool live = qi < p.nq;
     const float* qp = p.q + (size_t)(live ? qi : 0u) * p.qstride;
     uint64_t root = live ? p.heap[qi] : ~0ull;
+    uint32_t qtag = 0;
+    if constexpr (TAG) qtag = live ? p.query_tags[qi] : 0u;
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
 
     for (uint64_t base0 = 0; base0 < p.n; base0 += R) {
@@ -190,6 +205,9 @@ __global__ __launch_bounds__(kKnnThreads) void knn_scan_wide_kernel(KnnParams p)
                 else v = make_float4(bp[4 * c], bp[4 * c + 1], bp[4 * c + 2], bp[4 * c + 3]);
             }
             tile[e] = v;
+        }
+        if constexpr (TAG) {
+            if (t < R) tile_tag[t] = base0 + t < p.n ? p.row_tags[p.row0 + base0 + t] : 0u;
         }
         __syncthreads();
         float dist[R];
@@ -262,7 +280,8 @@ __global__ __launch_bounds__(kKnnThreads) void knn_scan_wide_kernel(KnnParams p)
         for (int r = 0; r < R; ++r) {
             const uint64_t row = p.row0 + base0 + r;
             const uint64_t key = ((uint64_t)knn_fkey(dist[r]) << 32) | (uint32_t)row;
-            const bool self = p.self_offset >= 0 && row == (uint64_t)qi + (uint64_t)p.self_offset;
+            bool self = p.self_offset >= 0 && row == (uint64_t)qi + (uint64_t)p.self_offset;
+            if constexpr (TAG) self = self || (tile_tag[r] & qtag) == 0u;
             if (live && base0 + r < p.n && !self && key < root)
                 root = heap_replace_root(p.heap + qi, p.heap_stride, p.k, key);
         }
@@ -283,41 +302,43 @@ __global__ __launch_bounds__(kKnnThreads) void knn_scan_wide_kernel(KnnParams p)
     }
 }
 
-template <int METRIC, int R>
+template <int METRIC, int R, bool TAG>
 hipError_t launch_knn_wide(const KnnParams& p, hipStream_t s) {
     const uint32_t steps8 = ((p.dim >> 2) + 7u) & ~7u;
-    const size_t lds = (size_t)R * steps8 * 16;
+    const size_t lds = (size_t)R * steps8 * 16 + (TAG ? R * 4 : 0);
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(knn_scan_wide_kernel<METRIC, R>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(knn_scan_wide_kernel<METRIC, R, TAG>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     const unsigned grid = (unsigned)((p.nq + (uint64_t)kKnnThreads - 1) / (uint64_t)kKnnThreads);
-    hipLaunchKernelGGL((knn_scan_wide_kernel<METRIC, R>), dim3(grid), dim3(kKnnThreads), lds, s, p);
+    hipLaunchKernelGGL((knn_scan_wide_kernel<METRIC, R, TAG>), dim3(grid), dim3(kKnnThreads), lds, s, p);
     return hipGetLastError();
 }
 
-template <int METRIC, int S, int QPT>
+template <int METRIC, int S, int QPT, bool TAG>
 hipError_t launch_knn_t(const KnnParams& p, hipStream_t s) {
-    const size_t lds = (size_t)kKnnTile * S * 16;
+    const size_t lds = (size_t)kKnnTile * S * 16 + (TAG ? kKnnTile * 4 : 0);
     const unsigned grid = (unsigned)((p.nq + (uint64_t)kKnnThreads * QPT - 1) / ((uint64_t)kKnnThreads * QPT));
-    hipLaunchKernelGGL((knn_scan_kernel<METRIC, S, QPT>), dim3(grid), dim3(kKnnThreads), lds, s, p);
+    hipLaunchKernelGGL((knn_scan_kernel<METRIC, S, QPT, TAG>), dim3(grid), dim3(kKnnThreads), lds, s, p);
     return hipGetLastError();
 }
 
-template <int METRIC>
+template <int METRIC, bool TAG>
 hipError_t launch_knn_m(const KnnParams& p, hipStream_t s) {
-    if (p.dim <= 32) return launch_knn_t<METRIC, 8, 2>(p, s);
-    if (p.dim <= 64) return launch_knn_t<METRIC, 16, 2>(p, s);
-    if (p.dim <= 128) return launch_knn_t<METRIC, 32, 1>(p, s);
+    if (p.dim <= 32) return launch_knn_t<METRIC, 8, 2, TAG>(p, s);
+    if (p.dim <= 64) return launch_knn_t<METRIC, 16, 2, TAG>(p, s);
+    if (p.dim <= 128) return launch_knn_t<METRIC, 32, 1, TAG>(p, s);
     // wide rows: tiles of 16 (L2) / 8 (dot) rows with their running sums in registers; the [R][d] tile must fit the
     // 160 KB of LDS (64 d bytes at R = 16), so very wide rows take fewer rows per tile: d <= 2560 / 5120 / 8192
+    // (a tagged instance's R tag words behind the tile: d = 8192 at R = 4 is 128 KB + 16 bytes)
     const size_t row_bytes = (size_t)(((p.dim >> 2) + 7u) & ~7u) * 16;
+    const size_t room = 160 * 1024 - (TAG ? 64 : 0);
     if constexpr (METRIC == 0) {
-        if (16 * row_bytes <= 160 * 1024) return launch_knn_wide<0, 16>(p, s);
+        if (16 * row_bytes <= room) return launch_knn_wide<0, 16, TAG>(p, s);
     }
-    if (8 * row_bytes <= 160 * 1024) return launch_knn_wide<METRIC, 8>(p, s);
-    if (4 * row_bytes <= 160 * 1024) return launch_knn_wide<METRIC, 4>(p, s);
+    if (8 * row_bytes <= room) return launch_knn_wide<METRIC, 8, TAG>(p, s);
+    if (4 * row_bytes <= room) return launch_knn_wide<METRIC, 4, TAG>(p, s);
     return hipErrorInvalidValue;  // d > 10240: refused by gbnns_exact_knn (d <= 8192) before it gets here
 }
 
@@ -396,7 +417,11 @@ __global__ __launch_bounds__(256) void knn_pack_kernel(const float* x, uint32_t 
 // while every workgroup sweeps it).  The accumulators start at -0.5 (1 - c) |x|^2 of their rows (16 rows of the block
 // per lane: four float4 loads of the norms), so a kept pair is  max over the lane's 16 rows >= rhs[query]  -- eight
 // v_max3 and one compare per tile beside its six matrix instructions.
-template <int KSTEPS, int QB>
+// TAG (gbnns_exact_knn_tagged): a pair whose row is not allowed for its query is not a hit -- neither counted nor stored.  The tag words of
+// a lane's 16 rows travel with the block's norms (four more 16-byte requests, the same address pattern; the array is padded like bnorm)
+// and are looked at where hits are counted: under a selective filter a query's threshold is its k-th ALLOWED distance, rows of every
+// tile pass it, and a fetch in the hit path was a dependent load in most tiles (DESIGN.md 5.1 has both measurements).
+template <int KSTEPS, int QB, bool TAG>
 __global__ __launch_bounds__(256) void knn_filter_kernel(KnnFilterParams p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t r = lane & 31, h = lane >> 5;
@@ -406,10 +431,12 @@ __global__ __launch_bounds__(256) void knn_filter_kernel(KnnFilterParams p) {
     // B fragments: query q0 + 32 b + r, k = 16 s + 8 h .. + 7 -> group 2 s + h: hi at halfword 16 (2 s + h), lo 8 further
     bf16x8 qh[QB][KSTEPS], ql[QB][KSTEPS];
     float rhs[QB];
+    uint32_t qtag[QB];
 #pragma unroll
     for (int b = 0; b < QB; ++b) {
         const uint32_t qi = q0 + 32u * b + r;
         const bool ok = qi < p.nq;
+        if constexpr (TAG) qtag[b] = ok ? p.qtag[qi] : 0u;
         const uint16_t* qp = p.qpack + (size_t)(ok ? qi : 0u) * groups * 16;
 #pragma unroll
         for (int s = 0; s < KSTEPS; ++s) {
@@ -423,6 +450,7 @@ __global__ __launch_bounds__(256) void knn_filter_kernel(KnnFilterParams p) {
 #pragma unroll
     for (int b = 0; b < QB; ++b) {
         asm volatile("" ::"v"(rhs[b]));
+        if constexpr (TAG) asm volatile("" ::"v"(qtag[b]));
 #pragma unroll
         for (int s = 0; s < KSTEPS; ++s) asm volatile("" ::"v"(qh[b][s]), "v"(ql[b][s]));
     }
@@ -439,7 +467,7 @@ __global__ __launch_bounds__(256) void knn_filter_kernel(KnnFilterParams p) {
     // refused where the hits are stored.)
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     typedef float f32x4v __attribute__((ext_vector_type(4)));
-    auto request_block = [&](uint32_t rb, u32x4 (&xh)[KSTEPS], u32x4 (&xl)[KSTEPS], f32x4v (&nx)[4]) {
+    auto request_block = [&](uint32_t rb, u32x4 (&xh)[KSTEPS], u32x4 (&xl)[KSTEPS], f32x4v (&nx)[4], u32x4 (&tg)[4]) {
         const uint32_t j = rb * 32u + r;
         const uint16_t* bp = p.bpack + ((size_t)(j < p.rows ? j : 0u) * groups + h) * 16;
         const float* np = p.bnorm + rb * 32u + 4u * h;
@@ -451,16 +479,25 @@ __global__ __launch_bounds__(256) void knn_filter_kernel(KnnFilterParams p) {
 #pragma unroll
         for (int g = 0; g < 4; ++g)  // accumulator registers 4 g .. 4 g + 3 = rows 8 g + 4 h + 0 .. 3 of the block
             asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(nx[g]) : "v"(np + 8 * g));
+        if constexpr (TAG) {
+            const uint32_t* tp = p.btag + rb * 32u + 4u * h;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(tg[g]) : "v"(tp + 8 * g));
+        }
     };
-    auto landed = [&](u32x4 (&xh)[KSTEPS], u32x4 (&xl)[KSTEPS], f32x4v (&nx)[4]) {
+    auto landed = [&](u32x4 (&xh)[KSTEPS], u32x4 (&xl)[KSTEPS], f32x4v (&nx)[4], u32x4 (&tg)[4]) {
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(nx[0]));
 #pragma unroll
         for (int g = 1; g < 4; ++g) asm volatile("" : "+v"(nx[g]));
 #pragma unroll
         for (int s = 0; s < KSTEPS; ++s) asm volatile("" : "+v"(xh[s]), "+v"(xl[s]));
+        if constexpr (TAG) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(tg[g]));
+        }
     };
     // the products and the test of one block of rows against the QB query blocks
-    auto sweep_block = [&](uint32_t rb, const u32x4 (&xhr)[KSTEPS], const u32x4 (&xlr)[KSTEPS], const f32x4v (&nx)[4]) {
+    auto sweep_block = [&](uint32_t rb, const u32x4 (&xhr)[KSTEPS], const u32x4 (&xlr)[KSTEPS], const f32x4v (&nx)[4], const u32x4 (&tg)[4]) {
         bf16x8 xh[KSTEPS], xl[KSTEPS];
 #pragma unroll
         for (int s = 0; s < KSTEPS; ++s) { xh[s] = __builtin_bit_cast(bf16x8, xhr[s]); xl[s] = __builtin_bit_cast(bf16x8, xlr[s]); }
@@ -496,6 +533,12 @@ __global__ __launch_bounds__(256) void knn_filter_kernel(KnnFilterParams p) {
                     const uint32_t j = rb * 32u + (uint32_t)((v & 3) + 8 * (v >> 2)) + 4u * h;
                     hits |= (acc[v] >= rhs[b] && j < p.rows) ? 1u << v : 0u;  // (a threshold of -inf -- list not full yet -- lets -inf through too)
                 }
+                if constexpr (TAG) {
+                    uint32_t tm = 0;
+#pragma unroll
+                    for (int v = 0; v < 16; ++v) tm |= ((tg[v >> 2][v & 3] & qtag[b]) ? 1u : 0u) << v;
+                    hits &= tm;
+                }
                 if (hits) {
                     uint32_t pos = atomicAdd(&p.count[qv], (uint32_t)__popc(hits));
                     do {
@@ -512,15 +555,16 @@ __global__ __launch_bounds__(256) void knn_filter_kernel(KnnFilterParams p) {
     // two register sets in turn: wait for the set at hand, request the next block into the other one, sweep
     u32x4 xh0[KSTEPS], xl0[KSTEPS], xh1[KSTEPS], xl1[KSTEPS];
     f32x4v nx0[4], nx1[4];
-    request_block(b_lo, xh0, xl0, nx0);
+    u32x4 tg0[4], tg1[4];
+    request_block(b_lo, xh0, xl0, nx0, tg0);
     for (uint32_t rb = b_lo;;) {
-        landed(xh0, xl0, nx0);
-        if (rb + 1u < b_hi) request_block(rb + 1u, xh1, xl1, nx1);
-        sweep_block(rb, xh0, xl0, nx0);
+        landed(xh0, xl0, nx0, tg0);
+        if (rb + 1u < b_hi) request_block(rb + 1u, xh1, xl1, nx1, tg1);
+        sweep_block(rb, xh0, xl0, nx0, tg0);
         if (++rb >= b_hi) break;
-        landed(xh1, xl1, nx1);
-        if (rb + 1u < b_hi) request_block(rb + 1u, xh0, xl0, nx0);
-        sweep_block(rb, xh1, xl1, nx1);
+        landed(xh1, xl1, nx1, tg1);
+        if (rb + 1u < b_hi) request_block(rb + 1u, xh0, xl0, nx0, tg0);
+        sweep_block(rb, xh1, xl1, nx1, tg1);
         if (++rb >= b_hi) break;
     }
 }
@@ -696,8 +740,8 @@ __global__ __launch_bounds__(64) void knn_pool_finalize_kernel(KnnPoolParams p) 
     }
 }
 
-template <int KSTEPS, int QB>
-hipError_t launch_knn_filter_t(const KnnFilterParams& p, hipStream_t s) {
+template <int KSTEPS, int QB, bool TAG>
+hipError_t launch_knn_filter_tt(const KnnFilterParams& p, hipStream_t s) {
     const unsigned gx = (p.nq + QB * 128u - 1) / (QB * 128u);
     const unsigned blocks = (p.rows + 31u) >> 5;
     static const unsigned simds = [] {  // 4 SIMDs per CU of the current device (the MI355X: 1 024)
@@ -708,14 +752,23 @@ hipError_t launch_knn_filter_t(const KnnFilterParams& p, hipStream_t s) {
     unsigned gy = gx >= simds ? 1u : (simds + gx - 1) / gx;   // enough workgroups for every SIMD
     if (gy > blocks) gy = blocks;
     if (gy < 1u) gy = 1u;
-    hipLaunchKernelGGL((knn_filter_kernel<KSTEPS, QB>), dim3(gx, gy), dim3(256), 0, s, p);
+    hipLaunchKernelGGL((knn_filter_kernel<KSTEPS, QB, TAG>), dim3(gx, gy), dim3(256), 0, s, p);
     return hipGetLastError();
+}
+
+template <int KSTEPS, int QB>
+hipError_t launch_knn_filter_t(const KnnFilterParams& p, hipStream_t s) {
+    return p.btag ? launch_knn_filter_tt<KSTEPS, QB, true>(p, s) : launch_knn_filter_tt<KSTEPS, QB, false>(p, s);
 }
 }  // namespace
 
 hipError_t launch_knn_scan(const KnnParams& p, int metric, hipStream_t s) {
     if (p.nq == 0) return hipSuccess;
-    return metric == 1 ? launch_knn_m<1>(p, s) : launch_knn_m<0>(p, s);
+    if (p.row_tags) {
+        if (!p.query_tags) return hipErrorInvalidValue;
+        return metric == 1 ? launch_knn_m<1, true>(p, s) : launch_knn_m<0, true>(p, s);
+    }
+    return metric == 1 ? launch_knn_m<1, false>(p, s) : launch_knn_m<0, false>(p, s);
 }
 
 hipError_t launch_knn_pack(const float* x, uint32_t stride, uint32_t dim, uint64_t rows, uint16_t* packed, float* norms, hipStream_t s) {
@@ -728,7 +781,8 @@ hipError_t launch_knn_pack(const float* x, uint32_t stride, uint32_t dim, uint64
 
 hipError_t launch_knn_filter(const KnnFilterParams& p, hipStream_t s) {
     if (p.nq == 0 || p.rows == 0) return hipSuccess;
-    switch (p.dp >> 4) {   // K steps of 16; query blocks per wavefront by what the operands leave of the register file
+    if (p.btag && !p.qtag) return hipErrorInvalidValue;
+    switch (p.dp >> 4) {  // K steps of 16; query blocks per wavefront by what the operands leave of the register file
         case 1: return launch_knn_filter_t<1, 4>(p, s);
         case 2: return launch_knn_filter_t<2, 4>(p, s);
         case 3: return launch_knn_filter_t<3, 2>(p, s);

@@ -33,7 +33,7 @@ constexpr int32_t kPassNone = INT32_MAX;  // ... of a lane without a query
 // G (a power of two >= dp / 16) neighbouring lanes per row, lane g packs columns 16 g .. 16 g + 15: one 16-byte store;
 // the row's sum of squares and sum are folded over the G lanes.  `used` = columns that count (4 floor(d / 4) for L2).
 template <int G>
-__global__ __launch_bounds__(256) void knn_bytes_pack_kernel(const uint8_t* x, uint32_t dim, uint32_t used, uint32_t dp, uint64_t rows,
+__global__ __launch_bounds__(256) void knn_bytes_pack_kernel(const uint8_t* x, uint32_t stride, uint32_t dim, uint32_t used, uint32_t dp, uint64_t rows,
                                                              int neg_dot, int query_side, int8_t* packed, int32_t* term) {
     const uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     const uint64_t row = e / G;
@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void knn_bytes_pack_kernel(const uint8_t* x, u
     const bool live = row < rows && g * 16u < dp;
     int32_t n2 = 0, sm = 0;
     if (live) {
-        const uint8_t* xr = x + (size_t)row * dim;
+        const uint8_t* xr = x + (size_t)row * stride;
         uint32_t w[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
@@ -77,7 +77,10 @@ __device__ __forceinline__ int32_t knn_bytes_thr(uint64_t root, int32_t qterm) {
 // products).  Lane (r, h) holds row / query r and the 16 bytes 32 s + 16 h .. + 15 of K step s for both operands: whatever
 // order the instruction gives those 16 + 16 columns, it is the same for A and B, and a dot product does not see it.
 // C/D: register v of lane (r, h) = row (v & 3) + 8 (v >> 2) + 4 h of the block, column r.
-template <int KSTEPS, int QB>
+// TAG (gbnns_exact_knn_bytes_tagged): a pair whose row is not allowed for its query -- (btag[row] & qtag[query]) == 0 -- is not a hit.  The
+// tag words of a lane's 16 rows travel with the block's terms (four more 16-byte requests, same address pattern, the array padded like
+// bterm) and are looked at where hits are counted, as in knn_filter_kernel: DESIGN.md 5.1 has the measurement against a fetch there.
+template <int KSTEPS, int QB, bool TAG>
 __global__ __launch_bounds__(256) void knn_bytes_sweep_kernel(KnnBytesSweepParams p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t r = lane & 31, h = lane >> 5;
@@ -85,6 +88,7 @@ __global__ __launch_bounds__(256) void knn_bytes_sweep_kernel(KnnBytesSweepParam
     if (q0 >= p.nq) return;
     i32x4 qf[QB][KSTEPS];
     int32_t thr[QB], qterm[QB];
+    uint32_t qtag[QB];
 #pragma unroll
     for (int b = 0; b < QB; ++b) {
         const uint32_t qi = q0 + 32u * b + r;
@@ -94,11 +98,13 @@ __global__ __launch_bounds__(256) void knn_bytes_sweep_kernel(KnnBytesSweepParam
         for (int s = 0; s < KSTEPS; ++s) qf[b][s] = *reinterpret_cast<const i32x4*>(qp + 32 * s);
         thr[b] = ok ? p.thr[qi] : kPassNone;  // (a query beyond the batch keeps nothing: s never reaches INT32_MAX)
         qterm[b] = ok ? p.qterm[qi] : 0;
+        if constexpr (TAG) qtag[b] = ok ? p.qtag[qi] : 0u;
     }
     // (every compiler-issued load is used here, once: its waits then sit in this prologue and not inside the sweep)
 #pragma unroll
     for (int b = 0; b < QB; ++b) {
         asm volatile("" ::"v"(thr[b]), "v"(qterm[b]));
+        if constexpr (TAG) asm volatile("" ::"v"(qtag[b]));
 #pragma unroll
         for (int s = 0; s < KSTEPS; ++s) asm volatile("" ::"v"(qf[b][s]));
     }
@@ -109,7 +115,7 @@ __global__ __launch_bounds__(256) void knn_bytes_sweep_kernel(KnnBytesSweepParam
     // Fragments and terms of one block of 32 rows (rows beyond the chunk read row 0; the terms' array is readable 64
     // entries beyond the set; such a row is refused where the hits are stored), requested by hand-written loads, as in
     // knn_filter_kernel (knn.hip): `landed` is the one wait, placed in front of the next requests.
-    auto request_block = [&](uint32_t rb, i32x4 (&xa)[KSTEPS], i32x4 (&bt)[4]) {
+    auto request_block = [&](uint32_t rb, i32x4 (&xa)[KSTEPS], i32x4 (&bt)[4], i32x4 (&tg)[4]) {
         const uint32_t j = rb * 32u + r;
         const int8_t* bp = p.bpack + (size_t)(j < p.rows ? j : 0u) * p.dp + 16u * h;
         const int32_t* np = p.bterm + rb * 32u + 4u * h;
@@ -118,16 +124,25 @@ __global__ __launch_bounds__(256) void knn_bytes_sweep_kernel(KnnBytesSweepParam
 #pragma unroll
         for (int g = 0; g < 4; ++g)  // accumulator registers 4 g .. 4 g + 3 = rows 8 g + 4 h + 0 .. 3 of the block
             asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(bt[g]) : "v"(np + 8 * g));
+        if constexpr (TAG) {
+            const uint32_t* tp = p.btag + rb * 32u + 4u * h;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(tg[g]) : "v"(tp + 8 * g));
+        }
     };
-    auto landed = [&](i32x4 (&xa)[KSTEPS], i32x4 (&bt)[4]) {
+    auto landed = [&](i32x4 (&xa)[KSTEPS], i32x4 (&bt)[4], i32x4 (&tg)[4]) {
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(bt[0]));
 #pragma unroll
         for (int g = 1; g < 4; ++g) asm volatile("" : "+v"(bt[g]));
 #pragma unroll
         for (int s = 0; s < KSTEPS; ++s) asm volatile("" : "+v"(xa[s]));
+        if constexpr (TAG) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(tg[g]));
+        }
     };
     const i32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    auto sweep_block = [&](uint32_t rb, const i32x4 (&xa)[KSTEPS], const i32x4 (&bt)[4]) {
+    auto sweep_block = [&](uint32_t rb, const i32x4 (&xa)[KSTEPS], const i32x4 (&bt)[4], const i32x4 (&tg)[4]) {
 #pragma unroll
         for (int b = 0; b < QB; ++b) {
             i32x16 acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(xa[0], qf[b][0], zero, 0, 0, 0);
@@ -149,6 +164,12 @@ __global__ __launch_bounds__(256) void knn_bytes_sweep_kernel(KnnBytesSweepParam
                     const uint32_t j = rb * 32u + (uint32_t)((v & 3) + 8 * (v >> 2)) + 4u * h;
                     hits |= (sv[v] >= thr[b] && j < p.rows) ? 1u << v : 0u;
                 }
+                if constexpr (TAG) {
+                    uint32_t m = 0;
+#pragma unroll
+                    for (int v = 0; v < 16; ++v) m |= (((uint32_t)tg[v >> 2][v & 3] & qtag[b]) ? 1u : 0u) << v;
+                    hits &= m;
+                }
                 if (hits) {
                     uint32_t pos = atomicAdd(&p.count[qv], (uint32_t)__popc(hits));
 #pragma unroll
@@ -166,16 +187,16 @@ __global__ __launch_bounds__(256) void knn_bytes_sweep_kernel(KnnBytesSweepParam
         }
     };
     // two register sets in turn: wait for the set at hand, request the next block into the other one, sweep
-    i32x4 xa0[KSTEPS], xa1[KSTEPS], bt0[4], bt1[4];
-    request_block(b_lo, xa0, bt0);
+    i32x4 xa0[KSTEPS], xa1[KSTEPS], bt0[4], bt1[4], tg0[4], tg1[4];
+    request_block(b_lo, xa0, bt0, tg0);
     for (uint32_t rb = b_lo;;) {
-        landed(xa0, bt0);
-        if (rb + 1u < b_hi) request_block(rb + 1u, xa1, bt1);
-        sweep_block(rb, xa0, bt0);
+        landed(xa0, bt0, tg0);
+        if (rb + 1u < b_hi) request_block(rb + 1u, xa1, bt1, tg1);
+        sweep_block(rb, xa0, bt0, tg0);
         if (++rb >= b_hi) break;
-        landed(xa1, bt1);
-        if (rb + 1u < b_hi) request_block(rb + 1u, xa0, bt0);
-        sweep_block(rb, xa1, bt1);
+        landed(xa1, bt1, tg1);
+        if (rb + 1u < b_hi) request_block(rb + 1u, xa0, bt0, tg0);
+        sweep_block(rb, xa1, bt1, tg1);
         if (++rb >= b_hi) break;
     }
 }
@@ -235,16 +256,16 @@ __global__ __launch_bounds__(64) void knn_bytes_offer_pool_kernel(KnnBytesOfferP
 }
 
 template <int G>
-hipError_t launch_pack_t(const uint8_t* x, uint32_t dim, uint32_t used, uint32_t dp, uint64_t rows, int neg_dot, int query_side, int8_t* packed,
+hipError_t launch_pack_t(const uint8_t* x, uint32_t stride, uint32_t dim, uint32_t used, uint32_t dp, uint64_t rows, int neg_dot, int query_side, int8_t* packed,
                          int32_t* term, hipStream_t s) {
     const uint64_t threads = rows * G;
-    hipLaunchKernelGGL(knn_bytes_pack_kernel<G>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, x, dim, used, dp, rows, neg_dot,
+    hipLaunchKernelGGL(knn_bytes_pack_kernel<G>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, x, stride, dim, used, dp, rows, neg_dot,
                        query_side, packed, term);
     return hipGetLastError();
 }
 
-template <int KSTEPS, int QB>
-hipError_t launch_sweep_t(const KnnBytesSweepParams& p, hipStream_t s) {
+template <int KSTEPS, int QB, bool TAG>
+hipError_t launch_sweep_tt(const KnnBytesSweepParams& p, hipStream_t s) {
     const unsigned gx = (p.nq + QB * 128u - 1) / (QB * 128u);
     const unsigned blocks = (p.rows + 31u) >> 5;
     static const unsigned simds = [] {  // 4 SIMDs per CU of the current device (the MI355X: 1 024)
@@ -255,27 +276,32 @@ hipError_t launch_sweep_t(const KnnBytesSweepParams& p, hipStream_t s) {
     unsigned gy = gx >= simds ? 1u : (simds + gx - 1) / gx;  // enough workgroups for every SIMD
     if (gy > blocks) gy = blocks;
     if (gy < 1u) gy = 1u;
-    hipLaunchKernelGGL((knn_bytes_sweep_kernel<KSTEPS, QB>), dim3(gx, gy), dim3(256), 0, s, p);
+    hipLaunchKernelGGL((knn_bytes_sweep_kernel<KSTEPS, QB, TAG>), dim3(gx, gy), dim3(256), 0, s, p);
     return hipGetLastError();
+}
+
+template <int KSTEPS, int QB>
+hipError_t launch_sweep_t(const KnnBytesSweepParams& p, hipStream_t s) {
+    return p.btag ? launch_sweep_tt<KSTEPS, QB, true>(p, s) : launch_sweep_tt<KSTEPS, QB, false>(p, s);
 }
 }  // namespace
 
-hipError_t launch_knn_bytes_pack(const uint8_t* x, uint32_t dim, uint32_t dp, int metric, int query_side, uint64_t rows, int8_t* packed,
+hipError_t launch_knn_bytes_pack(const uint8_t* x, uint32_t stride, uint32_t dim, uint32_t dp, int metric, int query_side, uint64_t rows, int8_t* packed,
                                  int32_t* term, hipStream_t s) {
     if (rows == 0) return hipSuccess;
-    if (dim == 0 || dim > 256 || dp < dim || dp % kKnnBytesKStep || dp > 256) return hipErrorInvalidValue;
+    if (dim == 0 || dim > 256 || stride < dim || dp < dim || dp % kKnnBytesKStep || dp > 256) return hipErrorInvalidValue;
     const int neg_dot = metric == 1;
     const uint32_t used = neg_dot ? dim : dim & ~3u;  // L2Metric::Dist reads the first 4 floor(d / 4) dimensions
     const uint32_t groups = dp / 16u;
-    if (groups <= 2) return launch_pack_t<2>(x, dim, used, dp, rows, neg_dot, query_side, packed, term, s);
-    if (groups <= 4) return launch_pack_t<4>(x, dim, used, dp, rows, neg_dot, query_side, packed, term, s);
-    if (groups <= 8) return launch_pack_t<8>(x, dim, used, dp, rows, neg_dot, query_side, packed, term, s);
-    return launch_pack_t<16>(x, dim, used, dp, rows, neg_dot, query_side, packed, term, s);
+    if (groups <= 2) return launch_pack_t<2>(x, stride, dim, used, dp, rows, neg_dot, query_side, packed, term, s);
+    if (groups <= 4) return launch_pack_t<4>(x, stride, dim, used, dp, rows, neg_dot, query_side, packed, term, s);
+    if (groups <= 8) return launch_pack_t<8>(x, stride, dim, used, dp, rows, neg_dot, query_side, packed, term, s);
+    return launch_pack_t<16>(x, stride, dim, used, dp, rows, neg_dot, query_side, packed, term, s);
 }
 
 hipError_t launch_knn_bytes_sweep(const KnnBytesSweepParams& p, hipStream_t s) {
     if (p.nq == 0 || p.rows == 0) return hipSuccess;
-    if (p.dp % kKnnBytesKStep) return hipErrorInvalidValue;
+    if (p.dp % kKnnBytesKStep || (p.btag && !p.qtag)) return hipErrorInvalidValue;
     switch (p.dp / kKnnBytesKStep) {  // K steps of 32; query blocks per wavefront by what the operands leave of the register file
         case 1: return launch_sweep_t<1, 4>(p, s);
         case 2: return launch_sweep_t<2, 4>(p, s);

@@ -605,6 +605,37 @@ int gbnns_exact_knn_bytes(int device, const uint8_t* base, uint64_t n, const uin
 int gbnns_debug_knn_bytes_plan(uint64_t n, uint64_t n_q, uint32_t d, int k,
                                uint32_t* dp, uint32_t* cap, uint64_t* first_rows, uint64_t* max_chunk, int* pool);
 
+/* Exact TAGGED nearest neighbours: the exact answer of a tagged query -- the ground truth of gbnns_search_tagged and of
+ * GBNNS_FLAG_TAG_BRIDGE, and what a caller falls back to when a filter is selective.  Row j is allowed for query i when
+ * (row_tags[j] & query_tags[i]) != 0, gbnns_search_tagged's test.  The result of query i is that of gbnns_exact_knn (gbnns_exact_knn_bytes)
+ * over the rows allowed for i, reported under their original ids: the k smallest (Dist(base_j, q_i), j) pairs among the allowed j in
+ * ascending pair order, ties towards the lower id, the distances in the reference's arithmetic.  Where fewer than k rows are allowed the
+ * rest is 0xFFFFFFFF / +inf; a query with query_tags[i] == 0 gets nothing else (data, not an error).  self_offset keeps its meaning in
+ * original ids: row i + self_offset is dropped whether allowed or not.  With every word of both tag arrays all ones every output byte is
+ * the untagged call's; the byte form equals the float form on the widened arrays, ids and distance bits.
+ * Arguments, refusals and status codes are those of the untagged twins; row_tags [n] and query_tags [n_q] are buffers of mem_kind, a NULL
+ * one is GBNNS_ERR_INVALID.  The same kernels with a compile-time tag test: a disallowed row is not offered by the scan, a disallowed pair
+ * is not a hit of the matrix-core sweeps (neither counted nor stored), so thresholds come from lists of allowed rows and a later chunk
+ * keeps about k ALLOWED rows per query.  Workspace beside the untagged call's: 4 (n + 64) bytes of padded row tags (and 4 n_q for HOST). */
+int gbnns_exact_knn_tagged(int device, const float* base, uint64_t n, const float* queries, uint64_t n_q, uint32_t d, int k, int metric,
+                           int64_t self_offset, const uint32_t* row_tags, const uint32_t* query_tags,
+                           uint32_t* out_ids, float* out_dist, int mem_kind, void* stream);
+int gbnns_exact_knn_bytes_tagged(int device, const uint8_t* base, uint64_t n, const uint8_t* queries, uint64_t n_q, uint32_t d, int k, int metric,
+                                 int64_t self_offset, const uint32_t* row_tags, const uint32_t* query_tags,
+                                 uint32_t* out_ids, float* out_dist, int mem_kind, void* stream);
+/* The same computation over a handle's resident original-space table, read in place at its device row stride (d_pad floats on a float
+ * handle, d_pad bytes on a byte handle): nothing of the table is uploaded and no float copy of a byte table is made.  The handle's metric.
+ * Exactly one of queries [n_q x d] float32 / queries_u8 [n_q x d] uint8 is non-NULL (else GBNNS_ERR_INVALID): a float handle takes
+ * `queries` (queries_u8 there: GBNNS_ERR_INVALID, as in gbnns_search_byte_queries), a byte handle takes queries_u8 (`queries` there:
+ * GBNNS_ERR_UNSUPPORTED -- there is no mixed-pair scan).  query_tags [n_q] != NULL: the tagged answer over the table of
+ * gbnns_index_set_tags (without one: GBNNS_ERR_INVALID, as in gbnns_search_tagged); NULL: the untagged answer, no tag table needed.
+ * queries, query_tags and the outputs are buffers of mem_kind.  The result is byte-identical to the free function's on the same table and
+ * tags.  The call obeys the stream rule above (it is ordered after a gbnns_index_set_tags on that stream), first joins the
+ * GBNNS_FLAG_DEFER_JOIN calls still owed, allocates its packed workspace per call, uses none of the lanes' workspaces, and returns when
+ * the work has finished, as gbnns_exact_knn does.  There is no deferred form and no gbnns_multi_* form. */
+int gbnns_index_exact_knn(gbnns_index* index, const float* queries, const uint8_t* queries_u8, uint64_t n_q, const uint32_t* query_tags,
+                          int k, int64_t self_offset, uint32_t* out_ids, float* out_dist, int mem_kind, void* stream);
+
 /* ---- several devices of one node: query-sharded replicas ----------------------------------------------------
  * The reference's only parallelism on this path is `#pragma omp parallel for` over the queries of a batch
  * (search_function.h:152; the loop body :348-385 is pure per query).  Here that loop is cut into contiguous blocks,
