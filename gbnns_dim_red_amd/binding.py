@@ -40,7 +40,7 @@ SYMBOLS = [
     "gbnns_round_to_half", "gbnns_index_enable_half_rows", "gbnns_index_low_rows",
     "gbnns_index_set_tags", "gbnns_search_tagged", "gbnns_debug_tag_plan", "gbnns_debug_bridge_plan",
     "gbnns_index_create_bytes", "gbnns_index_is_bytes", "gbnns_debug_byte_plan", "gbnns_debug_byte_walk_plan",
-    "gbnns_exact_knn_bytes", "gbnns_debug_knn_bytes_plan",
+    "gbnns_exact_knn_bytes", "gbnns_debug_knn_bytes_plan", "gbnns_debug_knn_slab",
     "gbnns_search_byte_queries", "gbnns_debug_byte_query_plan",
     "gbnns_exact_knn_tagged", "gbnns_exact_knn_bytes_tagged", "gbnns_index_exact_knn",
 ]
@@ -156,6 +156,7 @@ def load_library():
                                           C.c_int, C.c_void_p]
     lib.gbnns_debug_knn_bytes_plan.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+    lib.gbnns_debug_knn_slab.argtypes = [C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_uint32)]
     lib.gbnns_multi_last_error.restype = C.c_char_p
     lib.gbnns_multi_create.argtypes = [C.POINTER(_IndexDesc), C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
     lib.gbnns_multi_destroy.argtypes = [C.c_void_p]
@@ -324,10 +325,19 @@ def byte_plan(metric, dim, n, ell_stride, ef, aux_stride=0, n_entries=1, wide=Fa
 
 def knn_bytes_plan(n, n_q, d, k):
     """gbnns_debug_knn_bytes_plan (no device needed): what exact_knn does with uint8 inputs of that shape under the current knn_chunk /
-    knn_pool_min_k knobs -- dict(dp, cap, first_rows, max_chunk, pool)."""
+    knn_pool_min_k / knn_slab knobs -- dict(dp, cap, first_rows, max_chunk, pool, slab); slab: knn_slab(n_q, k, bytes=True)."""
     dp, cap, first, chunk, pool = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0), C.c_int(0)
     _check(load_library().gbnns_debug_knn_bytes_plan(n, n_q, d, k, C.byref(dp), C.byref(cap), C.byref(first), C.byref(chunk), C.byref(pool)))
-    return {"dp": int(dp.value), "cap": int(cap.value), "first_rows": int(first.value), "max_chunk": int(chunk.value), "pool": bool(pool.value)}
+    return {"dp": int(dp.value), "cap": int(cap.value), "first_rows": int(first.value), "max_chunk": int(chunk.value), "pool": bool(pool.value),
+            "slab": knn_slab(n_q, k, bytes=True)}
+
+
+def knn_slab(n_q, k, bytes=False):
+    """gbnns_debug_knn_slab (no device needed): the queries exact_knn serves at a time under the current knn_slab knob -- uint8 inputs
+    (bytes=True), or float inputs on the pool path; n_q, or a multiple of 128."""
+    slab = C.c_uint32(0)
+    _check(load_library().gbnns_debug_knn_slab(int(bool(bytes)), n_q, k, C.byref(slab)))
+    return int(slab.value)
 
 
 def _is_u8(x):

@@ -53,6 +53,17 @@ int knn_stage_tags(const KnnCall<T>& c, DevBuf& tag_dev, DevBuf& qtag_dev, const
     return GBNNS_OK;
 }
 
+// Queries the pool path of gbnns_exact_knn (keys of 4 bytes) and gbnns_exact_knn_bytes (keys of 8) serve at a time: as many as keep the
+// key lists (cap = 4 k + 64 slots a query) within 4 GiB, a multiple of 128, never fewer than 1 024 -- or all of them.  "knn_slab" > 0
+// caps that (a multiple of 128, at least 128: tests run several slabs at a few hundred queries); gbnns_debug_knn_slab reports it.
+uint32_t knn_slab(uint64_t nq, int k, uint32_t key_bytes) {
+    const uint64_t cap = (uint64_t)(4 * k + 64);
+    uint64_t slab = std::max<uint64_t>(1024, ((4ull << 30) / (cap * key_bytes)) & ~(uint64_t)127);
+    const int knob = g_knob_knn_slab.load(std::memory_order_relaxed);
+    if (knob > 0) slab = std::min<uint64_t>(slab, (uint64_t)std::max(128, knob & ~127));
+    return (uint32_t)std::min<uint64_t>(nq, slab);
+}
+
 int knn_float_call(const KnnCall<float>& c) {
     const int device = c.device, k = c.k, metric = c.metric, mem_kind = c.mem_kind;
     const float* const base = c.base;
@@ -131,8 +142,7 @@ int knn_float_call(const KnnCall<float>& c) {
         const uint64_t rows_first = cap & ~63u;  // a chunk of at most `cap` rows cannot overflow a query's list: the first chunk (no thresholds yet) and the fallback
         // (chunks four times the heap path's: every chunk costs a query a pass over its whole pool; measured at k = 1 000: 32 K rows 1.98 s, 64 K 1.86 s, 128 K 1.89 s)
         const uint64_t max_chunk = std::min<uint64_t>(4ull * (uint64_t)g_knob_knn_chunk.load(std::memory_order_relaxed), std::max<uint64_t>(64, (n / 16 + 63) & ~(uint64_t)63));
-        // queries in slabs whose candidate lists take at most 4 GiB
-        const uint32_t slab = (uint32_t)std::min<uint64_t>(nq, std::max<uint64_t>(1024, ((4ull << 30) / ((uint64_t)cap * 4)) & ~(uint64_t)127));
+        const uint32_t slab = knn_slab(nq, k, 4);  // queries in slabs whose candidate lists take at most 4 GiB
         DevBuf bpack, bnorm, qpack, qnorm, rhs, cand, count, flag, pool, root;
         struct Release3 {
             DevBuf* b[10];
@@ -280,7 +290,7 @@ KnnBytesPlan knn_bytes_plan(uint64_t n, uint64_t nq, uint32_t d, int k) {
     pl.first_rows = std::min<uint64_t>(n, pl.cap & ~63u);  // (chunks start on multiples of 64 rows: the sweep reads the row terms in aligned groups of four)
     pl.max_chunk = 4ull * (uint64_t)g_knob_knn_chunk.load(std::memory_order_relaxed);  // (the knob is a multiple of 64, at least 64)
     pl.pool = k >= g_knob_knn_pool_min_k.load(std::memory_order_relaxed);
-    pl.slab = (uint32_t)std::min<uint64_t>(nq, std::max<uint64_t>(1024, ((4ull << 30) / ((uint64_t)pl.cap * 8)) & ~(uint64_t)127));
+    pl.slab = knn_slab(nq, k, 8);
     return pl;
 }
 
@@ -505,6 +515,14 @@ int gbnns_debug_knn_bytes_plan(uint64_t n, uint64_t n_q, uint32_t d, int k, uint
         return fail(GBNNS_ERR_INVALID, "gbnns_debug_knn_bytes_plan: not a shape gbnns_exact_knn_bytes takes");
     const KnnBytesPlan pl = knn_bytes_plan(n, n_q, d, k);
     *dp = pl.dp; *cap = pl.cap; *first_rows = pl.first_rows; *max_chunk = pl.max_chunk; *pool = pl.pool ? 1 : 0;
+    return GBNNS_OK;
+}
+
+int gbnns_debug_knn_slab(int bytes, uint64_t n_q, int k, uint32_t* slab) {
+    if (!slab) return fail(GBNNS_ERR_INVALID, "gbnns_debug_knn_slab: null output");
+    if ((bytes != 0 && bytes != 1) || n_q >= (1ull << 31) || k < 1 || k > 4096)
+        return fail(GBNNS_ERR_INVALID, "gbnns_debug_knn_slab: not a shape the pool path of gbnns_exact_knn / gbnns_exact_knn_bytes takes");
+    *slab = knn_slab(n_q, k, bytes ? 8 : 4);
     return GBNNS_OK;
 }
 

@@ -276,6 +276,8 @@ int build_ell(const uint64_t* off, const uint32_t* nbr, uint64_t n, std::vector<
 //   "knn_pool_min_k" shortest list gbnns_exact_knn keeps as an unordered pool (one wavefront per query and chunk) instead of a heap
 //                    (measured on 10^6 x 32: k = 48 0.327 against 0.333 s, k = 100 0.425 against 0.536 s, k = 1 000 2.4 against 7.6 s)
 //   "knn_filter"     0 = gbnns_exact_knn without the matrix-core filter (GBNNS_KNN_FILTER; tests compare the two paths)
+//   "knn_slab"       0 = queries in slabs whose key lists take at most 4 GiB (default); v > 0: at most max(128, v & ~127) queries a slab
+//                    (tests: several slabs at a few hundred queries; gbnns_debug_knn_slab reports the slab of a shape)
 // The classes where the integer first pass measured faster than the float byte walk plus the widening kernel by more than the baseline's
 // run-to-run spread (profiles/byte_query_timing.txt)
 constexpr int kByteQueryIntDefault = 7;
@@ -328,6 +330,7 @@ Knobs knob_defaults() {
 std::atomic<int> g_knob_knn_chunk{std::max(64, knob_env("GBNNS_KNN_CHUNK", 1 << 15) & ~63)};  // (a multiple of 64, never 0: the chunk loops step by it)
 std::atomic<int> g_knob_knn_pool_min_k{std::max(1, knob_env("GBNNS_KNN_POOL_MIN_K", 64))};
 std::atomic<int> g_knob_knn_filter{knob_env("GBNNS_KNN_FILTER", 1)};
+std::atomic<int> g_knob_knn_slab{0};
 
 // (defined here, beside the defaults, so that gbnns_debug_knob below can reach them under the lock)
 static bool knob_default_set(const char* name, int value) {
@@ -758,6 +761,7 @@ int gbnns_debug_knob(const char* name, int value) {
     if (!std::strcmp(name, "knn_chunk")) g_knob_knn_chunk.store(std::max(64, value & ~63), std::memory_order_relaxed);
     else if (!std::strcmp(name, "knn_pool_min_k")) g_knob_knn_pool_min_k.store(std::max(1, value), std::memory_order_relaxed);
     else if (!std::strcmp(name, "knn_filter")) g_knob_knn_filter.store(value, std::memory_order_relaxed);
+    else if (!std::strcmp(name, "knn_slab")) g_knob_knn_slab.store(value > 0 ? std::max(128, value & ~127) : 0, std::memory_order_relaxed);
     else return fail(GBNNS_ERR_INVALID, "gbnns_debug_knob: unknown knob '%s'", name);
     return GBNNS_OK;
 }

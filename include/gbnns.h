@@ -498,7 +498,10 @@ int gbnns_profile_enable(gbnns_index* index, int on);
  * "knn_pool_min_k": shortest list gbnns_exact_knn's filter path and gbnns_exact_knn_bytes keep as an unordered pool with a
  * radix select (one wavefront per query) instead of a binary heap (default 64; GBNNS_KNN_POOL_MIN_K).
  * "knn_filter": gbnns_exact_knn's matrix-core filter -- 0 never, 1 by size (default), 2 whenever the shape allows
- * (GBNNS_KNN_FILTER). */
+ * (GBNNS_KNN_FILTER).
+ * "knn_slab": most queries gbnns_exact_knn's pool path and gbnns_exact_knn_bytes serve at a time -- 0 (default) = as many as keep their
+ * key lists within 4 GiB (the slab formula at gbnns_exact_knn_bytes); v > 0 caps a slab at max(128, v & ~127) queries, so that a few
+ * hundred queries already run several slabs (tests).  gbnns_debug_knn_slab reports the slab of a shape. */
 int gbnns_debug_knob(const char* name, int value);
 int gbnns_index_knob(gbnns_index* index, const char* name, int value);   /* GBNNS_ERR_INVALID: not a handle knob */
 int gbnns_index_knob_get(gbnns_index* index, const char* name, int* out_value);   /* the handle's current value */
@@ -591,7 +594,8 @@ int gbnns_exact_knn(int device, const float* base, uint64_t n, const float* quer
  * One scheme for every shape: the rows in chunks, a query's rows at or below its current k-th distance appended as keys, the keys offered
  * to a heap (k < "knn_pool_min_k") or an unordered pool with a radix select; a chunk that overflows a query's key list is swept again in
  * pieces that cannot.  GBNNS_ERR_UNSUPPORTED: d > 256 (the 2^24 bound), k > 4096 -- widen the rows and call gbnns_exact_knn.  No CPU path.
- * Device workspace for the duration of the call, dp = d rounded up to 32, cap = 4 k + 64, slab = min(n_q, max(1024, 2^32 / (8 cap))):
+ * Device workspace for the duration of the call, dp = d rounded up to 32, cap = 4 k + 64, slab = min(n_q, max(1024, floor(2^32 / (8 cap)) & ~127))
+ * queries served at a time (gbnns_exact_knn's pool path: the same with 4 cap; the knob "knn_slab" caps both):
  * n dp + 4 (n + 64) bytes of packed rows and row terms, and slab (dp + 8 cap + 8 k + 20) bytes of packed queries, key lists and
  * heaps / pools; HOST buffers add n d + n_q d bytes of uploaded rows and 4 (or 8) n_q k bytes of results. */
 int gbnns_exact_knn_bytes(int device, const uint8_t* base, uint64_t n, const uint8_t* queries, uint64_t n_q,
@@ -604,6 +608,10 @@ int gbnns_exact_knn_bytes(int device, const uint8_t* base, uint64_t n, const uin
  * GBNNS_ERR_INVALID for a shape the call refuses. */
 int gbnns_debug_knn_bytes_plan(uint64_t n, uint64_t n_q, uint32_t d, int k,
                                uint32_t* dp, uint32_t* cap, uint64_t* first_rows, uint64_t* max_chunk, int* pool);
+/* Diagnostic, no device needed: the queries a call with n_q queries and lists of k serves at a time under the current "knn_slab" knob --
+ * bytes = 1: gbnns_exact_knn_bytes and its tagged / handle forms (keys of 8 bytes), bytes = 0: the pool path of gbnns_exact_knn (keys of 4).
+ * *slab = n_q, or a multiple of 128.  GBNNS_ERR_INVALID: k outside 1 .. 4096, n_q >= 2^31. */
+int gbnns_debug_knn_slab(int bytes, uint64_t n_q, int k, uint32_t* slab);
 
 /* Exact TAGGED nearest neighbours: the exact answer of a tagged query -- the ground truth of gbnns_search_tagged and of
  * GBNNS_FLAG_TAG_BRIDGE, and what a caller falls back to when a filter is selective.  Row j is allowed for query i when

@@ -80,18 +80,27 @@ def f32_dot_eight_sums(x, q):
 
 
 @contextlib.contextmanager
-def knobs(g, knn_chunk=None, knn_pool_min_k=None):
-    """gbnns_exact_knn*'s process-wide knobs for the duration of a with-block; the defaults (32 768 rows, pools from k = 64) come back."""
+def knobs(g, knn_chunk=None, knn_pool_min_k=None, knn_slab=None):
+    """gbnns_exact_knn*'s process-wide knobs for the duration of a with-block; the defaults (32 768 rows, pools from k = 64, slabs by the
+    4 GiB rule: "knn_slab" 0) come back, also behind an exception."""
     lib = g.load_library()
     try:
         if knn_chunk is not None:
             assert lib.gbnns_debug_knob(b"knn_chunk", knn_chunk) == 0
         if knn_pool_min_k is not None:
             assert lib.gbnns_debug_knob(b"knn_pool_min_k", knn_pool_min_k) == 0
+        if knn_slab is not None:
+            assert lib.gbnns_debug_knob(b"knn_slab", knn_slab) == 0
         yield
     finally:
         lib.gbnns_debug_knob(b"knn_chunk", 1 << 15)
         lib.gbnns_debug_knob(b"knn_pool_min_k", 64)
+        lib.gbnns_debug_knob(b"knn_slab", 0)
+
+
+def slabs(slab, nq):
+    """The query slabs [(first query, queries)] of a call with nq queries, from knn_bytes_plan(...)["slab"] or knn_slab(...)."""
+    return [(q0, min(slab, nq - q0)) for q0 in range(0, nq, slab)]
 
 
 def chunk_plan(plan, n):
