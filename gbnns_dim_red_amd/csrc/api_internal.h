@@ -81,6 +81,15 @@ struct DevBuf {
     }
 };
 
+// A call's own temporary: released where it goes out of scope.  (Index and lane members stay DevBuf: they are copied by value and
+// released by gbnns_index_destroy.)
+struct ScopedDevBuf : DevBuf {
+    ScopedDevBuf() = default;
+    ScopedDevBuf(const ScopedDevBuf&) = delete;
+    ScopedDevBuf& operator=(const ScopedDevBuf&) = delete;
+    ~ScopedDevBuf() { release(); }
+};
+
 struct ProfCall {
     hipEvent_t ev[5];  // begin, after project, after walk, after general, after rerank
     uint64_t queries;

@@ -1,9 +1,11 @@
 // graph_api.cpp -- graph preparation entry points of the C ABI (include/gbnns.h): gbnns_exact_knn (getTruth, support_func.h:270-290,
 // generalised to k results: heaps, the matrix-core filter, long lists as pools), gbnns_exact_knn_bytes (the same lists over uint8 rows,
 // their distances from the int8 matrix cores: knn_bytes.hip) with gbnns_debug_knn_bytes_plan, their tagged forms gbnns_exact_knn_tagged /
-// gbnns_exact_knn_bytes_tagged and gbnns_index_exact_knn over a handle's resident table (one body each for float and byte rows, whichever
-// entry point brought the call), and gbnns_build_graph_gd_device (hnswlikeGD,
-// support_func.h:521-575, pruning on the device).  Cut out of api.cpp in round 5; api_internal.h lists the other units.
+// gbnns_exact_knn_bytes_tagged and gbnns_index_exact_knn over a handle's resident table, and gbnns_build_graph_gd_device (hnswlikeGD,
+// support_func.h:521-575, pruning on the device).  Every kNN entry point fills a KnnCall<T> and ends in knn_call (one body for float rows,
+// one for byte rows).  What the two bodies share exists once: knn_check (the refusals), KnnStaged (HOST buffers and the
+// tag words), KnnSlab (every address that depends on the query slab) and knn_sweep_chunks (the row chunks and the answer to a key list
+// that overflowed).  Cut out of api.cpp in round 5; api_internal.h lists the other units.
 
 #include "api_internal.h"
 
@@ -34,6 +36,43 @@ struct KnnCall {
     void* stream;
 };
 
+// What a row type does not take, between the checks every call shares and those that need a device (knn_check).
+int knn_refuse(const KnnCall<float>& c) {
+    if (c.d > 8192) return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_exact_knn: d <= 8192 (a tile of base rows is staged in LDS; got %u)", c.d);
+    if (c.metric == GBNNS_METRIC_NEG_DOT && c.d % 8 != 0)
+        return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_exact_knn: the negative-dot form needs d %% 8 == 0 (got %u)", c.d);
+    return GBNNS_OK;
+}
+int knn_refuse(const KnnCall<uint8_t>& c) {
+    if (c.d > 256)
+        return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_exact_knn_bytes: d <= 256 (every sum of the distance must stay an integer below 2^24 to be exact "
+                    "in float32 and on the int8 matrix cores; got %u): widen the rows and call gbnns_exact_knn", c.d);
+    if (c.k > 4096) return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_exact_knn_bytes: k <= 4096 (got %d): widen the rows and call gbnns_exact_knn", c.k);
+    if (c.metric == GBNNS_METRIC_NEG_DOT && c.d % 8 != 0)
+        return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_exact_knn_bytes: the negative-dot form needs d %% 8 == 0 (got %u)", c.d);
+    return GBNNS_OK;
+}
+
+// The refusals of a call, in the order tests/test_cabi_cpu.py and tests/test_knn_bytes_cpu.py pin.  (A call without queries is valid
+// and done: the caller returns behind this.)
+template <class T>
+int knn_check(const KnnCall<T>& c) {
+    if (!c.base || !c.queries || !c.out_ids || (c.tagged && (!c.row_tags || !c.query_tags))) return fail(GBNNS_ERR_INVALID, "null argument");
+    if (c.n == 0 || c.n >= (1ull << 32) - 1) return fail(GBNNS_ERR_INVALID, "n must be in [1, 2^32 - 1)");
+    if (c.n_q >= (1ull << 31)) return fail(GBNNS_ERR_INVALID, "n_q too large");
+    if (c.k < 1 || c.k > (1 << 20)) return fail(GBNNS_ERR_INVALID, "k must be in [1, 2^20]");
+    if (c.d == 0) return fail(GBNNS_ERR_INVALID, "d must be >= 1");
+    if (c.metric != GBNNS_METRIC_L2 && c.metric != GBNNS_METRIC_NEG_DOT) return fail(GBNNS_ERR_INVALID, "unknown metric %d", c.metric);
+    if (c.mem_kind != GBNNS_MEM_HOST && c.mem_kind != GBNNS_MEM_DEVICE) return fail(GBNNS_ERR_INVALID, "unknown mem_kind %d", c.mem_kind);
+    if (int rc = knn_refuse(c)) return rc;
+    if (c.self_offset < -1) return fail(GBNNS_ERR_INVALID, "self_offset must be >= -1");
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+        return fail(GBNNS_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
+    if (c.device < 0 || c.device >= count) return fail(GBNNS_ERR_NO_DEVICE, "device %d out of range (%d devices)", c.device, count);
+    return GBNNS_OK;
+}
+
 // The tag words of a tagged call on the device: the rows' in a copy of its own, 16-byte aligned and 64 words longer than the set (zero
 // there) -- the sweep kernels read them in aligned groups of four to the end of a block of 32 rows, as they read bnorm / bterm -- and the
 // queries' (uploaded for HOST buffers).
@@ -53,10 +92,55 @@ int knn_stage_tags(const KnnCall<T>& c, DevBuf& tag_dev, DevBuf& qtag_dev, const
     return GBNNS_OK;
 }
 
+// A call's arrays where the kernels read and write them: the caller's own (DEVICE buffers, a resident table), or copies (HOST).
+template <class T>
+struct KnnStaged {
+    ScopedDevBuf b_dev, q_dev, ids_dev, dist_dev, tag_dev, qtag_dev;
+    const T* base;
+    const T* q;
+    uint32_t* ids;
+    float* dist;
+    const uint32_t* tags = nullptr;   // tagged: the device copies of the tag words; a launch with null tags is the untagged instance
+    const uint32_t* qtags = nullptr;
+
+    int stage(const KnnCall<T>& c, hipStream_t s) {
+        const size_t nq = c.n_q;
+        int rc;
+        base = c.base; q = c.queries; ids = c.out_ids; dist = c.out_dist;
+        if (c.mem_kind == GBNNS_MEM_HOST) {  // (byte rows are uploaded as bytes: a quarter of the float call's traffic, and no float copy anywhere)
+            if (!c.resident) {
+                if ((rc = b_dev.ensure((size_t)c.n * c.d * sizeof(T)))) return rc;
+                HIP_TRY(hipMemcpyAsync(b_dev.p, c.base, (size_t)c.n * c.d * sizeof(T), hipMemcpyHostToDevice, s));
+                base = b_dev.as<T>();
+            }
+            if ((rc = q_dev.ensure(nq * c.d * sizeof(T)))) return rc;
+            if ((rc = ids_dev.ensure(nq * c.k * 4))) return rc;
+            if (c.out_dist && (rc = dist_dev.ensure(nq * c.k * 4))) return rc;
+            HIP_TRY(hipMemcpyAsync(q_dev.p, c.queries, nq * c.d * sizeof(T), hipMemcpyHostToDevice, s));
+            q = q_dev.as<T>(); ids = ids_dev.as<uint32_t>();
+            dist = c.out_dist ? dist_dev.as<float>() : nullptr;
+        }
+        if (c.tagged) {
+            if ((rc = knn_stage_tags(c, tag_dev, qtag_dev, qtags, s))) return rc;
+            tags = tag_dev.as<uint32_t>();
+        }
+        return GBNNS_OK;
+    }
+    // The lists back to HOST buffers, and the end of the call: its temporaries are released behind this, so it waits for the work that uses them.
+    int copy_back(const KnnCall<T>& c, hipStream_t s) const {
+        if (c.mem_kind == GBNNS_MEM_HOST) {
+            HIP_TRY(hipMemcpyAsync(c.out_ids, ids, (size_t)c.n_q * c.k * 4, hipMemcpyDeviceToHost, s));
+            if (c.out_dist) HIP_TRY(hipMemcpyAsync(c.out_dist, dist, (size_t)c.n_q * c.k * 4, hipMemcpyDeviceToHost, s));
+        }
+        HIP_TRY(hipStreamSynchronize(s));
+        return GBNNS_OK;
+    }
+};
+
 // Queries the pool path of gbnns_exact_knn (keys of 4 bytes) and gbnns_exact_knn_bytes (keys of 8) serve at a time: as many as keep the
 // key lists (cap = 4 k + 64 slots a query) within 4 GiB, a multiple of 128, never fewer than 1 024 -- or all of them.  "knn_slab" > 0
 // caps that (a multiple of 128, at least 128: tests run several slabs at a few hundred queries); gbnns_debug_knn_slab reports it.
-uint32_t knn_slab(uint64_t nq, int k, uint32_t key_bytes) {
+uint32_t knn_slab_queries(uint64_t nq, int k, uint32_t key_bytes) {
     const uint64_t cap = (uint64_t)(4 * k + 64);
     uint64_t slab = std::max<uint64_t>(1024, ((4ull << 30) / (cap * key_bytes)) & ~(uint64_t)127);
     const int knob = g_knob_knn_slab.load(std::memory_order_relaxed);
@@ -64,64 +148,110 @@ uint32_t knn_slab(uint64_t nq, int k, uint32_t key_bytes) {
     return (uint32_t)std::min<uint64_t>(nq, slab);
 }
 
-int knn_float_call(const KnnCall<float>& c) {
-    const int device = c.device, k = c.k, metric = c.metric, mem_kind = c.mem_kind;
-    const float* const base = c.base;
-    const float* const queries = c.queries;
-    const uint64_t n = c.n, n_q = c.n_q;
-    const uint32_t d = c.d;
-    const int64_t self_offset = c.self_offset;
-    uint32_t* const out_ids = c.out_ids;
-    float* const out_dist = c.out_dist;
-    void* const stream = c.stream;
-    if (!base || !queries || !out_ids || (c.tagged && (!c.row_tags || !c.query_tags))) return fail(GBNNS_ERR_INVALID, "null argument");
-    if (n == 0 || n >= (1ull << 32) - 1) return fail(GBNNS_ERR_INVALID, "n must be in [1, 2^32 - 1)");
-    if (n_q >= (1ull << 31)) return fail(GBNNS_ERR_INVALID, "n_q too large");
-    if (k < 1 || k > (1 << 20)) return fail(GBNNS_ERR_INVALID, "k must be in [1, 2^20]");
-    if (d == 0) return fail(GBNNS_ERR_INVALID, "d must be >= 1");
-    if (metric != GBNNS_METRIC_L2 && metric != GBNNS_METRIC_NEG_DOT) return fail(GBNNS_ERR_INVALID, "unknown metric %d", metric);
-    if (mem_kind != GBNNS_MEM_HOST && mem_kind != GBNNS_MEM_DEVICE) return fail(GBNNS_ERR_INVALID, "unknown mem_kind %d", mem_kind);
-    if (d > 8192) return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_exact_knn: d <= 8192 (a tile of base rows is staged in LDS; got %u)", d);
-    if (metric == GBNNS_METRIC_NEG_DOT && d % 8 != 0)
-        return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_exact_knn: the negative-dot form needs d %% 8 == 0 (got %u)", d);
-    if (self_offset < -1) return fail(GBNNS_ERR_INVALID, "self_offset must be >= -1");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-        return fail(GBNNS_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= count) return fail(GBNNS_ERR_NO_DEVICE, "device %d out of range (%d devices)", device, count);
-    if (n_q == 0) return GBNNS_OK;
-    HIP_TRY(hipSetDevice(device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool host = mem_kind == GBNNS_MEM_HOST;
-    const uint32_t nq = (uint32_t)n_q;
-    DevBuf b_dev, q_dev, ids_dev, dist_dev, heap, tag_dev, qtag_dev;
-    struct Release {  // DevBuf has no destructor (index members are released by gbnns_index_destroy)
-        DevBuf* b[7];
-        ~Release() { for (DevBuf* x : b) x->release(); }
-    } release{{&b_dev, &q_dev, &ids_dev, &dist_dev, &heap, &tag_dev, &qtag_dev}};
+// Queries q0 .. q0 + qn of a call: everything a slab reads or writes at an offset of its own.  (The per-slab workspaces -- packed query
+// operands, keys, thresholds, counts -- start at 0 in every slab and are set again by the body at the head of its slab loop.)
+template <class T>
+struct KnnSlab {
+    uint32_t q0, qn;
+    const T* q;
+    int64_t self_offset;    // of the slab's first query, or -1
+    const uint32_t* qtags;  // or nullptr
+    uint32_t* out_ids;
+    float* out_dist;        // or nullptr
+};
+template <class T>
+KnnSlab<T> knn_slab_at(const KnnCall<T>& c, const KnnStaged<T>& st, uint32_t q0, uint32_t slab) {
+    KnnSlab<T> sl{};
+    sl.q0 = q0; sl.qn = std::min(slab, (uint32_t)c.n_q - q0);
+    sl.q = st.q + (size_t)q0 * c.d;
+    sl.self_offset = c.self_offset >= 0 ? c.self_offset + (int64_t)q0 : -1;
+    sl.qtags = st.qtags ? st.qtags + q0 : nullptr;
+    sl.out_ids = st.ids + (size_t)q0 * c.k;
+    sl.out_dist = st.dist ? st.dist + (size_t)q0 * c.k : nullptr;
+    return sl;
+}
+
+// The rows of a set in chunks, for `qn` queries whose thresholds start at "every row passes": sweep(r0, rows) collects what a chunk's rows
+// leave in the queries' lists (`count`, and `flag` where a list overflowed), take() offers the lists to the heaps / pools and tightens the
+// thresholds.  The first chunk, of first_rows <= cap rows, cannot overflow a list; a later one is at most as long as everything before it
+// -- a query is then expected to keep about k rows of it, whatever the chunk -- and at most max_chunk rows.  Where some query kept more
+// rows of a chunk than its list holds (rows in an adversarial order, a mass of ties at the threshold) nothing of the chunk has been
+// offered yet: the chunk again in pieces of first_rows, which cannot overflow.
+template <class Sweep, class Take>
+int knn_sweep_chunks(uint64_t n, uint64_t first_rows, uint64_t max_chunk, uint32_t qn, uint32_t* count, uint32_t* flag, hipStream_t s, Sweep sweep,
+                     Take take) {
     int rc;
-    KnnParams p{};
-    p.base = base; p.q = queries; p.out_ids = out_ids; p.out_dist = out_dist;
-    if (host) {
-        if (!c.resident) {
-            if ((rc = b_dev.ensure((size_t)n * d * 4))) return rc;
-            HIP_TRY(hipMemcpyAsync(b_dev.p, base, (size_t)n * d * 4, hipMemcpyHostToDevice, s));
-            p.base = b_dev.as<float>();
+    auto swept = [&](uint64_t r0, uint32_t rows) -> int {
+        HIP_TRY(hipMemsetAsync(count, 0, (size_t)qn * 4, s));
+        HIP_TRY(hipMemsetAsync(flag, 0, 4, s));
+        return sweep(r0, rows);
+    };
+    uint32_t h_flag = 0;
+    for (uint64_t r0 = 0, chunk = 0; r0 < n; r0 += chunk) {
+        chunk = r0 == 0 ? first_rows : std::min<uint64_t>(max_chunk, r0);
+        const uint32_t rows = (uint32_t)std::min<uint64_t>(chunk, n - r0);
+        if ((rc = swept(r0, rows))) return rc;
+        if (r0 != 0) {
+            HIP_TRY(hipMemcpyAsync(&h_flag, flag, 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
         }
-        if ((rc = q_dev.ensure((size_t)nq * d * 4))) return rc;
-        if ((rc = ids_dev.ensure((size_t)nq * k * 4))) return rc;
-        if (out_dist && (rc = dist_dev.ensure((size_t)nq * k * 4))) return rc;
-        HIP_TRY(hipMemcpyAsync(q_dev.p, queries, (size_t)nq * d * 4, hipMemcpyHostToDevice, s));
-        p.q = q_dev.as<float>(); p.out_ids = ids_dev.as<uint32_t>();
-        p.out_dist = out_dist ? dist_dev.as<float>() : nullptr;
+        if (r0 == 0 || !h_flag) {
+            if ((rc = take())) return rc;
+            continue;
+        }
+        for (uint64_t r1 = r0; r1 < r0 + rows; r1 += first_rows) {
+            if ((rc = swept(r1, (uint32_t)std::min<uint64_t>(first_rows, r0 + rows - r1)))) return rc;
+            if ((rc = take())) return rc;
+        }
     }
-    const uint32_t* qtags = nullptr;  // tagged: the device copies of the tag words; a launch with null tags is the untagged instance
-    if (c.tagged) {
-        if ((rc = knn_stage_tags(c, tag_dev, qtag_dev, qtags, s))) return rc;
-        p.row_tags = tag_dev.as<uint32_t>(); p.query_tags = qtags;
+    return GBNNS_OK;
+}
+
+// The matrix-core filter's operands and lists (knn.hip) for `nq` queries at a time: the heap-filter path's whole call, a slab of the pool path.
+struct KnnFilterWork {
+    ScopedDevBuf bpack, bnorm, qpack, qnorm, rhs, cand, count, flag;
+    uint32_t dp, cap;
+    // the buffers, and the base set packed
+    int prepare(const KnnParams& p, uint32_t nq, uint32_t cap_, hipStream_t s) {
+        int rc;
+        dp = (p.dim + 15u) & ~15u; cap = cap_;
+        if ((rc = bpack.ensure((size_t)p.n * dp * 4))) return rc;       // 2 dp bf16 per row
+        if ((rc = bnorm.ensure(((size_t)p.n + 64) * 4))) return rc;  // (+inf behind the last row: the filter reads whole blocks of 32)
+        if ((rc = qpack.ensure((size_t)nq * dp * 4))) return rc;
+        if ((rc = qnorm.ensure((size_t)nq * 4))) return rc;
+        if ((rc = rhs.ensure((size_t)nq * 4))) return rc;
+        if ((rc = cand.ensure((size_t)nq * cap * 4))) return rc;
+        if ((rc = count.ensure((size_t)nq * 4))) return rc;
+        if ((rc = flag.ensure(4))) return rc;
+        HIP_TRY(launch_fill_u32(bnorm.as<uint32_t>() + p.n, 0x7F800000u, 64, s));
+        HIP_TRY(launch_knn_pack(p.base, p.bstride, p.dim, p.n, bpack.as<uint16_t>(), bnorm.as<float>(), s));
+        return GBNNS_OK;
     }
-    const uint32_t* const tags = tag_dev.as<uint32_t>();
-    p.bstride = c.bstride; p.qstride = d; p.n = n; p.nq = nq; p.dim = d; p.k = k; p.self_offset = self_offset;
+    // rows r0 .. r0 + rows against the qn queries packed last (tags: the rows' words by row id, qtags: those queries'; or null)
+    KnnFilterParams chunk(uint64_t r0, uint32_t rows, uint32_t qn, const uint32_t* tags, const uint32_t* qtags) const {
+        KnnFilterParams f{};
+        f.qpack = qpack.as<uint16_t>(); f.bpack = bpack.as<uint16_t>() + (size_t)r0 * dp * 2; f.bnorm = bnorm.as<float>() + r0;
+        f.rhs = rhs.as<float>(); f.nq = qn; f.dp = dp; f.rows = rows; f.row0 = (uint32_t)r0; f.cap = cap;
+        f.cand = cand.as<uint32_t>(); f.count = count.as<uint32_t>(); f.overflow = flag.as<uint32_t>();
+        if (qtags) { f.btag = tags + r0; f.qtag = qtags; }
+        return f;
+    }
+};
+
+int knn_call(const KnnCall<float>& c) {
+    int rc;
+    if ((rc = knn_check(c)) || c.n_q == 0) return rc;
+    HIP_TRY(hipSetDevice(c.device));
+    hipStream_t s = static_cast<hipStream_t>(c.stream);
+    const int k = c.k, metric = c.metric;
+    const uint64_t n = c.n;
+    const uint32_t d = c.d, nq = (uint32_t)c.n_q;
+    KnnStaged<float> st;
+    ScopedDevBuf heap;
+    if ((rc = st.stage(c, s))) return rc;
+    KnnParams p{};
+    p.base = st.base; p.q = st.q; p.out_ids = st.ids; p.out_dist = st.dist; p.row_tags = st.tags; p.query_tags = st.qtags;
+    p.bstride = c.bstride; p.qstride = d; p.n = n; p.nq = nq; p.dim = d; p.k = k; p.self_offset = c.self_offset;
     p.heap_stride = ((size_t)nq + 63) & ~(size_t)63;
     // Matrix-core filter in front of the exact distances (knn.hip): the L2 metric on rows of whole 16-byte steps, sets
     // large enough to amortise its passes.  Same output, byte for byte (tests/test_gpu_parity.py); "knn_filter" 0 = off.
@@ -137,75 +267,34 @@ int knn_float_call(const KnnCall<float>& c) {
         HIP_TRY(hipMemsetAsync(p.heap, 0xFF, p.heap_stride * (size_t)k * 8, s));
     }
     if (pool_path) {
-        const uint32_t dp = (d + 15u) & ~15u;
         const uint32_t cap = (uint32_t)(4 * k + 64);
         const uint64_t rows_first = cap & ~63u;  // a chunk of at most `cap` rows cannot overflow a query's list: the first chunk (no thresholds yet) and the fallback
         // (chunks four times the heap path's: every chunk costs a query a pass over its whole pool; measured at k = 1 000: 32 K rows 1.98 s, 64 K 1.86 s, 128 K 1.89 s)
         const uint64_t max_chunk = std::min<uint64_t>(4ull * (uint64_t)g_knob_knn_chunk.load(std::memory_order_relaxed), std::max<uint64_t>(64, (n / 16 + 63) & ~(uint64_t)63));
-        const uint32_t slab = knn_slab(nq, k, 4);  // queries in slabs whose candidate lists take at most 4 GiB
-        DevBuf bpack, bnorm, qpack, qnorm, rhs, cand, count, flag, pool, root;
-        struct Release3 {
-            DevBuf* b[10];
-            ~Release3() { for (DevBuf* x : b) x->release(); }
-        } release3{{&bpack, &bnorm, &qpack, &qnorm, &rhs, &cand, &count, &flag, &pool, &root}};
-        if ((rc = bpack.ensure((size_t)n * dp * 4))) return rc;
-        if ((rc = bnorm.ensure(((size_t)n + 64) * 4))) return rc;
-        if ((rc = qpack.ensure((size_t)slab * dp * 4))) return rc;
-        if ((rc = qnorm.ensure((size_t)slab * 4))) return rc;
-        if ((rc = rhs.ensure((size_t)slab * 4))) return rc;
-        if ((rc = cand.ensure((size_t)slab * cap * 4))) return rc;
-        if ((rc = count.ensure((size_t)slab * 4))) return rc;
-        if ((rc = flag.ensure(4))) return rc;
+        const uint32_t slab = knn_slab_queries(nq, k, 4);  // queries in slabs whose candidate lists take at most 4 GiB
+        KnnFilterWork w;
+        ScopedDevBuf pool, root;
         if ((rc = pool.ensure((size_t)slab * (size_t)k * 8))) return rc;
         if ((rc = root.ensure((size_t)slab * 8))) return rc;
-        HIP_TRY(launch_fill_u32(bnorm.as<uint32_t>() + n, 0x7F800000u, 64, s));
-        HIP_TRY(launch_knn_pack(p.base, p.bstride, d, n, bpack.as<uint16_t>(), bnorm.as<float>(), s));
+        if ((rc = w.prepare(p, slab, cap, s))) return rc;
         for (uint32_t q0 = 0; q0 < nq; q0 += slab) {
-            const uint32_t qn = std::min(slab, nq - q0);
+            const KnnSlab<float> sl = knn_slab_at(c, st, q0, slab);
             KnnPoolParams pp{};
             pp.k = p;
-            pp.k.q = p.q + (size_t)q0 * d; pp.k.nq = qn; pp.k.out_ids = p.out_ids + (size_t)q0 * k;
-            pp.k.out_dist = p.out_dist ? p.out_dist + (size_t)q0 * k : nullptr;
-            pp.k.self_offset = self_offset >= 0 ? self_offset + (int64_t)q0 : -1;
-            if (qtags) pp.k.query_tags = qtags + q0;
-            pp.pool = pool.as<uint64_t>(); pp.root = root.as<uint64_t>(); pp.cand = cand.as<uint32_t>(); pp.count = count.as<uint32_t>();
-            pp.cap = cap; pp.qnorm = qnorm.as<float>(); pp.rhs = rhs.as<float>();
-            HIP_TRY(launch_knn_pack(pp.k.q, d, d, qn, qpack.as<uint16_t>(), qnorm.as<float>(), s));
-            HIP_TRY(hipMemsetAsync(pool.p, 0xFF, (size_t)qn * (size_t)k * 8, s));
-            HIP_TRY(hipMemsetAsync(root.p, 0xFF, (size_t)qn * 8, s));
-            HIP_TRY(launch_fill_u32(rhs.as<uint32_t>(), 0xFF800000u, qn, s));  // -inf: every row passes
-            uint32_t h_flag = 0;
-            auto filter_rows = [&](uint64_t r0, uint32_t rows) -> int {
-                HIP_TRY(hipMemsetAsync(count.p, 0, (size_t)qn * 4, s));
-                HIP_TRY(hipMemsetAsync(flag.p, 0, 4, s));
-                KnnFilterParams f{};
-                f.qpack = qpack.as<uint16_t>(); f.bpack = bpack.as<uint16_t>() + (size_t)r0 * dp * 2; f.bnorm = bnorm.as<float>() + r0;
-                f.rhs = rhs.as<float>(); f.nq = qn; f.dp = dp; f.rows = rows; f.row0 = (uint32_t)r0; f.cap = cap;
-                f.cand = cand.as<uint32_t>(); f.count = count.as<uint32_t>(); f.overflow = flag.as<uint32_t>();
-                if (qtags) { f.btag = tags + r0; f.qtag = qtags + q0; }
-                HIP_TRY(launch_knn_filter(f, s));
-                return GBNNS_OK;
-            };
-            for (uint64_t r0 = 0, chunk = 0; r0 < n; r0 += chunk) {
-                chunk = r0 == 0 ? std::min<uint64_t>(n, rows_first) : std::min<uint64_t>(max_chunk, r0);
-                const uint32_t rows = (uint32_t)std::min<uint64_t>(chunk, n - r0);
-                if ((rc = filter_rows(r0, rows))) return rc;
-                HIP_TRY(hipMemcpyAsync(&h_flag, flag.p, 4, hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipStreamSynchronize(s));
-                if (!h_flag) {
-                    HIP_TRY(launch_knn_pool_update(pp, s));
-                    continue;
-                }
-                // some query kept more rows of this chunk than its list holds: the chunk again in pieces that cannot overflow
-                for (uint64_t r1 = r0; r1 < r0 + rows; r1 += rows_first) {
-                    if ((rc = filter_rows(r1, (uint32_t)std::min<uint64_t>(rows_first, r0 + rows - r1)))) return rc;
-                    HIP_TRY(launch_knn_pool_update(pp, s));
-                }
-            }
+            pp.k.q = sl.q; pp.k.nq = sl.qn; pp.k.out_ids = sl.out_ids; pp.k.out_dist = sl.out_dist;
+            pp.k.self_offset = sl.self_offset; pp.k.query_tags = sl.qtags;
+            pp.pool = pool.as<uint64_t>(); pp.root = root.as<uint64_t>(); pp.cand = w.cand.as<uint32_t>(); pp.count = w.count.as<uint32_t>();
+            pp.cap = cap; pp.qnorm = w.qnorm.as<float>(); pp.rhs = w.rhs.as<float>();
+            HIP_TRY(launch_knn_pack(sl.q, d, d, sl.qn, w.qpack.as<uint16_t>(), w.qnorm.as<float>(), s));
+            HIP_TRY(hipMemsetAsync(pool.p, 0xFF, (size_t)sl.qn * (size_t)k * 8, s));
+            HIP_TRY(hipMemsetAsync(root.p, 0xFF, (size_t)sl.qn * 8, s));
+            HIP_TRY(launch_fill_u32(w.rhs.as<uint32_t>(), 0xFF800000u, sl.qn, s));  // -inf: every row passes
+            auto sweep = [&](uint64_t r0, uint32_t rows) -> int { HIP_TRY(launch_knn_filter(w.chunk(r0, rows, sl.qn, st.tags, sl.qtags), s)); return GBNNS_OK; };
+            auto take = [&]() -> int { HIP_TRY(launch_knn_pool_update(pp, s)); return GBNNS_OK; };
+            if ((rc = knn_sweep_chunks(n, rows_first, max_chunk, sl.qn, w.count.as<uint32_t>(), w.flag.as<uint32_t>(), s, sweep, take))) return rc;
             HIP_TRY(launch_knn_pool_finalize(pp, s));
         }
     } else if (filter) {
-        const uint32_t dp = (d + 15u) & ~15u;
         const uint32_t cap = (uint32_t)std::max(256, 4 * k + 64);
         // The first rows are scanned exactly (they fill the heaps: thresholds exist afterwards); then filtered chunks, each
         // at most as long as everything before it -- a query is then expected to keep about k rows of a chunk, whatever
@@ -213,39 +302,21 @@ int knn_float_call(const KnnCall<float>& c) {
         // Chunks start on multiples of 64 rows (the filter reads the norms in aligned groups of four).
         const uint64_t max_chunk = std::min<uint64_t>((uint64_t)g_knob_knn_chunk.load(std::memory_order_relaxed), std::max<uint64_t>(64, (n / 16 + 63) & ~(uint64_t)63));  // (small sets, tests: a sixteenth)
         const uint64_t first = std::min<uint64_t>(n, (std::max<uint64_t>(std::min<uint64_t>(max_chunk, 8192), 4ull * (uint64_t)k) + 63) & ~(uint64_t)63);
-        DevBuf bpack, bnorm, qpack, qnorm, rhs, cand, count, flag;
-        struct Release2 {
-            DevBuf* b[8];
-            ~Release2() { for (DevBuf* x : b) x->release(); }
-        } release2{{&bpack, &bnorm, &qpack, &qnorm, &rhs, &cand, &count, &flag}};
-        if ((rc = bpack.ensure((size_t)n * dp * 4))) return rc;       // 2 dp bf16 per row
-        if ((rc = bnorm.ensure(((size_t)n + 64) * 4))) return rc;  // (+inf behind the last row: the filter reads whole blocks of 32)
-        if ((rc = qpack.ensure((size_t)nq * dp * 4))) return rc;
-        if ((rc = qnorm.ensure((size_t)nq * 4))) return rc;
-        if ((rc = rhs.ensure((size_t)nq * 4))) return rc;
-        if ((rc = cand.ensure((size_t)nq * cap * 4))) return rc;
-        if ((rc = count.ensure((size_t)nq * 4))) return rc;
-        if ((rc = flag.ensure(4))) return rc;
-        HIP_TRY(launch_fill_u32(bnorm.as<uint32_t>() + n, 0x7F800000u, 64, s));
-        HIP_TRY(launch_knn_pack(p.base, p.bstride, d, n, bpack.as<uint16_t>(), bnorm.as<float>(), s));
-        HIP_TRY(launch_knn_pack(p.q, d, d, nq, qpack.as<uint16_t>(), qnorm.as<float>(), s));
+        KnnFilterWork w;
+        if ((rc = w.prepare(p, nq, cap, s))) return rc;
+        HIP_TRY(launch_knn_pack(p.q, d, d, nq, w.qpack.as<uint16_t>(), w.qnorm.as<float>(), s));
         KnnParams ps = p;          // the first rows: the exact scan, heaps kept
         ps.n = first; ps.row0 = 0; ps.keep_heap = 1;
         HIP_TRY(launch_knn_scan(ps, metric, s));
-        HIP_TRY(launch_knn_thresholds(p.heap, p.heap_stride, k, qnorm.as<float>(), nq, rhs.as<float>(), s));
+        HIP_TRY(launch_knn_thresholds(p.heap, p.heap_stride, k, w.qnorm.as<float>(), nq, w.rhs.as<float>(), s));
         uint32_t h_flag = 0;
         for (uint64_t r0 = first, chunk = 0; r0 < n; r0 += chunk) {
             chunk = std::min<uint64_t>(max_chunk, r0);
             const uint32_t rows = (uint32_t)std::min<uint64_t>(chunk, n - r0);
-            HIP_TRY(hipMemsetAsync(count.p, 0, (size_t)nq * 4, s));
-            HIP_TRY(hipMemsetAsync(flag.p, 0, 4, s));
-            KnnFilterParams f{};
-            f.qpack = qpack.as<uint16_t>(); f.bpack = bpack.as<uint16_t>() + (size_t)r0 * dp * 2; f.bnorm = bnorm.as<float>() + r0;
-            f.rhs = rhs.as<float>(); f.nq = nq; f.dp = dp; f.rows = rows; f.row0 = (uint32_t)r0; f.cap = cap;
-            f.cand = cand.as<uint32_t>(); f.count = count.as<uint32_t>(); f.overflow = flag.as<uint32_t>();
-            if (qtags) { f.btag = tags + r0; f.qtag = qtags; }
-            HIP_TRY(launch_knn_filter(f, s));
-            HIP_TRY(hipMemcpyAsync(&h_flag, flag.p, 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemsetAsync(w.count.p, 0, (size_t)nq * 4, s));
+            HIP_TRY(hipMemsetAsync(w.flag.p, 0, 4, s));
+            HIP_TRY(launch_knn_filter(w.chunk(r0, rows, nq, st.tags, st.qtags), s));
+            HIP_TRY(hipMemcpyAsync(&h_flag, w.flag.p, 4, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
             if (h_flag) {
                 // some query kept more rows of this chunk than its list holds (adversarial order of the rows, or thresholds
@@ -253,11 +324,11 @@ int knn_float_call(const KnnCall<float>& c) {
                 KnnParams pc = p;
                 pc.base = p.base + (size_t)r0 * p.bstride; pc.n = rows; pc.row0 = r0; pc.keep_heap = 1;
                 HIP_TRY(launch_knn_scan(pc, metric, s));
-                HIP_TRY(launch_knn_thresholds(p.heap, p.heap_stride, k, qnorm.as<float>(), nq, rhs.as<float>(), s));
+                HIP_TRY(launch_knn_thresholds(p.heap, p.heap_stride, k, w.qnorm.as<float>(), nq, w.rhs.as<float>(), s));
             } else {
                 KnnRescoreParams rp{};
-                rp.k = p; rp.cand = cand.as<uint32_t>(); rp.count = count.as<uint32_t>(); rp.cap = cap;
-                rp.qnorm = qnorm.as<float>(); rp.rhs = rhs.as<float>();
+                rp.k = p; rp.cand = w.cand.as<uint32_t>(); rp.count = w.count.as<uint32_t>(); rp.cap = cap;
+                rp.qnorm = w.qnorm.as<float>(); rp.rhs = w.rhs.as<float>();
                 HIP_TRY(launch_knn_rescore(rp, s));
             }
         }
@@ -265,13 +336,7 @@ int knn_float_call(const KnnCall<float>& c) {
     } else {
         HIP_TRY(launch_knn_scan(p, metric, s));
     }
-    if (host) {
-        HIP_TRY(hipMemcpyAsync(out_ids, p.out_ids, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
-        if (out_dist) HIP_TRY(hipMemcpyAsync(out_dist, p.out_dist, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
-    }
-    // the temporaries are released below: wait for the work that uses them
-    HIP_TRY(hipStreamSynchronize(s));
-    return GBNNS_OK;
+    return st.copy_back(c, s);
 }
 
 // What gbnns_exact_knn_bytes does with a shape under the current knobs (gbnns_debug_knn_bytes_plan reports it).
@@ -290,71 +355,23 @@ KnnBytesPlan knn_bytes_plan(uint64_t n, uint64_t nq, uint32_t d, int k) {
     pl.first_rows = std::min<uint64_t>(n, pl.cap & ~63u);  // (chunks start on multiples of 64 rows: the sweep reads the row terms in aligned groups of four)
     pl.max_chunk = 4ull * (uint64_t)g_knob_knn_chunk.load(std::memory_order_relaxed);  // (the knob is a multiple of 64, at least 64)
     pl.pool = k >= g_knob_knn_pool_min_k.load(std::memory_order_relaxed);
-    pl.slab = knn_slab(nq, k, 8);
+    pl.slab = knn_slab_queries(nq, k, 8);
     return pl;
 }
 
-int knn_bytes_call(const KnnCall<uint8_t>& c) {
-    const int device = c.device, k = c.k, metric = c.metric, mem_kind = c.mem_kind;
-    const uint8_t* const base = c.base;
-    const uint8_t* const queries = c.queries;
-    const uint64_t n = c.n, n_q = c.n_q;
-    const uint32_t d = c.d;
-    const int64_t self_offset = c.self_offset;
-    uint32_t* const out_ids = c.out_ids;
-    float* const out_dist = c.out_dist;
-    void* const stream = c.stream;
-    if (!base || !queries || !out_ids || (c.tagged && (!c.row_tags || !c.query_tags))) return fail(GBNNS_ERR_INVALID, "null argument");
-    if (n == 0 || n >= (1ull << 32) - 1) return fail(GBNNS_ERR_INVALID, "n must be in [1, 2^32 - 1)");
-    if (n_q >= (1ull << 31)) return fail(GBNNS_ERR_INVALID, "n_q too large");
-    if (k < 1 || k > (1 << 20)) return fail(GBNNS_ERR_INVALID, "k must be in [1, 2^20]");
-    if (d == 0) return fail(GBNNS_ERR_INVALID, "d must be >= 1");
-    if (metric != GBNNS_METRIC_L2 && metric != GBNNS_METRIC_NEG_DOT) return fail(GBNNS_ERR_INVALID, "unknown metric %d", metric);
-    if (mem_kind != GBNNS_MEM_HOST && mem_kind != GBNNS_MEM_DEVICE) return fail(GBNNS_ERR_INVALID, "unknown mem_kind %d", mem_kind);
-    if (d > 256)
-        return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_exact_knn_bytes: d <= 256 (every sum of the distance must stay an integer below 2^24 to be exact "
-                    "in float32 and on the int8 matrix cores; got %u): widen the rows and call gbnns_exact_knn", d);
-    if (k > 4096) return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_exact_knn_bytes: k <= 4096 (got %d): widen the rows and call gbnns_exact_knn", k);
-    if (metric == GBNNS_METRIC_NEG_DOT && d % 8 != 0)
-        return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_exact_knn_bytes: the negative-dot form needs d %% 8 == 0 (got %u)", d);
-    if (self_offset < -1) return fail(GBNNS_ERR_INVALID, "self_offset must be >= -1");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-        return fail(GBNNS_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= count) return fail(GBNNS_ERR_NO_DEVICE, "device %d out of range (%d devices)", device, count);
-    if (n_q == 0) return GBNNS_OK;
-    HIP_TRY(hipSetDevice(device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool host = mem_kind == GBNNS_MEM_HOST;
-    const uint32_t nq = (uint32_t)n_q;
-    const KnnBytesPlan pl = knn_bytes_plan(n, n_q, d, k);
-    const uint32_t dp = pl.dp, cap = pl.cap, slab = pl.slab;
-    DevBuf b_dev, q_dev, ids_dev, dist_dev, bpack, bterm, qpack, qterm, thr, cand, cnt, flag, keys, root, tag_dev, qtag_dev;
-    struct Release {  // DevBuf has no destructor (index members are released by gbnns_index_destroy)
-        DevBuf* b[16];
-        ~Release() { for (DevBuf* x : b) x->release(); }
-    } release{{&b_dev, &q_dev, &ids_dev, &dist_dev, &bpack, &bterm, &qpack, &qterm, &thr, &cand, &cnt, &flag, &keys, &root, &tag_dev, &qtag_dev}};
+int knn_call(const KnnCall<uint8_t>& c) {
     int rc;
-    const uint8_t* base_d = base;
-    const uint8_t* q_d = queries;
-    uint32_t* ids_d = out_ids;
-    float* dist_d = out_dist;
-    if (host) {  // uploaded as bytes: a quarter of the float call's traffic, and no float copy anywhere
-        if (!c.resident) {
-            if ((rc = b_dev.ensure((size_t)n * d))) return rc;
-            HIP_TRY(hipMemcpyAsync(b_dev.p, base, (size_t)n * d, hipMemcpyHostToDevice, s));
-            base_d = b_dev.as<uint8_t>();
-        }
-        if ((rc = q_dev.ensure((size_t)nq * d))) return rc;
-        if ((rc = ids_dev.ensure((size_t)nq * k * 4))) return rc;
-        if (out_dist && (rc = dist_dev.ensure((size_t)nq * k * 4))) return rc;
-        HIP_TRY(hipMemcpyAsync(q_dev.p, queries, (size_t)nq * d, hipMemcpyHostToDevice, s));
-        q_d = q_dev.as<uint8_t>(); ids_d = ids_dev.as<uint32_t>();
-        dist_d = out_dist ? dist_dev.as<float>() : nullptr;
-    }
-    const uint32_t* qtags = nullptr;  // tagged: the device copies of the tag words; a sweep with null tags is the untagged instance
-    if (c.tagged && (rc = knn_stage_tags(c, tag_dev, qtag_dev, qtags, s))) return rc;
-    const uint32_t* const tags = tag_dev.as<uint32_t>();
+    if ((rc = knn_check(c)) || c.n_q == 0) return rc;
+    HIP_TRY(hipSetDevice(c.device));
+    hipStream_t s = static_cast<hipStream_t>(c.stream);
+    const int k = c.k, metric = c.metric;
+    const uint64_t n = c.n;
+    const uint32_t d = c.d, nq = (uint32_t)c.n_q;
+    const KnnBytesPlan pl = knn_bytes_plan(n, c.n_q, d, k);
+    const uint32_t dp = pl.dp, cap = pl.cap, slab = pl.slab;
+    KnnStaged<uint8_t> st;
+    ScopedDevBuf bpack, bterm, qpack, qterm, thr, cand, cnt, flag, keys, root;
+    if ((rc = st.stage(c, s))) return rc;
     const size_t heap_stride = ((size_t)slab + 63) & ~(size_t)63;
     if ((rc = bpack.ensure((size_t)n * dp))) return rc;
     if ((rc = bterm.ensure(((size_t)n + 64) * 4))) return rc;  // (the sweep reads whole blocks of 32 rows' terms)
@@ -367,72 +384,44 @@ int knn_bytes_call(const KnnCall<uint8_t>& c) {
     if ((rc = keys.ensure(pl.pool ? (size_t)slab * (size_t)k * 8 : heap_stride * (size_t)k * 8))) return rc;
     if (pl.pool && (rc = root.ensure((size_t)slab * 8))) return rc;
     HIP_TRY(hipMemsetAsync(bterm.as<int32_t>() + n, 0, 64 * 4, s));
-    HIP_TRY(launch_knn_bytes_pack(base_d, c.bstride, d, dp, metric, 0, n, bpack.as<int8_t>(), bterm.as<int32_t>(), s));
+    HIP_TRY(launch_knn_bytes_pack(st.base, c.bstride, d, dp, metric, 0, n, bpack.as<int8_t>(), bterm.as<int32_t>(), s));
     for (uint32_t q0 = 0; q0 < nq; q0 += slab) {
-        const uint32_t qn = std::min(slab, nq - q0);
+        const KnnSlab<uint8_t> sl = knn_slab_at(c, st, q0, slab);
         KnnBytesOfferParams op{};
-        op.cand = cand.as<uint64_t>(); op.count = cnt.as<uint32_t>(); op.cap = cap; op.nq = qn; op.k = k;
-        op.self_offset = self_offset >= 0 ? self_offset + (int64_t)q0 : -1;
+        op.cand = cand.as<uint64_t>(); op.count = cnt.as<uint32_t>(); op.cap = cap; op.nq = sl.qn; op.k = k;
+        op.self_offset = sl.self_offset;
         op.qterm = qterm.as<int32_t>(); op.thr = thr.as<int32_t>();
         if (pl.pool) { op.pool = keys.as<uint64_t>(); op.root = root.as<uint64_t>(); }
         else { op.heap = keys.as<uint64_t>(); op.heap_stride = heap_stride; }
-        HIP_TRY(launch_knn_bytes_pack(q_d + (size_t)q0 * d, d, d, dp, metric, 1, qn, qpack.as<int8_t>(), qterm.as<int32_t>(), s));
-        HIP_TRY(hipMemsetAsync(keys.p, 0xFF, pl.pool ? (size_t)qn * (size_t)k * 8 : heap_stride * (size_t)k * 8, s));
-        if (pl.pool) HIP_TRY(hipMemsetAsync(root.p, 0xFF, (size_t)qn * 8, s));
-        HIP_TRY(launch_fill_u32(thr.as<uint32_t>(), 0x80000000u, qn, s));  // INT32_MIN: every row passes
-        uint32_t h_flag = 0;
-        auto sweep_rows = [&](uint64_t r0, uint32_t rows) -> int {
-            HIP_TRY(hipMemsetAsync(cnt.p, 0, (size_t)qn * 4, s));
-            HIP_TRY(hipMemsetAsync(flag.p, 0, 4, s));
+        HIP_TRY(launch_knn_bytes_pack(sl.q, d, d, dp, metric, 1, sl.qn, qpack.as<int8_t>(), qterm.as<int32_t>(), s));
+        HIP_TRY(hipMemsetAsync(keys.p, 0xFF, pl.pool ? (size_t)sl.qn * (size_t)k * 8 : heap_stride * (size_t)k * 8, s));
+        if (pl.pool) HIP_TRY(hipMemsetAsync(root.p, 0xFF, (size_t)sl.qn * 8, s));
+        HIP_TRY(launch_fill_u32(thr.as<uint32_t>(), 0x80000000u, sl.qn, s));  // INT32_MIN: every row passes
+        auto sweep = [&](uint64_t r0, uint32_t rows) -> int {
             KnnBytesSweepParams f{};
             f.qpack = qpack.as<int8_t>(); f.bpack = bpack.as<int8_t>() + (size_t)r0 * dp; f.bterm = bterm.as<int32_t>() + r0;
-            f.qterm = qterm.as<int32_t>(); f.thr = thr.as<int32_t>(); f.nq = qn; f.dp = dp; f.rows = rows; f.row0 = (uint32_t)r0; f.cap = cap;
+            f.qterm = qterm.as<int32_t>(); f.thr = thr.as<int32_t>(); f.nq = sl.qn; f.dp = dp; f.rows = rows; f.row0 = (uint32_t)r0; f.cap = cap;
             f.shift = metric == GBNNS_METRIC_L2 ? 1 : 0;
             f.cand = cand.as<uint64_t>(); f.count = cnt.as<uint32_t>(); f.overflow = flag.as<uint32_t>();
-            if (qtags) { f.btag = tags + r0; f.qtag = qtags + q0; }
+            if (sl.qtags) { f.btag = st.tags + r0; f.qtag = sl.qtags; }
             HIP_TRY(launch_knn_bytes_sweep(f, s));
             return GBNNS_OK;
         };
-        // the first chunk cannot overflow a list; a later one is at most as long as everything before it -- a query is then
-        // expected to keep about k rows of it, whatever the chunk -- and at most max_chunk rows
-        for (uint64_t r0 = 0, chunk = 0; r0 < n; r0 += chunk) {
-            chunk = r0 == 0 ? pl.first_rows : std::min<uint64_t>(pl.max_chunk, r0);
-            const uint32_t rows = (uint32_t)std::min<uint64_t>(chunk, n - r0);
-            if ((rc = sweep_rows(r0, rows))) return rc;
-            if (r0 != 0) {
-                HIP_TRY(hipMemcpyAsync(&h_flag, flag.p, 4, hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipStreamSynchronize(s));
-            }
-            if (r0 == 0 || !h_flag) {
-                HIP_TRY(launch_knn_bytes_offer(op, s));
-                continue;
-            }
-            // some query kept more rows of this chunk than its list holds (rows in an adversarial order, a mass of ties at the
-            // threshold): nothing of the chunk has been offered yet; the chunk again in pieces that cannot overflow
-            for (uint64_t r1 = r0; r1 < r0 + rows; r1 += pl.first_rows) {
-                if ((rc = sweep_rows(r1, (uint32_t)std::min<uint64_t>(pl.first_rows, r0 + rows - r1)))) return rc;
-                HIP_TRY(launch_knn_bytes_offer(op, s));
-            }
-        }
+        auto take = [&]() -> int { HIP_TRY(launch_knn_bytes_offer(op, s)); return GBNNS_OK; };
+        if ((rc = knn_sweep_chunks(n, pl.first_rows, pl.max_chunk, sl.qn, cnt.as<uint32_t>(), flag.as<uint32_t>(), s, sweep, take))) return rc;
         if (pl.pool) {
             KnnPoolParams pp{};
-            pp.k.nq = qn; pp.k.k = k; pp.k.out_ids = ids_d + (size_t)q0 * k; pp.k.out_dist = dist_d ? dist_d + (size_t)q0 * k : nullptr;
+            pp.k.nq = sl.qn; pp.k.k = k; pp.k.out_ids = sl.out_ids; pp.k.out_dist = sl.out_dist;
             pp.pool = keys.as<uint64_t>();
             HIP_TRY(launch_knn_pool_finalize(pp, s));
         } else {
             KnnParams kp{};
-            kp.nq = qn; kp.k = k; kp.heap = keys.as<uint64_t>(); kp.heap_stride = heap_stride;
-            kp.out_ids = ids_d + (size_t)q0 * k; kp.out_dist = dist_d ? dist_d + (size_t)q0 * k : nullptr;
+            kp.nq = sl.qn; kp.k = k; kp.heap = keys.as<uint64_t>(); kp.heap_stride = heap_stride;
+            kp.out_ids = sl.out_ids; kp.out_dist = sl.out_dist;
             HIP_TRY(launch_knn_finalize(kp, s));
         }
     }
-    if (host) {
-        HIP_TRY(hipMemcpyAsync(out_ids, ids_d, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
-        if (out_dist) HIP_TRY(hipMemcpyAsync(out_dist, dist_d, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
-    }
-    // the temporaries are released below: wait for the work that uses them
-    HIP_TRY(hipStreamSynchronize(s));
-    return GBNNS_OK;
+    return st.copy_back(c, s);
 }
 
 template <class T>
@@ -444,6 +433,24 @@ KnnCall<T> knn_free_call(int device, const T* base, uint64_t n, const T* queries
     c.out_ids = out_ids; c.out_dist = out_dist; c.mem_kind = mem_kind; c.stream = stream;
     return c;
 }
+
+// gbnns_index_exact_knn behind its own refusals: `table` is the handle's float or byte table, read in place at its device row stride.
+template <class T>
+int knn_index_call(gbnns_index* ix, const T* table, const T* queries, uint64_t n_q, const uint32_t* query_tags, int k, int64_t self_offset,
+                   uint32_t* out_ids, float* out_dist, int mem_kind, void* stream) {
+    if (!table) return fail(GBNNS_ERR_INVALID, "gbnns_index_exact_knn: the handle has no original-space table");
+    KnnCall<T> c = knn_free_call(ix->device, table, ix->n, queries, n_q, ix->d, k, ix->metric, self_offset, query_tags != nullptr,
+                                 ix->tags.as<uint32_t>(), query_tags, out_ids, out_dist, mem_kind, stream);
+    c.bstride = ix->d_pad; c.resident = true;
+    // (enter_stream: the deferred calls still owed are joined, as by any call without GBNNS_FLAG_DEFER_JOIN, and `stream` waits for the
+    // handle's work in flight on another stream -- a gbnns_index_set_tags among it)
+    HIP_TRY(hipSetDevice(ix->device));
+    int rc;
+    if ((rc = enter_stream(ix, static_cast<hipStream_t>(stream)))) return rc;
+    rc = knn_call(c);
+    if (rc == GBNNS_OK && n_q) ix->in_flight = false;  // (the call returned behind a synchronisation of its stream)
+    return rc;
+}
 }  // namespace
 
 extern "C" {
@@ -451,25 +458,25 @@ extern "C" {
 int gbnns_exact_knn(int device, const float* base, uint64_t n, const float* queries, uint64_t n_q,
                     uint32_t d, int k, int metric, int64_t self_offset, uint32_t* out_ids, float* out_dist,
                     int mem_kind, void* stream) {
-    return knn_float_call(knn_free_call(device, base, n, queries, n_q, d, k, metric, self_offset, false, nullptr, nullptr, out_ids, out_dist, mem_kind, stream));
+    return knn_call(knn_free_call(device, base, n, queries, n_q, d, k, metric, self_offset, false, nullptr, nullptr, out_ids, out_dist, mem_kind, stream));
 }
 
 int gbnns_exact_knn_tagged(int device, const float* base, uint64_t n, const float* queries, uint64_t n_q, uint32_t d, int k, int metric,
                            int64_t self_offset, const uint32_t* row_tags, const uint32_t* query_tags, uint32_t* out_ids, float* out_dist,
                            int mem_kind, void* stream) {
-    return knn_float_call(knn_free_call(device, base, n, queries, n_q, d, k, metric, self_offset, true, row_tags, query_tags, out_ids, out_dist, mem_kind, stream));
+    return knn_call(knn_free_call(device, base, n, queries, n_q, d, k, metric, self_offset, true, row_tags, query_tags, out_ids, out_dist, mem_kind, stream));
 }
 
 int gbnns_exact_knn_bytes(int device, const uint8_t* base, uint64_t n, const uint8_t* queries, uint64_t n_q,
                           uint32_t d, int k, int metric, int64_t self_offset, uint32_t* out_ids, float* out_dist,
                           int mem_kind, void* stream) {
-    return knn_bytes_call(knn_free_call(device, base, n, queries, n_q, d, k, metric, self_offset, false, nullptr, nullptr, out_ids, out_dist, mem_kind, stream));
+    return knn_call(knn_free_call(device, base, n, queries, n_q, d, k, metric, self_offset, false, nullptr, nullptr, out_ids, out_dist, mem_kind, stream));
 }
 
 int gbnns_exact_knn_bytes_tagged(int device, const uint8_t* base, uint64_t n, const uint8_t* queries, uint64_t n_q, uint32_t d, int k, int metric,
                                  int64_t self_offset, const uint32_t* row_tags, const uint32_t* query_tags, uint32_t* out_ids, float* out_dist,
                                  int mem_kind, void* stream) {
-    return knn_bytes_call(knn_free_call(device, base, n, queries, n_q, d, k, metric, self_offset, true, row_tags, query_tags, out_ids, out_dist, mem_kind, stream));
+    return knn_call(knn_free_call(device, base, n, queries, n_q, d, k, metric, self_offset, true, row_tags, query_tags, out_ids, out_dist, mem_kind, stream));
 }
 
 // The same computation over the handle's own table, read in place at its device row stride (d_pad floats / bytes); the row tags are the
@@ -484,28 +491,8 @@ int gbnns_index_exact_knn(gbnns_index* ix, const float* queries, const uint8_t* 
         return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_index_exact_knn: float queries on a byte handle: there is no mixed-pair scan (uint8 rows against "
                     "float queries); pass queries_u8, or widen the table and call gbnns_exact_knn");
     if (query_tags && !ix->tags.p) return fail(GBNNS_ERR_INVALID, "gbnns_index_exact_knn with query_tags but without gbnns_index_set_tags");
-    const bool tagged = query_tags != nullptr;
-    int rc;
-    if (queries) {
-        if (!ix->db) return fail(GBNNS_ERR_INVALID, "gbnns_index_exact_knn: the handle has no original-space table");
-        KnnCall<float> c = knn_free_call(ix->device, ix->db, ix->n, queries, n_q, ix->d, k, ix->metric, self_offset, tagged, ix->tags.as<uint32_t>(),
-                                         query_tags, out_ids, out_dist, mem_kind, stream);
-        c.bstride = ix->d_pad; c.resident = true;
-        // (enter_stream: the deferred calls still owed are joined, as by any call without GBNNS_FLAG_DEFER_JOIN, and `stream` waits for the
-        // handle's work in flight on another stream -- a gbnns_index_set_tags among it)
-        HIP_TRY(hipSetDevice(ix->device));
-        if ((rc = enter_stream(ix, static_cast<hipStream_t>(stream)))) return rc;
-        rc = knn_float_call(c);
-    } else {
-        KnnCall<uint8_t> c = knn_free_call(ix->device, ix->db_b, ix->n, queries_u8, n_q, ix->d, k, ix->metric, self_offset, tagged,
-                                           ix->tags.as<uint32_t>(), query_tags, out_ids, out_dist, mem_kind, stream);
-        c.bstride = ix->d_pad; c.resident = true;
-        HIP_TRY(hipSetDevice(ix->device));
-        if ((rc = enter_stream(ix, static_cast<hipStream_t>(stream)))) return rc;
-        rc = knn_bytes_call(c);
-    }
-    if (rc == GBNNS_OK && n_q) ix->in_flight = false;  // (the call returned behind a synchronisation of its stream)
-    return rc;
+    if (queries) return knn_index_call(ix, ix->db, queries, n_q, query_tags, k, self_offset, out_ids, out_dist, mem_kind, stream);
+    return knn_index_call(ix, ix->db_b, queries_u8, n_q, query_tags, k, self_offset, out_ids, out_dist, mem_kind, stream);
 }
 
 int gbnns_debug_knn_bytes_plan(uint64_t n, uint64_t n_q, uint32_t d, int k, uint32_t* dp, uint32_t* cap, uint64_t* first_rows,
@@ -522,7 +509,7 @@ int gbnns_debug_knn_slab(int bytes, uint64_t n_q, int k, uint32_t* slab) {
     if (!slab) return fail(GBNNS_ERR_INVALID, "gbnns_debug_knn_slab: null output");
     if ((bytes != 0 && bytes != 1) || n_q >= (1ull << 31) || k < 1 || k > 4096)
         return fail(GBNNS_ERR_INVALID, "gbnns_debug_knn_slab: not a shape the pool path of gbnns_exact_knn / gbnns_exact_knn_bytes takes");
-    *slab = knn_slab(n_q, k, bytes ? 8 : 4);
+    *slab = knn_slab_queries(n_q, k, bytes ? 8 : 4);
     return GBNNS_OK;
 }
 
@@ -558,11 +545,7 @@ int gbnns_build_graph_gd_device(int device, const uint64_t* knn_offsets, const u
     const bool on_device = M <= 64 && d <= 128;
     if (on_device) {
         HIP_TRY(hipSetDevice(device));
-        DevBuf ds_dev, off_dev, nbr_dev, adj_dev, deg_dev;
-        struct Release {
-            DevBuf* b[5];
-            ~Release() { for (DevBuf* x : b) x->release(); }
-        } release{{&ds_dev, &off_dev, &nbr_dev, &adj_dev, &deg_dev}};
+        ScopedDevBuf ds_dev, off_dev, nbr_dev, adj_dev, deg_dev;
         const uint64_t total = knn_offsets[n];
         const uint32_t dpad = round_up(d, 4);
         int rc;

@@ -122,3 +122,27 @@ def overflow_case(k, nq=NQ, n=12000, d=32):
     q = np.full((nq, d), 128, np.uint8)
     q[1:, :4] += rng.integers(0, 4, (nq - 1, 4)).astype(np.uint8)
     return base, q, tu.tag_table(600 + k, n), np.full(nq, 1 << 1, np.uint32)
+
+
+FLOAT_OVERFLOW_N = {False: 12000, True: 20000}   # rows of overflow_case for gbnns_exact_knn's pool path: untagged / tagged (half the rows allowed)
+
+
+def float_pool_plan(n, k, knn_chunk):
+    """The chunks of gbnns_exact_knn's pool path (graph_api.cpp) in the form of a knn_bytes_plan dict, for knn_bytes_util.chunk_plan: the
+    byte call's first chunk and key slots, later chunks of at most 4 knn_chunk rows AND at most a sixteenth of the set (in whole 64s)."""
+    cap = 4 * k + 64
+    return dict(cap=cap, first_rows=min(n, cap & ~63), max_chunk=min(4 * knn_chunk, max(64, (n // 16 + 63) & ~63)))
+
+
+def kept_rows(plan, base, q, allowed, k):
+    """[queries x chunks of knn_bytes_util.chunk_plan(plan, n)] how many rows of a chunk a query's key list has to take: the allowed rows
+    no farther than the k-th nearest allowed row before the chunk (every allowed row while there are fewer than k).  From the integer
+    distances of byte rows; a lower bound of what a sweep keeps, whose threshold is never tighter than that."""
+    dist = ku.int_dist(base, q, ku.L2).astype(np.float64)
+    dist[:, ~allowed] = np.inf
+    out = []
+    for r0, rows in ku.chunk_plan(plan, base.shape[0]):
+        kth = np.partition(dist[:, :r0], k - 1, axis=1)[:, k - 1] if r0 >= k else np.full(q.shape[0], np.inf)
+        part = dist[:, r0:r0 + rows]
+        out.append((np.isfinite(part) & (part <= kth[:, None])).sum(1))
+    return np.stack(out, axis=1)

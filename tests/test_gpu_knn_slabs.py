@@ -198,25 +198,35 @@ def test_index_exact_knn(g, orc, kind):
 
 
 @pytest.mark.parametrize("tagged", (False, True))
-@pytest.mark.parametrize("k", (30, 100))
-def test_overflowing_chunks_are_swept_again_in_every_slab(g, orc, k, tagged):
+@pytest.mark.parametrize("k,kind", [pytest.param(30, "bytes", id="30"), pytest.param(100, "bytes", id="100"), pytest.param(100, "float", id="float-100")])
+def test_overflowing_chunks_are_swept_again_in_every_slab(g, orc, k, kind, tagged):
     """test_gpu_knn_bytes.test_overflowing_chunks_are_swept_again's rows (farthest first) against 300 queries, knn_chunk = 512: chunks that
     overflow a key list are swept again in pieces inside the second and third slab too.  k = 30 on heaps, k = 100 on pools; all rows, and
-    half of them allowed."""
-    base, q, T, Q = su.overflow_case(k)
-    n, nq = base.shape[0], q.shape[0]
-    with knobs(g, knn_chunk=512):
-        plan = g.knn_bytes_plan(n, nq, 32, k)
+    half of them allowed.  "float": the same rows widened, on gbnns_exact_knn's pool path ("knn_filter" = 2), whose chunks are a sixteenth
+    of the set -- 768 rows of 12 000, 1 280 of the tagged input's 20 000 -- against cap = 464 (tests/test_knn_slabs_cpu.py counts the hits)."""
+    if kind == "float":
+        base, q, T, Q = su.overflow_case(k, n=su.FLOAT_OVERFLOW_N[tagged])
+        n, nq = base.shape[0], q.shape[0]
+        plan = su.float_pool_plan(n, k, 512)
+        kn = dict(knn_filter=2, knn_chunk=512)
+    else:
+        base, q, T, Q = su.overflow_case(k)
+        n, nq = base.shape[0], q.shape[0]
+        kn = dict(knn_chunk=512)
+        with knobs(g, **kn):
+            plan = g.knn_bytes_plan(n, nq, 32, k)
         assert plan["max_chunk"] >= 4 * plan["cap"] and plan["pool"] == (k >= 64)
-        assert sum(rows > plan["cap"] for _, rows in ku.chunk_plan(plan, n)) >= 4
+    assert sum(rows > plan["cap"] for _, rows in ku.chunk_plan(plan, n)) >= 4
     d0 = ((base.astype(np.int64) - 128) ** 2).sum(1)
     assert (q[0] == 128).all() and (np.diff(d0) <= 0).all()   # (query 0: every row at least as near as all rows before it)
+    if kind == "float":
+        base, q = ku.widen(base), ku.widen(q)
     if tagged:
         want = tu.expected(orc, base, q, T, Q, k, ku.L2)
-        _slabbed(g, lambda: g.exact_knn(base, q, k, want_dist=True, row_tags=T, query_tags=Q), want, nq, k, True, ("overflow, tagged", k), knn_chunk=512)
+        _slabbed(g, lambda: g.exact_knn(base, q, k, want_dist=True, row_tags=T, query_tags=Q), want, nq, k, kind == "bytes", ("overflow, tagged", kind, k), **kn)
     else:
         want = orc.exact_knn(ku.widen(base), ku.widen(q), k, ku.L2, threads=8)
-        _slabbed(g, lambda: g.exact_knn(base, q, k, want_dist=True), want, nq, k, True, ("overflow", k), knn_chunk=512)
+        _slabbed(g, lambda: g.exact_knn(base, q, k, want_dist=True), want, nq, k, kind == "bytes", ("overflow", kind, k), **kn)
 
 
 # ---- the long lists: k = 1 000 .. 4 096 (one slab unless said otherwise) ----

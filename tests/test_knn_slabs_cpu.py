@@ -123,3 +123,22 @@ def test_fixture_preconditions(orc):
                 if tagged:
                     su.check_tag_offsets(T, Qo)
     assert ku.slabs(su.SLAB, su.NQ) == [(0, 128), (128, 128), (256, 44)]
+    # the float input of test_overflowing_chunks_are_swept_again_in_every_slab (k = 100, "knn_chunk" = 512): the pool rule's chunk for that
+    # n, and more hits of the centre query (every allowed row: the rows come farthest first) than a list holds in the first chunk of that
+    # length -- the first chunk longer than cap but for the tagged input, whose 896 rows at r0 = 896 hold fewer allowed ones than cap --
+    # and, for the slab loop, some query with more rows to keep than cap in some chunk of EVERY slab
+    for tagged, chunk in ((False, 768), (True, 1280)):
+        n = su.FLOAT_OVERFLOW_N[tagged]
+        base, q, T, Q = su.overflow_case(100, n=n)
+        allowed = (T & Q[0]) != 0 if tagged else np.ones(n, bool)
+        assert (Q == Q[0]).all() and (not tagged or 0.45 * n < np.count_nonzero(allowed) < 0.55 * n)
+        plan = su.float_pool_plan(n, 100, 512)
+        assert plan["cap"] == 464 and plan["first_rows"] == 448 and plan["max_chunk"] == chunk
+        chunks = ku.chunk_plan(plan, n)
+        j = next(j for j, (_, rows) in enumerate(chunks) if rows == chunk)
+        assert all(rows <= plan["cap"] or (tagged and rows == 896) for _, rows in chunks[:j])
+        kept = su.kept_rows(plan, base, q, allowed, 100)
+        r0 = chunks[j][0]
+        assert kept[0, j] == np.count_nonzero(allowed[r0:r0 + chunk]) > plan["cap"], (tagged, kept[0, j])
+        for q0, qn in ku.slabs(su.SLAB, su.NQ):
+            assert (kept[q0:q0 + qn] > plan["cap"]).any(axis=0).sum() >= 4, (tagged, q0)
