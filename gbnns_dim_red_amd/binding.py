@@ -43,6 +43,7 @@ SYMBOLS = [
     "gbnns_exact_knn_bytes", "gbnns_debug_knn_bytes_plan", "gbnns_debug_knn_slab",
     "gbnns_search_byte_queries", "gbnns_debug_byte_query_plan",
     "gbnns_exact_knn_tagged", "gbnns_exact_knn_bytes_tagged", "gbnns_index_exact_knn",
+    "gbnns_index_tag_census", "gbnns_search_tagged_auto",
 ]
 
 
@@ -154,6 +155,9 @@ def load_library():
     lib.gbnns_exact_knn_bytes_tagged.argtypes = lib.gbnns_exact_knn_tagged.argtypes
     lib.gbnns_index_exact_knn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_int, C.c_void_p]
+    lib.gbnns_index_tag_census.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.gbnns_search_tagged_auto.argtypes = [C.c_void_p, C.POINTER(_SearchArgs), C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]
     lib.gbnns_debug_knn_bytes_plan.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
     lib.gbnns_debug_knn_slab.argtypes = [C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_uint32)]
@@ -269,6 +273,23 @@ def bridge_graph(off, nbr, allowed):
     out = np.where(allowed[v], v, from_cut).astype(np.uint32)
     new_off = start[o].astype(np.uint64)
     return new_off, np.ascontiguousarray(out)
+
+
+def tag_census(T, Q):
+    """gbnns_index_tag_census by NumPy (no device needed): for the row tags T [n] and the query words Q [nq], (allowed uint32 [nq], first uint32
+    [nq]) -- allowed[i] = the number of rows j with (T[j] & Q[i]) != 0, first[i] = the lowest such j, 0xFFFFFFFF when there is none.  One pass
+    over T per distinct word of Q."""
+    T = np.ascontiguousarray(T, np.uint32).reshape(-1)
+    Q = np.ascontiguousarray(Q, np.uint32).reshape(-1)
+    allowed = np.zeros(len(Q), np.uint32)
+    first = np.full(len(Q), 0xFFFFFFFF, np.uint32)
+    for w in np.unique(Q):
+        rows = np.flatnonzero(T & w)
+        sel = Q == w
+        allowed[sel] = len(rows)
+        if len(rows):
+            first[sel] = rows[0]
+    return allowed, first
 
 
 def tag_plan(metric, dim, n, ell_stride, ef, aux_stride=0, n_entries=1, wide=False, rr_reserve=0):
@@ -913,6 +934,89 @@ class Index:
         _check(self._lib.gbnns_index_exact_knn(self._h, None if u8 else _ptr(queries), _ptr(queries) if u8 else None, nq, _ptr(query_tags), k,
                                                self_offset, _ptr(ids), _ptr(dist), MEM_DEVICE if dev else MEM_HOST, sptr))
         return (ids, dist) if want_dist else ids
+
+    def tag_census(self, query_tags):
+        """gbnns_index_tag_census over set_tags()'s table: (allowed, first) [nq] -- the number of rows query word i allows and the lowest of
+        them (0xFFFFFFFF: none); the module-level tag_census(T, Q) by the device.  numpy uint32 in -> numpy uint32 out (synchronous); a
+        CUDA/ROCm int32 tensor in -> int32 tensors out, enqueued on the current stream."""
+        dev = _is_dev(query_tags)
+        nq = int(query_tags.shape[0]) if dev else int(np.asarray(query_tags).reshape(-1).shape[0])
+        query_tags = _prep_tags(query_tags if dev else np.asarray(query_tags).reshape(-1), dev, nq, "query_tags")
+        if dev:
+            import torch
+            allowed = torch.empty(nq, dtype=torch.int32, device=query_tags.device)
+            first = torch.empty(nq, dtype=torch.int32, device=query_tags.device)
+            sptr = torch.cuda.current_stream(query_tags.device).cuda_stream
+        else:
+            allowed, first = np.empty(nq, np.uint32), np.empty(nq, np.uint32)
+            sptr = None
+        _check(self._lib.gbnns_index_tag_census(self._h, _ptr(query_tags) if nq else None, nq, _ptr(allowed), _ptr(first),
+                                                MEM_DEVICE if dev else MEM_HOST, sptr))
+        return allowed, first
+
+    def search_auto(self, queries, ef, top_k, query_tags, *, scan_below, mode=MODE_NET, queries_low=None, entry_ids=None,
+                    want=("hops", "dist_calc"), flags=0, aux=False, llf=False, hops_bound=50, hash_capacity=0):
+        """gbnns_search_tagged_auto: a tagged search that routes itself.  The census of set_tags()'s table gives every query the number of rows
+        its word allows; query i takes the exact scan (exact_knn(query_tags=...)'s row) when that number is <= scan_below -- a required
+        keyword: 0 sends only the queries that may see nothing to the scan, 2**64 - 1 every query -- and else the tagged walk
+        (search(query_tags=..., top_k=...)'s row; flags=FLAG_TAG_BRIDGE: the bridged walk), entered at the lowest row it may see unless
+        entry_ids are given.  Returns search()'s dict plus "top_ids" / "top_dist" [nq x top_k], "allowed" [nq] (the census) and "route" [nq]
+        uint8 (0 = walk, 1 = scan); a scan-routed query's "ids" is top_ids[:, 0] and its walk-only outputs are the bad-entry row.  numpy
+        in -> numpy out; CUDA/ROCm tensors in -> tensors out, on the current stream; either way the call returns when the work has finished.
+        uint8 queries go to the byte form (a byte handle; on a float handle: TypeError)."""
+        u8 = _is_u8(queries)
+        if u8 and not self.is_bytes:
+            raise TypeError("uint8 queries need a byte handle (Index(db=<uint8>)); widen them for a float handle")
+        if aux:
+            flags |= FLAG_AUX_GRAPH | (FLAG_LLF if llf else 0)
+        dev = _is_dev(queries)
+        if dev and not queries.is_cuda:
+            raise TypeError("queries: a numpy array or a CUDA/ROCm tensor")
+        queries = _prep(queries, np.uint8, "uint8") if u8 else _prep(queries, np.float32, "float32")
+        if queries_low is not None and _is_dev(queries_low) != dev:
+            raise TypeError("queries and queries_low must live in the same memory kind")
+        queries_low = _prep(queries_low, np.float32, "float32")
+        nq = int(queries.shape[0])
+        if queries.ndim != 2 or int(queries.shape[1]) != self.d:
+            raise ValueError("query dimension mismatch")
+        if query_tags is None:
+            raise TypeError("search_auto needs query_tags")
+        query_tags = _prep_tags(query_tags, dev, nq, "query_tags")
+        res = {}
+        if dev:
+            import torch
+            tdev = queries.device
+            if entry_ids is not None:
+                entry_ids = _prep(entry_ids, np.uint32, "int32")
+            alloc = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=tdev)
+            u32, i32, f32, u8t = torch.int32, torch.int32, torch.float32, torch.uint8
+            sptr = torch.cuda.current_stream(tdev).cuda_stream
+        else:
+            entry_ids = None if entry_ids is None else _host(entry_ids, np.uint32)
+            alloc = lambda shape, dtype: np.empty(shape, dtype=dtype)
+            u32, i32, f32, u8t = np.uint32, np.int32, np.float32, np.uint8
+            sptr = None
+        n_entries = int(entry_ids.shape[1]) if entry_ids is not None and len(entry_ids.shape) == 2 else 0
+        res["ids"] = alloc((nq,), u32)
+        a = _SearchArgs(struct_size=C.sizeof(_SearchArgs), mode=mode, ef=ef, k=ef, mem_kind=MEM_DEVICE if dev else MEM_HOST,
+                        hash_capacity=hash_capacity, n_q=nq, queries=None if u8 else _ptr(queries), queries_low=_ptr(queries_low),
+                        entry_ids=_ptr(entry_ids), out_ids=_ptr(res["ids"]), stream=sptr, flags=flags, hops_bound=hops_bound if aux else 0,
+                        n_entries=n_entries)
+        kk = max(int(ef), 1)
+        for name, field, shape, dtype in (("hops", "out_hops", (nq,), i32), ("dist_calc", "out_dist_calc", (nq,), i32),
+                                          ("cand", "out_cand", (nq, kk), u32), ("cand_dist", "out_cand_dist", (nq, kk), f32),
+                                          ("q_low", "out_q_low", (nq, self.d_low), f32), ("edges", "out_edges", (nq,), i32)):
+            if name in want:
+                res[name] = alloc(shape, dtype)
+                setattr(a, field, _ptr(res[name]))
+        kt = max(int(top_k), 1)   # (a k the call refuses still gets buffers: the refusal is the library's)
+        res["top_ids"], res["top_dist"] = alloc((nq, kt), u32), alloc((nq, kt), f32)
+        res["allowed"], res["route"] = alloc((nq,), u32), alloc((nq,), u8t)
+        _check(self._lib.gbnns_search_tagged_auto(self._h, C.byref(a), _ptr(queries) if u8 else None, _ptr(query_tags), int(top_k), int(scan_below),
+                                                  _ptr(res["top_ids"]), _ptr(res["top_dist"]), _ptr(res["allowed"]), _ptr(res["route"])))
+        self._in_flight.clear()
+        self._last = (queries, queries_low, entry_ids, query_tags, res)
+        return res
 
     # -- profiling -----------------------------------------------------------------------------
     def profile_enable(self, on=True):

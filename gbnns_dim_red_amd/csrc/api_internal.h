@@ -4,6 +4,7 @@
 //                   the diagnostic knobs, error text
 //   graph_api.cpp   graph preparation: gbnns_exact_knn (heaps / matrix-core filter / pools), gbnns_exact_knn_bytes (uint8 rows), their tagged forms and gbnns_index_exact_knn, gbnns_build_graph_gd_device
 //   lanes.cpp       gbnns_search_ex and the batches-in-flight machinery (lanes, fork / join events), gbnns_index_wait / _join
+//                   gbnns_index_tag_census and gbnns_search_tagged_auto (the census and the routing kernels: tag_census.hip)
 //   search_core.cpp one batch on one lane: workspaces, copies, the kernel sequence
 //   sizing.cpp      the visited-set sizing rule of the first pass (capacity, form, wavefronts per CU)
 //   walk_plan.cpp   which walk kernel instance serves a pass over a shape, and its LDS layout (walk_plan.h; no HIP calls)
@@ -134,6 +135,8 @@ struct Lane {
     DevBuf top_ids, top_dist;          // the k-answer rows of a HOST call (gbnns_rerank_topk / gbnns_search_topk)
     DevBuf qtags;                      // the query tag words of a HOST call (gbnns_search_tagged)
     DevBuf q_in_b;                     // the byte queries of a HOST call (gbnns_search_byte_queries; their widening goes to q_in)
+    DevBuf census_ws;                  // gbnns_index_tag_census: the dedupe table, the per-word counters and lists (and a HOST call's arrays)
+    DevBuf auto_ws, auto_scan;         // gbnns_search_tagged_auto: census results, walk words, entries, scan list / the scan's gathered queries and rows
     // visited-set sizing feedback: stats of an earlier call arrive asynchronously in pinned memory
     uint32_t* h_stats = nullptr;       // [4] copy of ctrl after the walk kernels
     hipEvent_t stats_ev = nullptr;
@@ -152,7 +155,8 @@ struct Lane {
     int stage_next = 0;
     DevBuf* bufs(int i) {
         DevBuf* b[] = {&q_in, &q_low, &h1, &h2, &cand, &cand_dist, &cnt, &hops, &dc, &edges, &out, &entries,
-                       &ovf_list, &ovf2_list, &ctrl, &g_bitmap, &g_keys, &fp_bitmap, &order, &order_hist, &top_ids, &top_dist, &qtags, &q_in_b};
+                       &ovf_list, &ovf2_list, &ctrl, &g_bitmap, &g_keys, &fp_bitmap, &order, &order_hist, &top_ids, &top_dist, &qtags, &q_in_b,
+                       &census_ws, &auto_ws, &auto_scan};
         return i < (int)(sizeof b / sizeof b[0]) ? b[i] : nullptr;
     }
 };
@@ -292,6 +296,14 @@ struct TagIn {
 // tag == nullptr: untagged; q_u8 != nullptr: the queries as bytes, a->queries is nullptr)
 int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk, const TagIn* tag = nullptr, const uint8_t* q_u8 = nullptr);
 
+// lanes.cpp: search_call's refusals, in its order, before anything touches a device; *empty: a valid call without queries, nothing to do
+int search_check(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk, const TagIn* tag, const uint8_t* q_u8, bool* empty);
+
+// graph_api.cpp: gbnns_index_exact_knn's computation (self_offset -1) for a caller that has entered the stream itself: DEVICE buffers,
+// exactly one of queries / queries_u8 (the handle's kind); returns behind a synchronisation of `s`
+int knn_scan_resident(gbnns_index* ix, const float* queries, const uint8_t* queries_u8, uint64_t n_q, const uint32_t* query_tags, int k,
+                      uint32_t* out_ids, float* out_dist, hipStream_t s);
+
 // search_core.cpp
 int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_t s, bool sync_host, const TopkOut* topk = nullptr,
                 const TagIn* tag = nullptr, const uint8_t* q_u8 = nullptr);
@@ -343,3 +355,16 @@ T* pinned_alias(const T* host_ptr, size_t bytes) {
 }
 
 }  // namespace gbnns_api
+
+// tag_census.hip: the census of a tag table and the routing kernels of gbnns_search_tagged_auto (documented there)
+namespace gbnns {
+size_t tag_census_ws_bytes(uint64_t nq);
+hipError_t launch_tag_census(const uint32_t* tags, uint64_t n, const uint32_t* qtags, uint32_t nq, void* ws, uint32_t* out_allowed,
+                             uint32_t* out_first, hipStream_t s);
+hipError_t launch_tag_route(const uint32_t* allowed, const uint32_t* first, const uint32_t* qtags, uint32_t nq, uint64_t scan_below, uint32_t* walk_tags,
+                            uint32_t* entries, uint32_t* out_allowed, uint8_t* out_route, hipStream_t s);
+hipError_t launch_tag_gather(const void* queries, int bytes, uint32_t d, const uint32_t* qtags, const uint32_t* list, uint32_t m, void* dst,
+                             uint32_t* dst_tags, hipStream_t s);
+hipError_t launch_tag_scatter(const uint32_t* ids, const float* dist, const uint32_t* list, uint32_t m, uint32_t k, uint32_t* top_ids, float* top_dist,
+                              uint32_t* out_ids, hipStream_t s);
+}  // namespace gbnns

@@ -434,14 +434,22 @@ KnnCall<T> knn_free_call(int device, const T* base, uint64_t n, const T* queries
     return c;
 }
 
+// A request over a handle's resident table (float or byte), read in place at its device row stride; the row tags are the handle's.
+template <class T>
+KnnCall<T> knn_resident_call(gbnns_index* ix, const T* table, const T* queries, uint64_t n_q, const uint32_t* query_tags, int k, int64_t self_offset,
+                             uint32_t* out_ids, float* out_dist, int mem_kind, void* stream) {
+    KnnCall<T> c = knn_free_call(ix->device, table, ix->n, queries, n_q, ix->d, k, ix->metric, self_offset, query_tags != nullptr,
+                                 ix->tags.as<uint32_t>(), query_tags, out_ids, out_dist, mem_kind, stream);
+    c.bstride = ix->d_pad; c.resident = true;
+    return c;
+}
+
 // gbnns_index_exact_knn behind its own refusals: `table` is the handle's float or byte table, read in place at its device row stride.
 template <class T>
 int knn_index_call(gbnns_index* ix, const T* table, const T* queries, uint64_t n_q, const uint32_t* query_tags, int k, int64_t self_offset,
                    uint32_t* out_ids, float* out_dist, int mem_kind, void* stream) {
     if (!table) return fail(GBNNS_ERR_INVALID, "gbnns_index_exact_knn: the handle has no original-space table");
-    KnnCall<T> c = knn_free_call(ix->device, table, ix->n, queries, n_q, ix->d, k, ix->metric, self_offset, query_tags != nullptr,
-                                 ix->tags.as<uint32_t>(), query_tags, out_ids, out_dist, mem_kind, stream);
-    c.bstride = ix->d_pad; c.resident = true;
+    const KnnCall<T> c = knn_resident_call(ix, table, queries, n_q, query_tags, k, self_offset, out_ids, out_dist, mem_kind, stream);
     // (enter_stream: the deferred calls still owed are joined, as by any call without GBNNS_FLAG_DEFER_JOIN, and `stream` waits for the
     // handle's work in flight on another stream -- a gbnns_index_set_tags among it)
     HIP_TRY(hipSetDevice(ix->device));
@@ -452,6 +460,14 @@ int knn_index_call(gbnns_index* ix, const T* table, const T* queries, uint64_t n
     return rc;
 }
 }  // namespace
+
+namespace gbnns_api {
+int knn_scan_resident(gbnns_index* ix, const float* queries, const uint8_t* queries_u8, uint64_t n_q, const uint32_t* query_tags, int k,
+                      uint32_t* out_ids, float* out_dist, hipStream_t s) {
+    if (queries) return knn_call(knn_resident_call(ix, ix->db, queries, n_q, query_tags, k, -1, out_ids, out_dist, GBNNS_MEM_DEVICE, s));
+    return knn_call(knn_resident_call(ix, ix->db_b, queries_u8, n_q, query_tags, k, -1, out_ids, out_dist, GBNNS_MEM_DEVICE, s));
+}
+}  // namespace gbnns_api
 
 extern "C" {
 

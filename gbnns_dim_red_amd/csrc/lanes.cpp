@@ -1,5 +1,7 @@
 // lanes.cpp -- gbnns_search_ex / gbnns_search_topk and the batches-in-flight machinery: lanes (workspace + internal stream + done events), the fork /
 // join events between the caller's stream and the lanes, gbnns_index_wait / _join, gbnns_search_batch.  Cut out of api.cpp in round 5.
+// Also gbnns_index_tag_census and gbnns_search_tagged_auto (census, then per query the tagged walk or the exact scan): they run on lane 0
+// in the caller's stream like a plain search call; their kernels are tag_census.hip's.
 
 #include "api_internal.h"
 
@@ -69,8 +71,9 @@ int flush_joins(gbnns_index* ix, size_t keep) {
 
 int flush_join(gbnns_index* ix) { return flush_joins(ix, 0); }
 
-// One search call: validation, the layout over the lanes, the batch (search_core).  `topk`: gbnns_search_topk's extra outputs.
-int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk, const TagIn* tag, const uint8_t* q_u8) {
+// The refusals of a search call, in the order the tests pin, before anything touches a device (declared in api_internal.h).
+int search_check(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk, const TagIn* tag, const uint8_t* q_u8, bool* empty) {
+    *empty = false;
     if (!ix || !a) return fail(GBNNS_ERR_INVALID, "null argument");
     if (a->struct_size != sizeof(gbnns_search_args))
         return fail(GBNNS_ERR_INVALID, "gbnns_search_args.struct_size mismatch (%u != %zu)",
@@ -79,7 +82,10 @@ int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk
     if (a->ef <= 0) return fail(GBNNS_ERR_INVALID, "ef must be >= 1");
     if (a->mem_kind != GBNNS_MEM_HOST && a->mem_kind != GBNNS_MEM_DEVICE)
         return fail(GBNNS_ERR_INVALID, "unknown mem_kind %d", a->mem_kind);
-    if (a->n_q == 0) return GBNNS_OK;
+    if (a->n_q == 0) {
+        *empty = true;
+        return GBNNS_OK;
+    }
     if (a->n_q >= (1ull << 31)) return fail(GBNNS_ERR_INVALID, "n_q too large");
     if ((!a->queries && !q_u8) || !a->out_ids) return fail(GBNNS_ERR_INVALID, "queries / out_ids missing");
     if (a->mode == GBNNS_MODE_NET && !ix->has_net) return fail(GBNNS_ERR_INVALID, "NET mode needs a net");
@@ -123,6 +129,14 @@ int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk
             return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_search_topk: query + %d candidates' keys and distances need %zu bytes of LDS (limit %zu)",
                         a->ef, lds, kMaxLds);
     }
+    return GBNNS_OK;
+}
+
+// One search call: validation, the layout over the lanes, the batch (search_core).  `topk`: gbnns_search_topk's extra outputs.
+int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk, const TagIn* tag, const uint8_t* q_u8) {
+    bool empty;
+    if (int rc = search_check(ix, a, topk, tag, q_u8, &empty)) return rc;
+    if (empty) return GBNNS_OK;
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t s = static_cast<hipStream_t>(a->stream);
     int rc;
@@ -186,6 +200,107 @@ int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk
     return GBNNS_OK;
 }
 
+namespace {
+
+// gbnns_search_tagged_auto's own outputs: k-answer rows, and per query the census count and the route taken (both optional)
+struct AutoOut {
+    int k;
+    uint32_t* top_ids;
+    float* top_dist;
+    uint32_t* allowed;
+    uint8_t* route;
+};
+
+// The routed call on DEVICE buffers, the caller's stream entered: census -> the routing on the host (the scan list, ascending) -> the walk of
+// the whole batch, scan-routed queries under word 0 -> the exact scan of the listed queries, its rows scattered behind the walk.  Returns
+// when the work has finished.
+int auto_device(gbnns_index* ix, const gbnns_search_args* a, const uint8_t* q_u8, const uint32_t* qtags, uint64_t scan_below, const AutoOut& o,
+                hipStream_t s) {
+    Lane& L = ix->lanes[0];
+    const uint32_t nq = (uint32_t)a->n_q, k = (uint32_t)o.k;
+    int rc;
+    if ((rc = L.census_ws.ensure(tag_census_ws_bytes(nq)))) return rc;
+    if ((rc = L.auto_ws.ensure((size_t)nq * 20))) return rc;
+    uint32_t* const allowed = L.auto_ws.as<uint32_t>();
+    uint32_t *const first = allowed + nq, *const walk_tags = first + nq, *const entries = walk_tags + nq, *const list = entries + nq;
+    HIP_TRY(launch_tag_census(ix->tags.as<uint32_t>(), ix->n, qtags, nq, L.census_ws.p, allowed, first, s));
+    std::vector<uint32_t> h;
+    try {
+        h.resize(nq);
+    } catch (...) {
+        return fail(GBNNS_ERR_OOM, "host allocation failed");
+    }
+    if ((rc = host_copy_out(L, h.data(), allowed, (size_t)nq * 4, (size_t)nq * 4, 1, s))) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    uint32_t m = 0;
+    for (uint32_t i = 0; i < nq; ++i)
+        if ((uint64_t)h[i] <= scan_below) h[m++] = i;  // (in place: m <= i)
+    if (m && (rc = host_copy_in(L, list, h.data(), (size_t)m * 4, s))) return rc;
+    HIP_TRY(launch_tag_route(allowed, first, qtags, nq, scan_below, walk_tags, a->entry_ids ? nullptr : entries, o.allowed, o.route, s));
+    gbnns_search_args w = *a;
+    if (!a->entry_ids) w.entry_ids = entries;  // every query enters at the lowest row it may see
+    const TopkOut t{o.k, o.top_ids, o.top_dist};
+    const TagIn g{walk_tags, (a->flags & GBNNS_FLAG_TAG_BRIDGE) != 0};
+    if ((rc = search_core(ix, L, &w, s, false, &t, &g, q_u8))) return rc;
+    if (m) {
+        const size_t qbytes = ((size_t)m * ix->d * (q_u8 ? 1 : 4) + 15) & ~(size_t)15, rows = (size_t)m * k * 4;
+        if ((rc = L.auto_scan.ensure(qbytes + (size_t)m * 4 + 2 * rows))) return rc;
+        char* const gq = L.auto_scan.as<char>();
+        uint32_t* const gtags = reinterpret_cast<uint32_t*>(gq + qbytes);
+        uint32_t* const gids = gtags + m;
+        float* const gdist = o.top_dist ? reinterpret_cast<float*>(gids + (size_t)m * k) : nullptr;
+        HIP_TRY(launch_tag_gather(q_u8 ? static_cast<const void*>(q_u8) : a->queries, q_u8 ? 1 : 0, ix->d, qtags, list, m, gq, gtags, s));
+        if ((rc = knn_scan_resident(ix, q_u8 ? nullptr : reinterpret_cast<const float*>(gq), q_u8 ? reinterpret_cast<const uint8_t*>(gq) : nullptr, m,
+                                    gtags, o.k, gids, gdist, s)))
+            return rc;
+        HIP_TRY(launch_tag_scatter(gids, gdist, list, m, k, o.top_ids, o.top_dist, a->out_ids, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    ix->in_flight = false;
+    return GBNNS_OK;
+}
+
+// HOST buffers: every input uploaded, the same path, every output downloaded.
+int auto_host(gbnns_index* ix, const gbnns_search_args* a, const uint8_t* q_u8, const uint32_t* qtags, uint64_t scan_below, const AutoOut& o,
+              hipStream_t s) {
+    Lane& L = ix->lanes[0];
+    const size_t nq = (size_t)a->n_q, b4 = nq * 4, bc = b4 * (size_t)a->ef, bk = b4 * (size_t)o.k, bl = b4 * ix->d_low;
+    const bool net = a->mode == GBNNS_MODE_NET;
+    ScopedDevBuf q, qb, ql, ent, tg, ids, hops, dc, edges, cand, cdist, qlow, tids, tdist, allowed, route;
+    int rc;
+    auto up = [&](ScopedDevBuf& b, const void* src, size_t bytes) -> int {  // the device copy of an input (none: nullptr stays)
+        if (!src) return GBNNS_OK;
+        if (int r = b.ensure(bytes)) return r;
+        return host_copy_in(L, b.p, src, bytes, s);
+    };
+    auto room = [&](ScopedDevBuf& b, const void* dst, size_t bytes) -> int { return dst ? b.ensure(bytes) : GBNNS_OK; };
+    auto down = [&](const ScopedDevBuf& b, void* dst, size_t bytes) -> int { return dst ? host_copy_out(L, dst, b.p, bytes, bytes, 1, s) : GBNNS_OK; };
+    if ((rc = up(q, a->queries, nq * ix->d * 4)) || (rc = up(qb, q_u8, nq * ix->d)) || (rc = up(ql, net ? nullptr : a->queries_low, bl)) ||
+        (rc = up(ent, a->entry_ids, b4 * std::max<size_t>(a->n_entries, 1))) || (rc = up(tg, qtags, b4)))
+        return rc;
+    if ((rc = room(ids, a->out_ids, b4)) || (rc = room(hops, a->out_hops, b4)) || (rc = room(dc, a->out_dist_calc, b4)) ||
+        (rc = room(edges, a->out_edges, b4)) || (rc = room(cand, a->out_cand, bc)) || (rc = room(cdist, a->out_cand_dist, bc)) ||
+        (rc = room(qlow, net ? a->out_q_low : nullptr, bl)) || (rc = room(tids, o.top_ids, bk)) || (rc = room(tdist, o.top_dist, bk)) ||
+        (rc = room(allowed, o.allowed, b4)) || (rc = room(route, o.route, nq)))
+        return rc;
+    gbnns_search_args w = *a;
+    w.mem_kind = GBNNS_MEM_DEVICE;
+    w.queries = q.as<float>(); w.queries_low = ql.as<float>(); w.entry_ids = ent.as<uint32_t>();
+    w.out_ids = ids.as<uint32_t>(); w.out_hops = hops.as<int32_t>(); w.out_dist_calc = dc.as<int32_t>(); w.out_edges = edges.as<int32_t>();
+    w.out_cand = cand.as<uint32_t>(); w.out_cand_dist = cdist.as<float>(); w.out_q_low = qlow.as<float>();
+    const AutoOut od{o.k, tids.as<uint32_t>(), tdist.as<float>(), allowed.as<uint32_t>(), route.as<uint8_t>()};
+    if ((rc = auto_device(ix, &w, qb.as<uint8_t>(), tg.as<uint32_t>(), scan_below, od, s))) return rc;
+    if ((rc = down(ids, a->out_ids, b4)) || (rc = down(hops, a->out_hops, b4)) || (rc = down(dc, a->out_dist_calc, b4)) ||
+        (rc = down(edges, a->out_edges, b4)) || (rc = down(cand, a->out_cand, bc)) || (rc = down(cdist, a->out_cand_dist, bc)) ||
+        (rc = down(qlow, net ? a->out_q_low : nullptr, bl)) || (rc = down(tids, o.top_ids, bk)) || (rc = down(tdist, o.top_dist, bk)) ||
+        (rc = down(allowed, o.allowed, b4)) || (rc = down(route, o.route, nq)))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    return GBNNS_OK;
+}
+
+}  // namespace
+
 }  // namespace gbnns_api
 
 extern "C" {
@@ -218,6 +333,81 @@ int gbnns_search_byte_queries(gbnns_index* ix, const gbnns_search_args* a, const
     if (k == 0 && !out_top_ids && !out_top_dist) return search_call(ix, a, nullptr, gp, queries_u8);
     const TopkOut t{k, out_top_ids, out_top_dist};
     return search_call(ix, a, &t, gp, queries_u8);
+}
+
+int gbnns_index_tag_census(gbnns_index* ix, const uint32_t* query_tags, uint64_t n_q, uint32_t* out_allowed, uint32_t* out_first, int mem_kind,
+                           void* stream) {
+    if (!ix) return fail(GBNNS_ERR_INVALID, "null argument");
+    if (!out_allowed && !out_first) return fail(GBNNS_ERR_INVALID, "gbnns_index_tag_census: out_allowed and out_first are both NULL");
+    if (mem_kind != GBNNS_MEM_HOST && mem_kind != GBNNS_MEM_DEVICE) return fail(GBNNS_ERR_INVALID, "unknown mem_kind %d", mem_kind);
+    if (!ix->tags.p) return fail(GBNNS_ERR_INVALID, "gbnns_index_tag_census without gbnns_index_set_tags");
+    if (!query_tags && n_q) return fail(GBNNS_ERR_INVALID, "gbnns_index_tag_census: query_tags missing");
+    if (n_q >= (1ull << 31)) return fail(GBNNS_ERR_INVALID, "n_q too large");
+    if (n_q == 0) return GBNNS_OK;
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc;
+    if ((rc = enter_stream(ix, s))) return rc;
+    Lane& L = ix->lanes[0];
+    const uint32_t nq = (uint32_t)n_q;
+    const bool host = mem_kind == GBNNS_MEM_HOST;
+    const size_t ws = (tag_census_ws_bytes(nq) + 15) & ~(size_t)15, b4 = (size_t)nq * 4;
+    if ((rc = L.census_ws.ensure(ws + (host ? 3 * b4 : 0)))) return rc;
+    uint32_t* const stage = reinterpret_cast<uint32_t*>(L.census_ws.as<char>() + ws);  // HOST buffers: the words, and the two results
+    const uint32_t* q_dev = query_tags;
+    uint32_t *a_dev = out_allowed, *f_dev = out_first;
+    if (host) {
+        if ((rc = host_copy_in(L, stage, query_tags, b4, s))) return rc;
+        q_dev = stage;
+        a_dev = out_allowed ? stage + nq : nullptr;
+        f_dev = out_first ? stage + 2 * (size_t)nq : nullptr;
+    }
+    HIP_TRY(launch_tag_census(ix->tags.as<uint32_t>(), ix->n, q_dev, nq, L.census_ws.p, a_dev, f_dev, s));
+    if (host) {
+        if (out_allowed && (rc = host_copy_out(L, out_allowed, a_dev, b4, b4, 1, s))) return rc;
+        if (out_first && (rc = host_copy_out(L, out_first, f_dev, b4, b4, 1, s))) return rc;
+        HIP_TRY(hipStreamSynchronize(s));
+        ix->in_flight = false;
+    }
+    return GBNNS_OK;
+}
+
+int gbnns_search_tagged_auto(gbnns_index* ix, const gbnns_search_args* a, const uint8_t* queries_u8, const uint32_t* query_tags, int k, uint64_t scan_below,
+                             uint32_t* out_top_ids, float* out_top_dist, uint32_t* out_allowed, uint8_t* out_route) {
+    // Every refusal before any work, none depending on the data: this call's own, then search_call's for the tagged top-k walk, then the scan's.
+    if (!ix || !a) return fail(GBNNS_ERR_INVALID, "null argument");
+    if (a->struct_size != sizeof(gbnns_search_args))
+        return fail(GBNNS_ERR_INVALID, "gbnns_search_args.struct_size mismatch (%u != %zu)", a->struct_size, sizeof(gbnns_search_args));
+    if (a->mode == GBNNS_MODE_PLAIN)
+        return fail(GBNNS_ERR_INVALID, "gbnns_search_tagged_auto: NET / LOWQ only (a PLAIN walk's out_cand / out_cand_dist are the answer in the walked space)");
+    if (a->flags & GBNNS_FLAG_DEFER_JOIN)
+        return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_search_tagged_auto: GBNNS_FLAG_DEFER_JOIN is not served (the call reads the census on the host)");
+    if (ix->db_b) {
+        if (a->queries && queries_u8) return fail(GBNNS_ERR_INVALID, "gbnns_search_tagged_auto: args->queries must be NULL beside queries_u8");
+        if (a->queries)
+            return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_search_tagged_auto: float queries on a byte handle: there is no mixed-pair scan (uint8 rows against "
+                        "float queries); pass queries_u8");
+        if (ix->d > 256)
+            return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_search_tagged_auto: d <= 256 on a byte handle (the byte scan's limit; got %u)", ix->d);
+    } else {
+        if (queries_u8) return fail(GBNNS_ERR_INVALID, "gbnns_search_tagged_auto: queries_u8 needs a byte handle (gbnns_index_create_bytes)");
+        if (ix->d > 8192) return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_search_tagged_auto: d <= 8192 (the scan's limit; got %u)", ix->d);
+    }
+    if (ix->metric == GBNNS_METRIC_NEG_DOT && ix->d % 8 != 0)
+        return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_search_tagged_auto: the scan's negative-dot form needs d %% 8 == 0 (got %u)", ix->d);
+    if (k < 1 || k > std::min(a->ef, 4096))
+        return fail(GBNNS_ERR_INVALID, "gbnns_search_tagged_auto: k = %d outside 1 .. min(ef = %d, 4096)", k, a->ef);
+    const TopkOut t{k, out_top_ids, out_top_dist};
+    const TagIn g{query_tags, (a->flags & GBNNS_FLAG_TAG_BRIDGE) != 0};
+    bool empty;
+    if (int rc = search_check(ix, a, &t, &g, queries_u8, &empty)) return rc;
+    if (empty) return GBNNS_OK;
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t s = static_cast<hipStream_t>(a->stream);
+    if (int rc = enter_stream(ix, s)) return rc;
+    const AutoOut o{k, out_top_ids, out_top_dist, out_allowed, out_route};
+    if (a->mem_kind == GBNNS_MEM_HOST) return auto_host(ix, a, queries_u8, query_tags, scan_below, o, s);
+    return auto_device(ix, a, queries_u8, query_tags, scan_below, o, s);
 }
 
 int gbnns_index_wait(gbnns_index* ix, uint32_t keep) {

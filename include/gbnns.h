@@ -644,6 +644,43 @@ int gbnns_exact_knn_bytes_tagged(int device, const uint8_t* base, uint64_t n, co
 int gbnns_index_exact_knn(gbnns_index* index, const float* queries, const uint8_t* queries_u8, uint64_t n_q, const uint32_t* query_tags,
                           int k, int64_t self_offset, uint32_t* out_ids, float* out_dist, int mem_kind, void* stream);
 
+/* The census of the tag table T of gbnns_index_set_tags, exact: for every query word Q[i] of query_tags [n_q]
+ *     out_allowed[i] = |{ j : (T[j] & Q[i]) != 0 }|      out_first[i] = the lowest such j, 0xFFFFFFFF when there is none.
+ * Both outputs are [n_q] buffers of mem_kind; either may be NULL, not both.  GBNNS_ERR_INVALID without a tag table, on NULL query_tags with
+ * n_q > 0 and for n_q >= 2^31; n_q == 0 returns GBNNS_OK and does nothing.  With DEVICE buffers the work is enqueued on `stream` under the
+ * stream rule of gbnns_index_exact_knn (ordered after a gbnns_index_set_tags on that stream; the deferred calls still owed are joined) and
+ * the call does not synchronise; with HOST buffers it is synchronous.  Nothing is cached across calls: gbnns_index_set_tags may change
+ * the table at any time.  The device work is n x U for the U DISTINCT words of the batch, not n x n_q (tag_census.hip: the words are
+ * deduplicated on the device, then every workgroup runs the U words over a tile of the table held in registers).  Workspace on the handle:
+ * 44 .. 76 bytes per query. */
+int gbnns_index_tag_census(gbnns_index* index, const uint32_t* query_tags, uint64_t n_q, uint32_t* out_allowed, uint32_t* out_first,
+                           int mem_kind, void* stream);
+
+/* Tagged search that routes itself: the census above, then per query the exact scan (gbnns_index_exact_knn with query_tags) or the tagged
+ * walk (gbnns_search_tagged, or on a byte handle gbnns_search_byte_queries with query_tags), entered at an allowed row.
+ *   - Routing rule: query i takes the scan when allowed[i] <= scan_below, boundary included -- a query that may see nothing has count 0
+ *     and always scans; otherwise it takes the walk.  scan_below has no default: 0 sends only the empty queries to the scan, UINT64_MAX
+ *     every query.  out_allowed [n_q] (the census count) and out_route [n_q] (0 = walk, 1 = scan) are optional.
+ *   - A scan-routed query: row i of out_top_ids / out_top_dist ([n_q x k]; dist optional) is row i of gbnns_index_exact_knn(index, ...,
+ *     query_tags, k, self_offset = -1) -- ascending (distance, id), padded with 0xFFFFFFFF / +inf --, args->out_ids[i] is column 0 of that
+ *     row, and the walk-only outputs of `args` hold the bad-entry row of a tagged call: out_cand all 0xFFFFFFFF, out_cand_dist +inf, hops,
+ *     dist_calc and edges 0.
+ *   - A walk-routed query: every output is that query's row of gbnns_search_tagged(index, args', query_tags, k, ...), args' = args except
+ *     for the entry points: with args->entry_ids == NULL query i enters at first[i], the lowest row it may see, so no walk-routed query has
+ *     a disallowed entry; entry_ids given are used as they are, under the rules of a tagged call.  GBNNS_FLAG_TAG_BRIDGE keeps its meaning.
+ *   - out_q_low (NET mode) is every query's projection, whichever its route.
+ * Queries are independent in both calls, so every row of this call is bit for bit a row of one of the two; nothing new is defined about
+ * arithmetic.  A float handle takes args->queries (queries_u8 there: GBNNS_ERR_INVALID); a byte handle takes queries_u8 with args->queries
+ * NULL (float queries there: GBNNS_ERR_UNSUPPORTED, there is no mixed-pair scan).  In LOWQ mode queries_low serves the walk, the
+ * original-space queries the scan and the re-rank.
+ * Refused before any work, whatever the data -- everything either route would refuse: PLAIN mode, k outside 1 .. min(ef, 4096), no tag
+ * table, NULL query_tags / out_top_ids: GBNNS_ERR_INVALID; GBNNS_FLAG_HALF_ROWS / GBNNS_FLAG_MFMA_PROJECTION, d > 256 on a byte handle, the
+ * negative dot with d % 8 != 0, gbnns_search_topk's LDS limit, and GBNNS_FLAG_DEFER_JOIN (the call reads the census on the host):
+ * GBNNS_ERR_UNSUPPORTED.  HOST buffers are uploaded, served by the same path and downloaded.  The call returns when its work has finished,
+ * as gbnns_index_exact_knn does; there is no gbnns_multi_* form, and gbnns_profile sees the walk only. */
+int gbnns_search_tagged_auto(gbnns_index* index, const gbnns_search_args* args, const uint8_t* queries_u8, const uint32_t* query_tags, int k,
+                             uint64_t scan_below, uint32_t* out_top_ids, float* out_top_dist, uint32_t* out_allowed, uint8_t* out_route);
+
 /* ---- several devices of one node: query-sharded replicas ----------------------------------------------------
  * The reference's only parallelism on this path is `#pragma omp parallel for` over the queries of a batch
  * (search_function.h:152; the loop body :348-385 is pure per query).  Here that loop is cut into contiguous blocks,
