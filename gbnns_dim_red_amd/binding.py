@@ -44,6 +44,7 @@ SYMBOLS = [
     "gbnns_search_byte_queries", "gbnns_debug_byte_query_plan",
     "gbnns_exact_knn_tagged", "gbnns_exact_knn_bytes_tagged", "gbnns_index_exact_knn",
     "gbnns_index_tag_census", "gbnns_search_tagged_auto",
+    "gbnns_debug_knn_plan", "gbnns_debug_census_slot",
 ]
 
 
@@ -161,6 +162,9 @@ def load_library():
     lib.gbnns_debug_knn_bytes_plan.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
     lib.gbnns_debug_knn_slab.argtypes = [C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_uint32)]
+    lib.gbnns_debug_knn_plan.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_char_p, C.c_uint32,
+                                         C.POINTER(C.c_int)]
+    lib.gbnns_debug_census_slot.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.gbnns_multi_last_error.restype = C.c_char_p
     lib.gbnns_multi_create.argtypes = [C.POINTER(_IndexDesc), C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
     lib.gbnns_multi_destroy.argtypes = [C.c_void_p]
@@ -359,6 +363,24 @@ def knn_slab(n_q, k, bytes=False):
     slab = C.c_uint32(0)
     _check(load_library().gbnns_debug_knn_slab(int(bool(bytes)), n_q, k, C.byref(slab)))
     return int(slab.value)
+
+
+def knn_plan(bytes, metric, n, n_q, d, k, tagged=False):
+    """gbnns_debug_knn_plan (no device needed): (name, pool) -- the kernel that sweeps the rows of an exact_knn call of that shape under the
+    current knn_filter / knn_pool_min_k knobs ("knn_filter_kernel<...>", "knn_scan_kernel<...>", "knn_scan_wide_kernel<...>"; bytes=True:
+    "knn_bytes_sweep_kernel<...>"), taken from the table the launch reads, and whether the lists are pools (True) or heaps."""
+    name = C.create_string_buffer(128)
+    pool = C.c_int(0)
+    _check(load_library().gbnns_debug_knn_plan(int(bool(bytes)), metric, n, n_q, d, k, int(bool(tagged)), name, 128, C.byref(pool)))
+    return name.value.decode(), bool(pool.value)
+
+
+def census_slot(word, n_q):
+    """gbnns_debug_census_slot (no device needed): (slot, cap) -- the slot a query word's probe sequence starts at in the dedupe table of a
+    tag census over n_q queries, and the table's slots (a power of two >= 2 n_q)."""
+    slot, cap = C.c_uint32(0), C.c_uint32(0)
+    _check(load_library().gbnns_debug_census_slot(int(word) & 0xFFFFFFFF, n_q, C.byref(slot), C.byref(cap)))
+    return int(slot.value), int(cap.value)
 
 
 def _is_u8(x):

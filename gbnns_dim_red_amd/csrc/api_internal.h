@@ -237,6 +237,7 @@ namespace gbnns_api {
 
 // handle.cpp
 int h2d_staged(void* dst, const void* src, size_t bytes);
+int d2h_staged(void* dst, const void* src_dev, size_t bytes, hipStream_t s);   // (waits for s; returns with the bytes in dst)
 // Copies between a caller's HOST buffer and device memory for the per-call entry points (gbnns_search_ex, gbnns_project,
 // gbnns_rerank), enqueued on `s`.  Page-locked caller memory is handed to the runtime as it is (asynchronous, as before); pageable
 // memory passes through the lane's own page-locked staging buffer in pieces, for the reason given at h2d_staged -- host_copy_out
@@ -359,6 +360,7 @@ T* pinned_alias(const T* host_ptr, size_t bytes) {
 // tag_census.hip: the census of a tag table and the routing kernels of gbnns_search_tagged_auto (documented there)
 namespace gbnns {
 size_t tag_census_ws_bytes(uint64_t nq);
+uint64_t tag_census_home_slot(uint32_t word, uint64_t nq, uint64_t* cap);
 hipError_t launch_tag_census(const uint32_t* tags, uint64_t n, const uint32_t* qtags, uint32_t nq, void* ws, uint32_t* out_allowed,
                              uint32_t* out_first, hipStream_t s);
 hipError_t launch_tag_route(const uint32_t* allowed, const uint32_t* first, const uint32_t* qtags, uint32_t nq, uint64_t scan_below, uint32_t* walk_tags,

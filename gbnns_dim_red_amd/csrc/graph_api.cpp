@@ -1,6 +1,6 @@
 // graph_api.cpp -- graph preparation entry points of the C ABI (include/gbnns.h): gbnns_exact_knn (getTruth, support_func.h:270-290,
 // generalised to k results: heaps, the matrix-core filter, long lists as pools), gbnns_exact_knn_bytes (the same lists over uint8 rows,
-// their distances from the int8 matrix cores: knn_bytes.hip) with gbnns_debug_knn_bytes_plan, their tagged forms gbnns_exact_knn_tagged /
+// their distances from the int8 matrix cores: knn_bytes.hip) with gbnns_debug_knn_bytes_plan / gbnns_debug_knn_plan, their tagged forms gbnns_exact_knn_tagged /
 // gbnns_exact_knn_bytes_tagged and gbnns_index_exact_knn over a handle's resident table, and gbnns_build_graph_gd_device (hnswlikeGD,
 // support_func.h:521-575, pruning on the device).  Every kNN entry point fills a KnnCall<T> and ends in knn_call (one body for float rows,
 // one for byte rows).  What the two bodies share exists once: knn_check (the refusals), KnnStaged (HOST buffers and the
@@ -82,11 +82,16 @@ int knn_stage_tags(const KnnCall<T>& c, DevBuf& tag_dev, DevBuf& qtag_dev, const
     if ((rc = tag_dev.ensure(((size_t)c.n + 64) * 4))) return rc;
     HIP_TRY(hipMemsetAsync(tag_dev.as<uint32_t>() + c.n, 0, 64 * 4, s));
     const bool host = c.mem_kind == GBNNS_MEM_HOST;
-    HIP_TRY(hipMemcpyAsync(tag_dev.p, c.row_tags, (size_t)c.n * 4, host && !c.resident ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+    // (a HOST array never reaches the runtime's copy calls: h2d_staged says why)
+    if (host && !c.resident) {
+        if ((rc = h2d_staged(tag_dev.p, c.row_tags, (size_t)c.n * 4))) return rc;
+    } else {
+        HIP_TRY(hipMemcpyAsync(tag_dev.p, c.row_tags, (size_t)c.n * 4, hipMemcpyDeviceToDevice, s));
+    }
     qtags = c.query_tags;
     if (host) {
         if ((rc = qtag_dev.ensure((size_t)c.n_q * 4))) return rc;
-        HIP_TRY(hipMemcpyAsync(qtag_dev.p, c.query_tags, (size_t)c.n_q * 4, hipMemcpyHostToDevice, s));
+        if ((rc = h2d_staged(qtag_dev.p, c.query_tags, (size_t)c.n_q * 4))) return rc;
         qtags = qtag_dev.as<uint32_t>();
     }
     return GBNNS_OK;
@@ -110,13 +115,13 @@ struct KnnStaged {
         if (c.mem_kind == GBNNS_MEM_HOST) {  // (byte rows are uploaded as bytes: a quarter of the float call's traffic, and no float copy anywhere)
             if (!c.resident) {
                 if ((rc = b_dev.ensure((size_t)c.n * c.d * sizeof(T)))) return rc;
-                HIP_TRY(hipMemcpyAsync(b_dev.p, c.base, (size_t)c.n * c.d * sizeof(T), hipMemcpyHostToDevice, s));
+                if ((rc = h2d_staged(b_dev.p, c.base, (size_t)c.n * c.d * sizeof(T)))) return rc;
                 base = b_dev.as<T>();
             }
             if ((rc = q_dev.ensure(nq * c.d * sizeof(T)))) return rc;
             if ((rc = ids_dev.ensure(nq * c.k * 4))) return rc;
             if (c.out_dist && (rc = dist_dev.ensure(nq * c.k * 4))) return rc;
-            HIP_TRY(hipMemcpyAsync(q_dev.p, c.queries, nq * c.d * sizeof(T), hipMemcpyHostToDevice, s));
+            if ((rc = h2d_staged(q_dev.p, c.queries, nq * c.d * sizeof(T)))) return rc;
             q = q_dev.as<T>(); ids = ids_dev.as<uint32_t>();
             dist = c.out_dist ? dist_dev.as<float>() : nullptr;
         }
@@ -129,8 +134,9 @@ struct KnnStaged {
     // The lists back to HOST buffers, and the end of the call: its temporaries are released behind this, so it waits for the work that uses them.
     int copy_back(const KnnCall<T>& c, hipStream_t s) const {
         if (c.mem_kind == GBNNS_MEM_HOST) {
-            HIP_TRY(hipMemcpyAsync(c.out_ids, ids, (size_t)c.n_q * c.k * 4, hipMemcpyDeviceToHost, s));
-            if (c.out_dist) HIP_TRY(hipMemcpyAsync(c.out_dist, dist, (size_t)c.n_q * c.k * 4, hipMemcpyDeviceToHost, s));
+            if (int rc = d2h_staged(c.out_ids, ids, (size_t)c.n_q * c.k * 4, s)) return rc;
+            if (c.out_dist)
+                if (int rc = d2h_staged(c.out_dist, dist, (size_t)c.n_q * c.k * 4, s)) return rc;
         }
         HIP_TRY(hipStreamSynchronize(s));
         return GBNNS_OK;
@@ -207,14 +213,34 @@ int knn_sweep_chunks(uint64_t n, uint64_t first_rows, uint64_t max_chunk, uint32
     return GBNNS_OK;
 }
 
+// What gbnns_exact_knn does with a shape under the current knobs (gbnns_debug_knn_plan reports it).
+struct KnnFloatPlan {
+    bool pool;    // the matrix-core filter in front of pools with a radix select (long lists)
+    bool filter;  // the matrix-core filter in front of the heaps; neither: the exact scan alone
+    uint32_t dp;  // floats of a packed row of the filter: d rounded up to its K step of 16
+};
+KnnFloatPlan knn_float_plan(uint64_t n, uint64_t nq, uint32_t d, int k, int metric) {
+    KnnFloatPlan pl{};
+    // Matrix-core filter in front of the exact distances (knn.hip): the L2 metric on rows of whole 16-byte steps, sets
+    // large enough to amortise its passes.  Same output, byte for byte (tests/test_gpu_parity.py); "knn_filter" 0 = off.
+    const int knob_filter = g_knob_knn_filter.load(std::memory_order_relaxed);  // 0 = never, 1 = by size, 2 = whenever the shape allows (tests)
+    const bool filter_shape = metric == GBNNS_METRIC_L2 && d % 4 == 0 && d <= 128 && n > (uint64_t)4 * k &&
+                              (knob_filter == 2 || (knob_filter == 1 && n >= (1u << 17) && nq >= 2048));
+    // long lists keep a query's keys as an unordered pool instead of a heap (knn.hip, knn_pool_update_kernel)
+    pl.pool = filter_shape && k >= g_knob_knn_pool_min_k.load(std::memory_order_relaxed) && k <= 4096;
+    pl.filter = filter_shape && k <= 512 && !pl.pool;
+    pl.dp = (d + 15u) & ~15u;
+    return pl;
+}
+
 // The matrix-core filter's operands and lists (knn.hip) for `nq` queries at a time: the heap-filter path's whole call, a slab of the pool path.
 struct KnnFilterWork {
     ScopedDevBuf bpack, bnorm, qpack, qnorm, rhs, cand, count, flag;
     uint32_t dp, cap;
     // the buffers, and the base set packed
-    int prepare(const KnnParams& p, uint32_t nq, uint32_t cap_, hipStream_t s) {
+    int prepare(const KnnParams& p, uint32_t nq, uint32_t dp_, uint32_t cap_, hipStream_t s) {
         int rc;
-        dp = (p.dim + 15u) & ~15u; cap = cap_;
+        dp = dp_; cap = cap_;
         if ((rc = bpack.ensure((size_t)p.n * dp * 4))) return rc;       // 2 dp bf16 per row
         if ((rc = bnorm.ensure(((size_t)p.n + 64) * 4))) return rc;  // (+inf behind the last row: the filter reads whole blocks of 32)
         if ((rc = qpack.ensure((size_t)nq * dp * 4))) return rc;
@@ -253,14 +279,8 @@ int knn_call(const KnnCall<float>& c) {
     p.base = st.base; p.q = st.q; p.out_ids = st.ids; p.out_dist = st.dist; p.row_tags = st.tags; p.query_tags = st.qtags;
     p.bstride = c.bstride; p.qstride = d; p.n = n; p.nq = nq; p.dim = d; p.k = k; p.self_offset = c.self_offset;
     p.heap_stride = ((size_t)nq + 63) & ~(size_t)63;
-    // Matrix-core filter in front of the exact distances (knn.hip): the L2 metric on rows of whole 16-byte steps, sets
-    // large enough to amortise its passes.  Same output, byte for byte (tests/test_gpu_parity.py); "knn_filter" 0 = off.
-    const int knob_filter = g_knob_knn_filter.load(std::memory_order_relaxed);  // 0 = never, 1 = by size, 2 = whenever the shape allows (tests)
-    const bool filter_shape = metric == GBNNS_METRIC_L2 && d % 4 == 0 && d <= 128 && n > (uint64_t)4 * k &&
-                              (knob_filter == 2 || (knob_filter == 1 && n >= (1u << 17) && nq >= 2048));
-    // long lists keep a query's keys as an unordered pool instead of a heap (knn.hip, knn_pool_update_kernel)
-    const bool pool_path = filter_shape && k >= g_knob_knn_pool_min_k.load(std::memory_order_relaxed) && k <= 4096;
-    const bool filter = filter_shape && k <= 512 && !pool_path;
+    const KnnFloatPlan pl = knn_float_plan(n, c.n_q, d, k, metric);
+    const bool pool_path = pl.pool, filter = pl.filter;
     if (!pool_path) {  // (the pool path keeps its keys in slabs of its own: at k = 1 000 and 10^6 queries the heaps would be 9 GB)
         if ((rc = heap.ensure(p.heap_stride * (size_t)k * 8))) return rc;
         p.heap = heap.as<uint64_t>();
@@ -276,7 +296,7 @@ int knn_call(const KnnCall<float>& c) {
         ScopedDevBuf pool, root;
         if ((rc = pool.ensure((size_t)slab * (size_t)k * 8))) return rc;
         if ((rc = root.ensure((size_t)slab * 8))) return rc;
-        if ((rc = w.prepare(p, slab, cap, s))) return rc;
+        if ((rc = w.prepare(p, slab, pl.dp, cap, s))) return rc;
         for (uint32_t q0 = 0; q0 < nq; q0 += slab) {
             const KnnSlab<float> sl = knn_slab_at(c, st, q0, slab);
             KnnPoolParams pp{};
@@ -303,7 +323,7 @@ int knn_call(const KnnCall<float>& c) {
         const uint64_t max_chunk = std::min<uint64_t>((uint64_t)g_knob_knn_chunk.load(std::memory_order_relaxed), std::max<uint64_t>(64, (n / 16 + 63) & ~(uint64_t)63));  // (small sets, tests: a sixteenth)
         const uint64_t first = std::min<uint64_t>(n, (std::max<uint64_t>(std::min<uint64_t>(max_chunk, 8192), 4ull * (uint64_t)k) + 63) & ~(uint64_t)63);
         KnnFilterWork w;
-        if ((rc = w.prepare(p, nq, cap, s))) return rc;
+        if ((rc = w.prepare(p, nq, pl.dp, cap, s))) return rc;
         HIP_TRY(launch_knn_pack(p.q, d, d, nq, w.qpack.as<uint16_t>(), w.qnorm.as<float>(), s));
         KnnParams ps = p;          // the first rows: the exact scan, heaps kept
         ps.n = first; ps.row0 = 0; ps.keep_heap = 1;
@@ -529,6 +549,33 @@ int gbnns_debug_knn_slab(int bytes, uint64_t n_q, int k, uint32_t* slab) {
     return GBNNS_OK;
 }
 
+int gbnns_debug_knn_plan(int bytes, int metric, uint64_t n, uint64_t n_q, uint32_t d, int k, int tagged, char* name, uint32_t name_bytes, int* pool) {
+    if (!name || name_bytes == 0 || !pool) return fail(GBNNS_ERR_INVALID, "gbnns_debug_knn_plan: null output");
+    if ((bytes != 0 && bytes != 1) || (metric != GBNNS_METRIC_L2 && metric != GBNNS_METRIC_NEG_DOT) || n == 0 || n >= (1ull << 32) - 1 ||
+        n_q >= (1ull << 31) || d == 0 || k < 1 || k > (1 << 20))
+        return fail(GBNNS_ERR_INVALID, "gbnns_debug_knn_plan: not a shape gbnns_exact_knn / gbnns_exact_knn_bytes takes");
+    // the plan functions of the two knn_call bodies and the tables their launches read
+    const char* kernel;
+    if (bytes) {
+        KnnCall<uint8_t> c{};
+        c.d = d; c.k = k; c.metric = metric;
+        if (int rc = knn_refuse(c)) return rc;
+        const KnnBytesPlan pl = knn_bytes_plan(n, n_q, d, k);
+        kernel = knn_bytes_sweep_kernel_name(pl.dp, tagged != 0);
+        *pool = pl.pool ? 1 : 0;
+    } else {
+        KnnCall<float> c{};
+        c.d = d; c.k = k; c.metric = metric;
+        if (int rc = knn_refuse(c)) return rc;
+        const KnnFloatPlan pl = knn_float_plan(n, n_q, d, k, metric);
+        kernel = pl.pool || pl.filter ? knn_filter_kernel_name(pl.dp, tagged != 0) : knn_scan_kernel_name(metric, d, tagged != 0);
+        *pool = pl.pool ? 1 : 0;
+    }
+    if (!kernel) return fail(GBNNS_ERR_INTERNAL, "gbnns_debug_knn_plan: no kernel instance for the plan");
+    std::snprintf(name, name_bytes, "%s", kernel);
+    return GBNNS_OK;
+}
+
 // graph_build.cpp
 extern "C" int gbnns_internal_gd_finish(const uint64_t* knn_offsets, const uint32_t* knn_nbrs, const float* ds,
                                         uint64_t n, uint32_t d, int M, int metric, int reverse, int threads,
@@ -577,8 +624,8 @@ int gbnns_build_graph_gd_device(int device, const uint64_t* knn_offsets, const u
         p.knn_off = off_dev.as<uint64_t>(); p.knn_nbr = nbr_dev.as<uint32_t>();
         p.adj = adj_dev.as<uint32_t>(); p.deg = deg_dev.as<uint32_t>();
         HIP_TRY(launch_gd_prune(p, metric, nullptr));
-        HIP_TRY(hipMemcpy(adj.data(), adj_dev.p, (size_t)n * cap * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(deg.data(), deg_dev.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        if ((rc = d2h_staged(adj.data(), adj_dev.p, (size_t)n * cap * 4, nullptr))) return rc;
+        if ((rc = d2h_staged(deg.data(), deg_dev.p, (size_t)n * 4, nullptr))) return rc;
     }
     const int rc = gbnns_internal_gd_finish(knn_offsets, knn_nbrs, ds, n, d, M, metric, reverse, threads, adj.data(),
                                             deg.data(), out_host_nodes, out_offsets, out_nbrs);

@@ -36,11 +36,16 @@ thread_local SlowLog g_slow;
 // std::vector) then has the next copy fault on the stale mapping now and then (round 4: "an illegal memory access" inside
 // the first upload of gbnns_index_create, about one full test-suite run in three; never in a short run).  One-time
 // uploads of an index do not miss the extra pass over host memory.
+namespace {
+std::mutex g_stage_mu;
+void* g_stage = nullptr;  // two halves of kStagePiece bytes, page-locked, shared by h2d_staged and d2h_staged under g_stage_mu
+constexpr size_t kStagePiece = 8u << 20;
+}  // namespace
+
 int h2d_staged(void* dst, const void* src, size_t bytes) {
-    static std::mutex mu;
-    static void* stage = nullptr;
-    constexpr size_t kPiece = 8u << 20;
-    std::lock_guard<std::mutex> lk(mu);
+    constexpr size_t kPiece = kStagePiece;
+    std::lock_guard<std::mutex> lk(g_stage_mu);
+    void*& stage = g_stage;
     if (!stage) HIP_TRY(hipHostMalloc(&stage, 2 * kPiece, hipHostMallocDefault));
     hipEvent_t ev[2] = {nullptr, nullptr};
     HIP_TRY(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming));
@@ -62,6 +67,20 @@ int h2d_staged(void* dst, const void* src, size_t bytes) {
     (void)hipEventDestroy(ev[0]);
     (void)hipEventDestroy(ev[1]);
     return rc;
+}
+
+// The way back, for the same reason: device -> a caller's (pageable) array through the staging buffer, behind the work enqueued on s.
+// Returns when the bytes are in dst.
+int d2h_staged(void* dst, const void* src_dev, size_t bytes, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(g_stage_mu);
+    if (!g_stage) HIP_TRY(hipHostMalloc(&g_stage, 2 * kStagePiece, hipHostMallocDefault));
+    for (size_t done = 0; done < bytes; done += 2 * kStagePiece) {
+        const size_t nb = std::min(2 * kStagePiece, bytes - done);
+        HIP_TRY(hipMemcpyAsync(g_stage, static_cast<const char*>(src_dev) + done, nb, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        std::memcpy(static_cast<char*>(dst) + done, g_stage, nb);
+    }
+    return GBNNS_OK;
 }
 
 // The per-call copies (declared in api_internal.h).  The caller's arrays of a long-lived process are exactly the arrays of the note

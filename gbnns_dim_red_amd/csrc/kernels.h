@@ -279,6 +279,12 @@ struct KnnParams {
     const uint32_t* query_tags; // [nq]
 };
 hipError_t launch_knn_scan(const KnnParams& p, int metric, hipStream_t s);
+// Host only, no device needed: the name, template arguments included, of the instance launch_knn_scan / launch_knn_filter /
+// launch_knn_bytes_sweep start for that shape -- taken from the table the launch itself reads (nullptr: no instance).  `tagged`: a launch
+// with row tags; dp: the packed row length (KnnFilterParams::dp, KnnBytesSweepParams::dp).
+const char* knn_scan_kernel_name(int metric, uint32_t dim, bool tagged);
+const char* knn_filter_kernel_name(uint32_t dp, bool tagged);
+const char* knn_bytes_sweep_kernel_name(uint32_t dp, bool tagged);
 
 // Matrix-core filter in front of the exact scan (knn.hip, round 4; L2 metric, d % 4 == 0, d <= 128).
 // Rows packed for v_mfma_f32_32x32x16_bf16: per row, per group of 8 dims, 8 bf16 "hi" parts then 8 bf16 "lo" parts

@@ -324,23 +324,33 @@ hipError_t launch_knn_t(const KnnParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int METRIC, bool TAG>
-hipError_t launch_knn_m(const KnnParams& p, hipStream_t s) {
-    if (p.dim <= 32) return launch_knn_t<METRIC, 8, 2, TAG>(p, s);
-    if (p.dim <= 64) return launch_knn_t<METRIC, 16, 2, TAG>(p, s);
-    if (p.dim <= 128) return launch_knn_t<METRIC, 32, 1, TAG>(p, s);
+// The scan instance of a shape: its launch and its name from one place (launch_knn_scan starts what gbnns_debug_knn_plan names).
+struct KnnScanPick {
+    hipError_t (*launch)(const KnnParams&, hipStream_t);
+    const char* name;
+};
+#define KNN_SCAN(M, S, QPT, TAG) KnnScanPick{&launch_knn_t<M, S, QPT, TAG>, "knn_scan_kernel<" #M ", " #S ", " #QPT ", " #TAG ">"}
+#define KNN_WIDE(M, R, TAG) KnnScanPick{&launch_knn_wide<M, R, TAG>, "knn_scan_wide_kernel<" #M ", " #R ", " #TAG ">"}
+// X(metric, ..., tagged) at the call's metric and tag form
+#define KNN_BY_METRIC_TAG(X, ...) \
+    (metric == 1 ? (tagged ? X(1, __VA_ARGS__, true) : X(1, __VA_ARGS__, false)) : (tagged ? X(0, __VA_ARGS__, true) : X(0, __VA_ARGS__, false)))
+KnnScanPick knn_scan_pick(int metric, uint32_t dim, bool tagged) {
+    if (dim <= 32) return KNN_BY_METRIC_TAG(KNN_SCAN, 8, 2);
+    if (dim <= 64) return KNN_BY_METRIC_TAG(KNN_SCAN, 16, 2);
+    if (dim <= 128) return KNN_BY_METRIC_TAG(KNN_SCAN, 32, 1);
     // wide rows: tiles of 16 (L2) / 8 (dot) rows with their running sums in registers; the [R][d] tile must fit the
     // 160 KB of LDS (64 d bytes at R = 16), so very wide rows take fewer rows per tile: d <= 2560 / 5120 / 8192
     // (a tagged instance's R tag words behind the tile: d = 8192 at R = 4 is 128 KB + 16 bytes)
-    const size_t row_bytes = (size_t)(((p.dim >> 2) + 7u) & ~7u) * 16;
-    const size_t room = 160 * 1024 - (TAG ? 64 : 0);
-    if constexpr (METRIC == 0) {
-        if (16 * row_bytes <= room) return launch_knn_wide<0, 16, TAG>(p, s);
-    }
-    if (8 * row_bytes <= room) return launch_knn_wide<METRIC, 8, TAG>(p, s);
-    if (4 * row_bytes <= room) return launch_knn_wide<METRIC, 4, TAG>(p, s);
-    return hipErrorInvalidValue;  // d > 10240: refused by gbnns_exact_knn (d <= 8192) before it gets here
+    const size_t row_bytes = (size_t)(((dim >> 2) + 7u) & ~7u) * 16;
+    const size_t room = 160 * 1024 - (tagged ? 64 : 0);
+    if (metric != 1 && 16 * row_bytes <= room) return tagged ? KNN_WIDE(0, 16, true) : KNN_WIDE(0, 16, false);
+    if (8 * row_bytes <= room) return KNN_BY_METRIC_TAG(KNN_WIDE, 8);
+    if (4 * row_bytes <= room) return KNN_BY_METRIC_TAG(KNN_WIDE, 4);
+    return KnnScanPick{nullptr, nullptr};  // d > 10240: refused by gbnns_exact_knn (d <= 8192) before it gets here
 }
+#undef KNN_BY_METRIC_TAG
+#undef KNN_WIDE
+#undef KNN_SCAN
 
 
 // ------------------------------------------------------------------------------------------
@@ -756,20 +766,38 @@ hipError_t launch_knn_filter_tt(const KnnFilterParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int KSTEPS, int QB>
-hipError_t launch_knn_filter_t(const KnnFilterParams& p, hipStream_t s) {
-    return p.btag ? launch_knn_filter_tt<KSTEPS, QB, true>(p, s) : launch_knn_filter_tt<KSTEPS, QB, false>(p, s);
+// The filter instance of a packed row length, launch and name from one place: K steps of 16; query blocks per wavefront by what the
+// operands leave of the register file.
+struct KnnFilterPick {
+    hipError_t (*launch)(const KnnFilterParams&, hipStream_t);
+    const char* name;
+};
+#define KNN_FILTER(K, QB)                                                                                                   \
+    (tagged ? KnnFilterPick{&launch_knn_filter_tt<K, QB, true>, "knn_filter_kernel<" #K ", " #QB ", true>"} \
+            : KnnFilterPick{&launch_knn_filter_tt<K, QB, false>, "knn_filter_kernel<" #K ", " #QB ", false>"})
+KnnFilterPick knn_filter_pick(uint32_t dp, bool tagged) {
+    switch (dp >> 4) {
+        case 1: return KNN_FILTER(1, 4);
+        case 2: return KNN_FILTER(2, 4);
+        case 3: return KNN_FILTER(3, 2);
+        case 4: return KNN_FILTER(4, 2);
+        case 5: return KNN_FILTER(5, 1);
+        case 6: return KNN_FILTER(6, 1);
+        case 7: return KNN_FILTER(7, 1);
+        case 8: return KNN_FILTER(8, 1);
+        default: return KnnFilterPick{nullptr, nullptr};
+    }
 }
+#undef KNN_FILTER
 }  // namespace
 
 hipError_t launch_knn_scan(const KnnParams& p, int metric, hipStream_t s) {
     if (p.nq == 0) return hipSuccess;
-    if (p.row_tags) {
-        if (!p.query_tags) return hipErrorInvalidValue;
-        return metric == 1 ? launch_knn_m<1, true>(p, s) : launch_knn_m<0, true>(p, s);
-    }
-    return metric == 1 ? launch_knn_m<1, false>(p, s) : launch_knn_m<0, false>(p, s);
+    if (p.row_tags && !p.query_tags) return hipErrorInvalidValue;
+    const KnnScanPick k = knn_scan_pick(metric, p.dim, p.row_tags != nullptr);
+    return k.launch ? k.launch(p, s) : hipErrorInvalidValue;
 }
+const char* knn_scan_kernel_name(int metric, uint32_t dim, bool tagged) { return knn_scan_pick(metric, dim, tagged).name; }
 
 hipError_t launch_knn_pack(const float* x, uint32_t stride, uint32_t dim, uint64_t rows, uint16_t* packed, float* norms, hipStream_t s) {
     if (rows == 0) return hipSuccess;
@@ -782,18 +810,10 @@ hipError_t launch_knn_pack(const float* x, uint32_t stride, uint32_t dim, uint64
 hipError_t launch_knn_filter(const KnnFilterParams& p, hipStream_t s) {
     if (p.nq == 0 || p.rows == 0) return hipSuccess;
     if (p.btag && !p.qtag) return hipErrorInvalidValue;
-    switch (p.dp >> 4) {  // K steps of 16; query blocks per wavefront by what the operands leave of the register file
-        case 1: return launch_knn_filter_t<1, 4>(p, s);
-        case 2: return launch_knn_filter_t<2, 4>(p, s);
-        case 3: return launch_knn_filter_t<3, 2>(p, s);
-        case 4: return launch_knn_filter_t<4, 2>(p, s);
-        case 5: return launch_knn_filter_t<5, 1>(p, s);
-        case 6: return launch_knn_filter_t<6, 1>(p, s);
-        case 7: return launch_knn_filter_t<7, 1>(p, s);
-        case 8: return launch_knn_filter_t<8, 1>(p, s);
-        default: return hipErrorInvalidValue;
-    }
+    const KnnFilterPick k = knn_filter_pick(p.dp, p.btag != nullptr);
+    return k.launch ? k.launch(p, s) : hipErrorInvalidValue;
 }
+const char* knn_filter_kernel_name(uint32_t dp, bool tagged) { return knn_filter_pick(dp, tagged).name; }
 
 hipError_t launch_knn_thresholds(const uint64_t* heap, size_t heap_stride, int k, const float* qnorm, uint32_t nq, float* rhs, hipStream_t s) {
     (void)heap_stride;

@@ -280,10 +280,30 @@ hipError_t launch_sweep_tt(const KnnBytesSweepParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int KSTEPS, int QB>
-hipError_t launch_sweep_t(const KnnBytesSweepParams& p, hipStream_t s) {
-    return p.btag ? launch_sweep_tt<KSTEPS, QB, true>(p, s) : launch_sweep_tt<KSTEPS, QB, false>(p, s);
+// The sweep instance of a packed row length, launch and name from one place: K steps of 32; query blocks per wavefront by what the
+// operands leave of the register file.
+struct KnnBytesSweepPick {
+    hipError_t (*launch)(const KnnBytesSweepParams&, hipStream_t);
+    const char* name;
+};
+#define KNN_BYTES_SWEEP(K, QB)                                                                                              \
+    (tagged ? KnnBytesSweepPick{&launch_sweep_tt<K, QB, true>, "knn_bytes_sweep_kernel<" #K ", " #QB ", true>"} \
+            : KnnBytesSweepPick{&launch_sweep_tt<K, QB, false>, "knn_bytes_sweep_kernel<" #K ", " #QB ", false>"})
+KnnBytesSweepPick knn_bytes_sweep_pick(uint32_t dp, bool tagged) {
+    if (dp % kKnnBytesKStep) return KnnBytesSweepPick{nullptr, nullptr};
+    switch (dp / kKnnBytesKStep) {
+        case 1: return KNN_BYTES_SWEEP(1, 4);
+        case 2: return KNN_BYTES_SWEEP(2, 4);
+        case 3: return KNN_BYTES_SWEEP(3, 4);
+        case 4: return KNN_BYTES_SWEEP(4, 4);
+        case 5: return KNN_BYTES_SWEEP(5, 2);
+        case 6: return KNN_BYTES_SWEEP(6, 2);
+        case 7: return KNN_BYTES_SWEEP(7, 2);
+        case 8: return KNN_BYTES_SWEEP(8, 2);
+        default: return KnnBytesSweepPick{nullptr, nullptr};
+    }
 }
+#undef KNN_BYTES_SWEEP
 }  // namespace
 
 hipError_t launch_knn_bytes_pack(const uint8_t* x, uint32_t stride, uint32_t dim, uint32_t dp, int metric, int query_side, uint64_t rows, int8_t* packed,
@@ -301,19 +321,11 @@ hipError_t launch_knn_bytes_pack(const uint8_t* x, uint32_t stride, uint32_t dim
 
 hipError_t launch_knn_bytes_sweep(const KnnBytesSweepParams& p, hipStream_t s) {
     if (p.nq == 0 || p.rows == 0) return hipSuccess;
-    if (p.dp % kKnnBytesKStep || (p.btag && !p.qtag)) return hipErrorInvalidValue;
-    switch (p.dp / kKnnBytesKStep) {  // K steps of 32; query blocks per wavefront by what the operands leave of the register file
-        case 1: return launch_sweep_t<1, 4>(p, s);
-        case 2: return launch_sweep_t<2, 4>(p, s);
-        case 3: return launch_sweep_t<3, 4>(p, s);
-        case 4: return launch_sweep_t<4, 4>(p, s);
-        case 5: return launch_sweep_t<5, 2>(p, s);
-        case 6: return launch_sweep_t<6, 2>(p, s);
-        case 7: return launch_sweep_t<7, 2>(p, s);
-        case 8: return launch_sweep_t<8, 2>(p, s);
-        default: return hipErrorInvalidValue;
-    }
+    if (p.btag && !p.qtag) return hipErrorInvalidValue;
+    const KnnBytesSweepPick k = knn_bytes_sweep_pick(p.dp, p.btag != nullptr);
+    return k.launch ? k.launch(p, s) : hipErrorInvalidValue;
 }
+const char* knn_bytes_sweep_kernel_name(uint32_t dp, bool tagged) { return knn_bytes_sweep_pick(dp, tagged).name; }
 
 hipError_t launch_knn_bytes_offer(const KnnBytesOfferParams& p, hipStream_t s) {
     if (p.nq == 0) return hipSuccess;

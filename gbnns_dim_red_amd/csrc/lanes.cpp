@@ -372,6 +372,15 @@ int gbnns_index_tag_census(gbnns_index* ix, const uint32_t* query_tags, uint64_t
     return GBNNS_OK;
 }
 
+int gbnns_debug_census_slot(uint32_t word, uint64_t n_q, uint32_t* slot, uint32_t* cap) {
+    if (!slot || !cap) return fail(GBNNS_ERR_INVALID, "gbnns_debug_census_slot: null output");
+    if (n_q == 0 || n_q > (1ull << 30)) return fail(GBNNS_ERR_INVALID, "gbnns_debug_census_slot: n_q must be in [1, 2^30] (the table's size is reported in 32 bits)");
+    uint64_t c = 0;
+    *slot = (uint32_t)tag_census_home_slot(word, n_q, &c);
+    *cap = (uint32_t)c;
+    return GBNNS_OK;
+}
+
 int gbnns_search_tagged_auto(gbnns_index* ix, const gbnns_search_args* a, const uint8_t* queries_u8, const uint32_t* query_tags, int k, uint64_t scan_below,
                              uint32_t* out_top_ids, float* out_top_dist, uint32_t* out_allowed, uint8_t* out_route) {
     // Every refusal before any work, none depending on the data: this call's own, then search_call's for the tagged top-k walk, then the scan's.

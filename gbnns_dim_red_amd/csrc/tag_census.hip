@@ -33,7 +33,7 @@ constexpr uint32_t kCensusChunk = 256;                                    // wor
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr unsigned long long kUsed = 1ull << 32;
 
-__device__ inline uint32_t census_hash(uint32_t w) {
+__host__ __device__ inline uint32_t census_hash(uint32_t w) {
     w ^= w >> 16; w *= 0x7FEB352Du; w ^= w >> 15; w *= 0x846CA68Bu; w ^= w >> 16;
     return w;
 }
@@ -199,6 +199,12 @@ unsigned blocks_for(uint64_t threads) { return (unsigned)std::min<uint64_t>((thr
 
 // Workspace of one census over n_q queries: the table, the per-slot counters, the queries' slots, the word list and U.
 size_t tag_census_ws_bytes(uint64_t nq) { return (size_t)(census_cap(nq) * 16 + nq * 12 + 16); }
+
+// Host only: the slots of the dedupe table of a census over nq queries, and the slot a word's probe sequence starts at (gbnns_debug_census_slot).
+uint64_t tag_census_home_slot(uint32_t word, uint64_t nq, uint64_t* cap) {
+    *cap = census_cap(nq);
+    return census_hash(word) & (*cap - 1);
+}
 
 // T = tags [n] (16-byte aligned), Q = qtags [nq]; out_allowed / out_first [nq] or nullptr; everything device memory; ws: tag_census_ws_bytes(nq)
 // bytes, 16-byte aligned.  Enqueued on s.

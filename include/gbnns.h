@@ -612,6 +612,19 @@ int gbnns_debug_knn_bytes_plan(uint64_t n, uint64_t n_q, uint32_t d, int k,
  * bytes = 1: gbnns_exact_knn_bytes and its tagged / handle forms (keys of 8 bytes), bytes = 0: the pool path of gbnns_exact_knn (keys of 4).
  * *slab = n_q, or a multiple of 128.  GBNNS_ERR_INVALID: k outside 1 .. 4096, n_q >= 2^31. */
 int gbnns_debug_knn_slab(int bytes, uint64_t n_q, int k, uint32_t* slab);
+/* Diagnostic, no device needed: the kernel that sweeps the rows of an exact-kNN call of that shape under the current "knn_filter" /
+ * "knn_pool_min_k" knobs, template arguments included, and whether the lists are pools (*pool = 1) or heaps (0).  bytes = 0:
+ * gbnns_exact_knn -- "knn_filter_kernel<KSTEPS, QB, TAG>" where the matrix-core filter takes the call (the first rows of its heap path,
+ * and a chunk whose lists overflowed, still go through the scan), else "knn_scan_kernel<METRIC, S, QPT, TAG>" (d <= 128) or
+ * "knn_scan_wide_kernel<METRIC, R, TAG>"; bytes = 1: gbnns_exact_knn_bytes -- "knn_bytes_sweep_kernel<KSTEPS, QB, TAG>".  tagged != 0:
+ * the _tagged call (gbnns_index_exact_knn with query_tags).  The name comes from the decision and the table the call itself launches
+ * from.  GBNNS_ERR_INVALID / GBNNS_ERR_UNSUPPORTED for a shape the call refuses. */
+int gbnns_debug_knn_plan(int bytes, int metric, uint64_t n, uint64_t n_q, uint32_t d, int k, int tagged, char* name, uint32_t name_bytes,
+                         int* pool);
+/* Diagnostic, no device needed: the dedupe table of a gbnns_index_tag_census over n_q queries has *cap slots (a power of two >= 2 n_q,
+ * at least 64) and a query word's probe sequence starts at *slot, going up by one and wrapping at *cap -- so that a test can build
+ * colliding words without restating the hash.  GBNNS_ERR_INVALID: n_q outside 1 .. 2^30. */
+int gbnns_debug_census_slot(uint32_t word, uint64_t n_q, uint32_t* slot, uint32_t* cap);
 
 /* Exact TAGGED nearest neighbours: the exact answer of a tagged query -- the ground truth of gbnns_search_tagged and of
  * GBNNS_FLAG_TAG_BRIDGE, and what a caller falls back to when a filter is selective.  Row j is allowed for query i when

@@ -80,9 +80,9 @@ def f32_dot_eight_sums(x, q):
 
 
 @contextlib.contextmanager
-def knobs(g, knn_chunk=None, knn_pool_min_k=None, knn_slab=None):
+def knobs(g, knn_chunk=None, knn_pool_min_k=None, knn_slab=None, knn_filter=None):
     """gbnns_exact_knn*'s process-wide knobs for the duration of a with-block; the defaults (32 768 rows, pools from k = 64, slabs by the
-    4 GiB rule: "knn_slab" 0) come back, also behind an exception."""
+    4 GiB rule: "knn_slab" 0; "knn_filter" 1 where the block set it) come back, also behind an exception."""
     lib = g.load_library()
     try:
         if knn_chunk is not None:
@@ -91,11 +91,15 @@ def knobs(g, knn_chunk=None, knn_pool_min_k=None, knn_slab=None):
             assert lib.gbnns_debug_knob(b"knn_pool_min_k", knn_pool_min_k) == 0
         if knn_slab is not None:
             assert lib.gbnns_debug_knob(b"knn_slab", knn_slab) == 0
+        if knn_filter is not None:
+            assert lib.gbnns_debug_knob(b"knn_filter", knn_filter) == 0
         yield
     finally:
         lib.gbnns_debug_knob(b"knn_chunk", 1 << 15)
         lib.gbnns_debug_knob(b"knn_pool_min_k", 64)
         lib.gbnns_debug_knob(b"knn_slab", 0)
+        if knn_filter is not None:
+            lib.gbnns_debug_knob(b"knn_filter", 1)
 
 
 def slabs(slab, nq):
