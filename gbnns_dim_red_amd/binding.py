@@ -25,6 +25,7 @@ FLAG_DEFER_JOIN = 128
 FLAG_MFMA_PROJECTION = 256
 FLAG_HALF_ROWS = 512
 FLAG_TAG_BRIDGE = 1024   # gbnns_search_tagged only: disallowed neighbours are looked through (bridge_graph)
+FLAG_SCAN_GATHER = 4096  # search_auto only: scan-routed queries are served by the gathered exact scan (Index.exact_knn(gather=True)); every output unchanged
 FLAG_BYTE_WALK = 2048    # MODE_PLAIN on a byte handle (Index(db=<uint8>)): walk the uint8 rows; the float handle's answers over db.astype(float32), bit for bit
 
 # every symbol include/gbnns.h declares (tests check the library exports all of them)
@@ -45,6 +46,7 @@ SYMBOLS = [
     "gbnns_exact_knn_tagged", "gbnns_exact_knn_bytes_tagged", "gbnns_index_exact_knn",
     "gbnns_index_tag_census", "gbnns_search_tagged_auto",
     "gbnns_debug_knn_plan", "gbnns_debug_census_slot",
+    "gbnns_index_exact_knn_gather", "gbnns_debug_gather_plan", "gbnns_debug_gather_schedule",
 ]
 
 
@@ -156,6 +158,10 @@ def load_library():
     lib.gbnns_exact_knn_bytes_tagged.argtypes = lib.gbnns_exact_knn_tagged.argtypes
     lib.gbnns_index_exact_knn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_int, C.c_void_p]
+    lib.gbnns_index_exact_knn_gather.argtypes = lib.gbnns_index_exact_knn.argtypes
+    lib.gbnns_debug_gather_plan.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.gbnns_debug_gather_schedule.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.gbnns_index_tag_census.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.gbnns_search_tagged_auto.argtypes = [C.c_void_p, C.POINTER(_SearchArgs), C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p]
@@ -373,6 +379,34 @@ def knn_plan(bytes, metric, n, n_q, d, k, tagged=False):
     pool = C.c_int(0)
     _check(load_library().gbnns_debug_knn_plan(int(bool(bytes)), metric, n, n_q, d, k, int(bool(tagged)), name, 128, C.byref(pool)))
     return name.value.decode(), bool(pool.value)
+
+
+def gather_plan(bytes, metric, d, k):
+    """gbnns_debug_gather_plan (no device needed): (name, W) -- the kernel that serves Index.exact_knn(gather=True) on a float (bytes=False) or
+    byte handle of that metric and dimension, "knn_gather_kernel<...>", and the queries W one of its workgroups serves; for a shape the
+    gathered kernel does not cover (d > 128, k > 4 096) the existing scan's tagged instance and W = 0: the call falls back to it."""
+    name = C.create_string_buffer(128)
+    w = C.c_uint32(0)
+    _check(load_library().gbnns_debug_gather_plan(int(bool(bytes)), metric, d, k, name, 128, C.byref(w)))
+    return name.value.decode(), int(w.value)
+
+
+GATHER_BUDGET = 1 << 26   # default of the handle knob "gather_budget": list entries a round of the gathered scan may hold
+
+
+def gather_schedule(words, allowed, n, budget=None, W=128):
+    """gbnns_debug_gather_schedule (no device needed): the schedule Index.exact_knn(gather=True) builds from the queries' tag words [nq] and
+    their census counts allowed [nq] (tag_census) over n rows -- dict(order, round_of, list_offset_of, rounds, workgroups); include/gbnns.h
+    defines each.  budget None: the call's default, max(GATHER_BUDGET, n); W: queries per workgroup (gather_plan)."""
+    words, allowed = _host(words, np.uint32).reshape(-1), _host(allowed, np.uint32).reshape(-1)
+    nq = int(words.shape[0])
+    if int(allowed.shape[0]) != nq:
+        raise ValueError("words and allowed must have the same length")
+    order, round_of, off = np.empty(nq, np.uint32), np.empty(nq, np.uint32), np.empty(nq, np.uint64)
+    rounds, wgs = C.c_uint32(0), C.c_uint32(0)
+    _check(load_library().gbnns_debug_gather_schedule(words.ctypes.data, allowed.ctypes.data, nq, n, max(GATHER_BUDGET, n) if budget is None else budget,
+                                                      W, order.ctypes.data, round_of.ctypes.data, off.ctypes.data, C.byref(rounds), C.byref(wgs)))
+    return {"order": order, "round_of": round_of, "list_offset_of": off, "rounds": int(rounds.value), "workgroups": int(wgs.value)}
 
 
 def census_slot(word, n_q):
@@ -926,12 +960,16 @@ class Index:
                                            ids.ctypes.data, _ptr(dist), MEM_HOST, None))
         return ids, dist
 
-    def exact_knn(self, queries, k, query_tags=None, self_offset=-1, want_dist=False):
+    def exact_knn(self, queries, k, query_tags=None, self_offset=-1, want_dist=False, gather=False):
         """gbnns_index_exact_knn: exact_knn(db, queries, k, metric=<the handle's>, ...) over the handle's resident table, read in place --
         nothing of the table is uploaded.  query_tags [nq]: the tagged answer over set_tags()'s table (exact_knn's row_tags / query_tags
         form, the ground truth of search(query_tags=...)); None: the untagged answer.  A float handle takes float queries (uint8 ones raise
         TypeError), a byte handle uint8 queries (float ones: GbnnsError, code 5 -- there is no mixed-pair scan).  numpy queries -> numpy
-        results; torch CUDA queries -> torch results, on the current stream.  Returns ids, or (ids, dist) with want_dist."""
+        results; torch CUDA queries -> torch results, on the current stream.  Returns ids, or (ids, dist) with want_dist.
+        gather=True: gbnns_index_exact_knn_gather -- the same bytes, computed from distances to the rows each query's word allows only (the
+        queries of a word scan that word's row list); needs query_tags (None: ValueError).  Opt-in; gather_plan() names its kernel."""
+        if gather and query_tags is None:
+            raise ValueError("exact_knn(gather=True) needs query_tags: an untagged call has nothing to gather")
         u8 = _is_u8(queries)
         if u8 and not self.is_bytes:
             raise TypeError("uint8 queries need a byte handle (Index(db=<uint8>)); widen them for a float handle")
@@ -953,8 +991,9 @@ class Index:
             ids = np.empty((nq, k), np.uint32)
             dist = np.empty((nq, k), np.float32) if want_dist else None
             sptr = None
-        _check(self._lib.gbnns_index_exact_knn(self._h, None if u8 else _ptr(queries), _ptr(queries) if u8 else None, nq, _ptr(query_tags), k,
-                                               self_offset, _ptr(ids), _ptr(dist), MEM_DEVICE if dev else MEM_HOST, sptr))
+        fn = self._lib.gbnns_index_exact_knn_gather if gather else self._lib.gbnns_index_exact_knn
+        _check(fn(self._h, None if u8 else _ptr(queries), _ptr(queries) if u8 else None, nq, _ptr(query_tags), k, self_offset, _ptr(ids), _ptr(dist),
+                  MEM_DEVICE if dev else MEM_HOST, sptr))
         return (ids, dist) if want_dist else ids
 
     def tag_census(self, query_tags):
@@ -981,7 +1020,7 @@ class Index:
         """gbnns_search_tagged_auto: a tagged search that routes itself.  The census of set_tags()'s table gives every query the number of rows
         its word allows; query i takes the exact scan (exact_knn(query_tags=...)'s row) when that number is <= scan_below -- a required
         keyword: 0 sends only the queries that may see nothing to the scan, 2**64 - 1 every query -- and else the tagged walk
-        (search(query_tags=..., top_k=...)'s row; flags=FLAG_TAG_BRIDGE: the bridged walk), entered at the lowest row it may see unless
+        (search(query_tags=..., top_k=...)'s row; flags=FLAG_TAG_BRIDGE: the bridged walk; flags=FLAG_SCAN_GATHER: the scan is exact_knn(gather=True)'s, same rows), entered at the lowest row it may see unless
         entry_ids are given.  Returns search()'s dict plus "top_ids" / "top_dist" [nq x top_k], "allowed" [nq] (the census) and "route" [nq]
         uint8 (0 = walk, 1 = scan); a scan-routed query's "ids" is top_ids[:, 0] and its walk-only outputs are the bad-entry row.  numpy
         in -> numpy out; CUDA/ROCm tensors in -> tensors out, on the current stream; either way the call returns when the work has finished.

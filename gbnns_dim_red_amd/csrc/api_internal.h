@@ -3,6 +3,7 @@
 //   handle.cpp      the index handle: creation (uploads, layouts), destruction, projection / re-rank entry points, profiling,
 //                   the diagnostic knobs, error text
 //   graph_api.cpp   graph preparation: gbnns_exact_knn (heaps / matrix-core filter / pools), gbnns_exact_knn_bytes (uint8 rows), their tagged forms and gbnns_index_exact_knn, gbnns_build_graph_gd_device
+//                   and gbnns_index_exact_knn_gather (the gathered exact scan: knn_gather.hip) with its two diagnostics
 //   lanes.cpp       gbnns_search_ex and the batches-in-flight machinery (lanes, fork / join events), gbnns_index_wait / _join
 //                   gbnns_index_tag_census and gbnns_search_tagged_auto (the census and the routing kernels: tag_census.hip)
 //   search_core.cpp one batch on one lane: workspaces, copies, the kernel sequence
@@ -166,7 +167,7 @@ struct Lane {
 // starts from, so a test or an A/B run that flips one no longer changes every other handle of the process.  The three knobs of
 // gbnns_exact_knn -- a function without a handle -- stay process-wide.
 struct Knobs {
-    int quotient, vs_disp, max_waves, spec_min_nq, spec_any_form, mlp_small, mlp_net, mlp_slab, late_rows, spec_tail, coop, hot, byte_query_int;
+    int quotient, vs_disp, max_waves, spec_min_nq, spec_any_form, mlp_small, mlp_net, mlp_slab, late_rows, spec_tail, coop, hot, byte_query_int, gather_budget, gather_timing;
 };
 Knobs knob_defaults();                                    // the process-wide defaults as they stand now
 bool knob_set(Knobs& k, const char* name, int value);     // clamps like the environment does; false = no such handle knob
@@ -231,6 +232,9 @@ struct gbnns_index {
     hipStream_t last_stream = nullptr;
     bool in_flight = false;
     hipEvent_t order_ev = nullptr;
+    // gbnns_index_exact_knn_gather with the knob "gather_timing": the last call's census / fill / scan microseconds and its rounds (gbnns_index_knob_get)
+    int gather_us[3] = {0, 0, 0};
+    int gather_rounds = 0;
 };
 
 namespace gbnns_api {
@@ -297,13 +301,18 @@ struct TagIn {
 // tag == nullptr: untagged; q_u8 != nullptr: the queries as bytes, a->queries is nullptr)
 int search_call(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk, const TagIn* tag = nullptr, const uint8_t* q_u8 = nullptr);
 
-// lanes.cpp: search_call's refusals, in its order, before anything touches a device; *empty: a valid call without queries, nothing to do
-int search_check(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk, const TagIn* tag, const uint8_t* q_u8, bool* empty);
+// lanes.cpp: search_call's refusals, in its order, before anything touches a device; *empty: a valid call without queries, nothing to do;
+// routed: the call is gbnns_search_tagged_auto, the one call GBNNS_FLAG_SCAN_GATHER belongs to
+int search_check(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk, const TagIn* tag, const uint8_t* q_u8, bool* empty, bool routed = false);
 
 // graph_api.cpp: gbnns_index_exact_knn's computation (self_offset -1) for a caller that has entered the stream itself: DEVICE buffers,
 // exactly one of queries / queries_u8 (the handle's kind); returns behind a synchronisation of `s`
 int knn_scan_resident(gbnns_index* ix, const float* queries, const uint8_t* queries_u8, uint64_t n_q, const uint32_t* query_tags, int k,
                       uint32_t* out_ids, float* out_dist, hipStream_t s);
+
+// graph_api.cpp: the same for gbnns_index_exact_knn_gather's computation (GBNNS_FLAG_SCAN_GATHER); query_tags required
+int knn_gather_resident(gbnns_index* ix, const float* queries, const uint8_t* queries_u8, uint64_t n_q, const uint32_t* query_tags, int k,
+                        uint32_t* out_ids, float* out_dist, hipStream_t s);
 
 // search_core.cpp
 int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_t s, bool sync_host, const TopkOut* topk = nullptr,

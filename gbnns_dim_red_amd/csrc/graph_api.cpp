@@ -5,7 +5,9 @@
 // support_func.h:521-575, pruning on the device).  Every kNN entry point fills a KnnCall<T> and ends in knn_call (one body for float rows,
 // one for byte rows).  What the two bodies share exists once: knn_check (the refusals), KnnStaged (HOST buffers and the
 // tag words), KnnSlab (every address that depends on the query slab) and knn_sweep_chunks (the row chunks and the answer to a key list
-// that overflowed).  Cut out of api.cpp in round 5; api_internal.h lists the other units.
+// that overflowed).  gbnns_index_exact_knn_gather (knn_gather_call: census, schedule, per round the lists' fill and the gathered scan --
+// knn_gather.hip) shares the refusals and the staging and falls back to knn_call for a shape its kernel does not cover.  Cut out of api.cpp
+// in round 5; api_internal.h lists the other units.
 
 #include "api_internal.h"
 
@@ -479,6 +481,171 @@ int knn_index_call(gbnns_index* ix, const T* table, const T* queries, uint64_t n
     if (rc == GBNNS_OK && n_q) ix->in_flight = false;  // (the call returned behind a synchronisation of its stream)
     return rc;
 }
+
+// Does the gathered scan (knn_gather.hip) cover a shape?  d <= 128 and lists the heaps take; else the call runs knn_call, the existing scan.
+bool gather_serves(int metric, uint32_t d, bool bytes, int k, const char** name, uint32_t* W) {
+    uint32_t w = 0;
+    const char* nm = knn_gather_kernel_name(metric, d, bytes, &w);
+    const bool ok = nm != nullptr && k <= 4096;
+    if (name) *name = ok ? nm : nullptr;
+    if (W) *W = ok ? w : 0;
+    return ok;
+}
+
+// The stage times of a gathered call for the handle knob "gather_timing" (tools/exact_gather_timing.py): three events around census, fill and
+// scan of a round, read at the round's end -- a diagnostic run serialises its rounds.
+struct GatherClock {
+    bool on = false;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    double ms[3] = {0, 0, 0};  // census, fill, scan
+    ~GatherClock() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    hipError_t start(bool want) {
+        on = want;
+        for (int i = 0; on && i < 3; ++i)
+            if (hipError_t e = hipEventCreate(&ev[i])) return e;
+        return hipSuccess;
+    }
+    hipError_t mark(int i, hipStream_t s) { return on ? hipEventRecord(ev[i], s) : hipSuccess; }
+    hipError_t take(int from, int stage) {  // ms[stage] += ev[from] .. ev[from + 1]
+        if (!on) return hipSuccess;
+        float t = 0;
+        if (hipError_t e = hipEventSynchronize(ev[from + 1])) return e;
+        if (hipError_t e = hipEventElapsedTime(&t, ev[from], ev[from + 1])) return e;
+        ms[stage] += t;
+        return hipSuccess;
+    }
+};
+
+// gbnns_index_exact_knn_gather behind its refusals, the stream entered: census -> allowed (and the words) to the host -> gather_schedule ->
+// per round the lists' fill and the gathered scan -> the heaps' finalize.  `table`: the handle's float or byte table, read in place.
+template <class T>
+int knn_gather_call(gbnns_index* ix, const T* table, const T* queries, uint64_t n_q, const uint32_t* query_tags, int k, int64_t self_offset,
+                    uint32_t* out_ids, float* out_dist, int mem_kind, hipStream_t s) {
+    constexpr bool bytes = sizeof(T) == 1;
+    if (!table) return fail(GBNNS_ERR_INVALID, "gbnns_index_exact_knn_gather: the handle has no original-space table");
+    const KnnCall<T> c = knn_resident_call(ix, table, queries, n_q, query_tags, k, self_offset, out_ids, out_dist, mem_kind, s);
+    int rc;
+    if ((rc = knn_check(c)) || n_q == 0) return rc;
+    uint32_t W = 0;
+    if (!gather_serves(c.metric, c.d, bytes, k, nullptr, &W)) return knn_call(c);  // a shape the gathered kernel does not cover: the same bytes from the scan
+    const uint32_t nq = (uint32_t)n_q;
+    const uint64_t n = c.n;
+    const bool host = mem_kind == GBNNS_MEM_HOST;
+    KnnCall<T> cs = c;
+    cs.tagged = false;  // (the rows' tag words are read where the handle keeps them: no padded copy)
+    KnnStaged<T> st;
+    ScopedDevBuf qtag_dev, census, meta, lists, heap;
+    if ((rc = st.stage(cs, s))) return rc;
+    GatherClock clock;
+    HIP_TRY(clock.start(ix->knob.gather_timing != 0));
+    std::vector<uint32_t> h_words, h_allowed;
+    GatherSchedule sch;
+    try {
+        h_words.resize(nq);
+        h_allowed.resize(nq);
+    } catch (...) {
+        return fail(GBNNS_ERR_OOM, "host allocation failed");
+    }
+    // 1. the census
+    const uint32_t* qtags = query_tags;
+    if (host) {
+        std::memcpy(h_words.data(), query_tags, (size_t)nq * 4);
+        if ((rc = qtag_dev.ensure((size_t)nq * 4))) return rc;
+        if ((rc = h2d_staged(qtag_dev.p, query_tags, (size_t)nq * 4))) return rc;
+        qtags = qtag_dev.as<uint32_t>();
+    }
+    const size_t cws = (tag_census_ws_bytes(nq) + 15) & ~(size_t)15;
+    if ((rc = census.ensure(cws + (size_t)nq * 4))) return rc;
+    uint32_t* const allowed_dev = reinterpret_cast<uint32_t*>(census.as<char>() + cws);
+    HIP_TRY(clock.mark(0, s));
+    HIP_TRY(launch_tag_census(ix->tags.as<uint32_t>(), n, qtags, nq, census.p, allowed_dev, nullptr, s));
+    HIP_TRY(clock.mark(1, s));
+    HIP_TRY(clock.take(0, 0));
+    if ((rc = d2h_staged(h_allowed.data(), allowed_dev, (size_t)nq * 4, s))) return rc;
+    if (!host && (rc = d2h_staged(h_words.data(), qtags, (size_t)nq * 4, s))) return rc;
+    // 2. the schedule
+    const uint64_t budget = std::max<uint64_t>((uint64_t)std::max(1, ix->knob.gather_budget), n);
+    try {
+        gather_schedule(h_words.data(), h_allowed.data(), nq, n, budget, W, sch);
+    } catch (...) {
+        return fail(GBNNS_ERR_OOM, "host allocation failed");
+    }
+    const size_t G = sch.groups.size(), NW = sch.wgs.size(), R = sch.round_entries.size();
+    // the heaps: all-ones, so that a query nobody scans for comes out as padding
+    const size_t heap_stride = ((size_t)nq + 63) & ~(size_t)63;
+    if ((rc = heap.ensure(heap_stride * (size_t)k * 8))) return rc;
+    HIP_TRY(hipMemsetAsync(heap.p, 0xFF, heap_stride * (size_t)k * 8, s));
+    if (G) {
+        // the schedule on the device: [order nq][words G][caps G][cursor G] u32, then 8-byte aligned [offs G] u64, [workgroups NW] 6 x u32
+        std::vector<uint32_t> h32;
+        std::vector<uint64_t> h_offs;
+        try {
+            h32.reserve((size_t)nq + 3 * G);
+            h32.insert(h32.end(), sch.order.begin(), sch.order.end());
+            for (const GatherGroup& g : sch.groups) h32.push_back(g.word);
+            for (const GatherGroup& g : sch.groups) h32.push_back(g.len);
+            h32.resize((size_t)nq + 3 * G, 0u);  // the cursors
+            h_offs.reserve(G);
+            for (const GatherGroup& g : sch.groups) h_offs.push_back(g.list_off);
+        } catch (...) {
+            return fail(GBNNS_ERR_OOM, "host allocation failed");
+        }
+        const size_t b32 = (h32.size() * 4 + 7) & ~(size_t)7, boffs = G * 8, bwg = NW * sizeof(GatherWorkgroup);
+        if ((rc = meta.ensure(b32 + boffs + bwg))) return rc;
+        if ((rc = h2d_staged(meta.p, h32.data(), h32.size() * 4))) return rc;
+        if ((rc = h2d_staged(meta.as<char>() + b32, h_offs.data(), boffs))) return rc;
+        if ((rc = h2d_staged(meta.as<char>() + b32 + boffs, sch.wgs.data(), bwg))) return rc;
+        const uint32_t* const order_dev = meta.as<uint32_t>();
+        const uint32_t *const words_dev = order_dev + nq, *const caps_dev = words_dev + G;
+        uint32_t* const cursor_dev = meta.as<uint32_t>() + nq + 2 * G;
+        const uint64_t* const offs_dev = reinterpret_cast<const uint64_t*>(meta.as<char>() + b32);
+        const GatherWorkgroup* const wgs_dev = reinterpret_cast<const GatherWorkgroup*>(meta.as<char>() + b32 + boffs);
+        uint64_t most = 0;
+        for (uint64_t e : sch.round_entries) most = std::max(most, e);
+        if ((rc = lists.ensure((size_t)most * 4))) return rc;
+        // 3. / 4. round by round: the lists, then their scans (one list buffer: a round's fill runs behind the scans of the round before)
+        for (size_t r = 0; r < R; ++r) {
+            const uint32_t g0 = sch.round_group0[r], g1 = sch.round_group0[r + 1], w0 = sch.round_wg0[r], w1 = sch.round_wg0[r + 1];
+            GatherFillParams f{};
+            f.tags = ix->tags.as<uint32_t>(); f.n = n; f.words = words_dev + g0; f.caps = caps_dev + g0; f.offs = offs_dev + g0;
+            f.groups = g1 - g0; f.cursor = cursor_dev + g0; f.list = lists.as<uint32_t>();
+            KnnGatherParams p{};
+            if constexpr (bytes) { p.base_b = st.base; p.q_b = st.q; }
+            else { p.base = st.base; p.q = st.q; }
+            p.bstride = c.bstride; p.qstride = c.d; p.dim = c.d; p.k = k; p.self_offset = self_offset;
+            p.heap = heap.as<uint64_t>(); p.heap_stride = heap_stride; p.order = order_dev;
+            p.wgs = wgs_dev + w0; p.n_wgs = w1 - w0; p.list = lists.as<uint32_t>();
+            HIP_TRY(clock.mark(0, s));
+            HIP_TRY(launch_gather_fill(f, s));
+            HIP_TRY(clock.mark(1, s));
+            HIP_TRY(launch_knn_gather(p, c.metric, s));
+            HIP_TRY(clock.mark(2, s));
+            HIP_TRY(clock.take(0, 1));
+            HIP_TRY(clock.take(1, 2));
+        }
+    }
+    KnnParams kp{};
+    kp.nq = nq; kp.k = k; kp.heap = heap.as<uint64_t>(); kp.heap_stride = heap_stride; kp.out_ids = st.ids; kp.out_dist = st.dist;
+    HIP_TRY(launch_knn_finalize(kp, s));
+    if ((rc = st.copy_back(c, s))) return rc;
+    if (clock.on) {
+        for (int i = 0; i < 3; ++i) ix->gather_us[i] = (int)std::min(clock.ms[i] * 1000.0 + 0.5, 2e9);
+        ix->gather_rounds = (int)R;
+    }
+    return GBNNS_OK;
+}
+
+// gbnns_index_exact_knn's refusals, which are this call's too, in its order
+int knn_index_refuse(const char* fn, gbnns_index* ix, const float* queries, const uint8_t* queries_u8, const uint32_t* query_tags) {
+    if ((queries != nullptr) == (queries_u8 != nullptr)) return fail(GBNNS_ERR_INVALID, "%s: exactly one of queries / queries_u8", fn);
+    if (!ix) return fail(GBNNS_ERR_INVALID, "null argument");
+    if (queries_u8 && !ix->db_b) return fail(GBNNS_ERR_INVALID, "%s: queries_u8 needs a byte handle (gbnns_index_create_bytes)", fn);
+    if (queries && ix->db_b)
+        return fail(GBNNS_ERR_UNSUPPORTED, "%s: float queries on a byte handle: there is no mixed-pair scan (uint8 rows against "
+                    "float queries); pass queries_u8, or widen the table and call gbnns_exact_knn", fn);
+    if (query_tags && !ix->tags.p) return fail(GBNNS_ERR_INVALID, "%s with query_tags but without gbnns_index_set_tags", fn);
+    return GBNNS_OK;
+}
 }  // namespace
 
 namespace gbnns_api {
@@ -486,6 +653,11 @@ int knn_scan_resident(gbnns_index* ix, const float* queries, const uint8_t* quer
                       uint32_t* out_ids, float* out_dist, hipStream_t s) {
     if (queries) return knn_call(knn_resident_call(ix, ix->db, queries, n_q, query_tags, k, -1, out_ids, out_dist, GBNNS_MEM_DEVICE, s));
     return knn_call(knn_resident_call(ix, ix->db_b, queries_u8, n_q, query_tags, k, -1, out_ids, out_dist, GBNNS_MEM_DEVICE, s));
+}
+int knn_gather_resident(gbnns_index* ix, const float* queries, const uint8_t* queries_u8, uint64_t n_q, const uint32_t* query_tags, int k,
+                        uint32_t* out_ids, float* out_dist, hipStream_t s) {
+    if (queries) return knn_gather_call(ix, ix->db, queries, n_q, query_tags, k, -1, out_ids, out_dist, GBNNS_MEM_DEVICE, s);
+    return knn_gather_call(ix, ix->db_b, queries_u8, n_q, query_tags, k, -1, out_ids, out_dist, GBNNS_MEM_DEVICE, s);
 }
 }  // namespace gbnns_api
 
@@ -519,16 +691,75 @@ int gbnns_exact_knn_bytes_tagged(int device, const uint8_t* base, uint64_t n, co
 // handle's.  The packed workspace is the call's own: none of the lanes' workspaces is touched.
 int gbnns_index_exact_knn(gbnns_index* ix, const float* queries, const uint8_t* queries_u8, uint64_t n_q, const uint32_t* query_tags, int k,
                           int64_t self_offset, uint32_t* out_ids, float* out_dist, int mem_kind, void* stream) {
-    if ((queries != nullptr) == (queries_u8 != nullptr))
-        return fail(GBNNS_ERR_INVALID, "gbnns_index_exact_knn: exactly one of queries / queries_u8");
-    if (!ix) return fail(GBNNS_ERR_INVALID, "null argument");
-    if (queries_u8 && !ix->db_b) return fail(GBNNS_ERR_INVALID, "gbnns_index_exact_knn: queries_u8 needs a byte handle (gbnns_index_create_bytes)");
-    if (queries && ix->db_b)
-        return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_index_exact_knn: float queries on a byte handle: there is no mixed-pair scan (uint8 rows against "
-                    "float queries); pass queries_u8, or widen the table and call gbnns_exact_knn");
-    if (query_tags && !ix->tags.p) return fail(GBNNS_ERR_INVALID, "gbnns_index_exact_knn with query_tags but without gbnns_index_set_tags");
+    if (int rc = knn_index_refuse("gbnns_index_exact_knn", ix, queries, queries_u8, query_tags)) return rc;
     if (queries) return knn_index_call(ix, ix->db, queries, n_q, query_tags, k, self_offset, out_ids, out_dist, mem_kind, stream);
     return knn_index_call(ix, ix->db_b, queries_u8, n_q, query_tags, k, self_offset, out_ids, out_dist, mem_kind, stream);
+}
+
+// The gathered form: the same bytes, from distances to the allowed rows only (knn_gather.hip).  This call's own refusals need no handle and
+// come first; then gbnns_index_exact_knn's, in its order.
+int gbnns_index_exact_knn_gather(gbnns_index* ix, const float* queries, const uint8_t* queries_u8, uint64_t n_q, const uint32_t* query_tags, int k,
+                                 int64_t self_offset, uint32_t* out_ids, float* out_dist, int mem_kind, void* stream) {
+    if ((queries != nullptr) == (queries_u8 != nullptr))
+        return fail(GBNNS_ERR_INVALID, "gbnns_index_exact_knn_gather: exactly one of queries / queries_u8");
+    if (!query_tags) return fail(GBNNS_ERR_INVALID, "gbnns_index_exact_knn_gather: query_tags missing (an untagged call has nothing to gather: gbnns_index_exact_knn)");
+    if (k < 1 || k > (1 << 20)) return fail(GBNNS_ERR_INVALID, "k must be in [1, 2^20]");
+    if (int rc = knn_index_refuse("gbnns_index_exact_knn_gather", ix, queries, queries_u8, query_tags)) return rc;
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc;
+    if ((rc = enter_stream(ix, s))) return rc;
+    rc = queries ? knn_gather_call(ix, ix->db, queries, n_q, query_tags, k, self_offset, out_ids, out_dist, mem_kind, s)
+                 : knn_gather_call(ix, ix->db_b, queries_u8, n_q, query_tags, k, self_offset, out_ids, out_dist, mem_kind, s);
+    if (rc == GBNNS_OK && n_q) ix->in_flight = false;  // (the call returned behind a synchronisation of its stream)
+    return rc;
+}
+
+int gbnns_debug_gather_plan(int bytes, int metric, uint32_t d, int k, char* name, uint32_t name_bytes, uint32_t* queries_per_workgroup) {
+    if (!name || name_bytes == 0 || !queries_per_workgroup) return fail(GBNNS_ERR_INVALID, "gbnns_debug_gather_plan: null output");
+    if ((bytes != 0 && bytes != 1) || (metric != GBNNS_METRIC_L2 && metric != GBNNS_METRIC_NEG_DOT) || d == 0 || k < 1 || k > (1 << 20))
+        return fail(GBNNS_ERR_INVALID, "gbnns_debug_gather_plan: not a shape gbnns_index_exact_knn_gather takes");
+    if (bytes) {
+        KnnCall<uint8_t> c{};
+        c.d = d; c.k = k; c.metric = metric;
+        if (int rc = knn_refuse(c)) return rc;
+    } else {
+        KnnCall<float> c{};
+        c.d = d; c.k = k; c.metric = metric;
+        if (int rc = knn_refuse(c)) return rc;
+    }
+    const char* kernel = nullptr;
+    if (!gather_serves(metric, d, bytes != 0, k, &kernel, queries_per_workgroup))  // the fallback: the tagged instance of the existing scan
+        kernel = bytes ? knn_bytes_sweep_kernel_name((d + kKnnBytesKStep - 1) / kKnnBytesKStep * kKnnBytesKStep, true) : knn_scan_kernel_name(metric, d, true);
+    if (!kernel) return fail(GBNNS_ERR_INTERNAL, "gbnns_debug_gather_plan: no kernel instance for the plan");
+    std::snprintf(name, name_bytes, "%s", kernel);
+    return GBNNS_OK;
+}
+
+int gbnns_debug_gather_schedule(const uint32_t* words, const uint32_t* allowed, uint64_t n_q, uint64_t n, uint64_t budget, uint32_t W, uint32_t* order,
+                                uint32_t* round_of, uint64_t* list_offset_of, uint32_t* n_rounds, uint32_t* n_workgroups) {
+    if (!order || !round_of || !list_offset_of || !n_rounds || !n_workgroups || (n_q && (!words || !allowed)))
+        return fail(GBNNS_ERR_INVALID, "gbnns_debug_gather_schedule: null argument");
+    if (n == 0 || n >= (1ull << 32) - 1 || n_q >= (1ull << 31) || W == 0 || budget == 0)
+        return fail(GBNNS_ERR_INVALID, "gbnns_debug_gather_schedule: n in [1, 2^32 - 1), n_q < 2^31, W >= 1, budget >= 1");
+    for (uint64_t i = 0; i < n_q; ++i)
+        if (allowed[i] > n) return fail(GBNNS_ERR_INVALID, "gbnns_debug_gather_schedule: allowed[%llu] = %u exceeds n", (unsigned long long)i, allowed[i]);
+    GatherSchedule sch;
+    try {
+        gather_schedule(words, allowed, n_q, n, budget, W, sch);
+    } catch (...) {
+        return fail(GBNNS_ERR_OOM, "host allocation failed");
+    }
+    for (uint64_t i = 0; i < n_q; ++i) { order[i] = sch.order[i]; round_of[i] = 0xFFFFFFFFu; list_offset_of[i] = 0; }
+    for (const GatherGroup& g : sch.groups)
+        for (uint32_t e = 0; e < g.q_count; ++e) {
+            const uint32_t i = sch.order[g.q_begin + e];
+            round_of[i] = g.round;
+            list_offset_of[i] = g.list_off;
+        }
+    *n_rounds = (uint32_t)sch.round_entries.size();
+    *n_workgroups = (uint32_t)sch.wgs.size();
+    return GBNNS_OK;
 }
 
 int gbnns_debug_knn_bytes_plan(uint64_t n, uint64_t n_q, uint32_t d, int k, uint32_t* dp, uint32_t* cap, uint64_t* first_rows,

@@ -286,6 +286,10 @@ int build_ell(const uint64_t* off, const uint32_t* nbr, uint64_t n, std::vector<
 //   "byte_query_int" gbnns_search_byte_queries: the beam classes whose byte-walk first pass is the integer instance (walk_bytes_q.hip) -- a mask,
 //                   bit 0 = one list register (ef <= 64), bit 1 = two (ef <= 128), bit 2 = the two-list kernel (ef <= 1 024); 0 = never: the call
 //                   is served by walk_bytes.hip on the widened queries (A/B runs; GBNNS_BYTE_QUERY_INT).  Default: kByteQueryIntDefault
+//   "gather_budget" gbnns_index_exact_knn_gather: list entries (4 bytes each) the id lists of one round may hold together; default 2^26 (256 MiB),
+//                   and the call never takes less than n.  Not for tuning: a test forces several rounds at a few thousand rows with it
+//   "gather_timing" 1 = a gathered call times its stages with events (its rounds then run one after the other); read back with
+//                   gbnns_index_knob_get: "gather_census_us", "gather_fill_us", "gather_scan_us", "gather_rounds" (tools/exact_gather_timing.py)
 //   "coop"          the two-wavefront walk for small batches (walk_coop.hip): -1 = where it serves and the batch leaves the room
 //                   (default), 0 = never, 1 = wherever the shape allows (tests, A/B runs; GBNNS_COOP)
 // Process-wide only (gbnns_exact_knn has no handle):
@@ -318,6 +322,8 @@ bool knob_set(Knobs& k, const char* name, int value) {
     else if (!std::strcmp(name, "coop")) k.coop = std::max(-1, std::min(1, value));
     else if (!std::strcmp(name, "hot")) k.hot = value != 0;
     else if (!std::strcmp(name, "byte_query_int")) k.byte_query_int = std::max(0, std::min(7, value));
+    else if (!std::strcmp(name, "gather_budget")) k.gather_budget = std::max(1, value);
+    else if (!std::strcmp(name, "gather_timing")) k.gather_timing = value != 0;
     else return false;
     return true;
 }
@@ -338,6 +344,8 @@ static Knobs& knob_default_ref() {  // (function-local: initialised on first use
         knob_set(k, "coop", knob_env("GBNNS_COOP", -1));
         knob_set(k, "hot", knob_env("GBNNS_HOT", 1));
         knob_set(k, "byte_query_int", knob_env("GBNNS_BYTE_QUERY_INT", kByteQueryIntDefault));
+        knob_set(k, "gather_budget", knob_env("GBNNS_GATHER_BUDGET", 1 << 26));
+        knob_set(k, "gather_timing", 0);
         return k;
     }();
     return d;
@@ -1073,7 +1081,9 @@ int gbnns_index_knob_get(gbnns_index* ix, const char* name, int* out) {
     const struct { const char* n; int v; } all[] = {
         {"quotient", k.quotient}, {"vs_disp", k.vs_disp}, {"max_waves", k.max_waves}, {"spec_min_nq", k.spec_min_nq},
         {"spec_any_form", k.spec_any_form}, {"mlp_small", k.mlp_small}, {"mlp_net", k.mlp_net}, {"mlp_slab", k.mlp_slab},
-        {"late_rows", k.late_rows}, {"spec_tail", k.spec_tail}, {"coop", k.coop}, {"hot", k.hot}, {"byte_query_int", k.byte_query_int}, {"mlp_net_form", ix->net_form}};
+        {"late_rows", k.late_rows}, {"spec_tail", k.spec_tail}, {"coop", k.coop}, {"hot", k.hot}, {"byte_query_int", k.byte_query_int}, {"mlp_net_form", ix->net_form},
+        {"gather_budget", k.gather_budget}, {"gather_timing", k.gather_timing}, {"gather_census_us", ix->gather_us[0]}, {"gather_fill_us", ix->gather_us[1]},
+        {"gather_scan_us", ix->gather_us[2]}, {"gather_rounds", ix->gather_rounds}};
     for (const auto& e : all)
         if (!std::strcmp(name, e.n)) { *out = e.v; return GBNNS_OK; }
     return fail(GBNNS_ERR_INVALID, "gbnns_index_knob_get: unknown handle knob '%s'", name);

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 namespace gbnns {
 
 constexpr uint32_t kInvalidId = 0xFFFFFFFFu;
@@ -382,6 +384,66 @@ struct KnnBytesOfferParams {
     int32_t* thr;
 };
 hipError_t launch_knn_bytes_offer(const KnnBytesOfferParams& p, hipStream_t s);
+
+// Gathered exact scan (knn_gather.hip; gbnns_index_exact_knn_gather): the queries of a batch that share a tag word scan the list of the
+// rows that word allows instead of the table.  gather_schedule (host, pure) groups and deals the work; the fill kernel materialises the
+// lists of a round; knn_gather_kernel is knn_scan_kernel's loop with the tile's rows read through a list and a thread's queries through
+// the schedule's permutation.  d <= 128, heaps [k x heap_stride] as the scan's, finished by launch_knn_finalize.
+struct GatherGroup {         // the queries of one distinct word with allowed > 0
+    uint32_t word;
+    uint32_t len;            // rows the word allows (the census count): the length of its list
+    uint32_t q_begin, q_count;  // its queries: order[q_begin .. q_begin + q_count), ascending index
+    uint32_t round;
+    uint64_t list_off;       // first entry of its list in the round's list buffer
+};
+struct GatherWorkgroup {     // one workgroup of knn_gather_kernel: up to W queries of one group
+    uint32_t list_off_lo, list_off_hi;  // (two words: the struct is read by the device as uint32 x 6)
+    uint32_t list_len;
+    uint32_t q_begin, q_count;  // order[q_begin .. q_begin + q_count), q_count <= W
+    uint32_t pad;
+};
+struct GatherSchedule {
+    std::vector<uint32_t> order;           // [nq] a permutation: groups in ascending word order, queries of a group in ascending index, then the queries that may see nothing
+    std::vector<GatherGroup> groups;       // ascending word, hence ascending round
+    std::vector<GatherWorkgroup> wgs;      // round by round, group by group
+    std::vector<uint32_t> round_group0;    // [n_rounds + 1] first group of every round
+    std::vector<uint32_t> round_wg0;       // [n_rounds + 1] first workgroup of every round
+    std::vector<uint64_t> round_entries;   // [n_rounds] list entries of the round
+};
+// words / allowed [nq]: every query's tag word and census count (<= n); budget: list entries a round may hold (a group longer than that gets a
+// round of its own); W: queries a workgroup serves.  Throws std::bad_alloc only.
+void gather_schedule(const uint32_t* words, const uint32_t* allowed, uint64_t nq, uint64_t n, uint64_t budget, uint32_t W, GatherSchedule& out);
+struct GatherFillParams {
+    const uint32_t* tags;    // [n] the handle's tag table, 16-byte aligned
+    uint64_t n;
+    const uint32_t* words;   // [groups] the round's words
+    const uint32_t* caps;    // [groups] their census counts: entries of a word's list; a store beyond is dropped
+    const uint64_t* offs;    // [groups] first entry of each word's list in `list`
+    uint32_t groups;
+    uint32_t* cursor;        // [groups] zero at launch
+    uint32_t* list;          // the round's list buffer
+};
+hipError_t launch_gather_fill(const GatherFillParams& p, hipStream_t s);
+struct KnnGatherParams {
+    const float* base;       // [n x bstride] float rows, or nullptr:
+    const uint8_t* base_b;   // [n x bstride] byte rows (16-byte aligned, zero padded to bstride), widened while staged
+    uint32_t bstride;        // elements between rows
+    const float* q;          // [nq x qstride], or nullptr:
+    const uint8_t* q_b;      // [nq x qstride] byte queries, widened into registers
+    uint32_t qstride;
+    uint32_t dim;            // <= 128
+    int32_t k;
+    int64_t self_offset;     // >= 0: query i is row i + self_offset (original ids) and is not its own neighbour; -1: off
+    uint64_t* heap;          // [k x heap_stride], by ORIGINAL query index
+    size_t heap_stride;
+    const uint32_t* order;   // [nq] the schedule's permutation
+    const GatherWorkgroup* wgs;  // the round's workgroups
+    uint32_t n_wgs;
+    const uint32_t* list;    // the round's list buffer, filled
+};
+hipError_t launch_knn_gather(const KnnGatherParams& p, int metric, hipStream_t s);
+// Host only, no device needed: the instance launch_knn_gather starts for a shape and the queries W one of its workgroups serves (nullptr / 0: d > 128)
+const char* knn_gather_kernel_name(int metric, uint32_t dim, bool bytes, uint32_t* W);
 
 // GD pruning of a kNN graph, one node per wavefront (support_func.h:521-563).  deg[i] = 0xFFFFFFFF marks a node
 // left to the host (equal distances in its list, list longer than 1024, id out of range).

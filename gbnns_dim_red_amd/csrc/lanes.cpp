@@ -72,7 +72,7 @@ int flush_joins(gbnns_index* ix, size_t keep) {
 int flush_join(gbnns_index* ix) { return flush_joins(ix, 0); }
 
 // The refusals of a search call, in the order the tests pin, before anything touches a device (declared in api_internal.h).
-int search_check(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk, const TagIn* tag, const uint8_t* q_u8, bool* empty) {
+int search_check(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* topk, const TagIn* tag, const uint8_t* q_u8, bool* empty, bool routed) {
     *empty = false;
     if (!ix || !a) return fail(GBNNS_ERR_INVALID, "null argument");
     if (a->struct_size != sizeof(gbnns_search_args))
@@ -103,6 +103,8 @@ int search_check(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* top
         return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_AUX_GRAPH without gbnns_index_set_aux_graph");
     if (!tag && (a->flags & GBNNS_FLAG_TAG_BRIDGE))
         return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_TAG_BRIDGE has a meaning in gbnns_search_tagged only");
+    if (!routed && (a->flags & GBNNS_FLAG_SCAN_GATHER))
+        return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_SCAN_GATHER has a meaning in gbnns_search_tagged_auto only");
     if (tag) {
         if (a->flags & (GBNNS_FLAG_HALF_ROWS | GBNNS_FLAG_MFMA_PROJECTION))
             return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_search_tagged: GBNNS_FLAG_HALF_ROWS / GBNNS_FLAG_MFMA_PROJECTION are not served");
@@ -250,8 +252,10 @@ int auto_device(gbnns_index* ix, const gbnns_search_args* a, const uint8_t* q_u8
         uint32_t* const gids = gtags + m;
         float* const gdist = o.top_dist ? reinterpret_cast<float*>(gids + (size_t)m * k) : nullptr;
         HIP_TRY(launch_tag_gather(q_u8 ? static_cast<const void*>(q_u8) : a->queries, q_u8 ? 1 : 0, ix->d, qtags, list, m, gq, gtags, s));
-        if ((rc = knn_scan_resident(ix, q_u8 ? nullptr : reinterpret_cast<const float*>(gq), q_u8 ? reinterpret_cast<const uint8_t*>(gq) : nullptr, m,
-                                    gtags, o.k, gids, gdist, s)))
+        // (GBNNS_FLAG_SCAN_GATHER: the same rows from gbnns_index_exact_knn_gather's computation)
+        const auto scan = (a->flags & GBNNS_FLAG_SCAN_GATHER) ? knn_gather_resident : knn_scan_resident;
+        if ((rc = scan(ix, q_u8 ? nullptr : reinterpret_cast<const float*>(gq), q_u8 ? reinterpret_cast<const uint8_t*>(gq) : nullptr, m, gtags, o.k, gids,
+                       gdist, s)))
             return rc;
         HIP_TRY(launch_tag_scatter(gids, gdist, list, m, k, o.top_ids, o.top_dist, a->out_ids, s));
     }
@@ -409,7 +413,7 @@ int gbnns_search_tagged_auto(gbnns_index* ix, const gbnns_search_args* a, const 
     const TopkOut t{k, out_top_ids, out_top_dist};
     const TagIn g{query_tags, (a->flags & GBNNS_FLAG_TAG_BRIDGE) != 0};
     bool empty;
-    if (int rc = search_check(ix, a, &t, &g, queries_u8, &empty)) return rc;
+    if (int rc = search_check(ix, a, &t, &g, queries_u8, &empty, true)) return rc;
     if (empty) return GBNNS_OK;
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t s = static_cast<hipStream_t>(a->stream);

@@ -501,7 +501,11 @@ int gbnns_profile_enable(gbnns_index* index, int on);
  * (GBNNS_KNN_FILTER).
  * "knn_slab": most queries gbnns_exact_knn's pool path and gbnns_exact_knn_bytes serve at a time -- 0 (default) = as many as keep their
  * key lists within 4 GiB (the slab formula at gbnns_exact_knn_bytes); v > 0 caps a slab at max(128, v & ~127) queries, so that a few
- * hundred queries already run several slabs (tests).  gbnns_debug_knn_slab reports the slab of a shape. */
+ * hundred queries already run several slabs (tests).  gbnns_debug_knn_slab reports the slab of a shape.
+ * "gather_budget" (handle knob): list entries the id lists of one round of gbnns_index_exact_knn_gather may hold together (default 2^26, at
+ * least 1; the call never takes less than n; GBNNS_GATHER_BUDGET) -- not for tuning: a test forces several rounds at a few thousand rows.
+ * "gather_timing" (handle knob): 1 = a gathered call times its stages with events, its rounds one after the other (default 0); the last
+ * such call's figures through gbnns_index_knob_get only: "gather_census_us", "gather_fill_us", "gather_scan_us", "gather_rounds". */
 int gbnns_debug_knob(const char* name, int value);
 int gbnns_index_knob(gbnns_index* index, const char* name, int value);   /* GBNNS_ERR_INVALID: not a handle knob */
 int gbnns_index_knob_get(gbnns_index* index, const char* name, int* out_value);   /* the handle's current value */
@@ -693,6 +697,49 @@ int gbnns_index_tag_census(gbnns_index* index, const uint32_t* query_tags, uint6
  * as gbnns_index_exact_knn does; there is no gbnns_multi_* form, and gbnns_profile sees the walk only. */
 int gbnns_search_tagged_auto(gbnns_index* index, const gbnns_search_args* args, const uint8_t* queries_u8, const uint32_t* query_tags, int k,
                              uint64_t scan_below, uint32_t* out_top_ids, float* out_top_dist, uint32_t* out_allowed, uint8_t* out_route);
+
+/* Gathered exact tagged kNN: gbnns_index_exact_knn(index, ..., query_tags, ...) computed from distances to the rows a query's tag word
+ * allows and to no others.  Every output byte is what gbnns_index_exact_knn returns for the same arguments on the same handle: each row
+ * holds the k smallest (Dist, id) pairs among the rows with (T[j] & Q[i]) != 0, distances in the reference's arithmetic, ties towards the
+ * lower id, padded with 0xFFFFFFFF / +inf; self_offset in original ids; the handle's metric; float and byte handles; the same stream rule
+ * (the deferred calls still owed are joined; the call returns when the work has finished).  Opt-in: nothing else calls it unless
+ * GBNNS_FLAG_SCAN_GATHER asks.
+ *   Pipeline (one host round trip): the census of gbnns_index_tag_census gives allowed[i]; the host groups the queries by word and deals
+ *   the groups into rounds whose id lists together fit "gather_budget" list entries (a handle knob: default 2^26 = 256 MiB, never less than
+ *   n; a test's means to force several rounds, not a tuning knob); per round one kernel writes the allowed row ids of every distinct word
+ *   of the round into the word's list (in whatever order its atomics give: selection is by the (distance, id) key) and one kernel lets the
+ *   queries of a word scan the word's list -- gbnns_exact_knn's scan loop with the rows read through the list, the same operations in the
+ *   same order per distance; byte rows are widened while they are staged (every partial sum is an integer below 2^24: exact), no float copy
+ *   of a byte table, no packed copy of any table.  Work: sum over the queries of allowed[i] x d, plus n x U for the U distinct words.
+ *   Covered by the gathered kernel: d <= 128, L2 at any d, the negative dot at d % 8 == 0, 1 <= k <= 4 096 (heaps; k >= 64 is untuned: there
+ *   is no pool path).  Any other shape the call accepts is NOT refused: the same call runs gbnns_index_exact_knn's scan and returns the same
+ *   bytes (gbnns_debug_gather_plan tells which).
+ * Refusals and status codes are gbnns_index_exact_knn's, and one more: query_tags == NULL is GBNNS_ERR_INVALID (an untagged call has nothing
+ * to gather).  Workspace per call: the heaps (8 k bytes a query), the census' workspace, 16 bytes a query, 44 bytes a distinct word, and the
+ * largest round's lists (4 bytes an entry). */
+int gbnns_index_exact_knn_gather(gbnns_index* index, const float* queries, const uint8_t* queries_u8, uint64_t n_q, const uint32_t* query_tags,
+                                 int k, int64_t self_offset, uint32_t* out_ids, float* out_dist, int mem_kind, void* stream);
+/* gbnns_search_tagged_auto only: the scan-routed queries are served by gbnns_index_exact_knn_gather's computation instead of
+ * gbnns_index_exact_knn's.  Every output is unchanged.  In every other search call the flag is GBNNS_ERR_INVALID, like GBNNS_FLAG_TAG_BRIDGE
+ * outside the tagged calls. */
+#define GBNNS_FLAG_SCAN_GATHER 4096u
+/* Diagnostic, no device needed: the kernel instance that serves a gbnns_index_exact_knn_gather call on a float (bytes = 0) or byte (1) handle
+ * of that metric, d and k -- "knn_gather_kernel<METRIC, S, QPT, U8>" with *queries_per_workgroup = W, the queries one of its workgroups serves;
+ * or, for a shape the gathered kernel does not cover (d > 128, k > 4 096), the tagged instance of the existing scan ("knn_scan_wide_kernel<...>",
+ * "knn_bytes_sweep_kernel<...>", ...) with W = 0: the fallback.  GBNNS_ERR_INVALID / GBNNS_ERR_UNSUPPORTED for a shape the call refuses. */
+int gbnns_debug_gather_plan(int bytes, int metric, uint32_t d, int k, char* name, uint32_t name_bytes, uint32_t* queries_per_workgroup);
+/* Diagnostic, no device needed: the schedule gbnns_index_exact_knn_gather builds -- the very host function -- from the queries' words [n_q] and
+ * census counts allowed [n_q] (each <= n), a budget of list entries per round and W queries per workgroup.
+ *   Groups: the queries with allowed > 0 by word, groups in ascending word order, queries inside a group in ascending index.  A word that
+ *   allows nothing has no group.  order [n_q]: the permutation that lists the groups' queries in that order, then the queries without a group
+ *   in ascending index.
+ *   Rounds: the groups, in order, fill a round while its lists' entries stay within `budget`; a group that does not fit opens the next
+ *   round, so a group longer than the budget has a round of its own.  round_of [n_q]: the round of query i's group (0xFFFFFFFF: none);
+ *   list_offset_of [n_q]: the first entry of its group's list in the round's list buffer (lists lie back to back in group order).
+ *   Workgroups: a group of g queries takes ceil(g / W) workgroups on its one list.  *n_rounds, *n_workgroups: the totals.
+ * GBNNS_ERR_INVALID: a NULL array, n outside [1, 2^32 - 1), n_q >= 2^31, W == 0, budget == 0, allowed[i] > n. */
+int gbnns_debug_gather_schedule(const uint32_t* words, const uint32_t* allowed, uint64_t n_q, uint64_t n, uint64_t budget, uint32_t W,
+                                uint32_t* order, uint32_t* round_of, uint64_t* list_offset_of, uint32_t* n_rounds, uint32_t* n_workgroups);
 
 /* ---- several devices of one node: query-sharded replicas ----------------------------------------------------
  * The reference's only parallelism on this path is `#pragma omp parallel for` over the queries of a batch

@@ -10,14 +10,16 @@ Every row draws r uniform in 0 .. 63 and gets bit b (b = 0 .. 6) when r < 64 >> 
             bridged   the bridged walk alone (search with FLAG_TAG_BRIDGE, top_k = k) entered at the census's `first` rows
             scan      the exact scan alone (Index.exact_knn with query_tags; recall 1 by definition)
             auto w/s  search_auto with scan_below 0 (every query walks, bridged) and 2^64 - 1 (every query scans): the routed call's overhead
-  mixed     one batch whose query i carries fraction 2^-(i % 7): search_auto at scan_below between every two neighbouring fractions
+  mixed     one batch whose query i carries fraction 2^-(i % 7): search_auto at scan_below between every two neighbouring fractions,
+            without and with FLAG_SCAN_GATHER (the scan-routed queries through the gathered exact scan), interleaved; --only-mixed runs
+            this section alone
 
 Wall ms: host clock around one call with the device idle before and after (every call here returns when its work has finished, or is
 followed by a synchronisation).  Medians over REPEATS rounds with the lowest and highest round beside them, the variants of a row
 interleaved on the same handle in the same run.  LOWQ mode at ef 64: the low-dimensional queries are the net's projection of the
 unquantised ones.  No threshold is asserted: the table is the answer, for this one synthetic recipe on this one device.
 
-    python tools/tag_auto_timing.py [--cache-dir DIR] [--n N] [--out FILE]
+    python tools/tag_auto_timing.py [--cache-dir DIR] [--n N] [--out FILE] [--only-mixed]
 """
 import argparse
 import json
@@ -91,6 +93,7 @@ def main():
     ap.add_argument("--cache-dir", default=os.environ.get("GBNNS_CACHE", "/tmp/gbnns_cache"))
     ap.add_argument("--n", type=int, default=None, help="override the base-set size (quick looks)")
     ap.add_argument("--out", default=None, help="also write the table to this file")
+    ap.add_argument("--only-mixed", action="store_true", help="the mixed batch alone")
     args = ap.parse_args()
     os.makedirs(args.cache_dir, exist_ok=True)
     kw = dict(SHAPE)
@@ -122,7 +125,7 @@ def main():
     q_f = q_u8.to(torch.float32).contiguous()
     times = {u: [] for u in batches}
     walk = []
-    for rnd in range(-WARMUP, REPEATS):
+    for rnd in range(-WARMUP, 0 if args.only_mixed else REPEATS):
         for u, words in batches.items():
             qt = words.to(dev)
             t = event_ms(lambda: ix.tag_census(qt), CALLS)
@@ -131,7 +134,7 @@ def main():
         w = cut_walk_ms(ix, q_f, q_low, ent_all, all_q)
         if rnd >= 0:
             walk.append(w)
-    for u, words in batches.items():
+    for u, words in ({} if args.only_mixed else batches).items():
         assert len(torch.unique(words)) == u
         a, f = ix.tag_census(words.to(dev))
         ha, hf = g.tag_census(tags.numpy().view("uint32"), words.numpy().view("uint32")) if u <= 13 else (None, None)
@@ -139,15 +142,16 @@ def main():
             assert (a.cpu().numpy().view("uint32") == ha).all() and (f.cpu().numpy().view("uint32") == hf).all()
         lines.append("census  U = %-6d %s ms" % (u, spread(times[u])))
         records.append({"census_U": u, "ms": statistics.median(times[u])})
-    lines.append("cut walk (gbnns_search_tagged, every row allowed), walk_ms %s" % spread(walk))
-    records.append({"cut_walk_ms": statistics.median(walk)})
+    if not args.only_mixed:
+        lines.append("cut walk (gbnns_search_tagged, every row allowed), walk_ms %s" % spread(walk))
+        records.append({"cut_walk_ms": statistics.median(walk)})
     print("\n".join(lines), file=sys.stderr, flush=True)
 
     # ---- one fraction per batch --------------------------------------------------------------------------------------------------
-    def auto(qt, k, sb):
-        return ix.search_auto(q_u8, EF, k, qt, scan_below=sb, mode=g.MODE_LOWQ, queries_low=q_low, flags=g.FLAG_TAG_BRIDGE, want=())
+    def auto(qt, k, sb, gather=0):
+        return ix.search_auto(q_u8, EF, k, qt, scan_below=sb, mode=g.MODE_LOWQ, queries_low=q_low, flags=g.FLAG_TAG_BRIDGE | gather, want=())
 
-    for b in BITS:
+    for b in (() if args.only_mixed else BITS):
         qt = torch.full((nq,), 1 << b, dtype=torch.int32, device=dev)
         _, first = ix.tag_census(qt)
         rows = int((tags & (1 << b) != 0).sum())
@@ -182,18 +186,22 @@ def main():
            [("2^64 - 1 (all scan)", ALL)]
     for k in KS:
         truth = ix.exact_knn(q_u8, k, query_tags=qt)
-        t = {name: [] for name, _ in cuts}
+        forms = (("", 0), (" + FLAG_SCAN_GATHER", g.FLAG_SCAN_GATHER))
+        t = {(name, form): [] for name, _ in cuts for form, _ in forms}
         for rnd in range(-WARMUP, REPEATS):
             for name, sb in cuts:
-                ms = wall_ms(lambda: auto(qt, k, sb))
-                if rnd >= 0:
-                    t[name].append(ms)
+                for form, flag in forms:
+                    ms = wall_ms(lambda: auto(qt, k, sb, flag))
+                    if rnd >= 0:
+                        t[(name, form)].append(ms)
         for name, sb in cuts:
-            res = auto(qt, k, sb)
-            rc = recall(res["top_ids"], truth)
-            scanned = int(res["route"].sum())
-            lines.append("  k %-2d  scan_below %-26s %s ms   recall@%d %.4f   scan-routed %d" % (k, name, spread(t[name]), k, rc, scanned))
-            records.append({"mixed": True, "k": k, "scan_below": sb, "ms": round(statistics.median(t[name]), 4), "recall": round(rc, 4), "scanned": scanned})
+            for form, flag in forms:
+                res = auto(qt, k, sb, flag)
+                rc = recall(res["top_ids"], truth)
+                scanned = int(res["route"].sum())
+                lines.append("  k %-2d  scan_below %-26s %s ms   recall@%d %.4f   scan-routed %d%s" % (k, name, spread(t[(name, form)]), k, rc, scanned, form))
+                records.append({"mixed": True, "k": k, "scan_below": sb, "gather": bool(flag), "ms": round(statistics.median(t[(name, form)]), 4),
+                                "recall": round(rc, 4), "scanned": scanned})
     ix.close()
     text = "\n".join(lines)
     print(text)
