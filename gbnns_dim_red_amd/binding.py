@@ -47,6 +47,7 @@ SYMBOLS = [
     "gbnns_index_tag_census", "gbnns_search_tagged_auto",
     "gbnns_debug_knn_plan", "gbnns_debug_census_slot",
     "gbnns_index_exact_knn_gather", "gbnns_debug_gather_plan", "gbnns_debug_gather_schedule",
+    "gbnns_debug_project_plan", "gbnns_index_project_last",
 ]
 
 
@@ -171,6 +172,10 @@ def load_library():
     lib.gbnns_debug_knn_plan.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_char_p, C.c_uint32,
                                          C.POINTER(C.c_int)]
     lib.gbnns_debug_census_slot.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    if hasattr(lib, "gbnns_debug_project_plan"):  # (as above: absent from an older library put in this one's place for an A/B run)
+        lib.gbnns_debug_project_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 C.c_char_p, C.c_uint32]
+        lib.gbnns_index_project_last.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32]
     lib.gbnns_multi_last_error.restype = C.c_char_p
     lib.gbnns_multi_create.argtypes = [C.POINTER(_IndexDesc), C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
     lib.gbnns_multi_destroy.argtypes = [C.c_void_p]
@@ -379,6 +384,16 @@ def knn_plan(bytes, metric, n, n_q, d, k, tagged=False):
     pool = C.c_int(0)
     _check(load_library().gbnns_debug_knn_plan(int(bool(bytes)), metric, n, n_q, d, k, int(bool(tagged)), name, 128, C.byref(pool)))
     return name.value.decode(), bool(pool.value)
+
+
+def project_plan(d, d_hidden, d_low, n_q, cus=256, in_flight=False, mfma=False, mlp_net=1, mlp_slab=1, mlp_small=4096):
+    """gbnns_debug_project_plan (no device needed): the names of the kernel instances the projection of an n_q-query batch through the net
+    d -> d_hidden -> d_hidden -> d_low launches on a device of `cus` compute units, in launch order, template arguments as in the source;
+    in_flight: a FLAG_DEFER_JOIN call, mfma: FLAG_MFMA_PROJECTION, mlp_*: the handle knobs of those names (defaults: the library's)."""
+    names = C.create_string_buffer(512)
+    _check(load_library().gbnns_debug_project_plan(d, d_hidden, d_low, n_q, cus, int(bool(in_flight)), int(bool(mfma)), mlp_net, mlp_slab,
+                                                   mlp_small, names, 512))
+    return tuple(names.value.decode().split("\n")) if names.value else ()
 
 
 def gather_plan(bytes, metric, d, k):
@@ -1091,6 +1106,13 @@ class Index:
         v = C.c_int(0)
         _check(self._lib.gbnns_index_knob_get(self._h, name.encode() if isinstance(name, str) else name, C.byref(v)))
         return v.value
+
+    def project_last(self):
+        """gbnns_index_project_last: the names of the kernel instances this handle's last projection launched, in launch order
+        (project_plan's format; () before the first one)."""
+        names = C.create_string_buffer(512)
+        _check(self._lib.gbnns_index_project_last(self._h, names, 512))
+        return tuple(names.value.decode().split("\n")) if names.value else ()
 
     def profile_read(self, reset=True):
         p = Profile()

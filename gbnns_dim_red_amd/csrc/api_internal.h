@@ -198,6 +198,7 @@ struct gbnns_index {
     DevBuf tags;                    // gbnns_index_set_tags: [n] tag words, all ones until written (empty: no table)
     bool net_mfma_ready = false;
     int net_form = -1;              // form of the last one-launch exact projection (kernels.h: kNetWholeCu / kNetHalfCu; -1: none yet)
+    gbnns::ProjPlan proj_last{};    // the kernel instances the last projection launched, in launch order (gbnns_index_project_last)
     uint32_t ell_stride = 0, aux_stride = 0;
     bool has_aux = false;
     bool has_net = false;

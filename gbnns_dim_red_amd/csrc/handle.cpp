@@ -278,6 +278,7 @@ int build_ell(const uint64_t* off, const uint32_t* nbr, uint64_t n, std::vector<
 //                   run_project's rule picks, 2 = always its whole-CU form, 3 = its half-CU form wherever that fits (GBNNS_MLP_NET)
 //   "mlp_net_form"  (read only, gbnns_index_knob_get) the form the handle's last one-launch projection ran in: 0 = whole-CU blocks,
 //                   1 = half-CU blocks, -1 = none yet
+//   "cus"           (read only) the compute units of the handle's device: what the projection's launch rules count rounds of the machine in
 //   "mlp_slab"      0 = never the slab kernel for single layers (mlp_net.hip, mlp_slab_kernel), 1 = where a layer is one round of it
 //   "late_rows"     generic two-list kernels over 192- / 256- / 576-byte rows -- -1 = by shape and residency (search_core.cpp), 0 = rows
 //                   requested before the visited test, 1 = after it (GBNNS_LATE_ROWS)
@@ -614,42 +615,145 @@ int gbnns_index_destroy(gbnns_index* ix) {
 namespace gbnns_api {
 
 
-// MLP over rows x [nx x xstride] (device) -> out [nx x dl_pad] (device); h1/h2 are scratch.
-int run_project(gbnns_index* ix, Lane& L, const float* x, uint32_t xstride, uint32_t nx, float* out,
-                hipStream_t s, bool in_flight, bool mfma) {
+// What decides a projection's launches: the net's shape, the batch, the device's CU count, the call's flags, the handle's knobs and the
+// ALIGNMENT of the buffers (x, w: never dereferenced here; the hidden activations live in 256-byte aligned scratch).
+struct ProjShape {
+    uint32_t d, dh, dl, dl_pad, nq, xstride;
+    int cus;
+    bool in_flight, mfma;
+    int mlp_net, mlp_slab, mlp_small;
+    const float* x;
+    const float* w[3];
+    uint32_t ws[3];
+};
+enum class ProjPath { Net, MfmaNet, Layers };
+enum class LayerPath { Layer, Slab, Mfma };
+struct ProjRoute {
+    ProjPath path;
+    int form;                // Net: kNetWholeCu / kNetHalfCu
+    int small_footprint;     // Layers: LayerParams::small_footprint of the three
+    LayerPath layer[3];
+};
+
+static NetLaunch net_of(const ProjShape& q) {
+    NetLaunch n{};
+    n.x = q.x; n.xstride = q.xstride; n.nq = q.nq; n.ostride = q.dl_pad; n.cus = q.cus;
+    for (int l = 0; l < 3; ++l) { n.w[l] = q.w[l]; n.wstride[l] = q.ws[l]; }
+    n.din[0] = q.d; n.din[1] = n.din[2] = q.dh;
+    n.dout[0] = n.dout[1] = q.dh; n.dout[2] = q.dl;
+    return n;
+}
+
+// layer l without its bias and output pointers; h: the hidden activations it reads (l > 0)
+static LayerParams layer_of(const ProjShape& q, int l, int small_footprint, const float* h) {
+    LayerParams p{};
+    p.x = l ? h : q.x; p.xstride = l ? q.dh : q.xstride; p.w = q.w[l]; p.wstride = q.ws[l];
+    p.nq = q.nq; p.din = l ? q.dh : q.d; p.dout = l < 2 ? q.dh : q.dl; p.ostride = l < 2 ? q.dh : q.dl_pad;
+    p.relu = l < 2; p.normalize = l == 2; p.small_footprint = small_footprint;
+    return p;
+}
+
+// The one place that says which kernels a projection runs on: the route run_project follows, and in `plan` (where asked for) the instance
+// of every launch, from the same pick functions the launchers switch on.
+static ProjRoute project_route(const ProjShape& q, ProjPlan* plan) {
+    ProjRoute r{};
+    ProjPlan none{};
+    if (!plan) plan = &none;
+    *plan = ProjPlan{};
     // the whole net in one launch where it serves (round 5, mlp_net.hip: 0.048 against 0.075 ms on the SIFT shape; the
     // round-2 one-launch form -- csrc/project.hip, deleted in round 4 -- was slower than the three launches)
-    if (!mfma && ix->knob.mlp_net) {
-        NetLaunch n{};
-        n.x = x; n.xstride = xstride; n.nq = nx; n.out = out; n.ostride = ix->dl_pad; n.cus = ix->cus;
-        n.w[0] = ix->w1; n.w[1] = ix->w2; n.w[2] = ix->w3;
-        n.wstride[0] = ix->ws1; n.wstride[1] = ix->ws2; n.wstride[2] = ix->ws3;
-        n.bias[0] = ix->b1; n.bias[1] = ix->b2; n.bias[2] = ix->b3;
-        n.din[0] = ix->d; n.din[1] = n.din[2] = ix->d_hidden;
-        n.dout[0] = n.dout[1] = ix->d_hidden; n.dout[2] = ix->d_low;
+    if (!q.mfma && q.mlp_net) {
+        NetLaunch n = net_of(q);
         if (mlp_net_serves(n)) {
             // batches in flight: blocks of half a CU (4 wavefronts, <= 80 KB) -- one is placed as soon as a CU is half drained of the
             // other lanes' walk wavefronts, where a whole-CU block waits for all of them (profiles/half_cu_projection.txt: sift-like
             // 33.2 against 32.2 M queries/s); alone the whole-CU form is the faster one (50 against 62 us), so lone calls keep it
-            const int mode = ix->knob.mlp_net;
-            const bool want_half = mode == 3 || (mode == 1 && in_flight);
+            const int mode = q.mlp_net;
+            const bool want_half = mode == 3 || (mode == 1 && q.in_flight);
             n.form = want_half && mlp_net_half_serves(n) ? kNetHalfCu : kNetWholeCu;
-            for (int l = 0; l < 3; ++l) n.img[l] = ix->net_img[n.form][l];
-            HIP_TRY(launch_mlp_net(n, s));
-            ix->net_form = n.form;
-            std::snprintf(ix->acc.project_kernel, sizeof(ix->acc.project_kernel), "mlp_net_kernel");
-            return GBNNS_OK;
+            r.path = ProjPath::Net;
+            r.form = n.form;
+            NetPick k{};
+            if (mlp_net_pick(n, &k)) plan->add(k.inst);
+            return r;
         }
     }
-    if (mfma && !getenv("GBNNS_MFMA_LAYERS") && mlp_mfma_net_serves(ix->d, ix->d_hidden, ix->d_low)) {
+    if (q.mfma && !getenv("GBNNS_MFMA_LAYERS") && mlp_mfma_net_serves(q.d, q.dh, q.dl)) {
         // the throughput option in one launch (round 6, mlp_mfma_net.hip); GBNNS_MFMA_LAYERS=1 keeps round 5's three launches (A/B)
-        NetLaunch n{};
-        n.x = x; n.xstride = xstride; n.nq = nx; n.out = out; n.ostride = ix->dl_pad; n.cus = ix->cus;
-        n.w[0] = ix->w1; n.w[1] = ix->w2; n.w[2] = ix->w3;
-        n.wstride[0] = ix->ws1; n.wstride[1] = ix->ws2; n.wstride[2] = ix->ws3;
-        n.bias[0] = ix->b1; n.bias[1] = ix->b2; n.bias[2] = ix->b3;
-        n.din[0] = ix->d; n.din[1] = n.din[2] = ix->d_hidden;
-        n.dout[0] = n.dout[1] = ix->d_hidden; n.dout[2] = ix->d_low;
+        r.path = ProjPath::MfmaNet;
+        MfmaNetPick k{};
+        if (mlp_mfma_net_pick(net_of(q), &k)) plan->add(k.inst);
+        return r;
+    }
+    r.path = ProjPath::Layers;
+    // batches in flight whose walks fill the machine: the small-footprint kernel for the hidden layers (mlp.hip; sift-like
+    // +2.5 % at ef 64, +3.6 % at ef 36; a 1 000-query GIST batch -- one walk wavefront per SIMD, nothing to squeeze in
+    // beside -- and every batch that runs alone are faster on the big-tile kernel)
+    const int small_min = q.mlp_small;
+    // (... up to 32 times that: a 1 M-query DEEP batch is twenty rounds of the machine on its own, its projection is not
+    // waiting for room, and the big-tile kernel's 12 % matter again: 43.1 against 41.5 M queries/s)
+    r.small_footprint = (q.in_flight && small_min > 0 && q.nq >= (uint32_t)small_min && (uint64_t)q.nq <= 32ull * (uint64_t)small_min) ? 1 : 0;
+    // a layer that is one round of the machine for the slab kernel (small batches, the GIST shape's 1 000 x 960 -> 1 024 -> 1 024 -> 64:
+    // 117 against 153 us, the 64-neuron last layer alone 15 against 43) takes that; everything else the per-layer kernels of mlp.hip
+    for (int l = 0; l < 3; ++l) {
+        const LayerParams lp = layer_of(q, l, r.small_footprint, nullptr);
+        LayerPick k{};
+        // (batches in flight: only the narrow shape -- 35 KB, 256 threads -- finds room beside the other lanes' walk wavefronts; the
+        // wide one's 103 KB workgroups wait for a CU to drain: GIST 2.27 against 2.58 M queries/s.  Knob value 2 = wide in flight too.)
+        const int slab = q.mlp_slab;
+        if (q.mfma) {
+            r.layer[l] = LayerPath::Mfma;
+            k = mlp_layer_mfma_pick(lp);
+        } else if (!lp.small_footprint && slab && (!q.in_flight || lp.dout <= 64u || slab >= 2) && mlp_slab_wins(lp, q.cus)) {
+            r.layer[l] = LayerPath::Slab;
+            SlabPick sk{};
+            if (mlp_slab_pick(lp, q.cus, 0, &sk)) { k.inst = sk.inst; k.normalize_after = sk.normalize_after; }
+        } else {
+            r.layer[l] = LayerPath::Layer;
+            k = mlp_layer_pick(lp);
+        }
+        plan->add(k.inst);
+        if (k.normalize_after && q.nq) {
+            ProjInstance nrm{};
+            nrm.family = ProjFamily::Normalize;
+            plan->add(nrm);
+        }
+    }
+    return r;
+}
+
+static ProjShape shape_of(const gbnns_index* ix, const float* x, uint32_t xstride, uint32_t nx, bool in_flight, bool mfma) {
+    ProjShape q{};
+    q.d = ix->d; q.dh = ix->d_hidden; q.dl = ix->d_low; q.dl_pad = ix->dl_pad; q.nq = nx; q.xstride = xstride;
+    q.cus = ix->cus; q.in_flight = in_flight; q.mfma = mfma;
+    q.mlp_net = ix->knob.mlp_net; q.mlp_slab = ix->knob.mlp_slab; q.mlp_small = ix->knob.mlp_small;
+    q.x = x;
+    q.w[0] = ix->w1; q.w[1] = ix->w2; q.w[2] = ix->w3;
+    q.ws[0] = ix->ws1; q.ws[1] = ix->ws2; q.ws[2] = ix->ws3;
+    return q;
+}
+
+// MLP over rows x [nx x xstride] (device) -> out [nx x dl_pad] (device); h1/h2 are scratch.
+int run_project(gbnns_index* ix, Lane& L, const float* x, uint32_t xstride, uint32_t nx, float* out,
+                hipStream_t s, bool in_flight, bool mfma) {
+    const ProjShape q = shape_of(ix, x, xstride, nx, in_flight, mfma);
+    const ProjRoute r = project_route(q, nullptr);
+    ProjPlan& ran = ix->proj_last;   // what the launchers report: the instances this projection ran on
+    ran = ProjPlan{};
+    const float* bias[3] = {ix->b1, ix->b2, ix->b3};
+    if (r.path == ProjPath::Net) {
+        NetLaunch n = net_of(q);
+        n.out = out; n.form = r.form;
+        for (int l = 0; l < 3; ++l) { n.bias[l] = bias[l]; n.img[l] = ix->net_img[n.form][l]; }
+        HIP_TRY(launch_mlp_net(n, s, &ran));
+        ix->net_form = n.form;
+        std::snprintf(ix->acc.project_kernel, sizeof(ix->acc.project_kernel), "mlp_net_kernel");
+        return GBNNS_OK;
+    }
+    if (r.path == ProjPath::MfmaNet) {
+        NetLaunch n = net_of(q);
+        n.out = out;
+        for (int l = 0; l < 3; ++l) n.bias[l] = bias[l];
         if (!ix->net_mfma_ready) {
             int rc0 = ix->net_mfma.ensure(mlp_mfma_net_packed_floats(ix->d, ix->d_hidden, ix->d_low) * 4);
             if (rc0) return rc0;
@@ -657,7 +761,7 @@ int run_project(gbnns_index* ix, Lane& L, const float* x, uint32_t xstride, uint
             HIP_TRY(hipStreamSynchronize(s));                                  //  other streams find it finished)
             ix->net_mfma_ready = true;
         }
-        HIP_TRY(launch_mlp_mfma_net(n, ix->net_mfma.as<float>(), s));
+        HIP_TRY(launch_mlp_mfma_net(n, ix->net_mfma.as<float>(), s, &ran));
         std::snprintf(ix->acc.project_kernel, sizeof(ix->acc.project_kernel), "mlp_mfma_net_kernel");
         return GBNNS_OK;
     }
@@ -665,38 +769,17 @@ int run_project(gbnns_index* ix, Lane& L, const float* x, uint32_t xstride, uint
     int rc = L.h1.ensure((size_t)nx * ix->d_hidden * 4);
     if (!rc) rc = L.h2.ensure((size_t)nx * ix->d_hidden * 4);
     if (rc) return rc;
-    LayerParams p{};
-    // batches in flight whose walks fill the machine: the small-footprint kernel for the hidden layers (mlp.hip; sift-like
-    // +2.5 % at ef 64, +3.6 % at ef 36; a 1 000-query GIST batch -- one walk wavefront per SIMD, nothing to squeeze in
-    // beside -- and every batch that runs alone are faster on the big-tile kernel)
-    const int small_min = ix->knob.mlp_small;
-    // (... up to 32 times that: a 1 M-query DEEP batch is twenty rounds of the machine on its own, its projection is not
-    // waiting for room, and the big-tile kernel's 12 % matter again: 43.1 against 41.5 M queries/s)
-    p.small_footprint = (in_flight && small_min > 0 && nx >= (uint32_t)small_min && (uint64_t)nx <= 32ull * (uint64_t)small_min) ? 1 : 0;
-    // a layer that is one round of the machine for the slab kernel (small batches, the GIST shape's 1 000 x 960 -> 1 024 -> 1 024 -> 64:
-    // 117 against 153 us, the 64-neuron last layer alone 15 against 43) takes that; everything else the per-layer kernels of mlp.hip
+    float* act[3] = {L.h1.as<float>(), L.h2.as<float>(), out};
     bool slab_used = false;
-    auto layer = [&](const LayerParams& lp) {
-        if (mfma) return launch_mlp_layer_mfma(lp, s);
-        // (batches in flight: only the narrow shape -- 35 KB, 256 threads -- finds room beside the other lanes' walk wavefronts; the
-        // wide one's 103 KB workgroups wait for a CU to drain: GIST 2.27 against 2.58 M queries/s.  Knob value 2 = wide in flight too.)
-        const int slab = ix->knob.mlp_slab;
-        if (!lp.small_footprint && slab && (!in_flight || lp.dout <= 64u || slab >= 2) && mlp_slab_wins(lp, ix->cus)) {
-            slab_used = true;
-            return launch_mlp_slab(lp, ix->cus, s);
+    for (int l = 0; l < 3; ++l) {
+        LayerParams p = layer_of(q, l, r.small_footprint, l ? act[l - 1] : nullptr);
+        p.bias = bias[l]; p.out = act[l];
+        switch (r.layer[l]) {
+            case LayerPath::Mfma: HIP_TRY(launch_mlp_layer_mfma(p, s, &ran)); break;
+            case LayerPath::Slab: slab_used = true; HIP_TRY(launch_mlp_slab(p, ix->cus, s, 0, &ran)); break;
+            case LayerPath::Layer: HIP_TRY(launch_mlp_layer(p, s, &ran)); break;
         }
-        return launch_mlp_layer(lp, s);
-    };
-    p.x = x; p.xstride = xstride; p.w = ix->w1; p.wstride = ix->ws1; p.bias = ix->b1;
-    p.out = L.h1.as<float>(); p.ostride = ix->d_hidden; p.nq = nx; p.din = ix->d;
-    p.dout = ix->d_hidden; p.relu = 1;
-    HIP_TRY(layer(p));
-    p.x = L.h1.as<float>(); p.xstride = ix->d_hidden; p.w = ix->w2; p.wstride = ix->ws2;
-    p.bias = ix->b2; p.out = L.h2.as<float>(); p.din = ix->d_hidden;
-    HIP_TRY(layer(p));
-    p.x = L.h2.as<float>(); p.w = ix->w3; p.wstride = ix->ws3; p.bias = ix->b3; p.out = out;
-    p.ostride = ix->dl_pad; p.dout = ix->d_low; p.relu = 0; p.normalize = 1;
-    HIP_TRY(layer(p));
+    }
     if (slab_used) std::snprintf(ix->acc.project_kernel, sizeof(ix->acc.project_kernel), "mlp_slab_kernel");
     return GBNNS_OK;
 }
@@ -802,6 +885,41 @@ int gbnns_debug_net_lds(uint32_t d, uint32_t d_hidden, uint32_t d_low, int form,
     n.dout[0] = n.dout[1] = d_hidden; n.dout[2] = d_low;
     *lds_bytes = mlp_net_lds_bytes(n, form, a);
     *admitted = mlp_net_lds_bytes(n, form, 4) <= (form == kNetHalfCu ? 80u : 160u) * 1024u;
+    return GBNNS_OK;
+}
+
+static void plan_names(const ProjPlan& plan, char* names, uint32_t names_bytes) {
+    std::string all;
+    for (int i = 0; i < plan.count; ++i) {
+        char one[64];
+        proj_instance_name(plan.inst[i], one, sizeof one);
+        if (i) all += '\n';
+        all += one;
+    }
+    std::snprintf(names, names_bytes, "%s", all.c_str());
+}
+
+int gbnns_debug_project_plan(uint32_t d, uint32_t d_hidden, uint32_t d_low, uint64_t n_q, int cus, int in_flight, int mfma, int mlp_net,
+                             int mlp_slab, int mlp_small, char* names, uint32_t names_bytes) {
+    if (!names || !names_bytes) return fail(GBNNS_ERR_INVALID, "gbnns_debug_project_plan: no room for the names");
+    if (!d || !d_hidden || !d_low || !n_q || n_q >= (1ull << 31) || cus < 1)
+        return fail(GBNNS_ERR_INVALID, "gbnns_debug_project_plan: no such net, batch or device");
+    if (mlp_net < 0 || mlp_net > 3 || mlp_slab < 0 || mlp_slab > 2 || mlp_small < 0)
+        return fail(GBNNS_ERR_INVALID, "gbnns_debug_project_plan: a knob value outside its range");
+    gbnns_api::ProjShape q{};
+    q.d = d; q.dh = d_hidden; q.dl = d_low; q.dl_pad = round_up(d_low, 4); q.nq = (uint32_t)n_q; q.xstride = d;
+    q.cus = cus; q.in_flight = in_flight != 0; q.mfma = mfma != 0;
+    q.mlp_net = mlp_net; q.mlp_slab = mlp_slab; q.mlp_small = mlp_small;
+    q.ws[0] = round_up(d, 16); q.ws[1] = q.ws[2] = round_up(d_hidden, 16);   // (the handle's repacked rows; x and w stay null: aligned)
+    ProjPlan plan;
+    (void)gbnns_api::project_route(q, &plan);
+    plan_names(plan, names, names_bytes);
+    return GBNNS_OK;
+}
+
+int gbnns_index_project_last(gbnns_index* ix, char* names, uint32_t names_bytes) {
+    if (!ix || !names || !names_bytes) return fail(GBNNS_ERR_INVALID, "gbnns_index_project_last: null argument");
+    plan_names(ix->proj_last, names, names_bytes);
     return GBNNS_OK;
 }
 
@@ -1081,7 +1199,7 @@ int gbnns_index_knob_get(gbnns_index* ix, const char* name, int* out) {
     const struct { const char* n; int v; } all[] = {
         {"quotient", k.quotient}, {"vs_disp", k.vs_disp}, {"max_waves", k.max_waves}, {"spec_min_nq", k.spec_min_nq},
         {"spec_any_form", k.spec_any_form}, {"mlp_small", k.mlp_small}, {"mlp_net", k.mlp_net}, {"mlp_slab", k.mlp_slab},
-        {"late_rows", k.late_rows}, {"spec_tail", k.spec_tail}, {"coop", k.coop}, {"hot", k.hot}, {"byte_query_int", k.byte_query_int}, {"mlp_net_form", ix->net_form},
+        {"late_rows", k.late_rows}, {"spec_tail", k.spec_tail}, {"coop", k.coop}, {"hot", k.hot}, {"byte_query_int", k.byte_query_int}, {"mlp_net_form", ix->net_form}, {"cus", ix->cus},
         {"gather_budget", k.gather_budget}, {"gather_timing", k.gather_timing}, {"gather_census_us", ix->gather_us[0]}, {"gather_fill_us", ix->gather_us[1]},
         {"gather_scan_us", ix->gather_us[2]}, {"gather_rounds", ix->gather_rounds}};
     for (const auto& e : all)

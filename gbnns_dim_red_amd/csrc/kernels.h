@@ -192,9 +192,43 @@ struct LayerParams {
     int32_t normalize;       // 1: follow the layer by normalizeVector over its dout outputs (fused when dout <= 64)
     int32_t small_footprint; // 1: hidden layers on the 60-register / 9 KB kernel (batches in flight: its blocks fit beside walk wavefronts)
 };
-hipError_t launch_mlp_layer(const LayerParams& p, hipStream_t s);
+// Which instance of a projection kernel a launch runs: decided by the *_pick functions below from shapes, strides and pointer ALIGNMENT alone
+// (no device, nothing dereferenced), and every launcher switches on the descriptor its pick returned.  An argument the family does not have stays
+// 0 / false.
+enum class ProjFamily : uint8_t {
+    None,       // nothing to launch (an empty batch or layer), or no instance serves the shape
+    Net,        // mlp_net_kernel<NW, A, BH, B3, GO>              (mlp_net.hip)
+    Slab,       // mlp_slab_kernel<NW, A, RELU, NORM>             (mlp_net.hip)
+    Layer,      // mlp_layer_kernel<RELU, NORM>                   (mlp.hip)
+    LayerVec,   // mlp_layer_vec_kernel<RELU, NORM>
+    LayerSw,    // mlp_layer_sw_kernel<RELU>
+    Narrow,     // mlp_narrow_kernel<RELU, NORM>
+    LayerMfma,  // mlp_layer_mfma_kernel<RELU>
+    MfmaNet,    // mlp_mfma_net_kernel<RB>                        (mlp_mfma_net.hip)
+    Normalize,  // normalize_kernel                               (mlp.hip)
+};
+struct ProjInstance {
+    ProjFamily family;
+    int nw, a, bh, b3, go;   // wavefronts, queries per lane, neurons per lane group (hidden / last layer), neuron groups per row of 16 lanes
+    bool relu, norm;
+    int rb;                  // row blocks of 16 queries per workgroup
+};
+// the instance as the source spells it: "mlp_net_kernel<8, 5, 8, 2, 2>", "mlp_layer_vec_kernel<true, false>", "normalize_kernel"
+void proj_instance_name(const ProjInstance& i, char* out, size_t cap);
+// the launches of one projection, in launch order (at most three layers and a normalize_kernel of its own)
+struct ProjPlan {
+    int count;
+    ProjInstance inst[4];
+    void add(const ProjInstance& i) { if (i.family != ProjFamily::None && count < 4) inst[count++] = i; }
+};
+// a layer's kernel and whether a normalize_kernel launch follows it (normalizeVector not fused)
+struct LayerPick { ProjInstance inst; bool normalize_after; };
+LayerPick mlp_layer_pick(const LayerParams& p);
+LayerPick mlp_layer_mfma_pick(const LayerParams& p);
+// (every launcher adds what it launched to `ran` when given one)
+hipError_t launch_mlp_layer(const LayerParams& p, hipStream_t s, ProjPlan* ran = nullptr);
 // the throughput option (GBNNS_FLAG_MFMA_PROJECTION): the same layer as a v_mfma_f32_32x32x2_f32 GEMM -- NOT bit-exact
-hipError_t launch_mlp_layer_mfma(const LayerParams& p, hipStream_t s);
+hipError_t launch_mlp_layer_mfma(const LayerParams& p, hipStream_t s, ProjPlan* ran = nullptr);
 // The whole three-layer net in one launch (mlp_net.hip): activations stay in LDS, one block per 16 .. 40 queries (8 .. 20 in the
 // half-CU form, which a batch in flight takes: its blocks start on half-drained CUs).  Same
 // arithmetic as three launch_mlp_layer calls (relu, relu, normalize), bit for bit.
@@ -242,21 +276,31 @@ void pack_net_image(const float* w, uint32_t wstride, uint32_t din, uint32_t dou
 bool mlp_net_serves(const NetLaunch& n);   // shape, alignment and batch size fit the one-launch kernel
 bool mlp_net_half_serves(const NetLaunch& n);   // ... and the half-CU form's block (16 queries and more) fits 80 KB of LDS
 size_t mlp_net_lds_bytes(const NetLaunch& n, int form, int A);   // LDS of a block of `form` with A queries per lane (2 .. 5)
-hipError_t launch_mlp_net(const NetLaunch& n, hipStream_t s);
+// the instance of n.form a batch takes (A: the strip that needs the fewest rounds of the machine x A among those whose LDS fits; B3 by d_low)
+// and the LDS layout of its block; false: the kernel, or the form, does not serve the call
+struct NetPick { ProjInstance inst; size_t lds; uint32_t bufa, bufb; };
+bool mlp_net_pick(const NetLaunch& n, NetPick* pick);
+hipError_t launch_mlp_net(const NetLaunch& n, hipStream_t s, ProjPlan* ran = nullptr);
 // The throughput option as ONE launch (mlp_mfma_net.hip): v_mfma_f32_16x16x4_f32, one workgroup per CU over its share of the batch, weights
 // repacked once per handle into the instruction's B-operand order, activations in LDS.  NOT bit-exact.
 bool mlp_mfma_net_serves(uint32_t d, uint32_t d_hidden, uint32_t d_low);
 size_t mlp_mfma_net_packed_floats(uint32_t d, uint32_t d_hidden, uint32_t d_low);
 hipError_t launch_mlp_mfma_pack(const NetLaunch& n, float* packed, hipStream_t s);
-hipError_t launch_mlp_mfma_net(const NetLaunch& n, const float* packed, hipStream_t s);
+// RB = row blocks of 16 queries per workgroup, `rows` = its queries: ceil(nq / CUs), at most what the LDS holds; false: the net does not fit
+struct MfmaNetPick { ProjInstance inst; uint32_t rows; };
+bool mlp_mfma_net_pick(const NetLaunch& n, MfmaNetPick* pick);
+hipError_t launch_mlp_mfma_net(const NetLaunch& n, const float* packed, hipStream_t s, ProjPlan* ran = nullptr);
 // y [nq x stride]: y /= sqrt(L2(y, 0)) over dim (4-lane order, d%4 tail ignored in the norm),
 // pad columns [dim, stride) are written as zero.
-hipError_t launch_normalize(float* y, uint32_t stride, uint32_t dim, uint32_t nq, hipStream_t s);
+hipError_t launch_normalize(float* y, uint32_t stride, uint32_t dim, uint32_t nq, hipStream_t s, ProjPlan* ran = nullptr);
 // One wide layer of a small batch with the one-launch kernel's inner loop (mlp_net.hip, mlp_slab_kernel): 8 A queries x 128 neurons
 // per workgroup, inputs a slab of 256 at a time.
 bool mlp_slab_serves(const LayerParams& p);
 bool mlp_slab_wins(const LayerParams& p, int cus);  // ... and the layer is one round of the machine in its workgroup shape
-hipError_t launch_mlp_slab(const LayerParams& p, int cus, hipStream_t s, int force_a = 0);
+// the workgroup shape (NW, A), the ReLU / normalise variant and the grid of a layer; false: mlp_slab_serves says no
+struct SlabPick { ProjInstance inst; bool normalize_after; uint64_t blocks; unsigned gx, gy; };
+bool mlp_slab_pick(const LayerParams& p, int cus, int force_a, SlabPick* pick);
+hipError_t launch_mlp_slab(const LayerParams& p, int cus, hipStream_t s, int force_a = 0, ProjPlan* ran = nullptr);
 
 // Exact brute-force kNN scan (knn.hip): getTruth (support_func.h:270-290) generalised to k results per query.
 struct KnnParams {

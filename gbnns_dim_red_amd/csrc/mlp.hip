@@ -1,6 +1,7 @@
 // mlp.hip -- the projection (GetLowQueryFromNet / computeNetLayer / normalizeVector, support_func.h:624-658): tiled layer
 // kernels in the reference's 8-sum order, the narrow last layer with the normalise step fused, and two small fill kernels.
 #include <algorithm>
+#include <cstdio>
 
 #include "launch_util.h"
 #include "walk_common.h"
@@ -611,67 +612,123 @@ __global__ void fill_u32_kernel(uint32_t* p, uint32_t v, size_t count) {
 
 }  // namespace
 
-hipError_t launch_mlp_layer(const LayerParams& p, hipStream_t s) {
-    if (p.nq == 0 || p.dout == 0) return hipSuccess;
-    const dim3 grid((p.nq + kTQ - 1) / kTQ, (p.dout + kTO - 1) / kTO);
+static ProjInstance layer_instance(ProjFamily family, bool relu, bool norm) {
+    ProjInstance i{};
+    i.family = family; i.relu = relu; i.norm = norm;
+    return i;
+}
+
+LayerPick mlp_layer_pick(const LayerParams& p) {
+    LayerPick k{};
+    if (p.nq == 0 || p.dout == 0) return k;
     const bool aligned = p.xstride % 4 == 0 && p.wstride % 4 == 0 && (reinterpret_cast<uintptr_t>(p.x) & 15) == 0 &&
                          (reinterpret_cast<uintptr_t>(p.w) & 15) == 0;
     if (aligned && p.dout <= 32u && p.din <= 256u && (!p.normalize || !p.relu)) {
         // narrow layer: whole-K staging, one load phase (the last projection layer)
-        const uint32_t kpad = (p.din + 7u) & ~7u;
-        const size_t lds = std::max<size_t>((size_t)64 * (kpad + 4), (size_t)32 * kNormLd) * sizeof(float);  // tiles, or the rows to normalise
-        const dim3 gn((p.nq + 31) / 32);
-        hipError_t e = hipSuccess;
-        if (p.normalize) {
-            e = set_lds(mlp_narrow_kernel<false, true>, lds);
-            if (e == hipSuccess) hipLaunchKernelGGL((mlp_narrow_kernel<false, true>), gn, dim3(256), lds, s, p);
-        } else if (p.relu) {
-            e = set_lds(mlp_narrow_kernel<true, false>, lds);
-            if (e == hipSuccess) hipLaunchKernelGGL((mlp_narrow_kernel<true, false>), gn, dim3(256), lds, s, p);
-        } else {
-            e = set_lds(mlp_narrow_kernel<false, false>, lds);
-            if (e == hipSuccess) hipLaunchKernelGGL((mlp_narrow_kernel<false, false>), gn, dim3(256), lds, s, p);
-        }
-        return e != hipSuccess ? e : hipGetLastError();
-    }
-    if (p.normalize && !p.relu && p.dout <= (uint32_t)kTO) {  // fused normalizeVector (one block column)
-        if (aligned) hipLaunchKernelGGL((mlp_layer_vec_kernel<false, true>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((mlp_layer_kernel<false, true>), grid, dim3(256), 0, s, p);
-        return hipGetLastError();
-    }
-    if (aligned && p.small_footprint && !p.normalize && p.dout >= 64u) {
-        const dim3 gsw((p.nq + kSwQ - 1) / kSwQ, (p.dout + kSwO - 1) / kSwO);
-        if (p.relu) hipLaunchKernelGGL((mlp_layer_sw_kernel<true>), gsw, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((mlp_layer_sw_kernel<false>), gsw, dim3(256), 0, s, p);
-    } else if (aligned) {
-        if (p.relu) hipLaunchKernelGGL((mlp_layer_vec_kernel<true>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((mlp_layer_vec_kernel<false>), grid, dim3(256), 0, s, p);
+        k.inst = layer_instance(ProjFamily::Narrow, !p.normalize && p.relu, p.normalize);
+    } else if (p.normalize && !p.relu && p.dout <= (uint32_t)kTO) {  // fused normalizeVector (one block column)
+        k.inst = layer_instance(aligned ? ProjFamily::LayerVec : ProjFamily::Layer, false, true);
     } else {
-        if (p.relu) hipLaunchKernelGGL((mlp_layer_kernel<true>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((mlp_layer_kernel<false>), grid, dim3(256), 0, s, p);
+        if (aligned && p.small_footprint && !p.normalize && p.dout >= 64u) k.inst = layer_instance(ProjFamily::LayerSw, p.relu, false);
+        else k.inst = layer_instance(aligned ? ProjFamily::LayerVec : ProjFamily::Layer, p.relu, false);
+        k.normalize_after = p.normalize;
     }
-    if (p.normalize) {
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        return launch_normalize(p.out, p.ostride, p.dout, p.nq, s);
-    }
-    return hipGetLastError();
+    return k;
 }
 
-hipError_t launch_mlp_layer_mfma(const LayerParams& p, hipStream_t s) {
-    if (p.nq == 0 || p.dout == 0) return hipSuccess;
+LayerPick mlp_layer_mfma_pick(const LayerParams& p) {
+    LayerPick k{};
+    if (p.nq == 0 || p.dout == 0) return k;
+    k.inst = layer_instance(ProjFamily::LayerMfma, p.relu, false);
+    k.normalize_after = p.normalize;
+    return k;
+}
+
+hipError_t launch_mlp_layer(const LayerParams& p, hipStream_t s, ProjPlan* ran) {
+    const LayerPick k = mlp_layer_pick(p);
+    const ProjInstance& i = k.inst;
+    if (i.family == ProjFamily::None) return hipSuccess;
+    const dim3 grid((p.nq + kTQ - 1) / kTQ, (p.dout + kTO - 1) / kTO);
+    hipError_t e = hipSuccess;
+    switch (i.family) {
+        case ProjFamily::Narrow: {
+            const uint32_t kpad = (p.din + 7u) & ~7u;
+            const size_t lds = std::max<size_t>((size_t)64 * (kpad + 4), (size_t)32 * kNormLd) * sizeof(float);  // tiles, or the rows to normalise
+            const dim3 gn((p.nq + 31) / 32);
+            if (i.norm) {
+                e = set_lds(mlp_narrow_kernel<false, true>, lds);
+                if (e == hipSuccess) hipLaunchKernelGGL((mlp_narrow_kernel<false, true>), gn, dim3(256), lds, s, p);
+            } else if (i.relu) {
+                e = set_lds(mlp_narrow_kernel<true, false>, lds);
+                if (e == hipSuccess) hipLaunchKernelGGL((mlp_narrow_kernel<true, false>), gn, dim3(256), lds, s, p);
+            } else {
+                e = set_lds(mlp_narrow_kernel<false, false>, lds);
+                if (e == hipSuccess) hipLaunchKernelGGL((mlp_narrow_kernel<false, false>), gn, dim3(256), lds, s, p);
+            }
+            break;
+        }
+        case ProjFamily::LayerSw: {
+            const dim3 gsw((p.nq + kSwQ - 1) / kSwQ, (p.dout + kSwO - 1) / kSwO);
+            if (i.relu) hipLaunchKernelGGL((mlp_layer_sw_kernel<true>), gsw, dim3(256), 0, s, p);
+            else hipLaunchKernelGGL((mlp_layer_sw_kernel<false>), gsw, dim3(256), 0, s, p);
+            break;
+        }
+        case ProjFamily::LayerVec:
+            if (i.norm) hipLaunchKernelGGL((mlp_layer_vec_kernel<false, true>), grid, dim3(256), 0, s, p);
+            else if (i.relu) hipLaunchKernelGGL((mlp_layer_vec_kernel<true>), grid, dim3(256), 0, s, p);
+            else hipLaunchKernelGGL((mlp_layer_vec_kernel<false>), grid, dim3(256), 0, s, p);
+            break;
+        case ProjFamily::Layer:
+            if (i.norm) hipLaunchKernelGGL((mlp_layer_kernel<false, true>), grid, dim3(256), 0, s, p);
+            else if (i.relu) hipLaunchKernelGGL((mlp_layer_kernel<true>), grid, dim3(256), 0, s, p);
+            else hipLaunchKernelGGL((mlp_layer_kernel<false>), grid, dim3(256), 0, s, p);
+            break;
+        default:
+            return hipErrorInvalidValue;
+    }
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (ran) ran->add(i);
+    return k.normalize_after ? launch_normalize(p.out, p.ostride, p.dout, p.nq, s, ran) : hipSuccess;
+}
+
+hipError_t launch_mlp_layer_mfma(const LayerParams& p, hipStream_t s, ProjPlan* ran) {
+    const LayerPick k = mlp_layer_mfma_pick(p);
+    if (k.inst.family == ProjFamily::None) return hipSuccess;
     const dim3 grid((p.nq + kMQ - 1) / kMQ, (p.dout + kMO - 1) / kMO);
-    if (p.relu) hipLaunchKernelGGL((mlp_layer_mfma_kernel<true>), grid, dim3(256), 0, s, p);
+    if (k.inst.relu) hipLaunchKernelGGL((mlp_layer_mfma_kernel<true>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((mlp_layer_mfma_kernel<false>), grid, dim3(256), 0, s, p);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess || !p.normalize) return e;
-    return launch_normalize(p.out, p.ostride, p.dout, p.nq, s);  // (the exact normalise step on the approximate outputs)
+    if (e != hipSuccess) return e;
+    if (ran) ran->add(k.inst);
+    if (!k.normalize_after) return e;
+    return launch_normalize(p.out, p.ostride, p.dout, p.nq, s, ran);  // (the exact normalise step on the approximate outputs)
 }
 
-hipError_t launch_normalize(float* y, uint32_t stride, uint32_t dim, uint32_t nq, hipStream_t s) {
+hipError_t launch_normalize(float* y, uint32_t stride, uint32_t dim, uint32_t nq, hipStream_t s, ProjPlan* ran) {
     if (nq == 0) return hipSuccess;
     hipLaunchKernelGGL(normalize_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, y, stride, dim, nq);
-    return hipGetLastError();
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess && ran) ran->add(layer_instance(ProjFamily::Normalize, false, false));
+    return e;
+}
+
+void proj_instance_name(const ProjInstance& i, char* out, size_t cap) {
+    if (!out || !cap) return;
+    const char* relu = i.relu ? "true" : "false";
+    const char* norm = i.norm ? "true" : "false";
+    switch (i.family) {
+        case ProjFamily::Net: std::snprintf(out, cap, "mlp_net_kernel<%d, %d, %d, %d, %d>", i.nw, i.a, i.bh, i.b3, i.go); break;
+        case ProjFamily::Slab: std::snprintf(out, cap, "mlp_slab_kernel<%d, %d, %s, %s>", i.nw, i.a, relu, norm); break;
+        case ProjFamily::Layer: std::snprintf(out, cap, "mlp_layer_kernel<%s, %s>", relu, norm); break;
+        case ProjFamily::LayerVec: std::snprintf(out, cap, "mlp_layer_vec_kernel<%s, %s>", relu, norm); break;
+        case ProjFamily::LayerSw: std::snprintf(out, cap, "mlp_layer_sw_kernel<%s>", relu); break;
+        case ProjFamily::Narrow: std::snprintf(out, cap, "mlp_narrow_kernel<%s, %s>", relu, norm); break;
+        case ProjFamily::LayerMfma: std::snprintf(out, cap, "mlp_layer_mfma_kernel<%s>", relu); break;
+        case ProjFamily::MfmaNet: std::snprintf(out, cap, "mlp_mfma_net_kernel<%d>", i.rb); break;
+        case ProjFamily::Normalize: std::snprintf(out, cap, "normalize_kernel"); break;
+        case ProjFamily::None: out[0] = 0; break;
+    }
 }
 
 hipError_t launch_fill_u32(uint32_t* p, uint32_t v, size_t count, hipStream_t s) {

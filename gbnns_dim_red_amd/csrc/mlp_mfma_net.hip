@@ -342,16 +342,28 @@ hipError_t launch_mlp_mfma_pack(const NetLaunch& n, float* packed, hipStream_t s
 }
 // One workgroup per CU where the batch allows: ceil(nq / CUs) queries each, in as many row blocks of 16 as that takes -- at most what the
 // LDS holds (then more workgroups than CUs).  GBNNS_MFMA_ROWS=<n> forces the queries per workgroup (A/B runs).
-hipError_t launch_mlp_mfma_net(const NetLaunch& n, const float* packed, hipStream_t s) {
-    if (n.nq == 0) return hipSuccess;
+bool mlp_mfma_net_pick(const NetLaunch& n, MfmaNetPick* pick) {
     const int cap = max_rb(n.din[0], n.dout[0], n.dout[2]);
-    if (cap <= 0) return hipErrorInvalidValue;
+    if (cap <= 0) return false;
     const uint32_t cus = (uint32_t)(n.cus > 0 ? n.cus : 256);
     static const uint32_t forced = getenv("GBNNS_MFMA_ROWS") ? (uint32_t)atoi(getenv("GBNNS_MFMA_ROWS")) : 0u;
     uint32_t rows = forced ? forced : (n.nq + cus - 1u) / cus;
     rows = std::max(1u, std::min(rows, 16u * (uint32_t)cap));
-    const int rb = (int)((rows + 15u) / 16u);
-    return rb == 1 ? launch_t<1>(n, packed, rows, s) : (rb == 2 ? launch_t<2>(n, packed, rows, s) : launch_t<3>(n, packed, rows, s));
+    pick->rows = rows;
+    pick->inst = ProjInstance{};
+    pick->inst.family = ProjFamily::MfmaNet;
+    pick->inst.rb = (int)((rows + 15u) / 16u);
+    return true;
+}
+
+hipError_t launch_mlp_mfma_net(const NetLaunch& n, const float* packed, hipStream_t s, ProjPlan* ran) {
+    if (n.nq == 0) return hipSuccess;
+    MfmaNetPick k{};
+    if (!mlp_mfma_net_pick(n, &k)) return hipErrorInvalidValue;
+    const int rb = k.inst.rb;
+    const hipError_t e = rb == 1 ? launch_t<1>(n, packed, k.rows, s) : (rb == 2 ? launch_t<2>(n, packed, k.rows, s) : launch_t<3>(n, packed, k.rows, s));
+    if (e == hipSuccess && ran) ran->add(k.inst);
+    return e;
 }
 
 }  // namespace gbnns

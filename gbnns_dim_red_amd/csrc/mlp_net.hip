@@ -767,13 +767,10 @@ static hipError_t net_launch_a(const NetParams& p, int A, int b3, size_t lds, hi
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_mlp_net(const NetLaunch& n, hipStream_t s) {
-    if (n.nq == 0) return hipSuccess;
-    if (!mlp_net_serves(n)) return hipErrorInvalidValue;
+bool mlp_net_pick(const NetLaunch& n, NetPick* pick) {
+    if (!mlp_net_serves(n)) return false;
     const bool half = n.form == kNetHalfCu;
-    if (half && !mlp_net_half_serves(n)) return hipErrorInvalidValue;
-    for (int l = 0; l < 3; ++l)   // the weights come from the staged-order image of the form alone
-        if (!n.img[l] || (reinterpret_cast<uintptr_t>(n.img[l]) & 15u)) return hipErrorInvalidValue;
+    if (half && !mlp_net_half_serves(n)) return false;
     // whole-CU form: 8 wavefronts x 8 neurons x 2 groups (blocks of 16 wavefronts x 8 neurons and of 4 x 16 were measured too: DESIGN.md 5.3)
     constexpr int bh = 8;
     const int nw = half ? 4 : 8;
@@ -784,7 +781,6 @@ hipError_t launch_mlp_net(const NetLaunch& n, hipStream_t s) {
     const uint64_t slots = (uint64_t)(n.cus > 0 ? n.cus : 256) * (half ? 2u : 1u);
     int bestA = 0;
     uint64_t best = ~0ull;
-    NetParams p{};
     for (int A = 5; A >= 2; --A) {
         uint32_t ba, bb;
         if (net_lds_bytes(n, A, nw, bh, gq, &ba, &bb) > lds_max) continue;
@@ -793,18 +789,33 @@ hipError_t launch_mlp_net(const NetLaunch& n, hipStream_t s) {
         const uint64_t cost = ((blocks + slots - 1) / slots) * A;
         if (cost < best) { best = cost; bestA = A; }
     }
-    if (!bestA) return hipErrorInvalidValue;
-    size_t lds = net_lds_bytes(n, bestA, nw, bh, gq, &p.bufa, &p.bufb);
+    if (!bestA) return false;
+    pick->lds = net_lds_bytes(n, bestA, nw, bh, gq, &pick->bufa, &pick->bufb);
     // (diagnostic: a larger request -- more than half a CU's keeps the half-CU blocks one per CU)
-    if (n.lds_floor > lds && n.lds_floor <= 160u * 1024u) lds = n.lds_floor;
+    if (n.lds_floor > pick->lds && n.lds_floor <= 160u * 1024u) pick->lds = n.lds_floor;
+    // neurons per lane group in the last layer: a pass covers 16 B3 neurons (NW x 2 B3, NW x 4 B3 in the half-CU form)
+    const uint32_t per = (n.dout[2] + 15u) / 16u;
+    pick->inst = ProjInstance{};
+    pick->inst.family = ProjFamily::Net;
+    pick->inst.nw = nw; pick->inst.a = bestA; pick->inst.bh = bh; pick->inst.b3 = per <= 2 ? 2 : 4; pick->inst.go = half ? 4 : 2;
+    return true;
+}
+
+hipError_t launch_mlp_net(const NetLaunch& n, hipStream_t s, ProjPlan* ran) {
+    if (n.nq == 0) return hipSuccess;
+    NetPick k{};
+    if (!mlp_net_pick(n, &k)) return hipErrorInvalidValue;
+    for (int l = 0; l < 3; ++l)   // the weights come from the staged-order image of the form alone
+        if (!n.img[l] || (reinterpret_cast<uintptr_t>(n.img[l]) & 15u)) return hipErrorInvalidValue;
+    NetParams p{};
+    p.bufa = k.bufa; p.bufb = k.bufb;
     p.x = n.x; p.xstride = n.xstride; p.nq = n.nq; p.out = n.out; p.ostride = n.ostride; p.stamps = n.stamps;
     for (int l = 0; l < 3; ++l) {
         p.img[l] = n.img[l]; p.bias[l] = n.bias[l]; p.din[l] = n.din[l]; p.dout[l] = n.dout[l];
     }
-    // neurons per lane group in the last layer: a pass covers 16 B3 neurons (NW x 2 B3, NW x 4 B3 in the half-CU form)
-    const uint32_t per = (n.dout[2] + 15u) / 16u;
-    const int b3 = per <= 2 ? 2 : 4;
-    return half ? net_launch_a<4, 8, 4>(p, bestA, b3, lds, s) : net_launch_a<8, 8, 2>(p, bestA, b3, lds, s);
+    const hipError_t e = k.inst.go == 4 ? net_launch_a<4, 8, 4>(p, k.inst.a, k.inst.b3, k.lds, s) : net_launch_a<8, 8, 2>(p, k.inst.a, k.inst.b3, k.lds, s);
+    if (e == hipSuccess && ran) ran->add(k.inst);
+    return e;
 }
 
 bool mlp_slab_serves(const LayerParams& p) {
@@ -813,16 +824,17 @@ bool mlp_slab_serves(const LayerParams& p) {
 }
 
 template <int NW, int A>
-static hipError_t slab_launch(const SlabParams& sp, unsigned gx, unsigned gy, size_t lds, bool norm, hipStream_t s) {
+static hipError_t slab_launch(const SlabParams& sp, unsigned gx, unsigned gy, size_t lds, const ProjInstance& i, hipStream_t s) {
     hipError_t e;
     if constexpr (NW <= 4) {
-        if (norm) {  // (the last layer: no ReLU)
+        if (i.norm) {  // (the last layer: no ReLU)
             if ((e = set_lds(mlp_slab_kernel<NW, A, false, true>, lds)) != hipSuccess) return e;
             hipLaunchKernelGGL((mlp_slab_kernel<NW, A, false, true>), dim3(gx, gy), dim3(NW * 64), lds, s, sp);
             return hipGetLastError();
         }
     }
-    if (sp.l.relu) {
+    if (i.norm) return hipErrorInvalidValue;
+    if (i.relu) {
         if ((e = set_lds(mlp_slab_kernel<NW, A, true, false>, lds)) != hipSuccess) return e;
         hipLaunchKernelGGL((mlp_slab_kernel<NW, A, true, false>), dim3(gx, gy), dim3(NW * 64), lds, s, sp);
     } else {
@@ -849,43 +861,55 @@ static void slab_shape(const LayerParams& p, int cus, int force_a, int& nw, int&
     }
 }
 
-// (measured, tools/ubench/mlp_lab MLP_LAB_SLAB=1: it wins where the layer is one round of the machine -- 1 000 x 960 -> 1 024 50.7
-// against 59.2 us, 1 000 x 200 -> 256 9.0 / 11.0 -- and loses beyond: 4 000 x 1 024 -> 1 024 201 / 183, 10 000 x 512 -> 512 123 / 119)
-bool mlp_slab_wins(const LayerParams& p, int cus) {
+bool mlp_slab_pick(const LayerParams& p, int cus, int force_a, SlabPick* pick) {
     if (!mlp_slab_serves(p)) return false;
-    if (cus <= 0) cus = 256;
-    int nw, a;
-    uint64_t blocks = 0;
-    slab_shape(p, cus, 0, nw, a, blocks);
-    return blocks <= (uint64_t)cus && p.din >= 64u;
-}
-
-hipError_t launch_mlp_slab(const LayerParams& p, int cus, hipStream_t s, int force_a) {
-    if (!mlp_slab_serves(p)) return hipErrorInvalidValue;
     if (cus <= 0) cus = 256;
     int nw, bestA;
     uint64_t blocks = 0;
     slab_shape(p, cus, force_a, nw, bestA, blocks);
+    pick->blocks = blocks;
+    pick->gx = (p.nq + 8u * bestA - 1u) / (8u * bestA);
+    pick->gy = (p.dout + 16u * nw - 1u) / (16u * nw);
+    // normalizeVector inside the launch when a workgroup holds all the outputs of its queries (and the layer has no ReLU)
+    const bool norm = p.normalize && !p.relu && pick->gy == 1 && nw <= 4;
+    pick->inst = ProjInstance{};
+    pick->inst.family = ProjFamily::Slab;
+    pick->inst.nw = nw; pick->inst.a = bestA; pick->inst.norm = norm; pick->inst.relu = !norm && p.relu;
+    pick->normalize_after = p.normalize && !norm;
+    return true;
+}
+
+// (measured, tools/ubench/mlp_lab MLP_LAB_SLAB=1: it wins where the layer is one round of the machine -- 1 000 x 960 -> 1 024 50.7
+// against 59.2 us, 1 000 x 200 -> 256 9.0 / 11.0 -- and loses beyond: 4 000 x 1 024 -> 1 024 201 / 183, 10 000 x 512 -> 512 123 / 119)
+bool mlp_slab_wins(const LayerParams& p, int cus) {
+    SlabPick k{};
+    if (!mlp_slab_pick(p, cus, 0, &k)) return false;
+    if (cus <= 0) cus = 256;
+    return k.blocks <= (uint64_t)cus && p.din >= 64u;
+}
+
+hipError_t launch_mlp_slab(const LayerParams& p, int cus, hipStream_t s, int force_a, ProjPlan* ran) {
+    SlabPick k{};
+    if (!mlp_slab_pick(p, cus, force_a, &k)) return hipErrorInvalidValue;
+    const int nw = k.inst.nw, bestA = k.inst.a;
     SlabParams sp{};
     sp.l = p;
     sp.sg = net_gstride(kSlabK, bestA);
     const size_t lds = ((size_t)2 * 8 * sp.sg + (size_t)nw * 2 * NetGeom<8>::BUF) * sizeof(float);
-    const unsigned gx = (p.nq + 8u * bestA - 1u) / (8u * bestA), gy = (p.dout + 16u * nw - 1u) / (16u * nw);
-    // normalizeVector inside the launch when a workgroup holds all the outputs of its queries (and the layer has no ReLU)
-    const bool norm = p.normalize && !p.relu && gy == 1 && nw <= 4;
     hipError_t e = hipErrorInvalidValue;
     switch (nw * 8 + bestA) {
-        case 8 * 8 + 2: e = slab_launch<8, 2>(sp, gx, gy, lds, norm, s); break;
-        case 8 * 8 + 3: e = slab_launch<8, 3>(sp, gx, gy, lds, norm, s); break;
-        case 8 * 8 + 4: e = slab_launch<8, 4>(sp, gx, gy, lds, norm, s); break;
-        case 8 * 8 + 5: e = slab_launch<8, 5>(sp, gx, gy, lds, norm, s); break;
-        case 4 * 8 + 1: e = slab_launch<4, 1>(sp, gx, gy, lds, norm, s); break;
-        case 4 * 8 + 2: e = slab_launch<4, 2>(sp, gx, gy, lds, norm, s); break;
-        case 2 * 8 + 1: e = slab_launch<2, 1>(sp, gx, gy, lds, norm, s); break;
-        case 2 * 8 + 2: e = slab_launch<2, 2>(sp, gx, gy, lds, norm, s); break;
+        case 8 * 8 + 2: e = slab_launch<8, 2>(sp, k.gx, k.gy, lds, k.inst, s); break;
+        case 8 * 8 + 3: e = slab_launch<8, 3>(sp, k.gx, k.gy, lds, k.inst, s); break;
+        case 8 * 8 + 4: e = slab_launch<8, 4>(sp, k.gx, k.gy, lds, k.inst, s); break;
+        case 8 * 8 + 5: e = slab_launch<8, 5>(sp, k.gx, k.gy, lds, k.inst, s); break;
+        case 4 * 8 + 1: e = slab_launch<4, 1>(sp, k.gx, k.gy, lds, k.inst, s); break;
+        case 4 * 8 + 2: e = slab_launch<4, 2>(sp, k.gx, k.gy, lds, k.inst, s); break;
+        case 2 * 8 + 1: e = slab_launch<2, 1>(sp, k.gx, k.gy, lds, k.inst, s); break;
+        case 2 * 8 + 2: e = slab_launch<2, 2>(sp, k.gx, k.gy, lds, k.inst, s); break;
     }
-    if (e != hipSuccess || !p.normalize || norm) return e;
-    return launch_normalize(p.out, p.ostride, p.dout, p.nq, s);
+    if (e == hipSuccess && ran) ran->add(k.inst);
+    if (e != hipSuccess || !k.normalize_after) return e;
+    return launch_normalize(p.out, p.ostride, p.dout, p.nq, s, ran);
 }
 
 }  // namespace gbnns

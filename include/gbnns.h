@@ -485,7 +485,8 @@ int gbnns_profile_enable(gbnns_index* index, int on);
  * whole CU (8 wavefronts) and of half a CU (4 wavefronts, at most 80 KB of LDS: nets up to 256 hidden units or so), which a
  * batch in flight (GBNNS_FLAG_DEFER_JOIN) takes where it fits -- its workgroups start on CUs the other batches' walks have half
  * left.  2 = always the whole-CU form, 3 = the half-CU form wherever it fits.  "mlp_net_form" (gbnns_index_knob_get only): the
- * form of the handle's last one-launch projection, 0 whole-CU, 1 half-CU, -1 none yet.
+ * form of the handle's last one-launch projection, 0 whole-CU, 1 half-CU, -1 none yet.  "cus" (gbnns_index_knob_get only): the
+ * compute units of the handle's device, which the projection's launch rules count rounds of the machine in.
  * "mlp_slab": 1 (default) = a projection layer that is one round of the machine for mlp_slab_kernel (small batches; the GIST
  * shape's 1 000 queries through 960 -> 1 024 -> 1 024 -> 64) takes it, 0 = never; identical outputs either way (GBNNS_MLP_SLAB).
  * "late_rows": the wide-row instances that have both forms (walk_reg_wide_kernel: 192- / 256-byte rows at ef <= 64; the two-list kernel
@@ -548,6 +549,19 @@ int gbnns_debug_byte_query_plan(int metric, uint32_t dim, uint64_t n, uint32_t e
  * the whole-CU form (form 0) or the half-CU form (form 1), with a queries per lane (2 .. 5), and whether that form takes the net at all
  * (*admitted: a workgroup with a = 4 fits 160 KB / 80 KB). */
 int gbnns_debug_net_lds(uint32_t d, uint32_t d_hidden, uint32_t d_low, int form, int a, uint64_t* lds_bytes, int* admitted);
+/* Diagnostic, no device needed: the kernel instances the projection of a batch launches, in launch order -- what run_project decides for a
+ * net d -> d_hidden -> d_hidden -> d_low, n_q queries, a device of `cus` compute units, a call in flight (GBNNS_FLAG_DEFER_JOIN, on a lane
+ * stream) or not, GBNNS_FLAG_MFMA_PROJECTION or not, and the handle knobs "mlp_net" / "mlp_slab" / "mlp_small".  Buffers count as 16-byte
+ * aligned, as the handle's are.  `names` receives the instances separated by '\n', template arguments as in the source --
+ * "mlp_net_kernel<8, 5, 8, 2, 2>", "mlp_slab_kernel<2, 2, false, true>", "mlp_layer_vec_kernel<true, false>", "mlp_mfma_net_kernel<3>",
+ * "normalize_kernel" (a launch of its own where normalizeVector is not fused) --, cut short and terminated when the buffer is too small.
+ * The same pick functions the launchers switch on compute it.  GBNNS_ERR_INVALID: a null or empty buffer, a zero dimension or batch,
+ * n_q >= 2^31, cus < 1, a knob value outside its range. */
+int gbnns_debug_project_plan(uint32_t d, uint32_t d_hidden, uint32_t d_low, uint64_t n_q, int cus, int in_flight, int mfma, int mlp_net,
+                             int mlp_slab, int mlp_small, char* names, uint32_t names_bytes);
+/* The instances the handle's last projection (a GBNNS_MODE_NET search, gbnns_project) actually launched, as its launchers reported them:
+ * same format; the empty string before the first one.  The knob "cus" (gbnns_index_knob_get only) is the compute-unit count the handle plans with. */
+int gbnns_index_project_last(gbnns_index* index, char* names, uint32_t names_bytes);
 
 /* hnswlikeGD (support_func.h:521-575, need_const_degree = false) + addReverseEdgesForGD
  * (:402-445): prunes a kNN graph (CSR, host) over `ds` [n x d] (host) into the search graph, as
