@@ -48,6 +48,7 @@ SYMBOLS = [
     "gbnns_debug_knn_plan", "gbnns_debug_census_slot",
     "gbnns_index_exact_knn_gather", "gbnns_debug_gather_plan", "gbnns_debug_gather_schedule",
     "gbnns_debug_project_plan", "gbnns_index_project_last",
+    "gbnns_index_order_last", "gbnns_debug_query_order",
 ]
 
 
@@ -176,6 +177,9 @@ def load_library():
         lib.gbnns_debug_project_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                  C.c_char_p, C.c_uint32]
         lib.gbnns_index_project_last.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32]
+    if hasattr(lib, "gbnns_index_order_last"):
+        lib.gbnns_index_order_last.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        lib.gbnns_debug_query_order.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p]
     lib.gbnns_multi_last_error.restype = C.c_char_p
     lib.gbnns_multi_create.argtypes = [C.POINTER(_IndexDesc), C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
     lib.gbnns_multi_destroy.argtypes = [C.c_void_p]
@@ -422,6 +426,25 @@ def gather_schedule(words, allowed, n, budget=None, W=128):
     _check(load_library().gbnns_debug_gather_schedule(words.ctypes.data, allowed.ctypes.data, nq, n, max(GATHER_BUDGET, n) if budget is None else budget,
                                                       W, order.ctypes.data, round_of.ctypes.data, off.ctypes.data, C.byref(rounds), C.byref(wgs)))
     return {"order": order, "round_of": round_of, "list_offset_of": off, "rounds": int(rounds.value), "workgroups": int(wgs.value)}
+
+
+def knob_default(name):
+    """gbnns_index_knob_get without a handle (no device needed): the process-wide default of "order_min" / "order_bits", what a handle
+    created now would start from."""
+    v = C.c_int(0)
+    _check(load_library().gbnns_index_knob_get(None, name.encode() if isinstance(name, str) else name, C.byref(v)))
+    return v.value
+
+
+def query_order(queries, bits=12, dim=None):
+    """gbnns_debug_query_order: the locality order of host queries [nq x qstride] (float32, C order) on the sign bits of their first `bits`
+    coordinates (clamped to 10 .. 16), sorted on the current device; dim: the coordinates a row holds (default: all of them, qstride = dim).
+    A permutation of 0 .. nq-1 with non-decreasing keys."""
+    queries = _host(queries, np.float32)
+    nq, qstride = int(queries.shape[0]), int(queries.shape[1])
+    order = np.empty(nq, np.uint32)
+    _check(load_library().gbnns_debug_query_order(queries.ctypes.data, qstride, qstride if dim is None else int(dim), nq, int(bits), order.ctypes.data))
+    return order
 
 
 def census_slot(word, n_q):
@@ -1113,6 +1136,17 @@ class Index:
         names = C.create_string_buffer(512)
         _check(self._lib.gbnns_index_project_last(self._h, names, 512))
         return tuple(names.value.decode().split("\n")) if names.value else ()
+
+    def order_last(self):
+        """gbnns_index_order_last: the permutation the handle's last ordered search call walked its batch in (knobs "order_min" /
+        "order_bits"; knob_get("order_last") tells whether the very last call was one), read once the device's work has completed."""
+        n = C.c_uint64(0)
+        rc = self._lib.gbnns_index_order_last(self._h, None, 0, C.byref(n))   # (the size first: refused, with n set)
+        if n.value == 0:
+            _check(rc)   # no ordered call yet
+        order = np.empty(n.value, np.uint32)
+        _check(self._lib.gbnns_index_order_last(self._h, order.ctypes.data, order.shape[0], C.byref(n)))
+        return order
 
     def profile_read(self, reset=True):
         p = Profile()

@@ -167,7 +167,7 @@ struct Lane {
 // starts from, so a test or an A/B run that flips one no longer changes every other handle of the process.  The three knobs of
 // gbnns_exact_knn -- a function without a handle -- stay process-wide.
 struct Knobs {
-    int quotient, vs_disp, max_waves, spec_min_nq, spec_any_form, mlp_small, mlp_net, mlp_slab, late_rows, spec_tail, coop, hot, byte_query_int, gather_budget, gather_timing;
+    int quotient, vs_disp, max_waves, spec_min_nq, spec_any_form, mlp_small, mlp_net, mlp_slab, late_rows, spec_tail, coop, hot, byte_query_int, gather_budget, gather_timing, order_min, order_bits;
 };
 Knobs knob_defaults();                                    // the process-wide defaults as they stand now
 bool knob_set(Knobs& k, const char* name, int value);     // clamps like the environment does; false = no such handle knob
@@ -233,6 +233,10 @@ struct gbnns_index {
     hipStream_t last_stream = nullptr;
     bool in_flight = false;
     hipEvent_t order_ev = nullptr;
+    // locality order (search_core.cpp; knobs "order_min" / "order_bits"): queries the last search call walked in it (0: none -- the knob
+    // "order_last"), and the lane and batch size of the last call that was ordered (gbnns_index_order_last reads that lane's permutation)
+    uint32_t order_last = 0, order_perm_n = 0;
+    int order_perm_lane = -1;
     // gbnns_index_exact_knn_gather with the knob "gather_timing": the last call's census / fill / scan microseconds and its rounds (gbnns_index_knob_get)
     int gather_us[3] = {0, 0, 0};
     int gather_rounds = 0;

@@ -293,6 +293,11 @@ int build_ell(const uint64_t* off, const uint32_t* nbr, uint64_t n, std::vector<
 //                   gbnns_index_knob_get: "gather_census_us", "gather_fill_us", "gather_scan_us", "gather_rounds" (tools/exact_gather_timing.py)
 //   "coop"          the two-wavefront walk for small batches (walk_coop.hip): -1 = where it serves and the batch leaves the room
 //                   (default), 0 = never, 1 = wherever the shape allows (tests, A/B runs; GBNNS_COOP)
+//   "order_min"     smallest batch of a NET / LOWQ search over at least 16 walked coordinates that is walked in locality order
+//                   (search_core.cpp, gd_order.hip); 0 = never, negative values count as 0 (GBNNS_ORDER_MIN; default 32 768)
+//   "order_bits"    width of that order's key, the sign bits of the first coordinates: 10 .. 16, clamped (GBNNS_ORDER_BITS; default 12)
+//   "order_last"    (read only) queries the handle's last search call walked in locality order: its batch size, or 0 when it was not
+//                   ordered; gbnns_index_order_last copies the permutation of the last call that was
 // Process-wide only (gbnns_exact_knn has no handle):
 //   "hot"            0 = the generic register-list / two-list instances also where the plan has a walk_hot* / walk_reg_wide instance
 //                    (GBNNS_HOT; A/B runs: the instance family a tagged call's kernels are built from, untagged)
@@ -325,6 +330,8 @@ bool knob_set(Knobs& k, const char* name, int value) {
     else if (!std::strcmp(name, "byte_query_int")) k.byte_query_int = std::max(0, std::min(7, value));
     else if (!std::strcmp(name, "gather_budget")) k.gather_budget = std::max(1, value);
     else if (!std::strcmp(name, "gather_timing")) k.gather_timing = value != 0;
+    else if (!std::strcmp(name, "order_min")) k.order_min = std::max(0, value);
+    else if (!std::strcmp(name, "order_bits")) k.order_bits = std::max(10, std::min(16, value));
     else return false;
     return true;
 }
@@ -347,6 +354,8 @@ static Knobs& knob_default_ref() {  // (function-local: initialised on first use
         knob_set(k, "byte_query_int", knob_env("GBNNS_BYTE_QUERY_INT", kByteQueryIntDefault));
         knob_set(k, "gather_budget", knob_env("GBNNS_GATHER_BUDGET", 1 << 26));
         knob_set(k, "gather_timing", 0);
+        knob_set(k, "order_min", knob_env("GBNNS_ORDER_MIN", 32768));
+        knob_set(k, "order_bits", knob_env("GBNNS_ORDER_BITS", 12));
         return k;
     }();
     return d;
@@ -923,6 +932,40 @@ int gbnns_index_project_last(gbnns_index* ix, char* names, uint32_t names_bytes)
     return GBNNS_OK;
 }
 
+// The locality order of host queries [n_q x qstride] on their first `bits` coordinates (clamped to 10 .. 16): launch_query_order alone, on
+// the current device, its histogram and order buffers this call's own.  The launcher's refusal (dim < bits after clamping) is the call's.
+int gbnns_debug_query_order(const float* queries, uint32_t qstride, uint32_t dim, uint64_t n_q, int bits, uint32_t* out_order) {
+    if (!queries || !out_order) return fail(GBNNS_ERR_INVALID, "gbnns_debug_query_order: null argument");
+    if (!dim || qstride < dim || !n_q || n_q >= (1ull << 31) || bits < 0)
+        return fail(GBNNS_ERR_INVALID, "gbnns_debug_query_order: no such batch");
+    const size_t qbytes = (size_t)n_q * qstride * 4, obytes = (size_t)n_q * 4;
+    ScopedDevBuf q, hist, order;
+    int rc;
+    // (order: room for 2 n_q entries -- a scatter whose cursors start too high, by up to a bucket's size, still writes inside the buffer;
+    // all ones first: a slot the scatter leaves out is no valid query)
+    if ((rc = q.ensure(qbytes)) || (rc = hist.ensure((size_t)4 << 16)) || (rc = order.ensure(2 * obytes))) return rc;
+    if ((rc = h2d_staged(q.p, queries, qbytes))) return rc;
+    HIP_TRY(hipMemset(order.p, 0xFF, 2 * obytes));
+    HIP_TRY(launch_query_order(q.as<float>(), qstride, dim, (uint32_t)n_q, (uint32_t)bits, hist.as<uint32_t>(), order.as<uint32_t>(), nullptr));
+    return d2h_staged(out_order, order.p, obytes, nullptr);
+}
+
+// The permutation the handle's last ordered search call walked its batch in (knob "order_last": whether the very last call was one), read
+// from that call's lane once everything enqueued on the device has completed.  capacity: entries out_order holds; *out_n: that call's
+// queries -- set also where out_order is NULL or too small (GBNNS_ERR_INVALID, nothing copied), so a caller can ask for the size first.
+int gbnns_index_order_last(gbnns_index* ix, uint32_t* out_order, uint64_t capacity, uint64_t* out_n) {
+    if (!ix || !out_n) return fail(GBNNS_ERR_INVALID, "gbnns_index_order_last: null argument");
+    *out_n = 0;
+    if (ix->order_perm_lane < 0) return fail(GBNNS_ERR_INVALID, "gbnns_index_order_last: no call of this handle was walked in locality order");
+    *out_n = ix->order_perm_n;
+    if (!out_order || capacity < ix->order_perm_n)
+        return fail(GBNNS_ERR_INVALID, "gbnns_index_order_last: room for %llu entries, the order has %u", (unsigned long long)(out_order ? capacity : 0),
+                    ix->order_perm_n);
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(hipDeviceSynchronize());  // (the call may have run on a lane's own stream, its join still owed)
+    return d2h_staged(out_order, ix->lanes[ix->order_perm_lane].order.p, (size_t)ix->order_perm_n * 4, nullptr);
+}
+
 // Diagnostic (not in gbnns.h; host only, no device): the staged-order image of one layer (kernels.h pack_net_image) for host weights
 // w [dout x wstride], b neurons per lane group (8 hidden; last layer: *b3_of_d_low says which), go neuron groups (2 whole-CU, 4 half-CU).
 // out == NULL: only the sizes.  geom: {ck, ldw, rows, buf, nch, slices, interleaved, floats of the image}.
@@ -1194,14 +1237,21 @@ int gbnns_index_low_rows(gbnns_index* ix, float* out, int mem_kind, void* stream
 }
 
 int gbnns_index_knob_get(gbnns_index* ix, const char* name, int* out) {
-    if (!ix || !name || !out) return fail(GBNNS_ERR_INVALID, "gbnns_index_knob_get: null argument");
+    if (!name || !out) return fail(GBNNS_ERR_INVALID, "gbnns_index_knob_get: null argument");
+    if (!ix) {  // no handle, no device: the process-wide default a new handle would start from (the two locality-order knobs)
+        const Knobs d = knob_defaults();
+        if (!std::strcmp(name, "order_min")) { *out = d.order_min; return GBNNS_OK; }
+        if (!std::strcmp(name, "order_bits")) { *out = d.order_bits; return GBNNS_OK; }
+        return fail(GBNNS_ERR_INVALID, "gbnns_index_knob_get: null argument");
+    }
     const Knobs& k = ix->knob;
     const struct { const char* n; int v; } all[] = {
         {"quotient", k.quotient}, {"vs_disp", k.vs_disp}, {"max_waves", k.max_waves}, {"spec_min_nq", k.spec_min_nq},
         {"spec_any_form", k.spec_any_form}, {"mlp_small", k.mlp_small}, {"mlp_net", k.mlp_net}, {"mlp_slab", k.mlp_slab},
         {"late_rows", k.late_rows}, {"spec_tail", k.spec_tail}, {"coop", k.coop}, {"hot", k.hot}, {"byte_query_int", k.byte_query_int}, {"mlp_net_form", ix->net_form}, {"cus", ix->cus},
         {"gather_budget", k.gather_budget}, {"gather_timing", k.gather_timing}, {"gather_census_us", ix->gather_us[0]}, {"gather_fill_us", ix->gather_us[1]},
-        {"gather_scan_us", ix->gather_us[2]}, {"gather_rounds", ix->gather_rounds}};
+        {"gather_scan_us", ix->gather_us[2]}, {"gather_rounds", ix->gather_rounds},
+        {"order_min", k.order_min}, {"order_bits", k.order_bits}, {"order_last", (int)ix->order_last}};
     for (const auto& e : all)
         if (!std::strcmp(name, e.n)) { *out = e.v; return GBNNS_OK; }
     return fail(GBNNS_ERR_INVALID, "gbnns_index_knob_get: unknown handle knob '%s'", name);

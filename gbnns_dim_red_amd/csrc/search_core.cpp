@@ -147,14 +147,17 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
     // Deep batches are walked in locality order (walk_common.h, walk_query_of): a counting sort on the sign bits of the
     // first 12 walked-space coordinates, three small launches.  Wavefronts resident together then walk neighbouring
     // regions and find each other's rows in the caches: -8 % kernel time on a 4 M-node index, -3 % on 1 M -- which the
-    // sort's launches would eat on a 10 000-query batch, so only from GBNNS_ORDER_MIN queries on (default 32 768).
-    static const uint32_t order_min = getenv("GBNNS_ORDER_MIN") ? (uint32_t)strtoul(getenv("GBNNS_ORDER_MIN"), nullptr, 10) : 32768u;
-    static const uint32_t order_bits = getenv("GBNNS_ORDER_BITS") ? (uint32_t)atoi(getenv("GBNNS_ORDER_BITS")) : 12u;  // tuning: 10 .. 16
+    // sort's launches would eat on a 10 000-query batch, so only from the knob "order_min" queries on (default 32 768, 0 = never;
+    // "order_bits": the key width, 10 .. 16, default 12 -- handle.cpp).
+    const uint32_t order_min = (uint32_t)ix->knob.order_min, order_bits = (uint32_t)ix->knob.order_bits;
+    ix->order_last = 0;
     if (!plain && nq >= order_min && order_min > 0 && w.dim >= 16u) {
         if ((rc = L.order.ensure((size_t)nq * 4))) return rc;
         if ((rc = L.order_hist.ensure((size_t)4 << 16))) return rc;
         HIP_TRY(launch_query_order(w.q, w.qstride, w.dim, nq, order_bits, L.order_hist.as<uint32_t>(), L.order.as<uint32_t>(), s));
         w.order = L.order.as<uint32_t>();
+        ix->order_last = ix->order_perm_n = nq;   // (gbnns_index_order_last: this lane's permutation)
+        ix->order_perm_lane = (int)(&L - ix->lanes);
     }
     if (prof) HIP_TRY(hipEventRecord(pc.ev[1], s));
 

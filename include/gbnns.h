@@ -506,7 +506,14 @@ int gbnns_profile_enable(gbnns_index* index, int on);
  * "gather_budget" (handle knob): list entries the id lists of one round of gbnns_index_exact_knn_gather may hold together (default 2^26, at
  * least 1; the call never takes less than n; GBNNS_GATHER_BUDGET) -- not for tuning: a test forces several rounds at a few thousand rows.
  * "gather_timing" (handle knob): 1 = a gathered call times its stages with events, its rounds one after the other (default 0); the last
- * such call's figures through gbnns_index_knob_get only: "gather_census_us", "gather_fill_us", "gather_scan_us", "gather_rounds". */
+ * such call's figures through gbnns_index_knob_get only: "gather_census_us", "gather_fill_us", "gather_scan_us", "gather_rounds".
+ * "order_min" (handle knob): smallest batch of a GBNNS_MODE_NET / GBNNS_MODE_LOWQ search over at least 16 walked coordinates that is walked
+ * in locality order -- the batch sorted by the sign bits of its queries' first walked-space coordinates, so that wavefronts resident
+ * together walk neighbouring regions; only the order of the work changes, every answer goes to its query's own slot (default 32 768,
+ * 0 = never, negative values count as 0; GBNNS_ORDER_MIN).  "order_bits" (handle knob): the width of that key, 10 .. 16, clamped (default 12;
+ * GBNNS_ORDER_BITS).  "order_last" (gbnns_index_knob_get only): the queries the handle's last search call walked in locality order -- its
+ * batch size, or 0 when it was not ordered.  gbnns_index_knob_get(NULL, "order_min" / "order_bits", &v) reads the process-wide default;
+ * every other name needs a handle. */
 int gbnns_debug_knob(const char* name, int value);
 int gbnns_index_knob(gbnns_index* index, const char* name, int value);   /* GBNNS_ERR_INVALID: not a handle knob */
 int gbnns_index_knob_get(gbnns_index* index, const char* name, int* out_value);   /* the handle's current value */
@@ -562,6 +569,18 @@ int gbnns_debug_project_plan(uint32_t d, uint32_t d_hidden, uint32_t d_low, uint
 /* The instances the handle's last projection (a GBNNS_MODE_NET search, gbnns_project) actually launched, as its launchers reported them:
  * same format; the empty string before the first one.  The knob "cus" (gbnns_index_knob_get only) is the compute-unit count the handle plans with. */
 int gbnns_index_project_last(gbnns_index* index, char* names, uint32_t names_bytes);
+/* The permutation the handle's last ORDERED search call walked its batch in (knobs "order_min" / "order_bits"; "order_last" tells whether
+ * the very last call was one): out_order[b] = the query the b-th work item walked, copied to the host array from that call's lane once all
+ * the work enqueued on the device has completed (a call in flight included).  capacity: the entries out_order holds; *out_n: that call's
+ * n_q, the entries written.  GBNNS_ERR_INVALID: a null index or out_n, no ordered call yet (*out_n = 0), out_order NULL or too little room
+ * (*out_n is set, nothing is copied: a caller may ask for the size first). */
+int gbnns_index_order_last(gbnns_index* index, uint32_t* out_order, uint64_t capacity, uint64_t* out_n);
+/* Diagnostic: the locality order alone, on the current device -- HOST queries [n_q x qstride] floats (qstride >= dim), the key the sign
+ * bits of the first `bits` coordinates (clamped to 10 .. 16), coordinate 0 the most significant, a coordinate counting as 1 exactly where
+ * it compares > 0.  out_order [n_q] receives a permutation of 0 .. n_q-1 with non-decreasing keys; the order inside a bucket is not
+ * defined.  GBNNS_ERR_INVALID: a null pointer, dim == 0, qstride < dim, n_q == 0 or >= 2^31, bits < 0; GBNNS_ERR_HIP ("invalid argument"):
+ * dim < bits after clamping, the sort's own refusal. */
+int gbnns_debug_query_order(const float* queries, uint32_t qstride, uint32_t dim, uint64_t n_q, int bits, uint32_t* out_order);
 
 /* hnswlikeGD (support_func.h:521-575, need_const_degree = false) + addReverseEdgesForGD
  * (:402-445): prunes a kNN graph (CSR, host) over `ds` [n x d] (host) into the search graph, as

@@ -10,6 +10,7 @@ import pytest
 import bridge_util as bu
 import datagen
 import golden_util as gu
+import locality_order_util as lo
 import tag_util as tg
 import topk_util as tu
 
@@ -90,6 +91,12 @@ def _instances(g, orc, key, c, metric, dlow, beams=tg.BEAMS, flags=0, general=Fa
         if planned != "walk_general_kernel" and p["general_queries"] * 8 > len(c["Q"]):
             bad.append("%d queries went to the general kernel" % p["general_queries"])
         print("bridged", key, ef, launched, "general_queries", p["general_queries"])
+        # once more with the batch walked in locality order (locality_order_util.in_order): same kernel, a valid order, the same bytes
+        (ro, lo_launched, po), in_order = lo.in_order(ix, c["q_low"], lambda: _bridged(g, ix, c, ef, flags=flags))
+        in_order += lo.same_bytes(ro, r, ("ids",) + WANT)
+        if (lo_launched, po["retry_kernel"]) != (launched, p["retry_kernel"]):
+            in_order.append("launched %s / '%s'" % (lo_launched, po["retry_kernel"]))
+        bad += ["in order: " + b for b in in_order]
         if bad:
             failures.append((key, ef, bad))
     ix.close()

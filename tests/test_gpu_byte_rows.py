@@ -14,6 +14,7 @@ import byte_rows_util as bu
 import datagen
 import golden_util as gu
 import half_rows_util as hu
+import locality_order_util as lo
 import oracle as orc_mod
 import tag_util as tg
 import topk_util as tu
@@ -161,7 +162,7 @@ def test_fused_instances(g, orc):
     failures = []
     for ef in bu.BEAMS:
         w, want = _oracle(orc, "contest", c, ef, 0)
-        r, launched, _ = _search(g, ix, c, ef)
+        r, launched, p = _search(g, ix, c, ef)
         bad = _against(r, w, want)
         planned, fused = g.byte_plan(0, 32, bu.N, 32, ef)
         if launched != planned:
@@ -169,6 +170,10 @@ def test_fused_instances(g, orc):
         if fused != (ef <= 128):
             bad.append("fused %s" % fused)
         print("byte rows", ef, launched, "fused" if fused else "stand-alone re-rank")
+        # the same case in locality order: the fused byte re-rank reads the staged query of the MAPPED work item
+        (ro, _, po), in_order = lo.in_order(ix, c["q_low"], lambda: _search(g, ix, c, ef))
+        in_order += lo.same_bytes(ro, r, ("ids",) + WANT) + lo.same_kernels(po, p, False)
+        bad += ["in order: " + b for b in in_order]
         if bad:
             failures.append((ef, bad))
     ix.close()

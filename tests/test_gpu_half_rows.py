@@ -9,6 +9,7 @@ import pytest
 import datagen
 import golden_util as gu
 import half_rows_util as hu
+import locality_order_util as lo
 import oracle as orc_mod
 import topk_util as tu
 
@@ -82,12 +83,15 @@ def test_half_instances_on_the_contest_indexes(g, orc, metric, d, dlow):
         w, want = _oracle(orc, ("contest", metric, d, dlow), c, ef, metric)
         for late in ((0, 1) if (dlow == 144 and ef > 128) else (0,)):
             ix.knob("late_rows", late)
-            r, launched, _ = _flagged(g, ix, c, ef)
+            r, launched, p = _flagged(g, ix, c, ef)
             bad = _against(r, w, want)
             planned = hu.half_kernel(metric, dlow, ef, True, late=bool(late))
             if launched != planned:
                 bad.append("launched %s, expected %s" % (launched, planned))
             print("half rows", (metric, d, dlow, ef, late), launched)
+            (ro, _, po), in_order = lo.in_order(ix, c["q_low"], lambda: _flagged(g, ix, c, ef))   # the same case in locality order
+            in_order += lo.same_bytes(ro, r, ("ids",) + WANT) + lo.same_kernels(po, p, False)
+            bad += ["in order: " + b for b in in_order]
             if bad:
                 failures.append(((metric, d, dlow, ef, late), bad))
     ix.close()
@@ -104,12 +108,15 @@ def test_half_instances_on_two_pass_adjacency_rows(g, orc, metric, dlow):
         w, want = _oracle(orc, ("two_pass", metric, dlow), c, ef, metric)
         for late in ((0, 1) if (dlow == 144 and ef > 128) else (0,)):
             ix.knob("late_rows", late)
-            r, launched, _ = _flagged(g, ix, c, ef)
+            r, launched, p = _flagged(g, ix, c, ef)
             bad = _against(r, w, want)
             planned = hu.half_kernel(metric, dlow, ef, False, late=bool(late))
             if launched != planned:
                 bad.append("launched %s, expected %s" % (launched, planned))
             print("half rows, two passes", (metric, dlow, ef, late), launched)
+            (ro, _, po), in_order = lo.in_order(ix, c["q_low"], lambda: _flagged(g, ix, c, ef))   # the same case in locality order
+            in_order += lo.same_bytes(ro, r, ("ids",) + WANT) + lo.same_kernels(po, p, False)
+            bad += ["in order: " + b for b in in_order]
             if bad:
                 failures.append(((metric, dlow, ef, late), bad))
     ix.close()

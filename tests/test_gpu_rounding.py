@@ -27,6 +27,7 @@ import pytest
 
 import datagen
 import golden_util as gu
+import locality_order_util as lo
 import oracle as orc_mod
 
 pytestmark = pytest.mark.gpu
@@ -251,6 +252,12 @@ def test_net_mode_on_a_contest_index(g, orc, metric, d, dlow):
         assert np.array_equal(gu.bits(r["q_low"]), gu.bits(q_low)), key
         assert np.array_equal(r["ids"], s["ids"]), key
         assert np.array_equal(r["hops"], s["hops"]) and np.array_equal(r["dist_calc"] + ef, s["dist_calc"]), key
+        if (metric, d, dlow) == lo.NET_SHAPE and ef == 64:
+            # once more in locality order: the sort reads the PROJECTED queries, rows dl_pad floats apart in the lane's buffer (the one
+            # shape of this test whose projected batch the sort moves: locality_order_util.NET_SHAPE)
+            ro, in_order = lo.in_order(ix, q_low, lambda: ix.search(c["queries"], ef, entry_ids=c["ent"], want=("hops", "dist_calc", "q_low")))
+            in_order += lo.same_bytes(ro, r, ("ids", "hops", "dist_calc", "q_low")) + lo.same_kernels(ix.profile_read(reset=True), p, False)
+            assert not in_order, (key, in_order)
     ix.close()
 
 

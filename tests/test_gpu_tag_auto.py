@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import knn_tagged_util as kt
+import locality_order_util as lo
 import tag_auto_util as au
 import tag_util as tg
 
@@ -158,6 +159,11 @@ def test_every_row_is_a_row_of_its_route(g, orc, metric, ef, k, bridge):
             scan = e["route"] == 1
             if not (r["edges"][scan] == 0).all():
                 bad.append("edges of scan-routed queries")
+            # the same call with the walk of the whole batch in locality order: a work item walks under the word the ROUTING gave its query
+            # (0 for a scan-routed one) from that query's entry, and the scan's rows are scattered over the walk's afterwards
+            ro, in_order = lo.in_order(ix, c["q_low"], lambda: _auto(g, ix, c, ef, k, sb, ent=ent, flags=flags))
+            in_order += lo.same_bytes(ro, r, ("ids", "top_ids", "top_dist", "allowed", "route") + WANT)
+            bad += ["in order: " + b for b in in_order]
             print("auto", metric, ef, k, bridge, sb, "given entries" if ent is not None else "first", "scan-routed", int(scan.sum()), bad)
             if bad:
                 failures.append((sb, ent is not None, bad))

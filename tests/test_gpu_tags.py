@@ -9,6 +9,7 @@ import pytest
 
 import datagen
 import golden_util as gu
+import locality_order_util as lo
 import tag_util as tg
 import topk_util as tu
 
@@ -70,7 +71,8 @@ def _index(g, c, metric, profile=True, **kw):
 
 
 def _instances(g, orc, key, c, metric, dlow, one_pass, beams=tg.BEAMS, vacuity=True):
-    """Every beam (and both row-request orders of the 576-byte instance) on one index -> the list of failures."""
+    """Every beam (and both row-request orders of the 576-byte instance) on one index -> the list of failures.  Each case runs a second time
+    in locality order (locality_order_util.in_order): same kernel, a valid order read back, every output equal byte for byte."""
     ix = _index(g, c, metric)
     failures = []
     for ef in beams:
@@ -91,6 +93,12 @@ def _instances(g, orc, key, c, metric, dlow, one_pass, beams=tg.BEAMS, vacuity=T
             if planned != "walk_general_kernel" and p["general_queries"] * 8 > len(c["Q"]):
                 bad.append("%d queries went to the general kernel" % p["general_queries"])
             print("tagged", key, ef, late, launched, "general_queries", p["general_queries"])
+            # once more with the batch walked in locality order: work item b walks query order[b], under that query's own word, from its entry
+            (ro, lo_launched, po), in_order = lo.in_order(ix, c["q_low"], lambda: _tagged(g, ix, c, ef))
+            in_order += lo.same_bytes(ro, r, ("ids",) + WANT)
+            if (lo_launched, po["retry_kernel"]) != (launched, p["retry_kernel"]):
+                in_order.append("launched %s / '%s'" % (lo_launched, po["retry_kernel"]))
+            bad += ["in order: " + b for b in in_order]
             if bad:
                 failures.append((key, ef, late, bad))
     ix.close()

@@ -8,6 +8,7 @@ import pytest
 
 import datagen
 import golden_util as gu
+import locality_order_util as lo
 import oracle as orc_mod
 import topk_util as tu
 
@@ -154,13 +155,19 @@ def test_search_topk_on_a_contest_index(g, orc, metric, d, dlow):
         for k in sorted({1, min(10, ef), ef}):
             ix.profile_read(reset=True)
             r = ix.search(c["queries"], ef, top_k=k, **kw)
-            key = (metric, d, dlow, ef, tuple(knobs.items()), flags, cap, k, ix.profile_read(reset=True)["walk_kernel"])
+            p = ix.profile_read(reset=True)
+            key = (metric, d, dlow, ef, tuple(knobs.items()), flags, cap, k, p["walk_kernel"])
             print("search_topk", key)
             want_ids, want_dist = _expected_from_walk(orc, c, w, metric, k, memo)
             _same_rows(r["top_ids"], r["top_dist"], want_ids, want_dist, key)
             for name in ("ids", "hops", "dist_calc", "cand"):
                 assert np.array_equal(r[name], plain[name]), (key, name)
             assert np.array_equal(r["top_ids"][:, 0], r["ids"]), key
+            # the same call with the batch walked in locality order: the top-k kernel behind it reads the candidate rows of the queries' own slots
+            ro, in_order = lo.in_order(ix, c["q_low"], lambda: ix.search(c["queries"], ef, top_k=k, **kw))
+            in_order += lo.same_bytes(ro, r, ("ids", "hops", "dist_calc", "cand", "top_ids", "top_dist"))
+            in_order += lo.same_kernels(ix.profile_read(reset=True), p, cap != 0)
+            assert not in_order, (key, in_order)
     ix.close()
 
 

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import golden_util as gu
+import locality_order_util as lo
 import walk_instances as wi
 
 pytestmark = pytest.mark.gpu
@@ -64,9 +65,13 @@ def test_every_walk_instance_bit_exact_and_by_name(g, orc, metric, dim):
     hash_capacity 128 also: retry_kernel equals the planned retry name, retry_queries - retry_general_queries >= nq / 2 (by
     test_walk_instance_retry_cases_outgrow_their_visited_set the first pass hands over at least 3 / 4 of the batch, and the retry
     pass's visited set -- a CU's whole LDS -- holds more entries than the index has rows), and every output equals the same case's at
-    hash_capacity 0.  Mismatches are collected over the set, so one run names every failing case."""
+    hash_capacity 0.  Mismatches are collected over the set, so one run names every failing case.
+    Every case then runs once more with its batch walked in locality order (knob "order_min" = 1; 12 key bits, the first case of each
+    index at 10 and 16 too): the whole batch is ordered, the permutation read back from the handle is a valid order of the walked-space
+    queries, the same kernels are named and every output equals the unordered run's byte for byte; a retry case hands over at least 3 / 4
+    of the batch again.  tests/test_locality_order_cpu.py proves that the sort moves nearly every work item of these batches."""
     cases = [c for c in wi.CASES if (c.metric, c.dim) == (metric, dim)]
-    failures, ran = [], 0
+    failures, ran, ordered = [], 0, 0
     plain_done = False
     for key in sorted({c.graph_key for c in cases}):
         group = [c for c in cases if c.graph_key == key]
@@ -102,6 +107,14 @@ def test_every_walk_instance_bit_exact_and_by_name(g, orc, metric, dim):
                         bad.append("%s differs from hash_capacity 0" % name)
             elif p["retry_queries"] < p["retry_general_queries"]:
                 bad.append("counts: %d handed over, %d to the general kernel" % (p["retry_queries"], p["retry_general_queries"]))
+            for bits in (lo.BITS if c is group[0] else (12,)):
+                (ro, po), in_order = lo.in_order(ix, v["q_low"], lambda: _search(g, ix, v, c, c.hash_capacity), bits)
+                ordered += 1
+                in_order += lo.same_bytes(ro, r, ("ids",) + WANT)
+                in_order += lo.same_kernels(po, p, c.hash_capacity != 0)
+                if c.hash_capacity and 4 * int(po["retry_queries"]) < 3 * wi.NQ:
+                    in_order.append("first pass handed over %d of %d" % (po["retry_queries"], wi.NQ))
+                bad += ["in order, %d bits: %s" % (bits, b) for b in in_order]
             if bad:
                 failures.append((tuple(c), bad))
         if not plain_done and n == 3000:
@@ -124,8 +137,8 @@ def test_every_walk_instance_bit_exact_and_by_name(g, orc, metric, dim):
             if bad:
                 failures.append((("PLAIN", metric, dim, deg, ef), bad))
         ix.close()
-    print("census", (metric, dim), "cases", ran, "failures", len(failures))
-    assert plain_done and ran == len(cases)
+    print("census", (metric, dim), "cases", ran, "ordered runs", ordered, "failures", len(failures))
+    assert plain_done and ran == len(cases) and ordered == ran + 2 * len({c.graph_key for c in cases})
     assert not failures, failures
 
 
