@@ -49,6 +49,7 @@ SYMBOLS = [
     "gbnns_index_exact_knn_gather", "gbnns_debug_gather_plan", "gbnns_debug_gather_schedule",
     "gbnns_debug_project_plan", "gbnns_index_project_last",
     "gbnns_index_order_last", "gbnns_debug_query_order",
+    "gbnns_debug_rerank_plan",
 ]
 
 
@@ -213,6 +214,7 @@ def load_library():
     lib.gbnns_search_byte_queries.argtypes = [C.c_void_p, C.POINTER(_SearchArgs), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.gbnns_debug_byte_plan.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int,
                                           C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(C.c_int)]
+    lib.gbnns_debug_rerank_plan.argtypes = [C.c_int, C.c_uint32, C.c_int, C.c_char_p, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.gbnns_index_d_low.argtypes = [C.c_void_p]
     lib.gbnns_index_d_low.restype = C.c_uint32
     _lib = lib
@@ -361,6 +363,17 @@ def byte_plan(metric, dim, n, ell_stride, ef, aux_stride=0, n_entries=1, wide=Fa
     _check(load_library().gbnns_debug_byte_plan(metric, dim, (dim + 3) // 4 * 4, n, ell_stride, aux_stride, ef, n_entries, int(wide), int(coop),
                                                 int(late_rows), int(spec_rows), pass_no, rr_reserve, name, 128, C.byref(fused)))
     return name.value.decode(), bool(fused.value)
+
+
+def rerank_plan(metric, d, bytes=False):
+    """gbnns_debug_rerank_plan (no device needed): (name, deep, fused) -- the kernel Index.rerank launches on rows of d coordinates (bytes=True:
+    the uint8 rows of a byte handle), the 16-byte row loads a lane of it has in flight in the first loop of its ladder (24 / 8 the float pair
+    form, 4 the byte chunk-pair form, 0 a lane per row), and whether a MODE_NET / MODE_LOWQ search may fuse the re-rank of such rows into its
+    walk kernels."""
+    name = C.create_string_buffer(128)
+    deep, fused = C.c_int(0), C.c_int(0)
+    _check(load_library().gbnns_debug_rerank_plan(metric, d, int(bool(bytes)), name, 128, C.byref(deep), C.byref(fused)))
+    return name.value.decode(), int(deep.value), bool(fused.value)
 
 
 def knn_bytes_plan(n, n_q, d, k):

@@ -1027,6 +1027,18 @@ int gbnns_debug_byte_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n
     return GBNNS_OK;
 }
 
+int gbnns_debug_rerank_plan(int metric, uint32_t d, int bytes, char* name, uint32_t name_bytes, int* deep, int* fused) {
+    if (!name || name_bytes == 0 || !deep || !fused) return fail(GBNNS_ERR_INVALID, "gbnns_debug_rerank_plan: null output");
+    if ((metric != GBNNS_METRIC_L2 && metric != GBNNS_METRIC_NEG_DOT) || d == 0)
+        return fail(GBNNS_ERR_INVALID, "gbnns_debug_rerank_plan: not the metric or the dimension of an index");
+    const RerankPlan plan = rerank_plan(metric, d, bytes != 0);
+    if (plan.form == RerankForm::ChunkPairs) std::snprintf(name, name_bytes, "rerank_bytes_pair_kernel");
+    else std::snprintf(name, name_bytes, "%s<%d>", bytes ? "rerank_bytes_kernel" : (plan.form == RerankForm::Pairs ? "rerank_pair_kernel" : "rerank_kernel"), metric);
+    *deep = plan.deep;
+    *fused = plan.fuses ? 1 : 0;
+    return GBNNS_OK;
+}
+
 int gbnns_debug_byte_walk_plan(int metric, uint32_t dim, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries, int force_wide,
                                int tagged, char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
     if (!name || name_bytes == 0 || !lds_bytes) return fail(GBNNS_ERR_INVALID, "gbnns_debug_byte_walk_plan: null output");

@@ -8,6 +8,8 @@
 
 #include <vector>
 
+#include "rerank_plan.h"
+
 namespace gbnns {
 
 constexpr uint32_t kInvalidId = 0xFFFFFFFFu;
@@ -166,11 +168,10 @@ size_t rerank_topk_lds(uint32_t dstride, uint32_t cand_stride);
 hipError_t launch_rerank_topk(const RerankTopkParams& p, int metric, hipStream_t s);
 // The same two over the uint8 rows of a byte handle (rerank_bytes.hip): `db` stays nullptr, `dstride` is the BYTES of a row -- round_up(dim, 16),
 // zero padded, which is also the floats of the staged query -- and `k` / `out_dist` are read by the k-answer launch only.  The distances are
-// the float kernels' on float32(db_b), bit for bit.  L2 with dim % 16 == 0: the chunk-pair form; else a lane per row.
+// the float kernels' on float32(db_b), bit for bit.  L2 with dim % 16 == 0: the chunk-pair form; else a lane per row (rerank_plan.h).
 struct RerankBytesParams : RerankTopkParams {
     const uint8_t* db_b;     // [n x dstride] bytes, rows 16-byte aligned
 };
-bool rerank_bytes_pair_form(uint32_t dim, int metric);
 hipError_t launch_rerank_bytes(const RerankBytesParams& p, int metric, hipStream_t s);
 hipError_t launch_rerank_topk_bytes(const RerankBytesParams& p, int metric, hipStream_t s);
 // diagnostic (tests): one batch merge of a sorted list [size] with up to 64 survivor keys (~0 = none)

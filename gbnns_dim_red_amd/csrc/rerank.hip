@@ -54,7 +54,7 @@ __global__ __launch_bounds__(64) void rerank_pair_kernel(RerankParams p) {
     const int cnt = p.count[qi];
     const uint32_t* cand = p.cand + (size_t)qi * p.cand_stride;
     RerankSrc a{p.q, p.qstride, p.db, p.dstride, p.dim, p.n};
-    const int win = (METRIC == 0 && p.dim >= 384u)
+    const int win = rerank_pairs_deep(METRIC, p.dim) == 24
                         ? rerank_pairs_core<METRIC, 24>(a, qi, cnt, reinterpret_cast<float*>(smem), lane, [&](int r) { return cand[r]; })
                         : rerank_pairs_core<METRIC>(a, qi, cnt, reinterpret_cast<float*>(smem), lane, [&](int r) { return cand[r]; });
     if (lane == 0) p.out[qi] = (win >= 0) ? cand[win] : kInvalidId;
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(64) void rerank_topk_pair_kernel(RerankTopkParams p
         t.keys[r] = ((uint64_t)fkey(dv) << 32) | (uint32_t)r;
         t.dist[r] = dv;
     };
-    if (METRIC == 0 && p.dim >= 384u) rerank_pairs_core<METRIC, 24>(a, qi, cnt, reinterpret_cast<float*>(smem), lane, id_at, 0, 1, nullptr, keep);
+    if (rerank_pairs_deep(METRIC, p.dim) == 24) rerank_pairs_core<METRIC, 24>(a, qi, cnt, reinterpret_cast<float*>(smem), lane, id_at, 0, 1, nullptr, keep);
     else rerank_pairs_core<METRIC>(a, qi, cnt, reinterpret_cast<float*>(smem), lane, id_at, 0, 1, nullptr, keep);
     topk_select(p, t, cand, qi, cnt, lane);
 }
@@ -115,8 +115,7 @@ __global__ __launch_bounds__(64) void rerank_topk_pair_kernel(RerankTopkParams p
 hipError_t launch_rerank(const RerankParams& p, int metric, hipStream_t s) {
     if (p.nq == 0) return hipSuccess;
     const size_t lds = (size_t)p.dstride * 4;
-    // pair form: both metrics at dim % 8 == 0; L2 at dim % 8 == 4 too (the last 16-byte step is the even lane's alone)
-    const bool pairs = p.dim > 0 && (p.dim % 8 == 0 || (metric == 0 && p.dim % 4 == 0));
+    const bool pairs = rerank_plan(metric, p.dim, false).form == RerankForm::Pairs;
     hipError_t e;
     if (metric == 1) {
         if (pairs) {
@@ -156,7 +155,7 @@ hipError_t launch_rerank_topk(const RerankTopkParams& p, int metric, hipStream_t
     if (p.nq == 0) return hipSuccess;
     if (p.k == 0 || p.k > p.cand_stride) return hipErrorInvalidValue;
     const size_t lds = rerank_topk_lds(p.dstride, p.cand_stride);
-    const bool pairs = p.dim > 0 && (p.dim % 8 == 0 || (metric == 0 && p.dim % 4 == 0));  // as launch_rerank
+    const bool pairs = rerank_plan(metric, p.dim, false).form == RerankForm::Pairs;  // as launch_rerank
     if (metric == 1) return pairs ? launch_topk(rerank_topk_pair_kernel<1>, p, lds, s) : launch_topk(rerank_topk_kernel<1>, p, lds, s);
     return pairs ? launch_topk(rerank_topk_pair_kernel<0>, p, lds, s) : launch_topk(rerank_topk_kernel<0>, p, lds, s);
 }

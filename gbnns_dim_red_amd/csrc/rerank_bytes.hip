@@ -91,14 +91,12 @@ bool bytes_shape_ok(const RerankBytesParams& p) { return p.db_b && p.dim > 0 && 
 
 }  // namespace
 
-bool rerank_bytes_pair_form(uint32_t dim, int metric) { return metric == 0 && dim > 0 && dim % 16 == 0; }
-
 hipError_t launch_rerank_bytes(const RerankBytesParams& p, int metric, hipStream_t s) {
     if (p.nq == 0) return hipSuccess;
     if (!bytes_shape_ok(p)) return hipErrorInvalidValue;
     const size_t lds = (size_t)p.dstride * 4;
-    if (metric == 1) return launch_bytes(rerank_bytes_kernel<1, false>, p, lds, s);
-    if (rerank_bytes_pair_form(p.dim, metric)) return launch_bytes(rerank_bytes_pair_kernel<false>, p, lds, s);
+    if (metric == 1) return launch_bytes(rerank_bytes_kernel<1, false>, p, lds, s);  // (never the chunk-pair form: rerank_plan.h)
+    if (rerank_plan(metric, p.dim, true).form == RerankForm::ChunkPairs) return launch_bytes(rerank_bytes_pair_kernel<false>, p, lds, s);
     return launch_bytes(rerank_bytes_kernel<0, false>, p, lds, s);
 }
 
@@ -107,7 +105,7 @@ hipError_t launch_rerank_topk_bytes(const RerankBytesParams& p, int metric, hipS
     if (!bytes_shape_ok(p) || p.k == 0 || p.k > p.cand_stride) return hipErrorInvalidValue;
     const size_t lds = rerank_topk_lds(p.dstride, p.cand_stride);
     if (metric == 1) return launch_bytes(rerank_bytes_kernel<1, true>, p, lds, s);
-    if (rerank_bytes_pair_form(p.dim, metric)) return launch_bytes(rerank_bytes_pair_kernel<true>, p, lds, s);
+    if (rerank_plan(metric, p.dim, true).form == RerankForm::ChunkPairs) return launch_bytes(rerank_bytes_pair_kernel<true>, p, lds, s);
     return launch_bytes(rerank_bytes_kernel<0, true>, p, lds, s);
 }
 

@@ -239,7 +239,7 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
     // A byte handle (gbnns_index_create_bytes): the re-rank is fused only into the byte instances (walk_plan.cpp decides, from bytes_dim);
     // every other first pass runs as on a float handle with GBNNS_FLAG_NO_FUSED_RERANK, the stand-alone byte kernel behind it
     const bool bytes = ix->db_b != nullptr;
-    if (bytes && !plain && !(a->flags & GBNNS_FLAG_NO_FUSED_RERANK) && rerank_bytes_pair_form(ix->d, ix->metric)) w.bytes_dim = ix->d;
+    if (bytes && !plain && !(a->flags & GBNNS_FLAG_NO_FUSED_RERANK) && rerank_plan(ix->metric, ix->d, true).fuses) w.bytes_dim = ix->d;
     // (a byte walk, GBNNS_FLAG_BYTE_WALK: a bit of its own too -- other kernels, no retry pass, and never the float handle's or the byte re-rank's state)
     // sizing statistics are kept per (ef, mode, aux, wide, byte instances: no retry pass behind them, half rows: another table, other walks; tagged: other graphs, shorter walks; bridged: two to three times the rows claimed; knob "hot" = 0: other kernels)
     const int skey = ((ef * 8 + a->mode * 2 + (aux ? 1 : 0)) * 2 + w.force_wide) | (w.half_rows ? 1 << 30 : 0) | (w.tagged ? 1 << 29 : 0) | (w.bridged ? 1 << 27 : 0) | (w.generic_only ? 1 << 28 : 0) | (w.bytes_dim ? 1 << 26 : 0) | (w.walk_bytes ? 1 << 25 : 0);
@@ -294,9 +294,8 @@ int search_core(gbnns_index* ix, Lane& L, const gbnns_search_args* a, hipStream_
     // lists (LDS-list kernel); taken when that at least doubles the resident wavefronts.
     size_t bitmap_per_cu = 0;
     WalkPlan bitmap_plan{};
-    // (L2: d % 8 == 4 too -- glove's 300 -- the pair form's last 16-byte step is the even lane's alone)
-    const bool pair_form = ix->d % 8 == 0 || (ix->d % 4 == 0 && ix->metric == GBNNS_METRIC_L2);
-    const bool want_fuse = bytes ? w.bytes_dim != 0u : (!plain && pair_form && !(a->flags & GBNNS_FLAG_NO_FUSED_RERANK));
+    // (rerank_plan.h: the pair form; L2: d % 8 == 4 too -- glove's 300 -- its last 16-byte step is the even lane's alone)
+    const bool want_fuse = bytes ? w.bytes_dim != 0u : (!plain && rerank_plan(ix->metric, ix->d, false).fuses && !(a->flags & GBNNS_FLAG_NO_FUSED_RERANK));
     w.rr_reserve = (want_fuse && !bytes) ? (uint32_t)ix->d_pad * 4u : 0u;  // (the bitmap pass has no byte instance)
     {
         // measured crossover on the GloVe-like shape: ef = 300 is faster with the register list + LDS table

@@ -260,7 +260,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int kQSteps = STEPS / 2;
     constexpr uint32_t kRowBytes = (uint32_t)STEPS * 16u;
-    constexpr int kRerankLoads = STEPS >= 12 ? 24 : 8;   // row pieces in flight per lane
+    constexpr int kRerankLoads = rerank_fused_deep(STEPS);   // row pieces in flight per lane
     const int lane = lane_id();
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t qi = walk_query_of(p, blockIdx.x);

@@ -1071,7 +1071,7 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
         return;
     }
     // (wide walked rows = the wide original rows of GIST: the re-rank keeps 24 loads in flight per lane, rerank_pairs_core)
-    B.template finish<(STEPS >= 12 ? 24 : 8)>(p, qi, hops, dist_calc, edges, after_q, lane);
+    B.template finish<rerank_fused_deep(STEPS)>(p, qi, hops, dist_calc, edges, after_q, lane);
 }
 
 // (rows of 32 steps and more: at most two wavefronts per SIMD -- left to its occupancy heuristic the compiler squeezes the 512-byte-row

@@ -542,6 +542,15 @@ int gbnns_debug_bridge_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t
 int gbnns_debug_byte_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef,
                           uint32_t n_entries, int force_wide, int coop, int late_rows, int spec_rows, int pass, uint32_t rr_reserve,
                           char* name, uint32_t name_bytes, int* fused);
+/* Diagnostic, no device needed: the distance form that re-ranks rows of d coordinates under `metric` -- float rows (bytes = 0) or the uint8
+ * rows of a byte handle (bytes != 0) --, from the predicate every launcher, the pair kernels and the search itself decide with.  `name`: the
+ * kernel gbnns_rerank launches ("rerank_pair_kernel<0>": two lanes per row; "rerank_kernel<1>": a lane per row; "rerank_bytes_pair_kernel";
+ * "rerank_bytes_kernel<0>"; the argument is the metric; gbnns_rerank_topk runs the same form's k-answer kernel).  *deep: the 16-byte row loads
+ * a lane has in flight in the first loop of its ladder -- 24 (L2, d >= 384) or 8 in the float pair form, 4 in the byte chunk-pair form, 0 a
+ * lane per row.  *fused: 1 where a GBNNS_MODE_NET / GBNNS_MODE_LOWQ search may leave the re-rank of such rows to its walk kernels (the pair
+ * forms; whether a call does depends on its flags, beam and LDS room as well), 0 where a re-rank launch always follows.  GBNNS_ERR_INVALID: a
+ * null output, an unknown metric, d == 0. */
+int gbnns_debug_rerank_plan(int metric, uint32_t d, int bytes, char* name, uint32_t name_bytes, int* deep, int* fused);
 /* Diagnostic, no device needed: the first-pass kernel a GBNNS_MODE_PLAIN call with GBNNS_FLAG_BYTE_WALK of that shape gets on a byte handle
  * ("walk_general_kernel": the general kernel's byte-walk instance takes the whole batch) and its LDS bytes per wavefront without the
  * visited set.  `dim` is the original dimension -- the walked row is round_up(dim, 16) bytes --, `tagged` != 0 a gbnns_search_tagged call;
