@@ -6,14 +6,15 @@
 //                   and gbnns_index_exact_knn_gather (the gathered exact scan: knn_gather.hip) with its two diagnostics
 //   lanes.cpp       gbnns_search_ex and the batches-in-flight machinery (lanes, fork / join events), gbnns_index_wait / _join
 //                   gbnns_index_tag_census and gbnns_search_tagged_auto (the census and the routing kernels: tag_census.hip)
-//   search_core.cpp one batch on one lane: workspaces, copies, the kernel sequence
-//   sizing.cpp      the visited-set sizing rule of the first pass (capacity, form, wavefronts per CU)
+//   search_core.cpp one batch on one lane, as a sequence of stages: workspaces, copies, the launches the call's plan names, statistics feedback
+//   call_plan.cpp   which kernels a search call launches, on which visited set: a value decided from const facts (call_plan.h; no HIP calls)
+//   sizing.cpp      the visited-set sizing rule of the first pass (capacity, form, wavefronts per CU), called by the plan
 //   walk_plan.cpp   which walk kernel instance serves a pass over a shape, and its LDS layout (walk_plan.h; no HIP calls)
 //   pin.cpp         gbnns_host_pin / gbnns_host_unpin and the page registry
 #pragma once
 
 #include "../../include/gbnns.h"
-#include "walk_plan.h"
+#include "call_plan.h"
 
 #include <hip/hip_runtime.h>
 
@@ -26,7 +27,6 @@
 #include <cstring>
 #include <cxxabi.h>
 #include <deque>
-#include <map>
 #include <new>
 #include <mutex>
 #include <set>
@@ -162,13 +162,7 @@ struct Lane {
     }
 };
 
-// The diagnostic knobs (defined and documented in handle.cpp).  Round 6: the eleven that steer a handle's searches live IN the handle
-// (gbnns_index::knob, set with gbnns_index_knob); the process-wide values (environment, gbnns_debug_knob) are only the defaults a handle
-// starts from, so a test or an A/B run that flips one no longer changes every other handle of the process.  The three knobs of
-// gbnns_exact_knn -- a function without a handle -- stay process-wide.
-struct Knobs {
-    int quotient, vs_disp, max_waves, spec_min_nq, spec_any_form, mlp_small, mlp_net, mlp_slab, late_rows, spec_tail, coop, hot, byte_query_int, gather_budget, gather_timing, order_min, order_bits;
-};
+// the diagnostic knobs: struct Knobs, call_plan.h (defined and documented in handle.cpp)
 Knobs knob_defaults();                                    // the process-wide defaults as they stand now
 bool knob_set(Knobs& k, const char* name, int value);     // clamps like the environment does; false = no such handle knob
 extern std::atomic<int> g_knob_knn_chunk, g_knob_knn_pool_min_k, g_knob_knn_filter, g_knob_knn_slab;
@@ -219,11 +213,7 @@ struct gbnns_index {
     uint32_t* prof_ctrl = nullptr;     // [4] page-locked copy of the last profiled call's control words (hand-over counts), made behind its general kernel
     bool prof_ctrl_pending = false;    // ... a copy is under way or done and not yet read; prof_ctrl_direct: that call's first pass appended to list B itself
     bool prof_ctrl_direct = false;
-    // visited-set sizing feedback, shared by the lanes (host-side bookkeeping; the statistics of a call arrive
-    // asynchronously in the lane's pinned block)
-    std::map<int, uint32_t> cap_for_ef;
-    std::map<int, uint32_t> maxdc_for_ef;  // largest dist_calc seen per (ef, mode, aux, wide): the raw figure behind cap_for_ef
-    std::map<int, int> calm_streak;   // per (ef, mode): consecutive observed batches without hand-over / resize
+    gbnns_api::SizingHistory history;  // visited-set sizing feedback, shared by the lanes (call_plan.h)
     uint32_t stats_tick = 0;
     std::deque<std::pair<hipEvent_t, hipStream_t>> joins;  // (batch's event, caller's stream) of the deferred calls not yet joined, oldest first
     int next_lane = 0;
@@ -264,29 +254,12 @@ int prof_flush(gbnns_index* ix);
 hipError_t rerank_launch(const gbnns_index* ix, const RerankParams& r, hipStream_t s);
 hipError_t rerank_topk_launch(const gbnns_index* ix, const RerankTopkParams& r, hipStream_t s);
 
-constexpr size_t kMaxLds = 160 * 1024;
-// LDS is handed out in granules of 1 280 bytes (measured, tools/ubench/occupancy_census.hip: one-wavefront workgroups of
-// 5 120 B -> 32 per CU, 5 121 .. 6 400 B -> 25, 6 401 .. 7 680 B -> 21): a wavefront's share is a multiple of it.
-#ifndef GBNNS_LDS_GRAN
-#define GBNNS_LDS_GRAN 1280
-#endif
-constexpr size_t kLdsGran = GBNNS_LDS_GRAN;
-
 // lanes.cpp
 int enter_stream(gbnns_index* ix, hipStream_t s);
 int ensure_lane(gbnns_index* ix, int i);
 void plan_call(gbnns_index* ix, const gbnns_search_args* a, int& lanes, int& lane);
 int flush_joins(gbnns_index* ix, size_t keep);
 int flush_join(gbnns_index* ix);
-
-// sizing.cpp: the first pass's visited set for this batch -- sets w.vs_shr / hash_cap / hash_limit / spec_rows / spec_from
-struct FirstPassSizing {
-    bool auto_cap;                // capacity chosen by the library (hash_capacity == 0)
-    int form;                     // 0 = 4-byte slots, 1 = packed, 2 = quotient
-    uint32_t cap;                 // entries
-};
-FirstPassSizing size_first_pass(gbnns_index* ix, WalkParams& w, const WalkPlan& plan, const gbnns_search_args* a, int ef, int skey, uint32_t nq,
-                                bool sync_host);
 
 // The k best of each query's candidates beside a search's answers (gbnns_search_topk): ids [n_q x k], dist likewise or nullptr;
 // buffers of args->mem_kind.

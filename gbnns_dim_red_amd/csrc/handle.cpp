@@ -984,47 +984,55 @@ int gbnns_debug_net_image(const float* w, uint32_t wstride, uint32_t din, uint32
     return GBNNS_OK;
 }
 
+// The six plan diagnostics below: one validation, the walked shape filled by the function search_core.cpp fills its own with (set_walk_shape,
+// call_plan.h), one plan_walk.  `f`: the handle's and the call's facts as the endpoint states them; `w`: the decisions it was given (late /
+// speculative rows, rr_reserve, bytes_dim); coop: asked for, taken where the shape has an instance.  general_lds: what *lds_bytes holds when
+// the general kernel takes the whole batch (0: the plan's figure).
+static int debug_plan(const char* fn, CallFacts f, WalkParams w, int force_wide, int coop, int pass, uint64_t general_lds, char* name, uint32_t name_bytes,
+                      uint64_t* lds_bytes, int* fused) {
+    if (!name || name_bytes == 0 || !(lds_bytes || fused)) return fail(GBNNS_ERR_INVALID, "%s: null output", fn);
+    if ((f.metric != GBNNS_METRIC_L2 && f.metric != GBNNS_METRIC_NEG_DOT) || f.dim == 0 || f.dstride != round_up(f.dim, f.walk_bytes ? 16 : 4) || f.n == 0 ||
+        f.n > 0xFFFFFFFFull || f.ell_stride == 0 || f.ell_stride % 16 || f.aux_stride % 16 || f.ef < 1 || f.n_entries > 4096 || pass < 0 || pass > 2)
+        return fail(GBNNS_ERR_INVALID, "%s: not the shape of an index or a search", fn);
+    f.flags = force_wide ? GBNNS_FLAG_WIDE_INDEX : 0u;
+    f.knob.hot = 1;
+    set_walk_shape(w, f);
+    const WalkPass wp = pass == 1 ? WalkPass::Bitmap : (pass == 2 ? WalkPass::Retry : WalkPass::First);
+    w.coop = coop && wp == WalkPass::First && plan_walk(w, f.metric, wp).coop_serves;
+    const WalkPlan plan = plan_walk(w, f.metric, wp);
+    const char* planned = plan.general_only ? "walk_general_kernel" : walk_plan_name(plan);
+    if (!planned) return fail(GBNNS_ERR_INTERNAL, "%s: no kernel instance for the plan", fn);
+    std::snprintf(name, name_bytes, "%s", planned);
+    if (lds_bytes) *lds_bytes = (plan.general_only && general_lds) ? general_lds : plan.lds_fixed;
+    if (fused) *fused = (!plan.general_only && plan.inst.bytes) ? 1 : 0;
+    return GBNNS_OK;
+}
+
+static CallFacts debug_facts(int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries) {
+    CallFacts f{};
+    f.metric = metric; f.dim = dim; f.dstride = dstride; f.n = n; f.ell_stride = ell_stride; f.aux_stride = aux_stride; f.ef = ef; f.n_entries = n_entries;
+    return f;
+}
+
 int gbnns_debug_walk_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef,
                           uint32_t n_entries, int force_wide, int coop, int late_rows, int spec_rows, int pass, uint32_t rr_reserve,
                           char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
-    if (!name || name_bytes == 0 || !lds_bytes) return fail(GBNNS_ERR_INVALID, "gbnns_debug_walk_plan: null output");
-    if ((metric != GBNNS_METRIC_L2 && metric != GBNNS_METRIC_NEG_DOT) || dim == 0 || dstride != round_up(dim, 4) || n == 0 || n > 0xFFFFFFFFull ||
-        ell_stride == 0 || ell_stride % 16 || aux_stride % 16 || ef < 1 || n_entries > 4096 || pass < 0 || pass > 2)
-        return fail(GBNNS_ERR_INVALID, "gbnns_debug_walk_plan: not the shape of an index or a search");
+    if (!lds_bytes) return fail(GBNNS_ERR_INVALID, "gbnns_debug_walk_plan: null output");
     WalkParams w{};
-    w.dim = dim; w.dstride = dstride; w.n = (uint32_t)n; w.ell_stride = ell_stride; w.ef = ef; w.n_entries = n_entries ? n_entries : 1u;
-    w.aux_ell = aux_stride ? &w.aux_stride : nullptr; w.aux_stride = aux_stride;  // (the plan asks only WHETHER there is an auxiliary graph)
-    w.force_wide = force_wide != 0; w.late_rows = late_rows != 0; w.spec_rows = spec_rows != 0; w.rr_reserve = rr_reserve;
-    const WalkPass wp = pass == 1 ? WalkPass::Bitmap : (pass == 2 ? WalkPass::Retry : WalkPass::First);
-    w.coop = coop && wp == WalkPass::First && plan_walk(w, metric, wp).coop_serves;
-    const WalkPlan plan = plan_walk(w, metric, wp);
-    const char* planned = plan.general_only ? "walk_general_kernel" : walk_plan_name(plan);
-    if (!planned) return fail(GBNNS_ERR_INTERNAL, "gbnns_debug_walk_plan: no kernel instance for the plan");
-    std::snprintf(name, name_bytes, "%s", planned);
-    *lds_bytes = plan.lds_fixed;
-    return GBNNS_OK;
+    w.late_rows = late_rows != 0; w.spec_rows = spec_rows != 0; w.rr_reserve = rr_reserve;
+    return debug_plan("gbnns_debug_walk_plan", debug_facts(metric, dim, dstride, n, ell_stride, aux_stride, ef, n_entries), w, force_wide, coop, pass, 0, name,
+                      name_bytes, lds_bytes, nullptr);
 }
 
 int gbnns_debug_byte_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef,
                           uint32_t n_entries, int force_wide, int coop, int late_rows, int spec_rows, int pass, uint32_t rr_reserve,
                           char* name, uint32_t name_bytes, int* fused) {
-    if (!name || name_bytes == 0 || !fused) return fail(GBNNS_ERR_INVALID, "gbnns_debug_byte_plan: null output");
-    if ((metric != GBNNS_METRIC_L2 && metric != GBNNS_METRIC_NEG_DOT) || dim == 0 || dstride != round_up(dim, 4) || n == 0 || n > 0xFFFFFFFFull ||
-        ell_stride == 0 || ell_stride % 16 || aux_stride % 16 || ef < 1 || n_entries > 4096 || pass < 0 || pass > 2)
-        return fail(GBNNS_ERR_INVALID, "gbnns_debug_byte_plan: not the shape of an index or a search");
+    if (!fused) return fail(GBNNS_ERR_INVALID, "gbnns_debug_byte_plan: null output");
     WalkParams w{};
-    w.dim = dim; w.dstride = dstride; w.n = (uint32_t)n; w.ell_stride = ell_stride; w.ef = ef; w.n_entries = n_entries ? n_entries : 1u;
-    w.aux_ell = aux_stride ? &w.aux_stride : nullptr; w.aux_stride = aux_stride;  // (the plan asks only WHETHER there is an auxiliary graph)
-    w.force_wide = force_wide != 0; w.late_rows = late_rows != 0; w.spec_rows = spec_rows != 0; w.rr_reserve = rr_reserve;
-    w.bytes_dim = metric == GBNNS_METRIC_L2 ? 16u : 0u;  // (an original dimension the chunk-pair re-rank serves: what search_core.cpp sets for such a handle)
-    const WalkPass wp = pass == 1 ? WalkPass::Bitmap : (pass == 2 ? WalkPass::Retry : WalkPass::First);
-    w.coop = coop && wp == WalkPass::First && plan_walk(w, metric, wp).coop_serves;
-    const WalkPlan plan = plan_walk(w, metric, wp);
-    const char* planned = plan.general_only ? "walk_general_kernel" : walk_plan_name(plan);
-    if (!planned) return fail(GBNNS_ERR_INTERNAL, "gbnns_debug_byte_plan: no kernel instance for the plan");
-    std::snprintf(name, name_bytes, "%s", planned);
-    *fused = (!plan.general_only && plan.inst.bytes) ? 1 : 0;
-    return GBNNS_OK;
+    w.late_rows = late_rows != 0; w.spec_rows = spec_rows != 0; w.rr_reserve = rr_reserve;
+    w.bytes_dim = metric == GBNNS_METRIC_L2 ? 16u : 0u;  // (an original dimension the chunk-pair re-rank serves: CallPlan::bytes_dim of such a handle)
+    return debug_plan("gbnns_debug_byte_plan", debug_facts(metric, dim, dstride, n, ell_stride, aux_stride, ef, n_entries), w, force_wide, coop, pass, 0, name,
+                      name_bytes, nullptr, fused);
 }
 
 int gbnns_debug_rerank_plan(int metric, uint32_t d, int bytes, char* name, uint32_t name_bytes, int* deep, int* fused) {
@@ -1039,69 +1047,44 @@ int gbnns_debug_rerank_plan(int metric, uint32_t d, int bytes, char* name, uint3
     return GBNNS_OK;
 }
 
+// (a flagged PLAIN call on a byte handle: rows of round_up(dim, 16) bytes; the general kernel: the staged query alone)
+static int debug_byte_walk_plan(const char* fn, bool byte_queries, int metric, uint32_t dim, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef,
+                                uint32_t n_entries, int force_wide, int tagged, char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
+    if (!lds_bytes) return fail(GBNNS_ERR_INVALID, "%s: null output", fn);
+    CallFacts f = debug_facts(metric, dim, round_up(dim, 16), n, ell_stride, aux_stride, ef, n_entries);
+    f.tagged = tagged != 0; f.walk_bytes = true;
+    f.byte_queries = byte_queries; f.knob.byte_query_int = 7;  // (... and whether the call brought byte queries; every beam class: knob "byte_query_int" = 7)
+    return debug_plan(fn, f, WalkParams{}, force_wide, 0, 0, (uint64_t)f.dstride * 4u, name, name_bytes, lds_bytes, nullptr);
+}
+
 int gbnns_debug_byte_walk_plan(int metric, uint32_t dim, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries, int force_wide,
                                int tagged, char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
-    if (!name || name_bytes == 0 || !lds_bytes) return fail(GBNNS_ERR_INVALID, "gbnns_debug_byte_walk_plan: null output");
-    if ((metric != GBNNS_METRIC_L2 && metric != GBNNS_METRIC_NEG_DOT) || dim == 0 || n == 0 || n > 0xFFFFFFFFull || ell_stride == 0 || ell_stride % 16 ||
-        aux_stride % 16 || ef < 1 || n_entries > 4096)
-        return fail(GBNNS_ERR_INVALID, "gbnns_debug_byte_walk_plan: not the shape of an index or a search");
-    WalkParams w{};
-    w.dim = dim; w.dstride = round_up(dim, 16); w.n = (uint32_t)n; w.ell_stride = ell_stride; w.ef = ef; w.n_entries = n_entries ? n_entries : 1u;
-    w.aux_ell = aux_stride ? &w.aux_stride : nullptr; w.aux_stride = aux_stride;  // (the plan asks only WHETHER there is an auxiliary graph)
-    w.force_wide = force_wide != 0; w.tagged = tagged != 0; w.walk_bytes = 1;   // (what search_core.cpp sets for a flagged PLAIN call)
-    const WalkPlan plan = plan_walk(w, metric, WalkPass::First);
-    const char* planned = plan.general_only ? "walk_general_kernel" : walk_plan_name(plan);
-    if (!planned) return fail(GBNNS_ERR_INTERNAL, "gbnns_debug_byte_walk_plan: no kernel instance for the plan");
-    std::snprintf(name, name_bytes, "%s", planned);
-    *lds_bytes = plan.general_only ? (uint64_t)w.dstride * 4u : plan.lds_fixed;  // (the general kernel: the staged query alone)
-    return GBNNS_OK;
+    return debug_byte_walk_plan("gbnns_debug_byte_walk_plan", false, metric, dim, n, ell_stride, aux_stride, ef, n_entries, force_wide, tagged, name, name_bytes, lds_bytes);
 }
 
 int gbnns_debug_byte_query_plan(int metric, uint32_t dim, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries, int force_wide,
                                 int tagged, char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
-    if (!name || name_bytes == 0 || !lds_bytes) return fail(GBNNS_ERR_INVALID, "gbnns_debug_byte_query_plan: null output");
-    if ((metric != GBNNS_METRIC_L2 && metric != GBNNS_METRIC_NEG_DOT) || dim == 0 || n == 0 || n > 0xFFFFFFFFull || ell_stride == 0 || ell_stride % 16 ||
-        aux_stride % 16 || ef < 1 || n_entries > 4096)
-        return fail(GBNNS_ERR_INVALID, "gbnns_debug_byte_query_plan: not the shape of an index or a search");
-    WalkParams w{};
-    w.dim = dim; w.dstride = round_up(dim, 16); w.n = (uint32_t)n; w.ell_stride = ell_stride; w.ef = ef; w.n_entries = n_entries ? n_entries : 1u;
-    w.aux_ell = aux_stride ? &w.aux_stride : nullptr; w.aux_stride = aux_stride;  // (the plan asks only WHETHER there is an auxiliary graph)
-    w.force_wide = force_wide != 0; w.tagged = tagged != 0; w.walk_bytes = 1;
-    w.q_b = reinterpret_cast<const uint8_t*>(&w); w.bq_classes = 7u;  // (... and whether the call brought byte queries; every beam class: knob "byte_query_int" = 7)
-    const WalkPlan plan = plan_walk(w, metric, WalkPass::First);
-    const char* planned = plan.general_only ? "walk_general_kernel" : walk_plan_name(plan);
-    if (!planned) return fail(GBNNS_ERR_INTERNAL, "gbnns_debug_byte_query_plan: no kernel instance for the plan");
-    std::snprintf(name, name_bytes, "%s", planned);
-    *lds_bytes = plan.general_only ? (uint64_t)w.dstride * 4u : plan.lds_fixed;  // (the general kernel: the staged query alone)
-    return GBNNS_OK;
+    return debug_byte_walk_plan("gbnns_debug_byte_query_plan", true, metric, dim, n, ell_stride, aux_stride, ef, n_entries, force_wide, tagged, name, name_bytes, lds_bytes);
 }
 
-static int debug_tag_plan(const char* fn, int bridged, int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries,
-                         int force_wide, uint32_t rr_reserve, char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
-    if (!name || name_bytes == 0 || !lds_bytes) return fail(GBNNS_ERR_INVALID, "%s: null output", fn);
-    if ((metric != GBNNS_METRIC_L2 && metric != GBNNS_METRIC_NEG_DOT) || dim == 0 || dstride != round_up(dim, 4) || n == 0 || n > 0xFFFFFFFFull ||
-        ell_stride == 0 || ell_stride % 16 || aux_stride % 16 || ef < 1 || n_entries > 4096)
-        return fail(GBNNS_ERR_INVALID, "%s: not the shape of an index or a search", fn);
+static int debug_tag_plan(const char* fn, bool bridged, int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries,
+                          int force_wide, uint32_t rr_reserve, char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
+    if (!lds_bytes) return fail(GBNNS_ERR_INVALID, "%s: null output", fn);
+    CallFacts f = debug_facts(metric, dim, dstride, n, ell_stride, aux_stride, ef, n_entries);
+    f.tagged = true; f.bridged = bridged;
     WalkParams w{};
-    w.dim = dim; w.dstride = dstride; w.n = (uint32_t)n; w.ell_stride = ell_stride; w.ef = ef; w.n_entries = n_entries ? n_entries : 1u;
-    w.aux_ell = aux_stride ? &w.aux_stride : nullptr; w.aux_stride = aux_stride;  // (the plan asks only WHETHER there is an auxiliary graph)
-    w.force_wide = force_wide != 0; w.rr_reserve = rr_reserve; w.tagged = 1; w.bridged = bridged;
-    const WalkPlan plan = plan_walk(w, metric, WalkPass::First);
-    const char* planned = plan.general_only ? "walk_general_kernel" : walk_plan_name(plan);
-    if (!planned) return fail(GBNNS_ERR_INTERNAL, "%s: no kernel instance for the plan", fn);
-    std::snprintf(name, name_bytes, "%s", planned);
-    *lds_bytes = plan.lds_fixed;
-    return GBNNS_OK;
+    w.rr_reserve = rr_reserve;
+    return debug_plan(fn, f, w, force_wide, 0, 0, 0, name, name_bytes, lds_bytes, nullptr);
 }
 
 int gbnns_debug_tag_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries,
                          int force_wide, uint32_t rr_reserve, char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
-    return debug_tag_plan("gbnns_debug_tag_plan", 0, metric, dim, dstride, n, ell_stride, aux_stride, ef, n_entries, force_wide, rr_reserve, name, name_bytes, lds_bytes);
+    return debug_tag_plan("gbnns_debug_tag_plan", false, metric, dim, dstride, n, ell_stride, aux_stride, ef, n_entries, force_wide, rr_reserve, name, name_bytes, lds_bytes);
 }
 
 int gbnns_debug_bridge_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries,
                             int force_wide, uint32_t rr_reserve, char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
-    return debug_tag_plan("gbnns_debug_bridge_plan", 1, metric, dim, dstride, n, ell_stride, aux_stride, ef, n_entries, force_wide, rr_reserve, name, name_bytes, lds_bytes);
+    return debug_tag_plan("gbnns_debug_bridge_plan", true, metric, dim, dstride, n, ell_stride, aux_stride, ef, n_entries, force_wide, rr_reserve, name, name_bytes, lds_bytes);
 }
 
 // ---- gbnns_search_tagged: the rows' tag words -------------------------------------------------------------------------------------------

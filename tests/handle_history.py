@@ -45,7 +45,7 @@ MODE_NET, MODE_LOWQ, MODE_PLAIN = 0, 1, 2
 WANT = ("hops", "dist_calc", "cand", "cand_dist")
 KNOBS = {"coop": 0, "late_rows": 0, "spec_min_nq": 0, "spec_any_form": 0, "spec_tail": 0, "order_min": 0, "order_bits": 12}
 SCAN_BELOW = 5300      # float deck, 12 000 rows: words of an eighth of the rows and empty ones always scan; the half-of-the-rows words (6 000 under table A, about 4 700 under B) walk under A and scan under B; all-rows words walk
-CALM_AFTER = 3         # observed batches of a key after which the library may leave the retry launch out (streak 0, 1, 2: search_core.cpp)
+CALM_AFTER = 3         # observed batches of a key after which the library may leave the retry launch out (streak 0, 1, 2: call_plan.cpp)
 
 
 class Card:
@@ -73,7 +73,7 @@ class Card:
 
     @property
     def skey(self):
-        """The ingredients of the library's sizing key (search_core.cpp: ef, mode, aux, wide, half rows, tagged, bridged, byte instances,
+        """The ingredients of the library's sizing key (call_plan.cpp: ef, mode, aux, wide, half rows, tagged, bridged, byte instances,
         byte walk; the knob "hot" is never touched here), None for a call that does not walk."""
         if self.kind not in ("search", "auto"):
             return None

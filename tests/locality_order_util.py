@@ -127,7 +127,7 @@ def in_order(ix, q_walked, run, bits=12):
 def same_kernels(po, p, explicit_capacity):
     """What the profile po of an ordered call names differently from the profile p of the unordered one: the first-pass kernel, and the
     retry kernel.  With the library's own visited-set capacity (explicit_capacity false) the retry launch is left out once calls of that
-    beam have been calm (search_core.cpp, skip_retry), so between two calls of one handle the retry name may turn into the empty string
+    beam have been calm (call_plan.cpp, skip_retry), so between two calls of one handle the retry name may turn into the empty string
     and back; there two NAMES have to be the same name.  With hash_capacity set the launch never depends on the handle's history."""
     bad = []
     if po["walk_kernel"].split(" (")[0] != p["walk_kernel"].split(" (")[0]:

@@ -72,8 +72,8 @@ def test_rerank_plan_reports_the_one_choice(g):
     assert lib.gbnns_debug_rerank_plan(*ok, name, 128, C.byref(deep), None) == 1
     short = C.create_string_buffer(8)
     assert lib.gbnns_debug_rerank_plan(*ok, short, 8, C.byref(deep), C.byref(fused)) == 0 and short.value == b"rerank_"
-    # one place: the launchers, the pair kernels and the search call rerank_plan(); no other unit spells the rule
-    for unit, calls in (("rerank.hip", 2), ("rerank_bytes.hip", 2), ("search_core.cpp", 2), ("handle.cpp", 1)):
+    # one place: the launchers, the pair kernels and the search call's plan call rerank_plan(); no other unit spells the rule
+    for unit, calls in (("rerank.hip", 2), ("rerank_bytes.hip", 2), ("call_plan.cpp", 2), ("search_core.cpp", 0), ("handle.cpp", 1)):
         assert len(re.findall(r"(?<!\w)rerank_plan\(", _src(unit))) == calls, unit
     assert _src("rerank.hip").count("rerank_pairs_deep(METRIC, p.dim) == 24") == 2    # (the pair kernels: DEEP of a length already in the pair form)
     for unit in sorted(os.listdir(CSRC)):

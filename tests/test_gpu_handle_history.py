@@ -141,7 +141,7 @@ class Harness:
             if now != first:
                 bad.append("(retry_queries, general queries) %r, first occurrence %r" % (now, first))
         # A surprise card's evidence.  retry_kernel == "" with queries finished by the general kernel is the path that leaves the retry
-        # launch out (skip_retry: the first pass appends to list B itself).  The other launch-free branch of search_core.cpp, "nothing to
+        # launch out (skip_retry: the first pass appends to list B itself).  The other launch-free branch of call_plan.cpp, "nothing to
         # gain: A -> B", needs a first-pass table at least as large as the retry pass's -- a CU's whole LDS -- or a tagged / byte first pass:
         # the surprise cards are neither, and their tables are the LDS share of several wavefronts.
         if card.twin and delta is not None:
