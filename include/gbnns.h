@@ -155,7 +155,10 @@ typedef struct {
     float* out_cand_dist;      /* optional, same shape: low-dim distances of out_cand (+inf pad) */
     float* out_q_low;          /* optional NET: [n_q x d_low] projected queries */
     int32_t* out_edges;        /* optional [n_q]: neighbour ids read by the walk (sum of the degrees of
-                                  the expanded nodes) -- feeds the algorithmic-bytes figure */
+                                  the expanded nodes) -- feeds the algorithmic-bytes figure.  The degrees are
+                                  those of the rows as the index keeps them: an id that repeats inside a row
+                                  of graph_nbrs is kept once (its first occurrence) and counted once; with
+                                  GBNNS_FLAG_AUX_GRAPH the auxiliary rows a hop reads count as well */
     void* stream;              /* hipStream_t to enqueue on (NULL = default stream) */
     uint32_t flags;            /* GBNNS_FLAG_* */
     uint32_t hops_bound;       /* with GBNNS_FLAG_AUX_GRAPH: auxiliary rows are expanded while hops < hops_bound
@@ -374,7 +377,9 @@ int gbnns_search_tagged(gbnns_index* index, const gbnns_search_args* args, const
  *   - one level only: a disallowed entry of v's row is dropped, not looked through;
  *   - the row is a plain concatenation: it may hold u itself and the same id more than once -- the reference's visited test disposes of both
  *     (of equal ids the first occurrence is the one claimed, measured and offered);
- *   - the auxiliary graph, where used, is bridged through itself.
+ *   - the auxiliary graph, where used, is bridged through itself;
+ *   - "u's row" and "v's own row" are the rows as the index keeps them: an id that repeats inside a row of graph_nbrs is kept once, at its
+ *     first occurrence (no walk can tell; out_edges counts the degrees of this G'').
  * Nothing else changes: ids, pop order, distance bits, hops, dist_calc, out_q_low and the top-k rows are the CPU oracle's on G''
  * (gbnns_dim_red_amd.bridge_graph builds it with NumPy), bit for bit.  Looking through v is not a hop; a disallowed row is never claimed in
  * the visited set, never has a distance computed and is never counted in dist_calc; out_edges is the degree in G'' of the expanded nodes,
