@@ -176,7 +176,7 @@ CallPlan call_plan(const CallFacts& f, const SizingHistory& h) {
     cp.first = plan_walk(w, f.metric, cp.bitmap_pass ? WalkPass::Bitmap : WalkPass::First);
     // (the two-list instances keep their result list in LDS and stage the re-rank query in the visited-set area)
     const size_t rr_room = cp.first.rr_room(walk_hash_bytes(w.hash_cap, cp.first.hash_form(w.vs_shr)));
-    cp.fuse = !cp.first.lds_list && want_fuse && !w.all_general && (size_t)f.d_pad * 4 <= rr_room && (!bytes || cp.first.inst.bytes);
+    cp.fuse = !cp.first.lds_list && want_fuse && !w.all_general && (size_t)f.d_pad * 4 <= rr_room && (!bytes || (cp.first.inst.flags & kRrBytes));
     // Once batches of this (ef, mode) have been calm (no hand-over, size settled), the retry launch is left
     // out: the first pass then appends what it cannot finish to list B directly and the general kernel --
     // always launched -- takes it.  Still exact; a surprise hand-over is just slower once, and un-calms.

@@ -280,7 +280,7 @@ int build_ell(const uint64_t* off, const uint32_t* nbr, uint64_t n, std::vector<
 //                   1 = half-CU blocks, -1 = none yet
 //   "cus"           (read only) the compute units of the handle's device: what the projection's launch rules count rounds of the machine in
 //   "mlp_slab"      0 = never the slab kernel for single layers (mlp_net.hip, mlp_slab_kernel), 1 = where a layer is one round of it
-//   "late_rows"     generic two-list kernels over 192- / 256- / 576-byte rows -- -1 = by shape and residency (search_core.cpp), 0 = rows
+//   "late_rows"     generic two-list kernels over 192- / 256- / 576-byte rows -- -1 = by shape and residency (call_plan.cpp), 0 = rows
 //                   requested before the visited test, 1 = after it (GBNNS_LATE_ROWS)
 //   "spec_tail"     largest partial last round of a lone launch, in percent of the device's wavefront slots, whose wavefronts request
 //                   their rows before the visited test (0 = off)
@@ -1004,7 +1004,7 @@ static int debug_plan(const char* fn, CallFacts f, WalkParams w, int force_wide,
     if (!planned) return fail(GBNNS_ERR_INTERNAL, "%s: no kernel instance for the plan", fn);
     std::snprintf(name, name_bytes, "%s", planned);
     if (lds_bytes) *lds_bytes = (plan.general_only && general_lds) ? general_lds : plan.lds_fixed;
-    if (fused) *fused = (!plan.general_only && plan.inst.bytes) ? 1 : 0;
+    if (fused) *fused = (!plan.general_only && (plan.inst.flags & kRrBytes)) ? 1 : 0;
     return GBNNS_OK;
 }
 

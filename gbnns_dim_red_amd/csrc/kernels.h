@@ -92,7 +92,8 @@ struct WalkParams {
     int32_t coop;            // 1: the first pass is the two-wavefront walk (walk_coop.hip: kCoopExtraLds, walk_plan.h, more bytes of LDS per query)
     int32_t force_wide;      // diagnostic: treat the index as a large one (64-bit offsets, 4-byte visited-set slots)
     unsigned long long* stamps;  // diagnostic builds only (GBNNS_STAMPS): [32] segment cycle sums / histograms
-    int32_t stamps_on;           // 1 in diagnostic builds: use the instrumented generic kernel    // GBNNS_FLAG_HALF_ROWS (last, so that no other field moves): the walked table is R = float32(float16(db_low)) -- `db` above is then the
+    int32_t stamps_on;           // 1 in diagnostic builds: use the instrumented generic kernel
+    // GBNNS_FLAG_HALF_ROWS (last, so that no other field moves): the walked table is R = float32(float16(db_low)) -- `db` above is then the
     // float32 copy of R, which every kernel but the half instances reads
     const void* db_h;        // [n x dstride] binary16 rows of R (dstride a multiple of 8, no padding), or nullptr
     int32_t half_rows;       // 1: the first pass takes a half instance where the plan has one (walk_plan.cpp)

@@ -22,14 +22,12 @@ struct WalkEntry {
     const char* name;
 };
 #define WALK_KERNEL(...) reinterpret_cast<const void*>(&__VA_ARGS__), #__VA_ARGS__
-// (macro arguments: the instance's fields in the order of the kernel's own template arguments)
-#define WALK_REG(M, S, OFF32, RETRY, R, ONE, AUX) \
-    {{WalkFamily::RegList, M, S, R, OFF32, RETRY, ONE, AUX}, WALK_KERNEL(walk_reg_kernel<M, S, OFF32, RETRY, R, ONE, AUX>)}
-#define WALK_BIG(M, S, OFF32, RETRY, AUX, ONE, LATE) \
-    {{WalkFamily::TwoList, M, S, 4, OFF32, RETRY, ONE, AUX, LATE}, WALK_KERNEL(walk_reg_big_kernel<M, S, OFF32, RETRY, AUX, ONE, LATE>)}
-#define WALK_LDS(M, S, RETRY, PACKED) \
-    {{WalkFamily::LdsList, M, S, 0, false, RETRY, false, false, false, false, PACKED}, WALK_KERNEL(walk_fast_kernel<M, S, RETRY, PACKED>)}
-#define WALK_WIDE(S, LATE) {{WalkFamily::RegWide, 0, S, 0, false, false, false, false, LATE}, WALK_KERNEL(walk_reg_wide_kernel<S, LATE>)}
+// (macro arguments: the kernel's own template arguments, which its printable name needs as written; the row's flags are built from them by name
+// -- for the register-list / two-list kernels by reg_flags, walk_generic.h, the expression the kernel itself hands to its walk)
+#define WALK_REG(M, S, OFF32, RETRY, R, ONE, AUX) {{WalkFamily::RegList, M, S, R, reg_flags(OFF32, RETRY, ONE, AUX)}, WALK_KERNEL(walk_reg_kernel<M, S, OFF32, RETRY, R, ONE, AUX>)}
+#define WALK_BIG(M, S, OFF32, RETRY, AUX, ONE, LATE) {{WalkFamily::TwoList, M, S, 4, reg_flags(OFF32, RETRY, ONE, AUX, LATE)}, WALK_KERNEL(walk_reg_big_kernel<M, S, OFF32, RETRY, AUX, ONE, LATE>)}
+#define WALK_LDS(M, S, RETRY, PACKED) {{WalkFamily::LdsList, M, S, 0, flag_if(RETRY, kRetry) | flag_if(PACKED, kPacked)}, WALK_KERNEL(walk_fast_kernel<M, S, RETRY, PACKED>)}
+#define WALK_WIDE(S, LATE) {{WalkFamily::RegWide, 0, S, 0, flag_if(LATE, kLate)}, WALK_KERNEL(walk_reg_wide_kernel<S, LATE>)}
 // per (metric, steps): the LDS-list kernels; R list registers, and the two-list kernels (+ first pass over one-pass adjacency rows): compact /
 // non-compact index x first pass / retry, the auxiliary-graph hop
 #define WALK_LDS_SET(M, S) WALK_LDS(M, S, false, false), WALK_LDS(M, S, false, true), WALK_LDS(M, S, true, false), WALK_LDS(M, S, true, true)
@@ -62,13 +60,10 @@ const WalkEntry* walk_hot_entry(const WalkInstance& k);
 const WalkEntry* walk_coop_entry(const WalkInstance& k);
 const WalkEntry* walk_bitmap_entry(const WalkInstance& k);
 const WalkEntry* walk_half_entry(const WalkInstance& k);
-// (a table of its own, asked last by walk_entry, walk_l2.hip: only an instance with `tag` set matches a row of it)
+// (tables of their own, asked last by walk_entry, walk_l2.hip: only an instance with kTag / kBridge / kByteWalk / kByteQuery set matches a row of them)
 const WalkEntry* walk_tag_entry(const WalkInstance& k);
-// (the same for `bridge`: walk_bridge.hip)
 const WalkEntry* walk_bridge_entry(const WalkInstance& k);
-// (the same for `bwalk`: walk_bytes.hip)
 const WalkEntry* walk_bytes_entry(const WalkInstance& k);
-// (the same for `bq`: walk_bytes_q.hip)
 const WalkEntry* walk_bytes_q_entry(const WalkInstance& k);
 
 }  // namespace gbnns

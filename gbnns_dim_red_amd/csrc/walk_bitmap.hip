@@ -8,8 +8,7 @@ namespace gbnns {
 // Register lists (ef <= 128, L2, 128-byte rows); the two-list walk over 128-byte rows (both metrics) and, pair form with L2, 256- and
 // 576-byte rows -- adjacency rows of one 32-slot pass, the common case, take the instance without the pass loop, 576-byte rows have
 // the rows-after-the-bit-test order too; the LDS-list walk for everything else.
-#define WALK_BITMAP_BIG(M, S, ONE, LATE) \
-    {{WalkFamily::BitmapBig, M, S, 0, false, false, ONE, false, LATE}, WALK_KERNEL(walk_bitmap_big_kernel<M, S, ONE, LATE>)}
+#define WALK_BITMAP_BIG(M, S, ONE, LATE) {{WalkFamily::BitmapBig, M, S, 0, flag_if(ONE, kOne) | flag_if(LATE, kLate)}, WALK_KERNEL(walk_bitmap_big_kernel<M, S, ONE, LATE>)}
 #define WALK_BITMAP_LDS(M, S) {{WalkFamily::BitmapLds, M, S}, WALK_KERNEL(walk_bitmap_kernel<M, S>)}
 static const WalkEntry kEntries[] = {
     {{WalkFamily::BitmapReg, 0, 0, 1}, WALK_KERNEL(walk_bitmap_reg_kernel<0, 1>)},

@@ -313,8 +313,7 @@ __global__ __launch_bounds__(64) void walk_bridge_kernel(WalkParams p) {
     walk_bridge_one<METRIC, STEPS, R>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
 }
 
-#define WALK_BRIDGE(M, S, R) \
-    {{WalkFamily::RegList, M, S, R, true, false, false, false, false, false, false, false, true, true}, WALK_KERNEL(walk_bridge_kernel<M, S, R>)}
+#define WALK_BRIDGE(M, S, R) {{WalkFamily::RegList, M, S, R, kOff32 | kTag | kBridge}, WALK_KERNEL(walk_bridge_kernel<M, S, R>)}
 #define WALK_BRIDGE_SET(M, S) WALK_BRIDGE(M, S, 1), WALK_BRIDGE(M, S, 2)
 
 const WalkEntry kEntries[] = {WALK_BRIDGE_SET(0, 8), WALK_BRIDGE_SET(1, 8), WALK_BRIDGE_SET(0, 12), WALK_BRIDGE_SET(0, 16)};

@@ -14,22 +14,22 @@ namespace gbnns {
 
 namespace {
 
+constexpr uint32_t bytes_flags(bool one) { return kOff32 | kByteWalk | flag_if(one, kOne); }  // (a kernel and its table row both take their flags from here)
+
 template <int R, bool ONE_CHUNK>
 __global__ __launch_bounds__(64) void walk_reg_bytes_kernel(WalkParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    walk_reg_one<0, 8, true, R, ONE_CHUNK, false, false, false, 0, false, false, true>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
+    walk_reg_one<0, 8, R, bytes_flags(ONE_CHUNK) | kNeverLate>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
 }
 
 template <bool ONE_PASS>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8))) void walk_reg_big_bytes_kernel(WalkParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    walk_reg_big_one<0, 8, true, false, false, ONE_PASS, false, false, false, true>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
+    walk_reg_big_one<0, 8, bytes_flags(ONE_PASS)>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
 }
 
-#define WALK_REG_BYTES(R, ONE) \
-    {{WalkFamily::RegList, 0, 8, R, true, false, ONE, false, false, false, false, false, false, false, false, true}, WALK_KERNEL(walk_reg_bytes_kernel<R, ONE>)}
-#define WALK_BIG_BYTES(ONE) \
-    {{WalkFamily::TwoList, 0, 8, 4, true, false, ONE, false, false, false, false, false, false, false, false, true}, WALK_KERNEL(walk_reg_big_bytes_kernel<ONE>)}
+#define WALK_REG_BYTES(R, ONE) {{WalkFamily::RegList, 0, 8, R, bytes_flags(ONE)}, WALK_KERNEL(walk_reg_bytes_kernel<R, ONE>)}
+#define WALK_BIG_BYTES(ONE) {{WalkFamily::TwoList, 0, 8, 4, bytes_flags(ONE)}, WALK_KERNEL(walk_reg_big_bytes_kernel<ONE>)}
 
 // one / two list registers and the two-list kernel, each over one-pass adjacency rows (no pass loop) and with the pass loop
 const WalkEntry kEntries[] = {

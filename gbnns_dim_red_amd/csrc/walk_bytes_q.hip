@@ -17,22 +17,22 @@ namespace gbnns {
 
 namespace {
 
+constexpr uint32_t u8_flags(bool one) { return kOff32 | kByteWalk | kByteQuery | flag_if(one, kOne); }  // (a kernel and its table row both take their flags from here)
+
 template <int R, bool ONE_CHUNK>
 __global__ __launch_bounds__(64) void beam_u8_kernel(WalkParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    walk_reg_one<0, 8, true, R, ONE_CHUNK, false, false, false, 0, false, false, true, true>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
+    walk_reg_one<0, 8, R, u8_flags(ONE_CHUNK) | kNeverLate>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
 }
 
 template <bool ONE_PASS>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8))) void beam_u8_big_kernel(WalkParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    walk_reg_big_one<0, 8, true, false, false, ONE_PASS, false, false, false, true, true>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
+    walk_reg_big_one<0, 8, u8_flags(ONE_PASS)>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
 }
 
-#define BEAM_U8(R, ONE) \
-    {{WalkFamily::RegList, 0, 8, R, true, false, ONE, false, false, false, false, false, false, false, false, true, true}, WALK_KERNEL(beam_u8_kernel<R, ONE>)}
-#define BEAM_U8_BIG(ONE) \
-    {{WalkFamily::TwoList, 0, 8, 4, true, false, ONE, false, false, false, false, false, false, false, false, true, true}, WALK_KERNEL(beam_u8_big_kernel<ONE>)}
+#define BEAM_U8(R, ONE) {{WalkFamily::RegList, 0, 8, R, u8_flags(ONE)}, WALK_KERNEL(beam_u8_kernel<R, ONE>)}
+#define BEAM_U8_BIG(ONE) {{WalkFamily::TwoList, 0, 8, 4, u8_flags(ONE)}, WALK_KERNEL(beam_u8_big_kernel<ONE>)}
 
 // the instances of walk_bytes.hip, one for one
 const WalkEntry kEntries[] = {

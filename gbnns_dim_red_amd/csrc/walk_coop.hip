@@ -31,7 +31,7 @@
 //
 // Shapes: L2, walked rows of 128 / 192 / 256 bytes (d_low 32 / 48 / 64), 128 < ef <= 1 024, compact index, adjacency rows of one
 // 32-slot pass, one entry point, no auxiliary graph.  The host takes it for a batch that runs alone and is resident at once in this form
-// (search_core.cpp; knob "coop").
+// (call_plan.cpp; knob "coop").
 #define GBNNS_WAVE_LOCAL_SYNC 1
 #define GBNNS_COOP_HINT 1
 #include "launch_util.h"
@@ -669,7 +669,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
 }  // namespace
 
 // walked rows of 128 / 192 / 256 bytes; LATE: the rows requested after the scout's visited test
-#define WALK_COOP(S, LATE) {{WalkFamily::Coop, 0, S, 0, false, false, false, false, LATE}, WALK_KERNEL(walk_coop_kernel<S, LATE>)}
+#define WALK_COOP(S, LATE) {{WalkFamily::Coop, 0, S, 0, flag_if(LATE, kLate)}, WALK_KERNEL(walk_coop_kernel<S, LATE>)}
 static const WalkEntry kEntries[] = {WALK_COOP(8, false), WALK_COOP(8, true), WALK_COOP(12, false), WALK_COOP(12, true), WALK_COOP(16, false), WALK_COOP(16, true)};
 const WalkEntry* walk_coop_entry(const WalkInstance& k) { return find_walk_entry(kEntries, k); }
 

@@ -241,13 +241,14 @@ __global__ __launch_bounds__(64) void walk_bitmap_kernel(WalkParams p) {
 }
 
 
-// AUX: the auxiliary-graph walk (search_function.h:73-89): a hop expands the node's auxiliary row first (while
+// FLAGS: WalkFlag bits (walk_plan.h); the body reads them under the names below.
+// kAux (AUX): the auxiliary-graph walk (search_function.h:73-89): a hop expands the node's auxiliary row first (while
 // hops < hops_bound), then -- unless llf and that step inserted something -- its main row.
-// BITMAP: visited set = one bit per node in HBM (`bitmap`, this wavefront's slot), see walk_bitmap_kernel.
-// LATE: rows requested after the visited test -- 1 always, 0 never, -1 by WalkParams::late_rows (both orders in the kernel)
-// HALF: the hop's rows come from the 2-byte table WalkParams::db_h (walk_half.hip; pair-form instances of a compact index) -- p.db is then
+// kBitmap (BITMAP): visited set = one bit per node in HBM (`bitmap`, this wavefront's slot), see walk_bitmap_kernel.
+// LATE: rows requested after the visited test -- kLate: 1, always; kNeverLate: 0, never; neither: -1, by WalkParams::late_rows (both orders in the kernel)
+// kHalf (HALF): the hop's rows come from the 2-byte table WalkParams::db_h (walk_half.hip; pair-form instances of a compact index) -- p.db is then
 // the float32 copy of the same table R, which the entry row is read from; nothing else differs
-// TAG: gbnns_search_tagged (walk_tag.hip; pair-form instances of a compact index) -- the walk of the graph whose adjacency rows keep only the
+// kTag (TAG): gbnns_search_tagged (walk_tag.hip; pair-form instances of a compact index) -- the walk of the graph whose adjacency rows keep only the
 // neighbours j with (p.tags[j] & p.qtags[qi]) != 0.  A hop loads the tag word of every live slot and treats a disallowed slot as an empty one
 // from there on: never claimed in the visited set, no distance, not counted in edges.  The end of a row is still decided by the slots that
 // are non-empty BEFORE the tag test -- a chunk of disallowed neighbours is not the end of the row.  The source asks for the tags first and
@@ -260,15 +261,18 @@ __global__ __launch_bounds__(64) void walk_bitmap_kernel(WalkParams p) {
 // rows BEHIND the tag test (three round trips, rows of allowed slots only).  keep_rows is what holds the first two classes' loads ahead of
 // the early `continue`.  The instances that request their rows after the visited test (LATE) ask for the new allowed ids only, as before.
 // The query's tag word is wave-uniform and lives in a scalar register.
-// BYTES: GBNNS_FLAG_BYTE_WALK (walk_bytes.hip; L2, STEPS = 8 = the 16-byte chunks of a 128-byte uint8 row of d = 128, compact index) -- the hop's
+// kByteWalk (BYTES): GBNNS_FLAG_BYTE_WALK (walk_bytes.hip; L2, STEPS = 8 = the 16-byte chunks of a 128-byte uint8 row of d = 128, compact index) -- the hop's
 // rows and the entry row come from the byte table WalkParams::db_b (p.db is nullptr, p.dstride the bytes of a row), a lane keeps its four
 // chunks packed until l2_pair_from_bytes consumes them, and the query (128 floats) is re-read from LDS every hop; nothing else differs
-// BQ (with BYTES): gbnns_search_byte_queries (walk_bytes_q.hip) -- the query is read as bytes from WalkParams::q_b into 16 registers (ByteQuery: no
+// kByteQuery (BQ, with kByteWalk): gbnns_search_byte_queries (walk_bytes_q.hip) -- the query is read as bytes from WalkParams::q_b into 16 registers (ByteQuery: no
 // query area in LDS, the visited set starts where it would) and the distance is l2_pair_u8's integer one, the entry row's included
-template <int METRIC, int STEPS, bool OFF32, int R, bool ONE_CHUNK = false, bool AUX = false, bool BITMAP = false, bool QLDS_W = false, int LATE = -1,
-          bool HALF = false, bool TAG = false, bool BYTES = false, bool BQ = false>
+template <int METRIC, int STEPS, int R, uint32_t FLAGS>
 __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, unsigned char* smem,
                                              uint32_t* ovf_count, uint32_t* ovf_list, uint32_t* bitmap = nullptr) {
+    static_assert(!(FLAGS & ~(kOff32 | kOne | kAux | kLate | kHalf | kTag | kByteWalk | kByteQuery | kBitmap | kQueryLds | kNeverLate)), "a switch this walk does not have");
+    constexpr bool OFF32 = FLAGS & kOff32, ONE_CHUNK = FLAGS & kOne, AUX = FLAGS & kAux, BITMAP = FLAGS & kBitmap, QLDS_W = FLAGS & kQueryLds;
+    constexpr bool HALF = FLAGS & kHalf, TAG = FLAGS & kTag, BYTES = FLAGS & kByteWalk, BQ = FLAGS & kByteQuery;
+    constexpr int LATE = (FLAGS & kLate) ? 1 : ((FLAGS & kNeverLate) ? 0 : -1);
     static_assert(!(AUX && ONE_CHUNK), "auxiliary rows have their own length");
 #ifdef GBNNS_STAMPS
     unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -302,7 +306,7 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
     const uint32_t cap = p.hash_cap;  // any size: slot = mulhi(id * C, cap)
     const uint32_t hash_lds = (uint32_t)(size_t)((__attribute__((address_space(3))) unsigned char*)reinterpret_cast<unsigned char*>(hash));
 
-    // OFF32 instantiations serve "compact" indexes (tables < 4 GiB and n < 2^24: WalkInstance::off32, walk_plan.cpp): 32-bit byte
+    // OFF32 instantiations serve "compact" indexes (tables < 4 GiB and n < 2^24: kOff32, walk_plan.cpp): 32-bit byte
     // offsets and the packed visited set (24-bit ids, five per 16-byte bucket)
     constexpr bool packed = OFF32;
     // (first pass of a compact index: the host may ask for the quotient form of the table -- p.vs_shr, GBNNS_VS_ASM)
@@ -717,12 +721,13 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
 // the base list in LDS + the front list in one register, so that selection and insertion cost what they cost at
 // ef <= 64 whatever ef is (the R-register lists spent 28 % of a hop selecting and 30 % inserting at ef = 300).
 // LDS: [BigList: big_list_fixed_bytes(ef)][query: dstride floats][visited set | (BITMAP) re-rank scratch].
-// ONE_PASS: adjacency rows of one pass (the host checks ell_stride), no auxiliary graph -- the hop is straight-line code.
-// HALF, TAG, BYTES: as in walk_reg_one.
-template <int METRIC, int STEPS, bool OFF32, bool AUX = false, bool BITMAP = false, bool ONE_PASS = false, bool LATE = false, bool HALF = false,
-          bool TAG = false, bool BYTES = false, bool BQ = false>
+// FLAGS: as in walk_reg_one.  kOne (ONE_PASS): adjacency rows of one pass (the host checks ell_stride), no auxiliary graph -- the hop is straight-line code.
+template <int METRIC, int STEPS, uint32_t FLAGS>
 __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t qi, unsigned char* smem,
                                                  uint32_t* ovf_count, uint32_t* ovf_list, uint32_t* bitmap = nullptr) {
+    static_assert(!(FLAGS & ~(kOff32 | kOne | kAux | kLate | kHalf | kTag | kByteWalk | kByteQuery | kBitmap)), "a switch this walk does not have");
+    constexpr bool OFF32 = FLAGS & kOff32, ONE_PASS = FLAGS & kOne, AUX = FLAGS & kAux, BITMAP = FLAGS & kBitmap, LATE = FLAGS & kLate;
+    constexpr bool HALF = FLAGS & kHalf, TAG = FLAGS & kTag, BYTES = FLAGS & kByteWalk, BQ = FLAGS & kByteQuery;
     constexpr bool kEarlyLoad = (STEPS > 0);
     // 128-byte rows, and 192- / 256- / 384- / 512- / 576-byte rows with L2: two lanes per neighbour
     constexpr bool kPair = (STEPS == 8) || ((STEPS == 12 || STEPS == 16 || STEPS == 24 || STEPS == 32 || STEPS == 36) && METRIC == 0);
@@ -730,7 +735,7 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
     // the new ids only.  Requested before it -- one memory round trip less per hop, what a launch that is short of wavefronts wants
     // -- a 10 000-query launch over 576-byte rows at ef = 300 moved 35.8 GB for 23.5 GB of algorithmic bytes, 7 TB/s of HBM traffic:
     // there bandwidth, not latency, is what runs out (5.08 -> 4.15 ms with the rows requested late).  The host decides
-    // (WalkParams::late_rows, search_core.cpp).
+    // (WalkParams::late_rows, call_plan.cpp).
     constexpr bool kLateLoad = LATE;
     static_assert(!LATE || (kPair && STEPS >= 12), "LATE: pair-form instances over wide rows");
     constexpr bool late = LATE;
@@ -1074,25 +1079,30 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
     B.template finish<rerank_fused_deep(STEPS)>(p, qi, hops, dist_calc, edges, after_q, lane);
 }
 
+// The instance flags of walk_reg_kernel / walk_reg_big_kernel: a kernel and its table row (launch_util.h) both take them from here; the walk of a retry instance keeps kOff32 and kAux.
+constexpr uint32_t reg_flags(bool off32, bool retry, bool one, bool aux, bool late = false) { return flag_if(off32, kOff32) | flag_if(retry, kRetry) | flag_if(one, kOne) | flag_if(aux, kAux) | flag_if(late, kLate); }
+
 // (rows of 32 steps and more: at most two wavefronts per SIMD -- left to its occupancy heuristic the compiler squeezes the 512-byte-row
 // instance into 165 registers for a third wavefront and splits the row loads into dependent groups: 2.50 against 2.08 ms at ef = 140)
 template <int METRIC, int STEPS, bool OFF32, bool RETRY, bool AUX = false, bool ONE_PASS = false, bool LATE = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, STEPS >= 32 ? 2 : 8))) void walk_reg_big_kernel(WalkParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr uint32_t F = reg_flags(OFF32, RETRY, ONE_PASS, AUX, LATE);
     if constexpr (RETRY) {
-        retry_loop(p, [&](uint32_t qi) { walk_reg_big_one<METRIC, STEPS, OFF32, AUX>(p, qi, smem, p.ovf2_count, p.ovf2_list); });
+        retry_loop(p, [&](uint32_t qi) { walk_reg_big_one<METRIC, STEPS, F & (kOff32 | kAux)>(p, qi, smem, p.ovf2_count, p.ovf2_list); });
     } else {
-        walk_reg_big_one<METRIC, STEPS, OFF32, AUX, false, ONE_PASS, LATE>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
+        walk_reg_big_one<METRIC, STEPS, F>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
     }
 }
 
 template <int METRIC, int STEPS, bool OFF32, bool RETRY, int R, bool ONE_CHUNK = false, bool AUX = false>
 __global__ __launch_bounds__(64) void walk_reg_kernel(WalkParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr uint32_t F = reg_flags(OFF32, RETRY, ONE_CHUNK, AUX);
     if constexpr (RETRY) {
-        retry_loop(p, [&](uint32_t qi) { walk_reg_one<METRIC, STEPS, OFF32, R, false, AUX>(p, qi, smem, p.ovf2_count, p.ovf2_list); });
+        retry_loop(p, [&](uint32_t qi) { walk_reg_one<METRIC, STEPS, R, F & (kOff32 | kAux)>(p, qi, smem, p.ovf2_count, p.ovf2_list); });
     } else {
-        walk_reg_one<METRIC, STEPS, OFF32, R, ONE_CHUNK, AUX>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
+        walk_reg_one<METRIC, STEPS, R, F>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
     }
 }
 
@@ -1102,7 +1112,7 @@ __global__ __launch_bounds__(64) void walk_reg_kernel(WalkParams p) {
 template <int STEPS, bool LATE = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(GBNNS_WIDE_VGPRS))) void walk_reg_wide_kernel(WalkParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    walk_reg_one<0, STEPS, true, 1, true, false, false, true, LATE ? 1 : 0>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
+    walk_reg_one<0, STEPS, 1, kOff32 | kOne | kQueryLds | (LATE ? kLate : kNeverLate)>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
 }
 
 // First pass with HBM visited bitmaps on register lists (128-byte rows, L2 or dot): persistent wavefronts.
@@ -1115,7 +1125,7 @@ __global__ __launch_bounds__(64) void walk_bitmap_reg_kernel(WalkParams p) {
         if (lane_id() == 0) w = atomicAdd(p.fp_cursor, 1u);
         w = (uint32_t)__builtin_amdgcn_readfirstlane((int)w);
         if (w >= p.nq) break;
-        walk_reg_one<METRIC, 8, true, R, false, false, true>(p, walk_query_of(p, w), smem, p.ovf_count, p.ovf_list, bitmap);
+        walk_reg_one<METRIC, 8, R, kOff32 | kBitmap>(p, walk_query_of(p, w), smem, p.ovf_count, p.ovf_list, bitmap);
         wave_sync();
     }
 }
@@ -1129,7 +1139,7 @@ __global__ __launch_bounds__(64) void walk_bitmap_big_kernel(WalkParams p) {
         if (lane_id() == 0) w = atomicAdd(p.fp_cursor, 1u);
         w = (uint32_t)__builtin_amdgcn_readfirstlane((int)w);
         if (w >= p.nq) break;
-        walk_reg_big_one<METRIC, STEPS, true, false, true, ONE_PASS, LATE>(p, walk_query_of(p, w), smem, p.ovf_count, p.ovf_list, bitmap);
+        walk_reg_big_one<METRIC, STEPS, kOff32 | kBitmap | flag_if(ONE_PASS, kOne) | flag_if(LATE, kLate)>(p, walk_query_of(p, w), smem, p.ovf_count, p.ovf_list, bitmap);
         wave_sync();
     }
 }

@@ -17,16 +17,18 @@ namespace gbnns {
 
 namespace {
 
+constexpr uint32_t half_flags(bool one, bool late = false) { return kOff32 | kHalf | flag_if(one, kOne) | flag_if(late, kLate); }  // (a kernel and its table row both take their flags from here)
+
 template <int METRIC, int STEPS, int R, bool ONE_CHUNK>
 __global__ __launch_bounds__(64) void walk_reg_half_kernel(WalkParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    walk_reg_one<METRIC, STEPS, true, R, ONE_CHUNK, false, false, false, -1, true>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
+    walk_reg_one<METRIC, STEPS, R, half_flags(ONE_CHUNK)>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
 }
 
 template <int METRIC, int STEPS, bool ONE_PASS, bool LATE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8))) void walk_reg_big_half_kernel(WalkParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    walk_reg_big_one<METRIC, STEPS, true, false, false, ONE_PASS, LATE, true>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
+    walk_reg_big_one<METRIC, STEPS, half_flags(ONE_PASS, LATE)>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
 }
 
 // float32 -> binary16 (round to nearest even, subnormals kept) and back: one thread per coordinate of the 2-byte table, whose rows are
@@ -45,10 +47,8 @@ __global__ __launch_bounds__(256) void half_rows_convert_kernel(const float* src
     }
 }
 
-#define WALK_REG_HALF(M, S, R, ONE) \
-    {{WalkFamily::RegList, M, S, R, true, false, ONE, false, false, false, false, true}, WALK_KERNEL(walk_reg_half_kernel<M, S, R, ONE>)}
-#define WALK_BIG_HALF(M, S, ONE, LATE) \
-    {{WalkFamily::TwoList, M, S, 4, true, false, ONE, false, LATE, false, false, true}, WALK_KERNEL(walk_reg_big_half_kernel<M, S, ONE, LATE>)}
+#define WALK_REG_HALF(M, S, R, ONE) {{WalkFamily::RegList, M, S, R, half_flags(ONE)}, WALK_KERNEL(walk_reg_half_kernel<M, S, R, ONE>)}
+#define WALK_BIG_HALF(M, S, ONE, LATE) {{WalkFamily::TwoList, M, S, 4, half_flags(ONE, LATE)}, WALK_KERNEL(walk_reg_big_half_kernel<M, S, ONE, LATE>)}
 // one list register (loop-free expansion over one-pass adjacency rows, and the pass loop), two list registers, the two-list kernel
 #define WALK_HALF_SET(M, S) \
     WALK_REG_HALF(M, S, 1, true), WALK_REG_HALF(M, S, 1, false), WALK_REG_HALF(M, S, 2, false), WALK_BIG_HALF(M, S, true, false), WALK_BIG_HALF(M, S, false, false)

@@ -1026,9 +1026,9 @@ __global__ __launch_bounds__(64) void walk_hot_dot_big_kernel(WalkParams p) {
 
 // The instances by beam class (ef <= 64, <= 128, above: 1 / 2 list registers, the two-list form), adjacency width (one pass, or walk_hotw*: two)
 // and metric; walk_hot_spec_kernel where the plan asks for the rows before the visited test.
-#define WALK_HOT(M, R, ONE, SPEC, ...) {{WalkFamily::Hot, M, 0, R, false, false, ONE, false, false, SPEC}, WALK_KERNEL(__VA_ARGS__)}
-// (the byte instances: `bytes` set, everything else as their float twins)
-#define WALK_HOT_BYTES(R, ...) {{WalkFamily::Hot, 0, 0, R, false, false, true, false, false, false, false, false, false, false, true}, WALK_KERNEL(__VA_ARGS__)}
+#define WALK_HOT(M, R, ONE, SPEC, ...) {{WalkFamily::Hot, M, 0, R, flag_if(ONE, kOne) | flag_if(SPEC, kSpec)}, WALK_KERNEL(__VA_ARGS__)}
+// (the byte instances: kRrBytes set, everything else as their float twins)
+#define WALK_HOT_BYTES(R, ...) {{WalkFamily::Hot, 0, 0, R, kOne | kRrBytes}, WALK_KERNEL(__VA_ARGS__)}
 static const WalkEntry kEntries[] = {
     WALK_HOT_BYTES(1, walk_hot_bytes_kernel), WALK_HOT_BYTES(2, walk_hot2_bytes_kernel),
     WALK_HOT(0, 1, true, false, walk_hot_kernel), WALK_HOT(0, 1, true, true, walk_hot_spec_kernel), WALK_HOT(0, 1, false, false, walk_hotw_kernel),

@@ -1,5 +1,5 @@
 // walk_plan.cpp -- plan_walk: the one mapping from (shape, beam, pass) to a walk kernel instance and its LDS layout (walk_plan.h).  Plain host code.
-// The tuning rules (when the two-wavefront walk, the bitmap pass, late or speculative rows are WANTED) stay in search_core.cpp and sizing.cpp.
+// The tuning rules (when the two-wavefront walk, the bitmap pass, late or speculative rows are WANTED) stay in call_plan.cpp and sizing.cpp.
 #include "walk_plan.h"
 #include <cstdlib>
 
@@ -40,16 +40,11 @@ static bool half_serves(int metric, int steps, int regs, uint32_t n_entries) {
 
 // The tag instances (walk_tag.hip): the same shapes -- first pass of a compact index, one entry point per query, no auxiliary graph (plan_walk
 // checks those).  A tagged call outside them runs whole on the general kernel (WalkPlan::general_only).
-static bool tag_serves(int metric, int steps, int regs) {
-    if (steps == 8) return true;
-    return metric == 0 && (steps == 12 || steps == 16 || (steps == 36 && regs == 4));
-}
+static bool tag_serves(int metric, int steps, int regs) { return half_serves(metric, steps, regs, 1u); }
 
 // The bridge instances (walk_bridge.hip): the tag instances' domain cut to the register lists (ef <= 128) over rows of 32 / 48 / 64 floats.  The
 // two-list shapes (beams above 128, 144-float rows) of a bridged call run whole on the general kernel.
-static bool bridge_serves(int metric, int steps, int regs) {
-    return regs <= 2 && (steps == 8 || (metric == 0 && (steps == 12 || steps == 16)));
-}
+static bool bridge_serves(int metric, int steps, int regs) { return regs <= 2 && (steps == 8 || (metric == 0 && (steps == 12 || steps == 16))); }
 
 WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv& env) {
     const bool off32 = compact_index(p), aux = p.aux_ell != nullptr, retry = pass == WalkPass::Retry;
@@ -59,7 +54,7 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
     WalkPlan pl{};
     WalkInstance& k = pl.inst;
     pl.pass = pass;
-    // (gbnns_search_tagged: first pass only -- a tagged call has neither a retry nor a bitmap pass, search_core.cpp)
+    // (gbnns_search_tagged: first pass only -- a tagged call has neither a retry nor a bitmap pass, call_plan.cpp)
     const bool tag = p.tagged != 0 && pass == WalkPass::First;
     const bool bridge = tag && p.bridged != 0;  // GBNNS_FLAG_TAG_BRIDGE: a table and instances of their own
     pl.general_only = p.n_entries > 1 || (tag && (aux || !off32));
@@ -85,15 +80,14 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
         pl.lds_list = false;
         pl.general_only = !fast;
         if (fast) {
-            k = {regs == 4 ? WalkFamily::TwoList : WalkFamily::RegList, 0, 8, regs, true, false, one};
-            k.bwalk = true;
+            k = {regs == 4 ? WalkFamily::TwoList : WalkFamily::RegList, 0, 8, regs, kOff32 | flag_if(one, kOne) | kByteWalk};
             pl.packed = true;
             pl.lds_fixed = lds_fixed_bytes(ef, p.dstride, false, false, false);  // (the query: dstride = 128 floats, re-read from LDS every hop)
             pl.knows_quotient = true;  // (as the float pair-form instances of a compact index)
             // gbnns_search_byte_queries: the call brought its queries as bytes -- the integer twin of the same instance (walk_bytes_q.hip), for the
             // beam classes the handle's knob "byte_query_int" names.  Its query lives in registers: no query area in LDS.
             if (p.q_b && (p.bq_classes & (regs == 4 ? 4u : (uint32_t)regs))) {
-                k.bq = true;
+                k.flags |= kByteQuery;
                 pl.lds_fixed = lds_fixed_bytes(ef, 0u, false, false, false);
             }
         }
@@ -104,7 +98,7 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
         // of a compact index, the two-list walk for 256- and 576-byte rows with L2 (the reference's glove 300 -> 144), else the LDS-list walk.
         const bool reg = (metric == 0 || regs == 4) && ef <= kRegListMaxEf && (rows == 32u || ((rows == 64u || rows == 144u) && metric == 0 && regs == 4)) && off32 && !aux;
         const bool big = reg && regs == 4;
-        if (big) k = {WalkFamily::BitmapBig, metric, (int)rows / 4, 0, false, false, one, false, rows == 144u && late, false, false};
+        if (big) k = {WalkFamily::BitmapBig, metric, (int)rows / 4, 0, flag_if(one, kOne) | flag_if(rows == 144u && late, kLate)};
         else if (reg) k = {WalkFamily::BitmapReg, 0, 0, regs};
         else k = {WalkFamily::BitmapLds, metric, metric == 0 && rows == 32u ? 8 : 0};
         pl.lds_list = !reg;
@@ -128,12 +122,12 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
     pl.rr_in_table = true;
     pl.rr_base = (regs == 4 && !pl.lds_list) ? 0 : pl.lds_fixed;
     if (coop || hot) {  // (the two-wavefront walk on a shape it has no instance for: WalkFamily::None)
-        if (hot) k = {WalkFamily::Hot, metric, 0, regs, false, false, one, false, false, regs == 1 && metric == 0 && one && p.spec_rows && !GBNNS_HOT1_SPEC};
+        if (hot) k = {WalkFamily::Hot, metric, 0, regs, flag_if(one, kOne) | flag_if(regs == 1 && metric == 0 && one && p.spec_rows && !GBNNS_HOT1_SPEC, kSpec)};
         // a byte handle (gbnns_index_create_bytes) that wants its re-rank fused: where walk_hot_kernel / walk_hot2_kernel serve -- not the
         // speculative-rows instance, not walk_hotw*, not the two-list form -- and the chunk-pair core serves the rows (L2, d % 16 == 0), their
         // byte twins; every other first pass of such a handle runs unfused, followed by the stand-alone byte kernel (rerank_bytes.hip)
-        if (hot) k.bytes = p.bytes_dim != 0u && p.bytes_dim % 16u == 0u && metric == 0 && regs <= 2 && one && !k.spec;
-        else if (pl.coop_serves) k = {WalkFamily::Coop, 0, (int)rows / 4, 0, false, false, false, false, late};
+        if (hot) k.flags |= flag_if(p.bytes_dim != 0u && p.bytes_dim % 16u == 0u && metric == 0 && regs <= 2 && one && !(k.flags & kSpec), kRrBytes);
+        else if (pl.coop_serves) k = {WalkFamily::Coop, 0, (int)rows / 4, 0, flag_if(late, kLate)};
         return pl;
     }
     // steps the generic instances are unrolled for: 128-byte rows (both metrics); with L2 192-, 256- and 576-byte rows and, by beam, the
@@ -145,48 +139,48 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
     else if (rows == 96u && env.wide2 && regs == 4 && !pl.lds_list) steps = 24;
     else if (rows == 128u && env.wide2 && ef > kPlain512PairMinEf && !pl.lds_list) steps = 32;
     if (pl.lds_list) {
-        k = {WalkFamily::LdsList, metric, steps, 0, false, retry, false, false, false, false, pl.packed};
+        k = {WalkFamily::LdsList, metric, steps, 0, flag_if(retry, kRetry) | flag_if(pl.packed, kPacked)};
         pl.general_only = pl.general_only || tag;  // (no tag form)
         return pl;
     }
     if (regs == 4) {  // the two-list kernels, one instance for every ef up to 1 024
         const bool l2_unrolled = metric == 0 && steps >= 12;
-        k = {WalkFamily::TwoList, metric, steps, 4, off32, retry, false, aux};  // (aux: off32 -- over a non-compact index it is an LDS-list plan)
+        k = {WalkFamily::TwoList, metric, steps, 4, flag_if(off32, kOff32) | flag_if(retry, kRetry) | flag_if(aux, kAux)};  // (aux: off32 -- over a non-compact index it is an LDS-list plan)
         if (!aux && off32 && !retry) {
             // the common shape (compact index, adjacency rows of one pass; pair form: 32 slots per pass) gets the hop without the pass loop;
             // 384- / 512- / 576-byte rows have instances with the rows requested after the visited test, in the pass loop too
-            k.one = p.ell_stride <= ((steps == 8 || l2_unrolled) ? 32u : 64u);
-            k.late = l2_unrolled && steps >= 24 && late;
-            k.half = half && half_serves(metric, steps, 4, p.n_entries);
-            k.tag = tag && !bridge && tag_serves(metric, steps, 4);  // (no bridged two-list instance)
+            k.flags |= flag_if(p.ell_stride <= ((steps == 8 || l2_unrolled) ? 32u : 64u), kOne);
+            k.flags |= flag_if(l2_unrolled && steps >= 24 && late, kLate);
+            k.flags |= flag_if(half && half_serves(metric, steps, 4, p.n_entries), kHalf);
+            k.flags |= flag_if(tag && !bridge && tag_serves(metric, steps, 4), kTag);  // (no bridged two-list instance)
         }
-        pl.general_only = pl.general_only || (tag && !k.tag);
+        pl.general_only = pl.general_only || (tag && !(k.flags & kTag));
         return pl;
     }
     // one / two list registers.  384-byte rows: the pair form for the first pass of a compact index over one-pass adjacency rows
     // (two-pass ones: the one-register list only -- GD(M = 30) graph, rows of up to 45 slots, ef 40: 0.678 against 0.763 ms a lane per
     // row; the two-register list 1.254 / 1.834 at ef 80 / 120 against 1.255 / 1.814: stays on the run-time-length instance)
     if (rows == 96u && metric == 0 && env.wide2 && !retry && off32 && !aux && (one || (p.ell_stride <= 64u && regs == 1)) && !p.stamps_on) {
-        k = {WalkFamily::RegList, 0, 24, regs, true, false, one};
+        k = {WalkFamily::RegList, 0, 24, regs, kOff32 | flag_if(one, kOne)};
         pl.general_only = pl.general_only || tag;  // (no tag form)
         return pl;
     }
     if (steps >= 24) steps = 0;  // (576-byte rows at ef <= 128: the run-time-length instances)
-    k = {WalkFamily::RegList, metric, steps, regs, off32, retry, false, aux};
+    k = {WalkFamily::RegList, metric, steps, regs, flag_if(off32, kOff32) | flag_if(retry, kRetry) | flag_if(aux, kAux)};
     if (!aux && regs == 1 && off32 && !retry && !bridge && p.ell_stride <= ((steps == 8 || (metric == 0 && steps >= 12)) ? 32u : 64u)) {
         // ef <= 64, adjacency rows of one pass: a loop-free expansion; 192- / 256-byte rows with L2: the instance with the query in LDS
         // (half rows: the loop-free expansion of the list family itself -- the query-in-LDS instances have no half form)
-        if (metric == 0 && steps >= 12 && !p.stamps_on && !half && !tag && !p.generic_only) k = {WalkFamily::RegWide, 0, steps, 0, false, false, false, false, late};
-        else k.one = true;
+        if (metric == 0 && steps >= 12 && !p.stamps_on && !half && !tag && !p.generic_only) k = {WalkFamily::RegWide, 0, steps, 0, flag_if(late, kLate)};
+        else k.flags |= kOne;
     }
-    k.half = half && !aux && off32 && half_serves(metric, steps, regs, p.n_entries);
-    k.tag = tag && !aux && off32 && p.n_entries <= 1u && tag_serves(metric, steps, regs) && (!bridge || bridge_serves(metric, steps, regs));
-    k.bridge = bridge && k.tag;
-    if (k.bridge) {  // the staged ids of a bridged row sit between the query and the visited set
+    k.flags |= flag_if(half && !aux && off32 && half_serves(metric, steps, regs, p.n_entries), kHalf);
+    k.flags |= flag_if(tag && !aux && off32 && p.n_entries <= 1u && tag_serves(metric, steps, regs) && (!bridge || bridge_serves(metric, steps, regs)), kTag);
+    k.flags |= flag_if(bridge && (k.flags & kTag), kBridge);
+    if (k.flags & kBridge) {  // the staged ids of a bridged row sit between the query and the visited set
         pl.lds_fixed += (size_t)kBridgeStageIds * 4;
         pl.rr_base = pl.lds_fixed;
     }
-    pl.general_only = pl.general_only || (tag && !k.tag);
+    pl.general_only = pl.general_only || (tag && !(k.flags & kTag));
     return pl;
 }
 

@@ -1,5 +1,5 @@
 // walk_plan.h -- which walk kernel instance serves a pass over a shape, and the LDS layout that instance uses: decided in ONE place, plan_walk
-// (walk_plan.cpp: plain host code).  The host layer (search_core.cpp, sizing.cpp) sizes the visited set, the re-rank room and the retry pass from
+// (walk_plan.cpp: plain host code).  The host layer (call_plan.cpp, sizing.cpp) sizes the visited set, the re-rank room and the retry pass from
 // the plan; launch_walk (walk_l2.hip) launches the very instance the plan names: the LDS a kernel runs on is always the LDS of its own layout.
 #pragma once
 
@@ -60,29 +60,37 @@ enum class WalkFamily : uint8_t {
     BitmapLds,  // walk_bitmap_kernel<METRIC, STEPS>
 };
 
-// One kernel instance, named completely: its family and every template argument.  An argument the family does not have stays 0 / false.
+// The switches of a walk kernel instance, one bit each: the one vocabulary of plan_walk, the units' instance tables and the device templates
+// (walk_reg_one / walk_reg_big_one take them as one mask, walk_generic.h).  A switch the family does not have stays clear.
+enum WalkFlag : uint32_t {
+    kOff32 = 1u << 0,       // compact index: 32-bit byte offsets, 24-bit ids
+    kRetry = 1u << 1,       // the retry pass over the hand-overs
+    kOne = 1u << 2,         // adjacency rows of one 32-slot pass (ONE_PASS / ONE_CHUNK; the hot family: its one-pass instances, else walk_hotw*)
+    kAux = 1u << 3,         // auxiliary-graph hop
+    kLate = 1u << 4,        // rows requested after the visited test (WalkParams::late_rows)
+    kSpec = 1u << 5,        // walk_hot_spec_kernel: rows requested before the visited test (spec_rows)
+    kPacked = 1u << 6,      // LDS-list family: visited set of 24-bit ids
+    kHalf = 1u << 7,        // the hop's rows come from the 2-byte table (WalkParams::db_h): walk_reg_half_kernel / walk_reg_big_half_kernel (walk_half.hip)
+    kTag = 1u << 8,         // the hop tests every neighbour's tag word against the query's (WalkParams::tags / qtags): walk_reg_tag_kernel / walk_reg_big_tag_kernel (walk_tag.hip)
+    kBridge = 1u << 9,      // (with kTag) a disallowed neighbour is looked through, its allowed neighbours staged in LDS in its place: walk_bridge_kernel (walk_bridge.hip)
+    kRrBytes = 1u << 10,    // the fused re-rank reads uint8 rows (WalkParams::rr_db_b, a byte handle): walk_hot_bytes_kernel / walk_hot2_bytes_kernel (walk_hot.hip)
+    kByteWalk = 1u << 11,   // the WALKED rows are uint8 (WalkParams::db_b, GBNNS_FLAG_BYTE_WALK): walk_reg_bytes_kernel / walk_reg_big_bytes_kernel (walk_bytes.hip)
+    kByteQuery = 1u << 12,  // (with kByteWalk) the queries are uint8 too (WalkParams::q_b, gbnns_search_byte_queries), the distance is integer: beam_u8_kernel / beam_u8_big_kernel (walk_bytes_q.hip)
+    kBitmap = 1u << 13,     // from here on the device templates only, never in a WalkInstance (its family says as much): visited set = one bit per node in HBM (walk_bitmap_*_kernel)
+    kQueryLds = 1u << 14,   // walk_reg_one: the lane's query pieces are re-read from LDS every hop (walk_reg_wide_kernel)
+    kNeverLate = 1u << 15,  // walk_reg_one: rows never requested after the visited test (without it and without kLate: by WalkParams::late_rows)
+};
+__host__ __device__ constexpr uint32_t flag_if(bool on, uint32_t flag) { return on ? flag : 0u; }
+
+// One kernel instance, named completely: its family and every template argument.  An argument the family does not have stays 0 / clear.
 struct WalkInstance {
     WalkFamily family;
-    int metric;   // 0 = L2, 1 = negative dot
-    int steps;    // 16-byte steps of a row the distance is unrolled for (0: run-time length)
-    int regs;     // list registers per lane: 1 (ef <= 64), 2 (ef <= 128); 4 = the two-list structure
-    bool off32;   // compact index: 32-bit byte offsets, 24-bit ids
-    bool retry;
-    bool one;     // adjacency rows of one 32-slot pass (ONE_PASS / ONE_CHUNK; the hot family: its one-pass instances, else walk_hotw*)
-    bool aux;     // auxiliary-graph hop
-    bool late, spec;  // rows requested after the visited test (WalkParams::late_rows) / walk_hot_spec_kernel: before it (spec_rows)
-    bool packed;  // LDS-list family: visited set of 24-bit ids
-    bool half;    // the hop's rows come from the 2-byte table (WalkParams::db_h): walk_reg_half_kernel / walk_reg_big_half_kernel (walk_half.hip)
-    bool tag;     // the hop tests every neighbour's tag word against the query's (WalkParams::tags / qtags): walk_reg_tag_kernel / walk_reg_big_tag_kernel (walk_tag.hip)
-    bool bridge;  // (with tag) a disallowed neighbour is looked through, its allowed neighbours staged in LDS in its place: walk_bridge_kernel (walk_bridge.hip)
-    bool bytes;   // the fused re-rank reads uint8 rows (WalkParams::rr_db_b, a byte handle): walk_hot_bytes_kernel / walk_hot2_bytes_kernel (walk_hot.hip)
-    bool bwalk;   // the WALKED rows are uint8 (WalkParams::db_b, GBNNS_FLAG_BYTE_WALK): walk_reg_bytes_kernel / walk_reg_big_bytes_kernel (walk_bytes.hip)
-    bool bq;      // (with bwalk) the queries are uint8 too (WalkParams::q_b, gbnns_search_byte_queries), the distance is integer: beam_u8_kernel / beam_u8_big_kernel (walk_bytes_q.hip)
+    int metric;      // 0 = L2, 1 = negative dot
+    int steps;       // 16-byte steps of a row the distance is unrolled for (0: run-time length)
+    int regs;        // list registers per lane: 1 (ef <= 64), 2 (ef <= 128); 4 = the two-list structure
+    uint32_t flags;  // WalkFlag bits
 };
-inline bool operator==(const WalkInstance& a, const WalkInstance& b) {
-    return a.family == b.family && a.metric == b.metric && a.steps == b.steps && a.regs == b.regs && a.off32 == b.off32 && a.retry == b.retry && a.one == b.one &&
-           a.aux == b.aux && a.late == b.late && a.spec == b.spec && a.packed == b.packed && a.half == b.half && a.tag == b.tag && a.bridge == b.bridge && a.bytes == b.bytes && a.bwalk == b.bwalk && a.bq == b.bq;
-}
+inline bool operator==(const WalkInstance& a, const WalkInstance& b) { return a.family == b.family && a.metric == b.metric && a.steps == b.steps && a.regs == b.regs && a.flags == b.flags; }
 
 struct WalkPlan {
     WalkPass pass;

@@ -13,23 +13,23 @@ namespace gbnns {
 
 namespace {
 
-// (LATE = 0: the rows always requested before the visited test -- with both orders in one kernel the wait ahead of the tag test covers the rows too)
+constexpr uint32_t tag_flags(bool one, bool late = false) { return kOff32 | kTag | flag_if(one, kOne) | flag_if(late, kLate); }  // (a kernel and its table row both take their flags from here)
+
+// (kNeverLate: the rows always requested before the visited test -- with both orders in one kernel the wait ahead of the tag test covers the rows too)
 template <int METRIC, int STEPS, int R, bool ONE_CHUNK>
 __global__ __launch_bounds__(64) void walk_reg_tag_kernel(WalkParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    walk_reg_one<METRIC, STEPS, true, R, ONE_CHUNK, false, false, false, 0, false, true>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
+    walk_reg_one<METRIC, STEPS, R, tag_flags(ONE_CHUNK) | kNeverLate>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
 }
 
 template <int METRIC, int STEPS, bool ONE_PASS, bool LATE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8))) void walk_reg_big_tag_kernel(WalkParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    walk_reg_big_one<METRIC, STEPS, true, false, false, ONE_PASS, LATE, false, true>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
+    walk_reg_big_one<METRIC, STEPS, tag_flags(ONE_PASS, LATE)>(p, walk_query_of(p, blockIdx.x), smem, p.ovf_count, p.ovf_list);
 }
 
-#define WALK_REG_TAG(M, S, R, ONE) \
-    {{WalkFamily::RegList, M, S, R, true, false, ONE, false, false, false, false, false, true}, WALK_KERNEL(walk_reg_tag_kernel<M, S, R, ONE>)}
-#define WALK_BIG_TAG(M, S, ONE, LATE) \
-    {{WalkFamily::TwoList, M, S, 4, true, false, ONE, false, LATE, false, false, false, true}, WALK_KERNEL(walk_reg_big_tag_kernel<M, S, ONE, LATE>)}
+#define WALK_REG_TAG(M, S, R, ONE) {{WalkFamily::RegList, M, S, R, tag_flags(ONE)}, WALK_KERNEL(walk_reg_tag_kernel<M, S, R, ONE>)}
+#define WALK_BIG_TAG(M, S, ONE, LATE) {{WalkFamily::TwoList, M, S, 4, tag_flags(ONE, LATE)}, WALK_KERNEL(walk_reg_big_tag_kernel<M, S, ONE, LATE>)}
 // one list register (loop-free expansion over one-pass adjacency rows, and the pass loop), two list registers, the two-list kernel
 #define WALK_TAG_SET(M, S) \
     WALK_REG_TAG(M, S, 1, true), WALK_REG_TAG(M, S, 1, false), WALK_REG_TAG(M, S, 2, false), WALK_BIG_TAG(M, S, true, false), WALK_BIG_TAG(M, S, false, false)

@@ -3,6 +3,8 @@
 //                                         the kernels that ran -- through call_plan(): the same first pass, grid, LDS, retry action, re-rank
 //   call_plan_units grid <dims> <beams>   the conditions the plan guarantees by construction, over dims x beams (comma lists) x both metrics x
 //                                         nq in {96, 2 048, 16 384} x untagged / tagged / byte-walk calls x no history / a calm history
+//   call_plan_units walkgrid <dims> <beams>  plan_walk() over the cross product of every input it reads (walk_grid below): the plan count and one
+//                                         digest of the formatted plans per (feature variant, pass), compared with tests/golden/walk_plan_grid.txt
 // Built by tests/test_call_plan_units.py from the three units' sources; the kernel tables' names (walk_plan_name), the visited set's byte counts
 // and the knob defaults come from the library.  No HIP call.
 #include "../../gbnns_dim_red_amd/csrc/call_plan.h"
@@ -144,9 +146,76 @@ static int grid(const char* dims_csv, const char* beams_csv) {
     return (g_failed || plans == 0) ? 1 : 0;
 }
 
+// ---- walkgrid --------------------------------------------------------------------------------------------------------------------------------
+// Fifteen feature variants over an otherwise zeroed WalkParams; `dim` is the grid's dimension (dstride = dim rounded up to 4).
+static const char* const kVariants[] = {"plain", "coop", "late_rows", "spec_rows", "half_rows", "tagged", "tagged+bridged", "generic_only", "bytes_dim=128", "bytes_dim=40",
+                                        "walk_bytes d=128", "walk_bytes q_b classes=7", "walk_bytes q_b classes=2", "stamps_on", "rr_reserve=160"};
+static void set_variant(WalkParams& p, int v) {
+    static const uint8_t byte_queries[16] = {0};
+    switch (v) {
+        case 1: p.coop = 1; break;
+        case 2: p.late_rows = 1; break;
+        case 3: p.spec_rows = 1; break;
+        case 4: p.half_rows = 1; break;
+        case 5: p.tagged = 1; break;
+        case 6: p.tagged = 1; p.bridged = 1; break;
+        case 7: p.generic_only = 1; break;
+        case 8: p.bytes_dim = 128; break;
+        case 9: p.bytes_dim = 40; break;
+        case 10: p.walk_bytes = 1; p.dim = p.dstride = 128; break;
+        case 11: p.walk_bytes = 1; p.q_b = byte_queries; p.bq_classes = 7; break;
+        case 12: p.walk_bytes = 1; p.q_b = byte_queries; p.bq_classes = 2; break;
+        case 13: p.stamps_on = 1; break;
+        case 14: p.rr_reserve = 160; break;
+        default: break;
+    }
+}
+
+static int walk_grid(const char* dims_csv, const char* beams_csv) {
+    static const uint32_t aux_rows[16] = {0};
+    static const char* const pass_names[] = {"First", "Bitmap", "Retry"};
+    const WalkEnv envs[] = {{true, false}, {false, true}};  // {wide2, stamps_generic}
+    const std::vector<int> dims = ints(dims_csv), beams = ints(beams_csv);
+    long long plans = 0;
+    std::string lines;
+    for (int v = 0; v < 15; ++v)
+        for (int pass = 0; pass < 3; ++pass) {
+            uint64_t digest = 0xcbf29ce484222325ull;  // FNV-1a, 64 bits, over the lines of this (variant, pass)
+            for (const WalkEnv& env : envs)
+                for (int metric = 0; metric < 2; ++metric)
+                    for (int dim : dims)
+                        for (uint32_t n : {3000u, 0xFEFFFFu, 0xFF0000u, 0x1000000u})  // either side of the two-wavefront walk's limit and of the 24-bit ids
+                            for (uint32_t ell : {32u, 64u, 96u})
+                                for (int aux = 0; aux < 2; ++aux)
+                                    for (int ef : beams)
+                                        for (uint32_t entries = 1; entries <= 2; ++entries)
+                                            for (int wide = 0; wide < 2; ++wide) {
+                                                WalkParams p{};
+                                                p.dim = (uint32_t)dim; p.dstride = ((uint32_t)dim + 3u) / 4u * 4u; p.n = n; p.ell_stride = ell; p.ef = ef;
+                                                p.n_entries = entries; p.force_wide = wide;
+                                                if (aux) { p.aux_ell = aux_rows; p.aux_stride = 16; }
+                                                set_variant(p, v);
+                                                const WalkPlan pl = plan_walk(p, metric, (WalkPass)pass, env);
+                                                const char* name = walk_plan_name(pl);
+                                                char line[512];
+                                                const int len = std::snprintf(line, sizeof line, "%s %d %zu %d %d %d %d %d %zu %d\n", name ? name : "-", (int)pl.inst.family, pl.lds_fixed,
+                                                                              (int)pl.packed, (int)pl.knows_quotient, (int)pl.lds_list, (int)pl.coop_serves, (int)pl.general_only,
+                                                                              pl.rr_base, (int)pl.rr_in_table);
+                                                for (int i = 0; i < len; ++i) digest = (digest ^ (unsigned char)line[i]) * 0x100000001b3ull;
+                                                ++plans;
+                                            }
+            char out[128];
+            std::snprintf(out, sizeof out, "%s | %s | %016llx\n", kVariants[v], pass_names[pass], (unsigned long long)digest);
+            lines += out;
+        }
+    std::printf("walkgrid: %lld plans\n%s", plans, lines.c_str());
+    return plans == 0 ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
     if (argc == 3 && std::string(argv[1]) == "golden") return golden(argv[2]);
     if (argc == 4 && std::string(argv[1]) == "grid") return grid(argv[2], argv[3]);
-    std::printf("usage: call_plan_units golden <file> | grid <dims> <beams>\n");
+    if (argc == 4 && std::string(argv[1]) == "walkgrid") return walk_grid(argv[2], argv[3]);
+    std::printf("usage: call_plan_units golden <file> | grid <dims> <beams> | walkgrid <dims> <beams>\n");
     return 2;
 }

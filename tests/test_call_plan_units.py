@@ -48,3 +48,15 @@ def test_plan_conditions_over_the_census_grid(unit):
     out = unit("grid", ",".join(str(d) for d in wi.DIMS), ",".join(str(e) for e in wi.BEAMS))
     plans = 3 * 2 * len(wi.DIMS) * len(wi.BEAMS) * 3 * 2
     assert "grid: %d plans, 0 failed" % plans in out, out
+
+
+def test_plan_walk_is_the_recorded_function(unit):
+    """plan_walk over the cross product of everything it reads -- both environments x metric x dim x n either side of the two-wavefront walk's
+    and the 24-bit ids' limits x adjacency width x auxiliary graph x beam x entry points x force_wide, for each of three passes and fifteen
+    feature variants: per (variant, pass) one digest of every plan's kernel name, family and layout facts.  tests/golden/walk_plan_grid.txt was
+    recorded by this driver built against the commit its first line names, before WalkInstance's switches became one set of named flags."""
+    with open(os.path.join(ROOT, "tests", "golden", "walk_plan_grid.txt")) as f:
+        want = [line.rstrip("\n") for line in f if not line.startswith("#")]
+    assert want[0] == "walkgrid: %d plans" % (15 * 3 * 2 * 2 * len(wi.DIMS) * 4 * 3 * 2 * len(wi.BEAMS) * 2 * 2) and len(want) == 1 + 15 * 3
+    got = unit("walkgrid", ",".join(str(d) for d in wi.DIMS), ",".join(str(e) for e in wi.BEAMS)).splitlines()
+    assert got == want, [pair for pair in zip(got, want) if pair[0] != pair[1]]
