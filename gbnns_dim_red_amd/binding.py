@@ -50,6 +50,7 @@ SYMBOLS = [
     "gbnns_debug_project_plan", "gbnns_index_project_last",
     "gbnns_index_order_last", "gbnns_debug_query_order",
     "gbnns_debug_rerank_plan",
+    "gbnns_index_create_half_base", "gbnns_index_is_half_base", "gbnns_debug_half_base_plan",
 ]
 
 
@@ -215,6 +216,9 @@ def load_library():
     lib.gbnns_debug_byte_plan.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int,
                                           C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(C.c_int)]
     lib.gbnns_debug_rerank_plan.argtypes = [C.c_int, C.c_uint32, C.c_int, C.c_char_p, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.gbnns_index_create_half_base.argtypes = [C.POINTER(_IndexDesc), C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.gbnns_index_is_half_base.argtypes = [C.c_void_p]
+    lib.gbnns_debug_half_base_plan.argtypes = [C.c_int, C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.gbnns_index_d_low.argtypes = [C.c_void_p]
     lib.gbnns_index_d_low.restype = C.c_uint32
     _lib = lib
@@ -376,6 +380,16 @@ def rerank_plan(metric, d, bytes=False):
     return name.value.decode(), int(deep.value), bool(fused.value)
 
 
+def half_base_plan(metric, d):
+    """gbnns_debug_half_base_plan (no device needed): (name, deep, fused) -- the kernel Index.rerank launches on the binary16 rows of a half-base
+    handle (Index(db=<float16>)) of d coordinates, the 16-byte row loads a lane of it has in flight in the first loop of its ladder (0: a lane
+    per row), and fused, which is always False: no walk kernel re-ranks half rows, a re-rank launch follows every first pass."""
+    name = C.create_string_buffer(128)
+    deep, fused = C.c_int(0), C.c_int(0)
+    _check(load_library().gbnns_debug_half_base_plan(metric, d, name, 128, C.byref(deep), C.byref(fused)))
+    return name.value.decode(), int(deep.value), bool(fused.value)
+
+
 def knn_bytes_plan(n, n_q, d, k):
     """gbnns_debug_knn_bytes_plan (no device needed): what exact_knn does with uint8 inputs of that shape under the current knn_chunk /
     knn_pool_min_k / knn_slab knobs -- dict(dp, cap, first_rows, max_chunk, pool, slab); slab: knn_slab(n_q, k, bytes=True)."""
@@ -473,6 +487,19 @@ def _is_u8(x):
         import torch
         return x.dtype == torch.uint8
     return isinstance(x, np.ndarray) and x.dtype == np.uint8
+
+
+def _is_f16(x):
+    if _is_dev(x):
+        import torch
+        return x.dtype == torch.float16
+    return isinstance(x, np.ndarray) and x.dtype == np.float16
+
+
+def _float32_queries(ix, queries):
+    """float16 queries on a half-base handle: TypeError (the handle's kind alone is read, before anything touches the library)."""
+    if _is_f16(queries) and getattr(ix, "is_half_base", False):
+        raise TypeError("float16 queries: a half-base handle (Index(db=<float16>)) takes float32 queries -- the query is never rounded")
 
 
 def _ptr(x):
@@ -713,7 +740,11 @@ class Index:
     """One dataset resident in HBM (gbnns_index).  db / db_low / net may be numpy arrays (copied
     to the device) or torch CUDA tensors (borrowed; kept alive by this object).
     db of dtype uint8 (numpy or torch): a byte handle (gbnns_index_create_bytes) -- the original-space table stays uint8 on the device and
-    every search, rerank and rerank_topk returns what the index over db.astype(float32) returns, bit for bit; needs db_low, no MODE_PLAIN."""
+    every search, rerank and rerank_topk returns what the index over db.astype(float32) returns, bit for bit; needs db_low, no MODE_PLAIN.
+    db of dtype float16 (numpy or torch): a half-base handle (gbnns_index_create_half_base) -- the original-space table stays IEEE binary16 on
+    the device, half the bytes of the float32 table, and every search, rerank and rerank_topk returns what the index over db.astype(float32)
+    returns, bit for bit; needs db_low (the library's error without it), no MODE_PLAIN, no exact_knn / search_auto, float32 queries only.  The
+    library rounds nothing itself: float32 data is rounded by the caller -- round_to_half(a)[0].view(np.float16) is that table."""
 
     def __init__(self, db, graph_offsets, graph_nbrs, db_low=None, net=None, metric=METRIC_L2,
                  device=0):
@@ -721,8 +752,8 @@ class Index:
         self._lib = lib
         self._h = C.c_void_p()
         dev = _is_dev(db)
-        is_bytes = _is_u8(db)
-        db = _prep(db, np.uint8, "uint8") if is_bytes else _prep(db, np.float32, "float32")
+        is_bytes, is_half = _is_u8(db), _is_f16(db)
+        db = _prep(db, np.uint8, "uint8") if is_bytes else (_prep(db, np.float16, "float16") if is_half else _prep(db, np.float32, "float32"))
         db_low = _prep(db_low, np.float32, "float32")
         if db_low is not None and _is_dev(db_low) != dev:
             raise TypeError("db and db_low must live in the same memory kind")
@@ -746,11 +777,13 @@ class Index:
         desc = _IndexDesc(
             struct_size=C.sizeof(_IndexDesc), device=device, metric=metric,
             mem_kind=MEM_DEVICE if dev else MEM_HOST, n=self.n, d=self.d, d_low=self.d_low,
-            d_hidden=self.d_hidden, db=None if is_bytes else _ptr(db), db_low=_ptr(db_low), graph_offsets=_ptr(off),
+            d_hidden=self.d_hidden, db=None if is_bytes or is_half else _ptr(db), db_low=_ptr(db_low), graph_offsets=_ptr(off),
             graph_nbrs=_ptr(nbr), net_l1=_ptr(net[0]) if net else None,
             net_l2=_ptr(net[1]) if net else None, net_l3=_ptr(net[2]) if net else None)
         if is_bytes:
             _check(lib.gbnns_index_create_bytes(C.byref(desc), _ptr(db), C.byref(self._h)))
+        elif is_half:
+            _check(lib.gbnns_index_create_half_base(C.byref(desc), _ptr(db), C.byref(self._h)))
         else:
             _check(lib.gbnns_index_create(C.byref(desc), C.byref(self._h)))
         self._in_flight = collections.deque(maxlen=8)  # (inputs, outputs) of the deferred calls not yet joined
@@ -763,6 +796,12 @@ class Index:
     def is_bytes(self):
         """gbnns_index_is_bytes: the original-space table is uint8 on the device (created from a uint8 db)."""
         return bool(self._lib.gbnns_index_is_bytes(self._h))
+
+    @property
+    def is_half_base(self):
+        """gbnns_index_is_half_base: the original-space table is binary16 on the device (created from a float16 db)."""
+        return bool(self._lib.gbnns_index_is_half_base(self._h))
+
 
     def set_aux_graph(self, offsets, nbrs):
         """The reference's auxiliary_graph (host CSR); None, None removes it."""
@@ -841,6 +880,7 @@ class Index:
         bit, that of the same call with queries.astype(float32); same keywords.  On a float handle they raise TypeError (exact_knn's mixed-pair
         rule)."""
         top_k = top_k or 0
+        _float32_queries(self, queries)
         u8 = _is_u8(queries)
         if u8 and not self.is_bytes:
             raise TypeError("uint8 queries need a byte handle (Index(db=<uint8>)); widen them for a float handle")
@@ -991,6 +1031,7 @@ class Index:
 
     def rerank(self, queries, cand, count=None):
         """getRealNearest over a batch (host buffers): cand [nq x stride] in pop order."""
+        _float32_queries(self, queries)
         q = _host(queries, np.float32)
         cand = _host(cand, np.uint32)
         count = None if count is None else _host(count, np.int32)
@@ -1002,6 +1043,7 @@ class Index:
     def rerank_topk(self, queries, cand, k, count=None, want_dist=True):
         """gbnns_rerank_topk (host buffers): the k best of each row of cand [nq x stride] (pop order) -> (ids, dist) [nq x k],
         ascending (distance, pop index); 0xFFFFFFFF / +inf from column count on.  ids[:, 0] == rerank(queries, cand, count)."""
+        _float32_queries(self, queries)
         q = _host(queries, np.float32)
         cand = _host(cand, np.uint32)
         count = None if count is None else _host(count, np.int32)

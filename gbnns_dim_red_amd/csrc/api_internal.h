@@ -182,8 +182,12 @@ struct gbnns_index {
     // gbnns_index_create_bytes: the original-space table as uint8 rows of d_pad BYTES (d_pad = round_up(d, 16) on such a handle: the bytes
     // of a row and the floats of a staged re-rank query), zero padded, 16-byte aligned; borrowed or db_b_own's.  No float copy exists.
     const uint8_t* db_b = nullptr;
+    // gbnns_index_create_half_base: the original-space table as binary16 rows of d_pad HALVES (d_pad = round_up(d, 8) on such a handle: the
+    // halves of a row and the floats of a staged re-rank query), zero padded, 16-byte aligned; borrowed or db_h_base_own's.  No float copy
+    // exists.  (Not low_half: that is the WALKED table of GBNNS_FLAG_HALF_ROWS, which such a handle may have as well.)
+    const uint16_t* db_h_base = nullptr;
     const float* db_low = nullptr;  // [n x dl_pad]
-    DevBuf db_own, db_b_own, db_low_own, ell, net, aux_ell;
+    DevBuf db_own, db_b_own, db_h_base_own, db_low_own, ell, net, aux_ell;
     DevBuf net_mfma;                // the net repacked for the one-launch matrix-core projection (filled on the option's first use)
     // GBNNS_FLAG_HALF_ROWS (gbnns_index_enable_half_rows): R = float32(float16(db_low)) as binary16 rows [n x round_up(d_low, 8)], zero padded,
     // and as float32 rows in db_low's own layout [n x dl_pad]; db_low itself stays, for the searches without the flag

@@ -38,10 +38,10 @@ namespace {
 size_t granules(size_t bytes) { return (bytes + kLdsGran - 1) / kLdsGran * kLdsGran; }
 size_t first_lds(const WalkParams& w, const WalkPlan& plan) { return plan.lds_fixed + walk_hash_bytes(w.hash_cap, plan.hash_form(w.vs_shr)); }
 
-// sizing statistics are kept per (ef, mode, aux, wide, byte instances: no retry pass behind them, half rows: another table, other walks; tagged: other graphs, shorter walks; bridged: two to three times the rows claimed; knob "hot" = 0: other kernels)
+// sizing statistics are kept per (ef, mode, aux, wide, byte instances: no retry pass behind them, half rows: another table, other walks; tagged: other graphs, shorter walks; bridged: two to three times the rows claimed; knob "hot" = 0: other kernels; a half-base handle: a class of its own, like the byte handle's)
 int stats_key(const CallFacts& f, const WalkParams& w) {
     const bool aux = f.aux_stride != 0;
-    return ((f.ef * 8 + f.mode * 2 + (aux ? 1 : 0)) * 2 + w.force_wide) | (w.half_rows ? 1 << 30 : 0) | (w.tagged ? 1 << 29 : 0) | (w.bridged ? 1 << 27 : 0) | (w.generic_only ? 1 << 28 : 0) | (w.bytes_dim ? 1 << 26 : 0) | (w.walk_bytes ? 1 << 25 : 0);
+    return ((f.ef * 8 + f.mode * 2 + (aux ? 1 : 0)) * 2 + w.force_wide) | (w.half_rows ? 1 << 30 : 0) | (w.tagged ? 1 << 29 : 0) | (w.bridged ? 1 << 27 : 0) | (w.generic_only ? 1 << 28 : 0) | (w.bytes_dim ? 1 << 26 : 0) | (w.walk_bytes ? 1 << 25 : 0) | (f.half_base ? 1 << 24 : 0);
 }
 
 // A small batch that runs ALONE (the reference's gist row: 1 000 queries per synchronous call, final_test.cpp:87) on the shapes that
@@ -168,7 +168,10 @@ CallPlan call_plan(const CallFacts& f, const SizingHistory& h) {
     // wavefront re-ranks its own query when its walk ends; no re-rank launch.  Needs the pair form
     // (d % 8 == 0) and room for the original-space query in the walk kernels' LDS.
     // (rerank_plan.h: the pair form; L2: d % 8 == 4 too -- glove's 300 -- its last 16-byte step is the even lane's alone)
-    const bool want_fuse = bytes ? w.bytes_dim != 0u : (!plain && rerank_plan(f.metric, f.d, false).fuses && !(f.flags & GBNNS_FLAG_NO_FUSED_RERANK));
+    // A half-base handle (gbnns_index_create_half_base): rerank_half_plan never fuses -- every first pass runs as on a float handle with
+    // GBNNS_FLAG_NO_FUSED_RERANK, the stand-alone half kernel behind it, and sets no LDS aside for a re-rank query
+    const bool want_fuse = f.half_base ? rerank_half_plan(f.metric, f.d).fuses
+                                       : (bytes ? w.bytes_dim != 0u : (!plain && rerank_plan(f.metric, f.d, false).fuses && !(f.flags & GBNNS_FLAG_NO_FUSED_RERANK)));
     w.rr_reserve = (want_fuse && !bytes) ? (uint32_t)f.d_pad * 4u : 0u;  // (the bitmap pass has no byte instance)
     cp.bitmap_per_cu = bitmap_rule(f, w, plan, fps.form);
     cp.bitmap_pass = cp.bitmap_per_cu != 0;

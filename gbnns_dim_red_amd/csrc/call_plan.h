@@ -50,7 +50,7 @@ struct CallFacts {
     // the handle
     int metric;
     uint64_t n;
-    uint32_t d, d_pad;        // original space (d_pad: floats of a row; on a byte handle its bytes)
+    uint32_t d, d_pad;        // original space (d_pad: floats of a row; on a byte handle its bytes, on a half-base handle its halves)
     uint32_t ell_stride;
     uint32_t aux_stride;      // of the auxiliary graph a GBNNS_FLAG_AUX_GRAPH call walks; 0: none
     bool byte_handle;         // gbnns_index_create_bytes
@@ -71,6 +71,8 @@ struct CallFacts {
     bool in_flight;           // on a lane's own stream: a batch of a deferred call
     bool sync_host;           // the call runs alone and is waited for
     bool stamps_on;           // diagnostic builds (GBNNS_STAMPS)
+    // the handle again (last: aggregate initialisers of the members above stay valid)
+    bool half_base = false;   // gbnns_index_create_half_base: binary16 original rows (d_pad: their halves) -- no walk kernel reads them, the re-rank is never fused
 };
 
 // sizing.cpp: the first pass's visited set for this batch -- sets w.vs_shr / hash_cap / hash_limit / spec_rows / spec_from

@@ -639,6 +639,9 @@ int knn_gather_call(gbnns_index* ix, const T* table, const T* queries, uint64_t 
 int knn_index_refuse(const char* fn, gbnns_index* ix, const float* queries, const uint8_t* queries_u8, const uint32_t* query_tags) {
     if ((queries != nullptr) == (queries_u8 != nullptr)) return fail(GBNNS_ERR_INVALID, "%s: exactly one of queries / queries_u8", fn);
     if (!ix) return fail(GBNNS_ERR_INVALID, "null argument");
+    if (ix->db_h_base)
+        return fail(GBNNS_ERR_UNSUPPORTED, "%s on a half-base handle (gbnns_index_create_half_base): there is no exact scan over the resident binary16 rows; "
+                    "widen the table and call gbnns_exact_knn", fn);
     if (queries_u8 && !ix->db_b) return fail(GBNNS_ERR_INVALID, "%s: queries_u8 needs a byte handle (gbnns_index_create_bytes)", fn);
     if (queries && ix->db_b)
         return fail(GBNNS_ERR_UNSUPPORTED, "%s: float queries on a byte handle: there is no mixed-pair scan (uint8 rows against "

@@ -391,15 +391,22 @@ int gbnns_device_count(void) {
 
 void gbnns_free(void* p) { std::free(p); }
 
-// gbnns_index_create (db_bytes == nullptr, !bytes) and gbnns_index_create_bytes
-static int index_create(const gbnns_index_desc* desc, const uint8_t* db_bytes, bool bytes, gbnns_index** out) {
+// gbnns_index_create (db_bytes == nullptr, !bytes), gbnns_index_create_bytes and gbnns_index_create_half_base (db_half: the table, !bytes)
+static int index_create(const gbnns_index_desc* desc, const uint8_t* db_bytes, bool bytes, gbnns_index** out, const uint16_t* db_half = nullptr,
+                        bool half_base = false) {
     if (!desc || !out) return fail(GBNNS_ERR_INVALID, "null argument");
     *out = nullptr;
     if (desc->struct_size != sizeof(gbnns_index_desc))
         return fail(GBNNS_ERR_INVALID, "gbnns_index_desc.struct_size mismatch (%u != %zu)",
                     desc->struct_size, sizeof(gbnns_index_desc));
     if (desc->n == 0 || desc->n >= (1ull << 31)) return fail(GBNNS_ERR_INVALID, "n must be in [1, 2^31)");
-    if (desc->d == 0 || (!bytes && !desc->db)) return fail(GBNNS_ERR_INVALID, "db / d missing");
+    if (desc->d == 0 || (!bytes && !half_base && !desc->db)) return fail(GBNNS_ERR_INVALID, "db / d missing");
+    if (half_base) {
+        if (desc->db) return fail(GBNNS_ERR_INVALID, "gbnns_index_create_half_base: desc->db must be NULL (the table is db_half)");
+        if (!db_half) return fail(GBNNS_ERR_INVALID, "gbnns_index_create_half_base: db_half missing");
+        if (desc->d_low == 0 || !desc->db_low)
+            return fail(GBNNS_ERR_INVALID, "gbnns_index_create_half_base: d_low and db_low are required (a half-base handle serves NET / LOWQ searches)");
+    }
     if (bytes) {
         if (desc->db) return fail(GBNNS_ERR_INVALID, "gbnns_index_create_bytes: desc->db must be NULL (the table is db_bytes)");
         if (!db_bytes) return fail(GBNNS_ERR_INVALID, "gbnns_index_create_bytes: db_bytes missing");
@@ -434,7 +441,7 @@ static int index_create(const gbnns_index_desc* desc, const uint8_t* db_bytes, b
     ix->d_hidden = desc->d_hidden;
     (void)hipDeviceGetAttribute(&ix->cus, hipDeviceAttributeMultiprocessorCount, ix->device);
     ix->knob = knob_defaults();
-    ix->d_pad = round_up(desc->d, bytes ? 16 : 4);  // (a byte handle: bytes of a row = floats of a staged re-rank query)
+    ix->d_pad = round_up(desc->d, bytes ? 16 : (half_base ? 8 : 4));  // (a byte handle: bytes of a row = floats of a staged re-rank query; a half-base handle: halves of a row)
     ix->dl_pad = round_up(desc->d_low, 4);
     int rc = GBNNS_OK;
 
@@ -447,38 +454,52 @@ static int index_create(const gbnns_index_desc* desc, const uint8_t* db_bytes, b
         dst = own.as<float>();
         return r;
     };
-    // uint8 rows: [n x d] -> [n x d_pad] bytes, zero padded, in an exactly sized buffer; a DEVICE table already in that layout is borrowed
-    auto take_bytes = [&]() -> int {
-        const size_t d = ix->d, pad = ix->d_pad, n = ix->n;
+    // rows of 1- or 2-byte elements: [n x d] -> [n x d_pad], zero padded, in an exactly sized buffer; a DEVICE table already in that layout
+    // (d_pad == d, a 16-byte aligned address) is borrowed
+    auto take_packed = [&](const void* table, size_t elem, DevBuf& own, const void*& dst, const char* what) -> int {
+        const size_t d = ix->d * elem, pad = ix->d_pad * elem, n = ix->n;  // (bytes of a row)
         const bool device = desc->mem_kind == GBNNS_MEM_DEVICE;
-        if (device && pad == d && (reinterpret_cast<uintptr_t>(db_bytes) & 15u) == 0) {
-            ix->db_b = db_bytes;
+        if (device && pad == d && (reinterpret_cast<uintptr_t>(table) & 15u) == 0) {
+            dst = table;
             return GBNNS_OK;
         }
-        const hipError_t ea = hipMalloc(&ix->db_b_own.p, n * pad);
+        const hipError_t ea = hipMalloc(&own.p, n * pad);
         if (ea != hipSuccess) {
-            ix->db_b_own.p = nullptr;
+            own.p = nullptr;
             return fail(GBNNS_ERR_OOM, "hipMalloc(%zu): %s", n * pad, hipGetErrorString(ea));
         }
-        ix->db_b_own.bytes = n * pad;
-        ix->db_b = ix->db_b_own.as<uint8_t>();
-        if (!device && pad == d) return h2d_staged(ix->db_b_own.p, db_bytes, n * d);
+        own.bytes = n * pad;
+        dst = own.p;
+        if (!device && pad == d) return h2d_staged(own.p, table, n * d);
         DevBuf packed;  // (HOST rows that need padding: packed on the device first, then spread)
-        const void* src = db_bytes;
+        const void* src = table;
         int r = GBNNS_OK;
         if (!device) {
             if ((r = packed.ensure(n * d))) return r;
-            r = h2d_staged(packed.p, db_bytes, n * d);
+            r = h2d_staged(packed.p, table, n * d);
             src = packed.p;
         }
-        hipError_t e = r ? hipSuccess : hipMemset(ix->db_b_own.p, 0, n * pad);
-        if (!r && e == hipSuccess) e = hipMemcpy2D(ix->db_b_own.p, pad, src, d, d, n, hipMemcpyDeviceToDevice);
+        hipError_t e = r ? hipSuccess : hipMemset(own.p, 0, n * pad);
+        if (!r && e == hipSuccess) e = hipMemcpy2D(own.p, pad, src, d, d, n, hipMemcpyDeviceToDevice);
         if (!r && e == hipSuccess) e = hipDeviceSynchronize();
         packed.release();
-        if (!r && e != hipSuccess) r = fail(GBNNS_ERR_HIP, "byte table upload: %s", hipGetErrorString(e));
+        if (!r && e != hipSuccess) r = fail(GBNNS_ERR_HIP, "%s table upload: %s", what, hipGetErrorString(e));
         return r;
     };
-    rc = bytes ? take_bytes() : take(desc->db, ix->d, ix->d_pad, ix->db_own, ix->db);
+    auto take_bytes = [&]() -> int {
+        const void* dst = nullptr;
+        const int r = take_packed(db_bytes, 1, ix->db_b_own, dst, "byte");
+        ix->db_b = static_cast<const uint8_t*>(dst);
+        return r;
+    };
+    // binary16 rows: d_pad = round_up(d, 8) halves
+    auto take_half = [&]() -> int {
+        const void* dst = nullptr;
+        const int r = take_packed(db_half, 2, ix->db_h_base_own, dst, "half");
+        ix->db_h_base = static_cast<const uint16_t*>(dst);
+        return r;
+    };
+    rc = bytes ? take_bytes() : (half_base ? take_half() : take(desc->db, ix->d, ix->d_pad, ix->db_own, ix->db));
     if (!rc && desc->db_low) rc = take(desc->db_low, ix->d_low, ix->dl_pad, ix->db_low_own, ix->db_low);
 
     if (!rc) {
@@ -572,6 +593,12 @@ int gbnns_index_create_bytes(const gbnns_index_desc* desc, const uint8_t* db_byt
 
 int gbnns_index_is_bytes(const gbnns_index* ix) { return ix && ix->db_b ? 1 : 0; }
 
+int gbnns_index_create_half_base(const gbnns_index_desc* desc, const uint16_t* db_half, gbnns_index** out) {
+    return index_create(desc, nullptr, false, out, db_half, true);
+}
+
+int gbnns_index_is_half_base(const gbnns_index* ix) { return ix && ix->db_h_base ? 1 : 0; }
+
 int gbnns_index_set_aux_graph(gbnns_index* ix, const uint64_t* offsets, const uint32_t* nbrs) {
     if (!ix) return fail(GBNNS_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(ix->device));
@@ -613,7 +640,7 @@ int gbnns_index_destroy(gbnns_index* ix) {
         if (L.stream) (void)hipStreamDestroy(L.stream);
         for (int i = 0; DevBuf* b = L.bufs(i); ++i) b->release();
     }
-    DevBuf* bufs[] = {&ix->db_own, &ix->db_b_own, &ix->db_low_own, &ix->ell, &ix->aux_ell, &ix->net, &ix->net_mfma, &ix->low_half, &ix->low_r, &ix->tags};
+    DevBuf* bufs[] = {&ix->db_own, &ix->db_b_own, &ix->db_h_base_own, &ix->db_low_own, &ix->ell, &ix->aux_ell, &ix->net, &ix->net_mfma, &ix->low_half, &ix->low_r, &ix->tags};
     for (DevBuf* b : bufs) b->release();
     delete ix;
     return GBNNS_OK;
@@ -800,6 +827,12 @@ hipError_t rerank_topk_launch(const gbnns_index* ix, const RerankTopkParams& r, 
         b.db = nullptr; b.db_b = ix->db_b; b.dstride = ix->d_pad;
         return launch_rerank_topk_bytes(b, ix->metric, s);
     }
+    if (ix->db_h_base) {
+        RerankHalfParams h{};
+        static_cast<RerankTopkParams&>(h) = r;
+        h.db = nullptr; h.db_h = ix->db_h_base; h.dstride = ix->d_pad;
+        return launch_rerank_topk_half(h, ix->metric, s);
+    }
     return launch_rerank_topk(r, ix->metric, s);
 }
 
@@ -809,6 +842,12 @@ hipError_t rerank_launch(const gbnns_index* ix, const RerankParams& r, hipStream
         static_cast<RerankParams&>(b) = r;
         b.db = nullptr; b.db_b = ix->db_b; b.dstride = ix->d_pad;
         return launch_rerank_bytes(b, ix->metric, s);
+    }
+    if (ix->db_h_base) {
+        RerankHalfParams h{};
+        static_cast<RerankParams&>(h) = r;
+        h.db = nullptr; h.db_h = ix->db_h_base; h.dstride = ix->d_pad;
+        return launch_rerank_half(h, ix->metric, s);
     }
     return launch_rerank(r, ix->metric, s);
 }
@@ -1042,6 +1081,18 @@ int gbnns_debug_rerank_plan(int metric, uint32_t d, int bytes, char* name, uint3
     const RerankPlan plan = rerank_plan(metric, d, bytes != 0);
     if (plan.form == RerankForm::ChunkPairs) std::snprintf(name, name_bytes, "rerank_bytes_pair_kernel");
     else std::snprintf(name, name_bytes, "%s<%d>", bytes ? "rerank_bytes_kernel" : (plan.form == RerankForm::Pairs ? "rerank_pair_kernel" : "rerank_kernel"), metric);
+    *deep = plan.deep;
+    *fused = plan.fuses ? 1 : 0;
+    return GBNNS_OK;
+}
+
+int gbnns_debug_half_base_plan(int metric, uint32_t d, char* name, uint32_t name_bytes, int* deep, int* fused) {
+    if (!name || name_bytes == 0 || !deep || !fused) return fail(GBNNS_ERR_INVALID, "gbnns_debug_half_base_plan: null output");
+    if ((metric != GBNNS_METRIC_L2 && metric != GBNNS_METRIC_NEG_DOT) || d == 0)
+        return fail(GBNNS_ERR_INVALID, "gbnns_debug_half_base_plan: not the metric or the dimension of an index");
+    const RerankPlan plan = rerank_half_plan(metric, d);
+    if (plan.form == RerankForm::HalfChunkPairs) std::snprintf(name, name_bytes, "rerank_half_pair_kernel");
+    else std::snprintf(name, name_bytes, "rerank_half_kernel<%d>", metric);
     *deep = plan.deep;
     *fused = plan.fuses ? 1 : 0;
     return GBNNS_OK;

@@ -175,6 +175,14 @@ struct RerankBytesParams : RerankTopkParams {
 };
 hipError_t launch_rerank_bytes(const RerankBytesParams& p, int metric, hipStream_t s);
 hipError_t launch_rerank_topk_bytes(const RerankBytesParams& p, int metric, hipStream_t s);
+// The same two over the binary16 rows of a half-base handle (rerank_half.hip): `db` stays nullptr, `dstride` is the HALVES of a row --
+// round_up(dim, 8), zero padded, which is also the floats of the staged query.  The distances are the float kernels' on float32(db_h), bit
+// for bit.  L2 with dim % 4 == 0: the half chunk-pair form; else a lane per row (rerank_plan.h: rerank_half_plan).
+struct RerankHalfParams : RerankTopkParams {
+    const uint16_t* db_h;    // [n x dstride] binary16 bit patterns, rows 16-byte aligned
+};
+hipError_t launch_rerank_half(const RerankHalfParams& p, int metric, hipStream_t s);
+hipError_t launch_rerank_topk_half(const RerankHalfParams& p, int metric, hipStream_t s);
 // diagnostic (tests): one batch merge of a sorted list [size] with up to 64 survivor keys (~0 = none)
 hipError_t launch_debug_merge(int regs, const uint64_t* entries, int size, const uint64_t* surv, int ef, uint64_t* out,
                               int* out_size, hipStream_t s);

@@ -147,7 +147,7 @@ CallFacts Call::call_facts() const {
     CallFacts f{};
     f.metric = ix->metric; f.n = ix->n; f.d = ix->d; f.d_pad = ix->d_pad; f.ell_stride = ix->ell_stride;
     f.aux_stride = (a->flags & GBNNS_FLAG_AUX_GRAPH) ? ix->aux_stride : 0u;
-    f.byte_handle = ix->db_b != nullptr; f.cus = ix->cu_count(); f.knob = ix->knob;
+    f.byte_handle = ix->db_b != nullptr; f.half_base = ix->db_h_base != nullptr; f.cus = ix->cu_count(); f.knob = ix->knob;
     f.dim = plain ? ix->d : ix->d_low; f.dstride = plain ? ix->d_pad : ix->dl_pad;
     f.half_rows = !plain && (a->flags & GBNNS_FLAG_HALF_ROWS);
     f.walk_bytes = plain && ix->db_b;  // GBNNS_FLAG_BYTE_WALK (checked by search_call): the walked rows are the handle's uint8 rows, d_pad bytes each; no float table exists

@@ -764,6 +764,142 @@ __device__ __forceinline__ int rerank_bytes_core(const RerankBytesSrc& a, uint32
     return (cnt > 0 && bestk != ~0ull) ? (int)(uint32_t)(bestk & 0xFFFFFFFFu) : -1;
 }
 
+// ------------------------------------------------------------------------------------------
+// re-rank over binary16 rows (gbnns_index_create_half_base): the original-space table holds IEEE binary16 coordinates, rows of
+// round_up(d, 8) halves, zero padded.  Every binary16 value -- subnormals, both zeros, +-65 504 -- is a binary32 value, so widening
+// (v_cvt_f32_f16; the kernels' default denormal mode keeps binary16 subnormals) rounds nothing: the distances below are the float forms'
+// distances on float32(db_half), operation for operation.  The query is never rounded.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ float half_bits_to_float(uint32_t bits16) {
+    return (float)__builtin_bit_cast(_Float16, (unsigned short)bits16);
+}
+// four coordinates of a row, widened: `lo` holds halves 0 and 1, `hi` halves 2 and 3 (the row stays packed until here)
+__device__ __forceinline__ float4 halves4_to_float4(uint32_t lo, uint32_t hi) {
+    return make_float4(half_bits_to_float(lo & 0xFFFFu), half_bits_to_float(lo >> 16), half_bits_to_float(hi & 0xFFFFu), half_bits_to_float(hi >> 16));
+}
+// a half row as l2_ordered / negdot_ordered read it: element t = the float4 of halves 4t .. 4t + 3 (the lane-per-row form)
+struct HalfRow4 {
+    const uint2* w;
+    __device__ __forceinline__ float4 operator[](uint32_t t) const {
+        const uint2 x = w[t];
+        return halves4_to_float4(x.x, x.y);
+    }
+};
+
+struct RerankHalfSrc {
+    const float* q;      // [nq x qstride] original-space queries
+    uint32_t qstride;
+    const uint16_t* db;  // [n x hstride] binary16 bit patterns, rows 16-byte aligned
+    uint32_t hstride;    // halves of a row = floats of the staged query: round_up(dim, 8)
+    uint32_t dim, n;     // dim % 4 == 0 here
+};
+
+// One 16-byte chunk `rv` = two of the reference's 4-wide steps against the query's two float4 `q`, added to the four running sums in order in
+// this lane: the even lane of a pair on top of the odd lane's sums (`u`), then the odd lane on top of the even lane's (`v`).
+__device__ __forceinline__ void half_chunk_add(const uint4 rv, const float4 (&q)[2], float (&u)[4], float (&v)[4]) {
+    const float4 f[2] = {halves4_to_float4(rv.x, rv.y), halves4_to_float4(rv.z, rv.w)};
+    float p[2][4];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        float e;
+        e = f[s].x - q[s].x; p[s][0] = e * e;
+        e = f[s].y - q[s].y; p[s][1] = e * e;
+        e = f[s].z - q[s].z; p[s][2] = e * e;
+        e = f[s].w - q[s].w; p[s][3] = e * e;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float x = dpp_swap_pair(v[j]);
+        x = x + p[0][j]; x = x + p[1][j];
+        u[j] = x;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float x = dpp_swap_pair(u[j]);
+        x = x + p[0][j]; x = x + p[1][j];
+        v[j] = x;
+    }
+}
+
+// Chunk-pair form (L2, dim % 4 == 0): lanes 2i / 2i+1 share candidate i's row; the even lane takes the 16-byte chunks 0, 2, 4, ..., the odd
+// lane 1, 3, 5, ... -- a pair reads 32 contiguous bytes per load.  The sums hop to the partner once per chunk; with an odd chunk count the
+// last chunk is the even lane's alone (rerank_bytes_core's trick).  DEEP: 16-byte loads a lane has in flight in the first loop of the ladder
+// (rerank_plan.h: rerank_half_deep; 4 * DEEP registers hold the packed row), then four at a time, then one.  Winner, `id_at` and `sink` as in
+// rerank_pairs_core; the finished sum is the odd lane's.
+template <int DEEP, typename IdAt, typename Sink = RerankNoSink>
+__device__ __forceinline__ int rerank_half_core(const RerankHalfSrc& a, uint32_t qi, int cnt, float* qf, int lane, IdAt id_at, Sink sink = Sink{}) {
+    const uint32_t half = (uint32_t)lane & 1u, slot = (uint32_t)lane >> 1;
+    const float4* qs = reinterpret_cast<const float4*>(qf);
+    // (dim % 8 == 4 -- glove's 300, rows of 304 halves: the last chunk's second 4-wide step is the row's zero padding against the zeros staged
+    // here; (0 - 0)^2 = +0 added to a sum of squares leaves it as it is)
+    for (uint32_t i = lane; i < a.hstride; i += 64)
+        qf[i] = (i < a.dim) ? a.q[(size_t)qi * a.qstride + i] : 0.f;
+    wave_sync();
+    const uint32_t chunks = a.hstride >> 3, cpairs = chunks >> 1, ctotal = cpairs + (chunks & 1u);
+    uint64_t bestk = ~0ull;
+    for (int base = 0; base < cnt; base += 32) {
+        const int r = base + (int)slot;
+        const bool valid = r < cnt;
+        uint32_t id = id_at(valid ? r : base);  // lanes beyond the list redo the first row (discarded)
+        id = id < a.n ? id : 0u;                // (never dereference an id outside the table)
+        const uint4* row = reinterpret_cast<const uint4*>(a.db + (size_t)id * a.hstride) + half;
+        const float4* qh = qs + 2u * half;       // (a chunk's 8 coordinates are two float4 of the staged query)
+        float u[4], v[4] = {0.f, 0.f, 0.f, 0.f};
+        uint32_t k = 0;
+        if constexpr (DEEP > 4) {
+            for (; k + DEEP <= cpairs; k += DEEP) {  // DEEP 16-B loads in flight per lane
+                uint4 rv[DEEP];
+#pragma unroll
+                for (int j = 0; j < DEEP; ++j) rv[j] = row[2 * (k + j)];
+#pragma unroll
+                for (int j = 0; j < DEEP; ++j) {
+                    const float4* qc = qh + 4 * (k + j);
+                    const float4 q[2] = {qc[0], qc[1]};
+                    half_chunk_add(rv[j], q, u, v);
+                }
+            }
+        }
+        for (; k + 4 <= cpairs; k += 4) {  // four 16-B loads in flight per lane
+            uint4 rv[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) rv[j] = row[2 * (k + j)];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float4* qc = qh + 4 * (k + j);
+                const float4 q[2] = {qc[0], qc[1]};
+                half_chunk_add(rv[j], q, u, v);
+            }
+        }
+        // (an odd chunk count -- d = 8, 40: the last chunk is the even lane's alone; the odd lane reads nothing and adds +0 to the sums it takes
+        // over, which leaves a sum of squares as it is)
+        for (; k < ctotal; ++k) {
+            const bool mine = k < cpairs || !half;
+            uint4 rv = make_uint4(0u, 0u, 0u, 0u);
+            float4 q[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
+            if (mine) {
+                const float4* qc = qh + 4 * k;
+                rv = row[2 * k];
+                q[0] = qc[0]; q[1] = qc[1];
+            }
+            half_chunk_add(rv, q, u, v);
+        }
+        const float dv = ((v[0] + v[1]) + v[2]) + v[3];
+        if (valid && half) {
+            sink(r, dv);
+            const uint64_t kv = ((uint64_t)fkey(dv) << 32) | (uint32_t)r;
+            bestk = kv < bestk ? kv : bestk;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint64_t o = shfl_u64(bestk, lane ^ off);
+        bestk = o < bestk ? o : bestk;
+    }
+    bestk = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(bestk >> 32)) << 32) |
+            (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bestk);
+    return (cnt > 0 && bestk != ~0ull) ? (int)(uint32_t)(bestk & 0xFFFFFFFFu) : -1;
+}
+
 // Fused re-rank at the end of a walk: the wavefront re-ranks its own query's candidates (pop index r =
 // list rank kept-1-r) instead of leaving them to a second kernel -- the re-rank's memory-bound work then
 // runs beside other wavefronts' walks and fills the slots the last "round" of a batch leaves idle.  The

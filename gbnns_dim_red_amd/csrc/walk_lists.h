@@ -262,9 +262,7 @@ __device__ __forceinline__ void load_row_half_alt(HalfRowRegs<4>& r, const void*
 #pragma unroll
     for (int t = 0; t < 4; ++t) r.v[t] = r2[2 * t];
 }
-__device__ __forceinline__ float half_bits_to_float(uint32_t bits16) {
-    return (float)__builtin_bit_cast(_Float16, (unsigned short)bits16);
-}
+// (half_bits_to_float: walk_common.h, beside the half-row re-rank core that widens with it too)
 template <int STEPS>
 __device__ __forceinline__ void widen_row(RowRegs<STEPS>& out, const HalfRowRegs<STEPS>& h) {
 #pragma unroll

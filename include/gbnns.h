@@ -120,6 +120,28 @@ int gbnns_index_create(const gbnns_index_desc* desc, gbnns_index** out);
  * fused re-rank, followed by the stand-alone byte re-rank kernel (gbnns_debug_byte_plan tells which). */
 int gbnns_index_create_bytes(const gbnns_index_desc* desc, const uint8_t* db_bytes, gbnns_index** out);
 int gbnns_index_is_bytes(const gbnns_index* index);   /* 1: created by gbnns_index_create_bytes; 0: not (or NULL) */
+/* The same index over IEEE binary16 base vectors -- the float datasets (deep, gist, glove) at half the table: db_half is [n x d] binary16 bit
+ * patterns of desc->mem_kind, desc->db must be NULL, d_low > 0 and db_low are required (GBNNS_ERR_INVALID else); graph and net as above.  On
+ * the device a row is round_up(d, 8) halves, zero padded, on a 16-byte aligned base: a HOST table is copied into that layout; a DEVICE table
+ * with d % 8 == 0 and a 16-byte aligned address is borrowed (it must outlive the index), any other is re-laid once into an owned copy of
+ * exactly n x round_up(d, 8) x 2 bytes.  No float32 copy of the table exists on a half-base handle.
+ * The library does not round a float32 table itself: a caller who has float32 data rounds it with gbnns_round_to_half and passes the bits.
+ * Contract: every call on a half-base handle returns what the same call returns on the handle created with db = float32(db_half), bit for
+ * bit -- ids, pop-order candidates, out_cand_dist, hops, dist_calc, and the exact top-k distances of gbnns_search_topk / gbnns_rerank_topk.
+ * (Widening binary16 to binary32 is exact -- subnormals, both zeros, +-65 504; all arithmetic stays float32 in the reference's order,
+ * multiply and add separate; the query is never rounded.)
+ * Served: gbnns_search_ex / gbnns_search_batch in NET and LOWQ mode with every flag that applies (GBNNS_FLAG_HALF_ROWS for the walked table
+ * included: it is orthogonal), gbnns_search_topk, gbnns_search_tagged (with and without GBNNS_FLAG_TAG_BRIDGE), gbnns_rerank,
+ * gbnns_rerank_topk, gbnns_project, gbnns_index_tag_census, several entry points, the auxiliary graph, HOST or DEVICE buffers, batches in
+ * flight.  Every search runs the very first-pass kernel a float handle runs under GBNNS_FLAG_NO_FUSED_RERANK, and the stand-alone half
+ * re-rank (rerank_half.hip; gbnns_debug_half_base_plan tells which kernel) follows on the same stream.
+ * Refused: GBNNS_MODE_PLAIN (GBNNS_ERR_UNSUPPORTED: there is no float table to walk), gbnns_index_exact_knn, gbnns_index_exact_knn_gather and
+ * gbnns_search_tagged_auto (GBNNS_ERR_UNSUPPORTED: they scan the resident table), GBNNS_FLAG_BYTE_WALK and gbnns_search_byte_queries
+ * (GBNNS_ERR_INVALID, as on a float handle).  gbnns_multi_create has no half form.
+ * Out of scope so far: a half re-rank fused into the walk kernels, a PLAIN walk over half rows, resident exact scans over a half table, half
+ * queries. */
+int gbnns_index_create_half_base(const gbnns_index_desc* desc, const uint16_t* db_half, gbnns_index** out);
+int gbnns_index_is_half_base(const gbnns_index* index);   /* 1: created by gbnns_index_create_half_base; 0: not (or NULL) */
 int gbnns_index_destroy(gbnns_index* index);
 /* what the handle was created with */
 uint64_t gbnns_index_n(const gbnns_index* index);
@@ -556,6 +578,13 @@ int gbnns_debug_byte_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n
  * forms; whether a call does depends on its flags, beam and LDS room as well), 0 where a re-rank launch always follows.  GBNNS_ERR_INVALID: a
  * null output, an unknown metric, d == 0. */
 int gbnns_debug_rerank_plan(int metric, uint32_t d, int bytes, char* name, uint32_t name_bytes, int* deep, int* fused);
+/* The same for the binary16 rows of a half-base handle (gbnns_index_create_half_base), from the predicate its launchers and the search decide
+ * with.  `name`: the kernel gbnns_rerank launches ("rerank_half_pair_kernel": L2, d % 4 == 0, two lanes per row, a 16-byte chunk of eight
+ * halves at a time; "rerank_half_kernel<0>" / "rerank_half_kernel<1>": a lane per row -- L2 with a d % 4 tail, the negative dot).  *deep: the
+ * 16-byte row loads a lane has in flight in the first loop of its ladder (the measured depth for d >= 384, 4 below, 0 a lane per row).
+ * *fused: always 0 -- no walk kernel re-ranks half rows, a re-rank launch always follows.  GBNNS_ERR_INVALID: a null output, an unknown
+ * metric, d == 0. */
+int gbnns_debug_half_base_plan(int metric, uint32_t d, char* name, uint32_t name_bytes, int* deep, int* fused);
 /* Diagnostic, no device needed: the first-pass kernel a GBNNS_MODE_PLAIN call with GBNNS_FLAG_BYTE_WALK of that shape gets on a byte handle
  * ("walk_general_kernel": the general kernel's byte-walk instance takes the whole batch) and its LDS bytes per wavefront without the
  * visited set.  `dim` is the original dimension -- the walked row is round_up(dim, 16) bytes --, `tagged` != 0 a gbnns_search_tagged call;
