@@ -27,6 +27,7 @@ FLAG_HALF_ROWS = 512
 FLAG_TAG_BRIDGE = 1024   # gbnns_search_tagged only: disallowed neighbours are looked through (bridge_graph)
 FLAG_SCAN_GATHER = 4096  # search_auto only: scan-routed queries are served by the gathered exact scan (Index.exact_knn(gather=True)); every output unchanged
 FLAG_BYTE_WALK = 2048    # MODE_PLAIN on a byte handle (Index(db=<uint8>)): walk the uint8 rows; the float handle's answers over db.astype(float32), bit for bit
+FLAG_HALF_WALK = 8192    # MODE_PLAIN on a half-base handle (Index(db=<float16>)): walk the binary16 rows; the float handle's answers over db.astype(float32), bit for bit
 
 # every symbol include/gbnns.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -51,6 +52,7 @@ SYMBOLS = [
     "gbnns_index_order_last", "gbnns_debug_query_order",
     "gbnns_debug_rerank_plan",
     "gbnns_index_create_half_base", "gbnns_index_is_half_base", "gbnns_debug_half_base_plan",
+    "gbnns_debug_half_walk_plan",
 ]
 
 
@@ -212,6 +214,7 @@ def load_library():
     lib.gbnns_debug_byte_walk_plan.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int,
                                               C.c_char_p, C.c_uint32, C.POINTER(C.c_uint64)]
     lib.gbnns_debug_byte_query_plan.argtypes = lib.gbnns_debug_byte_walk_plan.argtypes
+    lib.gbnns_debug_half_walk_plan.argtypes = lib.gbnns_debug_byte_walk_plan.argtypes
     lib.gbnns_search_byte_queries.argtypes = [C.c_void_p, C.POINTER(_SearchArgs), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.gbnns_debug_byte_plan.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int,
                                           C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(C.c_int)]
@@ -342,6 +345,17 @@ def byte_walk_plan(metric, dim, n, ell_stride, ef, aux_stride=0, n_entries=1, wi
     name = C.create_string_buffer(128)
     lds = C.c_uint64(0)
     _check(load_library().gbnns_debug_byte_walk_plan(metric, dim, n, ell_stride, aux_stride, ef, n_entries, int(wide), int(tagged), name, 128,
+                                                     C.byref(lds)))
+    return name.value.decode()
+
+
+def half_walk_plan(metric, dim, n, ell_stride, ef, aux_stride=0, n_entries=1, wide=False, tagged=False):
+    """gbnns_debug_half_walk_plan (no device needed): name of the first-pass kernel a MODE_PLAIN search with FLAG_HALF_WALK of that shape gets
+    on a half-base handle (dim: the original dimension; knob "half_walk_fast" = 2: every first-pass instance the library has, also of a class the default, 1, leaves to the general instance); "walk_general_kernel": the general kernel's half-walk
+    instance takes the whole batch."""
+    name = C.create_string_buffer(128)
+    lds = C.c_uint64(0)
+    _check(load_library().gbnns_debug_half_walk_plan(metric, dim, n, ell_stride, aux_stride, ef, n_entries, int(wide), int(tagged), name, 128,
                                                      C.byref(lds)))
     return name.value.decode()
 

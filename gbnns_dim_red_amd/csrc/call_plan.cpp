@@ -16,6 +16,9 @@ void set_walk_shape(WalkParams& w, const CallFacts& f) {
     w.half_rows = f.half_rows ? 1 : 0;
     w.tagged = f.tagged ? 1 : 0; w.bridged = f.bridged ? 1 : 0;
     w.walk_bytes = f.walk_bytes ? 1 : 0;
+    w.walk_half = f.walk_half ? 1 : 0;
+    w.half_general = (f.walk_half && !f.knob.half_walk_fast) ? 1 : 0;
+    w.half_unkept = (f.walk_half && f.knob.half_walk_fast == 2) ? 1 : 0;
     // byte queries: the plan may name the integer twin of a byte-walk instance (walk_plan.cpp; knob "byte_query_int": for which beam classes)
     w.q_b = (f.walk_bytes && f.byte_queries) ? reinterpret_cast<const uint8_t*>(present) : nullptr;
     w.bq_classes = f.walk_bytes ? (uint32_t)f.knob.byte_query_int : 0u;
@@ -38,10 +41,10 @@ namespace {
 size_t granules(size_t bytes) { return (bytes + kLdsGran - 1) / kLdsGran * kLdsGran; }
 size_t first_lds(const WalkParams& w, const WalkPlan& plan) { return plan.lds_fixed + walk_hash_bytes(w.hash_cap, plan.hash_form(w.vs_shr)); }
 
-// sizing statistics are kept per (ef, mode, aux, wide, byte instances: no retry pass behind them, half rows: another table, other walks; tagged: other graphs, shorter walks; bridged: two to three times the rows claimed; knob "hot" = 0: other kernels; a half-base handle: a class of its own, like the byte handle's)
+// sizing statistics are kept per (ef, mode, aux, wide, byte instances: no retry pass behind them, half rows: another table, other walks; tagged: other graphs, shorter walks; bridged: two to three times the rows claimed; knob "hot" = 0: other kernels; a half-base handle: a class of its own, like the byte handle's; a half walk, GBNNS_FLAG_HALF_WALK: one more -- bit 23 --, and with the knob "half_walk_fast" = 0 another -- bit 22: other kernels; beams below 2^18)
 int stats_key(const CallFacts& f, const WalkParams& w) {
     const bool aux = f.aux_stride != 0;
-    return ((f.ef * 8 + f.mode * 2 + (aux ? 1 : 0)) * 2 + w.force_wide) | (w.half_rows ? 1 << 30 : 0) | (w.tagged ? 1 << 29 : 0) | (w.bridged ? 1 << 27 : 0) | (w.generic_only ? 1 << 28 : 0) | (w.bytes_dim ? 1 << 26 : 0) | (w.walk_bytes ? 1 << 25 : 0) | (f.half_base ? 1 << 24 : 0);
+    return ((f.ef * 8 + f.mode * 2 + (aux ? 1 : 0)) * 2 + w.force_wide) | (w.half_rows ? 1 << 30 : 0) | (w.tagged ? 1 << 29 : 0) | (w.bridged ? 1 << 27 : 0) | (w.generic_only ? 1 << 28 : 0) | (w.bytes_dim ? 1 << 26 : 0) | (w.walk_bytes ? 1 << 25 : 0) | (f.half_base ? 1 << 24 : 0) | (w.walk_half ? 1 << 23 : 0) | (w.half_general ? 1 << 22 : 0);
 }
 
 // A small batch that runs ALONE (the reference's gist row: 1 000 queries per synchronous call, final_test.cpp:87) on the shapes that
@@ -80,7 +83,7 @@ size_t bitmap_rule(const CallFacts& f, const WalkParams& w, const WalkPlan& plan
     // below -- the pass must at least double the resident wavefronts: 8 by registers against <= 4 by the table -- does from ef 450 on)
     const int min_ef = min_ef_env ? min_ef_env : (rows576 ? 450 : (form == 2 ? 480 : 385));
     const bool forced = (f.flags & GBNNS_FLAG_BITMAP_PASS) != 0;  // diagnostic: whatever ef and batch size
-    if (w.all_general || w.coop || w.tagged || w.walk_bytes || !(ef >= min_ef || forced) || (f.flags & GBNNS_FLAG_WIDE_INDEX) || !(f.hash_capacity == 0 || forced))
+    if (w.all_general || w.coop || w.tagged || w.walk_bytes || w.walk_half || !(ef >= min_ef || forced) || (f.flags & GBNNS_FLAG_WIDE_INDEX) || !(f.hash_capacity == 0 || forced))
         return 0;
     const WalkPlan bitmap_plan = plan_walk(w, f.metric, WalkPass::Bitmap);
     const size_t per_wave = granules(bitmap_plan.lds_fixed);   // (the slot counts below follow the device's CU count, as in sizing.cpp)
@@ -100,6 +103,7 @@ size_t bitmap_rule(const CallFacts& f, const WalkParams& w, const WalkPlan& plan
 // least five wavefronts per CU by LDS (ef 300 / 400 / 600: 4.15 / 5.36 / 10.4 against 5.08 / 6.74 / 10.7 ms; ef 800 / 1 000, four and
 // fewer per CU: 18.2 / 23.8 against 17.4 / 22.3) on a batch that fills the machine
 int late_rows_rule(const CallFacts& f, const WalkParams& w, const WalkPlan& plan, size_t bitmap_per_cu) {
+    if (w.walk_half) return 0;  // (GBNNS_FLAG_HALF_WALK: no instance with its rows requested late)
     const int knob = f.knob.late_rows;
     const size_t per_wave = granules(first_lds(w, plan));
     const size_t lds_waves = per_wave ? kMaxLds / per_wave : 0;
@@ -125,7 +129,7 @@ void retry_rule(const CallFacts& f, const WalkParams& w, CallPlan& cp) {
     cp.retry_hash_limit = cp.retry_hash_cap - cp.retry_hash_cap / 16;
     if (cp.skip_retry)
         cp.retry_action = RetryAction::None;  // nothing to launch
-    else if (cp.retry_hash_cap > cp.sizing.cap && !w.tagged && !(cp.fuse && f.byte_handle) && !w.walk_bytes)  // (a tagged first pass has no retry pass: its hand-overs go straight to the general kernel; a byte instance's and a byte walk's to the general kernel's byte instances)
+    else if (cp.retry_hash_cap > cp.sizing.cap && !w.tagged && !(cp.fuse && f.byte_handle) && !w.walk_bytes && !w.walk_half)  // (a tagged first pass has no retry pass: its hand-overs go straight to the general kernel; a byte instance's and a byte walk's to the general kernel's byte instances, a half walk's to its half-walk instance)
         cp.retry_action = RetryAction::Launch;
     else
         cp.retry_action = RetryAction::Copy;  // nothing to gain: A -> B

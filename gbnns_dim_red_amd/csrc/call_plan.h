@@ -18,7 +18,7 @@ using namespace gbnns;
 // starts from, so a test or an A/B run that flips one no longer changes every other handle of the process.  The three knobs of
 // gbnns_exact_knn -- a function without a handle -- stay process-wide.
 struct Knobs {
-    int quotient, vs_disp, max_waves, spec_min_nq, spec_any_form, mlp_small, mlp_net, mlp_slab, late_rows, spec_tail, coop, hot, byte_query_int, gather_budget, gather_timing, order_min, order_bits;
+    int quotient, vs_disp, max_waves, spec_min_nq, spec_any_form, mlp_small, mlp_net, mlp_slab, late_rows, spec_tail, coop, hot, byte_query_int, gather_budget, gather_timing, order_min, order_bits, half_walk_fast;
 };
 
 constexpr size_t kMaxLds = 160 * 1024;
@@ -72,7 +72,8 @@ struct CallFacts {
     bool sync_host;           // the call runs alone and is waited for
     bool stamps_on;           // diagnostic builds (GBNNS_STAMPS)
     // the handle again (last: aggregate initialisers of the members above stay valid)
-    bool half_base = false;   // gbnns_index_create_half_base: binary16 original rows (d_pad: their halves) -- no walk kernel reads them, the re-rank is never fused
+    bool half_base = false;   // gbnns_index_create_half_base: binary16 original rows (d_pad: their halves) -- only a GBNNS_FLAG_HALF_WALK call's walk kernels read them, the re-rank is never fused
+    bool walk_half = false;   // GBNNS_FLAG_HALF_WALK: the walked rows are the handle's binary16 rows (knob.half_walk_fast = 0: the general instance takes the whole batch)
 };
 
 // sizing.cpp: the first pass's visited set for this batch -- sets w.vs_shr / hash_cap / hash_limit / spec_rows / spec_from

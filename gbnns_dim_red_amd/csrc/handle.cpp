@@ -287,6 +287,10 @@ int build_ell(const uint64_t* off, const uint32_t* nbr, uint64_t n, std::vector<
 //   "byte_query_int" gbnns_search_byte_queries: the beam classes whose byte-walk first pass is the integer instance (walk_bytes_q.hip) -- a mask,
 //                   bit 0 = one list register (ef <= 64), bit 1 = two (ef <= 128), bit 2 = the two-list kernel (ef <= 1 024); 0 = never: the call
 //                   is served by walk_bytes.hip on the widened queries (A/B runs; GBNNS_BYTE_QUERY_INT).  Default: kByteQueryIntDefault
+//   "half_walk_fast" GBNNS_FLAG_HALF_WALK: 0 = the general kernel's half-walk instance takes the whole batch also where walk_half_base.hip has an
+//                   instance; 1 (default) = the fast instances of the dimension classes the measurement rule has kept (walk_plan.cpp); 2 = every
+//                   fast instance the unit has (tools/half_walk_timing.py measures the three against each other; the tests run the unkept
+//                   instances with 2 and the general instance on the fast shapes with 0; GBNNS_HALF_WALK_FAST)
 //   "gather_budget" gbnns_index_exact_knn_gather: list entries (4 bytes each) the id lists of one round may hold together; default 2^26 (256 MiB),
 //                   and the call never takes less than n.  Not for tuning: a test forces several rounds at a few thousand rows with it
 //   "gather_timing" 1 = a gathered call times its stages with events (its rounds then run one after the other); read back with
@@ -328,6 +332,7 @@ bool knob_set(Knobs& k, const char* name, int value) {
     else if (!std::strcmp(name, "coop")) k.coop = std::max(-1, std::min(1, value));
     else if (!std::strcmp(name, "hot")) k.hot = value != 0;
     else if (!std::strcmp(name, "byte_query_int")) k.byte_query_int = std::max(0, std::min(7, value));
+    else if (!std::strcmp(name, "half_walk_fast")) k.half_walk_fast = std::max(0, std::min(2, value));
     else if (!std::strcmp(name, "gather_budget")) k.gather_budget = std::max(1, value);
     else if (!std::strcmp(name, "gather_timing")) k.gather_timing = value != 0;
     else if (!std::strcmp(name, "order_min")) k.order_min = std::max(0, value);
@@ -352,6 +357,7 @@ static Knobs& knob_default_ref() {  // (function-local: initialised on first use
         knob_set(k, "coop", knob_env("GBNNS_COOP", -1));
         knob_set(k, "hot", knob_env("GBNNS_HOT", 1));
         knob_set(k, "byte_query_int", knob_env("GBNNS_BYTE_QUERY_INT", kByteQueryIntDefault));
+        knob_set(k, "half_walk_fast", knob_env("GBNNS_HALF_WALK_FAST", 1));
         knob_set(k, "gather_budget", knob_env("GBNNS_GATHER_BUDGET", 1 << 26));
         knob_set(k, "gather_timing", 0);
         knob_set(k, "order_min", knob_env("GBNNS_ORDER_MIN", 32768));
@@ -1030,7 +1036,7 @@ int gbnns_debug_net_image(const float* w, uint32_t wstride, uint32_t din, uint32
 static int debug_plan(const char* fn, CallFacts f, WalkParams w, int force_wide, int coop, int pass, uint64_t general_lds, char* name, uint32_t name_bytes,
                       uint64_t* lds_bytes, int* fused) {
     if (!name || name_bytes == 0 || !(lds_bytes || fused)) return fail(GBNNS_ERR_INVALID, "%s: null output", fn);
-    if ((f.metric != GBNNS_METRIC_L2 && f.metric != GBNNS_METRIC_NEG_DOT) || f.dim == 0 || f.dstride != round_up(f.dim, f.walk_bytes ? 16 : 4) || f.n == 0 ||
+    if ((f.metric != GBNNS_METRIC_L2 && f.metric != GBNNS_METRIC_NEG_DOT) || f.dim == 0 || f.dstride != round_up(f.dim, f.walk_bytes ? 16 : (f.walk_half ? 8 : 4)) || f.n == 0 ||
         f.n > 0xFFFFFFFFull || f.ell_stride == 0 || f.ell_stride % 16 || f.aux_stride % 16 || f.ef < 1 || f.n_entries > 4096 || pass < 0 || pass > 2)
         return fail(GBNNS_ERR_INVALID, "%s: not the shape of an index or a search", fn);
     f.flags = force_wide ? GBNNS_FLAG_WIDE_INDEX : 0u;
@@ -1111,6 +1117,15 @@ static int debug_byte_walk_plan(const char* fn, bool byte_queries, int metric, u
 int gbnns_debug_byte_walk_plan(int metric, uint32_t dim, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries, int force_wide,
                                int tagged, char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
     return debug_byte_walk_plan("gbnns_debug_byte_walk_plan", false, metric, dim, n, ell_stride, aux_stride, ef, n_entries, force_wide, tagged, name, name_bytes, lds_bytes);
+}
+
+// (a flagged PLAIN call on a half-base handle: rows of round_up(dim, 8) halves, knob "half_walk_fast" = 2: every instance the unit has; the general kernel: the staged query alone)
+int gbnns_debug_half_walk_plan(int metric, uint32_t dim, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries, int force_wide,
+                               int tagged, char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
+    if (!lds_bytes) return fail(GBNNS_ERR_INVALID, "gbnns_debug_half_walk_plan: null output");
+    CallFacts f = debug_facts(metric, dim, round_up(dim, 8), n, ell_stride, aux_stride, ef, n_entries);
+    f.tagged = tagged != 0; f.walk_half = true; f.half_base = true; f.knob.half_walk_fast = 2;
+    return debug_plan("gbnns_debug_half_walk_plan", f, WalkParams{}, force_wide, 0, 0, (uint64_t)f.dstride * 4u, name, name_bytes, lds_bytes, nullptr);
 }
 
 int gbnns_debug_byte_query_plan(int metric, uint32_t dim, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries, int force_wide,
@@ -1294,7 +1309,7 @@ int gbnns_index_knob_get(gbnns_index* ix, const char* name, int* out) {
     const struct { const char* n; int v; } all[] = {
         {"quotient", k.quotient}, {"vs_disp", k.vs_disp}, {"max_waves", k.max_waves}, {"spec_min_nq", k.spec_min_nq},
         {"spec_any_form", k.spec_any_form}, {"mlp_small", k.mlp_small}, {"mlp_net", k.mlp_net}, {"mlp_slab", k.mlp_slab},
-        {"late_rows", k.late_rows}, {"spec_tail", k.spec_tail}, {"coop", k.coop}, {"hot", k.hot}, {"byte_query_int", k.byte_query_int}, {"mlp_net_form", ix->net_form}, {"cus", ix->cus},
+        {"late_rows", k.late_rows}, {"spec_tail", k.spec_tail}, {"coop", k.coop}, {"hot", k.hot}, {"byte_query_int", k.byte_query_int}, {"half_walk_fast", k.half_walk_fast}, {"mlp_net_form", ix->net_form}, {"cus", ix->cus},
         {"gather_budget", k.gather_budget}, {"gather_timing", k.gather_timing}, {"gather_census_us", ix->gather_us[0]}, {"gather_fill_us", ix->gather_us[1]},
         {"gather_scan_us", ix->gather_us[2]}, {"gather_rounds", ix->gather_rounds},
         {"order_min", k.order_min}, {"order_bits", k.order_bits}, {"order_last", (int)ix->order_last}};

@@ -121,6 +121,12 @@ struct WalkParams {
     // uint32, which for d <= 256 is the float walk's value exactly.
     uint32_t bq_classes;     // beam classes whose byte-walk first pass takes the integer instance: bit 0 one list register, bit 1 two, bit 2 the two-list kernel (in the struct's former tail padding)
     const uint8_t* q_b;      // [nq x dim] the queries as bytes, rows 16-byte aligned, or nullptr
+    // GBNNS_FLAG_HALF_WALK (last again): a PLAIN walk over a half-base handle's table -- the walked rows are binary16, `db` above is nullptr,
+    // `db_h` the handle's table (gbnns_index_create_half_base) and `dstride` the HALVES of a row (round_up(dim, 8), zero padded) = the floats
+    // of the staged query.  The distances are the float walk's on float32(db_h), operation for operation; no float copy of the table exists.
+    int32_t walk_half;       // 1: the first pass takes a half-walk instance (walk_half_base.hip) or the general kernel's the whole batch (walk_plan.cpp)
+    int32_t half_general;    // (with walk_half) 1: the handle knob "half_walk_fast" is 0 -- the general kernel's instance takes the whole batch also where the plan has a fast one
+    int32_t half_unkept;     // (with walk_half) 1: the knob is 2 -- also the fast instances of the dimension classes the measurement rule has not kept (walk_plan.cpp)
 };
 // uint8 -> float32, `count` values (every byte value is a binary32 value: nothing is rounded)
 hipError_t launch_widen_u8(const uint8_t* src, float* dst, size_t count, hipStream_t s);
@@ -135,7 +141,7 @@ hipError_t launch_walk(const WalkPlan& pl, const WalkParams& p, unsigned slots, 
 const char* walk_plan_name(const WalkPlan& pl);   // printable name of the plan's instance, template arguments included (no device needed); nullptr: none
 const char* walk_first_pass_name(hipStream_t s);  // (mangled) name of the first-pass kernel this thread launched last
 const char* walk_retry_pass_name(hipStream_t s);  // ... and of the retry-pass kernel
-hipError_t launch_walk_general(const WalkParams& p, int metric, hipStream_t s);  // (p.tagged: its instance with the tag test; p.bridged too: the one that looks through disallowed neighbours; p.walk_bytes: their byte-walk twins)
+hipError_t launch_walk_general(const WalkParams& p, int metric, hipStream_t s);  // (p.tagged: its instance with the tag test; p.bridged too: the one that looks through disallowed neighbours; p.walk_bytes: their byte-walk twins; p.walk_half: their half-walk twins)
 // GBNNS_FLAG_HALF_ROWS (walk_half.hip): src [n x sstride] (dim coordinates a row) -> out_h [n x hstride] binary16 bits, round to nearest even,
 // columns from dim on zero; out_f [n x fstride] the same values widened back (fstride <= hstride).  *bad_row (preset to 0xFFFFFFFF) receives the
 // lowest row that holds a coordinate which is not finite or rounds out of the binary16 range.

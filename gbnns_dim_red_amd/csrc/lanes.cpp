@@ -90,6 +90,11 @@ int search_check(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* top
     if ((!a->queries && !q_u8) || !a->out_ids) return fail(GBNNS_ERR_INVALID, "queries / out_ids missing");
     if (a->mode == GBNNS_MODE_NET && !ix->has_net) return fail(GBNNS_ERR_INVALID, "NET mode needs a net");
     if (a->mode != GBNNS_MODE_PLAIN && !ix->db_low) return fail(GBNNS_ERR_INVALID, "mode needs db_low");
+    if (a->flags & GBNNS_FLAG_HALF_WALK) {
+        if (a->flags & GBNNS_FLAG_BYTE_WALK) return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_HALF_WALK together with GBNNS_FLAG_BYTE_WALK: a handle has one kind of rows");
+        if (!ix->db_h_base) return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_HALF_WALK needs a half-base handle (gbnns_index_create_half_base)");
+        if (a->mode != GBNNS_MODE_PLAIN) return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_HALF_WALK: PLAIN only (NET / LOWQ walk db_low, which is float32)");
+    }
     if (a->mode == GBNNS_MODE_PLAIN && ix->db_b && !(a->flags & GBNNS_FLAG_BYTE_WALK))
         return fail(GBNNS_ERR_UNSUPPORTED, "GBNNS_MODE_PLAIN on a byte handle (gbnns_index_create_bytes) walks the uint8 rows: served with GBNNS_FLAG_BYTE_WALK only");
     if (a->flags & GBNNS_FLAG_BYTE_WALK) {
@@ -97,8 +102,8 @@ int search_check(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* top
         if (!ix->db_b) return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_BYTE_WALK needs a byte handle (gbnns_index_create_bytes)");
         if (a->mode != GBNNS_MODE_PLAIN) return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_BYTE_WALK: PLAIN only (NET / LOWQ walk db_low, which is float32)");
     }
-    if (a->mode == GBNNS_MODE_PLAIN && ix->db_h_base)
-        return fail(GBNNS_ERR_UNSUPPORTED, "GBNNS_MODE_PLAIN on a half-base handle (gbnns_index_create_half_base): there is no float table to walk and no half-row PLAIN walk; NET / LOWQ only");
+    if (a->mode == GBNNS_MODE_PLAIN && ix->db_h_base && !(a->flags & GBNNS_FLAG_HALF_WALK))
+        return fail(GBNNS_ERR_UNSUPPORTED, "GBNNS_MODE_PLAIN on a half-base handle (gbnns_index_create_half_base): there is no float table to walk; the half-row PLAIN walk is served with GBNNS_FLAG_HALF_WALK only");
     if (a->mode == GBNNS_MODE_LOWQ && !a->queries_low) return fail(GBNNS_ERR_INVALID, "queries_low missing");
     if ((a->flags & GBNNS_FLAG_LLF) && !(a->flags & GBNNS_FLAG_AUX_GRAPH))
         return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_LLF needs GBNNS_FLAG_AUX_GRAPH");

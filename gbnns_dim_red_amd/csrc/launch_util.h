@@ -60,10 +60,11 @@ const WalkEntry* walk_hot_entry(const WalkInstance& k);
 const WalkEntry* walk_coop_entry(const WalkInstance& k);
 const WalkEntry* walk_bitmap_entry(const WalkInstance& k);
 const WalkEntry* walk_half_entry(const WalkInstance& k);
-// (tables of their own, asked last by walk_entry, walk_l2.hip: only an instance with kTag / kBridge / kByteWalk / kByteQuery set matches a row of them)
+// (tables of their own, asked last by walk_entry, walk_l2.hip: only an instance with kTag / kBridge / kByteWalk / kByteQuery / kHalfWalk set matches a row of them)
 const WalkEntry* walk_tag_entry(const WalkInstance& k);
 const WalkEntry* walk_bridge_entry(const WalkInstance& k);
 const WalkEntry* walk_bytes_entry(const WalkInstance& k);
 const WalkEntry* walk_bytes_q_entry(const WalkInstance& k);
+const WalkEntry* walk_half_base_entry(const WalkInstance& k);
 
 }  // namespace gbnns

@@ -241,6 +241,7 @@ int gbnns_multi_search_ex(gbnns_multi* m, const gbnns_search_args* a) {
     // "NULL + lo" would take it for a buffer
     if (a->mode < GBNNS_MODE_NET || a->mode > GBNNS_MODE_PLAIN) return mfail(GBNNS_ERR_INVALID, "bad mode");
     if (a->flags & GBNNS_FLAG_BYTE_WALK) return mfail(GBNNS_ERR_INVALID, "GBNNS_FLAG_BYTE_WALK is not served by the gbnns_multi_* searches (their replicas are float handles)");
+    if (a->flags & GBNNS_FLAG_HALF_WALK) return mfail(GBNNS_ERR_INVALID, "GBNNS_FLAG_HALF_WALK is not served by the gbnns_multi_* searches (their replicas are float handles)");
     if (a->ef <= 0) return mfail(GBNNS_ERR_INVALID, "ef must be >= 1");
     if (a->n_q >= (1ull << 31)) return mfail(GBNNS_ERR_INVALID, "n_q too large");
     if (!a->queries || !a->out_ids) return mfail(GBNNS_ERR_INVALID, "queries / out_ids missing");
@@ -282,6 +283,7 @@ int gbnns_multi_search_device(gbnns_multi* m, const gbnns_search_args* tmpl, uin
     if (tmpl->struct_size != sizeof(gbnns_search_args)) return mfail(GBNNS_ERR_INVALID, "gbnns_search_args.struct_size mismatch");
     if (tmpl->mode == GBNNS_MODE_LOWQ) return mfail(GBNNS_ERR_UNSUPPORTED, "LOWQ mode is not offered in the device-block form");
     if (tmpl->flags & GBNNS_FLAG_BYTE_WALK) return mfail(GBNNS_ERR_INVALID, "GBNNS_FLAG_BYTE_WALK is not served by the gbnns_multi_* searches (their replicas are float handles)");
+    if (tmpl->flags & GBNNS_FLAG_HALF_WALK) return mfail(GBNNS_ERR_INVALID, "GBNNS_FLAG_HALF_WALK is not served by the gbnns_multi_* searches (their replicas are float handles)");
     if (n_q == 0) return GBNNS_OK;
     if (n_q >= (1ull << 31)) return mfail(GBNNS_ERR_INVALID, "n_q too large");
     const int R = (int)m->replicas.size();

@@ -151,6 +151,7 @@ CallFacts Call::call_facts() const {
     f.dim = plain ? ix->d : ix->d_low; f.dstride = plain ? ix->d_pad : ix->dl_pad;
     f.half_rows = !plain && (a->flags & GBNNS_FLAG_HALF_ROWS);
     f.walk_bytes = plain && ix->db_b;  // GBNNS_FLAG_BYTE_WALK (checked by search_call): the walked rows are the handle's uint8 rows, d_pad bytes each; no float table exists
+    f.walk_half = plain && ix->db_h_base;  // GBNNS_FLAG_HALF_WALK (checked by search_call): the walked rows are the handle's binary16 rows, d_pad halves each; no float table exists
     f.byte_queries = q_u8 != nullptr;
     f.mode = a->mode; f.ef = ef; f.n_entries = n_ent; f.flags = a->flags; f.hash_capacity = a->hash_capacity; f.nq = nq;
     f.tagged = tag != nullptr; f.bridged = tag && tag->bridge;
@@ -170,6 +171,7 @@ int Call::project() {
     if (plain) {
         w.q = q_dev; w.qstride = ix->d; w.db = ix->db;
         if (ix->db_b) { w.db = nullptr; w.db_b = ix->db_b; }
+        if (ix->db_h_base) { w.db = nullptr; w.db_h = ix->db_h_base; }
         w.q_b = w.walk_bytes ? qb_dev : nullptr;
     } else {
         if ((rc = L.q_low.ensure((size_t)nq * ix->dl_pad * 4))) return rc;

@@ -29,7 +29,12 @@ namespace {
 // row = the floats of the staged query) -- the three distances read the row through ByteRow4, a lane per row: l2_ordered / negdot_ordered on
 // float32(row), any dimension, both metrics.  Exact, not tuned.  It takes every flagged call outside the domain of walk_bytes.hip's instances
 // and every query those hand over.
-template <int METRIC, int TAG, bool BYTES = false, bool BWALK = false>
+// HWALK (GBNNS_FLAG_HALF_WALK: walk_general_hwalk_kernel<METRIC, TAG>): the WALKED rows are a half-base handle's binary16 rows (WalkParams::db_h,
+// p.dstride halves a row = the floats of the staged query) -- the three distances read the row through HalfRow4, a lane per row: l2_ordered /
+// negdot_ordered on float32(row), any dimension, both metrics (L2 never reads a coordinate beyond 4 * floor(d / 4): such a tail may hold any
+// bit pattern; the negative dot reads all d and the row's zero padding against the staged zeros).  Exact, not tuned.  It takes every flagged
+// call outside the domain of walk_half_base.hip's instances and every query those hand over.
+template <int METRIC, int TAG, bool BYTES = false, bool BWALK = false, bool HWALK = false>
 __device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* smem, uint32_t* bst = nullptr) {
     const int lane = lane_id();
     const uint32_t slot = blockIdx.x;
@@ -88,7 +93,8 @@ __device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* s
         const uint32_t entry = p.entries ? p.entries[(size_t)qi * n_ent + e] : 0u;
         {
             float d0;
-            if constexpr (BWALK) d0 = metric_dist<METRIC>(qs, ByteRow4{reinterpret_cast<const uint32_t*>(p.db_b + (size_t)entry * p.dstride)}, p.dim);
+            if constexpr (HWALK) d0 = metric_dist<METRIC>(qs, HalfRow4{reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(p.db_h) + (size_t)entry * p.dstride)}, p.dim);
+            else if constexpr (BWALK) d0 = metric_dist<METRIC>(qs, ByteRow4{reinterpret_cast<const uint32_t*>(p.db_b + (size_t)entry * p.dstride)}, p.dim);
             else d0 =
                 metric_dist<METRIC>(qs, reinterpret_cast<const float4*>(p.db + (size_t)entry * p.dstride),
                                     p.dim);
@@ -123,7 +129,9 @@ __device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* s
                     fresh = !(atomicOr(&bitmap[nb >> 5], bit) & bit);
                 }
                 uint32_t dk = 0xFFFFFFFFu;
-                if constexpr (BWALK) {
+                if constexpr (HWALK) {
+                    if (fresh) dk = fkey(metric_dist<METRIC>(qs, HalfRow4{reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(p.db_h) + (size_t)nb * p.dstride)}, p.dim));
+                } else if constexpr (BWALK) {
                     if (fresh) dk = fkey(metric_dist<METRIC>(qs, ByteRow4{reinterpret_cast<const uint32_t*>(p.db_b + (size_t)nb * p.dstride)}, p.dim));
                 } else
                 if (fresh)
@@ -161,7 +169,9 @@ __device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* s
                 fresh = !(atomicOr(&bitmap[nb >> 5], bit) & bit);
             }
             uint32_t dk = 0xFFFFFFFFu;
-            if constexpr (BWALK) {
+            if constexpr (HWALK) {
+                if (fresh) dk = fkey(metric_dist<METRIC>(qs, HalfRow4{reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(p.db_h) + (size_t)nb * p.dstride)}, p.dim));
+            } else if constexpr (BWALK) {
                 if (fresh) dk = fkey(metric_dist<METRIC>(qs, ByteRow4{reinterpret_cast<const uint32_t*>(p.db_b + (size_t)nb * p.dstride)}, p.dim));
             } else
             if (fresh)
@@ -288,6 +298,14 @@ __global__ __launch_bounds__(64) void walk_general_bwalk_kernel(WalkParams p) {
     walk_general_body<METRIC, TAG, false, true>(p, smem, TAG == 2 ? bst : nullptr);
 }
 
+// GBNNS_FLAG_HALF_WALK: plain, cut and bridged over binary16 walked rows
+template <int METRIC, int TAG>
+__global__ __launch_bounds__(64) void walk_general_hwalk_kernel(WalkParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ uint32_t bst[TAG == 2 ? 64 : 1];
+    walk_general_body<METRIC, TAG, false, false, true>(p, smem, TAG == 2 ? bst : nullptr);
+}
+
 template <typename K>
 hipError_t launch_general(K kernel, const WalkParams& p, size_t lds, hipStream_t s) {
     const hipError_t e = set_lds(kernel, lds);
@@ -337,6 +355,18 @@ __global__ __launch_bounds__(64) void debug_merge_kernel(const uint64_t* entries
 hipError_t launch_walk_general(const WalkParams& p, int metric, hipStream_t s) {
     if (p.nq == 0) return hipSuccess;
     const size_t lds = std::max((size_t)p.dstride * 4, (p.rr_db || p.rr_db_b) ? (size_t)p.rr_dstride * 4 : (size_t)0);
+    if (p.walk_half) {  // GBNNS_FLAG_HALF_WALK: a PLAIN walk over binary16 rows, no re-rank
+        if (!p.db_h || p.db || p.walk_bytes || p.rr_db || p.rr_db_b || (p.tagged && (!p.tags || !p.qtags))) return hipErrorInvalidValue;
+        const int tag = p.tagged ? (p.bridged ? 2 : 1) : 0;
+        if (metric == 1) {
+            if (tag == 2) return launch_general(walk_general_hwalk_kernel<1, 2>, p, lds, s);
+            if (tag == 1) return launch_general(walk_general_hwalk_kernel<1, 1>, p, lds, s);
+            return launch_general(walk_general_hwalk_kernel<1, 0>, p, lds, s);
+        }
+        if (tag == 2) return launch_general(walk_general_hwalk_kernel<0, 2>, p, lds, s);
+        if (tag == 1) return launch_general(walk_general_hwalk_kernel<0, 1>, p, lds, s);
+        return launch_general(walk_general_hwalk_kernel<0, 0>, p, lds, s);
+    }
     if (p.walk_bytes) {  // GBNNS_FLAG_BYTE_WALK: a PLAIN walk over uint8 rows, no re-rank
         if (!p.db_b || p.rr_db || p.rr_db_b || (p.tagged && (!p.tags || !p.qtags))) return hipErrorInvalidValue;
         const int tag = p.tagged ? (p.bridged ? 2 : 1) : 0;

@@ -266,12 +266,17 @@ __global__ __launch_bounds__(64) void walk_bitmap_kernel(WalkParams p) {
 // chunks packed until l2_pair_from_bytes consumes them, and the query (128 floats) is re-read from LDS every hop; nothing else differs
 // kByteQuery (BQ, with kByteWalk): gbnns_search_byte_queries (walk_bytes_q.hip) -- the query is read as bytes from WalkParams::q_b into 16 registers (ByteQuery: no
 // query area in LDS, the visited set starts where it would) and the distance is l2_pair_u8's integer one, the entry row's included
+// kHalfWalk (HWALK): GBNNS_FLAG_HALF_WALK (walk_half_base.hip; L2, compact index) -- the walked rows are a half-base handle's binary16 rows (WalkParams::db_h,
+// p.dstride halves a row; p.db is nullptr), the entry row's included.  STEPS = 24 (d = 96, 192-byte rows): the HALF hop, and the entry row loaded
+// the same way -- a lane's six 16-byte loads, widened, through the pair-form distance.  STEPS = 0 (d >= 128, d % 4 == 0): the hop's distances
+// are l2_pair_rows_half's (walk_lists.h), the entry row goes a lane per row through HalfRow4 -- the same sums.  Nothing else differs
 template <int METRIC, int STEPS, int R, uint32_t FLAGS>
 __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, unsigned char* smem,
                                              uint32_t* ovf_count, uint32_t* ovf_list, uint32_t* bitmap = nullptr) {
-    static_assert(!(FLAGS & ~(kOff32 | kOne | kAux | kLate | kHalf | kTag | kByteWalk | kByteQuery | kBitmap | kQueryLds | kNeverLate)), "a switch this walk does not have");
+    static_assert(!(FLAGS & ~(kOff32 | kOne | kAux | kLate | kHalf | kTag | kByteWalk | kByteQuery | kBitmap | kQueryLds | kNeverLate | kHalfWalk)), "a switch this walk does not have");
     constexpr bool OFF32 = FLAGS & kOff32, ONE_CHUNK = FLAGS & kOne, AUX = FLAGS & kAux, BITMAP = FLAGS & kBitmap, QLDS_W = FLAGS & kQueryLds;
-    constexpr bool HALF = FLAGS & kHalf, TAG = FLAGS & kTag, BYTES = FLAGS & kByteWalk, BQ = FLAGS & kByteQuery;
+    constexpr bool HWALK = FLAGS & kHalfWalk;
+    constexpr bool HALF = (FLAGS & kHalf) || (HWALK && STEPS > 0), TAG = FLAGS & kTag, BYTES = FLAGS & kByteWalk, BQ = FLAGS & kByteQuery;
     constexpr int LATE = (FLAGS & kLate) ? 1 : ((FLAGS & kNeverLate) ? 0 : -1);
     static_assert(!(AUX && ONE_CHUNK), "auxiliary rows have their own length");
 #ifdef GBNNS_STAMPS
@@ -294,6 +299,7 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
     static_assert(!TAG || (kPair && OFF32 && !BITMAP && !HALF), "TAG: pair-form instances of a compact index");
     static_assert(!BYTES || (METRIC == 0 && STEPS == 8 && OFF32 && !AUX && !BITMAP && !QLDS_W && !HALF && !TAG), "BYTES: L2 over 128-byte uint8 rows of a compact index");
     static_assert(!BQ || BYTES, "BQ: byte queries over byte rows");
+    static_assert(!HWALK || (METRIC == 0 && (STEPS == 0 || STEPS == 24) && OFF32 && !AUX && !BITMAP && !QLDS_W && !TAG && !BYTES && !(FLAGS & kHalf)), "HWALK: L2 over binary16 rows of a compact index");
     const int lane = lane_id();
     const uint32_t slot = kPair ? (uint32_t)lane >> 1 : (uint32_t)lane;    // adjacency slot of this lane
     const uint32_t half = kPair ? (uint32_t)lane & 1u : 0u;
@@ -356,6 +362,13 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
             load_row_alt(er, reinterpret_cast<const float*>(p.db_b + entry * kRowBytes + half * 16u));
             d0 = __uint_as_float(readlane_u32(__float_as_uint(l2_pair_u8(er, bq)), 1));
         } else if constexpr (BYTES) d0 = metric_dist<0>(qs, ByteRow4{reinterpret_cast<const uint32_t*>(p.db_b + entry * kRowBytes)}, p.dim);  // (a lane per row: the same sums)
+        else if constexpr (HWALK && STEPS > 0) {  // the pair form, from the half table (every pair computes it; the odd lane holds it)
+            HalfRowRegs<kQSteps> eh;
+            RowRegs<kQSteps> er;
+            load_row_half<kQSteps>(eh, reinterpret_cast<const char*>(p.db_h) + entry * (kRowBytes / 2u) + half * (kRowBytes / 4u));
+            widen_row(er, eh);
+            d0 = __uint_as_float(readlane_u32(__float_as_uint(l2_pair_from_regs_wide<kQSteps>(er, qreg.v)), 1));
+        } else if constexpr (HWALK) d0 = metric_dist<0>(qs, HalfRow4{reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(p.db_h) + entry * (p.dstride * 2u))}, p.dim);  // (a lane per row: the same sums)
         else d0 = walk_dist<METRIC, STEPS>(qs, row_ptr<OFF32>(p.db, entry, p.dstride), p.dim);
         worst = fkey(d0);
         if (lane == 0) {
@@ -630,6 +643,10 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
             } else {
                 if constexpr (METRIC == 0 && STEPS == 0) {
                     // long rows (PLAIN walks over the original vectors): four lanes per row (l2_quad_rows); short ones: a lane per row
+                    if constexpr (HWALK) {  // (binary16 rows: two lanes per row)
+                        const float dq = l2_pair_rows_half(mfresh, nb, p.db_h, p.dstride, qf, lane);
+                        dk = fresh ? fkey(dq) : 0xFFFFFFFFu;
+                    } else
                     if (p.dim >= kQuadRowsMinDim) {
                         const float dq = l2_quad_rows<OFF32>(mfresh, nb, p.db, p.dstride, p.dim, qf, lane);
                         dk = fresh ? fkey(dq) : 0xFFFFFFFFu;
@@ -725,9 +742,10 @@ __device__ __forceinline__ void walk_reg_one(const WalkParams& p, uint32_t qi, u
 template <int METRIC, int STEPS, uint32_t FLAGS>
 __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t qi, unsigned char* smem,
                                                  uint32_t* ovf_count, uint32_t* ovf_list, uint32_t* bitmap = nullptr) {
-    static_assert(!(FLAGS & ~(kOff32 | kOne | kAux | kLate | kHalf | kTag | kByteWalk | kByteQuery | kBitmap)), "a switch this walk does not have");
+    static_assert(!(FLAGS & ~(kOff32 | kOne | kAux | kLate | kHalf | kTag | kByteWalk | kByteQuery | kBitmap | kHalfWalk)), "a switch this walk does not have");
     constexpr bool OFF32 = FLAGS & kOff32, ONE_PASS = FLAGS & kOne, AUX = FLAGS & kAux, BITMAP = FLAGS & kBitmap, LATE = FLAGS & kLate;
-    constexpr bool HALF = FLAGS & kHalf, TAG = FLAGS & kTag, BYTES = FLAGS & kByteWalk, BQ = FLAGS & kByteQuery;
+    constexpr bool HWALK = FLAGS & kHalfWalk;  // (as in walk_reg_one)
+    constexpr bool HALF = (FLAGS & kHalf) || (HWALK && STEPS > 0), TAG = FLAGS & kTag, BYTES = FLAGS & kByteWalk, BQ = FLAGS & kByteQuery;
     constexpr bool kEarlyLoad = (STEPS > 0);
     // 128-byte rows, and 192- / 256- / 384- / 512- / 576-byte rows with L2: two lanes per neighbour
     constexpr bool kPair = (STEPS == 8) || ((STEPS == 12 || STEPS == 16 || STEPS == 24 || STEPS == 32 || STEPS == 36) && METRIC == 0);
@@ -748,6 +766,7 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
     static_assert(!TAG || (kPair && OFF32 && !BITMAP && !HALF), "TAG: pair-form instances of a compact index");
     static_assert(!BYTES || (METRIC == 0 && STEPS == 8 && OFF32 && !AUX && !BITMAP && !LATE && !HALF && !TAG), "BYTES: L2 over 128-byte uint8 rows of a compact index");
     static_assert(!BQ || BYTES, "BQ: byte queries over byte rows");
+    static_assert(!HWALK || (METRIC == 0 && (STEPS == 0 || STEPS == 24) && OFF32 && !AUX && !BITMAP && !LATE && !TAG && !BYTES && !(FLAGS & kHalf)), "HWALK: L2 over binary16 rows of a compact index");
     const int lane = lane_id();
 #ifdef GBNNS_STAMPS  // diagnostic build: cycles per segment of the hop (tools/stamps.py)
     unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -817,7 +836,11 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
             // the one-lane form reads the whole row and the whole query into registers and was the kernel's register peak
             RowRegs<kQSteps> er;
             if constexpr (BYTES) load_row_alt(er, reinterpret_cast<const float*>(p.db_b + entry * kRowBytes + half * 16u));
-            else {
+            else if constexpr (HWALK) {  // from the half table, as a hop loads its rows
+                HalfRowRegs<kQSteps> eh;
+                load_row_half<kQSteps>(eh, reinterpret_cast<const char*>(p.db_h) + entry * (kRowBytes / 2u) + half * (kRowBytes / 4u));
+                widen_row(er, eh);
+            } else {
             const float* rp = row_ptr<OFF32>(p.db, entry, p.dstride) + half * (kAlt ? 4u : kRowBytes / 8u);
             if constexpr (kAlt) load_row_alt(er, rp);
             else load_row<kQSteps>(er, rp);
@@ -830,6 +853,8 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
             else if constexpr (kQLds) kd = fkey_sumsq(l2_pair_from_regs_wide<kQSteps>(er, qs + kQSteps * half));
             else kd = fkey_sumsq(l2_pair_from_regs_wide<kQSteps>(er, qreg.v));
             k0 = readlane_u32(kd, 1);  // odd lanes hold the distance
+        } else if constexpr (HWALK) {  // (a lane per row: the same sums)
+            k0 = fkey(metric_dist<0>(qs, HalfRow4{reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(p.db_h) + entry * (p.dstride * 2u))}, p.dim));
         } else {
             k0 = fkey(walk_dist<METRIC, STEPS>(qs, row_ptr<OFF32>(p.db, entry, p.dstride), p.dim));
         }
@@ -1000,6 +1025,10 @@ __device__ __forceinline__ void walk_reg_big_one(const WalkParams& p, uint32_t q
             } else {
                 if constexpr (METRIC == 0 && STEPS == 0) {
                     // long rows (PLAIN walks over the original vectors): four lanes per row (l2_quad_rows); short ones: a lane per row
+                    if constexpr (HWALK) {  // (binary16 rows: two lanes per row)
+                        const float dq = l2_pair_rows_half(mfresh, nb, p.db_h, p.dstride, qf, lane);
+                        dk = fresh ? fkey(dq) : 0xFFFFFFFFu;
+                    } else
                     if (p.dim >= kQuadRowsMinDim) {
                         const float dq = l2_quad_rows<OFF32>(mfresh, nb, p.db, p.dstride, p.dim, qf, lane);
                         dk = fresh ? fkey(dq) : 0xFFFFFFFFu;

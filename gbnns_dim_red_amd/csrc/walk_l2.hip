@@ -22,7 +22,7 @@ uint32_t walk_hash_entries(size_t bytes, int form) {
 }
 
 static const WalkEntry* walk_entry(const WalkInstance& k) {
-    for (auto unit : {walk_hot_entry, walk_l2_entry, walk_dot_entry, walk_wide_entry, walk_wide2_entry, walk_wide3_entry, walk_coop_entry, walk_bitmap_entry, walk_half_entry, walk_tag_entry, walk_bridge_entry, walk_bytes_entry, walk_bytes_q_entry})
+    for (auto unit : {walk_hot_entry, walk_l2_entry, walk_dot_entry, walk_wide_entry, walk_wide2_entry, walk_wide3_entry, walk_coop_entry, walk_bitmap_entry, walk_half_entry, walk_tag_entry, walk_bridge_entry, walk_bytes_entry, walk_bytes_q_entry, walk_half_base_entry})
         if (const WalkEntry* e = unit(k)) return e;
     return nullptr;
 }

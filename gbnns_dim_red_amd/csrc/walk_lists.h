@@ -354,6 +354,88 @@ __device__ __forceinline__ float l2_quad_rows(uint64_t mfresh, uint32_t nb, cons
     return out;
 }
 
+// position of the n-th (from 0) set bit of a wave-uniform mask, n a per-lane value below its population count: a binary search on counts
+__device__ __forceinline__ uint32_t nth_set_bit(uint64_t m, uint32_t n) {
+    uint32_t w = (uint32_t)m, pos = 0u;
+    const uint32_t c32 = (uint32_t)__popc(w);
+    if (n >= c32) { n -= c32; w = (uint32_t)(m >> 32); pos = 32u; }
+#pragma unroll
+    for (uint32_t sh = 16u; sh; sh >>= 1) {
+        const uint32_t c = (uint32_t)__popc(w & ((1u << sh) - 1u));
+        if (n >= c) { n -= c; w >>= sh; pos += sh; }
+    }
+    return pos;
+}
+
+// The half form of l2_quad_rows (GBNNS_FLAG_HALF_WALK, walk_half_base.hip: the run-time-length instances over a half-base handle's rows, d >= 128,
+// d % 4 == 0) on the chunk-pair arithmetic of rerank_half_core (half_chunk_add, walk_common.h): two lanes share a row, 32 new rows per
+// round -- pair i takes the i-th of the round's rows; the even lane reads the 16-byte chunks 0, 2, 4, ... of the row of `hstride` halves,
+// the odd lane 1, 3, 5, ... (a pair reads 32 contiguous bytes per load), the running sums hop to the partner once per chunk, an odd chunk
+// count leaves the last chunk to the even lane, and a d % 8 == 4 row's last half-chunk is the row's zero padding against the zeros staged
+// behind the query in `qf` (hstride floats).  Eight loads in flight per lane, then four, then what is left -- at most three pairs and the
+// lone chunk -- as ONE masked batch (a chunk that is not there reads nothing and adds +0 to sums of squares: no change).  `mfresh` = the
+// lanes that need the distance of their row `nb`.  Returns it in those lanes: l2_ordered on float32(row), operation for operation.
+__device__ __forceinline__ float l2_pair_rows_half(uint64_t mfresh, uint32_t nb, const void* db_h, uint32_t hstride, const float* qf, int lane) {
+    float out = 0.f;
+    const uint32_t half = (uint32_t)lane & 1u, g = (uint32_t)lane >> 1;
+    const uint32_t chunks = hstride >> 3, cpairs = chunks >> 1, ctotal = cpairs + (chunks & 1u);
+    const float4* qh = reinterpret_cast<const float4*>(qf) + 2u * half;  // (a chunk's 8 coordinates are two float4 of the staged query)
+    uint64_t m = mfresh;
+    while (m) {
+        const uint32_t nrows = min((uint32_t)__popcll(m), 32u);
+        const uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        const bool owner = ((m >> lane) & 1ull) && rank < 32u;  // this lane's row is one of the round's
+        const uint32_t src = nth_set_bit(m, g);
+        uint32_t id = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)nb);
+        id = g < nrows ? id : 0u;  // (idle pairs read row 0)
+        const uint4* row = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(db_h) + id * (hstride * 2u)) + half;
+        float u[4], v[4] = {0.f, 0.f, 0.f, 0.f};
+        uint32_t k = 0;
+        for (; k + 8 <= cpairs; k += 8) {
+            uint4 rv[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) rv[j] = row[2 * (k + j)];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float4* qc = qh + 4 * (k + j);
+                const float4 q[2] = {qc[0], qc[1]};
+                half_chunk_add(rv[j], q, u, v);
+            }
+        }
+        for (; k + 4 <= cpairs; k += 4) {
+            uint4 rv[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) rv[j] = row[2 * (k + j)];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float4* qc = qh + 4 * (k + j);
+                const float4 q[2] = {qc[0], qc[1]};
+                half_chunk_add(rv[j], q, u, v);
+            }
+        }
+        if (k < ctotal) {
+            uint4 rv[4];
+            float4 q[4][2];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool mine = k + j < cpairs || (k + j < ctotal && !half);
+                const float4* qc = qh + 4 * (k + j);
+                rv[j] = mine ? row[2 * (k + j)] : make_uint4(0u, 0u, 0u, 0u);
+                q[j][0] = mine ? qc[0] : make_float4(0.f, 0.f, 0.f, 0.f);
+                q[j][1] = mine ? qc[1] : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (k + j < ctotal) half_chunk_add(rv[j], q[j], u, v);
+        }
+        const float dv = ((v[0] + v[1]) + v[2]) + v[3];  // (the odd lane's is the row's)
+        const float dr = __int_as_float(__builtin_amdgcn_ds_bpermute((int)((2u * rank + 1u) << 2), __float_as_int(dv)));
+        out = owner ? dr : out;
+        m &= ~__ballot(owner);
+    }
+    return out;
+}
+
 // Register-resident result list: entry of rank i lives in register i / 64 of lane i % 64
 // (R registers per lane, ef <= 64 * R).  Empty slots hold all-ones, which reads as "expanded".
 template <int R>

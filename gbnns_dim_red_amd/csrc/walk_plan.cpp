@@ -93,6 +93,41 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
         }
         return pl;  // (no rr_* room: PLAIN has no re-rank)
     }
+    if (p.walk_half) {
+        // GBNNS_FLAG_HALF_WALK: the walked rows are a half-base handle's binary16 rows (WalkParams::db_h; dstride = the HALVES of a row).  The
+        // half-walk instances (walk_half_base.hip): first pass, L2, compact index (the half table, the adjacency table < 4 GiB, 24-bit ids), one
+        // entry point per query, no auxiliary graph, untagged, ef <= 1 024 --
+        //   d = 96 (192-byte rows): the 24-step pair form in the instance set the float path has for it -- one list register over one- and
+        //     two-pass adjacency rows, two list registers over one-pass rows, the two-list kernel without and with the pass loop;
+        //   d >= 128, d % 4 == 0: the run-time-length instances on l2_pair_rows_half -- one list register (ONE_CHUNK: rows of one 64-slot pass),
+        //     two list registers, the two-list kernel (ONE_PASS likewise).
+        // Everything else -- and the whole batch with the handle knob "half_walk_fast" = 0 (WalkParams::half_general) -- runs on the general kernel's
+        // half-walk instance, which is also where a fast instance's hand-overs go: there is no half form of the retry pass, the bitmap pass,
+        // the two-wavefront walk, the walk_hot* family, late rows or the LDS-list kernel.
+        // The rule (tools/half_walk_timing.py, profiles/half_walk_timing.txt): a dimension class stays on its fast instance only if
+        // that beat the general instance by more than the float baseline's own run-to-run range in the same run, at every beam of the class.
+        //   d = 96 (deep, 10^6 x 96, 10 000 queries, ef 40 / 80 / 120 / 160 / 200): fast 0.371 / 0.681 / 0.930 / 1.454 / 1.980 ms against the general
+        //     instance's 45.0 / 78.8 / 107.4 / 143.9 / 180.5 ms, float ranges 0.007 - 0.027 ms: KEPT.
+        //   d >= 128 (gist's 960, glove's 300): not measured yet -- by the rule such a class goes to the general instance (kLongRowsKept); its
+        //     fast instances run with the handle knob "half_walk_fast" = 2 (WalkParams::half_unkept: the timing tool and the tests).
+        constexpr bool kLongRowsKept = false;
+        const bool compact = !p.force_wide && (uint64_t)p.n * p.dstride * 2 < (1ull << 32) && (uint64_t)p.n * p.ell_stride * 4 < (1ull << 32) && p.n <= 0xFFFFFFu;
+        const bool domain = !p.half_general && pass == WalkPass::First && metric == 0 && compact && p.n_entries <= 1u && !aux && !p.tagged && ef <= kRegListMaxEf &&
+                            p.dstride == ((p.dim + 7u) & ~7u);
+        const bool pair24 = domain && p.dim == 96u && (regs == 4 || one || (regs == 1 && p.ell_stride <= 64u));
+        const bool longrow = domain && p.dim >= 128u && p.dim % 4u == 0u && (kLongRowsKept || p.half_unkept);
+        pl.coop_serves = false;
+        pl.lds_list = false;
+        pl.general_only = !(pair24 || longrow);
+        if (pair24) k = {regs == 4 ? WalkFamily::TwoList : WalkFamily::RegList, 0, 24, regs, kOff32 | flag_if(one, kOne) | kHalfWalk};
+        else if (longrow) k = {regs == 4 ? WalkFamily::TwoList : WalkFamily::RegList, 0, 0, regs, kOff32 | flag_if(regs != 2 && p.ell_stride <= 64u, kOne) | kHalfWalk};
+        if (!pl.general_only) {
+            pl.packed = true;
+            pl.lds_fixed = lds_fixed_bytes(ef, p.dstride, false, false, false);  // (the query: dstride floats)
+            pl.knows_quotient = true;  // (as the float register-list / two-list instances of a compact index)
+        }
+        return pl;  // (no rr_* room: PLAIN has no re-rank)
+    }
     if (pass == WalkPass::Bitmap) {
         // The bitmap first pass runs the register-list (ef <= 128, L2) / two-list (128 < ef <= 1 024, both metrics) walk for 128-byte rows
         // of a compact index, the two-list walk for 256- and 576-byte rows with L2 (the reference's glove 300 -> 144), else the LDS-list walk.

@@ -54,6 +54,7 @@ enum class WalkFamily : uint8_t {
                 // bridge (register lists): walk_bridge_kernel<METRIC, STEPS, R>                (walk_bridge.hip)
                 // byte walk (either family): walk_reg_bytes_kernel<R, ONE_CHUNK> / walk_reg_big_bytes_kernel<ONE_PASS> (walk_bytes.hip)
                 // ... with byte queries: beam_u8_kernel<R, ONE_CHUNK> / beam_u8_big_kernel<ONE_PASS> (walk_bytes_q.hip)
+                // half walk (either family): walk_reg_hwalk_kernel<STEPS, R, ONE_CHUNK> / walk_reg_big_hwalk_kernel<STEPS, ONE_PASS> (walk_half_base.hip)
     LdsList,    // walk_fast_kernel<METRIC, STEPS, RETRY, PACKED>                    (walk_l2 / walk_dot / walk_wide)
     BitmapReg,  // walk_bitmap_reg_kernel<METRIC, R>                                 (walk_bitmap.hip)
     BitmapBig,  // walk_bitmap_big_kernel<METRIC, STEPS, ONE_PASS, LATE>
@@ -79,6 +80,7 @@ enum WalkFlag : uint32_t {
     kBitmap = 1u << 13,     // from here on the device templates only, never in a WalkInstance (its family says as much): visited set = one bit per node in HBM (walk_bitmap_*_kernel)
     kQueryLds = 1u << 14,   // walk_reg_one: the lane's query pieces are re-read from LDS every hop (walk_reg_wide_kernel)
     kNeverLate = 1u << 15,  // walk_reg_one: rows never requested after the visited test (without it and without kLate: by WalkParams::late_rows)
+    kHalfWalk = 1u << 16,   // (a WalkInstance flag again) the WALKED rows are a half-base handle's binary16 rows (WalkParams::db_h, GBNNS_FLAG_HALF_WALK), the entry row's included: walk_reg_hwalk_kernel / walk_reg_big_hwalk_kernel (walk_half_base.hip)
 };
 __host__ __device__ constexpr uint32_t flag_if(bool on, uint32_t flag) { return on ? flag : 0u; }
 
@@ -101,7 +103,7 @@ struct WalkPlan {
     bool knows_quotient;   // the instance reads WalkParams::vs_shr
     bool lds_list;         // result list in LDS as one sorted array: no fused re-rank
     bool coop_serves;      // the two-wavefront walk has an instance for this shape (whether or not this plan is it)
-    bool general_only;     // several entry points per query, or a tagged / bridged / byte-walk call outside its instances' domain: the general kernel takes the whole batch
+    bool general_only;     // several entry points per query, or a tagged / bridged / byte-walk / half-walk call outside its instances' domain: the general kernel takes the whole batch
     size_t rr_base;        // room of the fused re-rank's query = rr_base (+ the visited set's bytes when rr_in_table)
     bool rr_in_table;      // (rr_room below)
     // form of the visited set (walk_hash_bytes, kernels.h); vs_shr is set only where the instance knows the quotient form
@@ -113,7 +115,7 @@ struct WalkPlan {
 // GBNNS_STAMPS_GENERIC keeps diagnostic (GBNNS_STAMPS) builds off the hot two-list instances.
 struct WalkEnv { bool wide2, stamps_generic; };
 const WalkEnv& walk_env();
-// Reads the shape (dim, dstride, n, ell_stride, aux_ell / aux_stride), ef, n_entries, force_wide, coop, late_rows, spec_rows, stamps_on, half_rows, tagged, bridged, generic_only, bytes_dim, walk_bytes,
+// Reads the shape (dim, dstride, n, ell_stride, aux_ell / aux_stride), ef, n_entries, force_wide, coop, late_rows, spec_rows, stamps_on, half_rows, tagged, bridged, generic_only, bytes_dim, walk_bytes, walk_half, half_general, half_unkept,
 // q_b (whether the call brought byte queries), bq_classes and rr_reserve -- nothing the sizing rule writes (hash_cap, hash_limit, vs_shr), so the layout is known before the visited set is sized.
 WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv& env = walk_env());
 

@@ -135,11 +135,11 @@ int gbnns_index_is_bytes(const gbnns_index* index);   /* 1: created by gbnns_ind
  * gbnns_rerank_topk, gbnns_project, gbnns_index_tag_census, several entry points, the auxiliary graph, HOST or DEVICE buffers, batches in
  * flight.  Every search runs the very first-pass kernel a float handle runs under GBNNS_FLAG_NO_FUSED_RERANK, and the stand-alone half
  * re-rank (rerank_half.hip; gbnns_debug_half_base_plan tells which kernel) follows on the same stream.
- * Refused: GBNNS_MODE_PLAIN (GBNNS_ERR_UNSUPPORTED: there is no float table to walk), gbnns_index_exact_knn, gbnns_index_exact_knn_gather and
+ * With GBNNS_FLAG_HALF_WALK (below), gbnns_search_ex and gbnns_search_tagged also run in GBNNS_MODE_PLAIN, which walks the binary16 rows themselves.
+ * Refused: GBNNS_MODE_PLAIN without that flag (GBNNS_ERR_UNSUPPORTED: there is no float table to walk), gbnns_index_exact_knn, gbnns_index_exact_knn_gather and
  * gbnns_search_tagged_auto (GBNNS_ERR_UNSUPPORTED: they scan the resident table), GBNNS_FLAG_BYTE_WALK and gbnns_search_byte_queries
  * (GBNNS_ERR_INVALID, as on a float handle).  gbnns_multi_create has no half form.
- * Out of scope so far: a half re-rank fused into the walk kernels, a PLAIN walk over half rows, resident exact scans over a half table, half
- * queries. */
+ * Out of scope so far: a half re-rank fused into the walk kernels, resident exact scans over a half table, half queries. */
 int gbnns_index_create_half_base(const gbnns_index_desc* desc, const uint16_t* db_half, gbnns_index** out);
 int gbnns_index_is_half_base(const gbnns_index* index);   /* 1: created by gbnns_index_create_half_base; 0: not (or NULL) */
 int gbnns_index_destroy(gbnns_index* index);
@@ -439,6 +439,30 @@ int gbnns_search_tagged(gbnns_index* index, const gbnns_search_args* args, const
  * and in gbnns_debug_byte_walk_plan), which is exact, not tuned: a lane per row. */
 #define GBNNS_FLAG_BYTE_WALK 2048u
 
+/* Half-row PLAIN walk on a half-base handle (gbnns_index_create_half_base): GBNNS_MODE_PLAIN in gbnns_search_ex / gbnns_search_batch and in
+ * gbnns_search_tagged (cut and with GBNNS_FLAG_TAG_BRIDGE) walks the binary16 rows themselves -- the hnsw half of the reference's
+ * final_test, the efs_hnsw sweeps, on the handle that keeps the original table at two bytes a coordinate.
+ * Contract: every output equals, bit for bit, what the same call WITHOUT this flag returns on the float handle created with
+ * db = float32(db_half): ids, out_cand in pop order, out_cand_dist bit patterns, hops, dist_calc and edges -- for every k, both metrics, any
+ * d (the L2 d % 4 tail is never read into a sum and may hold any bit pattern; the dot reads all d and its masked tail the zero padding),
+ * several entry points, GBNNS_FLAG_AUX_GRAPH / GBNNS_FLAG_LLF, GBNNS_FLAG_WIDE_INDEX, hash_capacity, GBNNS_FLAG_SERIAL,
+ * GBNNS_FLAG_DEFER_JOIN, HOST or DEVICE buffers.  GBNNS_FLAG_BITMAP_PASS is ignored.  (Widening binary16 is exact, the query is never
+ * rounded, and the sums run in float32 in the reference's order.)  No float copy of the table is made, on the device or the host, at any
+ * point.
+ * Refused with GBNNS_ERR_INVALID: the flag on a float or a byte handle; the flag with NET / LOWQ (the walked space is db_low, which is
+ * float32); the flag together with GBNNS_FLAG_BYTE_WALK; the flag in the gbnns_multi_* searches.  uint8 and float16 queries stay refused,
+ * and gbnns_search_topk in PLAIN mode stays GBNNS_ERR_INVALID as on every handle.  The walk is opt-in: GBNNS_MODE_PLAIN without the flag on
+ * a half-base handle stays GBNNS_ERR_UNSUPPORTED.
+ * Kernels: L2 on a compact index (n < 2^24, the half table and the adjacency table < 4 GiB), one entry point per query, no auxiliary graph,
+ * untagged, ef <= 1 024 run a half-walk first pass (walk_reg_hwalk_kernel<STEPS, R, ONE_CHUNK> / walk_reg_big_hwalk_kernel<STEPS, ONE_PASS>
+ * in gbnns_profile.walk_kernel): d == 96 the 24-step pair form (six 16-byte loads a lane, packed until widened); d >= 128 with d % 4 == 0
+ * the run-time-length form, two lanes per row over 16-byte chunks -- built and exact, but not measured against the general instance yet, so
+ * only a handle whose knob "half_walk_fast" is 2 takes it (default 1: such a call runs on the general instance).  They have no retry pass; what they hand over, and every other flagged
+ * call -- other dimensions, the negative dot, several entry points, the auxiliary graph, GBNNS_FLAG_WIDE_INDEX, beams above 1 024, every
+ * tagged or bridged call, and every call of a handle whose knob "half_walk_fast" is 0 -- runs on the general kernel's half-walk instance
+ * ("walk_general_kernel" in the profile and in gbnns_debug_half_walk_plan), which is exact, not tuned: a lane per row. */
+#define GBNNS_FLAG_HALF_WALK 8192u
+
 /* Byte queries on a byte handle (gbnns_index_create_bytes): the search whose queries are uint8 as well -- BIGANN's query files are .bvecs too.
  * `queries_u8` is [n_q x d] dense bytes, a buffer of args->mem_kind; args->queries must be NULL.  query_tags == NULL: untagged; k / out_top_*
  * as in gbnns_search_tagged (k == 0 and both NULL: no k-answer rows).
@@ -590,6 +614,11 @@ int gbnns_debug_half_base_plan(int metric, uint32_t d, char* name, uint32_t name
  * visited set.  `dim` is the original dimension -- the walked row is round_up(dim, 16) bytes --, `tagged` != 0 a gbnns_search_tagged call;
  * the other inputs as for gbnns_debug_walk_plan. */
 int gbnns_debug_byte_walk_plan(int metric, uint32_t dim, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries, int force_wide,
+                               int tagged, char* name, uint32_t name_bytes, uint64_t* lds_bytes);
+/* Diagnostic, no device needed: the same for a GBNNS_MODE_PLAIN call with GBNNS_FLAG_HALF_WALK on a half-base handle (knob "half_walk_fast" = 2: every
+ * first-pass instance the library has, also those of a dimension class the default, 1, leaves to the general instance).
+ * `dim` is the original dimension -- the walked row is round_up(dim, 8) halves. */
+int gbnns_debug_half_walk_plan(int metric, uint32_t dim, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries, int force_wide,
                                int tagged, char* name, uint32_t name_bytes, uint64_t* lds_bytes);
 /* The same for a gbnns_search_byte_queries call of that shape with the knob "byte_query_int" = 7 (every beam class): the integer instance
  * inside the byte-walk first pass's domain (its query lives in registers: 512 bytes of LDS less), "walk_general_kernel" outside it. */
