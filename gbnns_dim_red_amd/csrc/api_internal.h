@@ -11,15 +11,18 @@
 //   sizing.cpp      the visited-set sizing rule of the first pass (capacity, form, wavefronts per CU), called by the plan
 //   walk_plan.cpp   which walk kernel instance serves a pass over a shape, and its LDS layout (walk_plan.h; no HIP calls)
 //   pin.cpp         gbnns_host_pin / gbnns_host_unpin and the page registry
+//   row_kind.h      RowKind: float32 / uint8 / binary16 original-space rows -- the one statement of a handle's kind (gbnns_index::rows)
 #pragma once
 
 #include "../../include/gbnns.h"
 #include "call_plan.h"
+#include "row_kind.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
+#include <cassert>
 #include <chrono>
 #include <cstdarg>
 #include <cstdio>
@@ -178,16 +181,20 @@ struct gbnns_index {
     uint64_t n = 0;
     uint32_t d = 0, d_low = 0, d_hidden = 0;
     uint32_t d_pad = 0, dl_pad = 0;
-    const float* db = nullptr;      // [n x d_pad]; nullptr on a byte handle
-    // gbnns_index_create_bytes: the original-space table as uint8 rows of d_pad BYTES (d_pad = round_up(d, 16) on such a handle: the bytes
-    // of a row and the floats of a staged re-rank query), zero padded, 16-byte aligned; borrowed or db_b_own's.  No float copy exists.
-    const uint8_t* db_b = nullptr;
-    // gbnns_index_create_half_base: the original-space table as binary16 rows of d_pad HALVES (d_pad = round_up(d, 8) on such a handle: the
-    // halves of a row and the floats of a staged re-rank query), zero padded, 16-byte aligned; borrowed or db_h_base_own's.  No float copy
-    // exists.  (Not low_half: that is the WALKED table of GBNNS_FLAG_HALF_ROWS, which such a handle may have as well.)
-    const uint16_t* db_h_base = nullptr;
+    // The original-space table [n x d_pad]: rows of `rows` elements (row_kind.h: float32, uint8 -- gbnns_index_create_bytes --, or binary16 --
+    // gbnns_index_create_half_base), d_pad = row_pad(d, rows) elements a row (= the floats of a staged re-rank query), zero padded, 16-byte
+    // aligned; borrowed or base_own's.  One table, one kind: no float copy of a byte or half table exists.  (Not low_half: that is the WALKED
+    // table of GBNNS_FLAG_HALF_ROWS, which a handle of any kind may have as well.)
+    gbnns::RowKind rows = gbnns::RowKind::F32;
+    const void* base = nullptr;
+    template <typename T>
+    const T* base_as() const {  // the table for a launcher of the kind whose element is T
+        assert(sizeof(T) == gbnns::row_elem_bytes(rows));
+        return static_cast<const T*>(base);
+    }
+    bool is(gbnns::RowKind k) const { return rows == k; }
     const float* db_low = nullptr;  // [n x dl_pad]
-    DevBuf db_own, db_b_own, db_h_base_own, db_low_own, ell, net, aux_ell;
+    DevBuf base_own, db_low_own, ell, net, aux_ell;
     DevBuf net_mfma;                // the net repacked for the one-launch matrix-core projection (filled on the option's first use)
     // GBNNS_FLAG_HALF_ROWS (gbnns_index_enable_half_rows): R = float32(float16(db_low)) as binary16 rows [n x round_up(d_low, 8)], zero padded,
     // and as float32 rows in db_low's own layout [n x dl_pad]; db_low itself stays, for the searches without the flag
@@ -253,10 +260,11 @@ int build_ell(const uint64_t* off, const uint32_t* nbr, uint64_t n, std::vector<
 int run_project(gbnns_index* ix, Lane& L, const float* x, uint32_t xstride, uint32_t nx, float* out, hipStream_t s, bool in_flight = false,
                 bool mfma = false);
 int prof_flush(gbnns_index* ix);
-// the stand-alone re-rank over the handle's original-space table: the float kernels (rerank.hip), or on a byte handle the byte ones
-// (rerank_bytes.hip); r.db / r.dstride are the handle's, whatever the caller put there
-hipError_t rerank_launch(const gbnns_index* ix, const RerankParams& r, hipStream_t s);
-hipError_t rerank_topk_launch(const gbnns_index* ix, const RerankTopkParams& r, hipStream_t s);
+// the stand-alone re-rank over the handle's original-space table, by the kernels of its row kind (rerank.hip / rerank_bytes.hip / rerank_half.hip);
+// the table and its row stride are the handle's, whatever the caller put into r.db / r.dstride.  P: RerankParams (the best of every list) or
+// RerankTopkParams (its k best)
+template <class P>
+hipError_t rerank_launch(const gbnns_index* ix, const P& r, hipStream_t s);
 
 // lanes.cpp
 int enter_stream(gbnns_index* ix, hipStream_t s);

@@ -15,16 +15,27 @@ void set_walk_shape(WalkParams& w, const CallFacts& f) {
     w.aux_ell = f.aux_stride ? present : nullptr; w.aux_stride = f.aux_stride;
     w.half_rows = f.half_rows ? 1 : 0;
     w.tagged = f.tagged ? 1 : 0; w.bridged = f.bridged ? 1 : 0;
-    w.walk_bytes = f.walk_bytes ? 1 : 0;
-    w.walk_half = f.walk_half ? 1 : 0;
-    w.half_general = (f.walk_half && !f.knob.half_walk_fast) ? 1 : 0;
-    w.half_unkept = (f.walk_half && f.knob.half_walk_fast == 2) ? 1 : 0;
+    w.walk_bytes = f.walked == RowKind::U8 ? 1 : 0;
+    w.walk_half = f.walked == RowKind::F16 ? 1 : 0;
+    w.half_general = (w.walk_half && !f.knob.half_walk_fast) ? 1 : 0;
+    w.half_unkept = (w.walk_half && f.knob.half_walk_fast == 2) ? 1 : 0;
     // byte queries: the plan may name the integer twin of a byte-walk instance (walk_plan.cpp; knob "byte_query_int": for which beam classes)
-    w.q_b = (f.walk_bytes && f.byte_queries) ? reinterpret_cast<const uint8_t*>(present) : nullptr;
-    w.bq_classes = f.walk_bytes ? (uint32_t)f.knob.byte_query_int : 0u;
+    w.q_b = (w.walk_bytes && f.byte_queries) ? reinterpret_cast<const uint8_t*>(present) : nullptr;
+    w.bq_classes = w.walk_bytes ? (uint32_t)f.knob.byte_query_int : 0u;
     w.stamps_on = f.stamps_on ? 1 : 0;
     w.force_wide = (f.flags & GBNNS_FLAG_WIDE_INDEX) ? 1 : 0;
     w.generic_only = f.knob.hot ? 0 : 1;
+}
+
+void set_walked_table(WalkParams& w, RowKind walked, const void* table) {
+    w.db = walked == RowKind::F32 ? static_cast<const float*>(table) : nullptr;
+    if (walked == RowKind::U8) w.db_b = static_cast<const uint8_t*>(table);
+    if (walked == RowKind::F16) w.db_h = table;
+}
+
+void set_fused_rerank_table(WalkParams& w, RowKind rows, const void* table) {
+    w.rr_db = rows == RowKind::F32 ? static_cast<const float*>(table) : nullptr;
+    w.rr_db_b = rows == RowKind::U8 ? static_cast<const uint8_t*>(table) : nullptr;
 }
 
 // the decision fields, under the same names in WalkParams and CallPlan: out of the plan's scratch parameters, into a call's
@@ -44,7 +55,7 @@ size_t first_lds(const WalkParams& w, const WalkPlan& plan) { return plan.lds_fi
 // sizing statistics are kept per (ef, mode, aux, wide, byte instances: no retry pass behind them, half rows: another table, other walks; tagged: other graphs, shorter walks; bridged: two to three times the rows claimed; knob "hot" = 0: other kernels; a half-base handle: a class of its own, like the byte handle's; a half walk, GBNNS_FLAG_HALF_WALK: one more -- bit 23 --, and with the knob "half_walk_fast" = 0 another -- bit 22: other kernels; beams below 2^18)
 int stats_key(const CallFacts& f, const WalkParams& w) {
     const bool aux = f.aux_stride != 0;
-    return ((f.ef * 8 + f.mode * 2 + (aux ? 1 : 0)) * 2 + w.force_wide) | (w.half_rows ? 1 << 30 : 0) | (w.tagged ? 1 << 29 : 0) | (w.bridged ? 1 << 27 : 0) | (w.generic_only ? 1 << 28 : 0) | (w.bytes_dim ? 1 << 26 : 0) | (w.walk_bytes ? 1 << 25 : 0) | (f.half_base ? 1 << 24 : 0) | (w.walk_half ? 1 << 23 : 0) | (w.half_general ? 1 << 22 : 0);
+    return ((f.ef * 8 + f.mode * 2 + (aux ? 1 : 0)) * 2 + w.force_wide) | (w.half_rows ? 1 << 30 : 0) | (w.tagged ? 1 << 29 : 0) | (w.bridged ? 1 << 27 : 0) | (w.generic_only ? 1 << 28 : 0) | (w.bytes_dim ? 1 << 26 : 0) | (w.walk_bytes ? 1 << 25 : 0) | (f.rows == RowKind::F16 ? 1 << 24 : 0) | (w.walk_half ? 1 << 23 : 0) | (w.half_general ? 1 << 22 : 0);
 }
 
 // A small batch that runs ALONE (the reference's gist row: 1 000 queries per synchronous call, final_test.cpp:87) on the shapes that
@@ -121,6 +132,7 @@ int late_rows_rule(const CallFacts& f, const WalkParams& w, const WalkPlan& plan
 
 // retry pass: hand-overs of the first pass, one wavefront per CU with all the LDS
 void retry_rule(const CallFacts& f, const WalkParams& w, CallPlan& cp) {
+    const bool bytes = f.rows == RowKind::U8;
     WalkParams w2 = w;
     w2.vs_shr = 0;  // (the retry kernels keep the packed form)
     w2.coop = 0;    // (... and one wavefront per query)
@@ -129,7 +141,7 @@ void retry_rule(const CallFacts& f, const WalkParams& w, CallPlan& cp) {
     cp.retry_hash_limit = cp.retry_hash_cap - cp.retry_hash_cap / 16;
     if (cp.skip_retry)
         cp.retry_action = RetryAction::None;  // nothing to launch
-    else if (cp.retry_hash_cap > cp.sizing.cap && !w.tagged && !(cp.fuse && f.byte_handle) && !w.walk_bytes && !w.walk_half)  // (a tagged first pass has no retry pass: its hand-overs go straight to the general kernel; a byte instance's and a byte walk's to the general kernel's byte instances, a half walk's to its half-walk instance)
+    else if (cp.retry_hash_cap > cp.sizing.cap && !w.tagged && !(cp.fuse && bytes) && !w.walk_bytes && !w.walk_half)  // (a tagged first pass has no retry pass: its hand-overs go straight to the general kernel; a byte instance's and a byte walk's to the general kernel's byte instances, a half walk's to its half-walk instance)
         cp.retry_action = RetryAction::Launch;
     else
         cp.retry_action = RetryAction::Copy;  // nothing to gain: A -> B
@@ -144,7 +156,7 @@ CallPlan call_plan(const CallFacts& f, const SizingHistory& h) {
     set_walk_shape(w, f);
     // A byte handle (gbnns_index_create_bytes): the re-rank is fused only into the byte instances (walk_plan.cpp decides, from bytes_dim);
     // every other first pass runs as on a float handle with GBNNS_FLAG_NO_FUSED_RERANK, the stand-alone byte kernel behind it
-    const bool bytes = f.byte_handle;
+    const bool bytes = f.rows == RowKind::U8;
     if (bytes && !plain && !(f.flags & GBNNS_FLAG_NO_FUSED_RERANK) && rerank_plan(f.metric, f.d, true).fuses) w.bytes_dim = f.d;
     // (a byte walk, GBNNS_FLAG_BYTE_WALK: a bit of its own too -- other kernels, no retry pass, and never the float handle's or the byte re-rank's state)
     cp.skey = stats_key(f, w);
@@ -174,7 +186,7 @@ CallPlan call_plan(const CallFacts& f, const SizingHistory& h) {
     // (rerank_plan.h: the pair form; L2: d % 8 == 4 too -- glove's 300 -- its last 16-byte step is the even lane's alone)
     // A half-base handle (gbnns_index_create_half_base): rerank_half_plan never fuses -- every first pass runs as on a float handle with
     // GBNNS_FLAG_NO_FUSED_RERANK, the stand-alone half kernel behind it, and sets no LDS aside for a re-rank query
-    const bool want_fuse = f.half_base ? rerank_half_plan(f.metric, f.d).fuses
+    const bool want_fuse = f.rows == RowKind::F16 ? rerank_half_plan(f.metric, f.d).fuses
                                        : (bytes ? w.bytes_dim != 0u : (!plain && rerank_plan(f.metric, f.d, false).fuses && !(f.flags & GBNNS_FLAG_NO_FUSED_RERANK)));
     w.rr_reserve = (want_fuse && !bytes) ? (uint32_t)f.d_pad * 4u : 0u;  // (the bitmap pass has no byte instance)
     cp.bitmap_per_cu = bitmap_rule(f, w, plan, fps.form);

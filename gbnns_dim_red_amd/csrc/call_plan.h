@@ -5,6 +5,7 @@
 #pragma once
 
 #include "../../include/gbnns.h"
+#include "row_kind.h"
 #include "walk_plan.h"
 
 #include <map>
@@ -50,16 +51,18 @@ struct CallFacts {
     // the handle
     int metric;
     uint64_t n;
-    uint32_t d, d_pad;        // original space (d_pad: floats of a row; on a byte handle its bytes, on a half-base handle its halves)
+    uint32_t d, d_pad;        // original space (d_pad: the elements of a row, row_pad(d, rows))
     uint32_t ell_stride;
     uint32_t aux_stride;      // of the auxiliary graph a GBNNS_FLAG_AUX_GRAPH call walks; 0: none
-    bool byte_handle;         // gbnns_index_create_bytes
+    RowKind rows;             // the kind of the original-space rows (row_kind.h).  U8: the re-rank is fused only into the byte instances; F16: only a
+                              // GBNNS_FLAG_HALF_WALK call's walk kernels read the rows, the re-rank is never fused
     size_t cus;               // compute units of the device
     Knobs knob;
     // the walked space
     uint32_t dim, dstride;
     bool half_rows;           // GBNNS_FLAG_HALF_ROWS
-    bool walk_bytes;          // GBNNS_FLAG_BYTE_WALK: the walked rows are the handle's uint8 rows
+    RowKind walked;           // the kind of the WALKED rows: F32 but for a PLAIN call on a U8 / F16 handle (GBNNS_FLAG_BYTE_WALK / GBNNS_FLAG_HALF_WALK), which
+                              // walks the handle's own rows (F16 with knob.half_walk_fast = 0: the general instance takes the whole batch)
     bool byte_queries;        // gbnns_search_byte_queries
     // the call
     int mode, ef;
@@ -71,9 +74,6 @@ struct CallFacts {
     bool in_flight;           // on a lane's own stream: a batch of a deferred call
     bool sync_host;           // the call runs alone and is waited for
     bool stamps_on;           // diagnostic builds (GBNNS_STAMPS)
-    // the handle again (last: aggregate initialisers of the members above stay valid)
-    bool half_base = false;   // gbnns_index_create_half_base: binary16 original rows (d_pad: their halves) -- only a GBNNS_FLAG_HALF_WALK call's walk kernels read them, the re-rank is never fused
-    bool walk_half = false;   // GBNNS_FLAG_HALF_WALK: the walked rows are the handle's binary16 rows (knob.half_walk_fast = 0: the general instance takes the whole batch)
 };
 
 // sizing.cpp: the first pass's visited set for this batch -- sets w.vs_shr / hash_cap / hash_limit / spec_rows / spec_from
@@ -106,6 +106,10 @@ struct CallPlan {
 // The fields of a WalkParams that say what is walked and by which kind of call: everything plan_walk reads but the decisions above.  The tables
 // plan_walk only asks the presence of (aux_ell, q_b) get a placeholder that is not null: a caller that launches puts its pointers there.
 void set_walk_shape(WalkParams& w, const CallFacts& f);
+// RowKind into the kernels' parameter fields, all of it (with set_walk_shape's walk_bytes / walk_half above): the table a call walks into
+// db / db_b / db_h, the table its walk kernels re-rank from into rr_db / rr_db_b (F16: no walk kernel re-ranks)
+void set_walked_table(WalkParams& w, RowKind walked, const void* table);
+void set_fused_rerank_table(WalkParams& w, RowKind rows, const void* table);
 
 CallPlan call_plan(const CallFacts& f, const SizingHistory& h);
 

@@ -639,11 +639,11 @@ int knn_gather_call(gbnns_index* ix, const T* table, const T* queries, uint64_t 
 int knn_index_refuse(const char* fn, gbnns_index* ix, const float* queries, const uint8_t* queries_u8, const uint32_t* query_tags) {
     if ((queries != nullptr) == (queries_u8 != nullptr)) return fail(GBNNS_ERR_INVALID, "%s: exactly one of queries / queries_u8", fn);
     if (!ix) return fail(GBNNS_ERR_INVALID, "null argument");
-    if (ix->db_h_base)
+    if (ix->is(RowKind::F16))
         return fail(GBNNS_ERR_UNSUPPORTED, "%s on a half-base handle (gbnns_index_create_half_base): there is no exact scan over the resident binary16 rows; "
                     "widen the table and call gbnns_exact_knn", fn);
-    if (queries_u8 && !ix->db_b) return fail(GBNNS_ERR_INVALID, "%s: queries_u8 needs a byte handle (gbnns_index_create_bytes)", fn);
-    if (queries && ix->db_b)
+    if (queries_u8 && !ix->is(RowKind::U8)) return fail(GBNNS_ERR_INVALID, "%s: queries_u8 needs a byte handle (gbnns_index_create_bytes)", fn);
+    if (queries && ix->is(RowKind::U8))
         return fail(GBNNS_ERR_UNSUPPORTED, "%s: float queries on a byte handle: there is no mixed-pair scan (uint8 rows against "
                     "float queries); pass queries_u8, or widen the table and call gbnns_exact_knn", fn);
     if (query_tags && !ix->tags.p) return fail(GBNNS_ERR_INVALID, "%s with query_tags but without gbnns_index_set_tags", fn);
@@ -654,13 +654,13 @@ int knn_index_refuse(const char* fn, gbnns_index* ix, const float* queries, cons
 namespace gbnns_api {
 int knn_scan_resident(gbnns_index* ix, const float* queries, const uint8_t* queries_u8, uint64_t n_q, const uint32_t* query_tags, int k,
                       uint32_t* out_ids, float* out_dist, hipStream_t s) {
-    if (queries) return knn_call(knn_resident_call(ix, ix->db, queries, n_q, query_tags, k, -1, out_ids, out_dist, GBNNS_MEM_DEVICE, s));
-    return knn_call(knn_resident_call(ix, ix->db_b, queries_u8, n_q, query_tags, k, -1, out_ids, out_dist, GBNNS_MEM_DEVICE, s));
+    if (queries) return knn_call(knn_resident_call(ix, ix->base_as<float>(), queries, n_q, query_tags, k, -1, out_ids, out_dist, GBNNS_MEM_DEVICE, s));
+    return knn_call(knn_resident_call(ix, ix->base_as<uint8_t>(), queries_u8, n_q, query_tags, k, -1, out_ids, out_dist, GBNNS_MEM_DEVICE, s));
 }
 int knn_gather_resident(gbnns_index* ix, const float* queries, const uint8_t* queries_u8, uint64_t n_q, const uint32_t* query_tags, int k,
                         uint32_t* out_ids, float* out_dist, hipStream_t s) {
-    if (queries) return knn_gather_call(ix, ix->db, queries, n_q, query_tags, k, -1, out_ids, out_dist, GBNNS_MEM_DEVICE, s);
-    return knn_gather_call(ix, ix->db_b, queries_u8, n_q, query_tags, k, -1, out_ids, out_dist, GBNNS_MEM_DEVICE, s);
+    if (queries) return knn_gather_call(ix, ix->base_as<float>(), queries, n_q, query_tags, k, -1, out_ids, out_dist, GBNNS_MEM_DEVICE, s);
+    return knn_gather_call(ix, ix->base_as<uint8_t>(), queries_u8, n_q, query_tags, k, -1, out_ids, out_dist, GBNNS_MEM_DEVICE, s);
 }
 }  // namespace gbnns_api
 
@@ -695,8 +695,8 @@ int gbnns_exact_knn_bytes_tagged(int device, const uint8_t* base, uint64_t n, co
 int gbnns_index_exact_knn(gbnns_index* ix, const float* queries, const uint8_t* queries_u8, uint64_t n_q, const uint32_t* query_tags, int k,
                           int64_t self_offset, uint32_t* out_ids, float* out_dist, int mem_kind, void* stream) {
     if (int rc = knn_index_refuse("gbnns_index_exact_knn", ix, queries, queries_u8, query_tags)) return rc;
-    if (queries) return knn_index_call(ix, ix->db, queries, n_q, query_tags, k, self_offset, out_ids, out_dist, mem_kind, stream);
-    return knn_index_call(ix, ix->db_b, queries_u8, n_q, query_tags, k, self_offset, out_ids, out_dist, mem_kind, stream);
+    if (queries) return knn_index_call(ix, ix->base_as<float>(), queries, n_q, query_tags, k, self_offset, out_ids, out_dist, mem_kind, stream);
+    return knn_index_call(ix, ix->base_as<uint8_t>(), queries_u8, n_q, query_tags, k, self_offset, out_ids, out_dist, mem_kind, stream);
 }
 
 // The gathered form: the same bytes, from distances to the allowed rows only (knn_gather.hip).  This call's own refusals need no handle and
@@ -712,8 +712,8 @@ int gbnns_index_exact_knn_gather(gbnns_index* ix, const float* queries, const ui
     hipStream_t s = static_cast<hipStream_t>(stream);
     int rc;
     if ((rc = enter_stream(ix, s))) return rc;
-    rc = queries ? knn_gather_call(ix, ix->db, queries, n_q, query_tags, k, self_offset, out_ids, out_dist, mem_kind, s)
-                 : knn_gather_call(ix, ix->db_b, queries_u8, n_q, query_tags, k, self_offset, out_ids, out_dist, mem_kind, s);
+    rc = queries ? knn_gather_call(ix, ix->base_as<float>(), queries, n_q, query_tags, k, self_offset, out_ids, out_dist, mem_kind, s)
+                 : knn_gather_call(ix, ix->base_as<uint8_t>(), queries_u8, n_q, query_tags, k, self_offset, out_ids, out_dist, mem_kind, s);
     if (rc == GBNNS_OK && n_q) ix->in_flight = false;  // (the call returned behind a synchronisation of its stream)
     return rc;
 }

@@ -10,6 +10,7 @@
 #include "api_internal.h"
 
 #include <cmath>
+#include <type_traits>
 
 using namespace gbnns;
 using namespace gbnns_api;
@@ -397,27 +398,24 @@ int gbnns_device_count(void) {
 
 void gbnns_free(void* p) { std::free(p); }
 
-// gbnns_index_create (db_bytes == nullptr, !bytes), gbnns_index_create_bytes and gbnns_index_create_half_base (db_half: the table, !bytes)
-static int index_create(const gbnns_index_desc* desc, const uint8_t* db_bytes, bool bytes, gbnns_index** out, const uint16_t* db_half = nullptr,
-                        bool half_base = false) {
+// gbnns_index_create (F32: the table is desc->db, `table` is ignored), gbnns_index_create_bytes and gbnns_index_create_half_base (`table`)
+static int index_create(const gbnns_index_desc* desc, RowKind rows, const void* table, gbnns_index** out) {
     if (!desc || !out) return fail(GBNNS_ERR_INVALID, "null argument");
     *out = nullptr;
     if (desc->struct_size != sizeof(gbnns_index_desc))
         return fail(GBNNS_ERR_INVALID, "gbnns_index_desc.struct_size mismatch (%u != %zu)",
                     desc->struct_size, sizeof(gbnns_index_desc));
     if (desc->n == 0 || desc->n >= (1ull << 31)) return fail(GBNNS_ERR_INVALID, "n must be in [1, 2^31)");
-    if (desc->d == 0 || (!bytes && !half_base && !desc->db)) return fail(GBNNS_ERR_INVALID, "db / d missing");
-    if (half_base) {
-        if (desc->db) return fail(GBNNS_ERR_INVALID, "gbnns_index_create_half_base: desc->db must be NULL (the table is db_half)");
-        if (!db_half) return fail(GBNNS_ERR_INVALID, "gbnns_index_create_half_base: db_half missing");
+    const bool narrow = rows != RowKind::F32;  // rows of 1- or 2-byte elements, handed over beside the descriptor
+    if (desc->d == 0 || (!narrow && !desc->db)) return fail(GBNNS_ERR_INVALID, "db / d missing");
+    if (narrow) {
+        const char *fn = row_create_fn(rows), *arg = row_table_arg(rows);
+        if (desc->db) return fail(GBNNS_ERR_INVALID, "%s: desc->db must be NULL (the table is %s)", fn, arg);
+        if (!table) return fail(GBNNS_ERR_INVALID, "%s: %s missing", fn, arg);
         if (desc->d_low == 0 || !desc->db_low)
-            return fail(GBNNS_ERR_INVALID, "gbnns_index_create_half_base: d_low and db_low are required (a half-base handle serves NET / LOWQ searches)");
-    }
-    if (bytes) {
-        if (desc->db) return fail(GBNNS_ERR_INVALID, "gbnns_index_create_bytes: desc->db must be NULL (the table is db_bytes)");
-        if (!db_bytes) return fail(GBNNS_ERR_INVALID, "gbnns_index_create_bytes: db_bytes missing");
-        if (desc->d_low == 0 || !desc->db_low)
-            return fail(GBNNS_ERR_INVALID, "gbnns_index_create_bytes: d_low and db_low are required (a byte handle serves NET / LOWQ searches)");
+            return fail(GBNNS_ERR_INVALID, "%s: d_low and db_low are required (a %s serves NET / LOWQ searches)", fn, row_handle_noun(rows));
+    } else {
+        table = desc->db;
     }
     if (!desc->graph_offsets || !desc->graph_nbrs) return fail(GBNNS_ERR_INVALID, "graph missing");
     if (desc->metric != GBNNS_METRIC_L2 && desc->metric != GBNNS_METRIC_NEG_DOT)
@@ -447,7 +445,8 @@ static int index_create(const gbnns_index_desc* desc, const uint8_t* db_bytes, b
     ix->d_hidden = desc->d_hidden;
     (void)hipDeviceGetAttribute(&ix->cus, hipDeviceAttributeMultiprocessorCount, ix->device);
     ix->knob = knob_defaults();
-    ix->d_pad = round_up(desc->d, bytes ? 16 : (half_base ? 8 : 4));  // (a byte handle: bytes of a row = floats of a staged re-rank query; a half-base handle: halves of a row)
+    ix->rows = rows;
+    ix->d_pad = row_pad(desc->d, rows);  // (elements of a row = floats of a staged re-rank query)
     ix->dl_pad = round_up(desc->d_low, 4);
     int rc = GBNNS_OK;
 
@@ -462,8 +461,8 @@ static int index_create(const gbnns_index_desc* desc, const uint8_t* db_bytes, b
     };
     // rows of 1- or 2-byte elements: [n x d] -> [n x d_pad], zero padded, in an exactly sized buffer; a DEVICE table already in that layout
     // (d_pad == d, a 16-byte aligned address) is borrowed
-    auto take_packed = [&](const void* table, size_t elem, DevBuf& own, const void*& dst, const char* what) -> int {
-        const size_t d = ix->d * elem, pad = ix->d_pad * elem, n = ix->n;  // (bytes of a row)
+    auto take_packed = [&](DevBuf& own, const void*& dst) -> int {
+        const size_t elem = row_elem_bytes(rows), d = ix->d * elem, pad = ix->d_pad * elem, n = ix->n;  // (bytes of a row)
         const bool device = desc->mem_kind == GBNNS_MEM_DEVICE;
         if (device && pad == d && (reinterpret_cast<uintptr_t>(table) & 15u) == 0) {
             dst = table;
@@ -489,23 +488,16 @@ static int index_create(const gbnns_index_desc* desc, const uint8_t* db_bytes, b
         if (!r && e == hipSuccess) e = hipMemcpy2D(own.p, pad, src, d, d, n, hipMemcpyDeviceToDevice);
         if (!r && e == hipSuccess) e = hipDeviceSynchronize();
         packed.release();
-        if (!r && e != hipSuccess) r = fail(GBNNS_ERR_HIP, "%s table upload: %s", what, hipGetErrorString(e));
+        if (!r && e != hipSuccess) r = fail(GBNNS_ERR_HIP, "%s table upload: %s", rows == RowKind::U8 ? "byte" : "half", hipGetErrorString(e));
         return r;
     };
-    auto take_bytes = [&]() -> int {
-        const void* dst = nullptr;
-        const int r = take_packed(db_bytes, 1, ix->db_b_own, dst, "byte");
-        ix->db_b = static_cast<const uint8_t*>(dst);
-        return r;
-    };
-    // binary16 rows: d_pad = round_up(d, 8) halves
-    auto take_half = [&]() -> int {
-        const void* dst = nullptr;
-        const int r = take_packed(db_half, 2, ix->db_h_base_own, dst, "half");
-        ix->db_h_base = static_cast<const uint16_t*>(dst);
-        return r;
-    };
-    rc = bytes ? take_bytes() : (half_base ? take_half() : take(desc->db, ix->d, ix->d_pad, ix->db_own, ix->db));
+    if (narrow) {
+        rc = take_packed(ix->base_own, ix->base);
+    } else {
+        const float* dst = nullptr;
+        rc = take(static_cast<const float*>(table), ix->d, ix->d_pad, ix->base_own, dst);
+        ix->base = dst;
+    }
     if (!rc && desc->db_low) rc = take(desc->db_low, ix->d_low, ix->dl_pad, ix->db_low_own, ix->db_low);
 
     if (!rc) {
@@ -591,19 +583,19 @@ static int index_create(const gbnns_index_desc* desc, const uint8_t* db_bytes, b
     return GBNNS_OK;
 }
 
-int gbnns_index_create(const gbnns_index_desc* desc, gbnns_index** out) { return index_create(desc, nullptr, false, out); }
+int gbnns_index_create(const gbnns_index_desc* desc, gbnns_index** out) { return index_create(desc, RowKind::F32, nullptr, out); }
 
 int gbnns_index_create_bytes(const gbnns_index_desc* desc, const uint8_t* db_bytes, gbnns_index** out) {
-    return index_create(desc, db_bytes, true, out);
+    return index_create(desc, RowKind::U8, db_bytes, out);
 }
 
-int gbnns_index_is_bytes(const gbnns_index* ix) { return ix && ix->db_b ? 1 : 0; }
+int gbnns_index_is_bytes(const gbnns_index* ix) { return ix && ix->is(RowKind::U8) ? 1 : 0; }
 
 int gbnns_index_create_half_base(const gbnns_index_desc* desc, const uint16_t* db_half, gbnns_index** out) {
-    return index_create(desc, nullptr, false, out, db_half, true);
+    return index_create(desc, RowKind::F16, db_half, out);
 }
 
-int gbnns_index_is_half_base(const gbnns_index* ix) { return ix && ix->db_h_base ? 1 : 0; }
+int gbnns_index_is_half_base(const gbnns_index* ix) { return ix && ix->is(RowKind::F16) ? 1 : 0; }
 
 int gbnns_index_set_aux_graph(gbnns_index* ix, const uint64_t* offsets, const uint32_t* nbrs) {
     if (!ix) return fail(GBNNS_ERR_INVALID, "null argument");
@@ -646,7 +638,7 @@ int gbnns_index_destroy(gbnns_index* ix) {
         if (L.stream) (void)hipStreamDestroy(L.stream);
         for (int i = 0; DevBuf* b = L.bufs(i); ++i) b->release();
     }
-    DevBuf* bufs[] = {&ix->db_own, &ix->db_b_own, &ix->db_h_base_own, &ix->db_low_own, &ix->ell, &ix->aux_ell, &ix->net, &ix->net_mfma, &ix->low_half, &ix->low_r, &ix->tags};
+    DevBuf* bufs[] = {&ix->base_own, &ix->db_low_own, &ix->ell, &ix->aux_ell, &ix->net, &ix->net_mfma, &ix->low_half, &ix->low_r, &ix->tags};
     for (DevBuf* b : bufs) b->release();
     delete ix;
     return GBNNS_OK;
@@ -826,37 +818,36 @@ int run_project(gbnns_index* ix, Lane& L, const float* x, uint32_t xstride, uint
     return GBNNS_OK;
 }
 
-hipError_t rerank_topk_launch(const gbnns_index* ix, const RerankTopkParams& r, hipStream_t s) {
-    if (ix->db_b) {
-        RerankBytesParams b{};
-        static_cast<RerankTopkParams&>(b) = r;
-        b.db = nullptr; b.db_b = ix->db_b; b.dstride = ix->d_pad;
-        return launch_rerank_topk_bytes(b, ix->metric, s);
+// One dispatch for both stand-alone re-ranks: the kind's parameter struct, filled from the handle, into the kind's launcher.
+template <class P>
+hipError_t rerank_launch(const gbnns_index* ix, const P& r, hipStream_t s) {
+    constexpr bool topk = std::is_same<P, RerankTopkParams>::value;
+    const int metric = ix->metric;
+    auto of_kind = [&](auto k) {  // (k: an empty parameter struct of the kind)
+        static_cast<P&>(k) = r;
+        k.db = nullptr; k.dstride = ix->d_pad;
+        return k;
+    };
+    switch (ix->rows) {
+        case RowKind::U8: {
+            RerankBytesParams b = of_kind(RerankBytesParams{});
+            b.db_b = ix->base_as<uint8_t>();
+            return topk ? launch_rerank_topk_bytes(b, metric, s) : launch_rerank_bytes(b, metric, s);
+        }
+        case RowKind::F16: {
+            RerankHalfParams h = of_kind(RerankHalfParams{});
+            h.db_h = ix->base_as<uint16_t>();
+            return topk ? launch_rerank_topk_half(h, metric, s) : launch_rerank_half(h, metric, s);
+        }
+        case RowKind::F32: break;
     }
-    if (ix->db_h_base) {
-        RerankHalfParams h{};
-        static_cast<RerankTopkParams&>(h) = r;
-        h.db = nullptr; h.db_h = ix->db_h_base; h.dstride = ix->d_pad;
-        return launch_rerank_topk_half(h, ix->metric, s);
-    }
-    return launch_rerank_topk(r, ix->metric, s);
+    P f = r;
+    f.db = ix->base_as<float>(); f.dstride = ix->d_pad;
+    if constexpr (topk) return launch_rerank_topk(f, metric, s);
+    else return launch_rerank(f, metric, s);
 }
-
-hipError_t rerank_launch(const gbnns_index* ix, const RerankParams& r, hipStream_t s) {
-    if (ix->db_b) {
-        RerankBytesParams b{};
-        static_cast<RerankParams&>(b) = r;
-        b.db = nullptr; b.db_b = ix->db_b; b.dstride = ix->d_pad;
-        return launch_rerank_bytes(b, ix->metric, s);
-    }
-    if (ix->db_h_base) {
-        RerankHalfParams h{};
-        static_cast<RerankParams&>(h) = r;
-        h.db = nullptr; h.db_h = ix->db_h_base; h.dstride = ix->d_pad;
-        return launch_rerank_half(h, ix->metric, s);
-    }
-    return launch_rerank(r, ix->metric, s);
-}
+template hipError_t rerank_launch<RerankParams>(const gbnns_index*, const RerankParams&, hipStream_t);
+template hipError_t rerank_launch<RerankTopkParams>(const gbnns_index*, const RerankTopkParams&, hipStream_t);
 
 int prof_flush(gbnns_index* ix) {
     for (auto& pc : ix->pending) {
@@ -1036,7 +1027,7 @@ int gbnns_debug_net_image(const float* w, uint32_t wstride, uint32_t din, uint32
 static int debug_plan(const char* fn, CallFacts f, WalkParams w, int force_wide, int coop, int pass, uint64_t general_lds, char* name, uint32_t name_bytes,
                       uint64_t* lds_bytes, int* fused) {
     if (!name || name_bytes == 0 || !(lds_bytes || fused)) return fail(GBNNS_ERR_INVALID, "%s: null output", fn);
-    if ((f.metric != GBNNS_METRIC_L2 && f.metric != GBNNS_METRIC_NEG_DOT) || f.dim == 0 || f.dstride != round_up(f.dim, f.walk_bytes ? 16 : (f.walk_half ? 8 : 4)) || f.n == 0 ||
+    if ((f.metric != GBNNS_METRIC_L2 && f.metric != GBNNS_METRIC_NEG_DOT) || f.dim == 0 || f.dstride != row_pad(f.dim, f.walked) || f.n == 0 ||
         f.n > 0xFFFFFFFFull || f.ell_stride == 0 || f.ell_stride % 16 || f.aux_stride % 16 || f.ef < 1 || f.n_entries > 4096 || pass < 0 || pass > 2)
         return fail(GBNNS_ERR_INVALID, "%s: not the shape of an index or a search", fn);
     f.flags = force_wide ? GBNNS_FLAG_WIDE_INDEX : 0u;
@@ -1108,8 +1099,8 @@ int gbnns_debug_half_base_plan(int metric, uint32_t d, char* name, uint32_t name
 static int debug_byte_walk_plan(const char* fn, bool byte_queries, int metric, uint32_t dim, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef,
                                 uint32_t n_entries, int force_wide, int tagged, char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
     if (!lds_bytes) return fail(GBNNS_ERR_INVALID, "%s: null output", fn);
-    CallFacts f = debug_facts(metric, dim, round_up(dim, 16), n, ell_stride, aux_stride, ef, n_entries);
-    f.tagged = tagged != 0; f.walk_bytes = true;
+    CallFacts f = debug_facts(metric, dim, row_pad(dim, RowKind::U8), n, ell_stride, aux_stride, ef, n_entries);
+    f.tagged = tagged != 0; f.rows = f.walked = RowKind::U8;
     f.byte_queries = byte_queries; f.knob.byte_query_int = 7;  // (... and whether the call brought byte queries; every beam class: knob "byte_query_int" = 7)
     return debug_plan(fn, f, WalkParams{}, force_wide, 0, 0, (uint64_t)f.dstride * 4u, name, name_bytes, lds_bytes, nullptr);
 }
@@ -1123,8 +1114,8 @@ int gbnns_debug_byte_walk_plan(int metric, uint32_t dim, uint64_t n, uint32_t el
 int gbnns_debug_half_walk_plan(int metric, uint32_t dim, uint64_t n, uint32_t ell_stride, uint32_t aux_stride, int ef, uint32_t n_entries, int force_wide,
                                int tagged, char* name, uint32_t name_bytes, uint64_t* lds_bytes) {
     if (!lds_bytes) return fail(GBNNS_ERR_INVALID, "gbnns_debug_half_walk_plan: null output");
-    CallFacts f = debug_facts(metric, dim, round_up(dim, 8), n, ell_stride, aux_stride, ef, n_entries);
-    f.tagged = tagged != 0; f.walk_half = true; f.half_base = true; f.knob.half_walk_fast = 2;
+    CallFacts f = debug_facts(metric, dim, row_pad(dim, RowKind::F16), n, ell_stride, aux_stride, ef, n_entries);
+    f.tagged = tagged != 0; f.rows = f.walked = RowKind::F16; f.knob.half_walk_fast = 2;
     return debug_plan("gbnns_debug_half_walk_plan", f, WalkParams{}, force_wide, 0, 0, (uint64_t)f.dstride * 4u, name, name_bytes, lds_bytes, nullptr);
 }
 
@@ -1416,7 +1407,7 @@ int gbnns_rerank(gbnns_index* ix, const float* queries, uint64_t n_q, const uint
     if ((rc = enter_stream(ix, s))) return rc;
     Lane& L = ix->lanes[0];
     RerankParams r{};
-    r.db = ix->db; r.dstride = ix->d_pad; r.dim = ix->d; r.qstride = ix->d; r.cand_stride = cand_stride;
+    r.dstride = ix->d_pad; r.dim = ix->d; r.qstride = ix->d; r.cand_stride = cand_stride;  // (r.db: rerank_launch, by the handle's row kind)
     r.nq = nq; r.n = (uint32_t)ix->n;
     if ((rc = L.cnt.ensure((size_t)nq * 4))) return rc;
     int32_t* cnt_dev = L.cnt.as<int32_t>();
@@ -1480,7 +1471,7 @@ int gbnns_rerank_topk(gbnns_index* ix, const float* queries, uint64_t n_q, const
     if ((rc = enter_stream(ix, s))) return rc;
     Lane& L = ix->lanes[0];
     RerankTopkParams r{};
-    r.db = ix->db; r.dstride = ix->d_pad; r.dim = ix->d; r.qstride = ix->d; r.cand_stride = cand_stride;
+    r.dstride = ix->d_pad; r.dim = ix->d; r.qstride = ix->d; r.cand_stride = cand_stride;  // (r.db: rerank_launch, by the handle's row kind)
     r.nq = nq; r.n = (uint32_t)ix->n; r.k = (uint32_t)k;
     if ((rc = L.cnt.ensure((size_t)nq * 4))) return rc;
     int32_t* cnt_dev = L.cnt.as<int32_t>();
@@ -1501,7 +1492,7 @@ int gbnns_rerank_topk(gbnns_index* ix, const float* queries, uint64_t n_q, const
     }
     if (!count) HIP_TRY(launch_fill_u32(reinterpret_cast<uint32_t*>(cnt_dev), cand_stride, nq, s));
     r.count = cnt_dev;
-    HIP_TRY(rerank_topk_launch(ix, r, s));
+    HIP_TRY(rerank_launch(ix, r, s));
     if (host) {
         if ((rc = host_copy_out(L, out_ids, r.out, bk, bk, 1, s))) return rc;
         if (out_dist && (rc = host_copy_out(L, out_dist, r.out_dist, bk, bk, 1, s))) return rc;

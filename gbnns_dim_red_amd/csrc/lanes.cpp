@@ -92,17 +92,17 @@ int search_check(gbnns_index* ix, const gbnns_search_args* a, const TopkOut* top
     if (a->mode != GBNNS_MODE_PLAIN && !ix->db_low) return fail(GBNNS_ERR_INVALID, "mode needs db_low");
     if (a->flags & GBNNS_FLAG_HALF_WALK) {
         if (a->flags & GBNNS_FLAG_BYTE_WALK) return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_HALF_WALK together with GBNNS_FLAG_BYTE_WALK: a handle has one kind of rows");
-        if (!ix->db_h_base) return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_HALF_WALK needs a half-base handle (gbnns_index_create_half_base)");
+        if (!ix->is(RowKind::F16)) return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_HALF_WALK needs a half-base handle (gbnns_index_create_half_base)");
         if (a->mode != GBNNS_MODE_PLAIN) return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_HALF_WALK: PLAIN only (NET / LOWQ walk db_low, which is float32)");
     }
-    if (a->mode == GBNNS_MODE_PLAIN && ix->db_b && !(a->flags & GBNNS_FLAG_BYTE_WALK))
+    if (a->mode == GBNNS_MODE_PLAIN && ix->is(RowKind::U8) && !(a->flags & GBNNS_FLAG_BYTE_WALK))
         return fail(GBNNS_ERR_UNSUPPORTED, "GBNNS_MODE_PLAIN on a byte handle (gbnns_index_create_bytes) walks the uint8 rows: served with GBNNS_FLAG_BYTE_WALK only");
     if (a->flags & GBNNS_FLAG_BYTE_WALK) {
-        if (ix->db_h_base) return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_BYTE_WALK on a half-base handle (gbnns_index_create_half_base): it needs a byte handle (gbnns_index_create_bytes)");
-        if (!ix->db_b) return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_BYTE_WALK needs a byte handle (gbnns_index_create_bytes)");
+        if (ix->is(RowKind::F16)) return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_BYTE_WALK on a half-base handle (gbnns_index_create_half_base): it needs a byte handle (gbnns_index_create_bytes)");
+        if (!ix->is(RowKind::U8)) return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_BYTE_WALK needs a byte handle (gbnns_index_create_bytes)");
         if (a->mode != GBNNS_MODE_PLAIN) return fail(GBNNS_ERR_INVALID, "GBNNS_FLAG_BYTE_WALK: PLAIN only (NET / LOWQ walk db_low, which is float32)");
     }
-    if (a->mode == GBNNS_MODE_PLAIN && ix->db_h_base && !(a->flags & GBNNS_FLAG_HALF_WALK))
+    if (a->mode == GBNNS_MODE_PLAIN && ix->is(RowKind::F16) && !(a->flags & GBNNS_FLAG_HALF_WALK))
         return fail(GBNNS_ERR_UNSUPPORTED, "GBNNS_MODE_PLAIN on a half-base handle (gbnns_index_create_half_base): there is no float table to walk; the half-row PLAIN walk is served with GBNNS_FLAG_HALF_WALK only");
     if (a->mode == GBNNS_MODE_LOWQ && !a->queries_low) return fail(GBNNS_ERR_INVALID, "queries_low missing");
     if ((a->flags & GBNNS_FLAG_LLF) && !(a->flags & GBNNS_FLAG_AUX_GRAPH))
@@ -337,8 +337,8 @@ int gbnns_search_byte_queries(gbnns_index* ix, const gbnns_search_args* a, const
     const bool sized = a->struct_size == sizeof(gbnns_search_args);  // (a mismatch: search_call's refusal)
     if (sized && a->queries) return fail(GBNNS_ERR_INVALID, "gbnns_search_byte_queries: args->queries must be NULL (the queries are queries_u8)");
     if (!ix) return fail(GBNNS_ERR_INVALID, "null argument");
-    if (ix->db_h_base) return fail(GBNNS_ERR_INVALID, "gbnns_search_byte_queries on a half-base handle (gbnns_index_create_half_base): it needs a byte handle (gbnns_index_create_bytes)");
-    if (!ix->db_b) return fail(GBNNS_ERR_INVALID, "gbnns_search_byte_queries needs a byte handle (gbnns_index_create_bytes)");
+    if (ix->is(RowKind::F16)) return fail(GBNNS_ERR_INVALID, "gbnns_search_byte_queries on a half-base handle (gbnns_index_create_half_base): it needs a byte handle (gbnns_index_create_bytes)");
+    if (!ix->is(RowKind::U8)) return fail(GBNNS_ERR_INVALID, "gbnns_search_byte_queries needs a byte handle (gbnns_index_create_bytes)");
     if (sized && !queries_u8 && a->n_q) return fail(GBNNS_ERR_INVALID, "gbnns_search_byte_queries: queries_u8 missing");
     // the corresponding float call: gbnns_search_tagged with query_tags, else gbnns_search_topk with k-answer rows, else gbnns_search_ex
     const TagIn g{query_tags, (a->flags & GBNNS_FLAG_TAG_BRIDGE) != 0};
@@ -404,9 +404,9 @@ int gbnns_search_tagged_auto(gbnns_index* ix, const gbnns_search_args* a, const 
         return fail(GBNNS_ERR_INVALID, "gbnns_search_tagged_auto: NET / LOWQ only (a PLAIN walk's out_cand / out_cand_dist are the answer in the walked space)");
     if (a->flags & GBNNS_FLAG_DEFER_JOIN)
         return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_search_tagged_auto: GBNNS_FLAG_DEFER_JOIN is not served (the call reads the census on the host)");
-    if (ix->db_h_base)
+    if (ix->is(RowKind::F16))
         return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_search_tagged_auto on a half-base handle (gbnns_index_create_half_base): its scan route reads the resident table, and there is no exact scan over binary16 rows");
-    if (ix->db_b) {
+    if (ix->is(RowKind::U8)) {
         if (a->queries && queries_u8) return fail(GBNNS_ERR_INVALID, "gbnns_search_tagged_auto: args->queries must be NULL beside queries_u8");
         if (a->queries)
             return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_search_tagged_auto: float queries on a byte handle: there is no mixed-pair scan (uint8 rows against "

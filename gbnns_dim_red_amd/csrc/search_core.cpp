@@ -147,11 +147,12 @@ CallFacts Call::call_facts() const {
     CallFacts f{};
     f.metric = ix->metric; f.n = ix->n; f.d = ix->d; f.d_pad = ix->d_pad; f.ell_stride = ix->ell_stride;
     f.aux_stride = (a->flags & GBNNS_FLAG_AUX_GRAPH) ? ix->aux_stride : 0u;
-    f.byte_handle = ix->db_b != nullptr; f.half_base = ix->db_h_base != nullptr; f.cus = ix->cu_count(); f.knob = ix->knob;
+    f.rows = ix->rows; f.cus = ix->cu_count(); f.knob = ix->knob;
     f.dim = plain ? ix->d : ix->d_low; f.dstride = plain ? ix->d_pad : ix->dl_pad;
     f.half_rows = !plain && (a->flags & GBNNS_FLAG_HALF_ROWS);
-    f.walk_bytes = plain && ix->db_b;  // GBNNS_FLAG_BYTE_WALK (checked by search_call): the walked rows are the handle's uint8 rows, d_pad bytes each; no float table exists
-    f.walk_half = plain && ix->db_h_base;  // GBNNS_FLAG_HALF_WALK (checked by search_call): the walked rows are the handle's binary16 rows, d_pad halves each; no float table exists
+    // a PLAIN call walks the handle's own rows, d_pad elements each, whatever their kind (GBNNS_FLAG_BYTE_WALK / GBNNS_FLAG_HALF_WALK: checked by
+    // search_call; no float copy of such a table exists); NET / LOWQ walk db_low, which is float32
+    f.walked = plain ? ix->rows : RowKind::F32;
     f.byte_queries = q_u8 != nullptr;
     f.mode = a->mode; f.ef = ef; f.n_entries = n_ent; f.flags = a->flags; f.hash_capacity = a->hash_capacity; f.nq = nq;
     f.tagged = tag != nullptr; f.bridged = tag && tag->bridge;
@@ -169,9 +170,8 @@ int Call::project() {
     set_walk_shape(w, facts);
     if (q_u8) HIP_TRY(launch_widen_u8(qb_dev, L.q_in.as<float>(), (size_t)nq * ix->d, s));
     if (plain) {
-        w.q = q_dev; w.qstride = ix->d; w.db = ix->db;
-        if (ix->db_b) { w.db = nullptr; w.db_b = ix->db_b; }
-        if (ix->db_h_base) { w.db = nullptr; w.db_h = ix->db_h_base; }
+        w.q = q_dev; w.qstride = ix->d;
+        set_walked_table(w, facts.walked, ix->base);
         w.q_b = w.walk_bytes ? qb_dev : nullptr;
     } else {
         if ((rc = L.q_low.ensure((size_t)nq * ix->dl_pad * 4))) return rc;
@@ -300,7 +300,8 @@ int Call::walk_params() {
     w.stamps = reinterpret_cast<unsigned long long*>(ctrl_base + 8);  // words 8..71, diagnostic builds
     if (plan.fuse) {
         // (a byte instance: rr_db_b, rows of d_pad bytes; rr_db stays nullptr)
-        w.rr_q = q_dev; w.rr_qstride = ix->d; w.rr_db = ix->db; w.rr_db_b = ix->db_b; w.rr_dstride = ix->d_pad; w.rr_dim = ix->d;
+        set_fused_rerank_table(w, ix->rows, ix->base);
+        w.rr_q = q_dev; w.rr_qstride = ix->d; w.rr_dstride = ix->d_pad; w.rr_dim = ix->d;
         w.rr_n = (uint32_t)ix->n; w.rr_out = out_dev; w.rr_metric = ix->metric;
     }
     if (plan.skip_retry) {  // the first pass appends what it cannot finish to list B directly
@@ -405,19 +406,19 @@ int Call::general_and_stats() {
 int Call::rerank() {
     if (!plain && !plan.fuse) {
         RerankParams r{};
-        r.q = q_dev; r.qstride = ix->d; r.db = ix->db; r.dstride = ix->d_pad; r.dim = ix->d;
+        r.q = q_dev; r.qstride = ix->d; r.dstride = ix->d_pad; r.dim = ix->d;
         r.cand = w.cand; r.cand_stride = cstride; r.count = w.count; r.nq = nq; r.n = (uint32_t)ix->n; r.out = out_dev;
         HIP_TRY(rerank_launch(ix, r, s));
     }
     // ... and the k best of the same candidates (gbnns_search_topk): every first pass, the retry pass and the general kernel leave the
     // candidate row and its count behind, whether they re-ranked their query themselves or not
     if (topk) {
-        tk.q = q_dev; tk.qstride = ix->d; tk.db = ix->db; tk.dstride = ix->d_pad; tk.dim = ix->d;
+        tk.q = q_dev; tk.qstride = ix->d; tk.dstride = ix->d_pad; tk.dim = ix->d;
         tk.cand = w.cand; tk.cand_stride = cstride; tk.count = w.count; tk.nq = nq; tk.n = (uint32_t)ix->n;
         tk.k = (uint32_t)topk->k;
         tk.out = host ? L.top_ids.as<uint32_t>() : topk->ids;
         tk.out_dist = topk->dist ? (host ? L.top_dist.as<float>() : topk->dist) : nullptr;
-        HIP_TRY(rerank_topk_launch(ix, tk, s));
+        HIP_TRY(rerank_launch(ix, tk, s));
     }
     if (prof) {
         HIP_TRY(hipEventRecord(pc.ev[4], s));

@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "launch_util.h"
+#include "row_kind.h"
 #include "walk_lists.h"
 
 namespace gbnns {
@@ -23,18 +24,26 @@ namespace {
 // (main graph through the main graph, auxiliary through the auxiliary) take its place, one level deep.  The ids of that row G'' are compacted
 // in order into `bst` (64 words of LDS) and run through the expansion a chunk at a time; of equal ids inside a chunk only the first stays
 // (two lanes that claim one id at once would both be told it is new, or the later one alone).
-// BYTES (walk_general_bytes_kernel: the hand-overs of a byte handle's fused first pass, gbnns_index_create_bytes): the same walk, the fused
+// RR == U8 (walk_general_bytes_kernel: the hand-overs of a byte handle's fused first pass, gbnns_index_create_bytes): the same walk, the fused
 // re-rank over uint8 rows (WalkParams::rr_db_b).
-// BWALK (GBNNS_FLAG_BYTE_WALK: walk_general_bwalk_kernel / _tag_ / _bridge_): the WALKED rows are uint8 (WalkParams::db_b, p.dstride bytes a
+// WALKED == U8 (GBNNS_FLAG_BYTE_WALK: walk_general_bwalk_kernel<METRIC, TAG>): the WALKED rows are uint8 (WalkParams::db_b, p.dstride bytes a
 // row = the floats of the staged query) -- the three distances read the row through ByteRow4, a lane per row: l2_ordered / negdot_ordered on
 // float32(row), any dimension, both metrics.  Exact, not tuned.  It takes every flagged call outside the domain of walk_bytes.hip's instances
 // and every query those hand over.
-// HWALK (GBNNS_FLAG_HALF_WALK: walk_general_hwalk_kernel<METRIC, TAG>): the WALKED rows are a half-base handle's binary16 rows (WalkParams::db_h,
+// WALKED == F16 (GBNNS_FLAG_HALF_WALK: walk_general_hwalk_kernel<METRIC, TAG>): the WALKED rows are a half-base handle's binary16 rows (WalkParams::db_h,
 // p.dstride halves a row = the floats of the staged query) -- the three distances read the row through HalfRow4, a lane per row: l2_ordered /
 // negdot_ordered on float32(row), any dimension, both metrics (L2 never reads a coordinate beyond 4 * floor(d / 4): such a tail may hold any
 // bit pattern; the negative dot reads all d and the row's zero padding against the staged zeros).  Exact, not tuned.  It takes every flagged
 // call outside the domain of walk_half_base.hip's instances and every query those hand over.
-template <int METRIC, int TAG, bool BYTES = false, bool BWALK = false, bool HWALK = false>
+// The distance of row `id` of the walked table from the staged query, by the table's kind: float4 rows, ByteRow4, HalfRow4 (a lane per row).
+template <int METRIC, RowKind WALKED>
+__device__ __forceinline__ float walked_row_dist(const WalkParams& p, const float4* qs, uint32_t id) {
+    if constexpr (WALKED == RowKind::F16) return metric_dist<METRIC>(qs, HalfRow4{reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(p.db_h) + (size_t)id * p.dstride)}, p.dim);
+    else if constexpr (WALKED == RowKind::U8) return metric_dist<METRIC>(qs, ByteRow4{reinterpret_cast<const uint32_t*>(p.db_b + (size_t)id * p.dstride)}, p.dim);
+    else return metric_dist<METRIC>(qs, reinterpret_cast<const float4*>(p.db + (size_t)id * p.dstride), p.dim);
+}
+
+template <int METRIC, int TAG, RowKind WALKED = RowKind::F32, RowKind RR = RowKind::F32>
 __device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* smem, uint32_t* bst = nullptr) {
     const int lane = lane_id();
     const uint32_t slot = blockIdx.x;
@@ -71,7 +80,7 @@ __device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* s
                 for (uint32_t e = 0; e < n_ent && !bad; ++e) bad |= (p.tags[p.entries ? p.entries[(size_t)qi * n_ent + e] : 0u] & qtag) == 0u;
             }
             if (bad) {
-                if constexpr (BYTES) write_bad_entry_bytes(p, qi, lane);
+                if constexpr (RR == RowKind::U8) write_bad_entry_bytes(p, qi, lane);
                 else write_bad_entry(p, qi, lane);
                 wave_sync();
                 continue;
@@ -92,12 +101,7 @@ __device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* s
         wave_sync();
         const uint32_t entry = p.entries ? p.entries[(size_t)qi * n_ent + e] : 0u;
         {
-            float d0;
-            if constexpr (HWALK) d0 = metric_dist<METRIC>(qs, HalfRow4{reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(p.db_h) + (size_t)entry * p.dstride)}, p.dim);
-            else if constexpr (BWALK) d0 = metric_dist<METRIC>(qs, ByteRow4{reinterpret_cast<const uint32_t*>(p.db_b + (size_t)entry * p.dstride)}, p.dim);
-            else d0 =
-                metric_dist<METRIC>(qs, reinterpret_cast<const float4*>(p.db + (size_t)entry * p.dstride),
-                                    p.dim);
+            const float d0 = walked_row_dist<METRIC, WALKED>(p, qs, entry);
             if (e == 0) {
                 if (lane == 0) keys[0] = make_key(fkey(d0), entry);
                 st.size = 1;
@@ -129,14 +133,7 @@ __device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* s
                     fresh = !(atomicOr(&bitmap[nb >> 5], bit) & bit);
                 }
                 uint32_t dk = 0xFFFFFFFFu;
-                if constexpr (HWALK) {
-                    if (fresh) dk = fkey(metric_dist<METRIC>(qs, HalfRow4{reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(p.db_h) + (size_t)nb * p.dstride)}, p.dim));
-                } else if constexpr (BWALK) {
-                    if (fresh) dk = fkey(metric_dist<METRIC>(qs, ByteRow4{reinterpret_cast<const uint32_t*>(p.db_b + (size_t)nb * p.dstride)}, p.dim));
-                } else
-                if (fresh)
-                    dk = fkey(metric_dist<METRIC>(
-                        qs, reinterpret_cast<const float4*>(p.db + (size_t)nb * p.dstride), p.dim));
+                if (fresh) dk = fkey(walked_row_dist<METRIC, WALKED>(p, qs, nb));
                 const uint64_t mf = __ballot(fresh);
                 st.dist_calc += __popcll(mf);
                 const uint32_t worst0 = key_hi(keys[st.size - 1]);
@@ -152,6 +149,8 @@ __device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* s
             }
         };
         // TAG == 2: one chunk of a row of G'' -- every id allowed, in order; what make_step does with a chunk, behind the first-occurrence filter
+        // (the tail from `fresh` on is make_step's, line for line, and stays written out twice: shared through one lambda, every instance of this
+        // body compiles to the same instructions in another order -- and the kernels' instructions are pinned)
         auto offer_chunk = [&](uint32_t nb, bool valid, bool& found) {
             uint64_t mv = __ballot(valid);
             st.edges += __popcll(mv);  // (the degree in G'' counts repeated ids)
@@ -169,13 +168,7 @@ __device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* s
                 fresh = !(atomicOr(&bitmap[nb >> 5], bit) & bit);
             }
             uint32_t dk = 0xFFFFFFFFu;
-            if constexpr (HWALK) {
-                if (fresh) dk = fkey(metric_dist<METRIC>(qs, HalfRow4{reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(p.db_h) + (size_t)nb * p.dstride)}, p.dim));
-            } else if constexpr (BWALK) {
-                if (fresh) dk = fkey(metric_dist<METRIC>(qs, ByteRow4{reinterpret_cast<const uint32_t*>(p.db_b + (size_t)nb * p.dstride)}, p.dim));
-            } else
-            if (fresh)
-                dk = fkey(metric_dist<METRIC>(qs, reinterpret_cast<const float4*>(p.db + (size_t)nb * p.dstride), p.dim));
+            if (fresh) dk = fkey(walked_row_dist<METRIC, WALKED>(p, qs, nb));
             const uint64_t mf = __ballot(fresh);
             st.dist_calc += __popcll(mf);
             const uint32_t worst0 = key_hi(keys[st.size - 1]);
@@ -253,7 +246,7 @@ __device__ __forceinline__ void walk_general_body(WalkParams p, unsigned char* s
         }  // entry points
         tie.clear(st.tsize, lane);  // leaves the tie bits all zero for the next query
         write_results(p, qi, keys, st, lane);
-        if constexpr (BYTES) {
+        if constexpr (RR == RowKind::U8) {
             if (p.rr_db_b) {
                 const int kept = st.size < p.k ? st.size : p.k;
                 fused_rerank<8, true>(p, qi, kept, smem, lane, [&](int rank) { return key_id(keys[rank]); });
@@ -280,7 +273,7 @@ __global__ __launch_bounds__(64) void walk_general_tag_kernel(WalkParams p) {
 
 __global__ __launch_bounds__(64) void walk_general_bytes_kernel(WalkParams p) {  // (the byte instances are L2 ones)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    walk_general_body<0, 0, true>(p, smem);
+    walk_general_body<0, 0, RowKind::F32, RowKind::U8>(p, smem);
 }
 
 template <int METRIC>
@@ -295,7 +288,7 @@ template <int METRIC, int TAG>
 __global__ __launch_bounds__(64) void walk_general_bwalk_kernel(WalkParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ uint32_t bst[TAG == 2 ? 64 : 1];
-    walk_general_body<METRIC, TAG, false, true>(p, smem, TAG == 2 ? bst : nullptr);
+    walk_general_body<METRIC, TAG, RowKind::U8>(p, smem, TAG == 2 ? bst : nullptr);
 }
 
 // GBNNS_FLAG_HALF_WALK: plain, cut and bridged over binary16 walked rows
@@ -303,7 +296,7 @@ template <int METRIC, int TAG>
 __global__ __launch_bounds__(64) void walk_general_hwalk_kernel(WalkParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ uint32_t bst[TAG == 2 ? 64 : 1];
-    walk_general_body<METRIC, TAG, false, false, true>(p, smem, TAG == 2 ? bst : nullptr);
+    walk_general_body<METRIC, TAG, RowKind::F16>(p, smem, TAG == 2 ? bst : nullptr);
 }
 
 template <typename K>
@@ -354,68 +347,26 @@ __global__ __launch_bounds__(64) void debug_merge_kernel(const uint64_t* entries
 
 hipError_t launch_walk_general(const WalkParams& p, int metric, hipStream_t s) {
     if (p.nq == 0) return hipSuccess;
-    const size_t lds = std::max((size_t)p.dstride * 4, (p.rr_db || p.rr_db_b) ? (size_t)p.rr_dstride * 4 : (size_t)0);
-    if (p.walk_half) {  // GBNNS_FLAG_HALF_WALK: a PLAIN walk over binary16 rows, no re-rank
-        if (!p.db_h || p.db || p.walk_bytes || p.rr_db || p.rr_db_b || (p.tagged && (!p.tags || !p.qtags))) return hipErrorInvalidValue;
-        const int tag = p.tagged ? (p.bridged ? 2 : 1) : 0;
-        if (metric == 1) {
-            if (tag == 2) return launch_general(walk_general_hwalk_kernel<1, 2>, p, lds, s);
-            if (tag == 1) return launch_general(walk_general_hwalk_kernel<1, 1>, p, lds, s);
-            return launch_general(walk_general_hwalk_kernel<1, 0>, p, lds, s);
-        }
-        if (tag == 2) return launch_general(walk_general_hwalk_kernel<0, 2>, p, lds, s);
-        if (tag == 1) return launch_general(walk_general_hwalk_kernel<0, 1>, p, lds, s);
-        return launch_general(walk_general_hwalk_kernel<0, 0>, p, lds, s);
-    }
-    if (p.walk_bytes) {  // GBNNS_FLAG_BYTE_WALK: a PLAIN walk over uint8 rows, no re-rank
-        if (!p.db_b || p.rr_db || p.rr_db_b || (p.tagged && (!p.tags || !p.qtags))) return hipErrorInvalidValue;
-        const int tag = p.tagged ? (p.bridged ? 2 : 1) : 0;
-        if (metric == 1) {
-            if (tag == 2) return launch_general(walk_general_bwalk_kernel<1, 2>, p, lds, s);
-            if (tag == 1) return launch_general(walk_general_bwalk_kernel<1, 1>, p, lds, s);
-            return launch_general(walk_general_bwalk_kernel<1, 0>, p, lds, s);
-        }
-        if (tag == 2) return launch_general(walk_general_bwalk_kernel<0, 2>, p, lds, s);
-        if (tag == 1) return launch_general(walk_general_bwalk_kernel<0, 1>, p, lds, s);
-        return launch_general(walk_general_bwalk_kernel<0, 0>, p, lds, s);
-    }
-    if (p.rr_db_b) {  // a byte handle's fused call: untagged, L2 (walk_plan.cpp)
-        if (p.rr_db || p.tagged || metric != 0) return hipErrorInvalidValue;
-        hipError_t e = set_lds(walk_general_bytes_kernel, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(walk_general_bytes_kernel, dim3(kGeneralSlots), dim3(64), lds, s, p);
-    } else if (p.tagged && p.bridged) {
-        if (!p.tags || !p.qtags) return hipErrorInvalidValue;
-        if (metric == 1) {
-            hipError_t e = set_lds(walk_general_bridge_kernel<1>, lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((walk_general_bridge_kernel<1>), dim3(kGeneralSlots), dim3(64), lds, s, p);
-        } else {
-            hipError_t e = set_lds(walk_general_bridge_kernel<0>, lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((walk_general_bridge_kernel<0>), dim3(kGeneralSlots), dim3(64), lds, s, p);
-        }
-    } else if (p.tagged) {
-        if (!p.tags || !p.qtags) return hipErrorInvalidValue;
-        if (metric == 1) {
-            hipError_t e = set_lds(walk_general_tag_kernel<1>, lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((walk_general_tag_kernel<1>), dim3(kGeneralSlots), dim3(64), lds, s, p);
-        } else {
-            hipError_t e = set_lds(walk_general_tag_kernel<0>, lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((walk_general_tag_kernel<0>), dim3(kGeneralSlots), dim3(64), lds, s, p);
-        }
-    } else if (metric == 1) {
-        hipError_t e = set_lds(walk_general_kernel<1>, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((walk_general_kernel<1>), dim3(kGeneralSlots), dim3(64), lds, s, p);
-    } else {
-        hipError_t e = set_lds(walk_general_kernel<0>, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((walk_general_kernel<0>), dim3(kGeneralSlots), dim3(64), lds, s, p);
-    }
-    return hipGetLastError();
+    const bool rerank = p.rr_db || p.rr_db_b;
+    // a PLAIN walk over the handle's own uint8 / binary16 rows (GBNNS_FLAG_BYTE_WALK / GBNNS_FLAG_HALF_WALK): one kind of rows, its table, no re-rank
+    if (p.walk_half && (!p.db_h || p.db || p.walk_bytes)) return hipErrorInvalidValue;
+    if (p.walk_bytes && !p.db_b) return hipErrorInvalidValue;
+    if ((p.walk_half || p.walk_bytes) && rerank) return hipErrorInvalidValue;
+    // a byte handle's fused call: untagged, L2 (walk_plan.cpp)
+    if (p.rr_db_b && (p.rr_db || p.tagged || metric != 0)) return hipErrorInvalidValue;
+    if (p.tagged && (!p.tags || !p.qtags)) return hipErrorInvalidValue;
+    const size_t lds = std::max((size_t)p.dstride * 4, rerank ? (size_t)p.rr_dstride * 4 : (size_t)0);
+    using Kernel = void (*)(WalkParams);
+    // [metric][untagged / cut / bridged] per kind of walked rows
+    static const Kernel f32[2][3] = {{walk_general_kernel<0>, walk_general_tag_kernel<0>, walk_general_bridge_kernel<0>},
+                                     {walk_general_kernel<1>, walk_general_tag_kernel<1>, walk_general_bridge_kernel<1>}};
+    static const Kernel u8[2][3] = {{walk_general_bwalk_kernel<0, 0>, walk_general_bwalk_kernel<0, 1>, walk_general_bwalk_kernel<0, 2>},
+                                    {walk_general_bwalk_kernel<1, 0>, walk_general_bwalk_kernel<1, 1>, walk_general_bwalk_kernel<1, 2>}};
+    static const Kernel f16[2][3] = {{walk_general_hwalk_kernel<0, 0>, walk_general_hwalk_kernel<0, 1>, walk_general_hwalk_kernel<0, 2>},
+                                     {walk_general_hwalk_kernel<1, 0>, walk_general_hwalk_kernel<1, 1>, walk_general_hwalk_kernel<1, 2>}};
+    const int m = metric == 1 ? 1 : 0, tag = p.tagged ? (p.bridged ? 2 : 1) : 0;
+    if (p.rr_db_b) return launch_general(walk_general_bytes_kernel, p, lds, s);
+    return launch_general((p.walk_half ? f16 : (p.walk_bytes ? u8 : f32))[m][tag], p, lds, s);
 }
 
 hipError_t launch_debug_merge(int regs, const uint64_t* entries, int size, const uint64_t* surv, int ef, uint64_t* out,

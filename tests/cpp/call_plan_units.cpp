@@ -1,8 +1,9 @@
 // call_plan_units.cpp -- the call plan (csrc/call_plan.cpp, with sizing.cpp and walk_plan.cpp) run without a device.
 //   call_plan_units golden <file>         every line of tests/golden/call_plan_cases.txt -- a search call traced on a device: its inputs and
 //                                         the kernels that ran -- through call_plan(): the same first pass, grid, LDS, retry action, re-rank
+//                                         (the file's byte_handle= / walk_bytes= keys: CallFacts::rows / walked of kind U8)
 //   call_plan_units grid <dims> <beams>   the conditions the plan guarantees by construction, over dims x beams (comma lists) x both metrics x
-//                                         nq in {96, 2 048, 16 384} x untagged / tagged / byte-walk calls x no history / a calm history
+//                                         nq in {96, 2 048, 16 384} x untagged / tagged / byte-walk / half-base / half-walk calls x no history / a calm history
 //   call_plan_units walkgrid <dims> <beams>  plan_walk() over the cross product of every input it reads (walk_grid below): the plan count and one
 //                                         digest of the formatted plans per (feature variant, pass), compared with tests/golden/walk_plan_grid.txt
 // Built by tests/test_call_plan_units.py from the three units' sources; the kernel tables' names (walk_plan_name), the visited set's byte counts
@@ -59,8 +60,8 @@ static int golden(const char* path) {
         auto num = [&](const char* k) { return std::strtoll(kv.at(k).c_str(), nullptr, 10); };
         CallFacts f{};
         f.metric = (int)num("metric"); f.n = (uint64_t)num("n"); f.d = (uint32_t)num("d"); f.d_pad = (uint32_t)num("d_pad"); f.ell_stride = (uint32_t)num("ell_stride");
-        f.aux_stride = 0; f.byte_handle = num("byte_handle") != 0; f.cus = (size_t)num("cus"); f.knob = knob_defaults(); f.knob.hot = (int)num("hot");
-        f.dim = (uint32_t)num("dim"); f.dstride = (uint32_t)num("dstride"); f.half_rows = false; f.walk_bytes = num("walk_bytes") != 0; f.byte_queries = false;
+        f.aux_stride = 0; f.rows = num("byte_handle") != 0 ? RowKind::U8 : RowKind::F32; f.cus = (size_t)num("cus"); f.knob = knob_defaults(); f.knob.hot = (int)num("hot");
+        f.dim = (uint32_t)num("dim"); f.dstride = (uint32_t)num("dstride"); f.half_rows = false; f.walked = num("walk_bytes") != 0 ? RowKind::U8 : RowKind::F32; f.byte_queries = false;
         f.mode = (int)num("mode"); f.ef = (int)num("ef"); f.n_entries = (uint32_t)num("n_entries"); f.flags = (uint32_t)num("flags"); f.hash_capacity = (int32_t)num("hash_capacity");
         f.nq = (uint32_t)num("nq"); f.tagged = num("tagged") != 0; f.bridged = false; f.in_flight = num("in_flight") != 0; f.sync_host = num("sync_host") != 0;
         const CallPlan p = call_plan(f, SizingHistory{});
@@ -108,7 +109,8 @@ static void check_one(const CallFacts& f, const SizingHistory& h, const char* wh
         const size_t room = p.first.rr_room(walk_hash_bytes(p.hash_cap, p.first.hash_form(p.vs_shr)));
         CHECK(!p.first.lds_list && (size_t)f.d_pad * 4 <= room, "%s: fused with room for %zu bytes", id, room);
     }
-    if (p.bitmap_pass) CHECK(!p.coop && !f.tagged && !f.walk_bytes && p.bitmap_per_cu > 0, "%s: bitmap pass", id);
+    if (p.bitmap_pass) CHECK(!p.coop && !f.tagged && f.walked == RowKind::F32 && p.bitmap_per_cu > 0, "%s: bitmap pass", id);
+    if (f.rows == RowKind::F16 && f.mode != GBNNS_MODE_PLAIN) CHECK(!p.fuse, "%s: a half-base handle's re-rank fused", id);  // (a stand-alone re-rank follows)
     if (p.skip_retry) CHECK(p.sizing.auto_cap && !p.all_general && p.retry_action == RetryAction::None, "%s: skip_retry", id);
     if (p.all_general) CHECK(p.retry_action == RetryAction::None && !p.bitmap_pass, "%s: all_general with a pass of its own", id);
     if (!p.all_general) CHECK(walk_plan_name(p.first) != nullptr, "%s: no instance for the first pass", id);
@@ -117,7 +119,8 @@ static void check_one(const CallFacts& f, const SizingHistory& h, const char* wh
 
 static int grid(const char* dims_csv, const char* beams_csv) {
     int plans = 0;
-    for (int kind = 0; kind < 3; ++kind)  // untagged LOWQ, tagged LOWQ, PLAIN byte walk
+    static const char* const kinds[] = {"untagged", "tagged", "byte walk", "half base", "half walk"};
+    for (int kind = 0; kind < 5; ++kind)  // untagged LOWQ, tagged LOWQ, PLAIN byte walk, a half-base handle's LOWQ, PLAIN half walk
         for (int metric = 0; metric < 2; ++metric)
             for (int dim : ints(dims_csv))
                 for (int ef : ints(beams_csv))
@@ -127,11 +130,14 @@ static int grid(const char* dims_csv, const char* beams_csv) {
                             f.metric = metric; f.n = 20000; f.ell_stride = 32; f.cus = 256; f.knob = knob_defaults();
                             f.ef = ef; f.n_entries = 1; f.nq = nq; f.sync_host = true;
                             if (kind == 2) {
-                                f.d = f.dim = (uint32_t)dim; f.d_pad = f.dstride = ((uint32_t)dim + 15u) / 16u * 16u;
-                                f.byte_handle = f.walk_bytes = true; f.mode = GBNNS_MODE_PLAIN;
+                                f.rows = f.walked = RowKind::U8; f.mode = GBNNS_MODE_PLAIN;
+                                f.d = f.dim = (uint32_t)dim; f.d_pad = f.dstride = row_pad((uint32_t)dim, f.rows);
+                            } else if (kind == 4) {
+                                f.rows = f.walked = RowKind::F16; f.mode = GBNNS_MODE_PLAIN;
+                                f.d = f.dim = (uint32_t)dim; f.d_pad = f.dstride = row_pad((uint32_t)dim, f.rows);
                             } else {
                                 f.d = f.d_pad = 128; f.dim = (uint32_t)dim; f.dstride = ((uint32_t)dim + 3u) / 4u * 4u;
-                                f.mode = GBNNS_MODE_LOWQ; f.tagged = kind == 1;
+                                f.mode = GBNNS_MODE_LOWQ; f.tagged = kind == 1; f.rows = kind == 3 ? RowKind::F16 : RowKind::F32;
                             }
                             SizingHistory h;
                             if (calm) {  // a settled class: three quiet batches whose longest walk computed 30 ef distances
@@ -139,7 +145,7 @@ static int grid(const char* dims_csv, const char* beams_csv) {
                                 const uint32_t maxdc = 30u * (uint32_t)ef;
                                 h.maxdc_for_ef[skey] = maxdc; h.cap_for_ef[skey] = (maxdc + maxdc / 16 + 64) / 15 * 16 + 16; h.calm_streak[skey] = 3;
                             }
-                            check_one(f, h, kind == 0 ? "untagged" : (kind == 1 ? "tagged" : "byte walk"));
+                            check_one(f, h, kinds[kind]);
                             ++plans;
                         }
     std::printf("grid: %d plans, %d failed\n", plans, g_failed);
@@ -147,9 +153,11 @@ static int grid(const char* dims_csv, const char* beams_csv) {
 }
 
 // ---- walkgrid --------------------------------------------------------------------------------------------------------------------------------
-// Fifteen feature variants over an otherwise zeroed WalkParams; `dim` is the grid's dimension (dstride = dim rounded up to 4).
+// Eighteen feature variants over an otherwise zeroed WalkParams; `dim` is the grid's dimension (dstride = dim rounded up to 4; "walk_half unkept": to 8).
 static const char* const kVariants[] = {"plain", "coop", "late_rows", "spec_rows", "half_rows", "tagged", "tagged+bridged", "generic_only", "bytes_dim=128", "bytes_dim=40",
-                                        "walk_bytes d=128", "walk_bytes q_b classes=7", "walk_bytes q_b classes=2", "stamps_on", "rr_reserve=160"};
+                                        "walk_bytes d=128", "walk_bytes q_b classes=7", "walk_bytes q_b classes=2", "stamps_on", "rr_reserve=160",
+                                        "walk_half d=96", "walk_half unkept", "walk_half general"};
+constexpr int kNumVariants = (int)(sizeof kVariants / sizeof kVariants[0]);
 static void set_variant(WalkParams& p, int v) {
     static const uint8_t byte_queries[16] = {0};
     switch (v) {
@@ -167,6 +175,9 @@ static void set_variant(WalkParams& p, int v) {
         case 12: p.walk_bytes = 1; p.q_b = byte_queries; p.bq_classes = 2; break;
         case 13: p.stamps_on = 1; break;
         case 14: p.rr_reserve = 160; break;
+        case 15: p.walk_half = 1; p.dim = p.dstride = 96; break;
+        case 16: p.walk_half = 1; p.half_unkept = 1; p.dstride = (p.dim + 7u) / 8u * 8u; break;
+        case 17: p.walk_half = 1; p.half_general = 1; break;
         default: break;
     }
 }
@@ -178,7 +189,7 @@ static int walk_grid(const char* dims_csv, const char* beams_csv) {
     const std::vector<int> dims = ints(dims_csv), beams = ints(beams_csv);
     long long plans = 0;
     std::string lines;
-    for (int v = 0; v < 15; ++v)
+    for (int v = 0; v < kNumVariants; ++v)
         for (int pass = 0; pass < 3; ++pass) {
             uint64_t digest = 0xcbf29ce484222325ull;  // FNV-1a, 64 bits, over the lines of this (variant, pass)
             for (const WalkEnv& env : envs)

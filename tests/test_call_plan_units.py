@@ -44,19 +44,20 @@ def test_traced_calls_get_the_same_plan(unit):
 
 def test_plan_conditions_over_the_census_grid(unit):
     """First-pass LDS within 160 KB unless all_general; fuse only off the LDS-list pass and within the re-rank room; a bitmap pass without
-    coop, tags or a byte walk; skip_retry only with an automatic capacity and not all_general; the history untouched; the same plan twice."""
+    coop, tags, a byte walk or a half walk; a half-base handle's LOWQ call never fused; skip_retry only with an automatic capacity and not all_general; the history untouched; the same plan twice."""
     out = unit("grid", ",".join(str(d) for d in wi.DIMS), ",".join(str(e) for e in wi.BEAMS))
-    plans = 3 * 2 * len(wi.DIMS) * len(wi.BEAMS) * 3 * 2
+    plans = 5 * 2 * len(wi.DIMS) * len(wi.BEAMS) * 3 * 2
     assert "grid: %d plans, 0 failed" % plans in out, out
 
 
 def test_plan_walk_is_the_recorded_function(unit):
     """plan_walk over the cross product of everything it reads -- both environments x metric x dim x n either side of the two-wavefront walk's
-    and the 24-bit ids' limits x adjacency width x auxiliary graph x beam x entry points x force_wide, for each of three passes and fifteen
+    and the 24-bit ids' limits x adjacency width x auxiliary graph x beam x entry points x force_wide, for each of three passes and eighteen
     feature variants: per (variant, pass) one digest of every plan's kernel name, family and layout facts.  tests/golden/walk_plan_grid.txt was
-    recorded by this driver built against the commit its first line names, before WalkInstance's switches became one set of named flags."""
+    recorded by this driver built against the commits its header names: the first fifteen variants before WalkInstance's switches became one
+    set of named flags, the three half-walk variants before the handle's row kind became one field."""
     with open(os.path.join(ROOT, "tests", "golden", "walk_plan_grid.txt")) as f:
         want = [line.rstrip("\n") for line in f if not line.startswith("#")]
-    assert want[0] == "walkgrid: %d plans" % (15 * 3 * 2 * 2 * len(wi.DIMS) * 4 * 3 * 2 * len(wi.BEAMS) * 2 * 2) and len(want) == 1 + 15 * 3
+    assert want[0] == "walkgrid: %d plans" % (18 * 3 * 2 * 2 * len(wi.DIMS) * 4 * 3 * 2 * len(wi.BEAMS) * 2 * 2) and len(want) == 1 + 18 * 3
     got = unit("walkgrid", ",".join(str(d) for d in wi.DIMS), ",".join(str(e) for e in wi.BEAMS)).splitlines()
     assert got == want, [pair for pair in zip(got, want) if pair[0] != pair[1]]
