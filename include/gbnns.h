@@ -303,7 +303,10 @@ int gbnns_index_wait(gbnns_index* index, uint32_t keep);
  * perform*Test functions pin the query / answer vectors before their timed region (the reference builds its
  * VisitedListPool there, search_function.h:333) and release them after it.  Pinning an already page-locked buffer
  * and releasing one that was not pinned here are no-ops.  Registrations are made in whole pages and never overlap:
- * small buffers that share a page share its registration (counted), which is released with its last user. */
+ * small buffers that share a page share its registration (counted), which is released with its last user.  Where the
+ * runtime cannot page-lock memory that the process already has (hipHostRegister fails, as under some virtual machines),
+ * gbnns_host_pin returns GBNNS_ERR_HIP and the buffer stays pageable: every call on it is still correct, the plain
+ * synchronous one; allocate the buffers page-locked (hipHostMalloc) to have batches in flight there. */
 int gbnns_host_pin(void* ptr, size_t bytes);
 int gbnns_host_unpin(void* ptr);
 
