@@ -260,7 +260,7 @@ int build_ell(const uint64_t* off, const uint32_t* nbr, uint64_t n, std::vector<
 int run_project(gbnns_index* ix, Lane& L, const float* x, uint32_t xstride, uint32_t nx, float* out, hipStream_t s, bool in_flight = false,
                 bool mfma = false);
 int prof_flush(gbnns_index* ix);
-// the stand-alone re-rank over the handle's original-space table, by the kernels of its row kind (rerank.hip / rerank_bytes.hip / rerank_half.hip);
+// the stand-alone re-rank over the handle's original-space table, by the kernels of its row kind (rerank.hip: F32; rerank_rows.hip: U8 and F16);
 // the table and its row stride are the handle's, whatever the caller put into r.db / r.dstride.  P: RerankParams (the best of every list) or
 // RerankTopkParams (its k best)
 template <class P>

@@ -154,10 +154,12 @@ CallPlan call_plan(const CallFacts& f, const SizingHistory& h) {
     const bool plain = f.mode == GBNNS_MODE_PLAIN;
     WalkParams w{};
     set_walk_shape(w, f);
+    // Does the call want the re-rank fused into its walk kernels?  The plan of the handle's rows says whether their form can be (rerank_plan.h).
     // A byte handle (gbnns_index_create_bytes): the re-rank is fused only into the byte instances (walk_plan.cpp decides, from bytes_dim);
     // every other first pass runs as on a float handle with GBNNS_FLAG_NO_FUSED_RERANK, the stand-alone byte kernel behind it
     const bool bytes = f.rows == RowKind::U8;
-    if (bytes && !plain && !(f.flags & GBNNS_FLAG_NO_FUSED_RERANK) && rerank_plan(f.metric, f.d, true).fuses) w.bytes_dim = f.d;
+    const bool want_fuse = !plain && !(f.flags & GBNNS_FLAG_NO_FUSED_RERANK) && rerank_plan(f.metric, f.d, f.rows).fuses;
+    if (bytes && want_fuse) w.bytes_dim = f.d;
     // (a byte walk, GBNNS_FLAG_BYTE_WALK: a bit of its own too -- other kernels, no retry pass, and never the float handle's or the byte re-rank's state)
     cp.skey = stats_key(f, w);
     const int calm = h.calm(cp.skey);
@@ -184,10 +186,8 @@ CallPlan call_plan(const CallFacts& f, const SizingHistory& h) {
     // wavefront re-ranks its own query when its walk ends; no re-rank launch.  Needs the pair form
     // (d % 8 == 0) and room for the original-space query in the walk kernels' LDS.
     // (rerank_plan.h: the pair form; L2: d % 8 == 4 too -- glove's 300 -- its last 16-byte step is the even lane's alone)
-    // A half-base handle (gbnns_index_create_half_base): rerank_half_plan never fuses -- every first pass runs as on a float handle with
+    // A half-base handle (gbnns_index_create_half_base): its plan never fuses -- every first pass runs as on a float handle with
     // GBNNS_FLAG_NO_FUSED_RERANK, the stand-alone half kernel behind it, and sets no LDS aside for a re-rank query
-    const bool want_fuse = f.rows == RowKind::F16 ? rerank_half_plan(f.metric, f.d).fuses
-                                       : (bytes ? w.bytes_dim != 0u : (!plain && rerank_plan(f.metric, f.d, false).fuses && !(f.flags & GBNNS_FLAG_NO_FUSED_RERANK)));
     w.rr_reserve = (want_fuse && !bytes) ? (uint32_t)f.d_pad * 4u : 0u;  // (the bitmap pass has no byte instance)
     cp.bitmap_per_cu = bitmap_rule(f, w, plan, fps.form);
     cp.bitmap_pass = cp.bitmap_per_cu != 0;

@@ -823,23 +823,12 @@ template <class P>
 hipError_t rerank_launch(const gbnns_index* ix, const P& r, hipStream_t s) {
     constexpr bool topk = std::is_same<P, RerankTopkParams>::value;
     const int metric = ix->metric;
-    auto of_kind = [&](auto k) {  // (k: an empty parameter struct of the kind)
-        static_cast<P&>(k) = r;
-        k.db = nullptr; k.dstride = ix->d_pad;
-        return k;
-    };
-    switch (ix->rows) {
-        case RowKind::U8: {
-            RerankBytesParams b = of_kind(RerankBytesParams{});
-            b.db_b = ix->base_as<uint8_t>();
-            return topk ? launch_rerank_topk_bytes(b, metric, s) : launch_rerank_bytes(b, metric, s);
-        }
-        case RowKind::F16: {
-            RerankHalfParams h = of_kind(RerankHalfParams{});
-            h.db_h = ix->base_as<uint16_t>();
-            return topk ? launch_rerank_topk_half(h, metric, s) : launch_rerank_half(h, metric, s);
-        }
-        case RowKind::F32: break;
+    if (ix->rows != RowKind::F32) {
+        RerankRowsParams n{};
+        static_cast<P&>(n) = r;
+        n.db = nullptr; n.dstride = ix->d_pad;
+        n.db_rows = ix->base;
+        return topk ? launch_rerank_topk_rows(ix->rows, n, metric, s) : launch_rerank_rows(ix->rows, n, metric, s);
     }
     P f = r;
     f.db = ix->base_as<float>(); f.dstride = ix->d_pad;
@@ -1071,28 +1060,26 @@ int gbnns_debug_byte_plan(int metric, uint32_t dim, uint32_t dstride, uint64_t n
                       name_bytes, nullptr, fused);
 }
 
-int gbnns_debug_rerank_plan(int metric, uint32_t d, int bytes, char* name, uint32_t name_bytes, int* deep, int* fused) {
-    if (!name || name_bytes == 0 || !deep || !fused) return fail(GBNNS_ERR_INVALID, "gbnns_debug_rerank_plan: null output");
+// the re-rank plan of rows of a kind, as both debug calls report it: the plan's label (not the C++ template's name), DEEP, the fused flag
+static int debug_rerank_plan(const char* fn, int metric, uint32_t d, RowKind rows, char* name, uint32_t name_bytes, int* deep, int* fused) {
+    if (!name || name_bytes == 0 || !deep || !fused) return fail(GBNNS_ERR_INVALID, "%s: null output", fn);
     if ((metric != GBNNS_METRIC_L2 && metric != GBNNS_METRIC_NEG_DOT) || d == 0)
-        return fail(GBNNS_ERR_INVALID, "gbnns_debug_rerank_plan: not the metric or the dimension of an index");
-    const RerankPlan plan = rerank_plan(metric, d, bytes != 0);
-    if (plan.form == RerankForm::ChunkPairs) std::snprintf(name, name_bytes, "rerank_bytes_pair_kernel");
-    else std::snprintf(name, name_bytes, "%s<%d>", bytes ? "rerank_bytes_kernel" : (plan.form == RerankForm::Pairs ? "rerank_pair_kernel" : "rerank_kernel"), metric);
+        return fail(GBNNS_ERR_INVALID, "%s: not the metric or the dimension of an index", fn);
+    const RerankPlan plan = rerank_plan(metric, d, rows);
+    const char* kind = rows == RowKind::U8 ? "bytes_" : (rows == RowKind::F16 ? "half_" : "");
+    if (plan.form == RerankForm::ChunkPairs) std::snprintf(name, name_bytes, "rerank_%spair_kernel", kind);
+    else std::snprintf(name, name_bytes, "rerank_%s%skernel<%d>", kind, plan.form == RerankForm::Pairs ? "pair_" : "", metric);
     *deep = plan.deep;
     *fused = plan.fuses ? 1 : 0;
     return GBNNS_OK;
 }
 
+int gbnns_debug_rerank_plan(int metric, uint32_t d, int bytes, char* name, uint32_t name_bytes, int* deep, int* fused) {
+    return debug_rerank_plan("gbnns_debug_rerank_plan", metric, d, bytes ? RowKind::U8 : RowKind::F32, name, name_bytes, deep, fused);
+}
+
 int gbnns_debug_half_base_plan(int metric, uint32_t d, char* name, uint32_t name_bytes, int* deep, int* fused) {
-    if (!name || name_bytes == 0 || !deep || !fused) return fail(GBNNS_ERR_INVALID, "gbnns_debug_half_base_plan: null output");
-    if ((metric != GBNNS_METRIC_L2 && metric != GBNNS_METRIC_NEG_DOT) || d == 0)
-        return fail(GBNNS_ERR_INVALID, "gbnns_debug_half_base_plan: not the metric or the dimension of an index");
-    const RerankPlan plan = rerank_half_plan(metric, d);
-    if (plan.form == RerankForm::HalfChunkPairs) std::snprintf(name, name_bytes, "rerank_half_pair_kernel");
-    else std::snprintf(name, name_bytes, "rerank_half_kernel<%d>", metric);
-    *deep = plan.deep;
-    *fused = plan.fuses ? 1 : 0;
-    return GBNNS_OK;
+    return debug_rerank_plan("gbnns_debug_half_base_plan", metric, d, RowKind::F16, name, name_bytes, deep, fused);
 }
 
 // (a flagged PLAIN call on a byte handle: rows of round_up(dim, 16) bytes; the general kernel: the staged query alone)

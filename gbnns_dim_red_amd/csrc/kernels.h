@@ -173,22 +173,15 @@ struct RerankTopkParams : RerankParams {
 constexpr uint32_t rerank_topk_key_slots(uint32_t cand_stride) { return (cand_stride + 1u) & ~1u; }
 size_t rerank_topk_lds(uint32_t dstride, uint32_t cand_stride);
 hipError_t launch_rerank_topk(const RerankTopkParams& p, int metric, hipStream_t s);
-// The same two over the uint8 rows of a byte handle (rerank_bytes.hip): `db` stays nullptr, `dstride` is the BYTES of a row -- round_up(dim, 16),
-// zero padded, which is also the floats of the staged query -- and `k` / `out_dist` are read by the k-answer launch only.  The distances are
-// the float kernels' on float32(db_b), bit for bit.  L2 with dim % 16 == 0: the chunk-pair form; else a lane per row (rerank_plan.h).
-struct RerankBytesParams : RerankTopkParams {
-    const uint8_t* db_b;     // [n x dstride] bytes, rows 16-byte aligned
+// The same two over the narrow rows of a byte handle (`rows` U8) or a half-base handle (F16), rerank_rows.hip: `db` stays nullptr, `dstride`
+// counts ELEMENTS of a row -- row_pad(dim, rows), zero padded, which is also the floats of the staged query -- and `k` / `out_dist` are read
+// by the k-answer launch only.  The distances are the float kernels' on float32(db_rows), bit for bit.  The chunk-pair form where
+// rerank_plan.h gives it (L2; U8: dim % 16 == 0, F16: dim % 4 == 0), else a lane per row.  rows == F32: hipErrorInvalidValue.
+struct RerankRowsParams : RerankTopkParams {
+    const void* db_rows;     // [n x dstride] uint8 values or binary16 bit patterns, rows 16-byte aligned
 };
-hipError_t launch_rerank_bytes(const RerankBytesParams& p, int metric, hipStream_t s);
-hipError_t launch_rerank_topk_bytes(const RerankBytesParams& p, int metric, hipStream_t s);
-// The same two over the binary16 rows of a half-base handle (rerank_half.hip): `db` stays nullptr, `dstride` is the HALVES of a row --
-// round_up(dim, 8), zero padded, which is also the floats of the staged query.  The distances are the float kernels' on float32(db_h), bit
-// for bit.  L2 with dim % 4 == 0: the half chunk-pair form; else a lane per row (rerank_plan.h: rerank_half_plan).
-struct RerankHalfParams : RerankTopkParams {
-    const uint16_t* db_h;    // [n x dstride] binary16 bit patterns, rows 16-byte aligned
-};
-hipError_t launch_rerank_half(const RerankHalfParams& p, int metric, hipStream_t s);
-hipError_t launch_rerank_topk_half(const RerankHalfParams& p, int metric, hipStream_t s);
+hipError_t launch_rerank_rows(RowKind rows, const RerankRowsParams& p, int metric, hipStream_t s);
+hipError_t launch_rerank_topk_rows(RowKind rows, const RerankRowsParams& p, int metric, hipStream_t s);
 // diagnostic (tests): one batch merge of a sorted list [size] with up to 64 survivor keys (~0 = none)
 hipError_t launch_debug_merge(int regs, const uint64_t* entries, int size, const uint64_t* surv, int ef, uint64_t* out,
                               int* out_size, hipStream_t s);

@@ -14,6 +14,15 @@ static hipError_t set_lds(K kernel, size_t bytes) {
     return hipSuccess;
 }
 
+// the re-rank kernels' launch: a wavefront per query (`p.nq` of them), `lds` bytes of dynamic LDS, `p` the kernel's one argument
+template <typename K, typename P>
+static hipError_t launch_per_query(K kernel, const P& p, size_t lds, hipStream_t s) {
+    const hipError_t e = set_lds(kernel, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(p.nq), dim3(64), lds, s, p);
+    return hipGetLastError();
+}
+
 // One row of a unit's instance table: the instance (walk_plan.h), its kernel, and the kernel's printable name -- taken from the same
 // expression as the pointer, written with every template argument the way the demangler prints it.
 struct WalkEntry {

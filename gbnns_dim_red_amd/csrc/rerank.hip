@@ -60,7 +60,7 @@ __global__ __launch_bounds__(64) void rerank_pair_kernel(RerankParams p) {
     if (lane == 0) p.out[qi] = (win >= 0) ? cand[win] : kInvalidId;
 }
 
-// (the k-answer selection -- TopkLds, topk_select, topk_count -- is rerank_topk.h's, shared with the byte-row kernels of rerank_bytes.hip)
+// (the k-answer selection -- TopkLds, topk_select, topk_count -- is rerank_topk.h's, shared with the narrow-row kernels of rerank_rows.hip)
 
 // a lane per row (d % 8 != 0 for the dot metric, d % 4 != 0 for L2): rerank_kernel's distances
 template <int METRIC>
@@ -115,49 +115,22 @@ __global__ __launch_bounds__(64) void rerank_topk_pair_kernel(RerankTopkParams p
 hipError_t launch_rerank(const RerankParams& p, int metric, hipStream_t s) {
     if (p.nq == 0) return hipSuccess;
     const size_t lds = (size_t)p.dstride * 4;
-    const bool pairs = rerank_plan(metric, p.dim, false).form == RerankForm::Pairs;
-    hipError_t e;
-    if (metric == 1) {
-        if (pairs) {
-            e = set_lds(rerank_pair_kernel<1>, lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((rerank_pair_kernel<1>), dim3(p.nq), dim3(64), lds, s, p);
-        } else {
-            e = set_lds(rerank_kernel<1>, lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((rerank_kernel<1>), dim3(p.nq), dim3(64), lds, s, p);
-        }
-    } else if (pairs) {
-        e = set_lds(rerank_pair_kernel<0>, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((rerank_pair_kernel<0>), dim3(p.nq), dim3(64), lds, s, p);
-    } else {
-        e = set_lds(rerank_kernel<0>, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((rerank_kernel<0>), dim3(p.nq), dim3(64), lds, s, p);
-    }
-    return hipGetLastError();
+    const bool pairs = rerank_plan(metric, p.dim, RowKind::F32).form == RerankForm::Pairs;
+    if (metric == 1) return pairs ? launch_per_query(rerank_pair_kernel<1>, p, lds, s) : launch_per_query(rerank_kernel<1>, p, lds, s);
+    return pairs ? launch_per_query(rerank_pair_kernel<0>, p, lds, s) : launch_per_query(rerank_kernel<0>, p, lds, s);
 }
 
 size_t rerank_topk_lds(uint32_t dstride, uint32_t cand_stride) {
     return (size_t)dstride * 4 + (size_t)rerank_topk_key_slots(cand_stride) * 8 + (size_t)cand_stride * 4;
 }
 
-template <typename K>
-static hipError_t launch_topk(K kernel, const RerankTopkParams& p, size_t lds, hipStream_t s) {
-    const hipError_t e = set_lds(kernel, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3(p.nq), dim3(64), lds, s, p);
-    return hipGetLastError();
-}
-
 hipError_t launch_rerank_topk(const RerankTopkParams& p, int metric, hipStream_t s) {
     if (p.nq == 0) return hipSuccess;
     if (p.k == 0 || p.k > p.cand_stride) return hipErrorInvalidValue;
     const size_t lds = rerank_topk_lds(p.dstride, p.cand_stride);
-    const bool pairs = rerank_plan(metric, p.dim, false).form == RerankForm::Pairs;  // as launch_rerank
-    if (metric == 1) return pairs ? launch_topk(rerank_topk_pair_kernel<1>, p, lds, s) : launch_topk(rerank_topk_kernel<1>, p, lds, s);
-    return pairs ? launch_topk(rerank_topk_pair_kernel<0>, p, lds, s) : launch_topk(rerank_topk_kernel<0>, p, lds, s);
+    const bool pairs = rerank_plan(metric, p.dim, RowKind::F32).form == RerankForm::Pairs;  // as launch_rerank
+    if (metric == 1) return pairs ? launch_per_query(rerank_topk_pair_kernel<1>, p, lds, s) : launch_per_query(rerank_topk_kernel<1>, p, lds, s);
+    return pairs ? launch_per_query(rerank_topk_pair_kernel<0>, p, lds, s) : launch_per_query(rerank_topk_kernel<0>, p, lds, s);
 }
 
 }  // namespace gbnns

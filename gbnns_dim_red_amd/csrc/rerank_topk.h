@@ -1,5 +1,5 @@
 // rerank_topk.h -- the k-answer selection of the stand-alone re-rank kernels (gbnns_rerank_topk / gbnns_search_topk), shared by the float
-// kernels (rerank.hip) and the byte-row kernels (rerank_bytes.hip): the distances differ in where the row comes from, the selection does not.
+// kernels (rerank.hip) and the narrow-row kernels (rerank_rows.hip: uint8 and binary16 rows): the distances differ in where the row comes from, the selection does not.
 #pragma once
 
 #include "walk_common.h"

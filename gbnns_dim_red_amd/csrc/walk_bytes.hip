@@ -3,7 +3,7 @@
 // float32 arithmetic in the reference's order (l2_ordered, walk_common.h), no float copy of the table anywhere.  The kernels here are
 // walk_reg_one / walk_reg_big_one (walk_generic.h) with BYTES set, which changes only where a hop's rows (and the entry row) come from and how
 // the distance consumes them: L2 over rows of d = 128 = eight 16-byte chunks, two lanes per neighbour, the even lane the chunks 0, 2, 4, 6
-// and the odd lane 1, 3, 5, 7 -- four 16-byte loads per lane, all in flight, kept packed (16 registers) until byte_chunk_add widens and
+// and the odd lane 1, 3, 5, 7 -- four 16-byte loads per lane, all in flight, kept packed (16 registers) until chunk_add<U8> widens and
 // consumes them chunk by chunk; the 128-float query lives in LDS and is re-read every hop in the shadow of the row loads.  Visited set,
 // lists, tie list, merge, hand-over and write_results are the float instances'.  There is no byte-walk retry pass: what these hand over goes
 // to the general kernel's byte-walk instance (walk_general.hip), which also takes every flagged batch outside the domain (walk_plan.cpp).

@@ -665,105 +665,6 @@ struct ByteRow4 {
     __device__ __forceinline__ float4 operator[](uint32_t t) const { return bytes4_to_float4(w[t]); }
 };
 
-struct RerankBytesSrc {
-    const float* q;      // [nq x qstride] original-space queries
-    uint32_t qstride;
-    const uint8_t* db;   // [n x bstride] bytes, rows 16-byte aligned
-    uint32_t bstride;    // bytes of a row = floats of the staged query: round_up(dim, 16)
-    uint32_t dim, n;     // dim % 16 == 0 here
-};
-
-// One 16-byte chunk `rv` = four of the reference's 4-wide steps against the query's four float4 `q`, added to the four running sums in order
-// in this lane: the even lane of a pair on top of the odd lane's sums (`u`), then the odd lane on top of the even lane's (`v`).
-__device__ __forceinline__ void byte_chunk_add(const uint4 rv, const float4 (&q)[4], float (&u)[4], float (&v)[4]) {
-    const uint32_t w[4] = {rv.x, rv.y, rv.z, rv.w};
-    float p[4][4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        const float4 f = bytes4_to_float4(w[s]);
-        float e;
-        e = f.x - q[s].x; p[s][0] = e * e;
-        e = f.y - q[s].y; p[s][1] = e * e;
-        e = f.z - q[s].z; p[s][2] = e * e;
-        e = f.w - q[s].w; p[s][3] = e * e;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float x = dpp_swap_pair(v[j]);
-        x = x + p[0][j]; x = x + p[1][j]; x = x + p[2][j]; x = x + p[3][j];
-        u[j] = x;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float x = dpp_swap_pair(u[j]);
-        x = x + p[0][j]; x = x + p[1][j]; x = x + p[2][j]; x = x + p[3][j];
-        v[j] = x;
-    }
-}
-
-// Chunk-pair form (L2, dim % 16 == 0): lanes 2i / 2i+1 share candidate i's row; the even lane takes the 16-byte chunks 0, 2, 4, ..., the odd
-// lane 1, 3, 5, ... -- a pair reads 32 contiguous bytes per load, a 128-byte row is four loads per lane, all four in flight (16 registers
-// against the float core's 32).  The sums hop to the partner once per chunk; with an odd chunk count the last chunk is the even lane's alone
-// (rerank_pairs_core's dim % 8 == 4 trick).  Winner, `id_at` and `sink` as in rerank_pairs_core; the finished sum is the odd lane's.
-template <typename IdAt, typename Sink = RerankNoSink>
-__device__ __forceinline__ int rerank_bytes_core(const RerankBytesSrc& a, uint32_t qi, int cnt, float* qf, int lane, IdAt id_at, Sink sink = Sink{}) {
-    const uint32_t half = (uint32_t)lane & 1u, slot = (uint32_t)lane >> 1;
-    const float4* qs = reinterpret_cast<const float4*>(qf);
-    for (uint32_t i = lane; i < a.bstride; i += 64)
-        qf[i] = (i < a.dim) ? a.q[(size_t)qi * a.qstride + i] : 0.f;
-    wave_sync();
-    const uint32_t chunks = a.dim >> 4, cpairs = chunks >> 1, ctotal = cpairs + (chunks & 1u);
-    uint64_t bestk = ~0ull;
-    for (int base = 0; base < cnt; base += 32) {
-        const int r = base + (int)slot;
-        const bool valid = r < cnt;
-        uint32_t id = id_at(valid ? r : base);  // lanes beyond the list redo the first row (discarded)
-        id = id < a.n ? id : 0u;                // (never dereference an id outside the table)
-        const uint4* row = reinterpret_cast<const uint4*>(a.db + (size_t)id * a.bstride) + half;
-        const float4* qh = qs + 4u * half;       // (a chunk's 16 coordinates are four float4 of the staged query)
-        float u[4], v[4] = {0.f, 0.f, 0.f, 0.f};
-        uint32_t k = 0;
-        for (; k + 4 <= cpairs; k += 4) {  // four 16-B loads in flight per lane
-            uint4 rv[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) rv[j] = row[2 * (k + j)];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float4* qc = qh + 8 * (k + j);
-                const float4 q[4] = {qc[0], qc[1], qc[2], qc[3]};
-                byte_chunk_add(rv[j], q, u, v);
-            }
-        }
-        // (an odd chunk count -- d = 48, 80, 112: the last chunk is the even lane's alone; the odd lane reads nothing and adds +0 to the sums
-        // it takes over, which leaves a sum of squares as it is)
-        for (; k < ctotal; ++k) {
-            const bool mine = k < cpairs || !half;
-            uint4 rv = make_uint4(0u, 0u, 0u, 0u);
-            float4 q[4] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
-            if (mine) {
-                const float4* qc = qh + 8 * k;
-                rv = row[2 * k];
-                q[0] = qc[0]; q[1] = qc[1]; q[2] = qc[2]; q[3] = qc[3];
-            }
-            byte_chunk_add(rv, q, u, v);
-        }
-        const float dv = ((v[0] + v[1]) + v[2]) + v[3];
-        if (valid && half) {
-            sink(r, dv);
-            const uint64_t kv = ((uint64_t)fkey(dv) << 32) | (uint32_t)r;
-            bestk = kv < bestk ? kv : bestk;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint64_t o = shfl_u64(bestk, lane ^ off);
-        bestk = o < bestk ? o : bestk;
-    }
-    bestk = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(bestk >> 32)) << 32) |
-            (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bestk);
-    return (cnt > 0 && bestk != ~0ull) ? (int)(uint32_t)(bestk & 0xFFFFFFFFu) : -1;
-}
-
 // ------------------------------------------------------------------------------------------
 // re-rank over binary16 rows (gbnns_index_create_half_base): the original-space table holds IEEE binary16 coordinates, rows of
 // round_up(d, 8) halves, zero padded.  Every binary16 value -- subnormals, both zeros, +-65 504 -- is a binary32 value, so widening
@@ -786,21 +687,62 @@ struct HalfRow4 {
     }
 };
 
-struct RerankHalfSrc {
-    const float* q;      // [nq x qstride] original-space queries
-    uint32_t qstride;
-    const uint16_t* db;  // [n x hstride] binary16 bit patterns, rows 16-byte aligned
-    uint32_t hstride;    // halves of a row = floats of the staged query: round_up(dim, 8)
-    uint32_t dim, n;     // dim % 4 == 0 here
+// ------------------------------------------------------------------------------------------
+// the two narrow row kinds (row_kind.h: U8, F16) as the re-rank and the walks read them: what differs between them, stated once
+// ------------------------------------------------------------------------------------------
+template <RowKind K>
+struct NarrowRow;
+template <>
+struct NarrowRow<RowKind::U8> {
+    using Elem = uint8_t;
+    using Row4 = ByteRow4;  // the lane-per-row adapter
+    static constexpr uint32_t kChunkElems = row_pad_elems(RowKind::U8), kSteps = kChunkElems / 4;  // a 16-byte chunk: 16 bytes, four 4-wide steps
+    // chunk_add widens a step right before it consumes it (U8) or the whole chunk ahead of the first step (F16): the same values either way;
+    // each kind keeps the order its kernels were scheduled and timed with (the other order costs the byte pair kernels seven vector registers
+    // and moves the half walk's instructions)
+    static constexpr bool kWidenAhead = false;
+    // step `s` of chunk `rv`, widened
+    static __device__ __forceinline__ float4 step(const uint4& rv, int s) {
+        const uint32_t w[4] = {rv.x, rv.y, rv.z, rv.w};
+        return bytes4_to_float4(w[s]);
+    }
+    static __device__ __forceinline__ Row4 row4(const Elem* row) { return {reinterpret_cast<const uint32_t*>(row)}; }
+};
+template <>
+struct NarrowRow<RowKind::F16> {
+    using Elem = uint16_t;
+    using Row4 = HalfRow4;
+    static constexpr uint32_t kChunkElems = row_pad_elems(RowKind::F16), kSteps = kChunkElems / 4;  // eight halves, two 4-wide steps
+    static constexpr bool kWidenAhead = true;
+    static __device__ __forceinline__ float4 step(const uint4& rv, int s) {
+        const uint32_t w[4] = {rv.x, rv.y, rv.z, rv.w};
+        return halves4_to_float4(w[2 * s], w[2 * s + 1]);
+    }
+    static __device__ __forceinline__ Row4 row4(const Elem* row) { return {reinterpret_cast<const uint2*>(row)}; }
 };
 
-// One 16-byte chunk `rv` = two of the reference's 4-wide steps against the query's two float4 `q`, added to the four running sums in order in
-// this lane: the even lane of a pair on top of the odd lane's sums (`u`), then the odd lane on top of the even lane's (`v`).
-__device__ __forceinline__ void half_chunk_add(const uint4 rv, const float4 (&q)[2], float (&u)[4], float (&v)[4]) {
-    const float4 f[2] = {halves4_to_float4(rv.x, rv.y), halves4_to_float4(rv.z, rv.w)};
-    float p[2][4];
+struct RerankRowsSrc {
+    const float* q;      // [nq x qstride] original-space queries
+    uint32_t qstride;
+    const void* db;      // [n x stride] elements of the kind, rows 16-byte aligned
+    uint32_t stride;     // elements of a row = floats of the staged query: row_pad(dim, kind)
+    uint32_t dim, n;     // dim % 16 == 0 (U8: stride == dim) / dim % 4 == 0 (F16) here
+};
+
+// One 16-byte chunk `rv` = kSteps of the reference's 4-wide steps against the query's float4 `q`, added to the four running sums in order
+// in this lane: the even lane of a pair on top of the odd lane's sums (`u`), then the odd lane on top of the even lane's (`v`).
+template <RowKind K>
+__device__ __forceinline__ void chunk_add(const uint4 rv, const float4 (&q)[NarrowRow<K>::kSteps], float (&u)[4], float (&v)[4]) {
+    constexpr int S = NarrowRow<K>::kSteps;
+    float4 f[S];
+    if constexpr (NarrowRow<K>::kWidenAhead) {
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
+        for (int s = 0; s < S; ++s) f[s] = NarrowRow<K>::step(rv, s);
+    }
+    float p[S][4];
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        if constexpr (!NarrowRow<K>::kWidenAhead) f[s] = NarrowRow<K>::step(rv, s);
         float e;
         e = f[s].x - q[s].x; p[s][0] = e * e;
         e = f[s].y - q[s].y; p[s][1] = e * e;
@@ -810,78 +752,84 @@ __device__ __forceinline__ void half_chunk_add(const uint4 rv, const float4 (&q)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         float x = dpp_swap_pair(v[j]);
-        x = x + p[0][j]; x = x + p[1][j];
+#pragma unroll
+        for (int s = 0; s < S; ++s) x = x + p[s][j];
         u[j] = x;
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         float x = dpp_swap_pair(u[j]);
-        x = x + p[0][j]; x = x + p[1][j];
+#pragma unroll
+        for (int s = 0; s < S; ++s) x = x + p[s][j];
         v[j] = x;
     }
 }
 
-// Chunk-pair form (L2, dim % 4 == 0): lanes 2i / 2i+1 share candidate i's row; the even lane takes the 16-byte chunks 0, 2, 4, ..., the odd
-// lane 1, 3, 5, ... -- a pair reads 32 contiguous bytes per load.  The sums hop to the partner once per chunk; with an odd chunk count the
-// last chunk is the even lane's alone (rerank_bytes_core's trick).  DEEP: 16-byte loads a lane has in flight in the first loop of the ladder
-// (rerank_plan.h: rerank_half_deep; 4 * DEEP registers hold the packed row), then four at a time, then one.  Winner, `id_at` and `sink` as in
-// rerank_pairs_core; the finished sum is the odd lane's.
-template <int DEEP, typename IdAt, typename Sink = RerankNoSink>
-__device__ __forceinline__ int rerank_half_core(const RerankHalfSrc& a, uint32_t qi, int cnt, float* qf, int lane, IdAt id_at, Sink sink = Sink{}) {
+// Rounds of N chunk pairs from pair `k` on, while N are left: N 16-byte loads in flight per lane (4 * N registers hold the packed row), then
+// their sums in order.  `row`: this lane's first chunk; `qh`: its float4 of the staged query (a chunk pair is 2 * kSteps of them).
+template <RowKind K, int N>
+__device__ __forceinline__ void chunk_rounds(const uint4* row, const float4* qh, uint32_t& k, uint32_t cpairs, float (&u)[4], float (&v)[4]) {
+    constexpr int S = NarrowRow<K>::kSteps;
+    for (; k + N <= cpairs; k += N) {
+        uint4 rv[N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) rv[j] = row[2 * (k + j)];
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const float4* qc = qh + 2 * S * (k + j);
+            float4 q[S];
+#pragma unroll
+            for (int s = 0; s < S; ++s) q[s] = qc[s];
+            chunk_add<K>(rv[j], q, u, v);
+        }
+    }
+}
+
+// Chunk-pair form (L2; U8: dim % 16 == 0, F16: dim % 4 == 0): lanes 2i / 2i+1 share candidate i's row; the even lane takes the 16-byte
+// chunks 0, 2, 4, ..., the odd lane 1, 3, 5, ... -- a pair reads 32 contiguous bytes per load.  The sums hop to the partner once per chunk;
+// with an odd chunk count the last chunk is the even lane's alone (rerank_pairs_core's dim % 8 == 4 trick).  DEEP: 16-byte loads a lane has
+// in flight in the first loop of the ladder (rerank_plan.h: 4 for U8 -- a 128-byte row is four loads per lane, 16 registers against the
+// float core's 32 -- and rerank_half_deep for F16), then four at a time, then one.  Winner, `id_at` and `sink` as in rerank_pairs_core; the
+// finished sum is the odd lane's.
+template <RowKind K, int DEEP, typename IdAt, typename Sink = RerankNoSink>
+__device__ __forceinline__ int rerank_chunk_core(const RerankRowsSrc& a, uint32_t qi, int cnt, float* qf, int lane, IdAt id_at, Sink sink = Sink{}) {
+    using Row = NarrowRow<K>;
+    constexpr int S = Row::kSteps;
     const uint32_t half = (uint32_t)lane & 1u, slot = (uint32_t)lane >> 1;
     const float4* qs = reinterpret_cast<const float4*>(qf);
-    // (dim % 8 == 4 -- glove's 300, rows of 304 halves: the last chunk's second 4-wide step is the row's zero padding against the zeros staged
-    // here; (0 - 0)^2 = +0 added to a sum of squares leaves it as it is)
-    for (uint32_t i = lane; i < a.hstride; i += 64)
+    // (F16, dim % 8 == 4 -- glove's 300, rows of 304 halves: the last chunk's second 4-wide step is the row's zero padding against the zeros
+    // staged here; (0 - 0)^2 = +0 added to a sum of squares leaves it as it is)
+    for (uint32_t i = lane; i < a.stride; i += 64)
         qf[i] = (i < a.dim) ? a.q[(size_t)qi * a.qstride + i] : 0.f;
     wave_sync();
-    const uint32_t chunks = a.hstride >> 3, cpairs = chunks >> 1, ctotal = cpairs + (chunks & 1u);
+    const uint32_t chunks = a.stride / Row::kChunkElems, cpairs = chunks >> 1, ctotal = cpairs + (chunks & 1u);
     uint64_t bestk = ~0ull;
     for (int base = 0; base < cnt; base += 32) {
         const int r = base + (int)slot;
         const bool valid = r < cnt;
         uint32_t id = id_at(valid ? r : base);  // lanes beyond the list redo the first row (discarded)
         id = id < a.n ? id : 0u;                // (never dereference an id outside the table)
-        const uint4* row = reinterpret_cast<const uint4*>(a.db + (size_t)id * a.hstride) + half;
-        const float4* qh = qs + 2u * half;       // (a chunk's 8 coordinates are two float4 of the staged query)
+        const uint4* row = reinterpret_cast<const uint4*>(static_cast<const typename Row::Elem*>(a.db) + (size_t)id * a.stride) + half;
+        const float4* qh = qs + (uint32_t)S * half;  // (a chunk's coordinates are kSteps float4 of the staged query)
         float u[4], v[4] = {0.f, 0.f, 0.f, 0.f};
         uint32_t k = 0;
-        if constexpr (DEEP > 4) {
-            for (; k + DEEP <= cpairs; k += DEEP) {  // DEEP 16-B loads in flight per lane
-                uint4 rv[DEEP];
-#pragma unroll
-                for (int j = 0; j < DEEP; ++j) rv[j] = row[2 * (k + j)];
-#pragma unroll
-                for (int j = 0; j < DEEP; ++j) {
-                    const float4* qc = qh + 4 * (k + j);
-                    const float4 q[2] = {qc[0], qc[1]};
-                    half_chunk_add(rv[j], q, u, v);
-                }
-            }
-        }
-        for (; k + 4 <= cpairs; k += 4) {  // four 16-B loads in flight per lane
-            uint4 rv[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) rv[j] = row[2 * (k + j)];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float4* qc = qh + 4 * (k + j);
-                const float4 q[2] = {qc[0], qc[1]};
-                half_chunk_add(rv[j], q, u, v);
-            }
-        }
-        // (an odd chunk count -- d = 8, 40: the last chunk is the even lane's alone; the odd lane reads nothing and adds +0 to the sums it takes
-        // over, which leaves a sum of squares as it is)
+        if constexpr (DEEP > 4) chunk_rounds<K, DEEP>(row, qh, k, cpairs, u, v);
+        chunk_rounds<K, 4>(row, qh, k, cpairs, u, v);
+        // (an odd chunk count -- U8: d = 48, 80, 112; F16: d = 8, 40: the last chunk is the even lane's alone; the odd lane reads nothing and adds
+        // +0 to the sums it takes over, which leaves a sum of squares as it is)
         for (; k < ctotal; ++k) {
             const bool mine = k < cpairs || !half;
             uint4 rv = make_uint4(0u, 0u, 0u, 0u);
-            float4 q[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
+            float4 q[S];
+#pragma unroll
+            for (int s = 0; s < S; ++s) q[s] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (mine) {
-                const float4* qc = qh + 4 * k;
+                const float4* qc = qh + 2 * S * k;
                 rv = row[2 * k];
-                q[0] = qc[0]; q[1] = qc[1];
+#pragma unroll
+                for (int s = 0; s < S; ++s) q[s] = qc[s];
             }
-            half_chunk_add(rv, q, u, v);
+            chunk_add<K>(rv, q, u, v);
         }
         const float dv = ((v[0] + v[1]) + v[2]) + v[3];
         if (valid && half) {
@@ -909,9 +857,9 @@ template <int DEEP = 8, bool BYTES = false, typename IdAtRank>
 __device__ __forceinline__ void fused_rerank(const WalkParams& p, uint32_t qi, int kept, unsigned char* smem, int lane,
                                              IdAtRank id_at_rank) {
     if constexpr (BYTES) {
-        const RerankBytesSrc b{p.rr_q, p.rr_qstride, p.rr_db_b, p.rr_dstride, p.rr_dim, p.rr_n};
+        const RerankRowsSrc b{p.rr_q, p.rr_qstride, p.rr_db_b, p.rr_dstride, p.rr_dim, p.rr_n};
         wave_sync();  // every lane is done with the walk's LDS
-        const int won = rerank_bytes_core(b, qi, kept, reinterpret_cast<float*>(smem), lane, [&](int r) { return id_at_rank(kept - 1 - r); });
+        const int won = rerank_chunk_core<RowKind::U8, 4>(b, qi, kept, reinterpret_cast<float*>(smem), lane, [&](int r) { return id_at_rank(kept - 1 - r); });
         const uint32_t best = id_at_rank(won >= 0 ? kept - 1 - won : 0);
         if (lane == 0) p.rr_out[qi] = won >= 0 ? best : kInvalidId;
         return;

@@ -28,7 +28,7 @@ __device__ __forceinline__ void keep_rows(const RowRegs<STEPS>& r) {
 
 // BYTES (GBNNS_FLAG_BYTE_WALK, walk_bytes.hip): a lane's share of a 128-byte uint8 row -- the even lane of a pair holds the 16-byte chunks
 // 0, 2, 4, 6, the odd lane 1, 3, 5, 7, packed as loaded (load_row_alt's pieces: 16 registers) -- against the query's float4 pieces in LDS
-// (`qh` = the staged query + 4 * half float4).  byte_chunk_add (walk_common.h) widens and consumes a chunk at a time; the sums hop to the
+// (`qh` = the staged query + 4 * half float4).  chunk_add<RowKind::U8> (walk_common.h) widens and consumes a chunk at a time; the sums hop to the
 // partner once per chunk, the finished sum of squares is the odd lane's: l2_ordered on float32(row), operation for operation.
 __device__ __forceinline__ float l2_pair_from_bytes(const RowRegs<4>& r, const float4* qh) {
     float u[4], v[4] = {0.f, 0.f, 0.f, 0.f};
@@ -36,7 +36,7 @@ __device__ __forceinline__ float l2_pair_from_bytes(const RowRegs<4>& r, const f
     for (int j = 0; j < 4; ++j) {
         const float4* qc = qh + 8 * j;
         const float4 q[4] = {qc[0], qc[1], qc[2], qc[3]};
-        byte_chunk_add(make_uint4(__float_as_uint(r.v[j].x), __float_as_uint(r.v[j].y), __float_as_uint(r.v[j].z), __float_as_uint(r.v[j].w)), q, u, v);
+        chunk_add<RowKind::U8>(make_uint4(__float_as_uint(r.v[j].x), __float_as_uint(r.v[j].y), __float_as_uint(r.v[j].z), __float_as_uint(r.v[j].w)), q, u, v);
     }
     return ((v[0] + v[1]) + v[2]) + v[3];
 }

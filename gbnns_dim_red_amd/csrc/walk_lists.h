@@ -368,7 +368,7 @@ __device__ __forceinline__ uint32_t nth_set_bit(uint64_t m, uint32_t n) {
 }
 
 // The half form of l2_quad_rows (GBNNS_FLAG_HALF_WALK, walk_half_base.hip: the run-time-length instances over a half-base handle's rows, d >= 128,
-// d % 4 == 0) on the chunk-pair arithmetic of rerank_half_core (half_chunk_add, walk_common.h): two lanes share a row, 32 new rows per
+// d % 4 == 0) on the chunk-pair arithmetic of rerank_chunk_core (chunk_add<RowKind::F16>, walk_common.h): two lanes share a row, 32 new rows per
 // round -- pair i takes the i-th of the round's rows; the even lane reads the 16-byte chunks 0, 2, 4, ... of the row of `hstride` halves,
 // the odd lane 1, 3, 5, ... (a pair reads 32 contiguous bytes per load), the running sums hop to the partner once per chunk, an odd chunk
 // count leaves the last chunk to the even lane, and a d % 8 == 4 row's last half-chunk is the row's zero padding against the zeros staged
@@ -399,7 +399,7 @@ __device__ __forceinline__ float l2_pair_rows_half(uint64_t mfresh, uint32_t nb,
             for (int j = 0; j < 8; ++j) {
                 const float4* qc = qh + 4 * (k + j);
                 const float4 q[2] = {qc[0], qc[1]};
-                half_chunk_add(rv[j], q, u, v);
+                chunk_add<RowKind::F16>(rv[j], q, u, v);
             }
         }
         for (; k + 4 <= cpairs; k += 4) {
@@ -410,7 +410,7 @@ __device__ __forceinline__ float l2_pair_rows_half(uint64_t mfresh, uint32_t nb,
             for (int j = 0; j < 4; ++j) {
                 const float4* qc = qh + 4 * (k + j);
                 const float4 q[2] = {qc[0], qc[1]};
-                half_chunk_add(rv[j], q, u, v);
+                chunk_add<RowKind::F16>(rv[j], q, u, v);
             }
         }
         if (k < ctotal) {
@@ -426,7 +426,7 @@ __device__ __forceinline__ float l2_pair_rows_half(uint64_t mfresh, uint32_t nb,
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                if (k + j < ctotal) half_chunk_add(rv[j], q[j], u, v);
+                if (k + j < ctotal) chunk_add<RowKind::F16>(rv[j], q[j], u, v);
         }
         const float dv = ((v[0] + v[1]) + v[2]) + v[3];  // (the odd lane's is the row's)
         const float dr = __int_as_float(__builtin_amdgcn_ds_bpermute((int)((2u * rank + 1u) << 2), __float_as_int(dv)));

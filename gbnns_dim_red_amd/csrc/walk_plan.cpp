@@ -160,7 +160,7 @@ WalkPlan plan_walk(const WalkParams& p, int metric, WalkPass pass, const WalkEnv
         if (hot) k = {WalkFamily::Hot, metric, 0, regs, flag_if(one, kOne) | flag_if(regs == 1 && metric == 0 && one && p.spec_rows && !GBNNS_HOT1_SPEC, kSpec)};
         // a byte handle (gbnns_index_create_bytes) that wants its re-rank fused: where walk_hot_kernel / walk_hot2_kernel serve -- not the
         // speculative-rows instance, not walk_hotw*, not the two-list form -- and the chunk-pair core serves the rows (L2, d % 16 == 0), their
-        // byte twins; every other first pass of such a handle runs unfused, followed by the stand-alone byte kernel (rerank_bytes.hip)
+        // byte twins; every other first pass of such a handle runs unfused, followed by the stand-alone byte kernel (rerank_rows.hip)
         if (hot) k.flags |= flag_if(p.bytes_dim != 0u && p.bytes_dim % 16u == 0u && metric == 0 && regs <= 2 && one && !(k.flags & kSpec), kRrBytes);
         else if (pl.coop_serves) k = {WalkFamily::Coop, 0, (int)rows / 4, 0, flag_if(late, kLate)};
         return pl;

@@ -134,7 +134,7 @@ int gbnns_index_is_bytes(const gbnns_index* index);   /* 1: created by gbnns_ind
  * included: it is orthogonal), gbnns_search_topk, gbnns_search_tagged (with and without GBNNS_FLAG_TAG_BRIDGE), gbnns_rerank,
  * gbnns_rerank_topk, gbnns_project, gbnns_index_tag_census, several entry points, the auxiliary graph, HOST or DEVICE buffers, batches in
  * flight.  Every search runs the very first-pass kernel a float handle runs under GBNNS_FLAG_NO_FUSED_RERANK, and the stand-alone half
- * re-rank (rerank_half.hip; gbnns_debug_half_base_plan tells which kernel) follows on the same stream.
+ * re-rank (rerank_rows.hip; gbnns_debug_half_base_plan tells which kernel) follows on the same stream.
  * With GBNNS_FLAG_HALF_WALK (below), gbnns_search_ex and gbnns_search_tagged also run in GBNNS_MODE_PLAIN, which walks the binary16 rows themselves.
  * Refused: GBNNS_MODE_PLAIN without that flag (GBNNS_ERR_UNSUPPORTED: there is no float table to walk), gbnns_index_exact_knn, gbnns_index_exact_knn_gather and
  * gbnns_search_tagged_auto (GBNNS_ERR_UNSUPPORTED: they scan the resident table), GBNNS_FLAG_BYTE_WALK and gbnns_search_byte_queries

@@ -65,7 +65,7 @@ def trace_dot_lane(d):
 
 
 def trace_byte_pairs(d):
-    """rerank_bytes_core: `chunks` 16-byte chunks, pairs of them four at a time, the leftover pairs, the even lane's lone chunk."""
+    """rerank_chunk_core: `chunks` 16-byte chunks, pairs of them four at a time, the leftover pairs, the even lane's lone chunk."""
     chunks = d >> 4
     cpairs = chunks >> 1
     return {"four": cpairs // 4, "rest": cpairs % 4, "odd_chunk": chunks & 1}

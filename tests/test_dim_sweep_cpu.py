@@ -73,7 +73,7 @@ def test_rerank_plan_reports_the_one_choice(g):
     short = C.create_string_buffer(8)
     assert lib.gbnns_debug_rerank_plan(*ok, short, 8, C.byref(deep), C.byref(fused)) == 0 and short.value == b"rerank_"
     # one place: the launchers, the pair kernels and the search call's plan call rerank_plan(); no other unit spells the rule
-    for unit, calls in (("rerank.hip", 2), ("rerank_bytes.hip", 2), ("call_plan.cpp", 2), ("search_core.cpp", 0), ("handle.cpp", 1)):
+    for unit, calls in (("rerank.hip", 2), ("rerank_rows.hip", 1), ("call_plan.cpp", 1), ("search_core.cpp", 0), ("handle.cpp", 1)):
         assert len(re.findall(r"(?<!\w)rerank_plan\(", _src(unit))) == calls, unit
     assert _src("rerank.hip").count("rerank_pairs_deep(METRIC, p.dim) == 24") == 2    # (the pair kernels: DEEP of a length already in the pair form)
     for unit in sorted(os.listdir(CSRC)):
@@ -81,6 +81,28 @@ def test_rerank_plan_reports_the_one_choice(g):
             text = _src(unit)
             assert "kRerankDeepMinDim" not in text and "dim >= 384" not in text and "rerank_bytes_pair_form" not in text, unit
             assert not re.search(r"% 8 == 0 \|\| \(.*% 4 == 0", text), unit
+
+
+def test_rerank_plan_grid_is_the_recorded_one(g):
+    """tests/golden/rerank_plan_grid.txt: (metric, d, kind) -> (name, deep, fused) for both metrics, d = 0 .. 1100 and the three row kinds, as
+    gbnns_debug_rerank_plan (f32, u8) and gbnns_debug_half_base_plan (f16) reported it in a build of the commit before rerank_plan took the row
+    kind ('refused': the call's error return, at d = 0) -- per (metric, kind) a digest of the 1101 answers and the distinct answers among
+    them, as tests/golden/walk_plan_grid.txt keeps its grid.  The built library reproduces it line for line."""
+    with open(os.path.join(ROOT, "tests", "golden", "rerank_plan_grid.txt")) as f:
+        want = [line.rstrip("\n") for line in f if not line.startswith("#")]
+    got = []
+    for metric in (0, 1):
+        for kind in ("f32", "u8", "f16"):
+            answers, digest = [], 0xcbf29ce484222325   # FNV-1a, 64 bits, over the lines "<d> <answer>\n"
+            for d in range(1101):
+                try:
+                    answers.append("%s %d %d" % (g.half_base_plan(metric, d) if kind == "f16" else g.rerank_plan(metric, d, bytes=kind == "u8")))
+                except g.GbnnsError:
+                    answers.append("refused")
+                for byte in ("%d %s\n" % (d, answers[-1])).encode():
+                    digest = ((digest ^ byte) * 0x100000001b3) & 0xFFFFFFFFFFFFFFFF
+            got.append("%d %s | %d | %016x | %s" % (metric, kind, len(answers), digest, "; ".join(sorted(set(answers)))))
+    assert got == want, [pair for pair in zip(got, want) if pair[0] != pair[1]]
 
 
 def test_device_side_thresholds_are_the_sources(g):

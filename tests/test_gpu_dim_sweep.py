@@ -117,7 +117,7 @@ def test_float_rerank_at_every_length(g, orc):
 
 # ---- 2. the stand-alone re-rank over byte rows ---------------------------------------------------------------------------------------
 def test_byte_rerank_at_every_length(g, orc):
-    """The same on a byte handle: uint8 rows against the widened table, every length, both metrics -- rerank_bytes_core (its 4-chunk-pair
+    """The same on a byte handle: uint8 rows against the widened table, every length, both metrics -- rerank_chunk_core (its 4-chunk-pair
     loop followed by leftover pairs and an odd chunk: d = 176; one pair alone: d = 32) and the lane-per-row form through ByteRow4.  Where the
     plan function names the chunk-pair form, the same on dim_sweep.byte_contest's equal-distance rows."""
     off, nbr = ds.graph()

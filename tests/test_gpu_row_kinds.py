@@ -95,3 +95,50 @@ def test_three_kinds_answer_alike(g, d, metric):
     for ix, _, _ in handles:
         ix.close()
     assert not failures, failures
+
+
+# The stand-alone re-rank of the three kinds.  Row lengths at which every rung of the one chunk-pair core (rerank_chunk_core) runs for both
+# narrow kinds -- uint8 rows / binary16 rows:
+#   8    a lane per row / one chunk, the even lane's alone            12   a lane per row / a half-padded chunk
+#   16   one chunk / one chunk pair, no rung                          48   three chunks, odd tail / six chunks, single loads
+#   128  one four-load round / two four-load rounds
+#   440  a lane per row / 55 chunks: DEEP round, four-load round, three single loads, odd tail
+#   464  29 chunks: three four-load rounds, two single loads, odd tail / 58 chunks: DEEP round, two four-load rounds, one single load
+RERANK_DIMS = (8, 12, 16, 48, 128, 440, 464)
+RERANK_COUNTS = (0, 1, 33, 200)
+
+
+@pytest.mark.parametrize("metric", (0, 1))
+@pytest.mark.parametrize("d", RERANK_DIMS)
+def test_three_kinds_rerank_alike(g, orc, d, metric):
+    """gbnns_rerank and gbnns_rerank_topk (k = 10) on three handles over one integer table, lists of 0, 1, 33 and 200 candidates in one batch:
+    the byte and the half-base handle answer what the float handle answers, and that is the CPU oracle's answer on the widened table -- ids,
+    and distances as bit patterns, no tolerance.  Every candidate id is a row of the table."""
+    rng = tu.rng_of(11300 + 2 * d + metric)
+    base = rng.integers(0, 256, size=(N, d)).astype(np.uint8)
+    wide, half = bu.wide(base), base.astype(np.float16)
+    assert np.array_equal(hb.wide(half), wide)   # exact in all three kinds
+    if metric == 0:   # the forms the lengths were chosen for
+        assert (g.rerank_plan(0, d, bytes=True)[0] == "rerank_bytes_pair_kernel") == (d % 16 == 0)
+        assert g.half_base_plan(0, d)[:2] == ("rerank_half_pair_kernel", 20 if d >= 384 else 4)
+    off, nbr = datagen.random_graph(rng, N, 2, 8)
+    db_low = datagen.full_mantissa(rng, N, D_LOW)
+    count = np.repeat(np.array(RERANK_COUNTS, np.int32), 2)
+    q = np.ascontiguousarray(wide[rng.integers(0, N, size=len(count))] + datagen.full_mantissa(rng, len(count), d))
+    cand = rng.integers(0, N, size=(len(count), max(RERANK_COUNTS))).astype(np.uint32)
+    want_ids, want_dd = tu.expected_topk(tu.list_distances(orc, wide, q, cand, count, metric), cand, count, K)
+    some = count > 0   # (the oracle's getRealNearest reads the first id of a list)
+    assert np.array_equal(want_ids[some, 0], orc.rerank(q[some], cand[some], count[some], wide, metric=metric, threads=4))
+    failures = []
+    for table, kind in ((wide, "float"), (base, "byte"), (half, "half")):
+        ix = g.Index(table, off, nbr, db_low=db_low, metric=metric)
+        best = ix.rerank(q, cand, count)
+        ids, dd = ix.rerank_topk(q, cand, K, count)
+        ix.close()
+        if not np.array_equal(best, want_ids[:, 0]):
+            failures.append((kind, "rerank ids"))
+        if not np.array_equal(ids, want_ids):
+            failures.append((kind, "top-10 ids"))
+        if dd.view(np.uint32).tobytes() != want_dd.view(np.uint32).tobytes():
+            failures.append((kind, "top-10 distance bits"))
+    assert not failures, failures

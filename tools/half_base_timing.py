@@ -24,7 +24,7 @@ half-base handle is slower says so, with the ratio.
 
     python tools/half_base_timing.py [--cache-dir DIR] [--only deep,gist,glove] [--n N] [--standalone-only] [--out FILE]
 
---standalone-only: the rerank_ms rows alone (the ladder-depth experiment: one run per build of csrc/rerank_half.hip with
+--standalone-only: the rerank_ms rows alone (the ladder-depth experiment: one run per build of csrc/rerank_rows.hip with
 -DGBNNS_HALF_RERANK_DEEP=<depth>, on the gist row; half_base_plan reports the depth of the library that ran).
 """
 import argparse
