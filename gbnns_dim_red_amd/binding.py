@@ -53,6 +53,7 @@ SYMBOLS = [
     "gbnns_debug_rerank_plan",
     "gbnns_index_create_half_base", "gbnns_index_is_half_base", "gbnns_debug_half_base_plan",
     "gbnns_debug_half_walk_plan",
+    "gbnns_exact_knn_half", "gbnns_index_exact_knn_half", "gbnns_debug_knn_half_plan",
 ]
 
 
@@ -165,6 +166,10 @@ def load_library():
     lib.gbnns_index_exact_knn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_int, C.c_void_p]
     lib.gbnns_index_exact_knn_gather.argtypes = lib.gbnns_index_exact_knn.argtypes
+    lib.gbnns_exact_knn_half.argtypes = lib.gbnns_exact_knn_tagged.argtypes
+    lib.gbnns_index_exact_knn_half.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.gbnns_debug_knn_half_plan.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_char_p, C.c_uint32,
+                                              C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.gbnns_debug_gather_plan.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.gbnns_debug_gather_schedule.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -431,6 +436,19 @@ def knn_plan(bytes, metric, n, n_q, d, k, tagged=False):
     return name.value.decode(), bool(pool.value)
 
 
+def knn_half_plan(n, n_q, d, k, metric=METRIC_L2, stride=0, tagged=False):
+    """gbnns_debug_knn_half_plan (no device needed): what exact_knn does with a float16 base of that shape under the current knn_filter /
+    knn_pool_min_k knobs -- dict(kernel, path, pool, packed): the kernel that sweeps the rows, path "filter" / "pool" (the f16 matrix-core
+    sweep in front of heaps / pools) or "scan", and whether the sweep reads a copy of the table (stride, the halves between rows -- 0: d --,
+    is no multiple of 8) or the table in place."""
+    name = C.create_string_buffer(128)
+    pool, packed = C.c_int(0), C.c_int(0)
+    _check(load_library().gbnns_debug_knn_half_plan(metric, n, n_q, d, stride, k, int(bool(tagged)), name, 128, C.byref(pool), C.byref(packed)))
+    kernel = name.value.decode()
+    path = "scan" if kernel.startswith("knn_scan") else ("pool" if pool.value else "filter")
+    return {"kernel": kernel, "path": path, "pool": bool(pool.value), "packed": bool(packed.value)}
+
+
 def project_plan(d, d_hidden, d_low, n_q, cus=256, in_flight=False, mfma=False, mlp_net=1, mlp_slab=1, mlp_small=4096):
     """gbnns_debug_project_plan (no device needed): the names of the kernel instances the projection of an n_q-query batch through the net
     d -> d_hidden -> d_hidden -> d_low launches on a device of `cus` compute units, in launch order, template arguments as in the source;
@@ -606,11 +624,17 @@ def exact_knn(base, queries, k, metric=METRIC_L2, self_offset=-1, want_dist=Fals
     bit, on the int8 matrix cores and without a float copy (d <= 256, k <= 4096).
     row_tags [n] and query_tags [n_q] (both or neither; numpy uint32, or int32 tensors beside device inputs): gbnns_exact_knn_tagged /
     gbnns_exact_knn_bytes_tagged -- the same lists over the rows j with (row_tags[j] & query_tags[i]) != 0 only, under their original ids;
-    0xFFFFFFFF / +inf where fewer than k rows are allowed."""
+    0xFFFFFFFF / +inf where fewer than k rows are allowed.
+    base float16 with float32 queries (numpy or torch): gbnns_exact_knn_half -- the same answer as over base.astype(float32), bit for bit,
+    with the rows swept as they are on the f16 matrix cores (knn_half_plan() tells the path); tags as above.  float16 queries: TypeError
+    (the query is never rounded)."""
     lib = load_library()
     dev = _is_dev(base)
     if _is_dev(queries) != dev:
         raise TypeError("base and queries must live in the same memory kind")
+    if _is_f16(queries):
+        raise TypeError("float16 queries: exact_knn takes float32 queries (beside a float16 base too -- the query is never rounded)")
+    f16 = _is_f16(base)
     u8 = _is_u8(base)
     if _is_u8(queries) != u8:
         raise TypeError("base and queries must both be uint8 (gbnns_exact_knn_bytes: byte rows against byte queries) or both be float "
@@ -618,11 +642,13 @@ def exact_knn(base, queries, k, metric=METRIC_L2, self_offset=-1, want_dist=Fals
     tagged = row_tags is not None
     if (query_tags is not None) != tagged:
         raise TypeError("row_tags and query_tags: both or neither")
-    if tagged:
+    if f16:
+        fn = lib.gbnns_exact_knn_half
+    elif tagged:
         fn = lib.gbnns_exact_knn_bytes_tagged if u8 else lib.gbnns_exact_knn_tagged
     else:
         fn = lib.gbnns_exact_knn_bytes if u8 else lib.gbnns_exact_knn
-    base = _prep(base, np.uint8, "uint8") if u8 else _prep(base, np.float32, "float32")
+    base = _prep(base, np.uint8, "uint8") if u8 else (_prep(base, np.float16, "float16") if f16 else _prep(base, np.float32, "float32"))
     queries = _prep(queries, np.uint8, "uint8") if u8 else _prep(queries, np.float32, "float32")
     n, d = int(base.shape[0]), int(base.shape[1])
     nq = int(queries.shape[0])
@@ -642,7 +668,7 @@ def exact_knn(base, queries, k, metric=METRIC_L2, self_offset=-1, want_dist=Fals
         ids = np.empty((nq, k), np.uint32)
         dist = np.empty((nq, k), np.float32) if want_dist else None
         sptr = None
-    tag_args = (_ptr(row_tags), _ptr(query_tags)) if tagged else ()
+    tag_args = (_ptr(row_tags), _ptr(query_tags)) if tagged else ((None, None) if f16 else ())
     _check(fn(device, _ptr(base), n, _ptr(queries), nq, d, k, metric, self_offset, *tag_args, _ptr(ids),
               _ptr(dist), MEM_DEVICE if dev else MEM_HOST, sptr))
     return (ids, dist) if want_dist else ids
@@ -757,7 +783,7 @@ class Index:
     every search, rerank and rerank_topk returns what the index over db.astype(float32) returns, bit for bit; needs db_low, no MODE_PLAIN.
     db of dtype float16 (numpy or torch): a half-base handle (gbnns_index_create_half_base) -- the original-space table stays IEEE binary16 on
     the device, half the bytes of the float32 table, and every search, rerank and rerank_topk returns what the index over db.astype(float32)
-    returns, bit for bit; needs db_low (the library's error without it), no MODE_PLAIN, no exact_knn / search_auto, float32 queries only.  The
+    returns, bit for bit; needs db_low (the library's error without it), no MODE_PLAIN, no exact_knn (but exact_knn(half_scan=True)) / search_auto, float32 queries only.  The
     library rounds nothing itself: float32 data is rounded by the caller -- round_to_half(a)[0].view(np.float16) is that table."""
 
     def __init__(self, db, graph_offsets, graph_nbrs, db_low=None, net=None, metric=METRIC_L2,
@@ -1067,14 +1093,21 @@ class Index:
                                            ids.ctypes.data, _ptr(dist), MEM_HOST, None))
         return ids, dist
 
-    def exact_knn(self, queries, k, query_tags=None, self_offset=-1, want_dist=False, gather=False):
+    def exact_knn(self, queries, k, query_tags=None, self_offset=-1, want_dist=False, gather=False, half_scan=False):
         """gbnns_index_exact_knn: exact_knn(db, queries, k, metric=<the handle's>, ...) over the handle's resident table, read in place --
         nothing of the table is uploaded.  query_tags [nq]: the tagged answer over set_tags()'s table (exact_knn's row_tags / query_tags
         form, the ground truth of search(query_tags=...)); None: the untagged answer.  A float handle takes float queries (uint8 ones raise
         TypeError), a byte handle uint8 queries (float ones: GbnnsError, code 5 -- there is no mixed-pair scan).  numpy queries -> numpy
         results; torch CUDA queries -> torch results, on the current stream.  Returns ids, or (ids, dist) with want_dist.
         gather=True: gbnns_index_exact_knn_gather -- the same bytes, computed from distances to the rows each query's word allows only (the
-        queries of a word scan that word's row list); needs query_tags (None: ValueError).  Opt-in; gather_plan() names its kernel."""
+        queries of a word scan that word's row list); needs query_tags (None: ValueError).  Opt-in; gather_plan() names its kernel.
+        half_scan=True, on a half-base handle (Index(db=<float16>)): gbnns_index_exact_knn_half -- exact_knn(db, queries, ...)'s answer over the
+        resident binary16 rows, read in place (float32 queries; knn_half_plan() tells the path).  Without it the call on such a handle is
+        refused (GbnnsError, code 5), as MODE_PLAIN is without FLAG_HALF_WALK; on a float or byte handle half_scan=True is GbnnsError, code 1."""
+        if half_scan:
+            if gather:
+                raise ValueError("exact_knn(half_scan=True) has no gathered form")
+            _float32_queries(self, queries)
         if gather and query_tags is None:
             raise ValueError("exact_knn(gather=True) needs query_tags: an untagged call has nothing to gather")
         u8 = _is_u8(queries)
@@ -1098,6 +1131,10 @@ class Index:
             ids = np.empty((nq, k), np.uint32)
             dist = np.empty((nq, k), np.float32) if want_dist else None
             sptr = None
+        if half_scan:
+            _check(self._lib.gbnns_index_exact_knn_half(self._h, _ptr(queries), nq, _ptr(query_tags), k, self_offset, _ptr(ids), _ptr(dist),
+                                                        MEM_DEVICE if dev else MEM_HOST, sptr))
+            return (ids, dist) if want_dist else ids
         fn = self._lib.gbnns_index_exact_knn_gather if gather else self._lib.gbnns_index_exact_knn
         _check(fn(self._h, None if u8 else _ptr(queries), _ptr(queries) if u8 else None, nq, _ptr(query_tags), k, self_offset, _ptr(ids), _ptr(dist),
                   MEM_DEVICE if dev else MEM_HOST, sptr))

@@ -2,8 +2,9 @@
 // generalised to k results: heaps, the matrix-core filter, long lists as pools), gbnns_exact_knn_bytes (the same lists over uint8 rows,
 // their distances from the int8 matrix cores: knn_bytes.hip) with gbnns_debug_knn_bytes_plan / gbnns_debug_knn_plan, their tagged forms gbnns_exact_knn_tagged /
 // gbnns_exact_knn_bytes_tagged and gbnns_index_exact_knn over a handle's resident table, and gbnns_build_graph_gd_device (hnswlikeGD,
-// support_func.h:521-575, pruning on the device).  Every kNN entry point fills a KnnCall<T> and ends in knn_call (one body for float rows,
-// one for byte rows).  What the two bodies share exists once: knn_check (the refusals), KnnStaged (HOST buffers and the
+// support_func.h:521-575, pruning on the device), and gbnns_exact_knn_half / gbnns_index_exact_knn_half (binary16 rows against float32
+// queries: knn_half.hip).  Every kNN entry point fills a KnnCall<T, Q> and ends in knn_call (one body for float32 queries against float or
+// binary16 rows -- knn_rows_call --, one for byte rows).  What the two bodies share exists once: knn_check (the refusals), KnnStaged (HOST buffers and the
 // tag words), KnnSlab (every address that depends on the query slab) and knn_sweep_chunks (the row chunks and the answer to a key list
 // that overflowed).  gbnns_index_exact_knn_gather (knn_gather_call: census, schedule, per round the lists' fill and the gathered scan --
 // knn_gather.hip) shares the refusals and the staging and falls back to knn_call for a shape its kernel does not cover.  Cut out of api.cpp
@@ -16,15 +17,16 @@ using namespace gbnns_api;
 
 namespace {
 // One exact-kNN request, whichever entry point brought it: gbnns_exact_knn / _bytes (untagged, caller's arrays), their _tagged twins, and
-// gbnns_index_exact_knn (the table and the row tags are the handle's, resident on the device at the handle's row stride).  T = float / uint8_t.
-template <class T>
+// gbnns_index_exact_knn (the table and the row tags are the handle's, resident on the device at the handle's row stride).  T = float / uint8_t
+// rows against queries of the same element; T = uint16_t, Q = float: binary16 rows against float32 queries (gbnns_exact_knn_half).
+template <class T, class Q = T>
 struct KnnCall {
     int device;
     const T* base;             // [n x bstride]; a buffer of mem_kind, or (resident) device memory whatever mem_kind says
     uint32_t bstride;          // elements between rows
     bool resident;
     uint64_t n;
-    const T* queries;          // [n_q x d], mem_kind
+    const Q* queries;          // [n_q x d], mem_kind
     uint64_t n_q;
     uint32_t d;
     int k, metric;
@@ -45,6 +47,14 @@ int knn_refuse(const KnnCall<float>& c) {
         return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_exact_knn: the negative-dot form needs d %% 8 == 0 (got %u)", c.d);
     return GBNNS_OK;
 }
+int knn_refuse(const KnnCall<uint16_t, float>& c) {
+    if (c.d > 8192) return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_exact_knn_half: d <= 8192 (a tile of base rows is staged in LDS; got %u)", c.d);
+    if (c.metric == GBNNS_METRIC_NEG_DOT && c.d % 8 != 0)
+        return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_exact_knn_half: the negative-dot form needs d %% 8 == 0 (got %u)", c.d);
+    if (!c.resident && (c.row_tags != nullptr) != (c.query_tags != nullptr))  // (a resident call's row tags are the handle's, asked for or not)
+        return fail(GBNNS_ERR_INVALID, "gbnns_exact_knn_half: row_tags and query_tags are both NULL or both set");
+    return GBNNS_OK;
+}
 int knn_refuse(const KnnCall<uint8_t>& c) {
     if (c.d > 256)
         return fail(GBNNS_ERR_UNSUPPORTED, "gbnns_exact_knn_bytes: d <= 256 (every sum of the distance must stay an integer below 2^24 to be exact "
@@ -57,8 +67,8 @@ int knn_refuse(const KnnCall<uint8_t>& c) {
 
 // The refusals of a call, in the order tests/test_cabi_cpu.py and tests/test_knn_bytes_cpu.py pin.  (A call without queries is valid
 // and done: the caller returns behind this.)
-template <class T>
-int knn_check(const KnnCall<T>& c) {
+template <class T, class Q>
+int knn_check(const KnnCall<T, Q>& c) {
     if (!c.base || !c.queries || !c.out_ids || (c.tagged && (!c.row_tags || !c.query_tags))) return fail(GBNNS_ERR_INVALID, "null argument");
     if (c.n == 0 || c.n >= (1ull << 32) - 1) return fail(GBNNS_ERR_INVALID, "n must be in [1, 2^32 - 1)");
     if (c.n_q >= (1ull << 31)) return fail(GBNNS_ERR_INVALID, "n_q too large");
@@ -78,8 +88,8 @@ int knn_check(const KnnCall<T>& c) {
 // The tag words of a tagged call on the device: the rows' in a copy of its own, 16-byte aligned and 64 words longer than the set (zero
 // there) -- the sweep kernels read them in aligned groups of four to the end of a block of 32 rows, as they read bnorm / bterm -- and the
 // queries' (uploaded for HOST buffers).
-template <class T>
-int knn_stage_tags(const KnnCall<T>& c, DevBuf& tag_dev, DevBuf& qtag_dev, const uint32_t*& qtags, hipStream_t s) {
+template <class T, class Q>
+int knn_stage_tags(const KnnCall<T, Q>& c, DevBuf& tag_dev, DevBuf& qtag_dev, const uint32_t*& qtags, hipStream_t s) {
     int rc;
     if ((rc = tag_dev.ensure(((size_t)c.n + 64) * 4))) return rc;
     HIP_TRY(hipMemsetAsync(tag_dev.as<uint32_t>() + c.n, 0, 64 * 4, s));
@@ -100,17 +110,17 @@ int knn_stage_tags(const KnnCall<T>& c, DevBuf& tag_dev, DevBuf& qtag_dev, const
 }
 
 // A call's arrays where the kernels read and write them: the caller's own (DEVICE buffers, a resident table), or copies (HOST).
-template <class T>
+template <class T, class Q = T>
 struct KnnStaged {
     ScopedDevBuf b_dev, q_dev, ids_dev, dist_dev, tag_dev, qtag_dev;
     const T* base;
-    const T* q;
+    const Q* q;
     uint32_t* ids;
     float* dist;
     const uint32_t* tags = nullptr;   // tagged: the device copies of the tag words; a launch with null tags is the untagged instance
     const uint32_t* qtags = nullptr;
 
-    int stage(const KnnCall<T>& c, hipStream_t s) {
+    int stage(const KnnCall<T, Q>& c, hipStream_t s) {
         const size_t nq = c.n_q;
         int rc;
         base = c.base; q = c.queries; ids = c.out_ids; dist = c.out_dist;
@@ -120,11 +130,11 @@ struct KnnStaged {
                 if ((rc = h2d_staged(b_dev.p, c.base, (size_t)c.n * c.d * sizeof(T)))) return rc;
                 base = b_dev.as<T>();
             }
-            if ((rc = q_dev.ensure(nq * c.d * sizeof(T)))) return rc;
+            if ((rc = q_dev.ensure(nq * c.d * sizeof(Q)))) return rc;
             if ((rc = ids_dev.ensure(nq * c.k * 4))) return rc;
             if (c.out_dist && (rc = dist_dev.ensure(nq * c.k * 4))) return rc;
-            if ((rc = h2d_staged(q_dev.p, c.queries, nq * c.d * sizeof(T)))) return rc;
-            q = q_dev.as<T>(); ids = ids_dev.as<uint32_t>();
+            if ((rc = h2d_staged(q_dev.p, c.queries, nq * c.d * sizeof(Q)))) return rc;
+            q = q_dev.as<Q>(); ids = ids_dev.as<uint32_t>();
             dist = c.out_dist ? dist_dev.as<float>() : nullptr;
         }
         if (c.tagged) {
@@ -134,7 +144,7 @@ struct KnnStaged {
         return GBNNS_OK;
     }
     // The lists back to HOST buffers, and the end of the call: its temporaries are released behind this, so it waits for the work that uses them.
-    int copy_back(const KnnCall<T>& c, hipStream_t s) const {
+    int copy_back(const KnnCall<T, Q>& c, hipStream_t s) const {
         if (c.mem_kind == GBNNS_MEM_HOST) {
             if (int rc = d2h_staged(c.out_ids, ids, (size_t)c.n_q * c.k * 4, s)) return rc;
             if (c.out_dist)
@@ -167,9 +177,9 @@ struct KnnSlab {
     uint32_t* out_ids;
     float* out_dist;        // or nullptr
 };
-template <class T>
-KnnSlab<T> knn_slab_at(const KnnCall<T>& c, const KnnStaged<T>& st, uint32_t q0, uint32_t slab) {
-    KnnSlab<T> sl{};
+template <class T, class Q>
+KnnSlab<Q> knn_slab_at(const KnnCall<T, Q>& c, const KnnStaged<T, Q>& st, uint32_t q0, uint32_t slab) {
+    KnnSlab<Q> sl{};
     sl.q0 = q0; sl.qn = std::min(slab, (uint32_t)c.n_q - q0);
     sl.q = st.q + (size_t)q0 * c.d;
     sl.self_offset = c.self_offset >= 0 ? c.self_offset + (int64_t)q0 : -1;
@@ -264,9 +274,115 @@ struct KnnFilterWork {
         if (qtags) { f.btag = tags + r0; f.qtag = qtags; }
         return f;
     }
+    // the steps of knn_rows_call by the names KnnHalfWork gives them
+    static int queries_covered(const float*, uint32_t, uint32_t, hipStream_t, bool* covered) { *covered = true; return GBNNS_OK; }  // (the float filter's bound asks nothing of a query)
+    int pack_queries(const float* q, uint32_t d, uint32_t qn, hipStream_t s) {
+        HIP_TRY(launch_knn_pack(q, d, d, qn, qpack.as<uint16_t>(), qnorm.as<float>(), s));
+        return GBNNS_OK;
+    }
+    int sweep(uint64_t r0, uint32_t rows, uint32_t qn, const uint32_t* tags, const uint32_t* qtags, hipStream_t s) const {
+        HIP_TRY(launch_knn_filter(chunk(r0, rows, qn, tags, qtags), s));
+        return GBNNS_OK;
+    }
 };
 
-int knn_call(const KnnCall<float>& c) {
+// What gbnns_exact_knn_half does with a shape (gbnns_debug_knn_half_plan reports it): gbnns_exact_knn's decision, and whether the sweep
+// reads the table in place or a copy at a stride of whole 16-byte chunks.
+// kKnnHalfBySize: does "knn_filter" = 1 turn the sweep on by size, as for float rows?  Decided by tools/knn_half_timing.py
+// (profiles/knn_half_timing.txt): only where the call beats gbnns_exact_knn on the widened copy by more than that call's run-to-run spread.
+constexpr bool kKnnHalfBySize = true;
+struct KnnHalfPlan {
+    KnnFloatPlan f;
+    bool packed;  // the table's stride is no multiple of 8 halves: swept from a copy at stride f.dp (a caller's array with d % 8 == 4)
+};
+KnnHalfPlan knn_half_plan(uint64_t n, uint64_t nq, uint32_t d, int k, int metric, uint32_t stride) {
+    KnnHalfPlan pl{};
+    pl.f = knn_float_plan(n, nq, d, k, metric);
+    if (!kKnnHalfBySize && g_knob_knn_filter.load(std::memory_order_relaxed) != 2) pl.f.pool = pl.f.filter = false;
+    pl.packed = (pl.f.pool || pl.f.filter) && stride % 8 != 0;
+    return pl;
+}
+
+// The same for binary16 rows (knn_half.hip): nothing of the table is packed -- the sweep reads it in place, or a copy where its stride is
+// no multiple of 8 halves --; the query side is the scaled hi + lo split.
+struct KnnHalfWork {
+    ScopedDevBuf copy, bnorm, qpack, qinv, qnorm, rhs, cand, count, flag;
+    uint32_t dp, cap, stride, last_chunk;
+    const uint16_t* table;
+    int prepare(const KnnParams& p, uint32_t nq, uint32_t dp_, uint32_t cap_, hipStream_t s) {
+        int rc;
+        dp = dp_; cap = cap_; table = p.base_h; stride = p.bstride; last_chunk = (p.dim + 7u) / 8u - 1u;
+        if (stride % 8 != 0) {
+            if ((rc = copy.ensure((size_t)p.n * dp * 2))) return rc;
+            HIP_TRY(launch_knn_half_pack(p.base_h, p.bstride, p.dim, dp, p.n, copy.as<uint16_t>(), s));
+            table = copy.as<uint16_t>(); stride = dp;
+        }
+        if ((rc = bnorm.ensure(((size_t)p.n + 64) * 4))) return rc;  // (+inf behind the last row: the sweep reads whole blocks of 32)
+        if ((rc = qpack.ensure((size_t)nq * dp * 4))) return rc;     // 2 dp halves per query
+        if ((rc = qinv.ensure((size_t)nq * 4))) return rc;
+        if ((rc = qnorm.ensure((size_t)nq * 4))) return rc;
+        if ((rc = rhs.ensure((size_t)nq * 4))) return rc;
+        if ((rc = cand.ensure((size_t)nq * cap * 4))) return rc;
+        if ((rc = count.ensure((size_t)nq * 4))) return rc;
+        if ((rc = flag.ensure(8))) return rc;  // [0] a list overflowed; [1] pack_queries' range flag (the call asked queries_covered before)
+        HIP_TRY(launch_fill_u32(bnorm.as<uint32_t>() + p.n, 0x7F800000u, 64, s));
+        HIP_TRY(launch_knn_half_norms(p.base_h, p.bstride, p.dim, p.n, bnorm.as<float>(), s));
+        return GBNNS_OK;
+    }
+    // Does the sweep's error bound cover every query (knn_half.hip)?  Asked once per call, before a path is taken: not covered -> the exact scan.
+    static int queries_covered(const float* q, uint32_t d, uint32_t nq, hipStream_t s, bool* covered) {
+        ScopedDevBuf f;
+        uint32_t h = 0;
+        if (int rc = f.ensure(4)) return rc;
+        HIP_TRY(launch_fill_u32(f.as<uint32_t>(), 0u, 1, s));
+        HIP_TRY(launch_knn_half_qsplit(q, d, d, (d + 15u) & ~15u, nq, nullptr, nullptr, nullptr, f.as<uint32_t>(), s));
+        HIP_TRY(hipMemcpyAsync(&h, f.p, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        *covered = h == 0;
+        return GBNNS_OK;
+    }
+    int pack_queries(const float* q, uint32_t d, uint32_t qn, hipStream_t s) {
+        HIP_TRY(launch_knn_half_qsplit(q, d, d, dp, qn, qpack.as<uint16_t>(), qinv.as<float>(), qnorm.as<float>(), flag.as<uint32_t>() + 1, s));
+        return GBNNS_OK;
+    }
+    int sweep(uint64_t r0, uint32_t rows, uint32_t qn, const uint32_t* tags, const uint32_t* qtags, hipStream_t s) const {
+        KnnHalfSweepParams f{};
+        f.qsplit = qpack.as<uint16_t>(); f.qinv = qinv.as<float>(); f.base = table + (size_t)r0 * stride; f.stride = stride; f.last_chunk = last_chunk;
+        f.bnorm = bnorm.as<float>() + r0; f.rhs = rhs.as<float>(); f.nq = qn; f.dp = dp; f.rows = rows; f.row0 = (uint32_t)r0; f.cap = cap;
+        f.cand = cand.as<uint32_t>(); f.count = count.as<uint32_t>(); f.overflow = flag.as<uint32_t>();
+        if (qtags) { f.btag = tags + r0; f.qtag = qtags; }
+        HIP_TRY(launch_knn_half_sweep(f, s));
+        return GBNNS_OK;
+    }
+};
+
+// What knn_rows_call asks of its rows' element: the filter's work, where a launch finds the table, the exact-distance launches, the plan.
+template <class B>
+struct KnnRowsOf;
+template <>
+struct KnnRowsOf<float> {
+    using Work = KnnFilterWork;
+    static void table(KnnParams& p, const float* rows) { p.base = rows; }
+    static hipError_t scan(const KnnParams& p, int metric, hipStream_t s) { return launch_knn_scan(p, metric, s); }
+    static hipError_t rescore(const KnnRescoreParams& p, hipStream_t s) { return launch_knn_rescore(p, s); }
+    static hipError_t pool_update(const KnnPoolParams& p, hipStream_t s) { return launch_knn_pool_update(p, s); }
+    static KnnFloatPlan plan(uint64_t n, uint64_t nq, uint32_t d, int k, int metric, uint32_t) { return knn_float_plan(n, nq, d, k, metric); }
+};
+template <>
+struct KnnRowsOf<uint16_t> {
+    using Work = KnnHalfWork;
+    static void table(KnnParams& p, const uint16_t* rows) { p.base_h = rows; }
+    static hipError_t scan(const KnnParams& p, int metric, hipStream_t s) { return launch_knn_half_scan(p, metric, s); }
+    static hipError_t rescore(const KnnRescoreParams& p, hipStream_t s) { return launch_knn_half_rescore(p, s); }
+    static hipError_t pool_update(const KnnPoolParams& p, hipStream_t s) { return launch_knn_half_pool_update(p, s); }
+    static KnnFloatPlan plan(uint64_t n, uint64_t nq, uint32_t d, int k, int metric, uint32_t stride) { return knn_half_plan(n, nq, d, k, metric, stride).f; }
+};
+
+// gbnns_exact_knn's body, for float32 queries against rows of B = float (gbnns_exact_knn) or binary16 (gbnns_exact_knn_half): one schedule
+// -- scan, or the matrix-core filter in front of heaps or pools -- whose launches come from KnnRowsOf<B>.
+template <class B>
+int knn_rows_call(const KnnCall<B, float>& c) {
+    using Rows = KnnRowsOf<B>;
     int rc;
     if ((rc = knn_check(c)) || c.n_q == 0) return rc;
     HIP_TRY(hipSetDevice(c.device));
@@ -274,15 +390,23 @@ int knn_call(const KnnCall<float>& c) {
     const int k = c.k, metric = c.metric;
     const uint64_t n = c.n;
     const uint32_t d = c.d, nq = (uint32_t)c.n_q;
-    KnnStaged<float> st;
+    KnnStaged<B, float> st;
     ScopedDevBuf heap;
     if ((rc = st.stage(c, s))) return rc;
+    if (sizeof(B) == 2 && (reinterpret_cast<uintptr_t>(st.base) & 15u))
+        return fail(GBNNS_ERR_INVALID, "gbnns_exact_knn_half: the table must be 16-byte aligned (the sweep reads a row in 16-byte chunks)");
     KnnParams p{};
-    p.base = st.base; p.q = st.q; p.out_ids = st.ids; p.out_dist = st.dist; p.row_tags = st.tags; p.query_tags = st.qtags;
+    Rows::table(p, st.base);
+    p.q = st.q; p.out_ids = st.ids; p.out_dist = st.dist; p.row_tags = st.tags; p.query_tags = st.qtags;
     p.bstride = c.bstride; p.qstride = d; p.n = n; p.nq = nq; p.dim = d; p.k = k; p.self_offset = c.self_offset;
     p.heap_stride = ((size_t)nq + 63) & ~(size_t)63;
-    const KnnFloatPlan pl = knn_float_plan(n, c.n_q, d, k, metric);
-    const bool pool_path = pl.pool, filter = pl.filter;
+    const KnnFloatPlan pl = Rows::plan(n, c.n_q, d, k, metric, c.bstride);
+    bool pool_path = pl.pool, filter = pl.filter;
+    if (pool_path || filter) {  // a query outside the filter's error bound (half rows: knn_half.hip): the exact scan serves any finite input
+        bool covered = true;
+        if ((rc = Rows::Work::queries_covered(st.q, d, nq, s, &covered))) return rc;
+        if (!covered) pool_path = filter = false;
+    }
     if (!pool_path) {  // (the pool path keeps its keys in slabs of its own: at k = 1 000 and 10^6 queries the heaps would be 9 GB)
         if ((rc = heap.ensure(p.heap_stride * (size_t)k * 8))) return rc;
         p.heap = heap.as<uint64_t>();
@@ -294,7 +418,7 @@ int knn_call(const KnnCall<float>& c) {
         // (chunks four times the heap path's: every chunk costs a query a pass over its whole pool; measured at k = 1 000: 32 K rows 1.98 s, 64 K 1.86 s, 128 K 1.89 s)
         const uint64_t max_chunk = std::min<uint64_t>(4ull * (uint64_t)g_knob_knn_chunk.load(std::memory_order_relaxed), std::max<uint64_t>(64, (n / 16 + 63) & ~(uint64_t)63));
         const uint32_t slab = knn_slab_queries(nq, k, 4);  // queries in slabs whose candidate lists take at most 4 GiB
-        KnnFilterWork w;
+        typename Rows::Work w;
         ScopedDevBuf pool, root;
         if ((rc = pool.ensure((size_t)slab * (size_t)k * 8))) return rc;
         if ((rc = root.ensure((size_t)slab * 8))) return rc;
@@ -305,15 +429,15 @@ int knn_call(const KnnCall<float>& c) {
             pp.k = p;
             pp.k.q = sl.q; pp.k.nq = sl.qn; pp.k.out_ids = sl.out_ids; pp.k.out_dist = sl.out_dist;
             pp.k.self_offset = sl.self_offset; pp.k.query_tags = sl.qtags;
-            pp.pool = pool.as<uint64_t>(); pp.root = root.as<uint64_t>(); pp.cand = w.cand.as<uint32_t>(); pp.count = w.count.as<uint32_t>();
-            pp.cap = cap; pp.qnorm = w.qnorm.as<float>(); pp.rhs = w.rhs.as<float>();
-            HIP_TRY(launch_knn_pack(sl.q, d, d, sl.qn, w.qpack.as<uint16_t>(), w.qnorm.as<float>(), s));
+            pp.pool = pool.as<uint64_t>(); pp.root = root.as<uint64_t>(); pp.cand = static_cast<uint32_t*>(w.cand.p); pp.count = static_cast<uint32_t*>(w.count.p);
+            pp.cap = cap; pp.qnorm = static_cast<float*>(w.qnorm.p); pp.rhs = static_cast<float*>(w.rhs.p);
+            if ((rc = w.pack_queries(sl.q, d, sl.qn, s))) return rc;
             HIP_TRY(hipMemsetAsync(pool.p, 0xFF, (size_t)sl.qn * (size_t)k * 8, s));
             HIP_TRY(hipMemsetAsync(root.p, 0xFF, (size_t)sl.qn * 8, s));
-            HIP_TRY(launch_fill_u32(w.rhs.as<uint32_t>(), 0xFF800000u, sl.qn, s));  // -inf: every row passes
-            auto sweep = [&](uint64_t r0, uint32_t rows) -> int { HIP_TRY(launch_knn_filter(w.chunk(r0, rows, sl.qn, st.tags, sl.qtags), s)); return GBNNS_OK; };
-            auto take = [&]() -> int { HIP_TRY(launch_knn_pool_update(pp, s)); return GBNNS_OK; };
-            if ((rc = knn_sweep_chunks(n, rows_first, max_chunk, sl.qn, w.count.as<uint32_t>(), w.flag.as<uint32_t>(), s, sweep, take))) return rc;
+            HIP_TRY(launch_fill_u32(static_cast<uint32_t*>(w.rhs.p), 0xFF800000u, sl.qn, s));  // -inf: every row passes
+            auto sweep = [&](uint64_t r0, uint32_t rows) -> int { return w.sweep(r0, rows, sl.qn, st.tags, sl.qtags, s); };
+            auto take = [&]() -> int { HIP_TRY(Rows::pool_update(pp, s)); return GBNNS_OK; };
+            if ((rc = knn_sweep_chunks(n, rows_first, max_chunk, sl.qn, static_cast<uint32_t*>(w.count.p), static_cast<uint32_t*>(w.flag.p), s, sweep, take))) return rc;
             HIP_TRY(launch_knn_pool_finalize(pp, s));
         }
     } else if (filter) {
@@ -324,42 +448,45 @@ int knn_call(const KnnCall<float>& c) {
         // Chunks start on multiples of 64 rows (the filter reads the norms in aligned groups of four).
         const uint64_t max_chunk = std::min<uint64_t>((uint64_t)g_knob_knn_chunk.load(std::memory_order_relaxed), std::max<uint64_t>(64, (n / 16 + 63) & ~(uint64_t)63));  // (small sets, tests: a sixteenth)
         const uint64_t first = std::min<uint64_t>(n, (std::max<uint64_t>(std::min<uint64_t>(max_chunk, 8192), 4ull * (uint64_t)k) + 63) & ~(uint64_t)63);
-        KnnFilterWork w;
+        typename Rows::Work w;
         if ((rc = w.prepare(p, nq, pl.dp, cap, s))) return rc;
-        HIP_TRY(launch_knn_pack(p.q, d, d, nq, w.qpack.as<uint16_t>(), w.qnorm.as<float>(), s));
+        if ((rc = w.pack_queries(p.q, d, nq, s))) return rc;
         KnnParams ps = p;          // the first rows: the exact scan, heaps kept
         ps.n = first; ps.row0 = 0; ps.keep_heap = 1;
-        HIP_TRY(launch_knn_scan(ps, metric, s));
-        HIP_TRY(launch_knn_thresholds(p.heap, p.heap_stride, k, w.qnorm.as<float>(), nq, w.rhs.as<float>(), s));
+        HIP_TRY(Rows::scan(ps, metric, s));
+        HIP_TRY(launch_knn_thresholds(p.heap, p.heap_stride, k, static_cast<float*>(w.qnorm.p), nq, static_cast<float*>(w.rhs.p), s));
         uint32_t h_flag = 0;
         for (uint64_t r0 = first, chunk = 0; r0 < n; r0 += chunk) {
             chunk = std::min<uint64_t>(max_chunk, r0);
             const uint32_t rows = (uint32_t)std::min<uint64_t>(chunk, n - r0);
             HIP_TRY(hipMemsetAsync(w.count.p, 0, (size_t)nq * 4, s));
             HIP_TRY(hipMemsetAsync(w.flag.p, 0, 4, s));
-            HIP_TRY(launch_knn_filter(w.chunk(r0, rows, nq, st.tags, st.qtags), s));
+            if ((rc = w.sweep(r0, rows, nq, st.tags, st.qtags, s))) return rc;
             HIP_TRY(hipMemcpyAsync(&h_flag, w.flag.p, 4, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
             if (h_flag) {
                 // some query kept more rows of this chunk than its list holds (adversarial order of the rows, or thresholds
                 // not yet tight): the chunk is scanned exactly for everyone instead -- same heaps, nothing offered twice
                 KnnParams pc = p;
-                pc.base = p.base + (size_t)r0 * p.bstride; pc.n = rows; pc.row0 = r0; pc.keep_heap = 1;
-                HIP_TRY(launch_knn_scan(pc, metric, s));
-                HIP_TRY(launch_knn_thresholds(p.heap, p.heap_stride, k, w.qnorm.as<float>(), nq, w.rhs.as<float>(), s));
+                Rows::table(pc, st.base + (size_t)r0 * p.bstride);
+                pc.n = rows; pc.row0 = r0; pc.keep_heap = 1;
+                HIP_TRY(Rows::scan(pc, metric, s));
+                HIP_TRY(launch_knn_thresholds(p.heap, p.heap_stride, k, static_cast<float*>(w.qnorm.p), nq, static_cast<float*>(w.rhs.p), s));
             } else {
                 KnnRescoreParams rp{};
-                rp.k = p; rp.cand = w.cand.as<uint32_t>(); rp.count = w.count.as<uint32_t>(); rp.cap = cap;
-                rp.qnorm = w.qnorm.as<float>(); rp.rhs = w.rhs.as<float>();
-                HIP_TRY(launch_knn_rescore(rp, s));
+                rp.k = p; rp.cand = static_cast<uint32_t*>(w.cand.p); rp.count = static_cast<uint32_t*>(w.count.p); rp.cap = cap;
+                rp.qnorm = static_cast<float*>(w.qnorm.p); rp.rhs = static_cast<float*>(w.rhs.p);
+                HIP_TRY(Rows::rescore(rp, s));
             }
         }
         HIP_TRY(launch_knn_finalize(p, s));
     } else {
-        HIP_TRY(launch_knn_scan(p, metric, s));
+        HIP_TRY(Rows::scan(p, metric, s));
     }
     return st.copy_back(c, s);
 }
+int knn_call(const KnnCall<float>& c) { return knn_rows_call(c); }
+int knn_call(const KnnCall<uint16_t, float>& c) { return knn_rows_call(c); }
 
 // What gbnns_exact_knn_bytes does with a shape under the current knobs (gbnns_debug_knn_bytes_plan reports it).
 struct KnnBytesPlan {
@@ -446,10 +573,10 @@ int knn_call(const KnnCall<uint8_t>& c) {
     return st.copy_back(c, s);
 }
 
-template <class T>
-KnnCall<T> knn_free_call(int device, const T* base, uint64_t n, const T* queries, uint64_t n_q, uint32_t d, int k, int metric, int64_t self_offset,
+template <class T, class Q>
+KnnCall<T, Q> knn_free_call(int device, const T* base, uint64_t n, const Q* queries, uint64_t n_q, uint32_t d, int k, int metric, int64_t self_offset,
                          bool tagged, const uint32_t* row_tags, const uint32_t* query_tags, uint32_t* out_ids, float* out_dist, int mem_kind, void* stream) {
-    KnnCall<T> c{};
+    KnnCall<T, Q> c{};
     c.device = device; c.base = base; c.bstride = d; c.resident = false; c.n = n; c.queries = queries; c.n_q = n_q; c.d = d; c.k = k;
     c.metric = metric; c.self_offset = self_offset; c.tagged = tagged; c.row_tags = row_tags; c.query_tags = query_tags;
     c.out_ids = out_ids; c.out_dist = out_dist; c.mem_kind = mem_kind; c.stream = stream;
@@ -457,21 +584,21 @@ KnnCall<T> knn_free_call(int device, const T* base, uint64_t n, const T* queries
 }
 
 // A request over a handle's resident table (float or byte), read in place at its device row stride; the row tags are the handle's.
-template <class T>
-KnnCall<T> knn_resident_call(gbnns_index* ix, const T* table, const T* queries, uint64_t n_q, const uint32_t* query_tags, int k, int64_t self_offset,
+template <class T, class Q>
+KnnCall<T, Q> knn_resident_call(gbnns_index* ix, const T* table, const Q* queries, uint64_t n_q, const uint32_t* query_tags, int k, int64_t self_offset,
                              uint32_t* out_ids, float* out_dist, int mem_kind, void* stream) {
-    KnnCall<T> c = knn_free_call(ix->device, table, ix->n, queries, n_q, ix->d, k, ix->metric, self_offset, query_tags != nullptr,
+    KnnCall<T, Q> c = knn_free_call(ix->device, table, ix->n, queries, n_q, ix->d, k, ix->metric, self_offset, query_tags != nullptr,
                                  ix->tags.as<uint32_t>(), query_tags, out_ids, out_dist, mem_kind, stream);
     c.bstride = ix->d_pad; c.resident = true;
     return c;
 }
 
 // gbnns_index_exact_knn behind its own refusals: `table` is the handle's float or byte table, read in place at its device row stride.
-template <class T>
-int knn_index_call(gbnns_index* ix, const T* table, const T* queries, uint64_t n_q, const uint32_t* query_tags, int k, int64_t self_offset,
+template <class T, class Q>
+int knn_index_call(gbnns_index* ix, const T* table, const Q* queries, uint64_t n_q, const uint32_t* query_tags, int k, int64_t self_offset,
                    uint32_t* out_ids, float* out_dist, int mem_kind, void* stream) {
     if (!table) return fail(GBNNS_ERR_INVALID, "gbnns_index_exact_knn: the handle has no original-space table");
-    const KnnCall<T> c = knn_resident_call(ix, table, queries, n_q, query_tags, k, self_offset, out_ids, out_dist, mem_kind, stream);
+    const KnnCall<T, Q> c = knn_resident_call(ix, table, queries, n_q, query_tags, k, self_offset, out_ids, out_dist, mem_kind, stream);
     // (enter_stream: the deferred calls still owed are joined, as by any call without GBNNS_FLAG_DEFER_JOIN, and `stream` waits for the
     // handle's work in flight on another stream -- a gbnns_index_set_tags among it)
     HIP_TRY(hipSetDevice(ix->device));
@@ -641,7 +768,7 @@ int knn_index_refuse(const char* fn, gbnns_index* ix, const float* queries, cons
     if (!ix) return fail(GBNNS_ERR_INVALID, "null argument");
     if (ix->is(RowKind::F16))
         return fail(GBNNS_ERR_UNSUPPORTED, "%s on a half-base handle (gbnns_index_create_half_base): there is no exact scan over the resident binary16 rows; "
-                    "widen the table and call gbnns_exact_knn", fn);
+                    "widen the table and call gbnns_exact_knn -- or call gbnns_index_exact_knn_half, the exact scan over the binary16 rows as they are", fn);
     if (queries_u8 && !ix->is(RowKind::U8)) return fail(GBNNS_ERR_INVALID, "%s: queries_u8 needs a byte handle (gbnns_index_create_bytes)", fn);
     if (queries && ix->is(RowKind::U8))
         return fail(GBNNS_ERR_UNSUPPORTED, "%s: float queries on a byte handle: there is no mixed-pair scan (uint8 rows against "
@@ -697,6 +824,25 @@ int gbnns_index_exact_knn(gbnns_index* ix, const float* queries, const uint8_t* 
     if (int rc = knn_index_refuse("gbnns_index_exact_knn", ix, queries, queries_u8, query_tags)) return rc;
     if (queries) return knn_index_call(ix, ix->base_as<float>(), queries, n_q, query_tags, k, self_offset, out_ids, out_dist, mem_kind, stream);
     return knn_index_call(ix, ix->base_as<uint8_t>(), queries_u8, n_q, query_tags, k, self_offset, out_ids, out_dist, mem_kind, stream);
+}
+
+// Binary16 rows against float32 queries (knn_half.hip): every output byte is gbnns_exact_knn's over the widened rows.  Tags: both or neither.
+int gbnns_exact_knn_half(int device, const uint16_t* base_half, uint64_t n, const float* queries, uint64_t n_q, uint32_t d, int k, int metric,
+                         int64_t self_offset, const uint32_t* row_tags, const uint32_t* query_tags, uint32_t* out_ids, float* out_dist,
+                         int mem_kind, void* stream) {
+    return knn_call(knn_free_call(device, base_half, n, queries, n_q, d, k, metric, self_offset, row_tags && query_tags, row_tags, query_tags, out_ids,
+                                  out_dist, mem_kind, stream));
+}
+
+// ... over a half-base handle's resident table, in place at its row stride (d_pad halves: whole 16-byte chunks, nothing is copied)
+int gbnns_index_exact_knn_half(gbnns_index* ix, const float* queries, uint64_t n_q, const uint32_t* query_tags, int k, int64_t self_offset,
+                               uint32_t* out_ids, float* out_dist, int mem_kind, void* stream) {
+    if (!ix || !queries) return fail(GBNNS_ERR_INVALID, "null argument");
+    if (!ix->is(RowKind::F16))
+        return fail(GBNNS_ERR_INVALID, "gbnns_index_exact_knn_half needs a half-base handle (gbnns_index_create_half_base); a %s takes gbnns_index_exact_knn",
+                    row_handle_noun(ix->rows));
+    if (query_tags && !ix->tags.p) return fail(GBNNS_ERR_INVALID, "gbnns_index_exact_knn_half with query_tags but without gbnns_index_set_tags");
+    return knn_index_call(ix, ix->base_as<uint16_t>(), queries, n_q, query_tags, k, self_offset, out_ids, out_dist, mem_kind, stream);
 }
 
 // The gathered form: the same bytes, from distances to the allowed rows only (knn_gather.hip).  This call's own refusals need no handle and
@@ -807,6 +953,25 @@ int gbnns_debug_knn_plan(int bytes, int metric, uint64_t n, uint64_t n_q, uint32
     }
     if (!kernel) return fail(GBNNS_ERR_INTERNAL, "gbnns_debug_knn_plan: no kernel instance for the plan");
     std::snprintf(name, name_bytes, "%s", kernel);
+    return GBNNS_OK;
+}
+
+int gbnns_debug_knn_half_plan(int metric, uint64_t n, uint64_t n_q, uint32_t d, uint32_t stride, int k, int tagged, char* name, uint32_t name_bytes,
+                              int* pool, int* packed) {
+    if (!name || name_bytes == 0 || !pool || !packed) return fail(GBNNS_ERR_INVALID, "gbnns_debug_knn_half_plan: null output");
+    if (stride == 0) stride = d;
+    if ((metric != GBNNS_METRIC_L2 && metric != GBNNS_METRIC_NEG_DOT) || n == 0 || n >= (1ull << 32) - 1 || n_q >= (1ull << 31) || d == 0 ||
+        stride < d || k < 1 || k > (1 << 20))
+        return fail(GBNNS_ERR_INVALID, "gbnns_debug_knn_half_plan: not a shape gbnns_exact_knn_half takes");
+    KnnCall<uint16_t, float> c{};
+    c.d = d; c.k = k; c.metric = metric;
+    if (int rc = knn_refuse(c)) return rc;
+    const KnnHalfPlan pl = knn_half_plan(n, n_q, d, k, metric, stride);
+    const char* kernel = pl.f.pool || pl.f.filter ? knn_half_sweep_kernel_name(pl.f.dp, tagged != 0) : knn_half_scan_kernel_name(metric, d, tagged != 0);
+    if (!kernel) return fail(GBNNS_ERR_INTERNAL, "gbnns_debug_knn_half_plan: no kernel instance for the plan");
+    std::snprintf(name, name_bytes, "%s", kernel);
+    *pool = pl.f.pool ? 1 : 0;
+    *packed = pl.packed ? 1 : 0;
     return GBNNS_OK;
 }
 

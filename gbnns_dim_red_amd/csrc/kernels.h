@@ -332,6 +332,8 @@ struct KnnParams {
     // the tagged instances of the scan kernels; the rescore / pool kernels see allowed candidates only and do not look
     const uint32_t* row_tags;   // [row0 + n] tag words by row ID (not by row of `base`), or nullptr: the untagged instances
     const uint32_t* query_tags; // [nq]
+    // gbnns_exact_knn_half (knn_half.hip): the table as binary16 bit patterns [n x bstride halves], read by the half-row instances in place of `base`
+    const uint16_t* base_h;
 };
 hipError_t launch_knn_scan(const KnnParams& p, int metric, hipStream_t s);
 // Host only, no device needed: the name, template arguments included, of the instance launch_knn_scan / launch_knn_filter /
@@ -389,6 +391,45 @@ struct KnnPoolParams {
 hipError_t launch_knn_pool_update(const KnnPoolParams& p, hipStream_t s);
 hipError_t launch_knn_pool_finalize(const KnnPoolParams& p, hipStream_t s);   // ascending order + outputs
 constexpr float kKnnFilterSlack = 1.0f / 4096.0f;  // c: |approximate - reference distance| <= c (|q|^2 + |x|^2) with room to spare (knn.hip)
+
+// Exact kNN over binary16 rows against float32 queries (knn_half.hip; gbnns_exact_knn_half): the filter scheme of knn.hip with the rows as
+// they are -- a binary16 row is an exact operand of v_mfma_f32_32x32x16_f16 and is swept in place -- and only the query split:
+//   q s = hi + lo + r,  hi, lo binary16, s a power of two per query that puts max |q_k s| into [2^12, 2^13)
+// (two products per K step, exact in f32).  KnnParams::base_h carries the table for the half-row instances of the scan, rescore and pool
+// kernels (knn_scan_kernels.h); thresholds, finalize and the pools' sort are knn.hip's own launches.
+// Row norms |x|^2 of n rows at `stride` halves (the caller fills the 64 entries behind them with +inf, as for launch_knn_pack).
+hipError_t launch_knn_half_norms(const uint16_t* x, uint32_t stride, uint32_t dim, uint64_t rows, float* norms, hipStream_t s);
+// A table whose stride is no multiple of 8 halves, copied to rows of `dp` halves (a multiple of 16), zero filled.
+hipError_t launch_knn_half_pack(const uint16_t* x, uint32_t stride, uint32_t dim, uint32_t dp, uint64_t rows, uint16_t* packed, hipStream_t s);
+// The query side: per query and group of 8 dims 8 hi then 8 lo halves of q s ([rows x 2 dp], dims zero-padded to dp), inv[q] = 1 / s,
+// norms[q] = |q|^2; *uncovered is set where a query lies outside the filter's error bound (|q|^2 not finite, or beyond 2^+-96: the
+// bound's terms are relative to |q|^2 + |x|^2 in normal float32 range).  packed == nullptr: that test alone (inv, norms unused).
+hipError_t launch_knn_half_qsplit(const float* q, uint32_t stride, uint32_t dim, uint32_t dp, uint64_t rows, uint16_t* packed, float* inv, float* norms,
+                                  uint32_t* uncovered, hipStream_t s);
+struct KnnHalfSweepParams {
+    const uint16_t* qsplit;  // [nq x 2 dp] launch_knn_half_qsplit's
+    const float* qinv;       // [nq] 1 / s
+    const uint16_t* base;    // the chunk's first row; rows `stride` halves apart, 16-byte aligned
+    uint32_t stride;         // a multiple of 8
+    uint32_t last_chunk;     // index of the last 16-byte chunk of a row that holds dimensions: (d + 7) / 8 - 1; a lane never reads beyond it
+    const float* bnorm;      // [rows] squared norms of the chunk's rows (+inf behind the set, 16-byte aligned)
+    const float* rhs;        // [nq] as KnnFilterParams::rhs
+    uint32_t nq, dp;         // dp = d rounded up to the K step of 16
+    uint32_t rows, row0, cap;
+    uint32_t* cand;          // [nq x cap] ids that passed
+    uint32_t* count;         // [nq]
+    uint32_t* overflow;      // [1]
+    const uint32_t* btag;    // as KnnFilterParams::btag / qtag, or nullptr: the untagged instances
+    const uint32_t* qtag;
+};
+hipError_t launch_knn_half_sweep(const KnnHalfSweepParams& p, hipStream_t s);
+// the half-row instances of launch_knn_scan / launch_knn_rescore / launch_knn_pool_update (p.base_h, p.bstride in halves)
+hipError_t launch_knn_half_scan(const KnnParams& p, int metric, hipStream_t s);
+hipError_t launch_knn_half_rescore(const KnnRescoreParams& p, hipStream_t s);
+hipError_t launch_knn_half_pool_update(const KnnPoolParams& p, hipStream_t s);
+// Host only, no device needed: "knn_half_sweep_kernel<KSTEPS, QB, TAG>" / "knn_scan_kernel<..., half>" -- the instance the launch starts
+const char* knn_half_sweep_kernel_name(uint32_t dp, bool tagged);
+const char* knn_half_scan_kernel_name(int metric, uint32_t dim, bool tagged);
 
 // Exact kNN over uint8 rows on the int8 matrix cores (knn_bytes.hip; d <= 256: every distance is an integer below 2^24, so
 // the int32 result of v_mfma_i32_32x32x32_i8 IS the reference's float distance).  Rows are packed as signed bytes x - 128,

@@ -733,6 +733,35 @@ int gbnns_debug_knn_slab(int bytes, uint64_t n_q, int k, uint32_t* slab);
  * from.  GBNNS_ERR_INVALID / GBNNS_ERR_UNSUPPORTED for a shape the call refuses. */
 int gbnns_debug_knn_plan(int bytes, int metric, uint64_t n, uint64_t n_q, uint32_t d, int k, int tagged, char* name, uint32_t name_bytes,
                          int* pool);
+/* gbnns_exact_knn over binary16 rows (a table whose float32 form is too large to keep: what gbnns_index_create_half_base holds) against
+ * float32 queries, which are never rounded.  The result -- ids, and the bit patterns of out_dist -- is that of
+ * gbnns_exact_knn(float32(base_half), queries, ...), argument for argument: widening is exact, and every exact distance is computed by the
+ * float call's kernels instantiated for half rows, which widen a row while they stage or load it.  base_half [n x d] is dense rows of
+ * IEEE binary16 bit patterns, 16-byte aligned; inputs finite (subnormal halves and queries of any float32 magnitude included).
+ * row_tags / query_tags: both NULL (the untagged answer) or both set (gbnns_exact_knn_tagged's answer); one alone: GBNNS_ERR_INVALID.
+ * The other refusals are gbnns_exact_knn's: d > 8192 and GBNNS_METRIC_NEG_DOT with d % 8 != 0 are GBNNS_ERR_UNSUPPORTED.
+ * Where gbnns_exact_knn runs its matrix-core filter (L2, d % 4 == 0, d <= 128; the same knobs) this call runs one of its own on
+ * v_mfma_f32_32x32x16_f16 (knn_half.hip): a binary16 row is an exact operand of that instruction and is swept where it lies -- nothing of
+ * the table is packed or copied, unless its stride is no multiple of 8 halves (d % 8 == 4 here), which costs one copy at stride
+ * round_up(d, 16) -- and only the query is split, scaled by a power of two, into two binary16 parts: two products per K step instead of
+ * three.  A query outside the sweep's error bound (|q|^2 not finite in float32, or beyond 2^+-96) sends the whole call to the exact scan.
+ * Workspace beside the float call's lists and heaps: 4 (n + 64) bytes of row norms; HOST buffers upload the table as halves. */
+int gbnns_exact_knn_half(int device, const uint16_t* base_half, uint64_t n, const float* queries, uint64_t n_q, uint32_t d, int k, int metric,
+                         int64_t self_offset, const uint32_t* row_tags, const uint32_t* query_tags, uint32_t* out_ids, float* out_dist,
+                         int mem_kind, void* stream);
+/* The same over the resident table of a half-base handle (gbnns_index_create_half_base), read in place at its row stride of d_pad halves;
+ * the handle's metric; query_tags != NULL: the tagged answer over gbnns_index_set_tags' table (without one: GBNNS_ERR_INVALID).
+ * GBNNS_ERR_INVALID on a float or byte handle (gbnns_index_exact_knn is theirs).  Stream rule, joins and return as gbnns_index_exact_knn;
+ * byte-identical to gbnns_exact_knn_half on the same table and tags.  gbnns_index_exact_knn, gbnns_index_exact_knn_gather and
+ * gbnns_search_tagged_auto stay refused on a half-base handle: this call is the opt-in, as GBNNS_FLAG_HALF_WALK is for GBNNS_MODE_PLAIN. */
+int gbnns_index_exact_knn_half(gbnns_index* index, const float* queries, uint64_t n_q, const uint32_t* query_tags, int k, int64_t self_offset,
+                               uint32_t* out_ids, float* out_dist, int mem_kind, void* stream);
+/* Diagnostic, no device needed: gbnns_debug_knn_plan for gbnns_exact_knn_half -- the kernel that sweeps the rows
+ * ("knn_half_sweep_kernel<KSTEPS, QB, TAG>" where the matrix-core sweep takes the call, else "knn_scan_kernel<..., half>" /
+ * "knn_scan_wide_kernel<..., half>"), whether lists are pools (*pool) and whether the sweep reads a copy of the table (*packed = 1:
+ * `stride`, the halves between rows -- 0 = d --, is no multiple of 8) or the table in place (0).  Same knobs as gbnns_debug_knn_plan. */
+int gbnns_debug_knn_half_plan(int metric, uint64_t n, uint64_t n_q, uint32_t d, uint32_t stride, int k, int tagged, char* name, uint32_t name_bytes,
+                              int* pool, int* packed);
 /* Diagnostic, no device needed: the dedupe table of a gbnns_index_tag_census over n_q queries has *cap slots (a power of two >= 2 n_q,
  * at least 64) and a query word's probe sequence starts at *slot, going up by one and wrapping at *cap -- so that a test can build
  * colliding words without restating the hash.  GBNNS_ERR_INVALID: n_q outside 1 .. 2^30. */
