@@ -15,6 +15,9 @@ Shapes, the smallest at which an instance can still go wrong:
                 where d % 4 != 0 and the distance leaves the last three columns out
   k             1 and 10 on heaps; 64, or "knn_pool_min_k" = 1, on pools
 Tagged cases take k >= 10 only: their words allow some rows but not all, and the word of rows 0 .. 6 allows fewer than k.
+
+The binary16 instances (gbnns_exact_knn_half: knn_half_sweep_kernel and the half-row scans, 38 instances) have the same census in
+tests/knn_half_instances.py.
 """
 import collections
 import functools

@@ -1,21 +1,20 @@
 """gbnns_exact_knn_half on a device: binary16 rows against float32 queries, ids and distance bytes equal to a plain reference -- the
-reference's ordered float32 sums (knn_bytes_util.f32_l2_four_sums / f32_dot_eight_sums, restated over whole arrays: the same operations in
-the same order, checked against those functions pair by pair on a sample) on the widened rows, then numpy's sort of (distance, id).  Not
-another call of the library.  n = 2 085 rows (no multiple of 32 or 64) in several chunks, every eighth row a duplicate of the row before
-it; three magnitude classes, the queries at the rows' scale: unit, rows x 2^-20 (most halves subnormal: pins that the f16 matrix cores
-keep subnormal operands, which the sweep's error bound assumes) and rows x 2^13."""
+reference's ordered float32 sums on the widened rows, then numpy's sort of (distance, id) (tests/knn_half_util.py).  Not another call of
+the library.  (Every kernel instance: tests/test_gpu_knn_half_instances.py; the sweep's edges: tests/test_gpu_knn_half_edges.py.)
+n = 2 085 rows (no multiple of 32 or 64) in several chunks, every eighth row a duplicate of the row before it; three magnitude classes,
+the queries at the rows' scale: unit, rows x 2^-20 (most halves subnormal: pins that the f16 matrix cores keep subnormal operands, which
+the sweep's error bound assumes) and rows x 2^13."""
 import functools
 
 import numpy as np
 import pytest
 
 import knn_bytes_util as ku
+from knn_half_util import F32, SCALE, half_rows, knn_of, ordered_dist, same
 
 pytestmark = pytest.mark.gpu
 
 N, NQ = 2085, 130
-SCALE = {"unit": 0, "subnormal": -20, "large": 13}
-F32 = np.float32
 
 
 @pytest.fixture(scope="module")
@@ -30,63 +29,16 @@ def g():
 @functools.lru_cache(maxsize=None)
 def data(d, cls, n=N):
     rng = np.random.default_rng(1000 * d + SCALE[cls] + n)
-    rows = (rng.standard_normal((n, d)).astype(F32) * F32(2.0 ** SCALE[cls])).astype(np.float16)
-    rows[7::8] = rows[6::8][:len(rows[7::8])]   # ties
+    rows = half_rows(rng, n, d, cls)            # (every eighth row a duplicate: ties)
     q = rng.standard_normal((NQ, d)).astype(F32) * F32(2.0 ** SCALE[cls])
     q[:4] = rows[10:14].astype(F32)             # distance 0 to a row and its duplicate's neighbourhood
     return rows, q
-
-
-def ordered_dist(rows, q, metric):
-    """[nq x n] float32: L2Metric::Dist / Angular::Dist of the reference on float32(rows), every operation rounded to float32 in its order."""
-    x, d = rows.astype(F32), rows.shape[1]
-    if metric == ku.L2:
-        s = [np.zeros((len(q), len(x)), F32) for _ in range(4)]
-        for c in range(d // 4 * 4):
-            e = x[None, :, c] - q[:, None, c]
-            s[c % 4] = s[c % 4] + e * e
-        out = ((s[0] + s[1]) + s[2]) + s[3]
-        one = ku.f32_l2_four_sums
-    else:
-        s = [np.zeros((len(q), len(x)), F32) for _ in range(8)]
-        for c in range(d):
-            s[c % 8] = s[c % 8] + x[None, :, c] * q[:, None, c]
-        m = [s[j + 4] + s[j] for j in range(4)]
-        out = -((m[0] + m[1]) + (m[2] + m[3]))
-        one = ku.f32_dot_eight_sums
-    assert out.dtype == F32
-    for i, j in ((0, 10), (5, 7), (len(q) - 1, len(x) - 1)):
-        assert ku.bits(out[i, j]) == ku.bits(one(x[j], q[i]))
-    return out + F32(0)   # (-0 reads +0, as in the float call)
-
-
-def knn_of(dist, k, allowed=None, self_offset=-1):
-    nq, n = dist.shape
-    ids, out = np.full((nq, k), ku.NONE_ID, np.uint32), np.full((nq, k), np.inf, F32)
-    rows = np.arange(n)
-    for i in range(nq):
-        order = np.lexsort((rows, dist[i]))
-        if allowed is not None:
-            order = order[allowed[i][order]]
-        if self_offset >= 0:
-            order = order[order != i + self_offset]
-        order = order[:k]
-        ids[i, :order.size], out[i, :order.size] = order, dist[i, order]
-    return ids, out
 
 
 @functools.lru_cache(maxsize=None)
 def reference(d, cls, metric, n=N):
     rows, q = data(d, cls, n)
     return ordered_dist(rows, q, metric)
-
-
-def same(got, want, what=""):
-    (gi, gd), (wi, wd) = got, want
-    gi, gd = (np.asarray(a.cpu()) if hasattr(a, "cpu") else a for a in (gi, gd))
-    bad = np.flatnonzero((gi.view(np.uint32) != wi).any(1) | (ku.bits(gd) != ku.bits(wd)).any(1))
-    print(what, "queries that differ:", bad.size, bad[:8])
-    assert bad.size == 0, what
 
 
 def knobs(g):
