@@ -245,23 +245,34 @@ KnnFloatPlan knn_float_plan(uint64_t n, uint64_t nq, uint32_t d, int k, int metr
     return pl;
 }
 
-// The matrix-core filter's operands and lists (knn.hip) for `nq` queries at a time: the heap-filter path's whole call, a slab of the pool path.
-struct KnnFilterWork {
-    ScopedDevBuf bpack, bnorm, qpack, qnorm, rhs, cand, count, flag;
+// What the float filter and the half-row sweep hold alike for `nq` queries at a time: the rows' norms, the packed queries and their norms,
+// the thresholds, the lists and the flag words.
+struct KnnSweepBufs {
+    ScopedDevBuf bnorm, qpack, qnorm, rhs, cand, count, flag;
     uint32_t dp, cap;
-    // the buffers, and the base set packed
-    int prepare(const KnnParams& p, uint32_t nq, uint32_t dp_, uint32_t cap_, hipStream_t s) {
+    int prepare_bufs(uint64_t n, uint32_t nq, uint32_t dp_, uint32_t cap_, size_t flag_bytes, hipStream_t s) {
         int rc;
         dp = dp_; cap = cap_;
-        if ((rc = bpack.ensure((size_t)p.n * dp * 4))) return rc;       // 2 dp bf16 per row
-        if ((rc = bnorm.ensure(((size_t)p.n + 64) * 4))) return rc;  // (+inf behind the last row: the filter reads whole blocks of 32)
-        if ((rc = qpack.ensure((size_t)nq * dp * 4))) return rc;
+        if ((rc = bnorm.ensure(((size_t)n + 64) * 4))) return rc;  // (+inf behind the last row: a sweep reads whole blocks of 32)
+        if ((rc = qpack.ensure((size_t)nq * dp * 4))) return rc;   // 2 dp 16-bit parts per query
         if ((rc = qnorm.ensure((size_t)nq * 4))) return rc;
         if ((rc = rhs.ensure((size_t)nq * 4))) return rc;
         if ((rc = cand.ensure((size_t)nq * cap * 4))) return rc;
         if ((rc = count.ensure((size_t)nq * 4))) return rc;
-        if ((rc = flag.ensure(4))) return rc;
-        HIP_TRY(launch_fill_u32(bnorm.as<uint32_t>() + p.n, 0x7F800000u, 64, s));
+        if ((rc = flag.ensure(flag_bytes))) return rc;
+        HIP_TRY(launch_fill_u32(bnorm.as<uint32_t>() + n, 0x7F800000u, 64, s));
+        return GBNNS_OK;
+    }
+};
+
+// The matrix-core filter's operands and lists (knn.hip) for `nq` queries at a time: the heap-filter path's whole call, a slab of the pool path.
+struct KnnFilterWork : KnnSweepBufs {
+    ScopedDevBuf bpack;
+    // the buffers, and the base set packed
+    int prepare(const KnnParams& p, uint32_t nq, uint32_t dp_, uint32_t cap_, hipStream_t s) {
+        int rc;
+        if ((rc = prepare_bufs(p.n, nq, dp_, cap_, 4, s))) return rc;
+        if ((rc = bpack.ensure((size_t)p.n * dp * 4))) return rc;       // 2 dp bf16 per row
         HIP_TRY(launch_knn_pack(p.base, p.bstride, p.dim, p.n, bpack.as<uint16_t>(), bnorm.as<float>(), s));
         return GBNNS_OK;
     }
@@ -305,27 +316,21 @@ KnnHalfPlan knn_half_plan(uint64_t n, uint64_t nq, uint32_t d, int k, int metric
 
 // The same for binary16 rows (knn_half.hip): nothing of the table is packed -- the sweep reads it in place, or a copy where its stride is
 // no multiple of 8 halves --; the query side is the scaled hi + lo split.
-struct KnnHalfWork {
-    ScopedDevBuf copy, bnorm, qpack, qinv, qnorm, rhs, cand, count, flag;
-    uint32_t dp, cap, stride, last_chunk;
+struct KnnHalfWork : KnnSweepBufs {
+    ScopedDevBuf copy, qinv;
+    uint32_t stride, last_chunk;
     const uint16_t* table;
     int prepare(const KnnParams& p, uint32_t nq, uint32_t dp_, uint32_t cap_, hipStream_t s) {
         int rc;
-        dp = dp_; cap = cap_; table = p.base_h; stride = p.bstride; last_chunk = (p.dim + 7u) / 8u - 1u;
+        // flag: [0] a list overflowed; [1] pack_queries' range flag (the call asked queries_covered before)
+        if ((rc = prepare_bufs(p.n, nq, dp_, cap_, 8, s))) return rc;
+        table = p.base_h; stride = p.bstride; last_chunk = (p.dim + 7u) / 8u - 1u;
         if (stride % 8 != 0) {
             if ((rc = copy.ensure((size_t)p.n * dp * 2))) return rc;
             HIP_TRY(launch_knn_half_pack(p.base_h, p.bstride, p.dim, dp, p.n, copy.as<uint16_t>(), s));
             table = copy.as<uint16_t>(); stride = dp;
         }
-        if ((rc = bnorm.ensure(((size_t)p.n + 64) * 4))) return rc;  // (+inf behind the last row: the sweep reads whole blocks of 32)
-        if ((rc = qpack.ensure((size_t)nq * dp * 4))) return rc;     // 2 dp halves per query
         if ((rc = qinv.ensure((size_t)nq * 4))) return rc;
-        if ((rc = qnorm.ensure((size_t)nq * 4))) return rc;
-        if ((rc = rhs.ensure((size_t)nq * 4))) return rc;
-        if ((rc = cand.ensure((size_t)nq * cap * 4))) return rc;
-        if ((rc = count.ensure((size_t)nq * 4))) return rc;
-        if ((rc = flag.ensure(8))) return rc;  // [0] a list overflowed; [1] pack_queries' range flag (the call asked queries_covered before)
-        HIP_TRY(launch_fill_u32(bnorm.as<uint32_t>() + p.n, 0x7F800000u, 64, s));
         HIP_TRY(launch_knn_half_norms(p.base_h, p.bstride, p.dim, p.n, bnorm.as<float>(), s));
         return GBNNS_OK;
     }

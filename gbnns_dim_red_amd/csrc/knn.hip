@@ -22,6 +22,7 @@
 #include "kernels.h"
 #include "knn_select.h"  // the distance keys, the heap, the radix select (shared with knn_bytes.hip)
 #include "knn_scan_dist.h"  // f32x2, the tile and workgroup sizes (shared with knn_gather.hip)
+#include "knn_sweep.h"  // the matrix-core sweep's skeleton (shared with knn_bytes.hip and knn_half.hip)
 #include "knn_scan_kernels.h"  // the scan, rescore and pool kernels, templates over the rows' element (shared with knn_half.hip): the float instances
 
 namespace gbnns {
@@ -97,163 +98,51 @@ __global__ __launch_bounds__(256) void knn_pack_kernel(const float* x, uint32_t 
     }
 }
 
-// A workgroup = 4 wavefronts x QB blocks of 32 queries (operand B of the product, in registers for the whole launch: the
-// lane's column of every 32 x 32 tile is ITS query, so one threshold per lane and block); blockIdx.y picks a slab of the
-// chunk's rows, walked in blocks of 32 (operand A straight from global memory, the next block's fragments requested
-// before the current block's products: a 32 K-row chunk of packed rows is 4 MB at d = 32, L2 / Infinity-Cache resident
-// while every workgroup sweeps it).  The accumulators start at -0.5 (1 - c) |x|^2 of their rows (16 rows of the block
-// per lane: four float4 loads of the norms), so a kept pair is  max over the lane's 16 rows >= rhs[query]  -- eight
-// v_max3 and one compare per tile beside its six matrix instructions.
-// TAG (gbnns_exact_knn_tagged): a pair whose row is not allowed for its query is not a hit -- neither counted nor stored.  The tag words of
-// a lane's 16 rows travel with the block's norms (four more 16-byte requests, the same address pattern; the array is padded like bnorm)
-// and are looked at where hits are counted: under a selective filter a query's threshold is its k-th ALLOWED distance, rows of every
-// tile pass it, and a fetch in the hit path was a dependent load in most tiles (DESIGN.md 5.1 has both measurements).
-template <int KSTEPS, int QB, bool TAG>
-__global__ __launch_bounds__(256) void knn_filter_kernel(KnnFilterParams p) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t r = lane & 31, h = lane >> 5;
-    const uint32_t q0 = (blockIdx.x * 4u + wave) * (QB * 32u);
-    if (q0 >= p.nq) return;
-    const uint32_t groups = p.dp >> 3;  // 8-dim groups per row = 2 KSTEPS
-    // B fragments: query q0 + 32 b + r, k = 16 s + 8 h .. + 7 -> group 2 s + h: hi at halfword 16 (2 s + h), lo 8 further
-    bf16x8 qh[QB][KSTEPS], ql[QB][KSTEPS];
-    float rhs[QB];
-    uint32_t qtag[QB];
+// The sweep (knn_sweep.h has the division of work, the hand-issued loads and the hit path): rows and queries as packed bf16 hi / lo pairs,
+// three products per K step -- xh.qh + xl.qh + xh.ql -- on accumulators that start at -0.5 (1 - c) |x|^2 of their rows, so a value is
+// q.x - 0.5 (1 - c) |x|^2 and a pair is kept when it is >= rhs[query]; the kept id goes to the rescore.
+struct KnnFilterOps {
+    typedef KnnFilterParams Params;
+    typedef float Val;
+    typedef f32x16 Vals;
+    struct Q { float thr; };
+    static constexpr int kQFrags = 2, kRowFrags = 2;  // hi, and lo 16 bytes further
+    static constexpr bool kKeepsValue = false;
+    static __device__ __forceinline__ Q load_q(const Params& p, uint32_t qi, bool ok) { return Q{ok ? p.rhs[qi] : __builtin_inff()}; }
+    static __device__ __forceinline__ void use_q(const Q& q) { asm volatile("" ::"v"(q.thr)); }
+    // fragments of K step s = group 2 s + h of 8 dims: hi at halfword 16 (2 s + h) of the packed row, lo 8 further; 64 bytes per K step
+    static __device__ __forceinline__ const uint4* q_ptr(const Params& p, uint32_t qi) {
+        return reinterpret_cast<const uint4*>(p.qpack + (size_t)qi * (p.dp >> 3) * 16);
+    }
+    static __device__ __forceinline__ const char* row_ptr(const Params& p, uint32_t j, uint32_t h) {
+        return reinterpret_cast<const char*>(p.bpack + ((size_t)j * (p.dp >> 3) + h) * 16);
+    }
+    static __device__ __forceinline__ uint32_t row_off(const Params&, int s, uint32_t) { return 64u * (uint32_t)s; }
+    static __device__ __forceinline__ const uint32_t* side(const Params& p) { return reinterpret_cast<const uint32_t*>(p.bnorm); }
+    static __device__ __forceinline__ Vals rows_init(const knn_u32x4 (&nx)[4]) {
+        const float scale = -0.5f * (1.0f - kKnnFilterSlack);
+        Vals c;
 #pragma unroll
-    for (int b = 0; b < QB; ++b) {
-        const uint32_t qi = q0 + 32u * b + r;
-        const bool ok = qi < p.nq;
-        if constexpr (TAG) qtag[b] = ok ? p.qtag[qi] : 0u;
-        const uint16_t* qp = p.qpack + (size_t)(ok ? qi : 0u) * groups * 16;
+        for (int v = 0; v < 16; ++v) c[v] = scale * __uint_as_float(nx[v >> 2][v & 3]);
+        return c;
+    }
+    template <int KSTEPS>
+    static __device__ __forceinline__ Vals tile(const Params&, const knn_u32x4 (&x)[2 * KSTEPS], Vals acc, const knn_u32x4 (&qf)[2 * KSTEPS], const Q&) {
 #pragma unroll
         for (int s = 0; s < KSTEPS; ++s) {
-            const uint4* src = reinterpret_cast<const uint4*>(qp + (size_t)(2 * s + h) * 16);
-            qh[b][s] = __builtin_bit_cast(bf16x8, src[0]);
-            ql[b][s] = __builtin_bit_cast(bf16x8, src[1]);
+            const bf16x8 xh = __builtin_bit_cast(bf16x8, x[2 * s]), xl = __builtin_bit_cast(bf16x8, x[2 * s + 1]);
+            const bf16x8 qh = __builtin_bit_cast(bf16x8, qf[2 * s]), ql = __builtin_bit_cast(bf16x8, qf[2 * s + 1]);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, qh, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl, qh, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, ql, acc, 0, 0, 0);
         }
-        rhs[b] = ok ? p.rhs[qi] : __builtin_inff();  // (a query beyond the batch keeps nothing)
+        return acc;
     }
-    // (every compiler-issued load is used here, once: its waits then sit in this prologue and not inside the sweep)
-#pragma unroll
-    for (int b = 0; b < QB; ++b) {
-        asm volatile("" ::"v"(rhs[b]));
-        if constexpr (TAG) asm volatile("" ::"v"(qtag[b]));
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) asm volatile("" ::"v"(qh[b][s]), "v"(ql[b][s]));
-    }
-    const uint32_t blocks = (p.rows + 31u) >> 5;
-    const uint32_t per = (blocks + gridDim.y - 1) / gridDim.y;
-    const uint32_t b_lo = blockIdx.y * per, b_hi = min(blocks, b_lo + per);
-    if (b_lo >= b_hi) return;
-    const float scale = -0.5f * (1.0f - kKnnFilterSlack);
-    // Fragments and norms of one block of 32 rows (rows beyond the chunk read row 0), requested by hand-written loads: the
-    // compiler's own bookkeeping put a full wait (vmcnt(0)) BEHIND the next block's requests -- no overlap at all --
-    // whatever the order in the source; these requests are invisible to it, and `landed` below is the one wait, placed in
-    // front of the next requests.  (No branch here: the norms' array is readable 64 entries beyond the set and +inf
-    // there, and the chunk starts on a multiple of 64 rows; a row of the NEXT chunk that slips through the test is
-    // refused where the hits are stored.)
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    typedef float f32x4v __attribute__((ext_vector_type(4)));
-    auto request_block = [&](uint32_t rb, u32x4 (&xh)[KSTEPS], u32x4 (&xl)[KSTEPS], f32x4v (&nx)[4], u32x4 (&tg)[4]) {
-        const uint32_t j = rb * 32u + r;
-        const uint16_t* bp = p.bpack + ((size_t)(j < p.rows ? j : 0u) * groups + h) * 16;
-        const float* np = p.bnorm + rb * 32u + 4u * h;
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) {  // group 2 s + h: 64 bytes per K step further on
-            asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(xh[s]) : "v"(bp + 32 * s));
-            asm volatile("global_load_dwordx4 %0, %1, off offset:16" : "=v"(xl[s]) : "v"(bp + 32 * s));
-        }
-#pragma unroll
-        for (int g = 0; g < 4; ++g)  // accumulator registers 4 g .. 4 g + 3 = rows 8 g + 4 h + 0 .. 3 of the block
-            asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(nx[g]) : "v"(np + 8 * g));
-        if constexpr (TAG) {
-            const uint32_t* tp = p.btag + rb * 32u + 4u * h;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(tg[g]) : "v"(tp + 8 * g));
-        }
-    };
-    auto landed = [&](u32x4 (&xh)[KSTEPS], u32x4 (&xl)[KSTEPS], f32x4v (&nx)[4], u32x4 (&tg)[4]) {
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(nx[0]));
-#pragma unroll
-        for (int g = 1; g < 4; ++g) asm volatile("" : "+v"(nx[g]));
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) asm volatile("" : "+v"(xh[s]), "+v"(xl[s]));
-        if constexpr (TAG) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(tg[g]));
-        }
-    };
-    // the products and the test of one block of rows against the QB query blocks
-    auto sweep_block = [&](uint32_t rb, const u32x4 (&xhr)[KSTEPS], const u32x4 (&xlr)[KSTEPS], const f32x4v (&nx)[4], const u32x4 (&tg)[4]) {
-        bf16x8 xh[KSTEPS], xl[KSTEPS];
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) { xh[s] = __builtin_bit_cast(bf16x8, xhr[s]); xl[s] = __builtin_bit_cast(bf16x8, xlr[s]); }
-        f32x16 cinit;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            cinit[4 * g + 0] = scale * nx[g].x; cinit[4 * g + 1] = scale * nx[g].y;
-            cinit[4 * g + 2] = scale * nx[g].z; cinit[4 * g + 3] = scale * nx[g].w;
-        }
-#pragma unroll
-        for (int b = 0; b < QB; ++b) {
-            f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh[0], qh[b][0], cinit, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl[0], qh[b][0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh[0], ql[b][0], acc, 0, 0, 0);
-#pragma unroll
-            for (int s = 1; s < KSTEPS; ++s) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh[s], qh[b][s], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl[s], qh[b][s], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh[s], ql[b][s], acc, 0, 0, 0);
-            }
-            float m = fmaxf(fmaxf(acc[0], acc[1]), acc[2]);
-#pragma unroll
-            for (int v = 3; v < 15; v += 2) m = fmaxf(fmaxf(m, acc[v]), acc[v + 1]);
-            m = fmaxf(m, acc[15]);
-            if (__builtin_expect(__ballot(m >= rhs[b]) != 0ull, 0)) {
-                // one returning atomic per lane with hits (its 16 rows of the tile): the places of all of them at once -- a
-                // returning atomic per hit serialised up to sixteen memory round trips in every tile that had any, and in
-                // the early chunks (thresholds still loose) that is most tiles
-                const uint32_t qv = q0 + 32u * b + r;   // (rhs = +inf beyond the batch: never here with qv >= nq)
-                uint32_t hits = 0;
-#pragma unroll
-                for (int v = 0; v < 16; ++v) {
-                    const uint32_t j = rb * 32u + (uint32_t)((v & 3) + 8 * (v >> 2)) + 4u * h;
-                    hits |= (acc[v] >= rhs[b] && j < p.rows) ? 1u << v : 0u;  // (a threshold of -inf -- list not full yet -- lets -inf through too)
-                }
-                if constexpr (TAG) {
-                    uint32_t tm = 0;
-#pragma unroll
-                    for (int v = 0; v < 16; ++v) tm |= ((tg[v >> 2][v & 3] & qtag[b]) ? 1u : 0u) << v;
-                    hits &= tm;
-                }
-                if (hits) {
-                    uint32_t pos = atomicAdd(&p.count[qv], (uint32_t)__popc(hits));
-                    do {
-                        const uint32_t v = (uint32_t)__ffs((int)hits) - 1u;
-                        hits &= hits - 1u;
-                        if (pos < p.cap) p.cand[(size_t)qv * p.cap + pos] = p.row0 + rb * 32u + ((v & 3u) + 8u * (v >> 2)) + 4u * h;
-                        else *p.overflow = 1u;
-                        pos += 1u;
-                    } while (hits);
-                }
-            }
-        }
-    };
-    // two register sets in turn: wait for the set at hand, request the next block into the other one, sweep
-    u32x4 xh0[KSTEPS], xl0[KSTEPS], xh1[KSTEPS], xl1[KSTEPS];
-    f32x4v nx0[4], nx1[4];
-    u32x4 tg0[4], tg1[4];
-    request_block(b_lo, xh0, xl0, nx0, tg0);
-    for (uint32_t rb = b_lo;;) {
-        landed(xh0, xl0, nx0, tg0);
-        if (rb + 1u < b_hi) request_block(rb + 1u, xh1, xl1, nx1, tg1);
-        sweep_block(rb, xh0, xl0, nx0, tg0);
-        if (++rb >= b_hi) break;
-        landed(xh1, xl1, nx1, tg1);
-        if (rb + 1u < b_hi) request_block(rb + 1u, xh0, xl0, nx0, tg0);
-        sweep_block(rb, xh1, xl1, nx1, tg1);
-        if (++rb >= b_hi) break;
-    }
+    static __device__ __forceinline__ uint32_t kept(const Q&, uint32_t id, float) { return id; }
+};
+template <int KSTEPS, int QB, bool TAG>
+__global__ __launch_bounds__(256) void knn_filter_kernel(KnnFilterParams p) {
+    knn_sweep_body<KnnFilterOps, KSTEPS, QB, TAG>(p);
 }
 
 __global__ __launch_bounds__(256) void knn_thresholds_kernel(const uint64_t* heap, int k, const float* qnorm, uint32_t nq, float* rhs) {
@@ -315,45 +204,13 @@ __global__ __launch_bounds__(64) void knn_pool_finalize_kernel(KnnPoolParams p) 
     }
 }
 
-template <int KSTEPS, int QB, bool TAG>
-hipError_t launch_knn_filter_tt(const KnnFilterParams& p, hipStream_t s) {
-    const unsigned gx = (p.nq + QB * 128u - 1) / (QB * 128u);
-    const unsigned blocks = (p.rows + 31u) >> 5;
-    static const unsigned simds = [] {  // 4 SIMDs per CU of the current device (the MI355X: 1 024)
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        return 4u * (unsigned)cus;
-    }();
-    unsigned gy = gx >= simds ? 1u : (simds + gx - 1) / gx;   // enough workgroups for every SIMD
-    if (gy > blocks) gy = blocks;
-    if (gy < 1u) gy = 1u;
-    hipLaunchKernelGGL((knn_filter_kernel<KSTEPS, QB, TAG>), dim3(gx, gy), dim3(256), 0, s, p);
-    return hipGetLastError();
-}
-
-// The filter instance of a packed row length, launch and name from one place: K steps of 16; query blocks per wavefront by what the
-// operands leave of the register file.
-struct KnnFilterPick {
-    hipError_t (*launch)(const KnnFilterParams&, hipStream_t);
-    const char* name;
-};
-#define KNN_FILTER(K, QB)                                                                                                   \
-    (tagged ? KnnFilterPick{&launch_knn_filter_tt<K, QB, true>, "knn_filter_kernel<" #K ", " #QB ", true>"} \
-            : KnnFilterPick{&launch_knn_filter_tt<K, QB, false>, "knn_filter_kernel<" #K ", " #QB ", false>"})
-KnnFilterPick knn_filter_pick(uint32_t dp, bool tagged) {
-    switch (dp >> 4) {
-        case 1: return KNN_FILTER(1, 4);
-        case 2: return KNN_FILTER(2, 4);
-        case 3: return KNN_FILTER(3, 2);
-        case 4: return KNN_FILTER(4, 2);
-        case 5: return KNN_FILTER(5, 1);
-        case 6: return KNN_FILTER(6, 1);
-        case 7: return KNN_FILTER(7, 1);
-        case 8: return KNN_FILTER(8, 1);
-        default: return KnnFilterPick{nullptr, nullptr};
-    }
-}
-#undef KNN_FILTER
+// K steps of 16 dims
+KNN_SWEEP_PICK_FN(knn_filter_pick, knn_filter_kernel, KnnFilterParams, 16, KNN_SWEEP_QB_TWO_PART)
+#undef KNN_SWEEP_PICK_FN
+#undef KNN_SWEEP_PICK_FN_
+#undef KNN_SWEEP_CASE_
+#undef KNN_SWEEP_INSTANCE_
+#undef KNN_SWEEP_QB_TWO_PART
 }  // namespace
 
 hipError_t launch_knn_scan(const KnnParams& p, int metric, hipStream_t s) {
@@ -375,7 +232,7 @@ hipError_t launch_knn_pack(const float* x, uint32_t stride, uint32_t dim, uint64
 hipError_t launch_knn_filter(const KnnFilterParams& p, hipStream_t s) {
     if (p.nq == 0 || p.rows == 0) return hipSuccess;
     if (p.btag && !p.qtag) return hipErrorInvalidValue;
-    const KnnFilterPick k = knn_filter_pick(p.dp, p.btag != nullptr);
+    const auto k = knn_filter_pick(p.dp, p.btag != nullptr);
     return k.launch ? k.launch(p, s) : hipErrorInvalidValue;
 }
 const char* knn_filter_kernel_name(uint32_t dp, bool tagged) { return knn_filter_pick(dp, tagged).name; }

@@ -19,6 +19,7 @@
 
 #include "kernels.h"
 #include "knn_select.h"
+#include "knn_sweep.h"
 
 namespace gbnns {
 
@@ -71,134 +72,53 @@ __device__ __forceinline__ int32_t knn_bytes_thr(uint64_t root, int32_t qterm) {
     return root == ~0ull ? kPassAll : qterm - (int32_t)knn_fkey_inv((uint32_t)(root >> 32));
 }
 
-// A workgroup = 4 wavefronts x QB blocks of 32 queries (operand B, in registers for the whole launch: the lane's column
-// of every 32 x 32 tile is ITS query, so one threshold per lane and block); blockIdx.y picks a slab of the chunk's rows,
-// walked in blocks of 32 (operand A straight from global memory, the next block requested before the current block's
-// products).  Lane (r, h) holds row / query r and the 16 bytes 32 s + 16 h .. + 15 of K step s for both operands: whatever
-// order the instruction gives those 16 + 16 columns, it is the same for A and B, and a dot product does not see it.
-// C/D: register v of lane (r, h) = row (v & 3) + 8 (v >> 2) + 4 h of the block, column r.
-// TAG (gbnns_exact_knn_bytes_tagged): a pair whose row is not allowed for its query -- (btag[row] & qtag[query]) == 0 -- is not a hit.  The
-// tag words of a lane's 16 rows travel with the block's terms (four more 16-byte requests, same address pattern, the array padded like
-// bterm) and are looked at where hits are counted, as in knn_filter_kernel: DESIGN.md 5.1 has the measurement against a fetch there.
+// The sweep (knn_sweep.h has the division of work, the hand-issued loads and the hit path): lane (r, h) holds the 16 bytes
+// 32 s + 16 h .. + 15 of K step s for both operands -- whatever order the instruction gives those 16 + 16 columns, it is the same for A
+// and B, and a dot product does not see it.  A value is s = (x'.q' << shift) + bterm, kept when s >= thr[query], i.e. distance <= T_q;
+// the kept pair is stored as its key: the distance qterm - s is final.
+struct KnnBytesOps {
+    typedef KnnBytesSweepParams Params;
+    typedef int32_t Val;
+    typedef i32x16 Vals;
+    struct Q { int32_t thr, qterm; };
+    static constexpr int kQFrags = 1, kRowFrags = 1;
+    static constexpr bool kKeepsValue = true;
+    // (a query beyond the batch keeps nothing: s never reaches INT32_MAX)
+    static __device__ __forceinline__ Q load_q(const Params& p, uint32_t qi, bool ok) { return Q{ok ? p.thr[qi] : kPassNone, ok ? p.qterm[qi] : 0}; }
+    static __device__ __forceinline__ void use_q(const Q& q) { asm volatile("" ::"v"(q.thr), "v"(q.qterm)); }
+    static __device__ __forceinline__ const uint4* q_ptr(const Params& p, uint32_t qi) {
+        return reinterpret_cast<const uint4*>(p.qpack + (size_t)qi * p.dp);
+    }
+    static __device__ __forceinline__ const char* row_ptr(const Params& p, uint32_t j, uint32_t h) {
+        return reinterpret_cast<const char*>(p.bpack + (size_t)j * p.dp + 16u * h);
+    }
+    static __device__ __forceinline__ uint32_t row_off(const Params&, int s, uint32_t) { return 32u * (uint32_t)s; }
+    static __device__ __forceinline__ const uint32_t* side(const Params& p) { return reinterpret_cast<const uint32_t*>(p.bterm); }
+    static __device__ __forceinline__ Vals rows_init(const knn_u32x4 (&bt)[4]) {
+        Vals c;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) c[v] = (int32_t)bt[v >> 2][v & 3];
+        return c;
+    }
+    template <int KSTEPS>
+    static __device__ __forceinline__ Vals tile(const Params& p, const knn_u32x4 (&x)[KSTEPS], const Vals& bterm, const knn_u32x4 (&qf)[KSTEPS], const Q&) {
+        i32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int s = 0; s < KSTEPS; ++s)
+            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4, x[s]), __builtin_bit_cast(i32x4, qf[s]), acc, 0, 0, 0);
+        Vals sv;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) sv[v] = (int32_t)((uint32_t)acc[v] << p.shift) + bterm[v];  // distance = qterm - sv
+        return sv;
+    }
+    static __device__ __forceinline__ uint64_t kept(const Q& q, uint32_t id, int32_t sv) {
+        const float dist = (float)(q.qterm - sv);  // exact: an integer of magnitude < 2^24
+        return ((uint64_t)knn_fkey(dist) << 32) | id;
+    }
+};
 template <int KSTEPS, int QB, bool TAG>
 __global__ __launch_bounds__(256) void knn_bytes_sweep_kernel(KnnBytesSweepParams p) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t r = lane & 31, h = lane >> 5;
-    const uint32_t q0 = (blockIdx.x * 4u + wave) * (QB * 32u);
-    if (q0 >= p.nq) return;
-    i32x4 qf[QB][KSTEPS];
-    int32_t thr[QB], qterm[QB];
-    uint32_t qtag[QB];
-#pragma unroll
-    for (int b = 0; b < QB; ++b) {
-        const uint32_t qi = q0 + 32u * b + r;
-        const bool ok = qi < p.nq;
-        const int8_t* qp = p.qpack + (size_t)(ok ? qi : 0u) * p.dp + 16u * h;
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) qf[b][s] = *reinterpret_cast<const i32x4*>(qp + 32 * s);
-        thr[b] = ok ? p.thr[qi] : kPassNone;  // (a query beyond the batch keeps nothing: s never reaches INT32_MAX)
-        qterm[b] = ok ? p.qterm[qi] : 0;
-        if constexpr (TAG) qtag[b] = ok ? p.qtag[qi] : 0u;
-    }
-    // (every compiler-issued load is used here, once: its waits then sit in this prologue and not inside the sweep)
-#pragma unroll
-    for (int b = 0; b < QB; ++b) {
-        asm volatile("" ::"v"(thr[b]), "v"(qterm[b]));
-        if constexpr (TAG) asm volatile("" ::"v"(qtag[b]));
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) asm volatile("" ::"v"(qf[b][s]));
-    }
-    const uint32_t blocks = (p.rows + 31u) >> 5;
-    const uint32_t per = (blocks + gridDim.y - 1) / gridDim.y;
-    const uint32_t b_lo = blockIdx.y * per, b_hi = min(blocks, b_lo + per);
-    if (b_lo >= b_hi) return;
-    // Fragments and terms of one block of 32 rows (rows beyond the chunk read row 0; the terms' array is readable 64
-    // entries beyond the set; such a row is refused where the hits are stored), requested by hand-written loads, as in
-    // knn_filter_kernel (knn.hip): `landed` is the one wait, placed in front of the next requests.
-    auto request_block = [&](uint32_t rb, i32x4 (&xa)[KSTEPS], i32x4 (&bt)[4], i32x4 (&tg)[4]) {
-        const uint32_t j = rb * 32u + r;
-        const int8_t* bp = p.bpack + (size_t)(j < p.rows ? j : 0u) * p.dp + 16u * h;
-        const int32_t* np = p.bterm + rb * 32u + 4u * h;
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(xa[s]) : "v"(bp + 32 * s));
-#pragma unroll
-        for (int g = 0; g < 4; ++g)  // accumulator registers 4 g .. 4 g + 3 = rows 8 g + 4 h + 0 .. 3 of the block
-            asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(bt[g]) : "v"(np + 8 * g));
-        if constexpr (TAG) {
-            const uint32_t* tp = p.btag + rb * 32u + 4u * h;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(tg[g]) : "v"(tp + 8 * g));
-        }
-    };
-    auto landed = [&](i32x4 (&xa)[KSTEPS], i32x4 (&bt)[4], i32x4 (&tg)[4]) {
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(bt[0]));
-#pragma unroll
-        for (int g = 1; g < 4; ++g) asm volatile("" : "+v"(bt[g]));
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) asm volatile("" : "+v"(xa[s]));
-        if constexpr (TAG) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(tg[g]));
-        }
-    };
-    const i32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    auto sweep_block = [&](uint32_t rb, const i32x4 (&xa)[KSTEPS], const i32x4 (&bt)[4], const i32x4 (&tg)[4]) {
-#pragma unroll
-        for (int b = 0; b < QB; ++b) {
-            i32x16 acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(xa[0], qf[b][0], zero, 0, 0, 0);
-#pragma unroll
-            for (int s = 1; s < KSTEPS; ++s) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(xa[s], qf[b][s], acc, 0, 0, 0);
-            int32_t sv[16];
-#pragma unroll
-            for (int v = 0; v < 16; ++v) sv[v] = (int32_t)((uint32_t)acc[v] << p.shift) + bt[v >> 2][v & 3];  // distance = qterm - sv
-            int32_t m = max(max(sv[0], sv[1]), sv[2]);
-#pragma unroll
-            for (int v = 3; v < 15; v += 2) m = max(max(m, sv[v]), sv[v + 1]);
-            m = max(m, sv[15]);
-            if (__builtin_expect(__ballot(m >= thr[b]) != 0ull, 0)) {
-                // one returning atomic per lane with hits (its 16 rows of the tile): the places of all of them at once
-                const uint32_t qv = q0 + 32u * b + r;  // (thr = INT32_MAX beyond the batch: never here with qv >= nq)
-                uint32_t hits = 0;
-#pragma unroll
-                for (int v = 0; v < 16; ++v) {
-                    const uint32_t j = rb * 32u + (uint32_t)((v & 3) + 8 * (v >> 2)) + 4u * h;
-                    hits |= (sv[v] >= thr[b] && j < p.rows) ? 1u << v : 0u;
-                }
-                if constexpr (TAG) {
-                    uint32_t m = 0;
-#pragma unroll
-                    for (int v = 0; v < 16; ++v) m |= (((uint32_t)tg[v >> 2][v & 3] & qtag[b]) ? 1u : 0u) << v;
-                    hits &= m;
-                }
-                if (hits) {
-                    uint32_t pos = atomicAdd(&p.count[qv], (uint32_t)__popc(hits));
-#pragma unroll
-                    for (int v = 0; v < 16; ++v) {
-                        if (hits & (1u << v)) {
-                            const uint32_t id = p.row0 + rb * 32u + (uint32_t)((v & 3) + 8 * (v >> 2)) + 4u * h;
-                            const float dist = (float)(qterm[b] - sv[v]);  // exact: an integer of magnitude < 2^24
-                            if (pos < p.cap) p.cand[(size_t)qv * p.cap + pos] = ((uint64_t)knn_fkey(dist) << 32) | id;
-                            else *p.overflow = 1u;
-                            pos += 1u;
-                        }
-                    }
-                }
-            }
-        }
-    };
-    // two register sets in turn: wait for the set at hand, request the next block into the other one, sweep
-    i32x4 xa0[KSTEPS], xa1[KSTEPS], bt0[4], bt1[4], tg0[4], tg1[4];
-    request_block(b_lo, xa0, bt0, tg0);
-    for (uint32_t rb = b_lo;;) {
-        landed(xa0, bt0, tg0);
-        if (rb + 1u < b_hi) request_block(rb + 1u, xa1, bt1, tg1);
-        sweep_block(rb, xa0, bt0, tg0);
-        if (++rb >= b_hi) break;
-        landed(xa1, bt1, tg1);
-        if (rb + 1u < b_hi) request_block(rb + 1u, xa0, bt0, tg0);
-        sweep_block(rb, xa1, bt1, tg1);
-        if (++rb >= b_hi) break;
-    }
+    knn_sweep_body<KnnBytesOps, KSTEPS, QB, TAG>(p);
 }
 
 // One thread per query: the keys the sweep kept, offered to the query's heap (knn_rescore_kernel of knn.hip without the
@@ -264,46 +184,13 @@ hipError_t launch_pack_t(const uint8_t* x, uint32_t stride, uint32_t dim, uint32
     return hipGetLastError();
 }
 
-template <int KSTEPS, int QB, bool TAG>
-hipError_t launch_sweep_tt(const KnnBytesSweepParams& p, hipStream_t s) {
-    const unsigned gx = (p.nq + QB * 128u - 1) / (QB * 128u);
-    const unsigned blocks = (p.rows + 31u) >> 5;
-    static const unsigned simds = [] {  // 4 SIMDs per CU of the current device (the MI355X: 1 024)
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        return 4u * (unsigned)cus;
-    }();
-    unsigned gy = gx >= simds ? 1u : (simds + gx - 1) / gx;  // enough workgroups for every SIMD
-    if (gy > blocks) gy = blocks;
-    if (gy < 1u) gy = 1u;
-    hipLaunchKernelGGL((knn_bytes_sweep_kernel<KSTEPS, QB, TAG>), dim3(gx, gy), dim3(256), 0, s, p);
-    return hipGetLastError();
-}
-
-// The sweep instance of a packed row length, launch and name from one place: K steps of 32; query blocks per wavefront by what the
-// operands leave of the register file.
-struct KnnBytesSweepPick {
-    hipError_t (*launch)(const KnnBytesSweepParams&, hipStream_t);
-    const char* name;
-};
-#define KNN_BYTES_SWEEP(K, QB)                                                                                              \
-    (tagged ? KnnBytesSweepPick{&launch_sweep_tt<K, QB, true>, "knn_bytes_sweep_kernel<" #K ", " #QB ", true>"} \
-            : KnnBytesSweepPick{&launch_sweep_tt<K, QB, false>, "knn_bytes_sweep_kernel<" #K ", " #QB ", false>"})
-KnnBytesSweepPick knn_bytes_sweep_pick(uint32_t dp, bool tagged) {
-    if (dp % kKnnBytesKStep) return KnnBytesSweepPick{nullptr, nullptr};
-    switch (dp / kKnnBytesKStep) {
-        case 1: return KNN_BYTES_SWEEP(1, 4);
-        case 2: return KNN_BYTES_SWEEP(2, 4);
-        case 3: return KNN_BYTES_SWEEP(3, 4);
-        case 4: return KNN_BYTES_SWEEP(4, 4);
-        case 5: return KNN_BYTES_SWEEP(5, 2);
-        case 6: return KNN_BYTES_SWEEP(6, 2);
-        case 7: return KNN_BYTES_SWEEP(7, 2);
-        case 8: return KNN_BYTES_SWEEP(8, 2);
-        default: return KnnBytesSweepPick{nullptr, nullptr};
-    }
-}
-#undef KNN_BYTES_SWEEP
+// K steps of 32 bytes; one 16-byte B fragment per step: twice the query blocks of the two-part sweeps
+KNN_SWEEP_PICK_FN(knn_bytes_sweep_pick, knn_bytes_sweep_kernel, KnnBytesSweepParams, kKnnBytesKStep, 4, 4, 4, 4, 2, 2, 2, 2)
+#undef KNN_SWEEP_PICK_FN
+#undef KNN_SWEEP_PICK_FN_
+#undef KNN_SWEEP_CASE_
+#undef KNN_SWEEP_INSTANCE_
+#undef KNN_SWEEP_QB_TWO_PART
 }  // namespace
 
 hipError_t launch_knn_bytes_pack(const uint8_t* x, uint32_t stride, uint32_t dim, uint32_t dp, int metric, int query_side, uint64_t rows, int8_t* packed,
@@ -322,7 +209,7 @@ hipError_t launch_knn_bytes_pack(const uint8_t* x, uint32_t stride, uint32_t dim
 hipError_t launch_knn_bytes_sweep(const KnnBytesSweepParams& p, hipStream_t s) {
     if (p.nq == 0 || p.rows == 0) return hipSuccess;
     if (p.btag && !p.qtag) return hipErrorInvalidValue;
-    const KnnBytesSweepPick k = knn_bytes_sweep_pick(p.dp, p.btag != nullptr);
+    const auto k = knn_bytes_sweep_pick(p.dp, p.btag != nullptr);
     return k.launch ? k.launch(p, s) : hipErrorInvalidValue;
 }
 const char* knn_bytes_sweep_kernel_name(uint32_t dp, bool tagged) { return knn_bytes_sweep_pick(dp, tagged).name; }

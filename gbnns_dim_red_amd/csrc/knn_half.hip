@@ -34,6 +34,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "knn_sweep.h"
 #include "knn_scan_kernels.h"  // the scan, rescore and pool kernels: the binary16 instances
 
 namespace gbnns {
@@ -45,8 +46,6 @@ static_assert(kKnnFilterSlack >= 4.0f * kKnnHalfMaxDim / 8388608.0f + 1.0f / 327
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 // one thread per row: |x|^2 in float32 (the widened squares are exact; the sum rounds, within the bound's d 2^-24)
 __global__ __launch_bounds__(256) void knn_half_norm_kernel(const uint16_t* x, uint32_t stride, uint32_t dim, uint64_t rows, float* norms) {
@@ -124,195 +123,64 @@ __global__ __launch_bounds__(256) void knn_half_qsplit_kernel(const float* q, ui
     out[1] = b;
 }
 
-// knn_filter_kernel's division of work (knn.hip): a workgroup = 4 wavefronts x QB blocks of 32 queries, operand B (hi and lo of the scaled
-// query) in registers for the whole launch; blockIdx.y picks a slab of the chunk's rows, walked in blocks of 32 with two register sets in
-// turn -- the next block's fragments requested before the current block's products; one returning atomic per lane with hits; ids to the
-// per-query lists.  Operand A: KSTEPS 16-byte loads per lane straight from the table (half the float filter's requests, a quarter of its
-// bytes per row).  C/D: register v of lane (r, h) = row (v & 3) + 8 (v >> 2) + 4 h of the block, column r.
-// TAG: as in knn_filter_kernel -- the tag words of a lane's 16 rows travel with the block's norms and are looked at where hits are counted.
-template <int KSTEPS, int QB, bool TAG>
-__global__ __launch_bounds__(256) void knn_half_sweep_kernel(KnnHalfSweepParams p) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t r = lane & 31, h = lane >> 5;
-    const uint32_t q0 = (blockIdx.x * 4u + wave) * (QB * 32u);
-    if (q0 >= p.nq) return;
-    const uint32_t groups = p.dp >> 3;  // 8-dim groups per query = 2 KSTEPS
-    f16x8 qh[QB][KSTEPS], ql[QB][KSTEPS];
-    float rhs[QB], qinv[QB];
-    uint32_t qtag[QB];
+// The sweep (knn_sweep.h has the division of work, the hand-issued loads and the hit path).  Operand A: one 16-byte load per K step and lane
+// straight from the table (half the float filter's requests, a quarter of its bytes per row); operand B: hi and lo of the scaled query, two
+// products per K step on accumulators that start at zero.  A value is fma(acc, 1 / s, -0.5 (1 - c) |x|^2), kept when >= rhs[query]; the
+// kept id goes to the rescore.
+struct KnnHalfOps {
+    typedef KnnHalfSweepParams Params;
+    typedef float Val;
+    typedef f32x16 Vals;
+    struct Q { float thr, qinv; };
+    static constexpr int kQFrags = 2, kRowFrags = 1;
+    static constexpr bool kKeepsValue = false;
+    static __device__ __forceinline__ Q load_q(const Params& p, uint32_t qi, bool ok) { return Q{ok ? p.rhs[qi] : __builtin_inff(), ok ? p.qinv[qi] : 0.f}; }
+    static __device__ __forceinline__ void use_q(const Q& q) { asm volatile("" ::"v"(q.thr), "v"(q.qinv)); }
+    // knn_pack_kernel's layout: group 2 s + h of 8 dims, hi then lo
+    static __device__ __forceinline__ const uint4* q_ptr(const Params& p, uint32_t qi) {
+        return reinterpret_cast<const uint4*>(p.qsplit + (size_t)qi * (p.dp >> 3) * 16);
+    }
+    static __device__ __forceinline__ const char* row_ptr(const Params& p, uint32_t j, uint32_t) {
+        return reinterpret_cast<const char*>(p.base + (size_t)j * p.stride);
+    }
+    // the lane's chunk of K step s: 2 s + h, or the row's last chunk where that lies beyond it
+    static __device__ __forceinline__ uint32_t row_off(const Params& p, int s, uint32_t h) { return 16u * min(2u * (uint32_t)s + h, p.last_chunk); }
+    static __device__ __forceinline__ const uint32_t* side(const Params& p) { return reinterpret_cast<const uint32_t*>(p.bnorm); }
+    static __device__ __forceinline__ Vals rows_init(const knn_u32x4 (&nx)[4]) {
+        const float scale = -0.5f * (1.0f - kKnnFilterSlack);
+        Vals c;
 #pragma unroll
-    for (int b = 0; b < QB; ++b) {
-        const uint32_t qi = q0 + 32u * b + r;
-        const bool ok = qi < p.nq;
-        if constexpr (TAG) qtag[b] = ok ? p.qtag[qi] : 0u;
-        const uint16_t* qp = p.qsplit + (size_t)(ok ? qi : 0u) * groups * 16;
+        for (int v = 0; v < 16; ++v) c[v] = scale * __uint_as_float(nx[v >> 2][v & 3]);
+        return c;
+    }
+    template <int KSTEPS>
+    static __device__ __forceinline__ Vals tile(const Params&, const knn_u32x4 (&xa)[KSTEPS], const Vals& cinit, const knn_u32x4 (&qf)[2 * KSTEPS], const Q& q) {
+        f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < KSTEPS; ++s) {
-            const uint4* src = reinterpret_cast<const uint4*>(qp + (size_t)(2 * s + h) * 16);
-            qh[b][s] = __builtin_bit_cast(f16x8, src[0]);
-            ql[b][s] = __builtin_bit_cast(f16x8, src[1]);
+            const f16x8 x = __builtin_bit_cast(f16x8, xa[s]);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(x, __builtin_bit_cast(f16x8, qf[2 * s]), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(x, __builtin_bit_cast(f16x8, qf[2 * s + 1]), acc, 0, 0, 0);
         }
-        rhs[b] = ok ? p.rhs[qi] : __builtin_inff();  // (a query beyond the batch keeps nothing)
-        qinv[b] = ok ? p.qinv[qi] : 0.f;
+        Vals t;  // q.x - 0.5 (1 - c) |x|^2: the scale undone and the norm added in one rounding
+#pragma unroll
+        for (int v = 0; v < 16; ++v) t[v] = __builtin_fmaf(acc[v], q.qinv, cinit[v]);
+        return t;
     }
-    // (every compiler-issued load is used here, once: its waits then sit in this prologue and not inside the sweep)
-#pragma unroll
-    for (int b = 0; b < QB; ++b) {
-        asm volatile("" ::"v"(rhs[b]), "v"(qinv[b]));
-        if constexpr (TAG) asm volatile("" ::"v"(qtag[b]));
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) asm volatile("" ::"v"(qh[b][s]), "v"(ql[b][s]));
-    }
-    const uint32_t blocks = (p.rows + 31u) >> 5;
-    const uint32_t per = (blocks + gridDim.y - 1) / gridDim.y;
-    const uint32_t b_lo = blockIdx.y * per, b_hi = min(blocks, b_lo + per);
-    if (b_lo >= b_hi) return;
-    const float scale = -0.5f * (1.0f - kKnnFilterSlack);
-    // the lane's chunk of every K step, in halves from the row's start: 2 s + h, or the row's last chunk where that lies beyond it
-    uint32_t coff[KSTEPS];
-#pragma unroll
-    for (int s = 0; s < KSTEPS; ++s) coff[s] = 8u * min(2u * (uint32_t)s + h, p.last_chunk);
-    // Fragments and norms of one block of 32 rows (rows beyond the chunk read row 0; the norms' array is readable 64 entries beyond the set
-    // and +inf there; the chunk starts on a multiple of 64 rows), requested by hand-written loads as in knn_filter_kernel: `landed` is the
-    // one wait, placed in front of the next requests.
-    auto request_block = [&](uint32_t rb, u32x4 (&xa)[KSTEPS], f32x4v (&nx)[4], u32x4 (&tg)[4]) {
-        const uint32_t j = rb * 32u + r;
-        const uint16_t* bp = p.base + (size_t)(j < p.rows ? j : 0u) * p.stride;
-        const float* np = p.bnorm + rb * 32u + 4u * h;
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(xa[s]) : "v"(bp + coff[s]));
-#pragma unroll
-        for (int g = 0; g < 4; ++g)  // accumulator registers 4 g .. 4 g + 3 = rows 8 g + 4 h + 0 .. 3 of the block
-            asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(nx[g]) : "v"(np + 8 * g));
-        if constexpr (TAG) {
-            const uint32_t* tp = p.btag + rb * 32u + 4u * h;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(tg[g]) : "v"(tp + 8 * g));
-        }
-    };
-    auto landed = [&](u32x4 (&xa)[KSTEPS], f32x4v (&nx)[4], u32x4 (&tg)[4]) {
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(nx[0]));
-#pragma unroll
-        for (int g = 1; g < 4; ++g) asm volatile("" : "+v"(nx[g]));
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) asm volatile("" : "+v"(xa[s]));
-        if constexpr (TAG) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(tg[g]));
-        }
-    };
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    // the products and the test of one block of rows against the QB query blocks
-    auto sweep_block = [&](uint32_t rb, const u32x4 (&xa)[KSTEPS], const f32x4v (&nx)[4], const u32x4 (&tg)[4]) {
-        f16x8 x[KSTEPS];
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) x[s] = __builtin_bit_cast(f16x8, xa[s]);
-        float cinit[16];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            cinit[4 * g + 0] = scale * nx[g].x; cinit[4 * g + 1] = scale * nx[g].y;
-            cinit[4 * g + 2] = scale * nx[g].z; cinit[4 * g + 3] = scale * nx[g].w;
-        }
-#pragma unroll
-        for (int b = 0; b < QB; ++b) {
-            f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(x[0], qh[b][0], zero, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(x[0], ql[b][0], acc, 0, 0, 0);
-#pragma unroll
-            for (int s = 1; s < KSTEPS; ++s) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(x[s], qh[b][s], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(x[s], ql[b][s], acc, 0, 0, 0);
-            }
-            float t[16];  // q.x - 0.5 (1 - c) |x|^2: the scale undone and the norm added in one rounding
-#pragma unroll
-            for (int v = 0; v < 16; ++v) t[v] = __builtin_fmaf(acc[v], qinv[b], cinit[v]);
-            float m = fmaxf(fmaxf(t[0], t[1]), t[2]);
-#pragma unroll
-            for (int v = 3; v < 15; v += 2) m = fmaxf(fmaxf(m, t[v]), t[v + 1]);
-            m = fmaxf(m, t[15]);
-            if (__builtin_expect(__ballot(m >= rhs[b]) != 0ull, 0)) {
-                const uint32_t qv = q0 + 32u * b + r;   // (rhs = +inf beyond the batch: never here with qv >= nq)
-                uint32_t hits = 0;
-#pragma unroll
-                for (int v = 0; v < 16; ++v) {
-                    const uint32_t j = rb * 32u + (uint32_t)((v & 3) + 8 * (v >> 2)) + 4u * h;
-                    hits |= (t[v] >= rhs[b] && j < p.rows) ? 1u << v : 0u;  // (a threshold of -inf -- list not full yet -- lets -inf through too)
-                }
-                if constexpr (TAG) {
-                    uint32_t tm = 0;
-#pragma unroll
-                    for (int v = 0; v < 16; ++v) tm |= ((tg[v >> 2][v & 3] & qtag[b]) ? 1u : 0u) << v;
-                    hits &= tm;
-                }
-                if (hits) {
-                    uint32_t pos = atomicAdd(&p.count[qv], (uint32_t)__popc(hits));
-                    do {
-                        const uint32_t v = (uint32_t)__ffs((int)hits) - 1u;
-                        hits &= hits - 1u;
-                        if (pos < p.cap) p.cand[(size_t)qv * p.cap + pos] = p.row0 + rb * 32u + ((v & 3u) + 8u * (v >> 2)) + 4u * h;
-                        else *p.overflow = 1u;
-                        pos += 1u;
-                    } while (hits);
-                }
-            }
-        }
-    };
-    // two register sets in turn: wait for the set at hand, request the next block into the other one, sweep
-    u32x4 xa0[KSTEPS], xa1[KSTEPS];
-    f32x4v nx0[4], nx1[4];
-    u32x4 tg0[4], tg1[4];
-    request_block(b_lo, xa0, nx0, tg0);
-    for (uint32_t rb = b_lo;;) {
-        landed(xa0, nx0, tg0);
-        if (rb + 1u < b_hi) request_block(rb + 1u, xa1, nx1, tg1);
-        sweep_block(rb, xa0, nx0, tg0);
-        if (++rb >= b_hi) break;
-        landed(xa1, nx1, tg1);
-        if (rb + 1u < b_hi) request_block(rb + 1u, xa0, nx0, tg0);
-        sweep_block(rb, xa1, nx1, tg1);
-        if (++rb >= b_hi) break;
-    }
-}
-
-template <int KSTEPS, int QB, bool TAG>
-hipError_t launch_half_sweep_tt(const KnnHalfSweepParams& p, hipStream_t s) {
-    const unsigned gx = (p.nq + QB * 128u - 1) / (QB * 128u);
-    const unsigned blocks = (p.rows + 31u) >> 5;
-    static const unsigned simds = [] {  // 4 SIMDs per CU of the current device (the MI355X: 1 024)
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        return 4u * (unsigned)cus;
-    }();
-    unsigned gy = gx >= simds ? 1u : (simds + gx - 1) / gx;   // enough workgroups for every SIMD
-    if (gy > blocks) gy = blocks;
-    if (gy < 1u) gy = 1u;
-    hipLaunchKernelGGL((knn_half_sweep_kernel<KSTEPS, QB, TAG>), dim3(gx, gy), dim3(256), 0, s, p);
-    return hipGetLastError();
-}
-
-// The sweep instance of a row length, launch and name from one place: K steps of 16; query blocks per wavefront by what the operands
-// leave of the register file (knn_filter_pick's table: the B operands are as many registers, the A sets half as many).
-struct KnnHalfSweepPick {
-    hipError_t (*launch)(const KnnHalfSweepParams&, hipStream_t);
-    const char* name;
+    static __device__ __forceinline__ uint32_t kept(const Q&, uint32_t id, float) { return id; }
 };
-#define KNN_HALF_SWEEP(K, QB)                                                                                          \
-    (tagged ? KnnHalfSweepPick{&launch_half_sweep_tt<K, QB, true>, "knn_half_sweep_kernel<" #K ", " #QB ", true>"} \
-            : KnnHalfSweepPick{&launch_half_sweep_tt<K, QB, false>, "knn_half_sweep_kernel<" #K ", " #QB ", false>"})
-KnnHalfSweepPick knn_half_sweep_pick(uint32_t dp, bool tagged) {
-    if (dp & 15u) return KnnHalfSweepPick{nullptr, nullptr};
-    switch (dp >> 4) {
-        case 1: return KNN_HALF_SWEEP(1, 4);
-        case 2: return KNN_HALF_SWEEP(2, 4);
-        case 3: return KNN_HALF_SWEEP(3, 2);
-        case 4: return KNN_HALF_SWEEP(4, 2);
-        case 5: return KNN_HALF_SWEEP(5, 1);
-        case 6: return KNN_HALF_SWEEP(6, 1);
-        case 7: return KNN_HALF_SWEEP(7, 1);
-        case 8: return KNN_HALF_SWEEP(8, 1);
-        default: return KnnHalfSweepPick{nullptr, nullptr};
-    }
+template <int KSTEPS, int QB, bool TAG>
+__global__ __launch_bounds__(256) void knn_half_sweep_kernel(KnnHalfSweepParams p) {
+    knn_sweep_body<KnnHalfOps, KSTEPS, QB, TAG>(p);
 }
-#undef KNN_HALF_SWEEP
+
+// K steps of 16 dims; knn_filter_pick's table: the B operands are as many registers, the A sets half as many
+KNN_SWEEP_PICK_FN(knn_half_sweep_pick, knn_half_sweep_kernel, KnnHalfSweepParams, 16, KNN_SWEEP_QB_TWO_PART)
+#undef KNN_SWEEP_PICK_FN
+#undef KNN_SWEEP_PICK_FN_
+#undef KNN_SWEEP_CASE_
+#undef KNN_SWEEP_INSTANCE_
+#undef KNN_SWEEP_QB_TWO_PART
 }  // namespace
 
 hipError_t launch_knn_half_norms(const uint16_t* x, uint32_t stride, uint32_t dim, uint64_t rows, float* norms, hipStream_t s) {
@@ -346,7 +214,7 @@ hipError_t launch_knn_half_sweep(const KnnHalfSweepParams& p, hipStream_t s) {
     // what keeps every 16-byte request inside its row: an aligned table at a stride of whole chunks that holds the last chunk read
     if ((p.stride & 7u) || (reinterpret_cast<uintptr_t>(p.base) & 15u) || 8u * (p.last_chunk + 1u) > p.stride || 8u * (p.last_chunk + 1u) > p.dp)
         return hipErrorInvalidValue;
-    const KnnHalfSweepPick k = knn_half_sweep_pick(p.dp, p.btag != nullptr);
+    const auto k = knn_half_sweep_pick(p.dp, p.btag != nullptr);
     return k.launch ? k.launch(p, s) : hipErrorInvalidValue;
 }
 const char* knn_half_sweep_kernel_name(uint32_t dp, bool tagged) { return knn_half_sweep_pick(dp, tagged).name; }
