@@ -428,7 +428,8 @@ def knn_slab(n_q, k, bytes=False):
 
 def knn_plan(bytes, metric, n, n_q, d, k, tagged=False):
     """gbnns_debug_knn_plan (no device needed): (name, pool) -- the kernel that sweeps the rows of an exact_knn call of that shape under the
-    current knn_filter / knn_pool_min_k knobs ("knn_filter_kernel<...>", "knn_scan_kernel<...>", "knn_scan_wide_kernel<...>"; bytes=True:
+    current knn_filter / knn_pool_min_k / knn_filter_wide knobs ("knn_filter_kernel<...>", "knn_scan_kernel<...>", "knn_scan_wide_kernel<...>",
+    "knn_wide_filter_kernel<...>" for float rows of 128 < d <= 1024 under gbnns_debug_knob("knn_filter_wide", 1 or 2); bytes=True:
     "knn_bytes_sweep_kernel<...>"), taken from the table the launch reads, and whether the lists are pools (True) or heaps."""
     name = C.create_string_buffer(128)
     pool = C.c_int(0)

@@ -10,6 +10,8 @@
 // knn_gather.hip) shares the refusals and the staging and falls back to knn_call for a shape its kernel does not cover.  Cut out of api.cpp
 // in round 5; api_internal.h lists the other units.
 
+#include <type_traits>
+
 #include "api_internal.h"
 
 using namespace gbnns;
@@ -230,7 +232,12 @@ struct KnnFloatPlan {
     bool pool;    // the matrix-core filter in front of pools with a radix select (long lists)
     bool filter;  // the matrix-core filter in front of the heaps; neither: the exact scan alone
     uint32_t dp;  // floats of a packed row of the filter: d rounded up to its K step of 16
+    bool wide;    // float rows of 128 < d <= 1024: the K-looped matrix-core filter (knn_wide.hip) in front of the heaps; never with pool / filter
 };
+// "knn_filter_wide" = 1 turns the wide filter on by size: from the smallest class tools/knn_wide_timing.py measures -- 10^5 rows, 1 000
+// queries -- where it beat the scan by more than the scan's run-to-run spread in that run (every measured class did, by a factor of 7 to
+// 80: profiles/knn_wide_timing.txt).  Smaller calls were not measured and keep the scan.
+constexpr uint64_t kKnnWideMinRows = 100000, kKnnWideMinQueries = 1000;
 KnnFloatPlan knn_float_plan(uint64_t n, uint64_t nq, uint32_t d, int k, int metric) {
     KnnFloatPlan pl{};
     // Matrix-core filter in front of the exact distances (knn.hip): the L2 metric on rows of whole 16-byte steps, sets
@@ -242,6 +249,10 @@ KnnFloatPlan knn_float_plan(uint64_t n, uint64_t nq, uint32_t d, int k, int metr
     pl.pool = filter_shape && k >= g_knob_knn_pool_min_k.load(std::memory_order_relaxed) && k <= 4096;
     pl.filter = filter_shape && k <= 512 && !pl.pool;
     pl.dp = (d + 15u) & ~15u;
+    // Wider rows (gist, glove): opt-in, a knob of its own -- "knn_filter" at any value leaves d > 128 to the scan.  Heaps only.
+    const int knob_wide = g_knob_knn_filter_wide.load(std::memory_order_relaxed);  // 0 = never (default), 1 = by size, 2 = whenever the shape allows
+    pl.wide = metric == GBNNS_METRIC_L2 && d % 4 == 0 && d > 128 && d <= kKnnWideMaxDim && k <= 512 && n > (uint64_t)4 * k &&
+              (knob_wide == 2 || (knob_wide == 1 && n >= kKnnWideMinRows && nq >= kKnnWideMinQueries));
     return pl;
 }
 
@@ -268,6 +279,7 @@ struct KnnSweepBufs {
 // The matrix-core filter's operands and lists (knn.hip) for `nq` queries at a time: the heap-filter path's whole call, a slab of the pool path.
 struct KnnFilterWork : KnnSweepBufs {
     ScopedDevBuf bpack;
+    bool wide = false;  // KnnFloatPlan::wide: the same operands, swept by knn_wide.hip's kernel
     // the buffers, and the base set packed
     int prepare(const KnnParams& p, uint32_t nq, uint32_t dp_, uint32_t cap_, hipStream_t s) {
         int rc;
@@ -292,7 +304,7 @@ struct KnnFilterWork : KnnSweepBufs {
         return GBNNS_OK;
     }
     int sweep(uint64_t r0, uint32_t rows, uint32_t qn, const uint32_t* tags, const uint32_t* qtags, hipStream_t s) const {
-        HIP_TRY(launch_knn_filter(chunk(r0, rows, qn, tags, qtags), s));
+        HIP_TRY(wide ? launch_knn_wide_filter(chunk(r0, rows, qn, tags, qtags), s) : launch_knn_filter(chunk(r0, rows, qn, tags, qtags), s));
         return GBNNS_OK;
     }
 };
@@ -309,6 +321,7 @@ struct KnnHalfPlan {
 KnnHalfPlan knn_half_plan(uint64_t n, uint64_t nq, uint32_t d, int k, int metric, uint32_t stride) {
     KnnHalfPlan pl{};
     pl.f = knn_float_plan(n, nq, d, k, metric);
+    pl.f.wide = false;  // (binary16 rows wider than 128 keep scanning: the wide filter reads float rows' packed images)
     if (!kKnnHalfBySize && g_knob_knn_filter.load(std::memory_order_relaxed) != 2) pl.f.pool = pl.f.filter = false;
     pl.packed = (pl.f.pool || pl.f.filter) && stride % 8 != 0;
     return pl;
@@ -406,7 +419,7 @@ int knn_rows_call(const KnnCall<B, float>& c) {
     p.bstride = c.bstride; p.qstride = d; p.n = n; p.nq = nq; p.dim = d; p.k = k; p.self_offset = c.self_offset;
     p.heap_stride = ((size_t)nq + 63) & ~(size_t)63;
     const KnnFloatPlan pl = Rows::plan(n, c.n_q, d, k, metric, c.bstride);
-    bool pool_path = pl.pool, filter = pl.filter;
+    bool pool_path = pl.pool, filter = pl.filter || pl.wide;  // (wide: the heap-filter schedule below with knn_wide.hip's sweep, rescore and slack)
     if (pool_path || filter) {  // a query outside the filter's error bound (half rows: knn_half.hip): the exact scan serves any finite input
         bool covered = true;
         if ((rc = Rows::Work::queries_covered(st.q, d, nq, s, &covered))) return rc;
@@ -451,15 +464,22 @@ int knn_rows_call(const KnnCall<B, float>& c) {
         // at most as long as everything before it -- a query is then expected to keep about k rows of a chunk, whatever
         // the chunk -- and at most 32 K rows (4 MB of packed rows at d = 32: L2 / Infinity-Cache resident while swept).
         // Chunks start on multiples of 64 rows (the filter reads the norms in aligned groups of four).
-        const uint64_t max_chunk = std::min<uint64_t>((uint64_t)g_knob_knn_chunk.load(std::memory_order_relaxed), std::max<uint64_t>(64, (n / 16 + 63) & ~(uint64_t)63));  // (small sets, tests: a sixteenth)
-        const uint64_t first = std::min<uint64_t>(n, (std::max<uint64_t>(std::min<uint64_t>(max_chunk, 8192), 4ull * (uint64_t)k) + 63) & ~(uint64_t)63);
+        uint64_t max_chunk = std::min<uint64_t>((uint64_t)g_knob_knn_chunk.load(std::memory_order_relaxed), std::max<uint64_t>(64, (n / 16 + 63) & ~(uint64_t)63));  // (small sets, tests: a sixteenth)
+        // (wide rows: 32 K packed rows of d = 960 are 126 MB; at most 64 MiB of them a chunk, which stays Infinity-Cache resident while swept)
+        if (pl.wide) max_chunk = std::min<uint64_t>(max_chunk, std::max<uint64_t>(64, ((64ull << 20) / ((uint64_t)pl.dp * 4)) & ~(uint64_t)63));
+        const float slack = pl.wide ? kKnnWideSlack : kKnnFilterSlack;
+        // (wide rows: 1 024 first rows, not 8 192 -- the scan does one VALU distance per pair, and at d = 960 those 8 192 rows were 64 of the
+        // call's 76 ms at 10^5 rows x 10 000 queries, 60 of 94 ms at 10^6 x 1 000: profiles/knn_wide_timing.txt)
+        const uint64_t first_most = pl.wide ? 1024 : 8192;
+        const uint64_t first = std::min<uint64_t>(n, (std::max<uint64_t>(std::min<uint64_t>(max_chunk, first_most), 4ull * (uint64_t)k) + 63) & ~(uint64_t)63);
         typename Rows::Work w;
+        if constexpr (std::is_same<typename Rows::Work, KnnFilterWork>::value) w.wide = pl.wide;
         if ((rc = w.prepare(p, nq, pl.dp, cap, s))) return rc;
         if ((rc = w.pack_queries(p.q, d, nq, s))) return rc;
         KnnParams ps = p;          // the first rows: the exact scan, heaps kept
         ps.n = first; ps.row0 = 0; ps.keep_heap = 1;
         HIP_TRY(Rows::scan(ps, metric, s));
-        HIP_TRY(launch_knn_thresholds(p.heap, p.heap_stride, k, static_cast<float*>(w.qnorm.p), nq, static_cast<float*>(w.rhs.p), s));
+        HIP_TRY(launch_knn_thresholds(p.heap, p.heap_stride, k, static_cast<float*>(w.qnorm.p), nq, static_cast<float*>(w.rhs.p), s, slack));
         uint32_t h_flag = 0;
         for (uint64_t r0 = first, chunk = 0; r0 < n; r0 += chunk) {
             chunk = std::min<uint64_t>(max_chunk, r0);
@@ -476,12 +496,12 @@ int knn_rows_call(const KnnCall<B, float>& c) {
                 Rows::table(pc, st.base + (size_t)r0 * p.bstride);
                 pc.n = rows; pc.row0 = r0; pc.keep_heap = 1;
                 HIP_TRY(Rows::scan(pc, metric, s));
-                HIP_TRY(launch_knn_thresholds(p.heap, p.heap_stride, k, static_cast<float*>(w.qnorm.p), nq, static_cast<float*>(w.rhs.p), s));
+                HIP_TRY(launch_knn_thresholds(p.heap, p.heap_stride, k, static_cast<float*>(w.qnorm.p), nq, static_cast<float*>(w.rhs.p), s, slack));
             } else {
                 KnnRescoreParams rp{};
                 rp.k = p; rp.cand = static_cast<uint32_t*>(w.cand.p); rp.count = static_cast<uint32_t*>(w.count.p); rp.cap = cap;
                 rp.qnorm = static_cast<float*>(w.qnorm.p); rp.rhs = static_cast<float*>(w.rhs.p);
-                HIP_TRY(Rows::rescore(rp, s));
+                HIP_TRY(pl.wide ? launch_knn_wide_rescore(rp, s) : Rows::rescore(rp, s));
             }
         }
         HIP_TRY(launch_knn_finalize(p, s));
@@ -953,7 +973,8 @@ int gbnns_debug_knn_plan(int bytes, int metric, uint64_t n, uint64_t n_q, uint32
         c.d = d; c.k = k; c.metric = metric;
         if (int rc = knn_refuse(c)) return rc;
         const KnnFloatPlan pl = knn_float_plan(n, n_q, d, k, metric);
-        kernel = pl.pool || pl.filter ? knn_filter_kernel_name(pl.dp, tagged != 0) : knn_scan_kernel_name(metric, d, tagged != 0);
+        kernel = pl.wide ? knn_wide_filter_kernel_name(pl.dp, tagged != 0)
+                         : (pl.pool || pl.filter ? knn_filter_kernel_name(pl.dp, tagged != 0) : knn_scan_kernel_name(metric, d, tagged != 0));
         *pool = pl.pool ? 1 : 0;
     }
     if (!kernel) return fail(GBNNS_ERR_INTERNAL, "gbnns_debug_knn_plan: no kernel instance for the plan");

@@ -347,6 +347,7 @@ const char* knn_bytes_sweep_kernel_name(uint32_t dp, bool tagged);
 // Rows packed for v_mfma_f32_32x32x16_bf16: per row, per group of 8 dims, 8 bf16 "hi" parts then 8 bf16 "lo" parts
 // (x = hi + lo + r, |r| <= 2^-16 |x|), dims zero-padded to a multiple of 16; and the row's squared norm.
 hipError_t launch_knn_pack(const float* x, uint32_t stride, uint32_t dim, uint64_t rows, uint16_t* packed, float* norms, hipStream_t s);
+constexpr float kKnnFilterSlack = 1.0f / 4096.0f;  // c: |approximate - reference distance| <= c (|q|^2 + |x|^2) with room to spare (knn.hip)
 struct KnnFilterParams {
     const uint16_t* qpack;   // [nq x 2 dp] packed queries
     const uint16_t* bpack;   // [rows x 2 dp] packed base rows of this chunk
@@ -365,7 +366,8 @@ struct KnnFilterParams {
 };
 hipError_t launch_knn_filter(const KnnFilterParams& p, hipStream_t s);
 // thresholds from the heaps: rhs[q] = 0.5 ((1 - c) |q|^2 - d_k(q)), -inf while the heap is not full
-hipError_t launch_knn_thresholds(const uint64_t* heap, size_t heap_stride, int k, const float* qnorm, uint32_t nq, float* rhs, hipStream_t s);
+hipError_t launch_knn_thresholds(const uint64_t* heap, size_t heap_stride, int k, const float* qnorm, uint32_t nq, float* rhs, hipStream_t s,
+                                 float slack = kKnnFilterSlack);  // (c; the wide filter passes kKnnWideSlack)
 // exact distances (the reference's arithmetic) of the candidates, offered to the heaps; then the new thresholds
 struct KnnRescoreParams {
     KnnParams k;             // base = the WHOLE base set, heap, q, ...
@@ -390,7 +392,16 @@ struct KnnPoolParams {
 };
 hipError_t launch_knn_pool_update(const KnnPoolParams& p, hipStream_t s);
 hipError_t launch_knn_pool_finalize(const KnnPoolParams& p, hipStream_t s);   // ascending order + outputs
-constexpr float kKnnFilterSlack = 1.0f / 4096.0f;  // c: |approximate - reference distance| <= c (|q|^2 + |x|^2) with room to spare (knn.hip)
+
+// The same filter for float rows of 128 < d <= 1024 (knn_wide.hip; "knn_filter_wide"): a K-looped kernel -- a workgroup's tile of 128 queries
+// x 128 rows, both operands (launch_knn_pack's images) staged through LDS -- with a slack of its own, whose error terms grow with d, and
+// a rescore that holds the query in LDS.  KnnFilterParams / KnnRescoreParams as above, rhs with kKnnWideSlack (launch_knn_thresholds' last
+// argument); bnorm and btag need be readable only up to the end of the chunk's last group of four rows.
+constexpr uint32_t kKnnWideMaxDim = 1024;
+constexpr float kKnnWideSlack = 1.0f / 1024.0f;  // c of the wide filter: the bound is written out in knn_wide.hip
+hipError_t launch_knn_wide_filter(const KnnFilterParams& p, hipStream_t s);
+hipError_t launch_knn_wide_rescore(const KnnRescoreParams& p, hipStream_t s);
+const char* knn_wide_filter_kernel_name(uint32_t dp, bool tagged);  // host only, as knn_filter_kernel_name; nullptr: dp > 1024
 
 // Exact kNN over binary16 rows against float32 queries (knn_half.hip; gbnns_exact_knn_half): the filter scheme of knn.hip with the rows as
 // they are -- a binary16 row is an exact operand of v_mfma_f32_32x32x16_f16 and is swept in place -- and only the query split:

@@ -145,13 +145,14 @@ __global__ __launch_bounds__(256) void knn_filter_kernel(KnnFilterParams p) {
     knn_sweep_body<KnnFilterOps, KSTEPS, QB, TAG>(p);
 }
 
-__global__ __launch_bounds__(256) void knn_thresholds_kernel(const uint64_t* heap, int k, const float* qnorm, uint32_t nq, float* rhs) {
+// (slack: the calling filter's c -- kKnnFilterSlack, or kKnnWideSlack for knn_wide.hip; 1 - c is exact for either)
+__global__ __launch_bounds__(256) void knn_thresholds_kernel(const uint64_t* heap, int k, const float* qnorm, uint32_t nq, float* rhs, float slack) {
     const uint32_t qi = blockIdx.x * 256u + threadIdx.x;
     if (qi >= nq) return;
     const uint64_t root = heap[qi];
     // heap not full yet (an all-ones key at the root): every row passes
     rhs[qi] = root == ~0ull ? -__builtin_inff()
-                            : 0.5f * ((1.0f - kKnnFilterSlack) * qnorm[qi] - knn_fkey_inv((uint32_t)(root >> 32)));
+                            : 0.5f * ((1.0f - slack) * qnorm[qi] - knn_fkey_inv((uint32_t)(root >> 32)));
     (void)k;
 }
 
@@ -237,10 +238,10 @@ hipError_t launch_knn_filter(const KnnFilterParams& p, hipStream_t s) {
 }
 const char* knn_filter_kernel_name(uint32_t dp, bool tagged) { return knn_filter_pick(dp, tagged).name; }
 
-hipError_t launch_knn_thresholds(const uint64_t* heap, size_t heap_stride, int k, const float* qnorm, uint32_t nq, float* rhs, hipStream_t s) {
+hipError_t launch_knn_thresholds(const uint64_t* heap, size_t heap_stride, int k, const float* qnorm, uint32_t nq, float* rhs, hipStream_t s, float slack) {
     (void)heap_stride;
     if (nq == 0) return hipSuccess;
-    hipLaunchKernelGGL(knn_thresholds_kernel, dim3((nq + 255u) / 256u), dim3(256), 0, s, heap, k, qnorm, nq, rhs);
+    hipLaunchKernelGGL(knn_thresholds_kernel, dim3((nq + 255u) / 256u), dim3(256), 0, s, heap, k, qnorm, nq, rhs, slack);
     return hipGetLastError();
 }
 

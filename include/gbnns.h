@@ -554,6 +554,9 @@ int gbnns_profile_enable(gbnns_index* index, int on);
  * radix select (one wavefront per query) instead of a binary heap (default 64; GBNNS_KNN_POOL_MIN_K).
  * "knn_filter": gbnns_exact_knn's matrix-core filter -- 0 never, 1 by size (default), 2 whenever the shape allows
  * (GBNNS_KNN_FILTER).
+ * "knn_filter_wide": the matrix-core filter of float rows wider than 128 dims (L2, 128 < d <= 1024, d % 4 == 0, k <= 512, n > 4 k; heaps)
+ * in gbnns_exact_knn / gbnns_exact_knn_tagged -- 0 never (default), 1 from 10^5 rows and 1 000 queries, 2 whenever the shape allows
+ * (GBNNS_KNN_FILTER_WIDE).  Same output, byte for byte; gbnns_debug_knn_plan then names "knn_wide_filter_kernel<2, TAG>".
  * "knn_slab": most queries gbnns_exact_knn's pool path and gbnns_exact_knn_bytes serve at a time -- 0 (default) = as many as keep their
  * key lists within 4 GiB (the slab formula at gbnns_exact_knn_bytes); v > 0 caps a slab at max(128, v & ~127) queries, so that a few
  * hundred queries already run several slabs (tests).  gbnns_debug_knn_slab reports the slab of a shape.
