@@ -439,9 +439,11 @@ def knn_plan(bytes, metric, n, n_q, d, k, tagged=False):
 
 def knn_half_plan(n, n_q, d, k, metric=METRIC_L2, stride=0, tagged=False):
     """gbnns_debug_knn_half_plan (no device needed): what exact_knn does with a float16 base of that shape under the current knn_filter /
-    knn_pool_min_k knobs -- dict(kernel, path, pool, packed): the kernel that sweeps the rows, path "filter" / "pool" (the f16 matrix-core
-    sweep in front of heaps / pools) or "scan", and whether the sweep reads a copy of the table (stride, the halves between rows -- 0: d --,
-    is no multiple of 8) or the table in place."""
+    knn_pool_min_k / knn_half_wide knobs -- dict(kernel, path, pool, packed): the kernel that sweeps the rows, path "filter" / "pool" (the
+    f16 matrix-core sweep in front of heaps / pools) or "scan", and whether the sweep reads a copy of the table (stride, the halves between
+    rows -- 0: d --, is no multiple of 8) or the table in place.  Rows of 128 < d <= 1024 are scanned unless
+    gbnns_debug_knob("knn_half_wide", 1 or 2) (env GBNNS_KNN_HALF_WIDE; 0 = never, the default, 1 = from 10^5 rows and 1 000 queries, 2 =
+    whenever L2, d % 4 == 0, k <= 512, n > 4 k): then "knn_half_wide_filter_kernel<2, TAG>", path "filter", the same output bytes."""
     name = C.create_string_buffer(128)
     pool, packed = C.c_int(0), C.c_int(0)
     _check(load_library().gbnns_debug_knn_half_plan(metric, n, n_q, d, stride, k, int(bool(tagged)), name, 128, C.byref(pool), C.byref(packed)))
@@ -1103,7 +1105,8 @@ class Index:
         gather=True: gbnns_index_exact_knn_gather -- the same bytes, computed from distances to the rows each query's word allows only (the
         queries of a word scan that word's row list); needs query_tags (None: ValueError).  Opt-in; gather_plan() names its kernel.
         half_scan=True, on a half-base handle (Index(db=<float16>)): gbnns_index_exact_knn_half -- exact_knn(db, queries, ...)'s answer over the
-        resident binary16 rows, read in place (float32 queries; knn_half_plan() tells the path).  Without it the call on such a handle is
+        resident binary16 rows, read in place (float32 queries; knn_half_plan() tells the path; rows wider than 128 dims take the f16
+        matrix-core filter under gbnns_debug_knob("knn_half_wide", 1 or 2), the scan otherwise).  Without it the call on such a handle is
         refused (GbnnsError, code 5), as MODE_PLAIN is without FLAG_HALF_WALK; on a float or byte handle half_scan=True is GbnnsError, code 1."""
         if half_scan:
             if gather:

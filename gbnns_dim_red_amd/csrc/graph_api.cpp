@@ -314,6 +314,10 @@ struct KnnFilterWork : KnnSweepBufs {
 // kKnnHalfBySize: does "knn_filter" = 1 turn the sweep on by size, as for float rows?  Decided by tools/knn_half_timing.py
 // (profiles/knn_half_timing.txt): only where the call beats gbnns_exact_knn on the widened copy by more than that call's run-to-run spread.
 constexpr bool kKnnHalfBySize = true;
+// "knn_half_wide" = 1 turns the wide half-row filter on by size, by the float filter's rule: from the smallest class
+// tools/knn_half_wide_timing.py measures -- 10^5 rows, 1 000 queries -- where it beat the half scan by more than that scan's run-to-run
+// spread in the same run (every measured class did: profiles/knn_half_wide_timing.txt).  Smaller calls were not measured and keep the scan.
+constexpr uint64_t kKnnHalfWideMinRows = 100000, kKnnHalfWideMinQueries = 1000;
 struct KnnHalfPlan {
     KnnFloatPlan f;
     bool packed;  // the table's stride is no multiple of 8 halves: swept from a copy at stride f.dp (a caller's array with d % 8 == 4)
@@ -321,9 +325,13 @@ struct KnnHalfPlan {
 KnnHalfPlan knn_half_plan(uint64_t n, uint64_t nq, uint32_t d, int k, int metric, uint32_t stride) {
     KnnHalfPlan pl{};
     pl.f = knn_float_plan(n, nq, d, k, metric);
-    pl.f.wide = false;  // (binary16 rows wider than 128 keep scanning: the wide filter reads float rows' packed images)
+    // Wider rows: knn_half_wide.hip's K-looped f16 filter, opt-in by a knob of its own ("knn_filter_wide" is the float rows' and leaves
+    // binary16 rows to the scan).  The float wide filter's shapes; heaps only.
+    const int knob_wide = g_knob_knn_half_wide.load(std::memory_order_relaxed);  // 0 = never (default), 1 = by size, 2 = whenever the shape allows
+    pl.f.wide = metric == GBNNS_METRIC_L2 && d % 4 == 0 && d > 128 && d <= kKnnWideMaxDim && k <= 512 && n > (uint64_t)4 * k &&
+                (knob_wide == 2 || (knob_wide == 1 && n >= kKnnHalfWideMinRows && nq >= kKnnHalfWideMinQueries));
     if (!kKnnHalfBySize && g_knob_knn_filter.load(std::memory_order_relaxed) != 2) pl.f.pool = pl.f.filter = false;
-    pl.packed = (pl.f.pool || pl.f.filter) && stride % 8 != 0;
+    pl.packed = (pl.f.pool || pl.f.filter || pl.f.wide) && stride % 8 != 0;
     return pl;
 }
 
@@ -333,6 +341,7 @@ struct KnnHalfWork : KnnSweepBufs {
     ScopedDevBuf copy, qinv;
     uint32_t stride, last_chunk;
     const uint16_t* table;
+    bool wide = false;  // KnnFloatPlan::wide: the same operands, swept by knn_half_wide.hip's kernel
     int prepare(const KnnParams& p, uint32_t nq, uint32_t dp_, uint32_t cap_, hipStream_t s) {
         int rc;
         // flag: [0] a list overflowed; [1] pack_queries' range flag (the call asked queries_covered before)
@@ -369,7 +378,7 @@ struct KnnHalfWork : KnnSweepBufs {
         f.bnorm = bnorm.as<float>() + r0; f.rhs = rhs.as<float>(); f.nq = qn; f.dp = dp; f.rows = rows; f.row0 = (uint32_t)r0; f.cap = cap;
         f.cand = cand.as<uint32_t>(); f.count = count.as<uint32_t>(); f.overflow = flag.as<uint32_t>();
         if (qtags) { f.btag = tags + r0; f.qtag = qtags; }
-        HIP_TRY(launch_knn_half_sweep(f, s));
+        HIP_TRY(wide ? launch_knn_half_wide_filter(f, s) : launch_knn_half_sweep(f, s));
         return GBNNS_OK;
     }
 };
@@ -383,8 +392,10 @@ struct KnnRowsOf<float> {
     static void table(KnnParams& p, const float* rows) { p.base = rows; }
     static hipError_t scan(const KnnParams& p, int metric, hipStream_t s) { return launch_knn_scan(p, metric, s); }
     static hipError_t rescore(const KnnRescoreParams& p, hipStream_t s) { return launch_knn_rescore(p, s); }
+    static hipError_t wide_rescore(const KnnRescoreParams& p, hipStream_t s) { return launch_knn_wide_rescore(p, s); }
     static hipError_t pool_update(const KnnPoolParams& p, hipStream_t s) { return launch_knn_pool_update(p, s); }
     static KnnFloatPlan plan(uint64_t n, uint64_t nq, uint32_t d, int k, int metric, uint32_t) { return knn_float_plan(n, nq, d, k, metric); }
+    static uint64_t wide_row_bytes(uint32_t dp, uint32_t) { return (uint64_t)dp * 4; }  // what the wide sweep reads of a row: the packed hi / lo image
 };
 template <>
 struct KnnRowsOf<uint16_t> {
@@ -392,8 +403,10 @@ struct KnnRowsOf<uint16_t> {
     static void table(KnnParams& p, const uint16_t* rows) { p.base_h = rows; }
     static hipError_t scan(const KnnParams& p, int metric, hipStream_t s) { return launch_knn_half_scan(p, metric, s); }
     static hipError_t rescore(const KnnRescoreParams& p, hipStream_t s) { return launch_knn_half_rescore(p, s); }
+    static hipError_t wide_rescore(const KnnRescoreParams& p, hipStream_t s) { return launch_knn_half_wide_rescore(p, s); }
     static hipError_t pool_update(const KnnPoolParams& p, hipStream_t s) { return launch_knn_half_pool_update(p, s); }
     static KnnFloatPlan plan(uint64_t n, uint64_t nq, uint32_t d, int k, int metric, uint32_t stride) { return knn_half_plan(n, nq, d, k, metric, stride).f; }
+    static uint64_t wide_row_bytes(uint32_t dp, uint32_t stride) { return 2ull * (stride % 8 ? dp : stride); }  // the row itself, in place or in the copy at stride dp
 };
 
 // gbnns_exact_knn's body, for float32 queries against rows of B = float (gbnns_exact_knn) or binary16 (gbnns_exact_knn_half): one schedule
@@ -419,7 +432,7 @@ int knn_rows_call(const KnnCall<B, float>& c) {
     p.bstride = c.bstride; p.qstride = d; p.n = n; p.nq = nq; p.dim = d; p.k = k; p.self_offset = c.self_offset;
     p.heap_stride = ((size_t)nq + 63) & ~(size_t)63;
     const KnnFloatPlan pl = Rows::plan(n, c.n_q, d, k, metric, c.bstride);
-    bool pool_path = pl.pool, filter = pl.filter || pl.wide;  // (wide: the heap-filter schedule below with knn_wide.hip's sweep, rescore and slack)
+    bool pool_path = pl.pool, filter = pl.filter || pl.wide;  // (wide: the heap-filter schedule below with knn_wide.hip's / knn_half_wide.hip's sweep, the wide rescore and slack)
     if (pool_path || filter) {  // a query outside the filter's error bound (half rows: knn_half.hip): the exact scan serves any finite input
         bool covered = true;
         if ((rc = Rows::Work::queries_covered(st.q, d, nq, s, &covered))) return rc;
@@ -465,15 +478,17 @@ int knn_rows_call(const KnnCall<B, float>& c) {
         // the chunk -- and at most 32 K rows (4 MB of packed rows at d = 32: L2 / Infinity-Cache resident while swept).
         // Chunks start on multiples of 64 rows (the filter reads the norms in aligned groups of four).
         uint64_t max_chunk = std::min<uint64_t>((uint64_t)g_knob_knn_chunk.load(std::memory_order_relaxed), std::max<uint64_t>(64, (n / 16 + 63) & ~(uint64_t)63));  // (small sets, tests: a sixteenth)
-        // (wide rows: 32 K packed rows of d = 960 are 126 MB; at most 64 MiB of them a chunk, which stays Infinity-Cache resident while swept)
-        if (pl.wide) max_chunk = std::min<uint64_t>(max_chunk, std::max<uint64_t>(64, ((64ull << 20) / ((uint64_t)pl.dp * 4)) & ~(uint64_t)63));
+        // (wide rows: 32 K packed rows of d = 960 are 126 MB; at most 64 MiB of swept row bytes a chunk -- 4 dp of a float row's packed image,
+        // twice the stride of a binary16 row --, which stay Infinity-Cache resident while swept.  64 MiB and the 1 024 first rows below were
+        // measured for float rows; binary16 rows start from the same schedule: profiles/knn_half_wide_timing.txt)
+        if (pl.wide) max_chunk = std::min<uint64_t>(max_chunk, std::max<uint64_t>(64, ((64ull << 20) / Rows::wide_row_bytes(pl.dp, c.bstride)) & ~(uint64_t)63));
         const float slack = pl.wide ? kKnnWideSlack : kKnnFilterSlack;
         // (wide rows: 1 024 first rows, not 8 192 -- the scan does one VALU distance per pair, and at d = 960 those 8 192 rows were 64 of the
         // call's 76 ms at 10^5 rows x 10 000 queries, 60 of 94 ms at 10^6 x 1 000: profiles/knn_wide_timing.txt)
         const uint64_t first_most = pl.wide ? 1024 : 8192;
         const uint64_t first = std::min<uint64_t>(n, (std::max<uint64_t>(std::min<uint64_t>(max_chunk, first_most), 4ull * (uint64_t)k) + 63) & ~(uint64_t)63);
         typename Rows::Work w;
-        if constexpr (std::is_same<typename Rows::Work, KnnFilterWork>::value) w.wide = pl.wide;
+        w.wide = pl.wide;
         if ((rc = w.prepare(p, nq, pl.dp, cap, s))) return rc;
         if ((rc = w.pack_queries(p.q, d, nq, s))) return rc;
         KnnParams ps = p;          // the first rows: the exact scan, heaps kept
@@ -501,7 +516,7 @@ int knn_rows_call(const KnnCall<B, float>& c) {
                 KnnRescoreParams rp{};
                 rp.k = p; rp.cand = static_cast<uint32_t*>(w.cand.p); rp.count = static_cast<uint32_t*>(w.count.p); rp.cap = cap;
                 rp.qnorm = static_cast<float*>(w.qnorm.p); rp.rhs = static_cast<float*>(w.rhs.p);
-                HIP_TRY(pl.wide ? launch_knn_wide_rescore(rp, s) : Rows::rescore(rp, s));
+                HIP_TRY(pl.wide ? Rows::wide_rescore(rp, s) : Rows::rescore(rp, s));
             }
         }
         HIP_TRY(launch_knn_finalize(p, s));
@@ -993,7 +1008,8 @@ int gbnns_debug_knn_half_plan(int metric, uint64_t n, uint64_t n_q, uint32_t d, 
     c.d = d; c.k = k; c.metric = metric;
     if (int rc = knn_refuse(c)) return rc;
     const KnnHalfPlan pl = knn_half_plan(n, n_q, d, k, metric, stride);
-    const char* kernel = pl.f.pool || pl.f.filter ? knn_half_sweep_kernel_name(pl.f.dp, tagged != 0) : knn_half_scan_kernel_name(metric, d, tagged != 0);
+    const char* kernel = pl.f.wide ? knn_half_wide_filter_kernel_name(pl.f.dp, tagged != 0)
+                                   : (pl.f.pool || pl.f.filter ? knn_half_sweep_kernel_name(pl.f.dp, tagged != 0) : knn_half_scan_kernel_name(metric, d, tagged != 0));
     if (!kernel) return fail(GBNNS_ERR_INTERNAL, "gbnns_debug_knn_half_plan: no kernel instance for the plan");
     std::snprintf(name, name_bytes, "%s", kernel);
     *pool = pl.f.pool ? 1 : 0;

@@ -441,6 +441,12 @@ hipError_t launch_knn_half_pool_update(const KnnPoolParams& p, hipStream_t s);
 // Host only, no device needed: "knn_half_sweep_kernel<KSTEPS, QB, TAG>" / "knn_scan_kernel<..., half>" -- the instance the launch starts
 const char* knn_half_sweep_kernel_name(uint32_t dp, bool tagged);
 const char* knn_half_scan_kernel_name(int metric, uint32_t dim, bool tagged);
+// Binary16 rows of 128 < d <= 1024 (knn_half_wide.hip; "knn_half_wide"): knn_wide.hip's K-looped tile of 128 queries x 128 rows with the rows
+// swept in place and the split query as its operands (KnnHalfSweepParams as above, dp <= kKnnWideMaxDim, rhs with kKnnWideSlack; bnorm and
+// btag as for launch_knn_wide_filter), and knn_wide.hip's rescore over binary16 rows (p.k.base_h, p.k.bstride in halves).
+hipError_t launch_knn_half_wide_filter(const KnnHalfSweepParams& p, hipStream_t s);
+hipError_t launch_knn_half_wide_rescore(const KnnRescoreParams& p, hipStream_t s);
+const char* knn_half_wide_filter_kernel_name(uint32_t dp, bool tagged);  // host only; "knn_half_wide_filter_kernel<KS, TAG>", nullptr: dp > 1024
 
 // Exact kNN over uint8 rows on the int8 matrix cores (knn_bytes.hip; d <= 256: every distance is an integer below 2^24, so
 // the int32 result of v_mfma_i32_32x32x32_i8 IS the reference's float distance).  Rows are packed as signed bytes x - 128,

@@ -41,6 +41,7 @@
 #include "kernels.h"
 #include "knn_select.h"     // the distance keys, the heap
 #include "knn_scan_dist.h"  // f32x2
+#include "knn_scan_kernels.h"  // knn_rows, knn_widen, knn_row_step: the rescore's binary16 instance
 
 namespace gbnns {
 
@@ -245,6 +246,9 @@ __global__ __launch_bounds__(256) void knn_wide_filter_kernel(KnnFilterParams p)
 // every lane takes one candidate row straight from global memory and runs L2Metric::Dist (support_func.h:107-128) in the scan kernels'
 // operations and order -- four running sums over ascending 16-byte steps, then ((s0 + s1) + s2) + s3 --; the keys below the heap's root
 // are offered in list order by lane 0; then the query's new threshold, with the wide slack.
+// B = uint16_t (knn_half_wide.hip's filter): the rows are binary16, widened as they are loaded -- exact --; vec: 16-byte chunks of eight
+// halves, two steps each, and 8 bytes for the last step of an odd count.
+template <class B>
 __global__ __launch_bounds__(64) void knn_wide_rescore_kernel(KnnRescoreParams p, int vec) {
     __shared__ float4 qs[kKnnWideMaxDim / 4];
     __shared__ uint64_t keys[64];
@@ -263,16 +267,35 @@ __global__ __launch_bounds__(64) void knn_wide_rescore_kernel(KnnRescoreParams p
         const uint32_t e = e0 + lane;
         const bool valid = e < cnt;
         const uint32_t row = valid ? p.cand[(size_t)qi * p.cap + e] : p.cand[(size_t)qi * p.cap];  // (an idle lane: the list's first row again)
-        const float* bp = kp.base + (size_t)row * kp.bstride;
+        const B* bp = knn_rows<B>(kp) + (size_t)row * kp.bstride;
         f32x2 s01{0.f, 0.f}, s23{0.f, 0.f};
-#pragma unroll 8
-        for (uint32_t c = 0; c < steps; ++c) {
-            const float4 b4 = vec ? reinterpret_cast<const float4*>(bp)[c] : make_float4(bp[4 * c], bp[4 * c + 1], bp[4 * c + 2], bp[4 * c + 3]);
-            const float4 q4 = qs[c];
+        auto step = [&](const float4 b4, const float4 q4) {
             const f32x2 e01 = f32x2{b4.x, b4.y} - f32x2{q4.x, q4.y};
             const f32x2 e23 = f32x2{b4.z, b4.w} - f32x2{q4.z, q4.w};
             s01 = s01 + e01 * e01;
             s23 = s23 + e23 * e23;
+        };
+        if constexpr (!kKnnHalfRows<B>) {
+#pragma unroll 8
+            for (uint32_t c = 0; c < steps; ++c)
+                step(vec ? reinterpret_cast<const float4*>(bp)[c] : make_float4(bp[4 * c], bp[4 * c + 1], bp[4 * c + 2], bp[4 * c + 3]), qs[c]);
+        } else if (vec) {
+            auto widen4 = [](uint32_t a, uint32_t b) {
+                return make_float4(knn_widen((uint16_t)a), knn_widen((uint16_t)(a >> 16)), knn_widen((uint16_t)b), knn_widen((uint16_t)(b >> 16)));
+            };
+#pragma unroll 4
+            for (uint32_t c = 0; c + 1u < steps; c += 2u) {
+                const uint4 w = reinterpret_cast<const uint4*>(bp)[c >> 1];
+                step(widen4(w.x, w.y), qs[c]);
+                step(widen4(w.z, w.w), qs[c + 1u]);
+            }
+            if (steps & 1u) {
+                const uint2 w = reinterpret_cast<const uint2*>(bp)[steps - 1u];
+                step(widen4(w.x, w.y), qs[steps - 1u]);
+            }
+        } else {
+#pragma unroll 8
+            for (uint32_t c = 0; c < steps; ++c) step(knn_row_step(bp, c, false), qs[c]);
         }
         const float dist = ((s01.x + s01.y) + s23.x) + s23.y;
         const uint64_t key = ((uint64_t)knn_fkey(dist) << 32) | row;
@@ -334,7 +357,16 @@ hipError_t launch_knn_wide_rescore(const KnnRescoreParams& p, hipStream_t s) {
     if (p.k.nq == 0) return hipSuccess;
     if (p.k.dim > kKnnWideMaxDim || (p.k.dim & 3u)) return hipErrorInvalidValue;
     const int vec = !(p.k.bstride & 3u) && !(p.k.qstride & 3u) && !(reinterpret_cast<uintptr_t>(p.k.base) & 15u) && !(reinterpret_cast<uintptr_t>(p.k.q) & 15u);
-    hipLaunchKernelGGL(knn_wide_rescore_kernel, dim3(p.k.nq), dim3(64), 0, s, p, vec);
+    hipLaunchKernelGGL(knn_wide_rescore_kernel<float>, dim3(p.k.nq), dim3(64), 0, s, p, vec);
+    return hipGetLastError();
+}
+
+hipError_t launch_knn_half_wide_rescore(const KnnRescoreParams& p, hipStream_t s) {
+    if (p.k.nq == 0) return hipSuccess;
+    if (!p.k.base_h || p.k.dim > kKnnWideMaxDim || (p.k.dim & 3u)) return hipErrorInvalidValue;
+    // (16-byte chunks of eight halves: a table at a stride of whole chunks; the query's float4 steps as above)
+    const int vec = !(p.k.bstride & 7u) && !(p.k.qstride & 3u) && !(reinterpret_cast<uintptr_t>(p.k.base_h) & 15u) && !(reinterpret_cast<uintptr_t>(p.k.q) & 15u);
+    hipLaunchKernelGGL(knn_wide_rescore_kernel<uint16_t>, dim3(p.k.nq), dim3(64), 0, s, p, vec);
     return hipGetLastError();
 }
 

@@ -557,6 +557,11 @@ int gbnns_profile_enable(gbnns_index* index, int on);
  * "knn_filter_wide": the matrix-core filter of float rows wider than 128 dims (L2, 128 < d <= 1024, d % 4 == 0, k <= 512, n > 4 k; heaps)
  * in gbnns_exact_knn / gbnns_exact_knn_tagged -- 0 never (default), 1 from 10^5 rows and 1 000 queries, 2 whenever the shape allows
  * (GBNNS_KNN_FILTER_WIDE).  Same output, byte for byte; gbnns_debug_knn_plan then names "knn_wide_filter_kernel<2, TAG>".
+ * "knn_half_wide": the f16 matrix-core filter of binary16 rows wider than 128 dims (the same shapes: L2, 128 < d <= 1024, d % 4 == 0,
+ * k <= 512, n > 4 k; heaps) in gbnns_exact_knn_half / gbnns_index_exact_knn_half, which "knn_filter_wide" leaves to the scan -- 0 never
+ * (default), 1 from 10^5 rows and 1 000 queries, 2 whenever the shape allows; the value is clamped to 0 .. 2 (GBNNS_KNN_HALF_WIDE).  Same
+ * output, byte for byte; the rows are swept in place, nothing of the table is packed (a table whose stride is no multiple of 8 halves is
+ * swept from a copy); gbnns_debug_knn_half_plan then names "knn_half_wide_filter_kernel<2, TAG>".
  * "knn_slab": most queries gbnns_exact_knn's pool path and gbnns_exact_knn_bytes serve at a time -- 0 (default) = as many as keep their
  * key lists within 4 GiB (the slab formula at gbnns_exact_knn_bytes); v > 0 caps a slab at max(128, v & ~127) queries, so that a few
  * hundred queries already run several slabs (tests).  gbnns_debug_knn_slab reports the slab of a shape.
