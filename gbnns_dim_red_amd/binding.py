@@ -429,7 +429,8 @@ def knn_slab(n_q, k, bytes=False):
 def knn_plan(bytes, metric, n, n_q, d, k, tagged=False):
     """gbnns_debug_knn_plan (no device needed): (name, pool) -- the kernel that sweeps the rows of an exact_knn call of that shape under the
     current knn_filter / knn_pool_min_k / knn_filter_wide knobs ("knn_filter_kernel<...>", "knn_scan_kernel<...>", "knn_scan_wide_kernel<...>",
-    "knn_wide_filter_kernel<...>" for float rows of 128 < d <= 1024 under gbnns_debug_knob("knn_filter_wide", 1 or 2); bytes=True:
+    "knn_wide_filter_kernel<...>" for float rows of 128 < d <= 1024 under gbnns_debug_knob("knn_filter_wide", 1 or 2),
+    "knn_dot_filter_kernel<...>" for METRIC_NEG_DOT on float rows of d <= 1024 under gbnns_debug_knob("knn_filter_dot", 1 or 2); bytes=True:
     "knn_bytes_sweep_kernel<...>"), taken from the table the launch reads, and whether the lists are pools (True) or heaps."""
     name = C.create_string_buffer(128)
     pool = C.c_int(0)
@@ -623,6 +624,8 @@ def exact_knn(base, queries, k, metric=METRIC_L2, self_offset=-1, want_dist=Fals
     """gbnns_exact_knn: ids [n_q x k] (and distances) of the k nearest base rows of every query, in the
     reference's distance arithmetic, ascending (distance, id).  numpy in -> numpy out; torch CUDA in -> torch
     out.  self_offset >= 0: query i is base row i + self_offset (excluded from its own list).
+    METRIC_NEG_DOT on float32 rows (d % 8 == 0, d <= 1024, k <= 512) takes the matrix-core filter of knn_dot.hip under
+    gbnns_debug_knob("knn_filter_dot", 1 or 2) (env GBNNS_KNN_FILTER_DOT; default 0: the exact scan) -- the same bytes either way.
     Both arguments uint8 (numpy or torch): gbnns_exact_knn_bytes -- the same answer as over the widened arrays, bit for
     bit, on the int8 matrix cores and without a float copy (d <= 256, k <= 4096).
     row_tags [n] and query_tags [n_q] (both or neither; numpy uint32, or int32 tensors beside device inputs): gbnns_exact_knn_tagged /

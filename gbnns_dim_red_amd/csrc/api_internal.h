@@ -168,7 +168,8 @@ struct Lane {
 // the diagnostic knobs: struct Knobs, call_plan.h (defined and documented in handle.cpp)
 Knobs knob_defaults();                                    // the process-wide defaults as they stand now
 bool knob_set(Knobs& k, const char* name, int value);     // clamps like the environment does; false = no such handle knob
-extern std::atomic<int> g_knob_knn_chunk, g_knob_knn_pool_min_k, g_knob_knn_filter, g_knob_knn_slab, g_knob_knn_filter_wide, g_knob_knn_half_wide;
+extern std::atomic<int> g_knob_knn_chunk, g_knob_knn_pool_min_k, g_knob_knn_filter, g_knob_knn_slab, g_knob_knn_filter_wide, g_knob_knn_half_wide,
+    g_knob_knn_filter_dot;
 
 }  // namespace gbnns_api
 

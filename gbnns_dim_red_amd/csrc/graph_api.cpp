@@ -233,11 +233,16 @@ struct KnnFloatPlan {
     bool filter;  // the matrix-core filter in front of the heaps; neither: the exact scan alone
     uint32_t dp;  // floats of a packed row of the filter: d rounded up to its K step of 16
     bool wide;    // float rows of 128 < d <= 1024: the K-looped matrix-core filter (knn_wide.hip) in front of the heaps; never with pool / filter
+    bool dot;     // float rows under the negative dot, d <= 1024: knn_dot.hip's K-looped filter in front of the heaps; never with the other three
 };
 // "knn_filter_wide" = 1 turns the wide filter on by size: from the smallest class tools/knn_wide_timing.py measures -- 10^5 rows, 1 000
 // queries -- where it beat the scan by more than the scan's run-to-run spread in that run (every measured class did, by a factor of 7 to
 // 80: profiles/knn_wide_timing.txt).  Smaller calls were not measured and keep the scan.
 constexpr uint64_t kKnnWideMinRows = 100000, kKnnWideMinQueries = 1000;
+// "knn_filter_dot" = 1 follows the same rule over tools/knn_dot_timing.py's classes: every one of them -- 10^5 x 960 with 10 000 queries up
+// to 10^6 x 960 with 1 000, 10^6 x 96 normalised -- beat the scan by more than its spread, by a factor of 10 to 146
+// (profiles/knn_dot_timing.txt), so the same smallest class.  Smaller calls were not measured and keep the scan; the default stays 0.
+constexpr uint64_t kKnnDotMinRows = 100000, kKnnDotMinQueries = 1000;
 KnnFloatPlan knn_float_plan(uint64_t n, uint64_t nq, uint32_t d, int k, int metric) {
     KnnFloatPlan pl{};
     // Matrix-core filter in front of the exact distances (knn.hip): the L2 metric on rows of whole 16-byte steps, sets
@@ -253,6 +258,11 @@ KnnFloatPlan knn_float_plan(uint64_t n, uint64_t nq, uint32_t d, int k, int metr
     const int knob_wide = g_knob_knn_filter_wide.load(std::memory_order_relaxed);  // 0 = never (default), 1 = by size, 2 = whenever the shape allows
     pl.wide = metric == GBNNS_METRIC_L2 && d % 4 == 0 && d > 128 && d <= kKnnWideMaxDim && k <= 512 && n > (uint64_t)4 * k &&
               (knob_wide == 2 || (knob_wide == 1 && n >= kKnnWideMinRows && nq >= kKnnWideMinQueries));
+    // The negative dot (angular sets, MIPS): opt-in, a knob of its own -- the other two leave the metric to the scan.  One K-looped kernel
+    // for narrow and wide rows; the API offers the dot for d % 8 == 0.  Heaps only.
+    const int knob_dot = g_knob_knn_filter_dot.load(std::memory_order_relaxed);  // 0 = never (default), 1 = by size, 2 = whenever the shape allows
+    pl.dot = metric == GBNNS_METRIC_NEG_DOT && d % 8 == 0 && d >= 8 && d <= kKnnWideMaxDim && k <= 512 && n > (uint64_t)4 * k &&
+             (knob_dot == 2 || (knob_dot == 1 && n >= kKnnDotMinRows && nq >= kKnnDotMinQueries));
     return pl;
 }
 
@@ -261,6 +271,7 @@ KnnFloatPlan knn_float_plan(uint64_t n, uint64_t nq, uint32_t d, int k, int metr
 struct KnnSweepBufs {
     ScopedDevBuf bnorm, qpack, qnorm, rhs, cand, count, flag;
     uint32_t dp, cap;
+    bool dot = false;  // KnnFloatPlan::dot (float rows only): the packed images with the norms turned by dot_operands, swept by knn_dot.hip's kernel
     int prepare_bufs(uint64_t n, uint32_t nq, uint32_t dp_, uint32_t cap_, size_t flag_bytes, hipStream_t s) {
         int rc;
         dp = dp_; cap = cap_;
@@ -274,6 +285,19 @@ struct KnnSweepBufs {
         HIP_TRY(launch_fill_u32(bnorm.as<uint32_t>() + n, 0x7F800000u, 64, s));
         return GBNNS_OK;
     }
+    // KnnFloatPlan::dot, behind the rows' and the queries' packing: the squared norms become knn_dot.hip's operands in place -- bnorm upper
+    // bounds of |x| (-inf behind the last row), qnorm c times upper bounds of |q| -- through the word at flag[1]; *covered: does the
+    // filter's error bound hold for every norm of the call?  (One check per call on norms computed anyway; not covered -> the exact scan.)
+    int dot_operands(uint64_t n, uint32_t qn, hipStream_t s, bool* covered) {
+        uint32_t h = 0;
+        HIP_TRY(launch_fill_u32(flag.as<uint32_t>() + 1, 0u, 1, s));
+        HIP_TRY(launch_knn_dot_bounds(bnorm.as<float>(), n, n + 64, 1.0f, flag.as<uint32_t>() + 1, s));
+        HIP_TRY(launch_knn_dot_bounds(qnorm.as<float>(), qn, qn, kKnnWideSlack, flag.as<uint32_t>() + 1, s));
+        HIP_TRY(hipMemcpyAsync(&h, flag.as<uint32_t>() + 1, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        *covered = h == 0;
+        return GBNNS_OK;
+    }
 };
 
 // The matrix-core filter's operands and lists (knn.hip) for `nq` queries at a time: the heap-filter path's whole call, a slab of the pool path.
@@ -283,7 +307,8 @@ struct KnnFilterWork : KnnSweepBufs {
     // the buffers, and the base set packed
     int prepare(const KnnParams& p, uint32_t nq, uint32_t dp_, uint32_t cap_, hipStream_t s) {
         int rc;
-        if ((rc = prepare_bufs(p.n, nq, dp_, cap_, 4, s))) return rc;
+        // flag: [0] a list overflowed; [1] dot_operands' range flag
+        if ((rc = prepare_bufs(p.n, nq, dp_, cap_, 8, s))) return rc;
         if ((rc = bpack.ensure((size_t)p.n * dp * 4))) return rc;       // 2 dp bf16 per row
         HIP_TRY(launch_knn_pack(p.base, p.bstride, p.dim, p.n, bpack.as<uint16_t>(), bnorm.as<float>(), s));
         return GBNNS_OK;
@@ -295,6 +320,7 @@ struct KnnFilterWork : KnnSweepBufs {
         f.rhs = rhs.as<float>(); f.nq = qn; f.dp = dp; f.rows = rows; f.row0 = (uint32_t)r0; f.cap = cap;
         f.cand = cand.as<uint32_t>(); f.count = count.as<uint32_t>(); f.overflow = flag.as<uint32_t>();
         if (qtags) { f.btag = tags + r0; f.qtag = qtags; }
+        if (dot) f.cq = qnorm.as<float>();
         return f;
     }
     // the steps of knn_rows_call by the names KnnHalfWork gives them
@@ -304,7 +330,8 @@ struct KnnFilterWork : KnnSweepBufs {
         return GBNNS_OK;
     }
     int sweep(uint64_t r0, uint32_t rows, uint32_t qn, const uint32_t* tags, const uint32_t* qtags, hipStream_t s) const {
-        HIP_TRY(wide ? launch_knn_wide_filter(chunk(r0, rows, qn, tags, qtags), s) : launch_knn_filter(chunk(r0, rows, qn, tags, qtags), s));
+        if (dot) HIP_TRY(launch_knn_dot_filter(chunk(r0, rows, qn, tags, qtags), s));
+        else HIP_TRY(wide ? launch_knn_wide_filter(chunk(r0, rows, qn, tags, qtags), s) : launch_knn_filter(chunk(r0, rows, qn, tags, qtags), s));
         return GBNNS_OK;
     }
 };
@@ -325,6 +352,7 @@ struct KnnHalfPlan {
 KnnHalfPlan knn_half_plan(uint64_t n, uint64_t nq, uint32_t d, int k, int metric, uint32_t stride) {
     KnnHalfPlan pl{};
     pl.f = knn_float_plan(n, nq, d, k, metric);
+    pl.f.dot = false;  // ("knn_filter_dot" is the float rows': binary16 rows under the negative dot keep the half scan)
     // Wider rows: knn_half_wide.hip's K-looped f16 filter, opt-in by a knob of its own ("knn_filter_wide" is the float rows' and leaves
     // binary16 rows to the scan).  The float wide filter's shapes; heaps only.
     const int knob_wide = g_knob_knn_half_wide.load(std::memory_order_relaxed);  // 0 = never (default), 1 = by size, 2 = whenever the shape allows
@@ -393,6 +421,7 @@ struct KnnRowsOf<float> {
     static hipError_t scan(const KnnParams& p, int metric, hipStream_t s) { return launch_knn_scan(p, metric, s); }
     static hipError_t rescore(const KnnRescoreParams& p, hipStream_t s) { return launch_knn_rescore(p, s); }
     static hipError_t wide_rescore(const KnnRescoreParams& p, hipStream_t s) { return launch_knn_wide_rescore(p, s); }
+    static hipError_t dot_rescore(const KnnRescoreParams& p, hipStream_t s) { return launch_knn_dot_rescore(p, s); }
     static hipError_t pool_update(const KnnPoolParams& p, hipStream_t s) { return launch_knn_pool_update(p, s); }
     static KnnFloatPlan plan(uint64_t n, uint64_t nq, uint32_t d, int k, int metric, uint32_t) { return knn_float_plan(n, nq, d, k, metric); }
     static uint64_t wide_row_bytes(uint32_t dp, uint32_t) { return (uint64_t)dp * 4; }  // what the wide sweep reads of a row: the packed hi / lo image
@@ -404,6 +433,7 @@ struct KnnRowsOf<uint16_t> {
     static hipError_t scan(const KnnParams& p, int metric, hipStream_t s) { return launch_knn_half_scan(p, metric, s); }
     static hipError_t rescore(const KnnRescoreParams& p, hipStream_t s) { return launch_knn_half_rescore(p, s); }
     static hipError_t wide_rescore(const KnnRescoreParams& p, hipStream_t s) { return launch_knn_half_wide_rescore(p, s); }
+    static hipError_t dot_rescore(const KnnRescoreParams&, hipStream_t) { return hipErrorInvalidValue; }  // (knn_half_plan never sets KnnFloatPlan::dot)
     static hipError_t pool_update(const KnnPoolParams& p, hipStream_t s) { return launch_knn_half_pool_update(p, s); }
     static KnnFloatPlan plan(uint64_t n, uint64_t nq, uint32_t d, int k, int metric, uint32_t stride) { return knn_half_plan(n, nq, d, k, metric, stride).f; }
     static uint64_t wide_row_bytes(uint32_t dp, uint32_t stride) { return 2ull * (stride % 8 ? dp : stride); }  // the row itself, in place or in the copy at stride dp
@@ -432,7 +462,9 @@ int knn_rows_call(const KnnCall<B, float>& c) {
     p.bstride = c.bstride; p.qstride = d; p.n = n; p.nq = nq; p.dim = d; p.k = k; p.self_offset = c.self_offset;
     p.heap_stride = ((size_t)nq + 63) & ~(size_t)63;
     const KnnFloatPlan pl = Rows::plan(n, c.n_q, d, k, metric, c.bstride);
-    bool pool_path = pl.pool, filter = pl.filter || pl.wide;  // (wide: the heap-filter schedule below with knn_wide.hip's / knn_half_wide.hip's sweep, the wide rescore and slack)
+    // (wide: the heap-filter schedule below with knn_wide.hip's / knn_half_wide.hip's sweep, the wide rescore and slack; dot: the same schedule
+    // with knn_dot.hip's sweep, rescore, thresholds and norm bounds)
+    bool pool_path = pl.pool, filter = pl.filter || pl.wide || pl.dot;
     if (pool_path || filter) {  // a query outside the filter's error bound (half rows: knn_half.hip): the exact scan serves any finite input
         bool covered = true;
         if ((rc = Rows::Work::queries_covered(st.q, d, nq, s, &covered))) return rc;
@@ -481,20 +513,37 @@ int knn_rows_call(const KnnCall<B, float>& c) {
         // (wide rows: 32 K packed rows of d = 960 are 126 MB; at most 64 MiB of swept row bytes a chunk -- 4 dp of a float row's packed image,
         // twice the stride of a binary16 row --, which stay Infinity-Cache resident while swept.  64 MiB and the 1 024 first rows below were
         // measured for float rows; binary16 rows start from the same schedule: profiles/knn_half_wide_timing.txt)
-        if (pl.wide) max_chunk = std::min<uint64_t>(max_chunk, std::max<uint64_t>(64, ((64ull << 20) / Rows::wide_row_bytes(pl.dp, c.bstride)) & ~(uint64_t)63));
+        // (the dot form starts from the wide rows' figures, at every d)
+        const bool looped = pl.wide || pl.dot;
+        if (looped) max_chunk = std::min<uint64_t>(max_chunk, std::max<uint64_t>(64, ((64ull << 20) / Rows::wide_row_bytes(pl.dp, c.bstride)) & ~(uint64_t)63));
         const float slack = pl.wide ? kKnnWideSlack : kKnnFilterSlack;
         // (wide rows: 1 024 first rows, not 8 192 -- the scan does one VALU distance per pair, and at d = 960 those 8 192 rows were 64 of the
         // call's 76 ms at 10^5 rows x 10 000 queries, 60 of 94 ms at 10^6 x 1 000: profiles/knn_wide_timing.txt)
-        const uint64_t first_most = pl.wide ? 1024 : 8192;
+        const uint64_t first_most = looped ? 1024 : 8192;
         const uint64_t first = std::min<uint64_t>(n, (std::max<uint64_t>(std::min<uint64_t>(max_chunk, first_most), 4ull * (uint64_t)k) + 63) & ~(uint64_t)63);
         typename Rows::Work w;
         w.wide = pl.wide;
+        w.dot = pl.dot;
         if ((rc = w.prepare(p, nq, pl.dp, cap, s))) return rc;
         if ((rc = w.pack_queries(p.q, d, nq, s))) return rc;
+        if (pl.dot) {  // a norm outside the range of the dot filter's error bound (knn_dot.hip): the exact scan serves any finite input
+            bool covered = true;
+            if ((rc = w.dot_operands(n, nq, s, &covered))) return rc;
+            if (!covered) {
+                HIP_TRY(Rows::scan(p, metric, s));
+                return st.copy_back(c, s);
+            }
+        }
+        // the thresholds behind an exact scan: the L2 filters' rhs from the norms, the dot filter's -T
+        auto thresholds = [&]() -> int {
+            if (pl.dot) HIP_TRY(launch_knn_dot_thresholds(p.heap, nq, static_cast<float*>(w.rhs.p), s));
+            else HIP_TRY(launch_knn_thresholds(p.heap, p.heap_stride, k, static_cast<float*>(w.qnorm.p), nq, static_cast<float*>(w.rhs.p), s, slack));
+            return GBNNS_OK;
+        };
         KnnParams ps = p;          // the first rows: the exact scan, heaps kept
         ps.n = first; ps.row0 = 0; ps.keep_heap = 1;
         HIP_TRY(Rows::scan(ps, metric, s));
-        HIP_TRY(launch_knn_thresholds(p.heap, p.heap_stride, k, static_cast<float*>(w.qnorm.p), nq, static_cast<float*>(w.rhs.p), s, slack));
+        if ((rc = thresholds())) return rc;
         uint32_t h_flag = 0;
         for (uint64_t r0 = first, chunk = 0; r0 < n; r0 += chunk) {
             chunk = std::min<uint64_t>(max_chunk, r0);
@@ -511,12 +560,12 @@ int knn_rows_call(const KnnCall<B, float>& c) {
                 Rows::table(pc, st.base + (size_t)r0 * p.bstride);
                 pc.n = rows; pc.row0 = r0; pc.keep_heap = 1;
                 HIP_TRY(Rows::scan(pc, metric, s));
-                HIP_TRY(launch_knn_thresholds(p.heap, p.heap_stride, k, static_cast<float*>(w.qnorm.p), nq, static_cast<float*>(w.rhs.p), s, slack));
+                if ((rc = thresholds())) return rc;
             } else {
                 KnnRescoreParams rp{};
                 rp.k = p; rp.cand = static_cast<uint32_t*>(w.cand.p); rp.count = static_cast<uint32_t*>(w.count.p); rp.cap = cap;
                 rp.qnorm = static_cast<float*>(w.qnorm.p); rp.rhs = static_cast<float*>(w.rhs.p);
-                HIP_TRY(pl.wide ? Rows::wide_rescore(rp, s) : Rows::rescore(rp, s));
+                HIP_TRY(pl.dot ? Rows::dot_rescore(rp, s) : pl.wide ? Rows::wide_rescore(rp, s) : Rows::rescore(rp, s));
             }
         }
         HIP_TRY(launch_knn_finalize(p, s));
@@ -988,7 +1037,8 @@ int gbnns_debug_knn_plan(int bytes, int metric, uint64_t n, uint64_t n_q, uint32
         c.d = d; c.k = k; c.metric = metric;
         if (int rc = knn_refuse(c)) return rc;
         const KnnFloatPlan pl = knn_float_plan(n, n_q, d, k, metric);
-        kernel = pl.wide ? knn_wide_filter_kernel_name(pl.dp, tagged != 0)
+        kernel = pl.dot ? knn_dot_filter_kernel_name(pl.dp, tagged != 0)
+                 : pl.wide ? knn_wide_filter_kernel_name(pl.dp, tagged != 0)
                          : (pl.pool || pl.filter ? knn_filter_kernel_name(pl.dp, tagged != 0) : knn_scan_kernel_name(metric, d, tagged != 0));
         *pool = pl.pool ? 1 : 0;
     }

@@ -363,6 +363,8 @@ struct KnnFilterParams {
     // gbnns_exact_knn_tagged (last): a pair whose row is not allowed for its query is not a hit -- neither counted nor stored
     const uint32_t* btag;    // [rows] tag words of the chunk's rows, 16-byte aligned and readable (any value) up to the end of the chunk's last block of 32, or nullptr: the untagged instances
     const uint32_t* qtag;    // [nq]
+    // the negative-dot filter (knn_dot.hip; last again): c times an upper bound of |q| -- there bnorm holds upper bounds of |x| and rhs is -T_q
+    const float* cq;         // [nq], or nullptr: the L2 filters
 };
 hipError_t launch_knn_filter(const KnnFilterParams& p, hipStream_t s);
 // thresholds from the heaps: rhs[q] = 0.5 ((1 - c) |q|^2 - d_k(q)), -inf while the heap is not full
@@ -402,6 +404,18 @@ constexpr float kKnnWideSlack = 1.0f / 1024.0f;  // c of the wide filter: the bo
 hipError_t launch_knn_wide_filter(const KnnFilterParams& p, hipStream_t s);
 hipError_t launch_knn_wide_rescore(const KnnRescoreParams& p, hipStream_t s);
 const char* knn_wide_filter_kernel_name(uint32_t dp, bool tagged);  // host only, as knn_filter_kernel_name; nullptr: dp > 1024
+
+// The negative dot (knn_dot.hip; "knn_filter_dot"; float rows, d % 8 == 0, d <= 1024): the same K-looped tile over launch_knn_pack's images with
+// an epilogue of its own -- a row is kept when fma(cq, ux, q.x) >= -T_q, the error of q.x scaling with |q||x| -- and kKnnWideSlack as its c.
+// launch_knn_dot_bounds turns squared norms into those operands in place: norms[i] = scale * (an upper bound of the norm) for i < live, -inf
+// for live <= i < count (the padding behind the rows); *uncovered (preset to 0) is set where a norm lies outside the range the error bound
+// holds for (zero, not finite, beyond 2^+-96 squared): the call is then the exact scan's.  KnnFilterParams with bnorm = the rows' bounds,
+// rhs = -T_q (launch_knn_dot_thresholds; the rescore rewrites it) and cq; KnnRescoreParams as above, qnorm unused.
+hipError_t launch_knn_dot_bounds(float* norms, uint64_t live, uint64_t count, float scale, uint32_t* uncovered, hipStream_t s);
+hipError_t launch_knn_dot_filter(const KnnFilterParams& p, hipStream_t s);
+hipError_t launch_knn_dot_rescore(const KnnRescoreParams& p, hipStream_t s);
+hipError_t launch_knn_dot_thresholds(const uint64_t* heap, uint32_t nq, float* thr, hipStream_t s);
+const char* knn_dot_filter_kernel_name(uint32_t dp, bool tagged);  // host only; "knn_dot_filter_kernel<2, TAG>", nullptr: dp > 1024
 
 // Exact kNN over binary16 rows against float32 queries (knn_half.hip; gbnns_exact_knn_half): the filter scheme of knn.hip with the rows as
 // they are -- a binary16 row is an exact operand of v_mfma_f32_32x32x16_f16 and is swept in place -- and only the query split:

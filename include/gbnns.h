@@ -562,6 +562,12 @@ int gbnns_profile_enable(gbnns_index* index, int on);
  * (default), 1 from 10^5 rows and 1 000 queries, 2 whenever the shape allows; the value is clamped to 0 .. 2 (GBNNS_KNN_HALF_WIDE).  Same
  * output, byte for byte; the rows are swept in place, nothing of the table is packed (a table whose stride is no multiple of 8 halves is
  * swept from a copy); gbnns_debug_knn_half_plan then names "knn_half_wide_filter_kernel<2, TAG>".
+ * "knn_filter_dot": the matrix-core filter of float rows under GBNNS_METRIC_NEG_DOT (angular sets, MIPS; d % 8 == 0, 8 <= d <= 1024, k <= 512,
+ * n > 4 k; heaps) in gbnns_exact_knn / gbnns_exact_knn_tagged / gbnns_index_exact_knn on a float handle, which "knn_filter" and
+ * "knn_filter_wide" leave to the scan -- 0 never (default), 1 from 10^5 rows and 1 000 queries, 2 whenever the shape allows; the value is
+ * clamped to 0 .. 2 (GBNNS_KNN_FILTER_DOT).  Same output, byte for byte: a call with a zero, non-finite, tiny or huge norm (|v|^2 outside
+ * 2^-96 .. 2^96), which the filter's error bound does not cover, is served by the scan.  Half and byte rows, pools (k > 512) and d > 1024 keep
+ * what they do today, whatever the value.  gbnns_debug_knn_plan then names "knn_dot_filter_kernel<2, TAG>".
  * "knn_slab": most queries gbnns_exact_knn's pool path and gbnns_exact_knn_bytes serve at a time -- 0 (default) = as many as keep their
  * key lists within 4 GiB (the slab formula at gbnns_exact_knn_bytes); v > 0 caps a slab at max(128, v & ~127) queries, so that a few
  * hundred queries already run several slabs (tests).  gbnns_debug_knn_slab reports the slab of a shape.
@@ -736,7 +742,8 @@ int gbnns_debug_knn_slab(int bytes, uint64_t n_q, int k, uint32_t* slab);
  * "knn_pool_min_k" knobs, template arguments included, and whether the lists are pools (*pool = 1) or heaps (0).  bytes = 0:
  * gbnns_exact_knn -- "knn_filter_kernel<KSTEPS, QB, TAG>" where the matrix-core filter takes the call (the first rows of its heap path,
  * and a chunk whose lists overflowed, still go through the scan), else "knn_scan_kernel<METRIC, S, QPT, TAG>" (d <= 128) or
- * "knn_scan_wide_kernel<METRIC, R, TAG>"; bytes = 1: gbnns_exact_knn_bytes -- "knn_bytes_sweep_kernel<KSTEPS, QB, TAG>".  tagged != 0:
+ * "knn_scan_wide_kernel<METRIC, R, TAG>" -- or, under their knobs, "knn_wide_filter_kernel<2, TAG>" ("knn_filter_wide": L2 rows of
+ * 128 < d <= 1024) and "knn_dot_filter_kernel<2, TAG>" ("knn_filter_dot": GBNNS_METRIC_NEG_DOT, d <= 1024); bytes = 1: gbnns_exact_knn_bytes -- "knn_bytes_sweep_kernel<KSTEPS, QB, TAG>".  tagged != 0:
  * the _tagged call (gbnns_index_exact_knn with query_tags).  The name comes from the decision and the table the call itself launches
  * from.  GBNNS_ERR_INVALID / GBNNS_ERR_UNSUPPORTED for a shape the call refuses. */
 int gbnns_debug_knn_plan(int bytes, int metric, uint64_t n, uint64_t n_q, uint32_t d, int k, int tagged, char* name, uint32_t name_bytes,
