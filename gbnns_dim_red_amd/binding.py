@@ -444,7 +444,9 @@ def knn_half_plan(n, n_q, d, k, metric=METRIC_L2, stride=0, tagged=False):
     f16 matrix-core sweep in front of heaps / pools) or "scan", and whether the sweep reads a copy of the table (stride, the halves between
     rows -- 0: d --, is no multiple of 8) or the table in place.  Rows of 128 < d <= 1024 are scanned unless
     gbnns_debug_knob("knn_half_wide", 1 or 2) (env GBNNS_KNN_HALF_WIDE; 0 = never, the default, 1 = from 10^5 rows and 1 000 queries, 2 =
-    whenever L2, d % 4 == 0, k <= 512, n > 4 k): then "knn_half_wide_filter_kernel<2, TAG>", path "filter", the same output bytes."""
+    whenever L2, d % 4 == 0, k <= 512, n > 4 k): then "knn_half_wide_filter_kernel<2, TAG>", path "filter", the same output bytes.
+    METRIC_NEG_DOT is scanned unless gbnns_debug_knob("knn_half_dot", 1 or 2) (env GBNNS_KNN_HALF_DOT; the same three values, for
+    d % 8 == 0, 8 <= d <= 1024, k <= 512, n > 4 k): then "knn_half_dot_filter_kernel<2, TAG>", path "filter", the same output bytes."""
     name = C.create_string_buffer(128)
     pool, packed = C.c_int(0), C.c_int(0)
     _check(load_library().gbnns_debug_knn_half_plan(metric, n, n_q, d, stride, k, int(bool(tagged)), name, 128, C.byref(pool), C.byref(packed)))
@@ -625,7 +627,8 @@ def exact_knn(base, queries, k, metric=METRIC_L2, self_offset=-1, want_dist=Fals
     reference's distance arithmetic, ascending (distance, id).  numpy in -> numpy out; torch CUDA in -> torch
     out.  self_offset >= 0: query i is base row i + self_offset (excluded from its own list).
     METRIC_NEG_DOT on float32 rows (d % 8 == 0, d <= 1024, k <= 512) takes the matrix-core filter of knn_dot.hip under
-    gbnns_debug_knob("knn_filter_dot", 1 or 2) (env GBNNS_KNN_FILTER_DOT; default 0: the exact scan) -- the same bytes either way.
+    gbnns_debug_knob("knn_filter_dot", 1 or 2) (env GBNNS_KNN_FILTER_DOT; default 0: the exact scan) -- the same bytes either way; on
+    float16 rows knn_half_dot.hip's under gbnns_debug_knob("knn_half_dot", 1 or 2) (env GBNNS_KNN_HALF_DOT), likewise.
     Both arguments uint8 (numpy or torch): gbnns_exact_knn_bytes -- the same answer as over the widened arrays, bit for
     bit, on the int8 matrix cores and without a float copy (d <= 256, k <= 4096).
     row_tags [n] and query_tags [n_q] (both or neither; numpy uint32, or int32 tensors beside device inputs): gbnns_exact_knn_tagged /
@@ -1109,7 +1112,8 @@ class Index:
         queries of a word scan that word's row list); needs query_tags (None: ValueError).  Opt-in; gather_plan() names its kernel.
         half_scan=True, on a half-base handle (Index(db=<float16>)): gbnns_index_exact_knn_half -- exact_knn(db, queries, ...)'s answer over the
         resident binary16 rows, read in place (float32 queries; knn_half_plan() tells the path; rows wider than 128 dims take the f16
-        matrix-core filter under gbnns_debug_knob("knn_half_wide", 1 or 2), the scan otherwise).  Without it the call on such a handle is
+        matrix-core filter under gbnns_debug_knob("knn_half_wide", 1 or 2), a METRIC_NEG_DOT handle's rows under
+        gbnns_debug_knob("knn_half_dot", 1 or 2), the scan otherwise).  Without it the call on such a handle is
         refused (GbnnsError, code 5), as MODE_PLAIN is without FLAG_HALF_WALK; on a float or byte handle half_scan=True is GbnnsError, code 1."""
         if half_scan:
             if gather:

@@ -169,7 +169,7 @@ struct Lane {
 Knobs knob_defaults();                                    // the process-wide defaults as they stand now
 bool knob_set(Knobs& k, const char* name, int value);     // clamps like the environment does; false = no such handle knob
 extern std::atomic<int> g_knob_knn_chunk, g_knob_knn_pool_min_k, g_knob_knn_filter, g_knob_knn_slab, g_knob_knn_filter_wide, g_knob_knn_half_wide,
-    g_knob_knn_filter_dot;
+    g_knob_knn_filter_dot, g_knob_knn_half_dot;
 
 }  // namespace gbnns_api
 

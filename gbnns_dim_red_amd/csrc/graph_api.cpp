@@ -233,7 +233,7 @@ struct KnnFloatPlan {
     bool filter;  // the matrix-core filter in front of the heaps; neither: the exact scan alone
     uint32_t dp;  // floats of a packed row of the filter: d rounded up to its K step of 16
     bool wide;    // float rows of 128 < d <= 1024: the K-looped matrix-core filter (knn_wide.hip) in front of the heaps; never with pool / filter
-    bool dot;     // float rows under the negative dot, d <= 1024: knn_dot.hip's K-looped filter in front of the heaps; never with the other three
+    bool dot;     // rows under the negative dot, d <= 1024: knn_dot.hip's (binary16 rows: knn_half_dot.hip's) K-looped filter in front of the heaps; never with the other three
 };
 // "knn_filter_wide" = 1 turns the wide filter on by size: from the smallest class tools/knn_wide_timing.py measures -- 10^5 rows, 1 000
 // queries -- where it beat the scan by more than the scan's run-to-run spread in that run (every measured class did, by a factor of 7 to
@@ -271,7 +271,7 @@ KnnFloatPlan knn_float_plan(uint64_t n, uint64_t nq, uint32_t d, int k, int metr
 struct KnnSweepBufs {
     ScopedDevBuf bnorm, qpack, qnorm, rhs, cand, count, flag;
     uint32_t dp, cap;
-    bool dot = false;  // KnnFloatPlan::dot (float rows only): the packed images with the norms turned by dot_operands, swept by knn_dot.hip's kernel
+    bool dot = false;  // KnnFloatPlan::dot: the sweep's operands with the norms turned by dot_operands, swept by knn_dot.hip's / knn_half_dot.hip's kernel
     int prepare_bufs(uint64_t n, uint32_t nq, uint32_t dp_, uint32_t cap_, size_t flag_bytes, hipStream_t s) {
         int rc;
         dp = dp_; cap = cap_;
@@ -345,6 +345,11 @@ constexpr bool kKnnHalfBySize = true;
 // tools/knn_half_wide_timing.py measures -- 10^5 rows, 1 000 queries -- where it beat the half scan by more than that scan's run-to-run
 // spread in the same run (every measured class did: profiles/knn_half_wide_timing.txt).  Smaller calls were not measured and keep the scan.
 constexpr uint64_t kKnnHalfWideMinRows = 100000, kKnnHalfWideMinQueries = 1000;
+// "knn_half_dot" = 1 follows the same rule over tools/knn_half_dot_timing.py's classes: every one of them -- 10^5 x 960 with 10 000 queries up
+// to 10^6 x 960 with 1 000, 10^6 x 96 normalised -- beat the half scan by more than that scan's spread in the same run, by a factor of 19 to
+// 260 (profiles/knn_half_dot_timing.txt), so the siblings' smallest class: the fewest rows and the fewest queries a measured class had.
+// Smaller calls were not measured and keep the scan; the default stays 0.
+constexpr uint64_t kKnnHalfDotMinRows = 100000, kKnnHalfDotMinQueries = 1000;
 struct KnnHalfPlan {
     KnnFloatPlan f;
     bool packed;  // the table's stride is no multiple of 8 halves: swept from a copy at stride f.dp (a caller's array with d % 8 == 4)
@@ -352,14 +357,18 @@ struct KnnHalfPlan {
 KnnHalfPlan knn_half_plan(uint64_t n, uint64_t nq, uint32_t d, int k, int metric, uint32_t stride) {
     KnnHalfPlan pl{};
     pl.f = knn_float_plan(n, nq, d, k, metric);
-    pl.f.dot = false;  // ("knn_filter_dot" is the float rows': binary16 rows under the negative dot keep the half scan)
+    // The negative dot: knn_half_dot.hip's K-looped f16 filter, opt-in by a knob of its own ("knn_filter_dot" is the float rows' and leaves
+    // binary16 rows to the scan, as does "knn_half_wide").  The float dot filter's shapes; heaps only.
+    const int knob_dot = g_knob_knn_half_dot.load(std::memory_order_relaxed);  // 0 = never (default), 1 = by size, 2 = whenever the shape allows
+    pl.f.dot = metric == GBNNS_METRIC_NEG_DOT && d % 8 == 0 && d >= 8 && d <= kKnnWideMaxDim && k <= 512 && n > (uint64_t)4 * k &&
+               (knob_dot == 2 || (knob_dot == 1 && n >= kKnnHalfDotMinRows && nq >= kKnnHalfDotMinQueries));
     // Wider rows: knn_half_wide.hip's K-looped f16 filter, opt-in by a knob of its own ("knn_filter_wide" is the float rows' and leaves
     // binary16 rows to the scan).  The float wide filter's shapes; heaps only.
     const int knob_wide = g_knob_knn_half_wide.load(std::memory_order_relaxed);  // 0 = never (default), 1 = by size, 2 = whenever the shape allows
     pl.f.wide = metric == GBNNS_METRIC_L2 && d % 4 == 0 && d > 128 && d <= kKnnWideMaxDim && k <= 512 && n > (uint64_t)4 * k &&
                 (knob_wide == 2 || (knob_wide == 1 && n >= kKnnHalfWideMinRows && nq >= kKnnHalfWideMinQueries));
     if (!kKnnHalfBySize && g_knob_knn_filter.load(std::memory_order_relaxed) != 2) pl.f.pool = pl.f.filter = false;
-    pl.packed = (pl.f.pool || pl.f.filter || pl.f.wide) && stride % 8 != 0;
+    pl.packed = (pl.f.pool || pl.f.filter || pl.f.wide || pl.f.dot) && stride % 8 != 0;
     return pl;
 }
 
@@ -406,6 +415,11 @@ struct KnnHalfWork : KnnSweepBufs {
         f.bnorm = bnorm.as<float>() + r0; f.rhs = rhs.as<float>(); f.nq = qn; f.dp = dp; f.rows = rows; f.row0 = (uint32_t)r0; f.cap = cap;
         f.cand = cand.as<uint32_t>(); f.count = count.as<uint32_t>(); f.overflow = flag.as<uint32_t>();
         if (qtags) { f.btag = tags + r0; f.qtag = qtags; }
+        if (dot) {  // (bnorm and qnorm turned by dot_operands, rhs = -T_q)
+            f.cq = qnorm.as<float>();
+            HIP_TRY(launch_knn_half_dot_filter(f, s));
+            return GBNNS_OK;
+        }
         HIP_TRY(wide ? launch_knn_half_wide_filter(f, s) : launch_knn_half_sweep(f, s));
         return GBNNS_OK;
     }
@@ -433,7 +447,7 @@ struct KnnRowsOf<uint16_t> {
     static hipError_t scan(const KnnParams& p, int metric, hipStream_t s) { return launch_knn_half_scan(p, metric, s); }
     static hipError_t rescore(const KnnRescoreParams& p, hipStream_t s) { return launch_knn_half_rescore(p, s); }
     static hipError_t wide_rescore(const KnnRescoreParams& p, hipStream_t s) { return launch_knn_half_wide_rescore(p, s); }
-    static hipError_t dot_rescore(const KnnRescoreParams&, hipStream_t) { return hipErrorInvalidValue; }  // (knn_half_plan never sets KnnFloatPlan::dot)
+    static hipError_t dot_rescore(const KnnRescoreParams& p, hipStream_t s) { return launch_knn_half_dot_rescore(p, s); }
     static hipError_t pool_update(const KnnPoolParams& p, hipStream_t s) { return launch_knn_half_pool_update(p, s); }
     static KnnFloatPlan plan(uint64_t n, uint64_t nq, uint32_t d, int k, int metric, uint32_t stride) { return knn_half_plan(n, nq, d, k, metric, stride).f; }
     static uint64_t wide_row_bytes(uint32_t dp, uint32_t stride) { return 2ull * (stride % 8 ? dp : stride); }  // the row itself, in place or in the copy at stride dp
@@ -463,7 +477,7 @@ int knn_rows_call(const KnnCall<B, float>& c) {
     p.heap_stride = ((size_t)nq + 63) & ~(size_t)63;
     const KnnFloatPlan pl = Rows::plan(n, c.n_q, d, k, metric, c.bstride);
     // (wide: the heap-filter schedule below with knn_wide.hip's / knn_half_wide.hip's sweep, the wide rescore and slack; dot: the same schedule
-    // with knn_dot.hip's sweep, rescore, thresholds and norm bounds)
+    // with knn_dot.hip's / knn_half_dot.hip's sweep, knn_dot.hip's rescore, thresholds and norm bounds)
     bool pool_path = pl.pool, filter = pl.filter || pl.wide || pl.dot;
     if (pool_path || filter) {  // a query outside the filter's error bound (half rows: knn_half.hip): the exact scan serves any finite input
         bool covered = true;
@@ -1058,7 +1072,8 @@ int gbnns_debug_knn_half_plan(int metric, uint64_t n, uint64_t n_q, uint32_t d, 
     c.d = d; c.k = k; c.metric = metric;
     if (int rc = knn_refuse(c)) return rc;
     const KnnHalfPlan pl = knn_half_plan(n, n_q, d, k, metric, stride);
-    const char* kernel = pl.f.wide ? knn_half_wide_filter_kernel_name(pl.f.dp, tagged != 0)
+    const char* kernel = pl.f.dot    ? knn_half_dot_filter_kernel_name(pl.f.dp, tagged != 0)
+                         : pl.f.wide ? knn_half_wide_filter_kernel_name(pl.f.dp, tagged != 0)
                                    : (pl.f.pool || pl.f.filter ? knn_half_sweep_kernel_name(pl.f.dp, tagged != 0) : knn_half_scan_kernel_name(metric, d, tagged != 0));
     if (!kernel) return fail(GBNNS_ERR_INTERNAL, "gbnns_debug_knn_half_plan: no kernel instance for the plan");
     std::snprintf(name, name_bytes, "%s", kernel);

@@ -320,6 +320,10 @@ int build_ell(const uint64_t* off, const uint32_t* nbr, uint64_t n, std::vector<
 //                    1024, k <= 512, n > 4 k): 0 = the exact scan (default), 1 = the K-looped matrix-core filter (knn_dot.hip) by size --
 //                    graph_api.cpp has the rule, from profiles/knn_dot_timing.txt --, 2 = wherever the shape allows (GBNNS_KNN_FILTER_DOT; same output,
 //                    byte for byte).  Half and byte rows, pools (k > 512) and d > 1024 keep what they do today, whatever the value
+//   "knn_half_dot"   gbnns_exact_knn_half / gbnns_index_exact_knn_half on binary16 rows under GBNNS_METRIC_NEG_DOT (d % 8 == 0, 8 <= d <= 1024,
+//                    k <= 512, n > 4 k): 0 = the exact scan (default), 1 = the K-looped f16 matrix-core filter (knn_half_dot.hip) by size -- from
+//                    10^5 rows and 1 000 queries: profiles/knn_half_dot_timing.txt --, 2 = wherever the shape allows (GBNNS_KNN_HALF_DOT; same
+//                    output, byte for byte).  "knn_filter_dot" and "knn_half_wide" leave these calls to the scan
 //   "knn_slab"       0 = queries in slabs whose key lists take at most 4 GiB (default); v > 0: at most max(128, v & ~127) queries a slab
 //                    (tests: several slabs at a few hundred queries; gbnns_debug_knn_slab reports the slab of a shape)
 // The classes where the integer first pass measured faster than the float byte walk plus the widening kernel by more than the baseline's
@@ -388,6 +392,7 @@ std::atomic<int> g_knob_knn_slab{0};
 std::atomic<int> g_knob_knn_filter_wide{std::max(0, std::min(2, knob_env("GBNNS_KNN_FILTER_WIDE", 0)))};
 std::atomic<int> g_knob_knn_half_wide{std::max(0, std::min(2, knob_env("GBNNS_KNN_HALF_WIDE", 0)))};
 std::atomic<int> g_knob_knn_filter_dot{std::max(0, std::min(2, knob_env("GBNNS_KNN_FILTER_DOT", 0)))};
+std::atomic<int> g_knob_knn_half_dot{std::max(0, std::min(2, knob_env("GBNNS_KNN_HALF_DOT", 0)))};
 
 // (defined here, beside the defaults, so that gbnns_debug_knob below can reach them under the lock)
 static bool knob_default_set(const char* name, int value) {
@@ -921,6 +926,7 @@ int gbnns_debug_knob(const char* name, int value) {
     else if (!std::strcmp(name, "knn_filter_wide")) g_knob_knn_filter_wide.store(std::max(0, std::min(2, value)), std::memory_order_relaxed);
     else if (!std::strcmp(name, "knn_half_wide")) g_knob_knn_half_wide.store(std::max(0, std::min(2, value)), std::memory_order_relaxed);
     else if (!std::strcmp(name, "knn_filter_dot")) g_knob_knn_filter_dot.store(std::max(0, std::min(2, value)), std::memory_order_relaxed);
+    else if (!std::strcmp(name, "knn_half_dot")) g_knob_knn_half_dot.store(std::max(0, std::min(2, value)), std::memory_order_relaxed);
     else if (!std::strcmp(name, "knn_slab")) g_knob_knn_slab.store(value > 0 ? std::max(128, value & ~127) : 0, std::memory_order_relaxed);
     else return fail(GBNNS_ERR_INVALID, "gbnns_debug_knob: unknown knob '%s'", name);
     return GBNNS_OK;

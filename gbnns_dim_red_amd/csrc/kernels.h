@@ -446,6 +446,8 @@ struct KnnHalfSweepParams {
     uint32_t* overflow;      // [1]
     const uint32_t* btag;    // as KnnFilterParams::btag / qtag, or nullptr: the untagged instances
     const uint32_t* qtag;
+    // the negative-dot filter (knn_half_dot.hip; last): c times an upper bound of |q| -- there bnorm holds upper bounds of |x| and rhs is -T_q
+    const float* cq;         // [nq], or nullptr: the L2 sweeps
 };
 hipError_t launch_knn_half_sweep(const KnnHalfSweepParams& p, hipStream_t s);
 // the half-row instances of launch_knn_scan / launch_knn_rescore / launch_knn_pool_update (p.base_h, p.bstride in halves)
@@ -461,6 +463,13 @@ const char* knn_half_scan_kernel_name(int metric, uint32_t dim, bool tagged);
 hipError_t launch_knn_half_wide_filter(const KnnHalfSweepParams& p, hipStream_t s);
 hipError_t launch_knn_half_wide_rescore(const KnnRescoreParams& p, hipStream_t s);
 const char* knn_half_wide_filter_kernel_name(uint32_t dp, bool tagged);  // host only; "knn_half_wide_filter_kernel<KS, TAG>", nullptr: dp > 1024
+// Binary16 rows under the negative dot (knn_half_dot.hip; "knn_half_dot"; d % 8 == 0, d <= 1024): the same tile over the same operands with
+// knn_dot.hip's epilogue -- a row is kept when fma(cq, ux, q.x) >= -T_q.  KnnHalfSweepParams with bnorm = the rows' bounds and cq
+// (launch_knn_dot_bounds over launch_knn_half_norms' / launch_knn_half_qsplit's squared norms), rhs = -T_q (launch_knn_dot_thresholds); and
+// knn_dot.hip's rescore over binary16 rows (p.k.base_h, p.k.bstride in halves).
+hipError_t launch_knn_half_dot_filter(const KnnHalfSweepParams& p, hipStream_t s);
+hipError_t launch_knn_half_dot_rescore(const KnnRescoreParams& p, hipStream_t s);
+const char* knn_half_dot_filter_kernel_name(uint32_t dp, bool tagged);  // host only; "knn_half_dot_filter_kernel<KS, TAG>", nullptr: dp > 1024
 
 // Exact kNN over uint8 rows on the int8 matrix cores (knn_bytes.hip; d <= 256: every distance is an integer below 2^24, so
 // the int32 result of v_mfma_i32_32x32x32_i8 IS the reference's float distance).  Rows are packed as signed bytes x - 128,

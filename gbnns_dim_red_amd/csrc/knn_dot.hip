@@ -1,6 +1,7 @@
 // knn_dot.hip -- the matrix-core filter of the exact kNN under the negative dot (angular sets, MIPS) for float rows on gfx950 (MI355X):
 // gbnns_exact_knn / gbnns_exact_knn_tagged / gbnns_index_exact_knn with GBNNS_METRIC_NEG_DOT and "knn_filter_dot" set, d % 8 == 0,
-// 8 <= d <= 1024, k <= 512 (heaps), n > 4 k.  Half and byte rows, pools (k > 512) and d > 1024 keep the paths they have.
+// 8 <= d <= 1024, k <= 512 (heaps), n > 4 k.  Byte rows, pools (k > 512) and d > 1024 keep the paths they have; binary16 rows have
+// knn_half_dot.hip's filter under a knob of their own, which shares this file's norm bounds, thresholds and rescore.
 //
 // The distance is Dist = -q.x, so there is no norm to fold in and no |q|^2 + |x|^2 to scale an error with: the error of q.x on the matrix
 // cores (v_mfma_f32_32x32x16_bf16 over knn_pack_kernel's hi / lo images, three products per K step: xh.qh + xl.qh + xh.ql) scales with
@@ -52,6 +53,7 @@
 #include "kernels.h"
 #include "knn_select.h"     // the distance keys, the heap
 #include "knn_scan_dist.h"  // f32x2
+#include "knn_scan_kernels.h"  // knn_rows, knn_widen, knn_row_step: the rescore's binary16 instance
 
 namespace gbnns {
 
@@ -64,6 +66,9 @@ constexpr float kKnnDotBound = 3.0f * kKnnWideMaxDim / 8388608.0f       // accum
 static_assert(kKnnWideSlack >= 1.5f * kKnnDotBound, "kKnnWideSlack no longer covers the dot filter's error bound at its longest row with a factor 1.5");
 constexpr float kDotNormUp = 1.0f + 1.0f / 4096.0f;
 static_assert(kDotNormUp - 1.0f >= 4.0f * (kKnnWideMaxDim / 33554432.0f + 2.0f / 16777216.0f), "kDotNormUp no longer covers the norm's summation and the sqrt");
+// (knn_half_dot.hip's norms are knn_half_norm_kernel's and knn_half_qsplit_kernel's sums, not knn_pack_kernel's: serial too, at most d products
+// and d adds that round, the product's rounding counted as a term of its own -- (d + 1) 2^-25 on the norm; the derivation is written out there)
+static_assert(kDotNormUp - 1.0f >= 4.0f * ((kKnnWideMaxDim + 1) / 33554432.0f + 2.0f / 16777216.0f), "kDotNormUp no longer covers the half-row calls' norm sums and the sqrt");
 constexpr float kDotNormLo = 0x1p-96f, kDotNormHi = 0x1p96f;  // the squared norms the bound's terms hold for
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -273,7 +278,9 @@ __global__ __launch_bounds__(256) void knn_dot_filter_kernel(KnnFilterParams p) 
 // four pairs -- an even 16-byte step adds to sums 0 .. 3, an odd one to 4 .. 7; d % 8 == 0: whole pairs of steps --, the high half added
 // onto the low half, the pairwise adds, the negation.  The keys below the heap's root are offered in list order by lane 0; then the
 // query's new threshold -T.
-template <bool VEC>  // rows and queries 16-byte aligned at strides of whole float4 steps: one load a step
+// B = uint16_t: binary16 rows (p.k.base_h, bstride in halves), widened as they are loaded -- exact --, then the same sums in the same order;
+// VEC there: a table of whole 16-byte chunks, one load of eight halves for a pair of steps.
+template <class B, bool VEC>  // rows and queries 16-byte aligned at strides of whole float4 steps: one load a step
 __global__ __launch_bounds__(64) void knn_dot_rescore_kernel(KnnRescoreParams p) {
     __shared__ float4 qs[kKnnWideMaxDim / 4];
     __shared__ uint64_t keys[64];
@@ -292,14 +299,29 @@ __global__ __launch_bounds__(64) void knn_dot_rescore_kernel(KnnRescoreParams p)
         const uint32_t e = e0 + lane;
         const bool valid = e < cnt;
         const uint32_t row = valid ? p.cand[(size_t)qi * p.cap + e] : p.cand[(size_t)qi * p.cap];  // (an idle lane: the list's first row again)
-        const float* bp = kp.base + (size_t)row * kp.bstride;
+        const B* bp = knn_rows<B>(kp) + (size_t)row * kp.bstride;
         f32x2 cs[4];  // {0,1} {2,3} {4,5} {6,7}
 #pragma unroll
         for (int j = 0; j < 4; ++j) cs[j] = f32x2{0.f, 0.f};
-        auto step = [&](uint32_t c) { return VEC ? reinterpret_cast<const float4*>(bp)[c] : make_float4(bp[4 * c], bp[4 * c + 1], bp[4 * c + 2], bp[4 * c + 3]); };
+        // steps c and c + 1 of the row
+        auto pair = [&](uint32_t c, float4& b0, float4& b1) {
+            if constexpr (!kKnnHalfRows<B>) {
+                b0 = VEC ? reinterpret_cast<const float4*>(bp)[c] : make_float4(bp[4 * c], bp[4 * c + 1], bp[4 * c + 2], bp[4 * c + 3]);
+                b1 = VEC ? reinterpret_cast<const float4*>(bp)[c + 1u] : make_float4(bp[4 * c + 4], bp[4 * c + 5], bp[4 * c + 6], bp[4 * c + 7]);
+            } else if constexpr (VEC) {
+                const uint4 w = reinterpret_cast<const uint4*>(bp)[c >> 1];
+                b0 = make_float4(knn_widen((uint16_t)w.x), knn_widen((uint16_t)(w.x >> 16)), knn_widen((uint16_t)w.y), knn_widen((uint16_t)(w.y >> 16)));
+                b1 = make_float4(knn_widen((uint16_t)w.z), knn_widen((uint16_t)(w.z >> 16)), knn_widen((uint16_t)w.w), knn_widen((uint16_t)(w.w >> 16)));
+            } else {
+                b0 = knn_row_step(bp, c, false);
+                b1 = knn_row_step(bp, c + 1u, false);
+            }
+        };
 #pragma unroll 4
         for (uint32_t c = 0; c < steps; c += 2u) {
-            const float4 b0 = step(c), b1 = step(c + 1u), q0 = qs[c], q1 = qs[c + 1u];
+            float4 b0, b1;
+            pair(c, b0, b1);
+            const float4 q0 = qs[c], q1 = qs[c + 1u];
             cs[0] = cs[0] + f32x2{b0.x, b0.y} * f32x2{q0.x, q0.y};
             cs[1] = cs[1] + f32x2{b0.z, b0.w} * f32x2{q0.z, q0.w};
             cs[2] = cs[2] + f32x2{b1.x, b1.y} * f32x2{q1.x, q1.y};
@@ -380,8 +402,18 @@ hipError_t launch_knn_dot_rescore(const KnnRescoreParams& p, hipStream_t s) {
     if (p.k.nq == 0) return hipSuccess;
     if (!p.k.base || p.k.dim == 0 || p.k.dim > kKnnWideMaxDim || (p.k.dim & 7u)) return hipErrorInvalidValue;
     const bool vec = !(p.k.bstride & 3u) && !(p.k.qstride & 3u) && !(reinterpret_cast<uintptr_t>(p.k.base) & 15u) && !(reinterpret_cast<uintptr_t>(p.k.q) & 15u);
-    if (vec) hipLaunchKernelGGL(knn_dot_rescore_kernel<true>, dim3(p.k.nq), dim3(64), 0, s, p);
-    else hipLaunchKernelGGL(knn_dot_rescore_kernel<false>, dim3(p.k.nq), dim3(64), 0, s, p);
+    if (vec) hipLaunchKernelGGL((knn_dot_rescore_kernel<float, true>), dim3(p.k.nq), dim3(64), 0, s, p);
+    else hipLaunchKernelGGL((knn_dot_rescore_kernel<float, false>), dim3(p.k.nq), dim3(64), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_knn_half_dot_rescore(const KnnRescoreParams& p, hipStream_t s) {
+    if (p.k.nq == 0) return hipSuccess;
+    if (!p.k.base_h || p.k.dim == 0 || p.k.dim > kKnnWideMaxDim || (p.k.dim & 7u)) return hipErrorInvalidValue;
+    // (16-byte chunks of eight halves: a table at a stride of whole chunks; the query's float4 steps as above)
+    const bool vec = !(p.k.bstride & 7u) && !(p.k.qstride & 3u) && !(reinterpret_cast<uintptr_t>(p.k.base_h) & 15u) && !(reinterpret_cast<uintptr_t>(p.k.q) & 15u);
+    if (vec) hipLaunchKernelGGL((knn_dot_rescore_kernel<uint16_t, true>), dim3(p.k.nq), dim3(64), 0, s, p);
+    else hipLaunchKernelGGL((knn_dot_rescore_kernel<uint16_t, false>), dim3(p.k.nq), dim3(64), 0, s, p);
     return hipGetLastError();
 }
 

@@ -568,6 +568,12 @@ int gbnns_profile_enable(gbnns_index* index, int on);
  * clamped to 0 .. 2 (GBNNS_KNN_FILTER_DOT).  Same output, byte for byte: a call with a zero, non-finite, tiny or huge norm (|v|^2 outside
  * 2^-96 .. 2^96), which the filter's error bound does not cover, is served by the scan.  Half and byte rows, pools (k > 512) and d > 1024 keep
  * what they do today, whatever the value.  gbnns_debug_knn_plan then names "knn_dot_filter_kernel<2, TAG>".
+ * "knn_half_dot": the f16 matrix-core filter of binary16 rows under GBNNS_METRIC_NEG_DOT (the same shapes: d % 8 == 0, 8 <= d <= 1024,
+ * k <= 512, n > 4 k; heaps) in gbnns_exact_knn_half / gbnns_index_exact_knn_half, which "knn_filter_dot" and "knn_half_wide" leave to the
+ * scan -- 0 never (default), 1 from 10^5 rows and 1 000 queries, 2 whenever the shape allows; the value is clamped to 0 .. 2
+ * (GBNNS_KNN_HALF_DOT).  Same output, byte for byte: a call with a zero, non-finite, tiny or huge norm (|v|^2 outside 2^-96 .. 2^96) is
+ * served by the scan.  The rows are swept in place, nothing of the table is packed (a table whose stride is no multiple of 8 halves is
+ * swept from a copy); gbnns_debug_knn_half_plan then names "knn_half_dot_filter_kernel<2, TAG>".
  * "knn_slab": most queries gbnns_exact_knn's pool path and gbnns_exact_knn_bytes serve at a time -- 0 (default) = as many as keep their
  * key lists within 4 GiB (the slab formula at gbnns_exact_knn_bytes); v > 0 caps a slab at max(128, v & ~127) queries, so that a few
  * hundred queries already run several slabs (tests).  gbnns_debug_knn_slab reports the slab of a shape.
@@ -774,7 +780,9 @@ int gbnns_index_exact_knn_half(gbnns_index* index, const float* queries, uint64_
 /* Diagnostic, no device needed: gbnns_debug_knn_plan for gbnns_exact_knn_half -- the kernel that sweeps the rows
  * ("knn_half_sweep_kernel<KSTEPS, QB, TAG>" where the matrix-core sweep takes the call, else "knn_scan_kernel<..., half>" /
  * "knn_scan_wide_kernel<..., half>"), whether lists are pools (*pool) and whether the sweep reads a copy of the table (*packed = 1:
- * `stride`, the halves between rows -- 0 = d --, is no multiple of 8) or the table in place (0).  Same knobs as gbnns_debug_knn_plan. */
+ * `stride`, the halves between rows -- 0 = d --, is no multiple of 8) or the table in place (0).  Same knobs as gbnns_debug_knn_plan, and
+ * the half rows' own: "knn_half_wide" ("knn_half_wide_filter_kernel<2, TAG>") and "knn_half_dot" ("knn_half_dot_filter_kernel<2, TAG>":
+ * GBNNS_METRIC_NEG_DOT, d % 8 == 0, d <= 1024). */
 int gbnns_debug_knn_half_plan(int metric, uint64_t n, uint64_t n_q, uint32_t d, uint32_t stride, int k, int tagged, char* name, uint32_t name_bytes,
                               int* pool, int* packed);
 /* Diagnostic, no device needed: the dedupe table of a gbnns_index_tag_census over n_q queries has *cap slots (a power of two >= 2 n_q,
